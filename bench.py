@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: Gaussian -> voxel splat forward on synthetic nuScenes-shaped input.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the splat forward (C ABI ``gf_splat_forward``, automatic point-layout detection, inputs and
@@ -13,6 +13,9 @@ Gaussian set is cut into N contiguous shards (``gaussianformer_amd.sharded.shard
 into a full partial grid and the partial logits are summed with one RCCL all-reduce over xGMI
 (``sharded.sharded_splat_forward``); ``value`` = P / (splat + all-reduce) time, max over ranks.  The reference itself
 only runs data-parallel replicas (train.py:41-43, :86-91).
+
+The headline times LOOPS = 5 loops of exactly K steps each; ``ms_per_step`` is the median loop / K.  ``--dump-outputs DIR``
+writes what the last of those steps computed (``logits`` [N, 18], float32) to DIR/<name>.npy.
 
 Rank 0 prints ONE JSON line.  Next to ``value``, never instead of it:
   N = 1  ``roofline`` (render kernel, hipEvents on the launch stream in a separate loop after the headline's K steps;
@@ -42,6 +45,27 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6290 GB/s measured copy ceiling
 KERNEL_SAMPLES = 16   # bracketed launches of the separate kernel-timing loop (>= 8)
 SETTLE_STEPS = 300     # untimed steps ahead of the W warm-up steps (GPU clock settle, ~15 ms); reported in the JSON line
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0          # --dump-outputs: the rows kept when the outputs exceed the limit
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes every array of ``arrays`` (name -> ndarray) as ``directory/<name>.npy`` in float32.  When together they would
+    exceed ``limit`` bytes, each keeps the same fraction of its rows, drawn with a fixed seed (sorted, the same rows on
+    every run), so two builds are compared on the same voxels.  Returns {name: shape written}."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    header = 4096    # generous bound on one .npy header
+    total = sum(a.nbytes for a in arrays.values())
+    budget = limit - header * len(arrays)
+    os.makedirs(directory, exist_ok=True)
+    shapes = {}
+    for name, a in arrays.items():
+        if total > budget:
+            keep = int(a.shape[0] * budget / total)
+            a = a[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        shapes[name] = a.shape
+    return shapes
 
 
 def headline_metric():
@@ -134,6 +158,9 @@ def main():
     ap.add_argument("--no-extras", "--no-two-stream", dest="no_extras", action="store_true",
                     help="headline measurement only (used for the rocprofv3 kernel trace, whose per-kernel averages would "
                          "otherwise mix the extras' launches into the headline's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; at most 64 MB in all) so that "
+                         "two builds can be compared output for output; the inputs are the same seeded set on every run")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): re-exec under torch.distributed.run, one
@@ -307,12 +334,18 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            wl.step()
+            last = wl.step()
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
         loop_s.append(max_over_ranks(time.perf_counter() - t0))
     elapsed = sorted(loop_s)[LOOPS // 2]
+    # what the last timed step computed, taken before anything below reuses the plan's output buffers
+    if args.dump_outputs and rank == 0:
+        dumped = {"logits": last}
+        if not use_dist and wl.variant == _lib.GF_SPLAT_PROB:
+            dumped.update(bin_logits=wl.plan.bin_logits, density=wl.plan.density, probability=wl.plan.probability)
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in dumped.items()})
 
     # ---- the dominant kernel, timed live in a SEPARATE loop after the headline: hipEvents around every launch of
     # KERNEL_SAMPLES further steps of the same workload, on the stream the kernel is launched on

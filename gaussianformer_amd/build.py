@@ -26,8 +26,8 @@ def _hipcc():
     return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
-def _stale():
-    lib = lib_path()
+def _stale(lib=None):
+    lib = lib or lib_path()
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
@@ -74,9 +74,13 @@ def build(force=False, verbose=False, extra_flags=(), lib_name=None):
 DEV_LIB_NAME = "libgf_hip_dev.so"
 
 
-def build_dev(verbose=False):
+def build_dev(verbose=False, force=True):
     """The development build tools/ use (``-DGF_DEV=1``: the measured-and-not-kept kernels of earlier rounds and the ``dev.*``
-    options of ``gf_set_option``), next to the product library and never in its place.  Select it with ``GF_LIB=<path>``."""
+    options of ``gf_set_option``), next to the product library and never in its place.  Select it with ``GF_LIB=<path>``.
+    ``force=False`` keeps a library that is newer than every source."""
+    dev = os.path.join(CSRC, DEV_LIB_NAME)
+    if not force and not _stale(dev):
+        return dev
     return build(force=True, verbose=verbose, extra_flags=("-DGF_DEV=1",), lib_name=DEV_LIB_NAME)
 
 

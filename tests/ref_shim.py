@@ -17,7 +17,8 @@ packages, in a process where mmengine / mmseg are not installed.
   (tools/make_golden_callers.py).  Only the four kernel entry points are replaced: the host mirrors'
   own code (integer path, covariance packing, autograd routing, dtype coercions) is what runs.
 
-Needs ``/root/reference``; never imported by the product.
+``load_reference()`` needs the reference tree (tools/make_golden_*.py); ``cpu_kernels()`` does not.  Never imported by
+the product.
 """
 import contextlib
 import importlib

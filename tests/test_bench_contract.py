@@ -69,3 +69,29 @@ def test_torch_cpu_baseline_formulation_matches_the_oracle():
     out = splat_forward_torch(t(pi), t(si.pts), t(si.means3D), t(mi), t(si.opacities), t(si.semantics), t(radii), t(cov6),
                               si.H, si.W, si.D, chunk_pairs=1 << 14).numpy()
     assert np.abs(out - ref).max() <= 1e-5 * max(1.0, np.abs(ref).max())
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """``--dump-outputs``: every array as <name>.npy in float32; over the limit, the same seeded rows of each, on every run."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(0)
+    small = {"logits": rng.standard_normal((1000, 18)), "density": rng.standard_normal(1000)}
+    assert bench.dump_outputs(tmp_path / "a", small) == {"logits": (1000, 18), "density": (1000,)}
+    for name, a in small.items():
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    big = {"logits": rng.standard_normal((4000, 18)).astype(np.float32), "density": rng.standard_normal(4000).astype(np.float32)}
+    limit = 1 << 18
+    shapes = bench.dump_outputs(tmp_path / "b", big, limit=limit)
+    assert shapes["logits"][0] == shapes["density"][0] < 4000 and shapes["logits"][1:] == (18,)
+    files = [tmp_path / "b" / f"{n}.npy" for n in big]
+    assert sum(os.path.getsize(f) for f in files) <= limit
+    bench.dump_outputs(tmp_path / "c", big, limit=limit)
+    logits = np.load(tmp_path / "b" / "logits.npy")
+    assert np.array_equal(logits, np.load(tmp_path / "c" / "logits.npy"))
+    rows = [int(np.flatnonzero((big["logits"] == r).all(axis=1))[0]) for r in logits[:50]]
+    assert rows == sorted(rows) and np.array_equal(np.load(tmp_path / "b" / "density.npy")[:50], big["density"][rows])

@@ -49,6 +49,34 @@ def test_bench_single_gpu_line(gpu):
     assert "error" not in b3 and b3["forward_prepared_rows"] is True and 0 < b3["us_per_call"] < b3["exact_fp32_us_per_call"]
 
 
+def test_bench_dump_outputs_is_the_timed_step(gpu, tmp_path):
+    """``--dump-outputs DIR``: K timed steps, and DIR/logits.npy is what the splat forward of the seeded workload computes
+    (a fresh plan over the same inputs, in this process: the forward repeats bit for bit)."""
+    import numpy as np
+    import torch
+    import oracle
+    from gaussianformer_amd import _lib
+    from gaussianformer_amd.local_aggregate import SplatForwardPlan
+    from gaussianformer_amd.synthetic import make_splat_inputs
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-extras",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    b = _last_json(r.stdout)
+    assert b["steps"] == 3 and b["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["logits.npy"]
+    got = np.load(tmp_path / "logits.npy")
+    assert got.dtype == np.float32 and got.shape == (640000, 18) and np.isfinite(got).all()
+    si = make_splat_inputs("nuscenes_gs25600_solid", seed=0)
+    pi, mi, radii, cov6 = oracle.prepare_splat_inputs(si.pts, si.means3D, si.scales, si.cov3D, si.pc_min, si.grid_size,
+                                                      si.scale_multiplier)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
+    plan = SplatForwardPlan(_lib.GF_SPLAT_BASE, up(si.pts), up(pi), up(si.means3D), up(mi), up(si.opacities),
+                            up(si.semantics), up(radii), up(cov6), si.H, si.W, si.D, flags=_lib.GF_PTS_AUTO)
+    want = plan.run().cpu().numpy()
+    assert np.abs(want).max() > 0 and np.array_equal(got, want)
+
+
 def test_bench_two_rank_strong_scaling_path(gpu):
     env = dict(os.environ, GF_BENCH_SHARED_GPU="1", GF_BENCH_CHECK="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",

@@ -6,9 +6,10 @@ tests/golden/caller_*.npz were recorded by tools/make_golden_callers.py: the ref
 registries (tests/ref_shim.py), running on this repository's drop-in packages with the raw kernels served by the
 CPU oracle.  Here:
 
-* CPU (``-m "not gpu"``, build container only -- skipped where /root/reference is absent): the reference classes
-  import against the drop-ins, construct from config-shaped kwargs, expose the reference's state-dict keys, and
-  re-running them reproduces the fixture;
+* CPU (``-m "not gpu"``): the drop-ins construct as the reference classes built them and expose the reference head's
+  state-dict entries (tests/golden/caller_construct.json), the recorded head call re-run on the CPU oracle reproduces the
+  fixture, and the key-point restatement reproduces the reference generator (tests/golden/caller_kps_activations.npz);
+  both extra fixtures were recorded by tools/make_golden_caller_facts.py;
 * GPU: the same module-level calls the reference caller made are replayed through the drop-in modules on the
   HIP kernels (outputs, labels and every gradient against the fixture), and through the fused entry points
   (``GaussianArgs`` + ``forward_from_rotations``, ``deformable_prepare``).
@@ -33,55 +34,53 @@ def _cuda_kwargs(d, prob):
 
 # ------------------------------------------------------------------------------------------------ CPU
 def test_reference_callers_import_and_construct_on_the_dropins():
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip("/root/reference absent (GPU box)")
-    ref = ref_shim.load_reference()
-    import local_aggregate, local_aggregate_prob, local_aggregate_prob_fast
-    d = _load("head_base")
-    head = ref.GaussianHead(apply_loss_type="random_1", num_classes=18, with_empty=True,
-                            empty_args=dict(mean=[0, 0, -1.0], scale=[100, 100, 8.0]), cuda_kwargs=_cuda_kwargs(d, False))
-    assert type(head.aggregator) is local_aggregate.LocalAggregator
-    assert "aggregator.pc_min" in head.state_dict()                 # eval.py:108 loads checkpoints with strict=True
-    head = ref.GaussianHead(apply_loss_type="all", use_localaggprob=True, cuda_kwargs=_cuda_kwargs(d, True))
-    assert type(head.aggregator) is local_aggregate_prob.LocalAggregator
-    head = ref.GaussianHead(apply_loss_type="fixed_0", use_localaggprob=True, use_localaggprob_fast=True,
-                            cuda_kwargs=dict(radii_min=2, **_cuda_kwargs(d, True)))
-    assert type(head.aggregator) is local_aggregate_prob_fast.LocalAggregator and head.aggregator.radii_min == 2
-    from model.encoder.gaussian_encoder.ops import DeformableAggregationFunction
-    assert ref.DAF is DeformableAggregationFunction
-    dfa = ref_shim.build_from_cfg(dict(type="DeformableFeatureAggregation", embed_dims=32, num_groups=4, num_levels=3,
-                                       num_cams=3, use_deformable_func=True, use_camera_embed=True, residual_mode="cat",
-                                       kps_generator=dict(type="SparseGaussian3DKeyPointsGenerator", num_learnable_pts=2,
-                                                          fix_scale=[[0, 0, 0]], pc_range=[-1, -1, -1, 1, 1, 1],
-                                                          scale_range=[0.1, 0.6])), ref_shim.MODELS)
-    assert dfa.use_deformable_func and dfa.num_pts == 3
+    """What the reference's ``GaussianHead.__init__`` and ``DeformableFeatureAggregation`` built on the drop-ins
+    (tests/golden/caller_construct.json): the same drop-in package's ``LocalAggregator`` constructed from the recorded
+    ``cuda_kwargs`` holds exactly the ``aggregator.*`` state-dict entries of the reference head (eval.py:108 loads
+    checkpoints with strict=True), and the op the reference module imports is the product's."""
+    import importlib
+    import json
+    import torch
+    with open(os.path.join(GOLDEN, "caller_construct.json")) as f:
+        facts = json.load(f)
+    assert [h["aggregator_package"] for h in facts["heads"]] == ["local_aggregate", "local_aggregate_prob",
+                                                                 "local_aggregate_prob_fast"]
+    for h in facts["heads"]:
+        agg = importlib.import_module(h["aggregator_package"]).LocalAggregator(**h["aggregator_kwargs"])
+        state = {"aggregator." + k: v for k, v in agg.state_dict().items()}
+        assert set(state) == set(h["state_dict"]), (h["aggregator_package"], sorted(state))
+        for k, want in h["state_dict"].items():
+            assert list(state[k].shape) == want["shape"] and state[k].dtype == torch.float32, k
+            assert state[k].flatten().tolist() == want["values"], k
+        if h["radii_min"] is not None:
+            assert agg.radii_min == h["radii_min"]
+    from gaussianformer_amd.deformable_aggregation import DeformableAggregationFunction
+    dfa = facts["dfa"]
+    assert dfa["use_deformable_func"] and dfa["num_pts"] == 1 + dfa["config"]["kps_generator"]["num_learnable_pts"]
+    assert importlib.import_module(dfa["op_module"]).DeformableAggregationFunction is DeformableAggregationFunction
 
 
 def test_reference_head_reproduces_the_fixture_on_cpu():
+    """The module-level call the reference's GaussianHead made (tests/golden/caller_head_base.npz), through the drop-in
+    LocalAggregator with its raw ops served by the CPU oracle (tests/ref_shim.py ``cpu_kernels``), and the head's epilogue
+    (gaussian_head.py:164-185): ``pred_occ`` and ``final_occ`` as the reference computed them."""
     import torch
     import ref_shim
-    if not ref_shim.available():
-        pytest.skip("/root/reference absent (GPU box)")
-    ref = ref_shim.load_reference()
+    import local_aggregate
+    from oracle import prepare_ref
     d = _load("head_base")
-    saved = getattr(torch.Tensor, "cuda")
-    torch.Tensor.cuda = lambda self, *a, **k: self          # gaussian_head.py:119 on a CPU-only box
-    try:
-        head = ref.GaussianHead(apply_loss_type="random_1", num_classes=18, with_empty=True,
-                                empty_args=dict(mean=[0, 0, -1.0], scale=[100, 100, 8.0]), cuda_kwargs=_cuda_kwargs(d, False))
-        t = lambda k: torch.from_numpy(d[k])
-        rep = [dict(gaussian=ref.GaussianPrediction(means=t("means"), scales=t("scales"), rotations=t("rotations"),
-                                                    opacities=t("opacities"), semantics=t("semantics")))]
-        H, W, D = int(d["grid_H"]), int(d["grid_W"]), int(d["grid_D"])
-        metas = dict(occ_xyz=t("occ_xyz"), occ_label=torch.zeros(1, H, W, D, dtype=torch.long),
-                     occ_cam_mask=torch.ones(1, H, W, D, dtype=torch.bool))
-        with ref_shim.cpu_kernels():
-            out = head(rep, metas)
-    finally:
-        torch.Tensor.cuda = saved
-    assert np.allclose(out["pred_occ"][-1].detach().numpy(), d["pred_occ"], rtol=1e-5, atol=1e-6)
-    assert np.array_equal(out["final_occ"].numpy(), d["final_occ"])
+    agg = local_aggregate.LocalAggregator(**_cuda_kwargs(d, False))
+    t = lambda k: torch.from_numpy(d[k])
+    # the Sigma^-1 the head handed over (gaussian_head.py:108-119) from its inputs, before the appended empty Gaussian
+    g = d["means"].shape[1]
+    assert np.allclose(prepare_ref.covariance_inverse(t("scales"), t("rotations")).numpy(), d["agg_in_cov3D"][:, :g],
+                       rtol=1e-5, atol=1e-6)
+    with ref_shim.cpu_kernels():
+        outs = agg(t("agg_in_pts"), t("agg_in_means3D"), t("agg_in_opacities"), t("agg_in_semantics"), t("agg_in_scales"),
+                   t("agg_in_cov3D"))
+    pred, _, _ = _head_epilogue("base", outs, False)
+    assert np.allclose(pred.detach().numpy(), d["pred_occ"], rtol=1e-5, atol=1e-6)
+    assert np.array_equal(pred.argmax(dim=1).numpy(), d["final_occ"])
 
 
 def test_key_point_restatement_matches_the_reference_caller():
@@ -104,26 +103,19 @@ def test_key_point_restatement_matches_the_reference_caller():
 @pytest.mark.parametrize("xyz_act,scale_act", [("sigmoid", "sigmoid"), ("identity", "sigmoid"), ("sigmoid", "none"),
                                                ("identity", "identity")])
 def test_key_point_restatement_activations_vs_the_reference_generator(xyz_act, scale_act):
-    """The activation switches of the key-point generator (deformable_module.py:27-28, :66-67, :79-80): the
-    reference's own class, executed here, against the restatement that checks gf_key_points on the GPU."""
+    """The activation switches of the key-point generator (deformable_module.py:27-28, :66-67, :79-80): what the
+    reference's own class computed (tests/golden/caller_kps_activations.npz, float64) against the restatement that checks
+    gf_key_points on the GPU."""
     import torch
-    import ref_shim
     from oracle import daf_prepare_ref
-    if not ref_shim.available():
-        pytest.skip("/root/reference absent (GPU box)")
-    ref_shim.load_reference()
-    fix = [[0, 0, 0], [0.45, 0, 0], [-0.45, 0, 0], [0, 0.45, 0], [0, -0.45, 0], [0, 0, 0.45], [0, 0, -0.45]]
-    pc_range, scale_range = [-50.0, -50.0, -5.0, 50.0, 50.0, 3.0], [0.08, 0.64]
-    gen = ref_shim.build_from_cfg(dict(type="SparseGaussian3DKeyPointsGenerator", embed_dims=16, num_learnable_pts=2,
-                                       fix_scale=fix, pc_range=pc_range, scale_range=scale_range,
-                                       xyz_activation=xyz_act, scale_activation=scale_act), ref_shim.MODELS).double()
-    g = torch.Generator().manual_seed(11)
-    anchor = torch.randn(2, 50, 12, generator=g, dtype=torch.float64)
-    feat = torch.randn(2, 50, 16, generator=g, dtype=torch.float64)
-    want = gen(anchor, feat)
-    got = daf_prepare_ref.key_points(anchor, feat, fix, gen.learnable_fc.weight.detach(), gen.learnable_fc.bias.detach(),
-                                     pc_range, scale_range, xyz_activation=xyz_act, scale_activation=scale_act)
-    assert torch.allclose(got, want.detach(), rtol=1e-12, atol=1e-12)
+    d = np.load(os.path.join(GOLDEN, "caller_kps_activations.npz"))
+    key = f"{xyz_act}_{scale_act}"
+    t = lambda k: torch.from_numpy(d[k])
+    got = daf_prepare_ref.key_points(t("anchor"), t("instance_feature"), d["fix_scale"].tolist(), t(f"{key}_weight"),
+                                     t(f"{key}_bias"), d["pc_range"].tolist(), d["scale_range"].tolist(),
+                                     xyz_activation=xyz_act, scale_activation=scale_act)
+    assert got.dtype == torch.float64
+    assert torch.allclose(got, t(f"{key}_key_points"), rtol=1e-12, atol=1e-12)
 
 
 # ------------------------------------------------------------------------------------------------ GPU
