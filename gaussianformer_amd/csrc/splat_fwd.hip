@@ -2208,7 +2208,8 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     auto request_records_at = [&](int qh, int start, int count) {
         const uint32_t id = q_id[(qh + start + (n < count ? n : 0)) & (kQCap - 1)];
         const char *rec = reinterpret_cast<const char *>(a.records + (size_t)id * kRecDwords);
-        const int o3 = (3 + 3 * h) * 16, o4 = (4 + 3 * h) * 16, o5 = (h ? 7 : 5) * 16;
+        // (semantics: lane h = 0 takes pieces 3..5 = channels 0..11, lane h = 1 pieces 5..7 = channels 8..19 -- see S' below)
+        const int o3 = (3 + 2 * h) * 16, o4 = (4 + 2 * h) * 16, o5 = (5 + 2 * h) * 16;
         char *dst = reinterpret_cast<char *>(slot);
         lds_dma16((gptr)(rec), (lptr)(dst));
         lds_dma16((gptr)(rec + 16), (lptr)(dst + 1024));
@@ -2607,16 +2608,13 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         const bool last_group = final_batch && nnext == 0;
                         if (last_group && lane == 0 && !(GF_STATIC2 && first_unit))
                             asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(claimed) : "v"(ctr), "v"(1u) : "memory");
-                            {
+                        {
+                            // S' rows 8 h .. 8 h + 9 of column n: one instruction stream for both half-lanes (10 products and stores
+                            // instead of 12 and 6 in two branches); rows 8 and 9 are written by both, with the same value
                             const float opa = live ? r0.w : 0.f;
-                            const float v[12] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w};
-                            if (h == 0) {
+                            const float v[10] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y};
 #pragma unroll
-                                for (int k = 0; k < 12; ++k) S[k * kSRow + n] = opa * v[k];
-                            } else {
-#pragma unroll
-                                for (int k = 0; k < 6; ++k) S[(12 + k) * kSRow + n] = opa * v[k];
-                            }
+                            for (int k = 0; k < 10; ++k) S[(8 * h + k) * kSRow + n] = opa * v[k];
                         }
                         H8 t1, t2, t3;
                         {
@@ -2640,13 +2638,25 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         }
                         H8 tb;
                         {
+                            // one-hot rows of the box: element j of half-lane 0 = [x0 <= j < x1] (j < 4), [y0 <= j - 4 < y1] (j >= 4),
+                            // of half-lane 1 = [z0 <= j < z1]; 0 inside, -32768 (f16 0xF800) outside or past the group's end.
+                            // Branch-free, two elements per packed 16-bit operation: (j - lo) | (hi - 1 - j) is negative exactly
+                            // outside [lo, hi) (|offsets| < 2 100 fit 16 bits).
                             const uint32_t glo = __float_as_uint(r2.z), ghi = __float_as_uint(r2.w);
                             const int x0 = ux(glo) - Xw, x1 = ux(ghi) - Xw, y0 = uy(glo) - Y0, y1 = uy(ghi) - Y0;
                             const int z0 = uz(glo) - Zw, z1 = uz(ghi) - Zw;
+                            typedef short i16x2 __attribute__((ext_vector_type(2)));
+                            auto dup = [](int v) { return i16x2{(short)v, (short)v}; };
+                            const i16x2 lo_a = dup(h ? z0 : x0), hi_a = dup((h ? z1 : x1) - 1);   // elements 0..3
+                            const i16x2 lo_b = dup(h ? z0 : y0), hi_b = dup((h ? z1 : y1) - 1);   // elements 4..7
+                            const short j4 = h ? 4 : 0;
+                            const i16x2 dead = dup(live ? 0 : -1);
 #pragma unroll
-                            for (int j = 0; j < 8; ++j) {
-                                const bool in = h ? (j >= z0 && j < z1) : (j < 4 ? (j >= x0 && j < x1) : (j - 4 >= y0 && j - 4 < y1));
-                                tb.e[j] = (_Float16)((in && live) ? 0.f : -32768.f);
+                            for (int k = 0; k < 4; ++k) {
+                                const short j0 = (short)(2 * (k & 1)) + (k < 2 ? (short)0 : j4);
+                                const i16x2 jj = i16x2{j0, (short)(j0 + 1)};
+                                const i16x2 out = ((jj - (k < 2 ? lo_a : lo_b)) | ((k < 2 ? hi_a : hi_b) - jj) | dead) >> (short)15;
+                                tb.u[k] = __builtin_bit_cast(uint32_t, out) & 0xF800F800u;
                             }
                         }
                         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -2656,10 +2666,14 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         for (int q = 0; q < 4; ++q) {
                             const float4 v4 = *reinterpret_cast<const float4 *>(S + min(n, kC) * kSRow + 8 * q + 4 * h);
                             const fp16x2 ha = __builtin_amdgcn_cvt_pkrtz(v4.x, v4.y), hb = __builtin_amdgcn_cvt_pkrtz(v4.z, v4.w);
-                            const fp16x2 la = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)ha[0], -1.0f, v4.x), __builtin_fmaf((float)ha[1], -1.0f, v4.y));
-                            const fp16x2 lb = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)hb[0], -1.0f, v4.z), __builtin_fmaf((float)hb[1], -1.0f, v4.w));
+                            // residuals v - hi (exact), the f16 halves read in place (v_fma_mix_f32): no separate conversions
+                            float ra0, ra1, rb0, rb1;
+                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(ra0) : "v"(ha), "v"(v4.x));
+                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ra1) : "v"(ha), "v"(v4.y));
+                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rb0) : "v"(hb), "v"(v4.z));
+                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rb1) : "v"(hb), "v"(v4.w));
                             sh[q >> 1].p[2 * (q & 1)] = ha; sh[q >> 1].p[2 * (q & 1) + 1] = hb;
-                            sl[q >> 1].p[2 * (q & 1)] = la; sl[q >> 1].p[2 * (q & 1) + 1] = lb;
+                            sl[q >> 1].p[2 * (q & 1)] = __builtin_amdgcn_cvt_pkrtz(ra0, ra1); sl[q >> 1].p[2 * (q & 1) + 1] = __builtin_amdgcn_cvt_pkrtz(rb0, rb1);
                         }
                         auto pair = [&](int b0) {
                             f32x16 d0, d1;
