@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GF_LIB selects a development variant built by build.build(lib_name=...) (tools/ only)
 LIB_PATH = os.environ.get("GF_LIB") or os.path.join(_HERE, "csrc", "libgf_hip.so")
 
-GF_ABI_VERSION = 4
+GF_ABI_VERSION = 5
 GF_SPLAT_BASE, GF_SPLAT_PROB = 0, 1
 GF_NUM_CHANNELS = 18
 GF_LABELS_ARGMAX, GF_LABELS_PROB_THRESHOLD, GF_LABELS_PROB_GEOSEM = 0, 1, 2
@@ -70,6 +70,8 @@ SIGNATURES = {
     "gf_gaussian_pack": (_i, [_i] * 7 + [_vp] * 14 + [_vp]),
     "gf_key_points": (_i, [_i] * 4 + [_vp] * 4 + [_f] * 3 + [_i, _vp, _vp]),
     "gf_key_points_backward": (_i, [_i] * 4 + [_vp] * 4 + [_f] * 3 + [_i] + [_vp] * 3 + [_vp]),
+    "gf_fps_workspace_bytes": (_sz, [_i]),
+    "gf_farthest_point_sampling": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gf_profile_enable": (_i, [_i]),
     "gf_profile_stride": (_i, [_i]),
     "gf_profile_read": (_i, [_vp, _i]),

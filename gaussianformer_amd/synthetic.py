@@ -158,3 +158,52 @@ def make_daf_inputs(num_pts=230400, seed=0, B=1, cams=6, C=128, G=4, levels=DAF_
     weights = np.ascontiguousarray(w.reshape(B, num_pts, cams, L, G), dtype=np.float32)
     return dict(mc_ms_feat=feat, spatial_shape=spatial_shape, scale_start_index=start,
                 sampling_location=loc, weights=weights)
+
+
+PC_RANGE = (-50.0, -50.0, -5.0, 50.0, 50.0, 3.0)   # GaussianLifterV2's pc_range (config/prob/nuscenes_gs6400.py)
+
+
+def make_lifter_points(seed=0, cams=6, h=108, w=200, bins=128, image_wh=(1600, 864), pc_range=PC_RANGE):
+    """Candidate anchors shaped like GaussianLifterV2's ``scan`` (model/lifter/gaussian_lifter_v2.py:177-206) with one
+    anchor per pixel: ``cams`` cameras on a ring (nuScenes-like yaws, 64 deg horizontal field of view, 1.5 m up) each
+    cast a ray through every pixel centre of an ``h`` x ``w`` feature map; every ray gets one of ``bins`` depth bins in
+    1-72 m (the lifter's ``depth_bins``, seeded draw), and the points are clamped to ``pc_range``.  Returns
+    ``[cams * h * w, 3]`` float32 (129 600 points at the configs' 108 x 200)."""
+    rng = np.random.default_rng(seed)
+    W_img, H_img = image_wh
+    f = 0.79 * W_img                                   # fx = fy: 64 deg across the width
+    depth_bins = np.linspace(1.0, 72.0, bins, dtype=np.float32)
+    u = (np.arange(w) + 0.5) / w * W_img
+    v = (np.arange(h) + 0.5) / h * H_img
+    uu, vv = np.meshgrid(u, v)                         # [h, w]
+    rays = np.stack([(uu - W_img / 2) / f, (vv - H_img / 2) / f, np.ones_like(uu)], -1).reshape(-1, 3)  # camera frame
+    out = []
+    for k, yaw in enumerate(np.deg2rad([0.0, -55.0, -110.0, 180.0, 110.0, 55.0][:cams] if cams <= 6 else
+                                       np.linspace(0.0, 360.0, cams, endpoint=False))):
+        depth = depth_bins[rng.integers(0, bins, rays.shape[0])][:, None]
+        pc = rays * depth                              # x right, y down, z forward
+        fwd = np.array([np.cos(yaw), np.sin(yaw), 0.0])
+        right = np.array([np.sin(yaw), -np.cos(yaw), 0.0])
+        down = np.array([0.0, 0.0, -1.0])
+        pts = pc[:, :1] * right + pc[:, 1:2] * down + pc[:, 2:3] * fwd + np.array([0.0, 0.0, 1.5])
+        out.append(pts)
+    pts = np.concatenate(out).astype(np.float32)
+    lo, hi = np.array(pc_range[:3], np.float32), np.array(pc_range[3:], np.float32)
+    return np.clip(pts, lo, hi).astype(np.float32)
+
+
+def make_fps_tie_points(kind, n=4096, seed=0):
+    """Point sets whose farthest point sampling is decided by exact distance ties: ``"lattice"`` (an integer lattice,
+    shuffled, ties everywhere), ``"duplicates"`` (``n`` points drawn from n // 8 distinct ones) or ``"identical"``
+    (one point ``n`` times).  float32 ``[n, 3]``."""
+    rng = np.random.default_rng(seed)
+    if kind == "lattice":
+        s = int(np.ceil(n ** (1 / 3)))
+        g = np.stack(np.meshgrid(np.arange(s), np.arange(s), np.arange(s), indexing="ij"), -1).reshape(-1, 3)
+        return rng.permutation(g)[:n].astype(np.float32)
+    if kind == "duplicates":
+        base = rng.uniform(-10.0, 10.0, (max(n // 8, 1), 3)).astype(np.float32)
+        return base[rng.integers(0, base.shape[0], n)]
+    if kind == "identical":
+        return np.tile(np.array([[1.5, -2.25, 0.5]], np.float32), (n, 1))
+    raise ValueError(kind)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 4   /* 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 5   /* 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -111,7 +111,7 @@ int gf_abi_version(void);
 const char *gf_last_error(void);
 
 /* Library options: process-wide integers set by explicit calls -- the library never reads the environment.  Unknown names
- * return GF_EINVAL.  The product library knows four, all 0 by default, each selecting an alternative kernel kept for comparison
+ * return GF_EINVAL.  The product library knows six, all 0 by default, each selecting an alternative kernel kept for comparison
  * (same results within the documented bounds):
  *   "splat.mfma_tile_kernel"  1: the matrix-core forward runs on the tile kernel (one workgroup per tile) even where the wave
  *                                kernel applies (P <= 39 552); the two are bit-identical
@@ -120,6 +120,8 @@ const char *gf_last_error(void);
  *   "subm.tile_gemm"          1: gf_subm_conv_apply's gather-GEMM with one tile of 128 pairs per workgroup also on long segments
  *   "subm.bf16x3"             1: gf_subm_conv_apply_scratch on the three-term bf16 split (six products) instead of two f16 terms (three)
  *                                (>= 32 tiles per offset on average: runs of eight tiles per workgroup otherwise); equal bits
+ *   "fps.exhaustive"          1: gf_farthest_point_sampling updates every bucket on every pick instead of pruning by box bounds;
+ *                                the same bits (the exactness cross-check and the brute-force baseline)
  * A development build (gf_is_development_build() == 1; built by tools/ with -DGF_DEV=1, never shipped as libgf_hip.so) also accepts
  * "dev.*" names for the measured-and-not-kept kernels of earlier rounds. */
 int gf_set_option(const char *name, int value);
@@ -512,6 +514,26 @@ int gf_key_points_backward(int n, int anchor_dim, int F, int K, const float *anc
                            const float *fix_scale, const float *pc_range, float scale_lo, float scale_hi,
                            float learnable_fixed_scale, int identity_activations, const float *grad_key_points,
                            float *grad_anchor, float *grad_learned, void *stream);
+
+/* ---- farthest point sampling -------------------------------------------------------------------------------------
+ * Replaces pointops.farthest_point_sampling(xyz, offset, new_offset) as GaussianLifterV2 calls it with random_sampling=False
+ * (model/lifter/gaussian_lifter_v2.py:233-251; pointops is not part of the reference tree).  Segment s is points
+ * [offset[s-1], offset[s]) and writes picks [new_offset[s-1], new_offset[s]) (offset[-1] = new_offset[-1] = 0):
+ *   the first pick is the segment's first point; every point keeps d = 1e10f; after each pick c, d[p] = min(d[p], dist2(p, c))
+ *   with dist2 = (dx*dx + dy*dy) + dz*dz, dx = p.x - c.x, each operation rounded to fp32 and none fused; the next pick is the
+ *   point with the largest d, ties to the LOWEST index (this op's own rule).  More picks than points repeat by the same rule.
+ * The result is bit-for-bit deterministic.  One workgroup per segment; at most 262 144 points per segment.
+ *   xyz         f32 [n, 3]
+ *   offset_host, new_offset_host   int [b], HOST pointers: validated here (non-decreasing, offset[b-1] == n, no segment over
+ *               the limit, no empty segment with picks) before any HIP call
+ *   offset, new_offset             int [b], DEVICE copies of the same values (the kernel reads them)
+ *   idx         int [new_offset[b-1]]  global indices into xyz
+ *   workspace   gf_fps_workspace_bytes(n) bytes
+ * gf_set_option("fps.exhaustive", 1) updates every point on every pick (no pruning; the same bits). */
+size_t gf_fps_workspace_bytes(int n);
+int gf_farthest_point_sampling(int n, int b, const int *offset_host, const int *new_offset_host, const float *xyz,
+                               const int *offset, const int *new_offset, int *idx, void *workspace, size_t workspace_bytes,
+                               void *stream);
 
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */
