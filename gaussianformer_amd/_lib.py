@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GF_LIB selects a development variant built by build.build(lib_name=...) (tools/ only)
 LIB_PATH = os.environ.get("GF_LIB") or os.path.join(_HERE, "csrc", "libgf_hip.so")
 
-GF_ABI_VERSION = 5
+GF_ABI_VERSION = 6
 GF_SPLAT_BASE, GF_SPLAT_PROB = 0, 1
 GF_NUM_CHANNELS = 18
 GF_LABELS_ARGMAX, GF_LABELS_PROB_THRESHOLD, GF_LABELS_PROB_GEOSEM = 0, 1, 2
@@ -63,6 +63,9 @@ SIGNATURES = {
     "gf_feature_maps_format": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "gf_head_labels": (_i, [ctypes.c_longlong, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "gf_daf_fused_forward": (_i, [_i] * 8 + [_vp] * 11),
+    "gf_daf_fused_forward_masked": (_i, [_i] * 8 + [_vp] * 12),
+    "gf_daf_fused_backward_workspace_bytes": (_sz, [_i] * 6),
+    "gf_daf_fused_backward": (_i, [_i] * 8 + [_vp] * 17 + [_sz, _vp]),
     "gf_daf_prepare": (_i, [_i] * 6 + [_vp] * 7 + [_vp]),
     "gf_daf_prepare_backward": (_i, [_i] * 6 + [_vp] * 8 + [_vp]),
     "gf_gaussian_prepare": (_i, [_i] * 4 + [_vp, _f, _f, _i, _i] + [_vp] * 8 + [_vp]),

@@ -53,12 +53,15 @@ struct DafFusedArgs {
     const int *scale_start;    // [L]
     float *out;                // [B, A, C]
     int B, A, pts, cams, L, G, C, num_feat;
+    const unsigned char *wmask;   // [B, A, cams, L, pts, G] attention-dropout keep-mask (read by the MASK instantiations only)
 };
 
 __device__ __forceinline__ float fu_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
-// one workgroup = 4 waves = 4 consecutive anchors
-template <int CPL>   // channels per lane (8: C = 128 in sixteen lanes)
+// one workgroup = 4 waves = 4 consecutive anchors.  MASK: entries the keep-mask drops leave their group's maximum and sum and
+// weigh 0; a group with no visible, kept entry gives zero channels (all_miss, deformable_module.py:199-214).  The MASK = false
+// instantiation is the code of gf_daf_fused_forward.
+template <int CPL, bool MASK = false>   // channels per lane (8: C = 128 in sixteen lanes)
 __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedArgs a)
 {
     extern __shared__ float s_dyn[];
@@ -142,20 +145,34 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
             if (a.raw) return a.raw[(anchor * a.cams + cam) * LPG + o];
             return s_anc[o] + (s_cam ? s_cam[cam * LPG + o] : a.raw_cam[((size_t)b * a.cams + cam) * LPG + o]);
         };
+        auto kept = [&](int pc, int l, int g) -> bool {
+            if (!MASK) return true;
+            return a.wmask[(anchor * a.cams + (pc & 255)) * LPG + (l * a.pts + (pc >> 8)) * a.G + g] != 0;
+        };
         // (entries of a lane: e = lane + 64 k.  Where L G divides 64 -- the usual 4 x 4 -- the lane keeps its (level, group) and walks
         // the pairs in steps of 64 / (L G): no division per entry)
         const bool stepped = (64 % LG) == 0;
         const int dv = lane / LG, r0 = lane - dv * LG, l0 = r0 / a.G, g0 = r0 - l0 * a.G, vstep = stepped ? 64 / LG : 0;
         auto logit = [&](int e, int k) -> float {
-            if (stepped) return logit_at(s_list[dv + k * vstep], l0, g0);
+            if (stepped) {
+                const int pc = s_list[dv + k * vstep];
+                return kept(pc, l0, g0) ? logit_at(pc, l0, g0) : -INFINITY;
+            }
             const int v = e / LG, r = e - v * LG, l = r / a.G;
-            return logit_at(s_list[v], l, r - l * a.G);
+            return kept(s_list[v], l, r - l * a.G) ? logit_at(s_list[v], l, r - l * a.G) : -INFINITY;
         };
         float m = -INFINITY;
         for (int e = lane, k = 0; e < E; e += 64, ++k) m = fmaxf(m, logit(e, k));
         for (int d = a.G; d < 64; d <<= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
         float s = 0.f;
-        for (int e = lane, k = 0; e < E; e += 64, ++k) s += fu_exp(logit(e, k) - m);
+        for (int e = lane, k = 0; e < E; e += 64, ++k) {
+            if (MASK) {
+                const float x = logit(e, k);   // (a dropped entry is -inf: its group's maximum may be -inf too)
+                s += x == -INFINITY ? 0.f : fu_exp(x - m);
+            } else {
+                s += fu_exp(logit(e, k) - m);
+            }
+        }
         for (int d = a.G; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
         // (lane % G == g holds group g's maximum and sum; a sampling lane needs those of ITS channel group: lane grp < G has them)
         const float inv_mine = s > 0.f ? 1.f / s : 0.f;
@@ -189,7 +206,7 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
                     *reinterpret_cast<float4 *>(v3 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc0) * a.C + jo);
                     *reinterpret_cast<float4 *>(v4 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc1) * a.C + jo);
                 }
-                const float wt = fu_exp(logit_at(pc, l, grp) - mg) * inv;
+                const float wt = kept(pc, l, grp) ? fu_exp(logit_at(pc, l, grp) - mg) * inv : 0.f;
 #if GF_FU_SPLIT
                 const float wt1 = fu_exp(logit_at(pc, l, grp1) - mg1) * inv1;
 #endif
@@ -217,21 +234,327 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
     }
 }
 
-}  // namespace gf
 
-extern "C" int gf_daf_fused_forward(int B, int A, int pts, int cams, int L, int G, int C, int num_feat, const float *key_points,
-                                    const float *projection_mat, const float *image_wh, const float *raw_weights,
-                                    const float *raw_anchor, const float *raw_cam, const float *mc_ms_feat, const int *spatial_shape,
-                                    const int *scale_start_index, float *out, void *stream_)
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Backward of the block (training).  For anchor a and group g, with the kept entries e = (key point, camera, level) -- the camera
+// sees the pair and the keep-mask keeps the entry --, w_e = exp(x_e - m) / sum and S_e[c] the bilinear sample:
+//     gw_e          = sum_{c in g} grad_out[a, c] S_e[c]
+//     d logit_e     = w_e (gw_e - sum_e' w_e' gw_e')                  (0 for entries that are not kept and for all-miss groups)
+//     d mc_ms_feat += coef_tap w_e grad_out[a, c]                     (deformable_aggregation_cuda.cu:80-110)
+//     d (u, v)      = sum_c w_e grad_out[a, c] (W dS/dw_im, H dS/dh_im)  (:92-121), mapped to the key point through the
+//                     projection as gf_daf_prepare_backward does it
+// One wave per anchor, as the forward: the projection, the visible list and the softmax are formed again from the logits (nothing
+// is saved but the inputs), then the lane groups take the visible pairs round-robin and gather the forward's taps.  gw goes to LDS
+// per (visible pair, level, group) -- pts * cams * L * G floats per wave at most, which is why a workgroup holds fewer waves where
+// that does not fit four times --, the (u, v) gradient per pair to LDS, and the feature gradient leaves as float atomics (no
+// [A * pts, C] expanded gradient, no [A * pts, cams, L, G] weights tensor).  The camera part of split logits is a sum over all the
+// anchors of a batch element into cams * L * pts * G addresses: each workgroup (per_wg anchors of ONE batch element) adds its
+// anchors' parts in LDS and writes one partial row; gf_daf_fused_cam_reduce_kernel sums the rows.
+struct DafFusedBwdArgs {
+    DafFusedArgs f;
+    const float *grad_out;       // [B, A, C]
+    float *grad_feat;            // [B, cams * num_feat, C], accumulated, or null
+    float *grad_kp;              // [B, A, pts, 3] or null
+    float *grad_raw;             // [B, A, cams, L, pts, G] or null (full logits)
+    float *grad_raw_anchor;      // [B, A, L, pts, G] or null (split logits)
+    float *part_cam;             // [B * nchunk, cams * L * pts * G] per-workgroup sums of d raw_cam, or null
+    int per_wg, nchunk;          // anchors per workgroup, workgroups per batch element
+};
+
+__host__ __device__ inline int fu_even(int n) { return n + (n & 1); }
+// floats of LDS per wave: uv, d uv (float2 each), anchor logits, visible list, pair -> list slot, key-point partials, gw
+__host__ __device__ inline int fu_bwd_per_wave(int npair, int LG, int LPG) { return fu_even(4 * npair + LPG + 2 * npair + 3 * npair + npair * LG); }
+
+template <int CPL>
+__global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs args)
 {
-    using namespace gf;
-    hipStream_t stream = (hipStream_t)stream_;
+    const DafFusedArgs &a = args.f;
+    extern __shared__ float s_dyn[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int npair = a.pts * a.cams, LG = a.L * a.G, LPG = a.L * a.pts * a.G, J = a.cams * LPG;
+    const int b = blockIdx.x / args.nchunk, chunk = blockIdx.x - b * args.nchunk;
+    const bool split = a.raw == nullptr;
+    const bool need_gw = args.grad_raw || args.grad_raw_anchor || args.part_cam;
+    float *s_cam = s_dyn, *s_gcam = s_dyn + (split ? J : 0);
+    float *s_mine = s_dyn + fu_even((split ? J : 0) + (args.part_cam ? J : 0)) + wave * fu_bwd_per_wave(npair, LG, LPG);
+    float2 *s_uv = reinterpret_cast<float2 *>(s_mine), *s_guv = s_uv + npair;
+    float *s_anc = s_mine + 4 * npair;
+    int *s_list = reinterpret_cast<int *>(s_anc + LPG), *s_pidx = s_list + npair;
+    float *s_part = reinterpret_cast<float *>(s_pidx + npair), *s_gw = s_part + 3 * npair;
+    if (split)
+        for (int i = threadIdx.x; i < J; i += blockDim.x) s_cam[i] = a.raw_cam[(size_t)b * J + i];
+    if (args.part_cam)
+        for (int i = threadIdx.x; i < J; i += blockDim.x) s_gcam[i] = 0.f;
+    __syncthreads();
+    const int CV = a.C / CPL;
+    const int sg = lane / CV, cv = lane - sg * CV, nsg = 64 / CV;
+    const int c0 = cv * CPL, grp = c0 / (a.C / a.G), lanes_per_group = (a.C / a.G) / CPL;
+    const int a_end = min(a.A, (chunk + 1) * args.per_wg);
+    for (int ia = chunk * args.per_wg + wave; ia < a_end; ia += nw) {
+        const long long anchor = (long long)b * a.A + ia;
+        // ---- 1. projection and the list of visible pairs (as the forward)
+        if (split)
+            for (int i = lane; i < LPG; i += 64) s_anc[i] = a.raw_anchor[anchor * LPG + i];
+        int nvis = 0;
+        for (int q0 = 0; q0 < npair; q0 += 64) {
+            const int q = q0 + lane;
+            bool vis = false;
+            if (q < npair) {
+                const int pt = q / a.cams, cam = q - pt * a.cams;
+                const float *kp = a.key_points + (anchor * a.pts + pt) * 3;
+                const float *M = a.proj + ((size_t)b * a.cams + cam) * 16;
+                const float X = kp[0], Y = kp[1], Z = kp[2];
+                const float px = M[0] * X + M[1] * Y + M[2] * Z + M[3];
+                const float py = M[4] * X + M[5] * Y + M[6] * Z + M[7];
+                const float pz = M[8] * X + M[9] * Y + M[10] * Z + M[11];
+                const float zc = fmaxf(pz, 1e-5f);
+                float u = px / zc, v = py / zc;
+                if (a.image_wh) {
+                    u /= a.image_wh[((size_t)b * a.cams + cam) * 2];
+                    v /= a.image_wh[((size_t)b * a.cams + cam) * 2 + 1];
+                }
+                vis = (pz > 1e-5f) && (u > 0) && (u < 1) && (v > 0) && (v < 1);
+                s_uv[q] = make_float2(u, v);
+                s_guv[q] = make_float2(0.f, 0.f);
+            }
+            const unsigned long long bal = __builtin_amdgcn_ballot_w64(vis);
+            const int pos = nvis + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+            if (q < npair) s_pidx[q] = vis ? pos : -1;
+            if (vis) s_list[pos] = ((q / a.cams) << 8) | (q % a.cams);
+            nvis += __builtin_popcountll(bal);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        auto logit_at = [&](int pc, int l, int g) -> float {
+            const int pt = pc >> 8, cam = pc & 255;
+            const int o = (l * a.pts + pt) * a.G + g;
+            if (!split) return a.raw[(anchor * a.cams + cam) * LPG + o];
+            return s_anc[o] + s_cam[cam * LPG + o];
+        };
+        auto kept = [&](int pc, int l, int g) -> bool {
+            return !a.wmask || a.wmask[(anchor * a.cams + (pc & 255)) * LPG + (l * a.pts + (pc >> 8)) * a.G + g] != 0;
+        };
+        // ---- 2. the softmax's maximum and sum per group (entry e = (v * L + l) * G + g; lane % G == g)
+        const int E = nvis * LG;
+        auto entry = [&](int e, int &pc, int &l) {
+            const int v = e / LG, r = e - v * LG;
+            pc = s_list[v];
+            l = r / a.G;
+        };
+        const int gl = lane % a.G;
+        float m = -INFINITY;
+        for (int e = lane; e < E; e += 64) {
+            int pc, l;
+            entry(e, pc, l);
+            if (kept(pc, l, gl)) m = fmaxf(m, logit_at(pc, l, gl));
+        }
+        for (int d = a.G; d < 64; d <<= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+        float s = 0.f;
+        for (int e = lane; e < E; e += 64) {
+            int pc, l;
+            entry(e, pc, l);
+            if (kept(pc, l, gl)) s += fu_exp(logit_at(pc, l, gl) - m);
+        }
+        for (int d = a.G; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
+        const float inv_mine = s > 0.f ? 1.f / s : 0.f;
+        const float inv = __shfl(inv_mine, grp, 64), mg = __shfl(m, grp, 64);
+        // ---- 3. the forward's taps again: gw, d (u, v), d mc_ms_feat
+        float go[CPL];
+#pragma unroll
+        for (int j = 0; j < CPL; j += 4)
+            *reinterpret_cast<float4 *>(go + j) = *reinterpret_cast<const float4 *>(args.grad_out + anchor * a.C + c0 + j);
+        for (int v = sg; v < nvis; v += nsg) {
+            const int pc = s_list[v], pt = pc >> 8, cam = pc & 255;
+            const float2 uv = s_uv[pt * a.cams + cam];
+            const size_t row0 = ((size_t)b * a.cams + cam) * a.num_feat;
+            const float *fcam = a.feat + row0 * a.C + c0;
+            float gu = 0.f, gv = 0.f;
+            for (int l = 0; l < a.L; ++l) {
+                const int h = a.spatial_shape[2 * l], w = a.spatial_shape[2 * l + 1];
+                const float h_im = uv.y * h - 0.5f, w_im = uv.x * w - 0.5f;
+                const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
+                const float lh = h_im - h_low, lw = w_im - w_low, hh = 1 - lh, hw = 1 - lw;
+                const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
+                const bool ok1 = h_low >= 0 && w_low >= 0, ok2 = h_low >= 0 && w_low + 1 <= w - 1;
+                const bool ok3 = h_low + 1 <= h - 1 && w_low >= 0, ok4 = h_low + 1 <= h - 1 && w_low + 1 <= w - 1;
+                const int hc0 = max(h_low, 0), hc1 = min(h_low + 1, h - 1), wc0 = max(w_low, 0), wc1 = min(w_low + 1, w - 1);
+                const size_t p1 = (size_t)(hc0 * w + wc0) * a.C, p2 = (size_t)(hc0 * w + wc1) * a.C;
+                const size_t p3 = (size_t)(hc1 * w + wc0) * a.C, p4 = (size_t)(hc1 * w + wc1) * a.C;
+                const float *base = fcam + (size_t)a.scale_start[l] * a.C;
+                float v1[CPL], v2[CPL], v3[CPL], v4[CPL];
+#pragma unroll
+                for (int j = 0; j < CPL; j += 4) {
+                    *reinterpret_cast<float4 *>(v1 + j) = *reinterpret_cast<const float4 *>(base + p1 + j);
+                    *reinterpret_cast<float4 *>(v2 + j) = *reinterpret_cast<const float4 *>(base + p2 + j);
+                    *reinterpret_cast<float4 *>(v3 + j) = *reinterpret_cast<const float4 *>(base + p3 + j);
+                    *reinterpret_cast<float4 *>(v4 + j) = *reinterpret_cast<const float4 *>(base + p4 + j);
+                }
+                const float wt = kept(pc, l, grp) ? fu_exp(logit_at(pc, l, grp) - mg) * inv : 0.f;
+                float sv = 0.f, sw = 0.f, sh = 0.f;
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) {
+                    const float x1 = ok1 ? v1[j] : 0.f, x2 = ok2 ? v2[j] : 0.f, x3 = ok3 ? v3[j] : 0.f, x4 = ok4 ? v4[j] : 0.f;
+                    sv += go[j] * (w1 * x1 + w2 * x2 + w3 * x3 + w4 * x4);
+                    sw += go[j] * (hh * (x2 - x1) + lh * (x4 - x3));   // grad_w_weight, :84-110
+                    sh += go[j] * (hw * (x3 - x1) + lw * (x4 - x2));   // grad_h_weight
+                }
+                if (need_gw) {
+                    for (int d = 1; d < lanes_per_group; d <<= 1) sv += __shfl_xor(sv, d, 64);
+                    if (cv % lanes_per_group == 0) s_gw[v * LG + l * a.G + grp] = sv;
+                }
+                gu += (float)w * wt * sw;
+                gv += (float)h * wt * sh;
+                if (args.grad_feat && wt != 0.f) {
+                    float *gbase = args.grad_feat + (row0 + a.scale_start[l]) * a.C + c0;
+                    const bool ok[4] = {ok1, ok2, ok3, ok4};
+                    const size_t po[4] = {p1, p2, p3, p4};
+                    const float cw[4] = {w1 * wt, w2 * wt, w3 * wt, w4 * wt};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (ok[k])
+#pragma unroll
+                            for (int j = 0; j < CPL; ++j) unsafeAtomicAdd(gbase + po[k] + j, cw[k] * go[j]);
+                }
+            }
+            if (args.grad_kp) {
+                for (int d = 1; d < CV; d <<= 1) {
+                    gu += __shfl_xor(gu, d, 64);
+                    gv += __shfl_xor(gv, d, 64);
+                }
+                if (cv == 0) s_guv[pt * a.cams + cam] = make_float2(gu, gv);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        // ---- 4. softmax backward: d logit_e = w_e (gw_e - sum_e' w_e' gw_e'), written in the logits' layouts
+        if (need_gw) {
+            float dot = 0.f;
+            for (int e = lane; e < E; e += 64) {
+                int pc, l;
+                entry(e, pc, l);
+                if (kept(pc, l, gl)) dot += fu_exp(logit_at(pc, l, gl) - m) * inv_mine * s_gw[e];
+            }
+            for (int d = a.G; d < 64; d <<= 1) dot += __shfl_xor(dot, d, 64);
+            auto dlogit = [&](int pt, int cam, int l) -> float {   // group gl
+                const int v = s_pidx[pt * a.cams + cam], pc = (pt << 8) | cam;
+                if (v < 0 || !kept(pc, l, gl)) return 0.f;
+                return fu_exp(logit_at(pc, l, gl) - m) * inv_mine * (s_gw[v * LG + l * a.G + gl] - dot);
+            };
+            if (args.grad_raw)   // [cams][L][pts][G], every entry written
+                for (int i = lane; i < J; i += 64) {
+                    int r = i / a.G;
+                    const int pt = r % a.pts;
+                    r /= a.pts;
+                    const int l = r % a.L, cam = r / a.L;
+                    args.grad_raw[anchor * J + i] = dlogit(pt, cam, l);
+                }
+            if (split && (args.grad_raw_anchor || args.part_cam))   // [L][pts][G]: the anchor part sums the cameras
+                for (int i = lane; i < LPG; i += 64) {
+                    const int r = i / a.G, pt = r % a.pts, l = r / a.pts;
+                    float sum = 0.f;
+                    for (int cam = 0; cam < a.cams; ++cam) {
+                        const float x = dlogit(pt, cam, l);
+                        sum += x;
+                        if (args.part_cam && x != 0.f) atomicAdd(s_gcam + cam * LPG + i, x);
+                    }
+                    if (args.grad_raw_anchor) args.grad_raw_anchor[anchor * LPG + i] = sum;
+                }
+        }
+        // ---- 5. projection backward (gf_daf_prepare_backward's arithmetic): u = x / max(z, 1e-5) / w_img
+        if (args.grad_kp) {
+            for (int q = lane; q < npair; q += 64) {
+                const int pt = q / a.cams, cam = q - pt * a.cams;
+                const float *kp = a.key_points + (anchor * a.pts + pt) * 3;
+                const float *M = a.proj + ((size_t)b * a.cams + cam) * 16;
+                const float X = kp[0], Y = kp[1], Z = kp[2];
+                const float px = M[0] * X + M[1] * Y + M[2] * Z + M[3];
+                const float py = M[4] * X + M[5] * Y + M[6] * Z + M[7];
+                const float pz = M[8] * X + M[9] * Y + M[10] * Z + M[11];
+                const float zc = fmaxf(pz, 1e-5f), iz = 1.f / zc;
+                const float2 g2 = s_guv[q];
+                float gu = g2.x, gv = g2.y;
+                if (a.image_wh) {
+                    gu /= a.image_wh[((size_t)b * a.cams + cam) * 2];
+                    gv /= a.image_wh[((size_t)b * a.cams + cam) * 2 + 1];
+                }
+                const float cz = pz > 1e-5f ? -(gu * px + gv * py) * iz * iz : 0.f;
+                const float cx = gu * iz, cy = gv * iz;
+                s_part[3 * q] = cx * M[0] + cy * M[4] + cz * M[8];
+                s_part[3 * q + 1] = cx * M[1] + cy * M[5] + cz * M[9];
+                s_part[3 * q + 2] = cx * M[2] + cy * M[6] + cz * M[10];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            for (int pt = lane; pt < a.pts; pt += 64) {
+                float gx = 0.f, gy = 0.f, gz = 0.f;
+                for (int cam = 0; cam < a.cams; ++cam) {
+                    const float *c = s_part + 3 * (pt * a.cams + cam);
+                    gx += c[0]; gy += c[1]; gz += c[2];
+                }
+                float *o = args.grad_kp + (anchor * a.pts + pt) * 3;
+                o[0] = gx; o[1] = gy; o[2] = gz;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();   // the wave's LDS is reused by its next anchor
+    }
+    if (args.part_cam) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < J; i += blockDim.x) args.part_cam[(size_t)blockIdx.x * J + i] = s_gcam[i];
+    }
+}
+
+// d raw_cam[b, i] = sum over the batch element's workgroup rows.  64 entries x 4 row subsets per workgroup, gridDim.z slices of the
+// rows; the slices meet with one float atomic each (out is zeroed first).
+__global__ __launch_bounds__(256) void gf_daf_fused_cam_reduce_kernel(const float *part, float *out, int J, int nchunk)
+{
+    __shared__ float s_red[4][64];
+    const int t = threadIdx.x & 63, sub = threadIdx.x >> 6, b = blockIdx.y;
+    const int i = blockIdx.x * 64 + t;
+    float s = 0.f;
+    if (i < J)
+        for (int c = blockIdx.z * 4 + sub; c < nchunk; c += 4 * gridDim.z) s += part[((size_t)b * nchunk + c) * J + i];
+    s_red[sub][t] = s;
+    __syncthreads();
+    if (sub == 0 && i < J) unsafeAtomicAdd(out + (size_t)b * J + i, s_red[0][t] + s_red[1][t] + s_red[2][t] + s_red[3][t]);
+}
+
+// the launch geometry of the backward: waves per workgroup (4, or fewer where four waves' LDS does not fit), anchors per workgroup
+struct FuBwdGeom {
+    int nw, per_wg, nchunk;
+    size_t lds;
+};
+static FuBwdGeom fu_bwd_geom(int A, int pts, int cams, int L, int G, bool split, bool cam_part)
+{
+    const int npair = pts * cams, LG = L * G, LPG = L * pts * G, J = cams * LPG;
+    FuBwdGeom g;
+    const size_t shared = (size_t)fu_even((split ? J : 0) + (cam_part ? J : 0)), per = (size_t)fu_bwd_per_wave(npair, LG, LPG);
+    g.nw = 4;
+    while (g.nw > 1 && sizeof(float) * (shared + g.nw * per) > 160 * 1024) g.nw >>= 1;
+    g.lds = sizeof(float) * (shared + g.nw * per);
+    g.per_wg = 4 * g.nw;   // (each wave takes four anchors: a quarter of the partial rows of one anchor per wave)
+    g.nchunk = (A + g.per_wg - 1) / g.per_wg;
+    return g;
+}
+
+static int fu_check(int B, int A, int pts, int cams, int L, int G, int C, int num_feat)
+{
     GF_CHECK_ARG(B >= 0 && A >= 0 && pts > 0 && cams > 0 && L > 0 && G > 0 && C > 0 && num_feat > 0, "bad size");
     GF_CHECK_ARG((G & (G - 1)) == 0 && G <= 64, "G must be a power of two <= 64");
     GF_CHECK_ARG(pts * cams <= kFuMaxPairs, "pts * cams too large");
     GF_CHECK_ARG(L * G <= kFuMaxLG, "L * G too large");
     GF_CHECK_ARG(C % 8 == 0 && C % G == 0 && (C / G) % 8 == 0 && 64 % (C / 8) == 0 && C / 8 >= G,
                  "channels: C a multiple of 8 G with C / 8 lanes dividing a wave");
+    return GF_OK;
+}
+
+static int fu_forward(int B, int A, int pts, int cams, int L, int G, int C, int num_feat, const float *key_points,
+                      const float *projection_mat, const float *image_wh, const float *raw_weights, const float *raw_anchor,
+                      const float *raw_cam, const unsigned char *weight_mask, const float *mc_ms_feat, const int *spatial_shape,
+                      const int *scale_start_index, float *out, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = fu_check(B, A, pts, cams, L, G, C, num_feat)) return rc;
     if ((long long)B * A == 0) return GF_OK;
     GF_CHECK_ARG(key_points && projection_mat && mc_ms_feat && spatial_shape && scale_start_index && out, "null pointer");
     GF_CHECK_ARG((raw_weights != nullptr) != (raw_anchor != nullptr && raw_cam != nullptr) && ((raw_anchor != nullptr) == (raw_cam != nullptr)),
@@ -240,14 +563,97 @@ extern "C" int gf_daf_fused_forward(int B, int A, int pts, int cams, int L, int 
     DafFusedArgs a;
     a.key_points = key_points; a.proj = projection_mat; a.image_wh = image_wh; a.raw = raw_weights; a.raw_anchor = raw_anchor;
     a.raw_cam = raw_cam; a.feat = mc_ms_feat; a.spatial_shape = spatial_shape; a.scale_start = scale_start_index; a.out = out;
-    a.B = B; a.A = A; a.pts = pts; a.cams = cams; a.L = L; a.G = G; a.C = C; a.num_feat = num_feat;
+    a.B = B; a.A = A; a.pts = pts; a.cams = cams; a.L = L; a.G = G; a.C = C; a.num_feat = num_feat; a.wmask = weight_mask;
     const int npair = pts * cams, LPG = L * pts * G;
     const size_t lds = sizeof(float) * ((raw_weights ? 0 : (size_t)cams * LPG) + 4 * ((size_t)LPG + (LPG & 1) + 3 * npair + (npair & 1)));
     GF_CHECK_ARG(lds <= 160 * 1024, "shape needs more LDS than a CU has");
     const long long nanchor = (long long)B * A;
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gf_daf_fused_kernel<GF_FU_CPL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(gf_daf_fused_kernel<GF_FU_CPL>, dim3((unsigned)((nanchor + 3) / 4)), dim3(256), lds, stream, a);
+    const void *kernel = weight_mask ? reinterpret_cast<const void *>(gf_daf_fused_kernel<GF_FU_CPL, true>)
+                                     : reinterpret_cast<const void *>(gf_daf_fused_kernel<GF_FU_CPL, false>);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (weight_mask)
+        hipLaunchKernelGGL((gf_daf_fused_kernel<GF_FU_CPL, true>), dim3((unsigned)((nanchor + 3) / 4)), dim3(256), lds, stream, a);
+    else
+        hipLaunchKernelGGL((gf_daf_fused_kernel<GF_FU_CPL, false>), dim3((unsigned)((nanchor + 3) / 4)), dim3(256), lds, stream, a);
     GF_CHECK_LAUNCH();
+    return GF_OK;
+}
+
+}  // namespace gf
+
+extern "C" int gf_daf_fused_forward(int B, int A, int pts, int cams, int L, int G, int C, int num_feat, const float *key_points,
+                                    const float *projection_mat, const float *image_wh, const float *raw_weights,
+                                    const float *raw_anchor, const float *raw_cam, const float *mc_ms_feat, const int *spatial_shape,
+                                    const int *scale_start_index, float *out, void *stream_)
+{
+    return gf::fu_forward(B, A, pts, cams, L, G, C, num_feat, key_points, projection_mat, image_wh, raw_weights, raw_anchor, raw_cam,
+                          nullptr, mc_ms_feat, spatial_shape, scale_start_index, out, stream_);
+}
+
+extern "C" int gf_daf_fused_forward_masked(int B, int A, int pts, int cams, int L, int G, int C, int num_feat, const float *key_points,
+                                           const float *projection_mat, const float *image_wh, const float *raw_weights,
+                                           const float *raw_anchor, const float *raw_cam, const unsigned char *weight_mask,
+                                           const float *mc_ms_feat, const int *spatial_shape, const int *scale_start_index, float *out,
+                                           void *stream_)
+{
+    return gf::fu_forward(B, A, pts, cams, L, G, C, num_feat, key_points, projection_mat, image_wh, raw_weights, raw_anchor, raw_cam,
+                          weight_mask, mc_ms_feat, spatial_shape, scale_start_index, out, stream_);
+}
+
+extern "C" size_t gf_daf_fused_backward_workspace_bytes(int B, int A, int pts, int cams, int L, int G)
+{
+    using namespace gf;
+    if (B < 0 || A < 0 || pts <= 0 || cams <= 0 || L <= 0 || G <= 0 || pts * cams > kFuMaxPairs || L * G > kFuMaxLG) return 0;
+    const FuBwdGeom g = fu_bwd_geom(A, pts, cams, L, G, true, true);
+    return sizeof(float) * (size_t)B * g.nchunk * cams * L * pts * G;
+}
+
+extern "C" int gf_daf_fused_backward(int B, int A, int pts, int cams, int L, int G, int C, int num_feat, const float *key_points,
+                                     const float *projection_mat, const float *image_wh, const float *raw_weights,
+                                     const float *raw_anchor, const float *raw_cam, const unsigned char *weight_mask,
+                                     const float *mc_ms_feat, const int *spatial_shape, const int *scale_start_index,
+                                     const float *grad_out, float *grad_mc_ms_feat, float *grad_key_points, float *grad_raw_weights,
+                                     float *grad_raw_anchor, float *grad_raw_cam, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    using namespace gf;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = fu_check(B, A, pts, cams, L, G, C, num_feat)) return rc;
+    GF_CHECK_ARG((raw_weights != nullptr) != (raw_anchor != nullptr && raw_cam != nullptr) && ((raw_anchor != nullptr) == (raw_cam != nullptr)),
+                 "give raw_weights, or raw_anchor and raw_cam");
+    const bool split = raw_weights == nullptr;
+    GF_CHECK_ARG(!grad_raw_weights || !split, "grad_raw_weights needs raw_weights");
+    GF_CHECK_ARG(!(grad_raw_anchor || grad_raw_cam) || split, "grad_raw_anchor / grad_raw_cam need raw_anchor and raw_cam");
+    if ((long long)B * A == 0) return GF_OK;
+    GF_CHECK_ARG(key_points && projection_mat && mc_ms_feat && spatial_shape && scale_start_index && grad_out, "null pointer");
+    GF_CHECK_ARG((((uintptr_t)mc_ms_feat | (uintptr_t)grad_out) & 15) == 0, "features and grad_out must be 16-byte aligned");
+    const FuBwdGeom g = fu_bwd_geom(A, pts, cams, L, G, split, grad_raw_cam != nullptr);
+    GF_CHECK_ARG(g.lds <= 160 * 1024, "shape needs more LDS than a CU has");
+    const size_t J = (size_t)cams * L * pts * G;
+    GF_CHECK_ARG(!grad_raw_cam || (workspace && workspace_bytes >= sizeof(float) * (size_t)B * g.nchunk * J),
+                 "workspace too small: see gf_daf_fused_backward_workspace_bytes");
+    GF_CHECK_ARG((long long)B * g.nchunk < (1ll << 31), "problem too large");
+    if (!(grad_mc_ms_feat || grad_key_points || grad_raw_weights || grad_raw_anchor || grad_raw_cam)) return GF_OK;
+    DafFusedBwdArgs a{};
+    DafFusedArgs &f = a.f;
+    f.key_points = key_points; f.proj = projection_mat; f.image_wh = image_wh; f.raw = raw_weights; f.raw_anchor = raw_anchor;
+    f.raw_cam = raw_cam; f.feat = mc_ms_feat; f.spatial_shape = spatial_shape; f.scale_start = scale_start_index; f.out = nullptr;
+    f.B = B; f.A = A; f.pts = pts; f.cams = cams; f.L = L; f.G = G; f.C = C; f.num_feat = num_feat; f.wmask = weight_mask;
+    a.grad_out = grad_out; a.grad_feat = grad_mc_ms_feat; a.grad_kp = grad_key_points; a.grad_raw = grad_raw_weights;
+    a.grad_raw_anchor = grad_raw_anchor; a.part_cam = grad_raw_cam ? static_cast<float *>(workspace) : nullptr;
+    a.per_wg = g.per_wg; a.nchunk = g.nchunk;
+    if (g.lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gf_daf_fused_bwd_kernel<GF_FU_CPL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
+    hipLaunchKernelGGL(gf_daf_fused_bwd_kernel<GF_FU_CPL>, dim3((unsigned)(B * g.nchunk)), dim3(64 * g.nw), g.lds, stream, a);
+    GF_CHECK_LAUNCH();
+    if (grad_raw_cam) {
+        if (hipMemsetAsync(grad_raw_cam, 0, sizeof(float) * B * J, stream) != hipSuccess) {
+            set_error("%s: hipMemsetAsync failed", __func__);
+            return GF_ELAUNCH;
+        }
+        const int slices = std::min(32, (g.nchunk + 3) / 4);
+        hipLaunchKernelGGL(gf_daf_fused_cam_reduce_kernel, dim3((unsigned)((J + 63) / 64), (unsigned)B, (unsigned)slices), dim3(256), 0,
+                           stream, a.part_cam, grad_raw_cam, (int)J, g.nchunk);
+        GF_CHECK_LAUNCH();
+    }
     return GF_OK;
 }

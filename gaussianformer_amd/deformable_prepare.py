@@ -102,3 +102,91 @@ def deformable_fused_forward(key_points, projection_mat, image_wh, mc_ms_feat, s
                                       _lib.current_stream(kp.device))
     _lib.check(rc, "gf_daf_fused_forward")
     return out
+
+
+def _mask_u8(weight_mask):
+    """The keep-mask as bytes without a copy where it already is one byte per entry (bool / uint8)."""
+    if weight_mask is None:
+        return None
+    m = weight_mask.detach()
+    return (m if m.dtype in (torch.bool, torch.uint8) else m.to(torch.uint8)).contiguous()
+
+
+class DeformableFusedFunction(Function):
+    """``features [bs, A, C] = apply(key_points, projection_mat, image_wh, mc_ms_feat, spatial_shape, scale_start_index,
+    raw_weights, raw_anchor, raw_cam, weight_mask)``: the training form of :func:`deformable_fused_forward`, backed by
+    ``gf_daf_fused_forward_masked`` / ``gf_daf_fused_backward``.  Differentiable in ``key_points``, ``mc_ms_feat`` and the logits;
+    the context keeps the inputs only (the backward forms the projection and the softmax again)."""
+
+    @staticmethod
+    def forward(ctx, key_points, projection_mat, image_wh, mc_ms_feat, spatial_shape, scale_start_index,
+                raw_weights, raw_anchor, raw_cam, weight_mask):
+        _lib.require_gpu(key_points, projection_mat, image_wh, mc_ms_feat, spatial_shape, scale_start_index, raw_weights,
+                         raw_anchor, raw_cam, weight_mask)
+        lib = _lib.load()
+        kp, pm, wh = _c(key_points), _c(projection_mat), _c(image_wh)
+        raw, ra, rc_ = _c(raw_weights), _c(raw_anchor), _c(raw_cam)
+        feat, wm = _c(mc_ms_feat), _mask_u8(weight_mask)
+        B, A, pts = kp.shape[:3]
+        cams, num_feat, C = feat.shape[1], feat.shape[2], feat.shape[3]
+        L = spatial_shape.shape[0]
+        if raw is not None:
+            if ra is not None or rc_ is not None:
+                raise ValueError("give raw_weights, or raw_anchor and raw_cam")
+            G = raw.shape[5]
+            assert raw.shape == (B, A, cams, L, pts, G)
+        else:
+            if ra is None or rc_ is None:
+                raise ValueError("give raw_weights, or raw_anchor and raw_cam")
+            G = ra.shape[4]
+            assert ra.shape == (B, A, L, pts, G) and rc_.shape == (B, cams, L, pts, G)
+        assert pm.shape == (B, cams, 4, 4) and feat.shape[0] == B
+        assert wm is None or wm.shape == (B, A, cams, L, pts, G)
+        ss, st = spatial_shape.to(torch.int32).contiguous(), scale_start_index.to(torch.int32).contiguous()
+        out = torch.empty(B, A, C, dtype=f32, device=kp.device)
+        with torch.cuda.device(kp.device):
+            rc = lib.gf_daf_fused_forward_masked(B, A, pts, cams, L, G, C, num_feat, _lib.ptr(kp), _lib.ptr(pm), _lib.ptr(wh),
+                                                 _lib.ptr(raw), _lib.ptr(ra), _lib.ptr(rc_), _lib.ptr(wm), _lib.ptr(feat),
+                                                 _lib.ptr(ss), _lib.ptr(st), _lib.ptr(out), _lib.current_stream(kp.device))
+        _lib.check(rc, "gf_daf_fused_forward_masked")
+        ctx.save_for_backward(kp, pm, wh, feat, ss, st, raw, ra, rc_, wm)
+        ctx.dims = (B, A, pts, cams, L, G, C, num_feat)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        kp, pm, wh, feat, ss, st, raw, ra, rc_, wm = ctx.saved_tensors
+        B, A, pts, cams, L, G, C, num_feat = ctx.dims
+        need = ctx.needs_input_grad
+        dev = kp.device
+        g_kp = torch.empty_like(kp) if need[0] else None
+        g_feat = torch.zeros_like(feat) if need[3] else None
+        g_raw = torch.empty_like(raw) if raw is not None and need[6] else None
+        g_ra = torch.empty_like(ra) if ra is not None and need[7] else None
+        g_rc = torch.empty_like(rc_) if rc_ is not None and need[8] else None
+        if not any(t is not None for t in (g_kp, g_feat, g_raw, g_ra, g_rc)):
+            return (None,) * 10
+        lib = _lib.load()
+        go = _c(grad_out)
+        ws_bytes = lib.gf_daf_fused_backward_workspace_bytes(B, A, pts, cams, L, G) if g_rc is not None else 0
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev) if g_rc is not None else None
+        with torch.cuda.device(dev):
+            rc = lib.gf_daf_fused_backward(B, A, pts, cams, L, G, C, num_feat, _lib.ptr(kp), _lib.ptr(pm), _lib.ptr(wh),
+                                           _lib.ptr(raw), _lib.ptr(ra), _lib.ptr(rc_), _lib.ptr(wm), _lib.ptr(feat), _lib.ptr(ss),
+                                           _lib.ptr(st), _lib.ptr(go), _lib.ptr(g_feat), _lib.ptr(g_kp), _lib.ptr(g_raw),
+                                           _lib.ptr(g_ra), _lib.ptr(g_rc), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
+        _lib.check(rc, "gf_daf_fused_backward")
+        return g_kp, None, None, g_feat, None, None, g_raw, g_ra, g_rc, None
+
+
+def deformable_fused(key_points, projection_mat, image_wh, mc_ms_feat, spatial_shape, scale_start_index,
+                     raw_weights=None, raw_anchor=None, raw_cam=None, weight_mask=None):
+    """``features [bs, A, C]`` of ``DeformableFeatureAggregation.forward`` for TRAINING (deformable_module.py:174-242): the
+    one-launch block of :func:`deformable_fused_forward` with the attention-dropout keep-mask ``weight_mask``
+    (``[bs, A, cams, L, pts, G]``, bool / uint8, ``True`` = keep; the reference draws it with ``torch.rand_like(weights) >
+    attn_drop``, :263-282) and a backward (``gf_daf_fused_backward``) into ``key_points``, ``mc_ms_feat`` (and through it
+    ``DAF.feature_maps_format`` to the pyramid levels) and the logits -- ``raw_weights`` or ``raw_anchor`` + ``raw_cam``.
+    No ``[A*pts, cams, L, G]`` weights tensor and no ``[A*pts, C]`` sampled features in either direction."""
+    return DeformableFusedFunction.apply(key_points, projection_mat, image_wh, mc_ms_feat, spatial_shape, scale_start_index,
+                                         raw_weights, raw_anchor, raw_cam, weight_mask)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 5   /* 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 6   /* 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -465,6 +465,46 @@ int gf_daf_fused_forward(int B, int A, int pts, int cams, int L, int G, int C, i
                          const float *projection_mat, const float *image_wh, const float *raw_weights, const float *raw_anchor,
                          const float *raw_cam, const float *mc_ms_feat, const int *spatial_shape, const int *scale_start_index,
                          float *out, void *stream);
+
+/*
+ * gf_daf_fused_forward with the attention-dropout keep-mask of training (deformable_module.py:199-214, 263-282):
+ *   weight_mask u8 [B,A,cams,L,pts,G] (the layout of raw_weights and of gf_daf_prepare's mask; non-zero = keep) or NULL.
+ * A dropped entry leaves its group's maximum and sum and weighs 0; a group whose entries are all dropped or invisible gives zero
+ * channels (the reference's all_miss, which can hold for one group of an anchor and not for the others).  With weight_mask NULL
+ * this is gf_daf_fused_forward (the same kernel: the same bits).  Other arguments and limits as gf_daf_fused_forward.
+ */
+int gf_daf_fused_forward_masked(int B, int A, int pts, int cams, int L, int G, int C, int num_feat, const float *key_points,
+                                const float *projection_mat, const float *image_wh, const float *raw_weights, const float *raw_anchor,
+                                const float *raw_cam, const unsigned char *weight_mask, const float *mc_ms_feat,
+                                const int *spatial_shape, const int *scale_start_index, float *out, void *stream);
+
+/* Bytes of the workspace gf_daf_fused_backward needs for grad_raw_cam (per-workgroup partial sums); 0 for invalid sizes. */
+size_t gf_daf_fused_backward_workspace_bytes(int B, int A, int pts, int cams, int L, int G);
+
+/*
+ * Backward of gf_daf_fused_forward_masked (training): replaces the autograd of the reference's block -- the softmax / mask /
+ * all_miss (deformable_module.py:199-233), DAF backward (ops/src/deformable_aggregation_cuda.cu:56-121, 190-259), the sum over the
+ * key points (:242) and project_points (:268-285) -- without the [A*pts, cams, L, G] weights tensor and the [A*pts, C] expanded
+ * gradient.  For anchor a, group g and kept entries e = (pt, cam, l), w_e the forward's weight and S_e[c] its bilinear sample:
+ *   gw_e = sum_{c in g} grad_out[a,c] S_e[c],   d logit_e = w_e (gw_e - sum_e' w_e' gw_e')   (0 where not kept, 0 for all-miss groups)
+ * Inputs: the forward's (the same logits form, the same weight_mask or NULL) and grad_out f32 [B,A,C] (16-byte aligned).
+ * Outputs, each may be NULL:
+ *   grad_mc_ms_feat f32 like mc_ms_feat: ACCUMULATED (zero it first), float atomics -- the last bits may differ between runs
+ *   grad_key_points f32 [B,A,pts,3]                     (gf_daf_prepare_backward's projection backward)
+ *   grad_raw_weights f32 [B,A,cams,L,pts,G]             (full logits only)
+ *   grad_raw_anchor f32 [B,A,L,pts,G]                   (split logits only: d logit summed over the cameras)
+ *   grad_raw_cam f32 [B,cams,L,pts,G]                   (split logits only: d logit summed over the anchors of each batch element;
+ *                                                        needs gf_daf_fused_backward_workspace_bytes(B, A, pts, cams, L, G) bytes)
+ * Every output but grad_mc_ms_feat is fully written, zeros included.  Limits as gf_daf_fused_forward, and one wave's LDS (the gw
+ * of every visible entry, pts * cams * L * G floats) must fit a CU: shapes the forward takes are all taken for L * G <= 43 (the
+ * reference's block: 16); larger ones may be refused with GF_EINVAL.  Every check runs before any HIP call.
+ */
+int gf_daf_fused_backward(int B, int A, int pts, int cams, int L, int G, int C, int num_feat, const float *key_points,
+                          const float *projection_mat, const float *image_wh, const float *raw_weights, const float *raw_anchor,
+                          const float *raw_cam, const unsigned char *weight_mask, const float *mc_ms_feat, const int *spatial_shape,
+                          const int *scale_start_index, const float *grad_out, float *grad_mc_ms_feat, float *grad_key_points,
+                          float *grad_raw_weights, float *grad_raw_anchor, float *grad_raw_cam, void *workspace,
+                          size_t workspace_bytes, void *stream);
 
 /*
  * Fused caller-side preparation of the deformable aggregation.

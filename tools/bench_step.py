@@ -5,6 +5,7 @@ the parts that stay torch / mmcv in the reference: image backbone, FFNs, norms, 
     image pyramid -> feature_maps_format
     4 encoder blocks: SparseConv3D (rulebook + gather-GEMM) -> weights_fc (torch GEMM) ->
                       deformable_prepare (projection + masked softmax) -> DAF.apply -> sum over key points
+                      (--daf fused: deformable_fused, the same block in one launch each way)
     head:             LocalAggregator.forward_from_rotations (fused Gaussian pre-processing + splat)
     loss = <logits, fixed target>; backward through everything.
 
@@ -25,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from gaussianformer_amd.deformable_aggregation import DeformableAggregationFunction as DAF  # noqa: E402
-from gaussianformer_amd.deformable_prepare import deformable_prepare  # noqa: E402
+from gaussianformer_amd.deformable_prepare import deformable_fused, deformable_prepare  # noqa: E402
 from gaussianformer_amd.local_aggregate import LocalAggregator  # noqa: E402
 from gaussianformer_amd.sparse_conv import SparseConv3D  # noqa: E402
 from gaussianformer_amd.synthetic import DAF_LEVELS, voxel_centres  # noqa: E402
@@ -47,8 +48,9 @@ def cameras(dev):
 
 
 class Block(torch.nn.Module):
-    def __init__(self):
+    def __init__(self, daf="three_step"):
         super().__init__()
+        self.daf = daf
         self.spconv = SparseConv3D(EMBED, EMBED, PC_RANGE, [0.5, 0.5, 0.5], use_out_proj=False, kernel_size=5)
         self.weights_fc = torch.nn.Linear(EMBED, CAMS * LEVELS * KEY_PTS * GROUPS)
         self.key_offsets = torch.nn.Parameter(torch.randn(KEY_PTS, 3) * 0.5)
@@ -58,13 +60,18 @@ class Block(torch.nn.Module):
         feat = feat + self.spconv(feat, anchor)
         key_points = means.unsqueeze(2) + self.key_offsets * scales.unsqueeze(2)
         raw = self.weights_fc(feat).reshape(bs, A, CAMS, LEVELS, KEY_PTS, GROUPS)
+        if self.daf == "fused":
+            return feat + deformable_fused(key_points, pm, wh, table, ss, st, raw_weights=raw)
         points_2d, weights = deformable_prepare(key_points, pm, wh, raw)
         sampled = DAF.apply(table, ss, st, points_2d, weights)          # [bs, A * KEY_PTS, EMBED]
         return feat + sampled.view(bs, A, KEY_PTS, EMBED).sum(2)
 
 
-def run(anchors=25600, steps=10, warmup=3):
-    """Runs the chained step and returns the result record (raises if a leaf got no usable gradient)."""
+def run(anchors=25600, steps=10, warmup=3, daf="three_step"):
+    """Runs the chained step and returns the result record (raises if a leaf got no usable gradient).  ``daf="fused"`` runs
+    each block's deformable aggregation as deformable_fused instead of deformable_prepare -> DAF.apply -> sum."""
+    if daf not in ("three_step", "fused"):
+        raise ValueError(f"daf must be 'three_step' or 'fused', not {daf!r}")
     args = argparse.Namespace(anchors=anchors, steps=steps, warmup=warmup)
     if not torch.cuda.is_available():
         raise RuntimeError("bench_step.py needs an MI355X")
@@ -74,7 +81,7 @@ def run(anchors=25600, steps=10, warmup=3):
     H, W, D, cell = 200, 200, 16, 0.5      # grid_size 0.5 m (config :154): voxel centres are exact in fp32
     pc_min = PC_RANGE[:3]
 
-    blocks = torch.nn.ModuleList([Block() for _ in range(4)]).to(dev)
+    blocks = torch.nn.ModuleList([Block(daf) for _ in range(4)]).to(dev)
     for b in blocks:
         torch.nn.init.normal_(b.spconv.layer.weight, std=0.01)
     anchor = torch.randn(1, A, 11, device=dev).requires_grad_(True)
@@ -133,6 +140,8 @@ def run(anchors=25600, steps=10, warmup=3):
     out = {"op": "hot-path training step (4 x [sparse conv + DAF prepare + DAF] + fused prepare + splat, fwd + bwd)",
            "anchors": A, "sample_points": A * KEY_PTS, "forward_ms": fwd * 1e3, "forward_backward_ms": full * 1e3,
            "loss": float(loss.detach()), "leaves": len(leaves), "leaves_without_finite_nonzero_grad": bad}
+    if daf != "three_step":
+        out["daf"] = daf
     if bad:
         raise RuntimeError(f"gradient check failed for leaves {bad}: {out}")
     return out
@@ -143,8 +152,9 @@ def main():
     ap.add_argument("--anchors", type=int, default=25600)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--daf", choices=("three_step", "fused"), default="three_step")
     args = ap.parse_args()
-    print(json.dumps(run(args.anchors, args.steps, args.warmup)))
+    print(json.dumps(run(args.anchors, args.steps, args.warmup, args.daf)))
 
 
 if __name__ == "__main__":
