@@ -696,8 +696,9 @@ __device__ __forceinline__ bool finish_row_layout(const RenderArgs &a, uint32_t 
 
 // The same for long rows (kWRow < nwords <= kLongWords waves of Gaussians; round 6): `per` = ceil(nwords / 64) layout words per lane,
 // in batches of twelve loads (as a plain loop every load was a round trip of its own); the prefix of every wave goes to LDS --
-// up to 16 KB: the long-row kernel's whole block is idle at this point --, then workgroup b writes the first rows of the waves
-// b, b + kRowLayoutBlocks, ... (36 of them at P = 144 000).
+// up to 16 KB, dwords [0, nwords) of the long-row kernel's block: idle at this point except for the first unit's prefetched summary
+// row at kLSumAt, which rows of more than kLSumAt words overwrite (the caller then has the unit fetch it again) --, then workgroup b
+// writes the first rows of the waves b, b + kRowLayoutBlocks, ... (36 of them at P = 144 000).
 __device__ __forceinline__ bool finish_row_layout_long(const RenderArgs &a, uint32_t *s_base, int lane)
 {
     const int nw = a.nwords;
@@ -2044,6 +2045,9 @@ static_assert(2 * 64 * kC <= 1536 + 3 * kWList, "output staging fits over the sl
 //   [17232, 20480)  hit queue, opacity * semantics: as above
 constexpr int kLDense = 576, kLIds = 896;   // (both multiples of 64: the gathers write whole rounds of 64 entries)
 static_assert(2 * kLDense + kLDense / 2 <= 1536 && 1536 + 3 * kLIds <= 3072 + 2 * kWRow && kLDense % 64 == 0 && kLIds % 64 == 0 && kLIds == kBwdPubLong, "LDS map of the long-row instantiation");
+constexpr int kLSumAt = 3968;   // dword offset of the summary row: [15872, 16896) bytes in the map above, box hi's last 64 x 4 dwords
+static_assert(kLSumAt == 1536 + 3 * kLIds - 64 * 4, "the summary row is the tail of box hi (LDS map above)");
+static_assert(kLSumAt < kLongWords, "finish_row_layout_long's prefix reaches the summary row: the first unit re-fetches it past kLSumAt words");
 static_assert(kLongWords <= 64 * 64, "one summary bit per word, 64 per lane");
 template <bool LABELS, bool PREP = false, bool INTER = true, bool LONG = false>
 __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(RenderArgs a)
@@ -2054,7 +2058,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     uint32_t *s_lg = s_u + 1536, *s_blo = s_u + 1536 + kListN, *s_bhi = s_u + 1536 + 2 * kListN;
     float *stage = reinterpret_cast<float *>(s_u);
     unsigned long long *s_row = reinterpret_cast<unsigned long long *>(s_u + 3072);
-    uint32_t *s_sum = s_u + 3968;   // LONG: the summary row (64 lanes x 16 bytes)
+    uint32_t *s_sum = s_u + kLSumAt;   // LONG: the summary row (64 lanes x 16 bytes)
     uint32_t *q_id = s_u + 3072 + 2 * kWRow;
     float *S = reinterpret_cast<float *>(s_u + 3072 + 2 * kWRow + kQCap);
 
@@ -2153,8 +2157,12 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     }
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(q0x), "+v"(q0y), "+v"(q0z), "+v"(q1x), "+v"(q1y), "+v"(q1z)::"memory");   // (landed with the verdict words)
     uint32_t rows_ready = 0u;
-    if (PREP && blockIdx.x < (unsigned)kRowLayoutBlocks && a.rows_valid && !verdict)   // (slot area of the LDS block: idle until the first list is built)
+    if (PREP && blockIdx.x < (unsigned)kRowLayoutBlocks && a.rows_valid && !verdict) {   // (slot area of the LDS block: idle until the first list is built)
         rows_ready = (LONG ? finish_row_layout_long(a, s_u, lane) : finish_row_layout(a, s_u, lane)) ? 1u : 2u;
+        // (long rows: the prefix took s_u[0, nwords), over the prefetched summary row past kLSumAt words -- landed before the
+        // prefix was written, by the wait above -- so the first unit requests it again, like any later unit)
+        if (LONG && a.nwords > kLSumAt) row_there = false;
+    }
     if (blockIdx.x == 0 && lane == 0 && a.state) {
         a.state[0] = (verdict & 1) ? 1u : 0u;
         a.state[1] = verdict ? GF_PATH_ARBITRARY : GF_PATH_MATRIX_CORE_WAVE;
