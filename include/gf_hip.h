@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 7   /* 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 8   /* 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -611,6 +611,52 @@ int gf_occ_loss_backward(int L, int N, int C, int flags, const float *const *pre
                          const long long *label, const unsigned char *mask, const float *class_weights, float ce_weight,
                          float lovasz_weight, int lovasz_ignore, int ignore_index, int empty_label, const float *grad_loss,
                          float *const *grad_pred, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- GaussianLifterV2's pixel lifting and PixelDistributionLoss ----------------------------------------------------
+ * gf_lift_pixels replaces the per-frame pixel work of GaussianLifterV2.forward from the pixel logits to the FPS call
+ * (model/lifter/gaussian_lifter_v2.py:169-233 with model/utils/sampler.py:9-37), DESIGN.md §3.10.  Per batch element
+ * bi, camera c, pixel (i, j) (q = (c h + i) w + j) and depth bin k < S:
+ *   u = (j + 0.5f) / w * image_wh[bi][c][0], v = (i + 0.5f) / h * image_wh[bi][c][1] (fp32, in this order);
+ *   point_k = (img2lidar[bi][c] @ (u d_k, v d_k, d_k, 1))[:3], d = depth_bins;
+ *   pdf = softmax(logits[bi][q][0..S]); disabled = argmax(pdf) == S (ties to the lower index);
+ *   sample j < a: stochastic (uniforms given): index = #{k : cdf_k <= uniforms[bi][q][j]} clipped to S, cdf = cumsum(pdf /
+ *   (FLT_EPSILON + sum pdf)); deterministic (uniforms NULL): the j-th largest pdf entry, ties to the lower index.
+ *   The candidate of slot q a + j is point_min(index, S-1) when the pixel is not disabled and pc_min <= point < pc_max on
+ *   every axis.  points[bi][0 .. counts[bi]) are the candidates in slot order; src[bi][.] their slots; the rest of the
+ *   [n h w a] rows holds 0 (points) and -1 (src).
+ *   pixel_gt[bi][q][k] = in range(point_k) && occ[bi][ix][iy][iz], i* = trunc((p - pc_min) / voxel_size) clamped to the
+ *   grid; pixel_gt[bi][q][S] = no k set.
+ *   logits      f32 [b][n h w][S + 1];  img2lidar f32 [b][n][4][4];  image_wh f32 [b][n][2];  depth_bins f32 [S]
+ *   pc_range_host   HOST float[6] (x, y, z min, x, y, z max)
+ *   occ         uint8 [b][X][Y][Z], (label != empty) & cam_mask, needed with pixel_gt only
+ *   uniforms    f32 [b][n h w][a] or NULL (deterministic)
+ *   points      f32 [b][n h w a][3], counts int [b], src int [b][n h w a] (or NULL): points and counts both or neither
+ *   pixel_gt    uint8 [b][n h w][S + 1] or NULL
+ *   workspace   gf_lift_workspace_bytes(b, n h w, a) bytes
+ * Limits: S + 1 <= GF_LIFT_MAX_BINS (four entries per lane of a 64-lane wave), 1 <= a <= GF_LIFT_MAX_ANCHORS; every check
+ * runs before any HIP call.  No float atomics: the outputs are bitwise reproducible.
+ *
+ * gf_pixel_loss_forward / _backward: PixelDistributionLoss.loss_voxel (loss/bce_loss.py:60-87) without its weight:
+ *   p = softmax over each row of `bins` (GF_PIXEL_LOSS_SOFTMAX) or sigmoid (GF_PIXEL_LOSS_SIGMOID) in fp32;
+ *   loss = mean over rows x bins of -(t max(log p, -100) + (1 - t) max(log1p(-p), -100)), t = pixel_gt != 0 (torch's
+ *   binary_cross_entropy), summed in a fixed order (bitwise reproducible);
+ *   backward: d/dp = grad_loss (p - t) / max((1 - p) p, 1e-12f) / (rows bins) (torch's BCE backward), then through the
+ *   softmax (p (g - sum g p)) or the sigmoid (g (1 - p) p).  Every element of grad_logits is written.
+ *   workspace   gf_pixel_loss_workspace_bytes(rows, bins) bytes (the forward's partials) */
+#define GF_LIFT_MAX_BINS 256
+#define GF_LIFT_MAX_ANCHORS 8
+#define GF_PIXEL_LOSS_SOFTMAX 1
+#define GF_PIXEL_LOSS_SIGMOID 2
+size_t gf_lift_workspace_bytes(int b, int npix, int a);
+int gf_lift_pixels(int b, int n, int h, int w, int S, int a, const float *logits, const float *img2lidar,
+                   const float *image_wh, const float *depth_bins, const float *pc_range_host, float voxel_size, int X, int Y,
+                   int Z, const unsigned char *occ, const float *uniforms, float *points, int *counts, int *src,
+                   unsigned char *pixel_gt, void *workspace, size_t workspace_bytes, void *stream);
+size_t gf_pixel_loss_workspace_bytes(int rows, int bins);
+int gf_pixel_loss_forward(int rows, int bins, int flags, const float *logits, const unsigned char *pixel_gt, float *loss,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int gf_pixel_loss_backward(int rows, int bins, int flags, const float *logits, const unsigned char *pixel_gt,
+                           const float *grad_loss, float *grad_logits, void *stream);
 
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */

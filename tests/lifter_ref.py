@@ -1,0 +1,159 @@
+"""Float64 numpy restatement of GaussianLifterV2's pixel work and of PixelDistributionLoss (the oracle of the lifter tests;
+gaussianformer_amd/lifter.py states the semantics).  Inputs are the fp32 arrays the op receives; everything after the
+fp32 ray coordinates ``u = (j + 0.5) / w * W`` is evaluated in float64.  Alongside its results, ``lift`` reports the
+entries whose exact answer depends on rounding (the exemption rule of the tests):
+
+* (a) a point coordinate within ``face_tol`` of a voxel face or a ``pc_range`` face;
+* (b) a uniform within ``cdf_tol`` of an end of the cdf step it falls in;
+* (c) the two largest pdf entries within ``tie_tol`` relative (argmax / top-a order).
+"""
+import numpy as np
+
+FLT_EPSILON = float(np.finfo(np.float32).eps)
+
+
+def softmax64(x):
+    x = np.asarray(x, np.float64)
+    e = np.exp(x - x.max(-1, keepdims=True))
+    return e / e.sum(-1, keepdims=True)
+
+
+def ray_points(img2lidar, image_wh, depth_bins, h, w):
+    """``[b, n, h, w, S, 3]`` float64 points of every depth bin (u, v formed in fp32, as the reference)."""
+    j = ((np.arange(w, dtype=np.float32) + np.float32(0.5)) / np.float32(w)).astype(np.float32)
+    i = ((np.arange(h, dtype=np.float32) + np.float32(0.5)) / np.float32(h)).astype(np.float32)
+    wh = np.asarray(image_wh, np.float32)
+    U = (j[None, None, None, :] * wh[:, :, None, None, 0]).astype(np.float64)     # b, n, 1, w
+    V = (i[None, None, :, None] * wh[:, :, None, None, 1]).astype(np.float64)     # b, n, h, 1
+    d = np.asarray(depth_bins, np.float32).astype(np.float64)
+    M = np.asarray(img2lidar, np.float32).astype(np.float64)                        # b, n, 4, 4
+    X = U[..., None] * d                                                            # b, n, 1, w, S
+    Y = V[..., None] * d                                                            # b, n, h, 1, S
+    out = []
+    for r in range(3):
+        m = M[:, :, r]
+        out.append(m[:, :, 0, None, None, None] * X + m[:, :, 1, None, None, None] * Y + m[:, :, 2, None, None, None] * d
+                   + m[:, :, 3, None, None, None])
+    return np.stack(np.broadcast_arrays(*out), -1)
+
+
+def _near_face(p, lo, vs, hi, tol):
+    """Coordinates within tol of a voxel face (multiples of vs from lo) or of the range's faces."""
+    near = (np.abs(p - lo) <= tol) | (np.abs(p - hi) <= tol)
+    if vs is not None:
+        t = (p - lo) / vs
+        near |= np.abs(t - np.round(t)) * vs <= tol
+    return near.any(-1)
+
+
+def lift(logits, img2lidar, image_wh, depth_bins, pc_range, voxel_size, occ_resolution, a, uniforms=None, occ=None,
+         face_tol=2e-4, cdf_tol=1e-5, tie_tol=1e-6):
+    """Returns a dict: ``scans`` (list of [count, 3] float64), ``src`` (list of slot indices), ``pixel_gt`` ([b, n, h, w,
+    S + 1] bool or None), and the exemption masks ``slot_exempt`` ([b, n h w a]: the slot's candidate status or point may
+    depend on rounding) and ``gt_exempt`` ([b, n, h, w, S]).  ``occ`` is the packed [b, X, Y, Z] table."""
+    logits = np.asarray(logits, np.float32)
+    b, n, h, w, nb = logits.shape
+    S = nb - 1
+    lo, hi = np.asarray(pc_range[:3], np.float64), np.asarray(pc_range[3:], np.float64)
+    vs = float(np.float32(voxel_size))
+    pts = ray_points(img2lidar, image_wh, depth_bins, h, w)                          # b, n, h, w, S, 3
+    pdf = softmax64(logits)
+    order = np.argsort(-pdf, axis=-1, kind="stable")                                 # descending, ties to the lower index
+    top = np.take_along_axis(pdf, order[..., :2], -1)
+    tie = np.abs(top[..., 0] - top[..., 1]) <= tie_tol * top[..., 0]
+    disabled = order[..., 0] == S
+    if uniforms is None:
+        index = order[..., :a]
+        # top-a order depends on rounding when any of the first a + 1 entries are near-equal neighbours
+        srt = np.take_along_axis(pdf, order[..., :min(a + 1, nb)], -1)
+        close = (np.abs(np.diff(srt, axis=-1)) <= tie_tol * srt[..., :-1]).any(-1) if srt.shape[-1] > 1 else tie
+        pix_ex = tie | close
+    else:
+        u = np.asarray(uniforms, np.float32).astype(np.float64)                      # b, n, h, w, a
+        cdf = np.cumsum(pdf / (FLT_EPSILON + pdf.sum(-1, keepdims=True)), -1)
+        index = np.minimum((cdf[..., None, :] <= u[..., None]).sum(-1), S)
+        # the chosen step is [cdf[index - 1], cdf[index]): u near either end
+        lo_edge = np.take_along_axis(cdf, np.maximum(index - 1, 0), -1)
+        hi_edge = np.take_along_axis(cdf, np.minimum(index, S), -1)
+        near = ((index > 0) & (np.abs(u - lo_edge) <= cdf_tol)) | (np.abs(u - hi_edge) <= cdf_tol)
+        pix_ex = tie[..., None] | near
+    if pix_ex.ndim == 4:
+        pix_ex = np.broadcast_to(pix_ex[..., None], (b, n, h, w, a))
+    k = np.minimum(index, S - 1)
+    cand = np.take_along_axis(pts, k[..., None].repeat(3, -1), -2)                  # b, n, h, w, a, 3
+    inr = ((cand >= lo) & (cand < hi)).all(-1)
+    keep = ~disabled[..., None] & inr
+    slot_ex = pix_ex | _near_face(cand, lo, None, hi, face_tol)
+    slot_ex = slot_ex.reshape(b, -1)
+    keep = keep.reshape(b, -1)
+    cand = cand.reshape(b, -1, 3)
+    scans = [cand[i][keep[i]] for i in range(b)]
+    src = [np.nonzero(keep[i])[0].astype(np.int32) for i in range(b)]
+    pixel_gt = gt_ex = None
+    if occ is not None:
+        R = np.asarray(occ_resolution)
+        inr_all = ((pts >= lo) & (pts < hi)).all(-1)
+        idx = np.clip(np.trunc((pts - lo) / vs).astype(np.int64), 0, R - 1)
+        occ = np.asarray(occ)
+        hit = np.stack([occ[i][idx[i, ..., 0], idx[i, ..., 1], idx[i, ..., 2]] != 0 for i in range(b)])
+        g = inr_all & hit
+        pixel_gt = np.concatenate([g, ~g.any(-1, keepdims=True)], -1)
+        gt_ex = _near_face(pts, lo, vs, hi, face_tol)
+    return dict(scans=scans, src=src, pixel_gt=pixel_gt, slot_exempt=slot_ex, gt_exempt=gt_ex, keep=keep, cand=cand,
+                disabled=disabled)
+
+
+def check_lift(r, scans, srcs, pixel_gt=None, atol=1e-4, bound=1e-4, what=""):
+    """Compares an op's output with ``lift``'s ``r``.  Candidates (by slot, via ``srcs``), their order and ``pixel_gt`` must
+    match exactly and points within ``atol``, except at entries ``lift`` marks as rounding-dependent; the entries that differ
+    there are the exempted ones.  Asserts, prints and returns ``(exempted, compared)``; exempted <= bound * compared."""
+    exempted = compared = 0
+    for i, (scan, src) in enumerate(zip(scans, srcs)):
+        scan, src = np.asarray(scan, np.float64), np.asarray(src, np.int64)
+        keep_ref, ex, cand = r["keep"][i], r["slot_exempt"][i], r["cand"][i]
+        assert scan.shape == (src.size, 3)
+        assert (np.diff(src) > 0).all(), "candidates out of slot order"
+        keep = np.zeros(keep_ref.size, bool)
+        keep[src] = True
+        pts = np.full((keep_ref.size, 3), np.nan)
+        pts[src] = scan
+        bad = keep != keep_ref
+        both = keep & keep_ref
+        bad[both] |= ~(np.abs(pts[both] - cand[both]) <= atol).all(-1)
+        assert not (bad & ~ex).any(), f"{what}: slots {np.nonzero(bad & ~ex)[0][:10]} differ"
+        exempted += int(bad.sum())
+        compared += keep_ref.size
+    if pixel_gt is not None:
+        got, want, ex = np.asarray(pixel_gt, bool), r["pixel_gt"], r["gt_exempt"]
+        assert got.shape == want.shape
+        bad = got[..., :-1] != want[..., :-1]
+        assert not (bad & ~ex).any(), f"{what}: pixel_gt differs at {np.argwhere(bad & ~ex)[:5].tolist()}"
+        bad_last = got[..., -1] != want[..., -1]
+        assert not (bad_last & ~ex.any(-1)).any(), f"{what}: pixel_gt[..., S] differs"
+        exempted += int(bad.sum() + bad_last.sum())
+        compared += got.size
+    print(f"{what}: {exempted} exempted of {compared} compared entries")
+    assert exempted <= bound * compared, (exempted, compared)
+    return exempted, compared
+
+
+def pixel_loss(logits, gt, use_sigmoid):
+    """``(loss, grad)``: torch's binary_cross_entropy of ``p = softmax / sigmoid(logits)`` (fp32 p, as the reference) with
+    the log clamped at -100, mean over all entries, and its gradient in the logits (BCE backward floor 1e-12 on
+    ``p (1 - p)``), evaluated in float64 from the fp32 ``p``."""
+    x = np.asarray(logits, np.float32).astype(np.float64)
+    t = np.asarray(gt).astype(np.float64)
+    if use_sigmoid:
+        p = (1.0 / (1.0 + np.exp(-x))).astype(np.float32).astype(np.float64)
+    else:
+        p = softmax64(x).astype(np.float32).astype(np.float64)
+    with np.errstate(divide="ignore"):
+        lp = np.maximum(np.log(p), -100.0)
+        l1p = np.maximum(np.log1p(-p), -100.0)
+    loss = float(-(t * lp + (1 - t) * l1p).mean())
+    gp = (p - t) / np.maximum((1 - p) * p, float(np.float32(1e-12))) / t.size
+    if use_sigmoid:
+        g = gp * (1 - p) * p
+    else:
+        g = p * (gp - (gp * p).sum(-1, keepdims=True))
+    return loss, g
