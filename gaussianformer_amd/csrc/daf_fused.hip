@@ -41,6 +41,8 @@ namespace gf {
 constexpr int kFuMaxPairs = 256;   // pts * cams per anchor (as gf_daf_prepare)
 constexpr int kFuMaxLG = 64;       // L * G entries per pair
 
+__host__ __device__ inline int fu_even(int n) { return n + (n & 1); }
+
 struct DafFusedArgs {
     const float *key_points;   // [B, A, pts, 3]
     const float *proj;         // [B, cams, 4, 4]
@@ -67,10 +69,11 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
     extern __shared__ float s_dyn[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int npair = a.pts * a.cams, LG = a.L * a.G, LPG = a.L * a.pts * a.G;
-    // dynamic LDS: [cams][LPG] camera logits (shared) | per wave: [LPG] anchor logits, [npair] uv (float2), [npair] list of visible pairs
+    // dynamic LDS: [cams][LPG] camera logits (shared, padded to an even count) | per wave: [LPG] anchor logits, [npair] uv (float2),
+    // [npair] list of visible pairs
     float *s_cam = s_dyn;
     const int per_wave = LPG + (LPG & 1) + 3 * npair + (npair & 1);   // (even: the uv pairs are read as float2)
-    float *s_mine = s_dyn + (a.raw ? 0 : a.cams * LPG) + wave * per_wave;
+    float *s_mine = s_dyn + (a.raw ? 0 : fu_even(a.cams * LPG)) + wave * per_wave;
     float *s_anc = s_mine;
     float2 *s_uv = reinterpret_cast<float2 *>(s_mine + LPG + (LPG & 1));
     int *s_list = reinterpret_cast<int *>(s_mine + LPG + (LPG & 1) + 2 * npair);
@@ -261,7 +264,6 @@ struct DafFusedBwdArgs {
     int per_wg, nchunk;          // anchors per workgroup, workgroups per batch element
 };
 
-__host__ __device__ inline int fu_even(int n) { return n + (n & 1); }
 // floats of LDS per wave: uv, d uv (float2 each), anchor logits, visible list, pair -> list slot, key-point partials, gw
 __host__ __device__ inline int fu_bwd_per_wave(int npair, int LG, int LPG) { return fu_even(4 * npair + LPG + 2 * npair + 3 * npair + npair * LG); }
 
@@ -565,12 +567,16 @@ static int fu_forward(int B, int A, int pts, int cams, int L, int G, int C, int 
     a.raw_cam = raw_cam; a.feat = mc_ms_feat; a.spatial_shape = spatial_shape; a.scale_start = scale_start_index; a.out = out;
     a.B = B; a.A = A; a.pts = pts; a.cams = cams; a.L = L; a.G = G; a.C = C; a.num_feat = num_feat; a.wmask = weight_mask;
     const int npair = pts * cams, LPG = L * pts * G;
-    const size_t lds = sizeof(float) * ((raw_weights ? 0 : (size_t)cams * LPG) + 4 * ((size_t)LPG + (LPG & 1) + 3 * npair + (npair & 1)));
+    const size_t lds = sizeof(float) * ((raw_weights ? 0 : (size_t)fu_even(cams * LPG)) + 4 * ((size_t)LPG + (LPG & 1) + 3 * npair + (npair & 1)));
     GF_CHECK_ARG(lds <= 160 * 1024, "shape needs more LDS than a CU has");
     const long long nanchor = (long long)B * A;
     const void *kernel = weight_mask ? reinterpret_cast<const void *>(gf_daf_fused_kernel<GF_FU_CPL, true>)
                                      : reinterpret_cast<const void *>(gf_daf_fused_kernel<GF_FU_CPL, false>);
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > 64 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();   // (not left for the next launch check to find)
+        set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed", __func__, lds);
+        return GF_ELAUNCH;
+    }
     if (weight_mask)
         hipLaunchKernelGGL((gf_daf_fused_kernel<GF_FU_CPL, true>), dim3((unsigned)((nanchor + 3) / 4)), dim3(256), lds, stream, a);
     else
@@ -641,8 +647,13 @@ extern "C" int gf_daf_fused_backward(int B, int A, int pts, int cams, int L, int
     a.grad_out = grad_out; a.grad_feat = grad_mc_ms_feat; a.grad_kp = grad_key_points; a.grad_raw = grad_raw_weights;
     a.grad_raw_anchor = grad_raw_anchor; a.part_cam = grad_raw_cam ? static_cast<float *>(workspace) : nullptr;
     a.per_wg = g.per_wg; a.nchunk = g.nchunk;
-    if (g.lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gf_daf_fused_bwd_kernel<GF_FU_CPL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
+    if (g.lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(gf_daf_fused_bwd_kernel<GF_FU_CPL>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)g.lds) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed", __func__, g.lds);
+        return GF_ELAUNCH;
+    }
     hipLaunchKernelGGL(gf_daf_fused_bwd_kernel<GF_FU_CPL>, dim3((unsigned)(B * g.nchunk)), dim3(64 * g.nw), g.lds, stream, a);
     GF_CHECK_LAUNCH();
     if (grad_raw_cam) {

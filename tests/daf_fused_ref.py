@@ -77,3 +77,98 @@ def block(key_points, projection_mat, image_wh, maps, raw, weight_mask=None):
     L, G = w.shape[4], w.shape[5]
     out = daf(maps, uv.reshape(b, A * pts, cams, 2), w.reshape(b, A * pts, cams, L, G))
     return out.reshape(b, A, pts, -1).sum(dim=2)
+
+
+# ---- chunked drivers: the same restatement at full size (points in slices, leaf gradients accumulated across slices) ----------
+
+def table_levels(feat, spatial_shape, scale_start):
+    """The formatted table ``[b, cams, num_feat, C]`` (DAF.feature_maps_format) as per-level ``[b, cams, C, h, w]`` views, so that
+    the restatement's gradient lands in the table's own layout."""
+    b, cams, _, C = feat.shape
+    out = []
+    for (h, w), s in zip(spatial_shape.tolist(), scale_start.tolist()):
+        out.append(feat[:, :, s:s + h * w].reshape(b, cams, h, w, C).permute(0, 1, 4, 2, 3))
+    return out
+
+
+def slice_len(cams, C, L, budget=3e9, lo=1024, hi=32768):
+    """Points per slice: what autograd keeps of one slice (about 40 gathered [n, cams, C] tensors per level of taps) under
+    ``budget`` bytes of float64."""
+    return int(max(lo, min(hi, budget // (cams * C * 8 * 10 * L))))
+
+
+def daf_chunked(feat, spatial_shape, scale_start, loc, weights, grad_out, dtype=torch.float64, chunk=None):
+    """DAF.apply's forward and its three gradients by the restatement in ``dtype``: feat [b, cams, num_feat, C], loc
+    [b, N, cams, 2], weights [b, N, cams, L, G], grad_out [b, N, C] -> (out [b, N, C], grad_feat, grad_loc, grad_weights)."""
+    b, N, cams = loc.shape[:3]
+    C, L = feat.shape[3], weights.shape[3]
+    chunk = chunk or slice_len(cams, C, L)
+    ft = feat.detach().to(dtype).requires_grad_(True)
+    out = torch.empty(b, N, C, dtype=dtype, device=feat.device)
+    g_loc = torch.empty(loc.shape, dtype=dtype, device=feat.device)
+    g_w = torch.empty(weights.shape, dtype=dtype, device=feat.device)
+    for s in range(0, N, chunk):
+        e = min(N, s + chunk)
+        uv = loc[:, s:e].detach().to(dtype).requires_grad_(True)
+        w = weights[:, s:e].detach().to(dtype).requires_grad_(True)
+        o = daf(table_levels(ft, spatial_shape, scale_start), uv, w)
+        o.backward(grad_out[:, s:e].to(dtype))
+        out[:, s:e], g_loc[:, s:e], g_w[:, s:e] = o.detach(), uv.grad, w.grad
+        del o, uv, w
+    return out, ft.grad, g_loc, g_w
+
+
+def block_chunked(key_points, projection_mat, image_wh, feat, spatial_shape, scale_start, grad_out, raw=None, raw_anchor=None,
+                  raw_cam=None, weight_mask=None, dtype=torch.float64, chunk=None):
+    """The fused op (deformable_fused) by the restatement in ``dtype``, anchors in slices: key_points [b, A, pts, 3], feat the
+    formatted table, logits ``raw`` [b, A, cams, L, pts, G] or ``raw_anchor`` [b, A, L, pts, G] + ``raw_cam`` [b, cams, L, pts, G],
+    grad_out [b, A, C] -> (out [b, A, C], dict of leaf gradients: kp, feat, and raw or ra and rc)."""
+    b, A, pts = key_points.shape[:3]
+    cams, C, L = feat.shape[1], feat.shape[3], spatial_shape.shape[0]
+    step = max(1, (chunk or slice_len(cams, C, L)) // pts)
+    cast = lambda t: None if t is None else t.detach().to(dtype)
+    pm, wh = cast(projection_mat), cast(image_wh)
+    ft = feat.detach().to(dtype).requires_grad_(True)
+    rc = None if raw_cam is None else raw_cam.detach().to(dtype).requires_grad_(True)
+    out = torch.empty(b, A, C, dtype=dtype, device=feat.device)
+    grads = {"kp": torch.empty(key_points.shape, dtype=dtype, device=feat.device)}
+    lead = raw if raw is not None else raw_anchor
+    grads["raw" if raw is not None else "ra"] = torch.empty(lead.shape, dtype=dtype, device=feat.device)
+    for s in range(0, A, step):
+        e = min(A, s + step)
+        kp = key_points[:, s:e].detach().to(dtype).requires_grad_(True)
+        lg = lead[:, s:e].detach().to(dtype).requires_grad_(True)
+        x = lg if raw is not None else lg[:, :, None] + rc[:, None]
+        wm = None if weight_mask is None else weight_mask[:, s:e]
+        o = block(kp, pm, wh, table_levels(ft, spatial_shape, scale_start), x, wm)
+        o.backward(grad_out[:, s:e].to(dtype))
+        out[:, s:e] = o.detach()
+        grads["kp"][:, s:e] = kp.grad
+        grads["raw" if raw is not None else "ra"][:, s:e] = lg.grad
+        del o, kp, lg, x
+    grads["feat"] = ft.grad
+    if rc is not None:
+        grads["rc"] = rc.grad
+    return out, grads
+
+
+def touched_rows(spatial_shape, scale_start, loc, num_feat, slack=1e-4):
+    """[b, cams, num_feat] bool: the table rows some tap of a visible (point, camera) pair lands on (in the map), at any level.
+    A tap coordinate within ``slack`` pixels of a cell edge marks the cells on both sides (float32 arithmetic may round it either
+    way; the coefficient of the extra row is then ~0)."""
+    b, N, cams = loc.shape[:3]
+    inside = ((loc > 0) & (loc < 1)).all(-1)                                          # [b, N, cams]
+    hit = torch.zeros(b, cams, num_feat, dtype=torch.bool, device=loc.device)
+    bi = torch.arange(b, device=loc.device)[:, None, None].expand(b, N, cams)
+    ci = torch.arange(cams, device=loc.device)[None, None, :].expand(b, N, cams)
+    for (h, w), st in zip(spatial_shape.tolist(), scale_start.tolist()):
+        y, x = loc[..., 1].double() * h - 0.5, loc[..., 0].double() * w - 0.5
+        for ey in (-slack, slack):
+            for ex in (-slack, slack):
+                h0, w0 = torch.floor(y + ey).long(), torch.floor(x + ex).long()
+                for dy in (0, 1):
+                    for dx in (0, 1):
+                        py, px = h0 + dy, w0 + dx
+                        ok = inside & (py >= 0) & (py < h) & (px >= 0) & (px < w)
+                        hit[bi[ok], ci[ok], st + py[ok] * w + px[ok]] = True
+    return hit

@@ -67,3 +67,37 @@ def test_backward_matches_reference_fallback():
     loc.backward(torch.tensor(gl, dtype=torch.float64))
     want = d["grad_key_points_f64"]
     assert np.abs(kp.grad.numpy() - want).max() <= 5e-5 * np.abs(want).max()
+
+
+def test_float64_restatement_is_the_reference_fallback():
+    """tests/daf_fused_ref.py -- the yardstick of tests/test_daf_truth_gpu.py -- in float64 against the same fixture, through the
+    sliced drivers (slices smaller than the fixture, so that the gradients are accumulated across slices): the DAF with the
+    fixture's per-key-point gradient, and the whole block (projection, masked softmax of ``raw``, DAF, sum over the key points)."""
+    import daf_fused_ref as ref
+    d, levels, feat, ss, st, _, (bs, A, K, cams, L, G, C) = _load()
+    f64 = torch.float64
+    kp, pm, wh = (torch.tensor(d[k], dtype=f64) for k in ("key_points", "projection_mat", "image_wh"))
+    feat, ss, st = torch.tensor(feat), torch.tensor(ss), torch.tensor(st)
+    uv, vis = ref.project(kp, pm, wh)
+    assert np.array_equal(vis.permute(0, 3, 1, 2).numpy(), d["visible"])
+    w = ref.softmax_weights(vis, torch.tensor(d["raw"], dtype=f64))                      # [bs, A, K, cams, L, G]
+    assert np.abs(w.permute(0, 1, 3, 4, 2, 5).numpy() - d["weights"]).max() <= 1e-6
+    out, g_feat, g_loc, g_w = ref.daf_chunked(feat, ss, st, uv.reshape(bs, A * K, cams, 2), w.reshape(bs, A * K, cams, L, G),
+                                              torch.tensor(d["grad_output"]).reshape(bs, A * K, C), chunk=37)
+    scale = np.abs(d["output_f64"]).max()
+    assert np.abs(out.reshape(bs, A, K, C).numpy() - d["output_f64"]).max() <= 1e-12 * scale
+    for i, lv in enumerate(ref.table_levels(g_feat, ss, st)):
+        want = d[f"grad_feature_map{i}_f64"]
+        assert np.abs(lv.numpy() - want).max() <= 1e-12 * np.abs(want).max(), i
+    # weights: where the gate is open (the fallback zero-pads the cameras the kernel skips, test_backward_matches_... above)
+    want = d["grad_weights_f64"].transpose(0, 1, 4, 2, 3, 5)                              # [bs, A, K, cams, L, G]
+    gw = g_w.reshape(want.shape).numpy()
+    assert np.abs(gw - want)[vis.numpy()].max() <= 1e-12 * np.abs(want).max() and not gw[~vis.numpy()].any()
+    kp_ = kp.clone().requires_grad_(True)
+    ref.project(kp_, pm, wh)[0].backward(g_loc.reshape(uv.shape))
+    want = d["grad_key_points_f64"]
+    assert np.abs(kp_.grad.numpy() - want).max() <= 1e-10 * np.abs(want).max()
+    touched = ref.touched_rows(ss, st, uv.reshape(bs, A * K, cams, 2).float(), feat.shape[2])
+    assert not g_feat[~touched].any() and touched.float().mean() > 0.2
+    out, _ = ref.block_chunked(kp, pm, wh, feat, ss, st, torch.zeros(bs, A, C, dtype=f64), raw=torch.tensor(d["raw"]), chunk=23)
+    assert np.abs(out.numpy() - d["output_f64"].sum(axis=2)).max() <= 1e-12 * scale

@@ -105,6 +105,52 @@ def assert_grad_rows_close(got, ref, whole=None, what="grad", rtol=GRAD_RTOL):
     return e
 
 
+def daf_row_errors(got, ref, ref32, row_dims, rtol, touched=None, exempt=None):
+    """Row-by-row error record of a deformable-aggregation result against its float64 restatement ``ref``, with the float32 run of
+    the same restatement ``ref32`` as the yardstick of plain float32 arithmetic (torch tensors, any device).  A row is one index of
+    the first ``row_dims`` dimensions.  Row r is bounded by max(rtol * max(max|ref_r|, floor), 4 * max|ref32_r - ref_r|), floor =
+    the median of max|ref_r| over the touched rows.  ``touched`` (bool, one per row; None = every row): the other rows must be
+    exactly 0.  ``exempt`` (bool, one per row): touched rows the bound does not judge (the caller says why)."""
+    import torch
+    R = int(np.prod(ref.shape[:row_dims]))
+    g2, r2, f2 = (t.reshape(R, -1).to(torch.float64) for t in (got, ref, ref32))
+    err = (g2 - r2).abs().amax(dim=1)
+    err32 = (f2 - r2).abs().amax(dim=1)
+    rowmax = r2.abs().amax(dim=1)
+    touched = torch.ones(R, dtype=torch.bool, device=r2.device) if touched is None else touched.reshape(R).to(r2.device)
+    judged = touched if exempt is None else touched & ~exempt.reshape(R).to(r2.device)
+    out = {"rows": R, "touched": int(touched.sum()), "exempt": int((touched & ~judged).sum()),
+           "untouched_nonzero": int(((g2[~touched] != 0).any(dim=1)).sum()) if bool((~touched).any()) else 0,
+           "tensor": float(err.max() / rowmax.max().clamp(min=1e-30)), "ratio": 0.0, "row": -1, "err": 0.0, "bound": 0.0,
+           "rel": 0.0, "term": "-", "fp32_rel": 0.0}
+    if bool(judged.any()):
+        floor = float(rowmax[touched].median().clamp(min=1e-30))
+        scale = rowmax.clamp(min=floor)
+        tol_term, f32_term = rtol * scale, 4.0 * err32
+        bound = torch.maximum(tol_term, f32_term)
+        ratio = torch.where(judged, err / bound.clamp(min=1e-300), torch.zeros_like(err))
+        i = int(ratio.argmax())
+        out.update(floor=floor, ratio=float(ratio[i]), row=i, err=float(err[i]), bound=float(bound[i]),
+                   rel=float((torch.where(judged, err / scale, torch.zeros_like(err))).max()),
+                   fp32_rel=float((torch.where(judged, err32 / scale, torch.zeros_like(err))).max()),
+                   term="fp32" if float(f32_term[i]) > float(tol_term[i]) else f"{rtol:g} x row")
+    return out
+
+
+def assert_daf_rows_close(got, ref, ref32, what, row_dims, rtol=GRAD_RTOL, touched=None, exempt=None):
+    """:func:`daf_row_errors`, asserted and printed (worst row, its bound and the term that set it); returns the record."""
+    assert tuple(got.shape) == tuple(ref.shape) == tuple(ref32.shape), (what, tuple(got.shape), tuple(ref.shape), tuple(ref32.shape))
+    assert bool(got.isfinite().all()), f"{what}: non-finite values"
+    e = daf_row_errors(got, ref, ref32, row_dims, rtol, touched, exempt)
+    print(f"  {what:28s} rows {e['touched']:>9d}/{e['rows']:<9d} worst row {e['row']:>9d}: err {e['err']:.2e} <= bound "
+          f"{e['bound']:.2e} ({e['term']}), ratio {e['ratio']:.3f} | max row err / max(|ref row|, floor) {e['rel']:.2e} "
+          f"(fp32 restatement {e['fp32_rel']:.2e}) | tensor-wide {e['tensor']:.2e} | exempt {e['exempt']}")
+    assert e["untouched_nonzero"] == 0, f"{what}: {e['untouched_nonzero']} rows no visible tap touches are not exactly 0"
+    assert e["ratio"] <= 1.0, (f"{what}: row {e['row']}: err {e['err']:.3e} > bound {e['bound']:.3e} ({e['term']}) "
+                               f"= max({rtol:g} x max(|ref row|, floor {e.get('floor', 0):.3e}), 4 x fp32 restatement's error)")
+    return e
+
+
 def to_dev(dev, *arrays):
     import torch
     return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays]

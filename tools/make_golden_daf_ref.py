@@ -4,7 +4,8 @@ fallback: ``DeformableFeatureAggregation.project_points`` / ``feature_sampling``
 is absent) and the fallback is dead code behind an assert (:119-120), so the three methods are cut out of the
 file with ``ast`` and executed unchanged inside a bare class of the same name.  Build container only.
 
-The fixture holds the inputs, the fallback's output ``[bs, A, K, C]`` and autograd gradients with respect to the
+The fixture holds the inputs (the raw attention logits ``raw [bs, A, cams, L, K, G]`` among them, so that a path that takes the
+logits -- deformable_prepare, the fused ops -- can be run on it), the fallback's output ``[bs, A, K, C]`` and autograd gradients with respect to the
 feature maps, the attention weights and the key points, in fp32 (what the reference would compute) and fp64.
 Weights are masked the way the real forward masks them (:199-224: zero wherever the camera does not see the
 point), because the fallback zero-pads out-of-view cameras while the CUDA kernel skips them.
@@ -86,7 +87,7 @@ for tag, dt in (("f32", torch.float32), ("f64", torch.float64)):
         out["visible"] = visible.numpy()
 
 np.savez_compressed(os.path.join(ROOT, "tests", "golden", "daf_ref.npz"), key_points=key_points, projection_mat=projection_mat,
-                    image_wh=image_wh, grad_output=grad_out, levels=np.array(levels, dtype=np.int32),
+                    image_wh=image_wh, grad_output=grad_out, raw=raw, levels=np.array(levels, dtype=np.int32),
                     **{f"feature_map{i}": f for i, f in enumerate(feature_maps)}, **out)
 print("wrote tests/golden/daf_ref.npz; visible fraction", float(out["visible"].mean()),
       "| max |f32 - f64| of the output", float(np.abs(out["output_f32"] - out["output_f64"]).max()))
