@@ -8,7 +8,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# GF_LIB selects a development variant built by build.build(lib_name=...) (tools/ only)
+# GF_LIB selects an instrumentation build (-DGF_TIMELINE=1, -DGF_DAF_TL) made by build.build(lib_name=...) (tools/ only)
 LIB_PATH = os.environ.get("GF_LIB") or os.path.join(_HERE, "csrc", "libgf_hip.so")
 
 GF_ABI_VERSION = 8
@@ -123,7 +123,7 @@ def check(rc, what):
 
 def set_option(name, value):
     """``gf_set_option``: a process-wide library option (include/gf_hip.h); explicit calls -- the library never reads the
-    environment.  Returns the previous value.  ``dev.*`` names exist in the development build only (tools/)."""
+    environment.  Returns the previous value."""
     lib = load()
     old = ctypes.c_int(0)
     check(lib.gf_get_option(name.encode(), ctypes.addressof(old)), f"gf_get_option({name})")

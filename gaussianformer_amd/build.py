@@ -11,7 +11,7 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_NAME = "libgf_hip.so"
 SOURCES = ["gf_api.hip", "splat_fwd.hip", "splat_bwd.hip", "splat_bwd_mfma.hip", "daf.hip", "gaussian_prepare.hip", "daf_prepare.hip", "daf_fused.hip", "head_labels.hip", "feature_format.hip", "subm_conv.hip", "key_points.hip", "fps.hip", "occ_loss.hip", "lifter.hip"]
-HEADERS = ["gf_common.hpp", "splat_fwd_pair.inc", "splat_fwd_solo.inc", os.path.join("..", "..", "include", "gf_hip.h")]
+HEADERS = ["gf_common.hpp", os.path.join("..", "..", "include", "gf_hip.h")]
 ARCH = "gfx950"
 # -munsafe-fp-atomics only for the translation units that issue float atomics (hardware fp32 adds without a CAS loop); the
 # others are built without it
@@ -37,7 +37,7 @@ def _stale(lib=None):
 
 def build(force=False, verbose=False, extra_flags=(), lib_name=None):
     """Compile every HIP source into one shared library.  Returns its path.
-    ``extra_flags`` / ``lib_name`` build a development variant (e.g. ``-DGF_TIMELINE=1``)
+    ``extra_flags`` / ``lib_name`` build an instrumentation variant (``-DGF_TIMELINE=1``, ``-DGF_DAF_TL``)
     next to the product library without touching it."""
     if lib_name is None and not force and not _stale():
         return lib_path()
@@ -71,21 +71,5 @@ def build(force=False, verbose=False, extra_flags=(), lib_name=None):
     return out_lib
 
 
-DEV_LIB_NAME = "libgf_hip_dev.so"
-
-
-def build_dev(verbose=False, force=True):
-    """The development build tools/ use (``-DGF_DEV=1``: the measured-and-not-kept kernels of earlier rounds and the ``dev.*``
-    options of ``gf_set_option``), next to the product library and never in its place.  Select it with ``GF_LIB=<path>``.
-    ``force=False`` keeps a library that is newer than every source."""
-    dev = os.path.join(CSRC, DEV_LIB_NAME)
-    if not force and not _stale(dev):
-        return dev
-    return build(force=True, verbose=verbose, extra_flags=("-DGF_DEV=1",), lib_name=DEV_LIB_NAME)
-
-
 if __name__ == "__main__":
-    if "--dev" in sys.argv:
-        print(build_dev(verbose=True))
-    else:
-        print(build(force="--force" in sys.argv, verbose=True))
+    print(build(force="--force" in sys.argv, verbose=True))

@@ -1296,13 +1296,13 @@ static int daf_forward_impl(bool pin_groups, int B, int num_cams, int num_feat, 
         const long long npts = (long long)B * num_pts, chunks = (npts + 31) / 32;
         const int chunks_per_sub = (int)((chunks + nsub - 1) / nsub);
         hipLaunchKernelGGL(gf_daf_fwd_grouped_kernel<8>, dim3((unsigned)(8 * chunks_per_sub)), dim3(256), 0, stream, a, chunks_per_sub);
-    } else if (vec == 4 && num_cams <= 8 && C % 8 == 0 && (C / G) % 8 == 0 && !dev_option(kOptDafVec4)) {
+    } else if (vec == 4 && num_cams <= 8 && C % 8 == 0 && (C / G) % 8 == 0) {
         // eight channels per lane (bit-identical: the arithmetic per channel is unchanged): the tap geometry of a (point, camera,
         // level) is computed by every lane of the point, so half the lanes per point is half of that work -- 139 -> 117 us with
         // projected geometry at 230 400 points, where the kernel is bound by vector-ALU issue (uniform locations: unchanged)
         a.total = (long long)B * num_pts * (C / 8);
         hipLaunchKernelGGL(gf_daf_fwd4_kernel<8>, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, stream, a);
-    } else if (vec == 4 && num_cams <= 8 && !dev_option(kOptDafPlain))
+    } else if (vec == 4 && num_cams <= 8)
         hipLaunchKernelGGL(gf_daf_fwd4_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
     else if (vec == 4) hipLaunchKernelGGL(gf_daf_fwd_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
     else if (vec == 2) hipLaunchKernelGGL(gf_daf_fwd_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
@@ -1404,7 +1404,7 @@ extern "C" int gf_daf_backward_sorted(int B, int num_cams, int num_feat, int C, 
     const int lpp = C / 4, lpg = (C / G) / 4;
     // eight channels per lane where the layout allows (both kernels are bound by vector-ALU issue with projected geometry, and
     // the tap geometry is computed by every lane of a point: half the lanes, half of that work per point)
-    const bool vec8 = C % 8 == 0 && (C / G) % 8 == 0 && is_pow2(C / 8) && is_pow2((C / G) / 8) && C / 8 <= 64 && !dev_option(kOptDafVec4);
+    const bool vec8 = C % 8 == 0 && (C / G) % 8 == 0 && is_pow2(C / 8) && is_pow2((C / G) / 8) && C / 8 <= 64;
     if (vec8) {
         a.total = (long long)B * num_pts * (C / 8);
         hipLaunchKernelGGL((gf_daf_bwd_kernel<8, true, false>), dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, stream, a, (C / G) / 8, C / 8);

@@ -32,9 +32,6 @@
 #ifndef GF_FU_CPL
 #define GF_FU_CPL 8      // channels per lane
 #endif
-#ifndef GF_FU_SPLIT
-#define GF_FU_SPLIT 0   // experiment: a lane owns channels [4 cv, 4 cv + 4) and [C/2 + 4 cv, + 4) instead of eight consecutive ones
-#endif
 
 namespace gf {
 
@@ -95,15 +92,8 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
     if (anchor >= nanchor) return;
     const int CV = a.C / CPL;              // lanes per row
     const int sg = lane / CV, cv = lane - sg * CV, nsg = 64 / CV;
-#if GF_FU_SPLIT
-    // (a tap's row as two load instructions of sixteen CONSECUTIVE 16-byte pieces each, instead of two instructions that each touch
-    // every second piece of all four 128-byte lines)
-    const int c0 = cv * 4, c1 = a.C / 2 + cv * 4;
-    const int grp = c0 / (a.C / a.G), grp1 = c1 / (a.C / a.G);
-#else
     const int c0 = cv * CPL;
     const int grp = c0 / (a.C / a.G);
-#endif
     // ---- 1. projection (project_points, deformable_module.py:268-285) and the list of visible pairs
     if (!a.raw)
         for (int i = lane; i < LPG; i += 64) s_anc[i] = a.raw_anchor[anchor * LPG + i];
@@ -180,9 +170,6 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
         // (lane % G == g holds group g's maximum and sum; a sampling lane needs those of ITS channel group: lane grp < G has them)
         const float inv_mine = s > 0.f ? 1.f / s : 0.f;
         const float inv = __shfl(inv_mine, grp, 64), mg = __shfl(m, grp, 64);
-#if GF_FU_SPLIT
-        const float inv1 = __shfl(inv_mine, grp1, 64), mg1 = __shfl(m, grp1, 64);
-#endif
         // ---- 3. sampling: lane group sg takes the visible pairs sg, sg + nsg, ...
         for (int v = sg; v < nvis; v += nsg) {
             const int pc = s_list[v], cam = pc & 255;
@@ -203,24 +190,16 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
                 float v1[CPL], v2[CPL], v3[CPL], v4[CPL];
 #pragma unroll
                 for (int j = 0; j < CPL; j += 4) {
-                    const int jo = GF_FU_SPLIT ? (j ? a.C / 2 : 0) : j;   // (split: the second piece lies C/2 channels further)
-                    *reinterpret_cast<float4 *>(v1 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc0 * w + wc0) * a.C + jo);
-                    *reinterpret_cast<float4 *>(v2 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc0 * w + wc1) * a.C + jo);
-                    *reinterpret_cast<float4 *>(v3 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc0) * a.C + jo);
-                    *reinterpret_cast<float4 *>(v4 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc1) * a.C + jo);
+                    *reinterpret_cast<float4 *>(v1 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc0 * w + wc0) * a.C + j);
+                    *reinterpret_cast<float4 *>(v2 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc0 * w + wc1) * a.C + j);
+                    *reinterpret_cast<float4 *>(v3 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc0) * a.C + j);
+                    *reinterpret_cast<float4 *>(v4 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc1) * a.C + j);
                 }
                 const float wt = kept(pc, l, grp) ? fu_exp(logit_at(pc, l, grp) - mg) * inv : 0.f;
-#if GF_FU_SPLIT
-                const float wt1 = fu_exp(logit_at(pc, l, grp1) - mg1) * inv1;
-#endif
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
                     const float x1 = ok1 ? v1[j] : 0.f, x2 = ok2 ? v2[j] : 0.f, x3 = ok3 ? v3[j] : 0.f, x4 = ok4 ? v4[j] : 0.f;
-#if GF_FU_SPLIT
-                    acc[j] += (w1 * x1 + w2 * x2 + w3 * x3 + w4 * x4) * (j < 4 ? wt : wt1);
-#else
                     acc[j] += (w1 * x1 + w2 * x2 + w3 * x3 + w4 * x4) * wt;
-#endif
                 }
             }
         }
@@ -233,7 +212,7 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
         float *o = a.out + anchor * a.C + c0;
 #pragma unroll
         for (int j = 0; j < CPL; j += 4)
-            *reinterpret_cast<float4 *>(o + (GF_FU_SPLIT ? (j ? a.C / 2 : 0) : j)) = make_float4(acc[j], acc[j + 1], acc[j + 2], acc[j + 3]);
+            *reinterpret_cast<float4 *>(o + j) = make_float4(acc[j], acc[j + 1], acc[j + 2], acc[j + 3]);
     }
 }
 

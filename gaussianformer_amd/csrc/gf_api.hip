@@ -34,13 +34,13 @@ bool profile_slot(hipEvent_t *before, hipEvent_t *after)
 }
 }  // namespace gf
 
-extern "C" int gf_profile_enable(int max_records)
+extern "C" int gf_profile_enable(int max_pairs)
 {
     for (hipEvent_t e : gf::g_events) (void)hipEventDestroy(e);
     gf::g_events.clear();
     gf::g_used = 0;
     gf::g_calls = 0;
-    for (int i = 0; i < 2 * max_records; ++i) {
+    for (int i = 0; i < 2 * max_pairs; ++i) {
         hipEvent_t e;
         if (hipEventCreate(&e) != hipSuccess) {
             gf::set_error("gf_profile_enable: hipEventCreate failed");
@@ -81,12 +81,6 @@ int option(int which) { return which >= 0 && which < kOptCount ? g_options[which
 static const struct { const char *name; int which; } kOptionNames[] = {
     {"splat.mfma_tile_kernel", kOptSplatTileKernel}, {"daf.backward_tiles", kOptDafBackwardTiles}, {"subm.f32_mfma", kOptSubmF32Mfma}, {"subm.tile_gemm", kOptSubmTileGemm}, {"subm.bf16x3", kOptSubmBf16x3},
     {"fps.exhaustive", kOptFpsExhaustive},
-#if GF_DEV
-    {"dev.splat_pair", kOptSplatPair}, {"dev.splat_solo", kOptSplatSolo}, {"dev.splat_solo_waves", kOptSplatSoloWaves},
-    {"dev.splat_fused", kOptSplatFused}, {"dev.splat_fused_why", kOptSplatFusedWhy}, {"dev.units_bands", kOptUnitsBands},
-    {"dev.prep_waves", kOptPrepWaves}, {"dev.bwd_no_lists", kOptBwdNoLists}, {"dev.bwd_no_big", kOptBwdNoBig},
-    {"dev.daf_vec4", kOptDafVec4}, {"dev.daf_plain", kOptDafPlain},
-#endif
 };
 static int option_index(const char *name)
 {
@@ -119,7 +113,8 @@ extern "C" int gf_get_option(const char *name, int *value)
     return GF_OK;
 }
 
-extern "C" int gf_is_development_build(void) { return GF_DEV ? 1 : 0; }
+// (ABI 8: there was a development build until a5ba306; the library is always the product now)
+extern "C" int gf_is_development_build(void) { return 0; }
 
 extern "C" int gf_abi_version(void) { return GF_ABI_VERSION; }
 extern "C" const char *gf_last_error(void) { return gf::g_err; }

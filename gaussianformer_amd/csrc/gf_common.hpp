@@ -6,11 +6,6 @@
 
 #include "../../include/gf_hip.h"
 
-#ifndef GF_DEV
-#define GF_DEV 0   // -DGF_DEV=1: the development build tools/ use (libgf_hip_dev.so): measured-and-not-kept kernels (pair, solo, fused
-                   // forward), comparison mappings and the development options of gf_set_option.  The product build holds none of them.
-#endif
-
 namespace gf {
 
 // ---- library options (gf_set_option, include/gf_hip.h): explicit calls, never the environment -- the library does not call getenv
@@ -21,18 +16,9 @@ enum Option {
     kOptSubmTileGemm,          // "subm.tile_gemm": gf_subm_conv_apply's gather-GEMM with one tile per workgroup also where runs of tiles apply
     kOptSubmBf16x3,            // "subm.bf16x3": gf_subm_conv_apply_scratch on the three-term bf16 split (six products) instead of two f16 terms (three)
     kOptFpsExhaustive,         // "fps.exhaustive": gf_farthest_point_sampling updates every bucket on every pick (no pruning; same bits)
-    kOptProductCount,
-    // development build only (GF_DEV)
-    kOptSplatPair = kOptProductCount, kOptSplatSolo, kOptSplatSoloWaves, kOptSplatFused, kOptSplatFusedWhy, kOptUnitsBands, kOptPrepWaves,
-    kOptBwdNoLists, kOptBwdNoBig, kOptDafVec4, kOptDafPlain,
     kOptCount
 };
 int option(int which);           // gf_api.hip; 0 unless set
-#if GF_DEV
-inline int dev_option(int which) { return option(which); }
-#else
-constexpr int dev_option(int) { return 0; }   // (constant: the code behind a development option is not even compiled in)
-#endif
 
 // ---- geometry constants -------------------------------------------------------------
 constexpr int kC = GF_NUM_CHANNELS;  // 18 semantic channels
@@ -52,8 +38,6 @@ constexpr int kBwdList = 256;       // candidate-list entries of the matrix-core
 constexpr int kBwdPubLong = 896;    // ... entries of a list the forward's long-row instantiation publishes (its whole one-pass list; the backward
                                     // takes it in pieces of kBwdList)
 constexpr int kListsBad = 8101;      // flag-section word: a supertile's list did not fit kBwdList (the backward then scans the bitmask rows itself)
-constexpr int kFusedCounters = 6144; // flag-section index of the fused forward's per-XCD counter blocks ([+ 128 x] dwords = 64 64-bit words each)
-constexpr int kFusedRowMax = 1024;   // bitmask row words up to which a workspace carries the fused forward's per-XCD copies
 constexpr int kVerdictWords = 8104;  // flag-section index (16-byte aligned) of the single-word verdict block [A, B, V0, V1] of a workspace that was
                                      // handed over zeroed (GF_WORKSPACE_ZEROED; splat_fwd.hip, "one verdict word")
 constexpr int kGenWord = 8100;       // generation word of a workspace: index into its flag section -- the same word whatever the call's
@@ -101,10 +85,6 @@ struct SplatWorkspace {
     uint32_t *bwd_list_len;    // [nsuper] ... its length
     float *bwd_rows;        // [bwd_cap][32] matrix-core backward: partial gradients per (Gaussian, double brick)
     uint32_t bwd_cap;       // rows available (0: the shape does not take the matrix-core backward)
-    float *x_records;       // [8][P][32] fused single-launch forward (round 5): every XCD's own copy of the records ...
-    uint2 *x_boxes;         // [8][P] ... of the packed boxes ...
-    unsigned long long *x_bitmask;  // [8][nsuper][nrow] ... and of the bitmask (each XCD fills the rows of its own supertiles); null: shape not taken
-    unsigned long long *x_flags;    // [8][2][kFusedRowMax] ... per XCD and pass, one "done" word per 64 Gaussians, tagged with the launch id
     int nwords, nrow, nsx, nsy, nsuper;
     size_t total_bytes;
 };
@@ -155,15 +135,6 @@ inline SplatWorkspace carve_workspace(void *base, int P, int N, int H, int W, in
     ws.bwd_lists = (uint32_t *)(p + off); off += align256((size_t)(ws.bwd_cap ? ws.nsuper : 0) * 3 * ws.bwd_pub * 4);
     ws.bwd_list_len = (uint32_t *)(p + off); off += align256((size_t)(ws.bwd_cap ? ws.nsuper : 0) * 4);
     ws.bwd_rows = (float *)(p + off); off += align256((size_t)ws.bwd_cap * kBwdRowDwords * 4);
-    {
-        // (the fused single-launch forward -- measured, not kept: DESIGN.md section 3.2c -- exists in the development build only;
-        // the product's workspace carries none of its per-XCD copies)
-        const bool fused_ok = GF_DEV && P > 0 && P < 65536 && ws.nrow <= kFusedRowMax;
-        ws.x_records = fused_ok ? (float *)(p + off) : nullptr; off += align256(fused_ok ? (size_t)8 * P * kRecDwords * 4 : 0);
-        ws.x_boxes = fused_ok ? (uint2 *)(p + off) : nullptr; off += align256(fused_ok ? (size_t)8 * P * 8 : 0);
-        ws.x_bitmask = fused_ok ? (unsigned long long *)(p + off) : nullptr; off += align256(fused_ok ? (size_t)8 * ws.nsuper * ws.nrow * 8 : 0);
-        ws.x_flags = fused_ok ? (unsigned long long *)(p + off) : nullptr; off += align256(fused_ok ? (size_t)8 * 2 * kFusedRowMax * 8 : 0);
-    }
     ws.total_bytes = off;
     return ws;
 }

@@ -43,10 +43,6 @@
 
 #include "gf_common.hpp"
 
-#ifndef GF_XB
-#define GF_XB 0   // development, timing experiments only (wrong results): 1 = every row store goes to row 0 (same instructions, no scatter),
-                  // 4 = the four blocks of a group compiled out
-#endif
 #ifndef GF_TIMELINE
 #define GF_TIMELINE 0  // -DGF_TIMELINE=1: per-unit timestamps of the gradient kernel (tools/timeline_bwd.py)
 #endif
@@ -281,7 +277,7 @@ __device__ __forceinline__ void zero_big_gaussians(const BwdMArgs &a, int lane)
 // no longer holds the forward's lists, falls back to the chunked fill below, which reads the row's words from global memory (correct
 // for any row length; ~1 us per 64 words).  Same groups in the same order as the short-row instantiation would form: the arithmetic
 // per (Gaussian, double brick) does not depend on how the list was delivered.
-template <bool INTER, bool LONG = false>   // INTER: supertiles dealt to the XCDs round-robin (default) or in contiguous bands: see gf_splat_render_mfma_wave_kernel
+template <bool LONG = false>   // supertiles dealt to the XCDs round-robin, as in gf_splat_render_mfma_wave_kernel
 __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_u[kMLdsDwords];
@@ -309,8 +305,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
     typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
     const int xcd = (int)(blockIdx.x & 7u);
     const int per_super = 4 * ((a.D + 7) >> 3);
-    const int nunits = a.nsx * a.nsy * per_super;
-    const int per_xcd = INTER ? ((a.nsx * a.nsy + 7) >> 3) * per_super : (nunits + 7) >> 3;
+    const int per_xcd = ((a.nsx * a.nsy + 7) >> 3) * per_super;
     const uint32_t m_ps = a.m_ps, m_nsy = a.m_nsy;
     using gptr = const __attribute__((address_space(1))) void *;
     using lptr = __attribute__((address_space(3))) void *;
@@ -392,11 +387,11 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
     const int nchunk = (a.nwords + 63) >> 6;
     int local = (int)(blockIdx.x >> 3);
     while (true) {  // units of this wave
-        const int logical = INTER ? local : xcd * per_xcd + local;
+        const int logical = local;
         const int qs = (int)__umulhi((uint32_t)logical, m_ps);
-        if (!(local < per_xcd && (INTER ? 8 * qs + xcd < a.nsx * a.nsy : logical < nunits))) break;
+        if (!(local < per_xcd && 8 * qs + xcd < a.nsx * a.nsy)) break;
         uint32_t claimed = 0u;
-        const int s = INTER ? 8 * qs + xcd : qs, r = logical - qs * per_super;
+        const int s = 8 * qs + xcd, r = logical - qs * per_super;
         const int srow = a.nsy == 1 ? s : (int)__umulhi((uint32_t)s, m_nsy), scol = s - srow * a.nsy;
         const int Xw = srow * kSuper + 4 * (r & 1), Y0 = scol * kSuper + 4 * ((r >> 1) & 1), Zw = 8 * (r >> 2);
         if (Xw < a.H && Y0 < a.W) {
@@ -864,7 +859,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
 #pragma unroll
                         for (int q = 0; q < 16; ++q) { mom[q] = 0.f; dsm[q] = 0.f; }
 #pragma unroll
-                        for (int b = 0; b < ((GF_XB & 4) ? 0 : 4); ++b) {
+                        for (int b = 0; b < 4; ++b) {
                             // one-hot operand of this block: half 0 takes set b & 1, half 1 set b >> 1 (selected register by register:
                             // indexing the two sets with a per-lane index sends them through scratch memory)
                             typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -980,7 +975,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
                             if (has_row) {
                                 // SIX store instructions per group, whatever the lanes hold (the counted wait above relies on it):
                                 // two that both halves take part in, four of half 0
-                                float4 *row = reinterpret_cast<float4 *>(a.rows + ((GF_XB & 1) ? (size_t)0 : (size_t)first + (size_t)idx) * kBwdRowDwords);
+                                float4 *row = reinterpret_cast<float4 *>(a.rows + ((size_t)first + (size_t)idx) * kBwdRowDwords);
                                 row[h] = make_float4(o[0], o[1], o[2], o[3]);
                                 row[2 + h] = make_float4(o[4], o[5], o[6], o[7]);
                                 if (h == 0) {
@@ -1308,7 +1303,7 @@ void launch_splat_backward_mfma(int radii_per_axis, int P, int N, int H, int W, 
     a.means_grad = means_grad; a.opa_grad = opa_grad; a.sem_grad = sem_grad; a.cov_grad = cov_grad; a.state = state;
     a.tile_counters = ws.flags + kBwdCounters; a.gen_word = gen_word; a.row_first = ws.bwd_row_first; a.wave_total = ws.bwd_wave_total;
     a.big_table = ws.bwd_wave_total + kBwdBigTableAt;
-    a.lists = dev_option(kOptBwdNoLists) ? nullptr : ws.bwd_lists; a.list_len = ws.bwd_list_len; a.lists_bad = ws.flags + kListsBad;
+    a.lists = ws.bwd_lists; a.list_len = ws.bwd_list_len; a.lists_bad = ws.flags + kListsBad;
     a.P = P; a.N = N; a.nwords = ws.nwords; a.nrow = ws.nrow; a.H = H; a.W = W; a.D = D; a.nsx = ws.nsx; a.nsy = ws.nsy;
     a.gate = gate ? 1 : 0; a.records_asserted = records_asserted;
     a.timeline = g_bwd_timeline;
@@ -1318,15 +1313,11 @@ void launch_splat_backward_mfma(int radii_per_axis, int P, int N, int H, int W, 
         a.m_ps = (uint32_t)(((1ull << 32) + per_super - 1) / per_super);
         a.m_nsy = (uint32_t)(((1ull << 32) + (unsigned)ws.nsy - 1) / (unsigned)ws.nsy);
     }
-#if GF_DEV
-    if (dev_option(kOptUnitsBands)) hipLaunchKernelGGL(gf_splat_bwd_mfma_kernel<false>, dim3(grid), dim3(64), 0, stream, a);   // (comparison: rounds 3, 4)
-    else
-#endif
-    if (ws.nrow > kWRow) hipLaunchKernelGGL((gf_splat_bwd_mfma_kernel<true, true>), dim3(grid), dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL(gf_splat_bwd_mfma_kernel<true>, dim3(grid), dim3(64), 0, stream, a);
+    if (ws.nrow > kWRow) hipLaunchKernelGGL(gf_splat_bwd_mfma_kernel<true>, dim3(grid), dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL(gf_splat_bwd_mfma_kernel<false>, dim3(grid), dim3(64), 0, stream, a);
     BwdRowsArgs r{ws.records, ws.bwd_rows, means_grad, opa_grad, sem_grad, cov_grad, ws.bwd_wave_total, ws.bwd_row_first, gen_word,
                   ws.bwd_wave_total + kBwdBigTableAt, ws.flags + kBwdCounters, state, (uint32_t)(grid / 8), P, gate, (P + 31) / 32, records_asserted};
-    hipLaunchKernelGGL(gf_splat_bwd_rows_kernel, dim3(r.ngauss_blocks + (dev_option(kOptBwdNoBig) ? 0 : 256)), dim3(256), 0, stream, r);
+    hipLaunchKernelGGL(gf_splat_bwd_rows_kernel, dim3(r.ngauss_blocks + 256), dim3(256), 0, stream, r);
 }
 
 }  // namespace gf

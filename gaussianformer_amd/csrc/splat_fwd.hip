@@ -26,30 +26,11 @@
 //      arbitrary-points body instead (one lane per point).
 //   3. gf_splat_render_general_kernel   arbitrary query points when N != H*W*D.
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 
 #include "gf_common.hpp"
 
 #ifndef GF_TIMELINE
 #define GF_TIMELINE 0  // -DGF_TIMELINE=1: per-workgroup timestamps of the render kernel (tools/timeline.py)
-#endif
-#ifndef GF_X
-#define GF_X 0   // development: timing experiments in the solo kernel (tools/xbuild.sh); 0 in the product
-#endif
-#ifndef GF_VD1
-#define GF_VD1 1   // one verdict word on GF_WORKSPACE_ZEROED workspaces (gf_splat_prep_kernel); 0: every render wave reads every verdict word
-#endif
-#ifndef GF_PHITAB
-#define GF_PHITAB 1   // wave kernel: the exponent MFMAs' B operands from a compile-time table (kPhiHot) instead of 235 VALU per wave
-#endif
-#ifndef GF_STATIC2
-#define GF_STATIC2 0   // experiment (VERDICT r5 #3b): every wave of the wave kernel takes its SECOND unit statically too (unit local + waves per
-                       // XCD) and only claims from the third on; measured in round 6, see DESIGN.md section 3.2d
-#endif
-#ifndef GF_XP
-#define GF_XP 0   // development: parts of the records pass compiled out (timing experiments only: 1 bitmask stores, 2 record
-                  // stores, 4 LDS atomics, 8 verification waves, 16 records waves)
 #endif
 
 namespace gf {
@@ -134,19 +115,10 @@ __device__ __forceinline__ uint32_t range_bits_of(const float *c, const float *s
     bool snan = false;
 #pragma unroll
     for (int j = 0; j < kC; ++j) {
-#if GF_DEV
-        // (the pair / solo kernels of the development build carry the opacity in the exponent and the RAW semantics as S': both
-        // magnitudes are bounded there)
-        const float v = fmaxf(fabsf(opa * sm[j]), fabsf(sm[j]));
-#else
         const float v = fabsf(opa * sm[j]);
-#endif
         snan |= !(v == v);
         smax = fmaxf(smax, v);
     }
-#if GF_DEV
-    snan |= !(opa >= 0.f);   // (pair / solo kernels: log2(opacity) in the exponent: a negative (or NaN) opacity takes the fall-back)
-#endif
     return ((!(bound < 3.0e4f) || !(Q < 1331.4f)) ? 4u : 0u) | ((snan || !(smax < kSemRangeMax)) ? 8u : 0u);
 }
 
@@ -179,8 +151,6 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
         if (WAVES > 1) __syncthreads();
         else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // single wave: LDS ops stay ordered
     };
-    if (GF_XP & 8) { if ((int)blockIdx.x >= a.nprep_blocks) return; }
-    if (GF_XP & 16) { if ((int)blockIdx.x < a.nprep_blocks) return; }
     if ((int)blockIdx.x >= a.nprep_blocks) {
         // ---- verification role: is point n in voxel n for all n?  Each wave reports its own
         // slice unconditionally (no zero-initialised flag needed).
@@ -412,7 +382,7 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
         // ---- records, small P: each lane loads and stores its own Gaussian (strided, but one
         // memory round trip; the staged variant below costs two more and measured 2 us slower
         // at P = 25 601, where the kernel is latency-bound)
-        if (valid && !(GF_XP & 2)) {
+        if (valid) {
             const uint32_t plo = pack3(lo[0], lo[1], lo[2]);
             const uint32_t phi = nonempty ? pack3(hi[0], hi[1], hi[2]) : plo;
             a.boxes[g] = make_uint2(plo, phi);
@@ -560,7 +530,7 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
         }
         wg_sync();
         // small footprints: each lane ORs its own bit (order-independent => deterministic)
-        if (npairs > 0 && npairs <= 16 && !(GF_XP & 4)) {
+        if (npairs > 0 && npairs <= 16) {
             for (int sx = sx_lo; sx <= sx_hi; ++sx)
                 for (int sy = sy_lo; sy <= sy_hi; ++sy) {
                     const int s = sx * a.nsy + sy - s0;
@@ -584,7 +554,7 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
         for (int i = threadIdx.x; i < ns * WAVES; i += 64 * WAVES) {
             const int si = i / WAVES, w = i - si * WAVES;
             unsigned long long bits = 0ull;
-            if ((int)blockIdx.x * WAVES + w < a.nwords && !(GF_XP & 1)) {
+            if ((int)blockIdx.x * WAVES + w < a.nwords) {
                 bits = s_bits[i];
                 a.bitmask[(size_t)(s0 + si) * a.nrow + blockIdx.x * WAVES + w] = bits;
             }
@@ -614,7 +584,6 @@ struct RenderArgs {
     unsigned long long *timeline;  // debug: 4 timestamps per workgroup (null = off)
     const int *tile_perm;          // debug (GF_TIMELINE builds): workgroup -> logical tile, for scheduling experiments
     int P, N, nwords, nrow, H, W, D, nsx, nsy, ntiles_total, verify_dense;
-    int bands;   // exact tile kernel: 1 = tiles dealt to the XCDs in contiguous bands (rounds 1 - 4; GF_UNITS_BANDS=1), 0 = by supertile, round-robin
     // optional head epilogue (gf_splat_forward_labels): labels straight from the accumulators
     long long *out_labels;  // null = off
     int label_mode, empty_label;
@@ -1028,9 +997,7 @@ __global__ __launch_bounds__(kBlock, kRenderWavesPerSimd) void gf_splat_render_k
     // tile of this workgroup.  XCD-aware order: the tiles of a supertile stay on one XCD (workgroup b runs on XCD b % 8) so its L2
     // keeps that supertile's bitmask, boxes and records; the supertiles are dealt to the XCDs round-robin (round 5: in contiguous
     // bands the XCDs of the middle of the grid carried several times the work of the outer ones when the Gaussians cluster there).
-    const int per_xcd = (int)(gridDim.x >> 3);
-    int logical = a.bands ? (int)(blockIdx.x & 7u) * per_xcd + (int)(blockIdx.x >> 3)
-                          : (8 * ((int)(blockIdx.x >> 3) / kTilesPerSuper) + (int)(blockIdx.x & 7u)) * kTilesPerSuper + (int)(blockIdx.x >> 3) % kTilesPerSuper;
+    int logical = (8 * ((int)(blockIdx.x >> 3) / kTilesPerSuper) + (int)(blockIdx.x & 7u)) * kTilesPerSuper + (int)(blockIdx.x >> 3) % kTilesPerSuper;
 #if GF_TIMELINE
     if (a.tile_perm) logical = a.tile_perm[blockIdx.x];
 #endif
@@ -1362,7 +1329,7 @@ __device__ __forceinline__ void lds_dma4(const __attribute__((address_space(1)))
 {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(g), "s"((uint32_t)(uintptr_t)l) : "memory", "m0");
 }
-template <bool LABELS, bool INTER = true>   // INTER: supertiles dealt to the XCDs round-robin (see gf_splat_render_mfma_wave_kernel)
+template <bool LABELS>
 __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderArgs a)
 {
     // the output staging area is NOT aliased onto the list here (two workgroups per CU leave the LDS for it): a wave that
@@ -1384,9 +1351,9 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
     // the following ones come from a per-XCD counter (initialised by the prep kernel), claimed late in the current tile.
     __shared__ int s_next;
     const int xcd = (int)(blockIdx.x & 7u);
-    // logical tiles per XCD: an eighth of the tiles in one contiguous band (the last XCD's tail may be short), or -- INTER -- the
-    // tiles of every eighth supertile
-    const int per_xcd = INTER ? ((a.nsx * a.nsy + 7) >> 3) * kTilesPerSuper : (a.ntiles_total + 7) >> 3;
+    // logical tiles per XCD: the tiles of every eighth supertile (supertiles dealt to the XCDs round-robin, see
+    // gf_splat_render_mfma_wave_kernel)
+    const int per_xcd = ((a.nsx * a.nsy + 7) >> 3) * kTilesPerSuper;
 
     // The prep launch's verdict words (point scans: 4 x 16 bytes per thread) and the records pass's range verdicts (four clamped
     // 16-byte reads per thread: 4 096 words, P <= 262 144; longer rows add a loop) in ONE round trip: all eight loads are
@@ -1413,11 +1380,11 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
         }
     }
     int local = (int)(blockIdx.x >> 3);
-    int logical = INTER ? local : xcd * per_xcd + local;
-    int s = INTER ? 8 * (logical / kTilesPerSuper) + xcd : logical / kTilesPerSuper, t = logical % kTilesPerSuper;
+    int logical = local;
+    int s = 8 * (logical / kTilesPerSuper) + xcd, t = logical % kTilesPerSuper;
     int X0 = (s / a.nsy) * kSuper;
     int Y0 = (s % a.nsy) * kSuper + t * kTileY;
-    bool tile_ok = local < per_xcd && (INTER ? s < a.nsx * a.nsy : logical < a.ntiles_total) && X0 < a.H && Y0 < a.W;
+    bool tile_ok = local < per_xcd && s < a.nsx * a.nsy && X0 < a.H && Y0 < a.W;
     const unsigned long long *__restrict__ bm = a.bitmask + (size_t)(tile_ok ? s : 0) * a.nrow;
 
     // verdicts of the prep launch: bit 0 = a point is not in its voxel, bit 1 = pts is not an exact affine lattice,
@@ -1944,11 +1911,11 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     next_local = s_next;
     local = next_local;
-    logical = INTER ? local : xcd * per_xcd + local;
-    s = INTER ? 8 * (logical / kTilesPerSuper) + xcd : logical / kTilesPerSuper; t = logical % kTilesPerSuper;
+    logical = local;
+    s = 8 * (logical / kTilesPerSuper) + xcd; t = logical % kTilesPerSuper;
     X0 = (s / a.nsy) * kSuper;
     Y0 = (s % a.nsy) * kSuper + t * kTileY;
-    if (!(local < per_xcd && (INTER ? s < a.nsx * a.nsy : logical < a.ntiles_total))) break;  // workgroup-uniform
+    if (!(local < per_xcd && s < a.nsx * a.nsy)) break;  // workgroup-uniform
     bm = a.bitmask + (size_t)s * a.nrow;
     // the slowest wave is done with the list and the scan scratch.  LDS ordering only: a full __syncthreads() also waits
     // (vmcnt) for the output stores just issued to be acknowledged
@@ -2023,8 +1990,8 @@ static_assert(2 * 64 * kC <= 1536 + 3 * kWList, "output staging fits over the sl
 // default kernel's code is unchanged.
 // PREP: the GF_PREPARE_BACKWARD variant (row layout + published candidate lists) -- an instantiation of its own, so that the plain
 // forward keeps its code and register allocation (as one kernel the extra paths cost it 0.8 us per step: 31 more spilled SGPRs).
-// INTER (the default since round 5): supertiles dealt to the XCDs round-robin (supertile s on XCD s % 8) instead of in eight
-// contiguous bands of units (INTER = false, GF_UNITS_BANDS=1 for comparison).  With Gaussians clustered in the middle of the grid
+// Supertiles are dealt to the XCDs round-robin (supertile s on XCD s % 8; since round 5) instead of in eight contiguous bands of
+// units (rounds 3 and 4).  With Gaussians clustered in the middle of the grid
 // -- what a trained model produces -- the bands of the middle XCDs hold several times the work of the outer ones and nothing moves
 // work between XCDs: 61.1 us per step at gs25600 with sigmoid(N(0,1)) centres; dealt round-robin every XCD sees the same density:
 // 48.1 us.  The locality given up (a Gaussian's record is fetched by as many XCDs as it has neighbouring supertiles) does not
@@ -2049,7 +2016,7 @@ constexpr int kLSumAt = 3968;   // dword offset of the summary row: [15872, 1689
 static_assert(kLSumAt == 1536 + 3 * kLIds - 64 * 4, "the summary row is the tail of box hi (LDS map above)");
 static_assert(kLSumAt < kLongWords, "finish_row_layout_long's prefix reaches the summary row: the first unit re-fetches it past kLSumAt words");
 static_assert(kLongWords <= 64 * 64, "one summary bit per word, 64 per lane");
-template <bool LABELS, bool PREP = false, bool INTER = true, bool LONG = false>
+template <bool LABELS, bool PREP = false, bool LONG = false>
 __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(RenderArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_u[kWLdsDwords];
@@ -2065,8 +2032,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     const int lane = threadIdx.x;
     const int xcd = (int)(blockIdx.x & 7u);
     const int per_super = 4 * ((a.D + 7) >> 3);          // units of a supertile: 2 x 2 column quarters x z bricks
-    const int nunits = a.nsx * a.nsy * per_super;
-    const int per_xcd = INTER ? ((a.nsx * a.nsy + 7) >> 3) * per_super : (nunits + 7) >> 3;
+    const int per_xcd = ((a.nsx * a.nsy + 7) >> 3) * per_super;
 
     // unit index -> (supertile, quarter, z brick) -> supertile row and column: divisions by launch constants, as multiplications
     // by rounded-up reciprocals (exact for the < 2^20 indices of a grid)
@@ -2078,10 +2044,9 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     // The first unit's bitmask row is requested before anything else: its round trip then runs under the verdict loads and the
     // set-up below instead of behind them (a failed verdict wastes one LDS-DMA).
     {
-        const int logical = INTER ? local : xcd * per_xcd + local;
-        const int q0 = (int)__umulhi((uint32_t)logical, m_ps);
-        if (local < per_xcd && (INTER ? 8 * q0 + xcd < a.nsx * a.nsy : logical < nunits)) {
-            const int s0 = INTER ? 8 * q0 + xcd : q0, r0 = logical - q0 * per_super;
+        const int q0 = (int)__umulhi((uint32_t)local, m_ps);
+        if (local < per_xcd && 8 * q0 + xcd < a.nsx * a.nsy) {
+            const int s0 = 8 * q0 + xcd, r0 = local - q0 * per_super;
             const int srow0 = a.nsy == 1 ? s0 : (int)__umulhi((uint32_t)s0, m_nsy), scol0 = s0 - srow0 * a.nsy;
             if (srow0 * kSuper + 4 * (r0 & 1) < a.H && scol0 * kSuper + 4 * ((r0 >> 1) & 1) < a.W) {
                 if (LONG) {
@@ -2112,14 +2077,12 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                      : "v"(pp), "v"(pp + ix), "v"(pp + iy), "v"(pp + iz)
                      : "memory");
     }
-#if GF_PHITAB
     uint4 phihot_raw[8];
     {
         const uint4 *tp = reinterpret_cast<const uint4 *>(&kPhiHot.w[0][0][0]) + lane;
 #pragma unroll
         for (int k = 0; k < 8; ++k) phihot_raw[k] = tp[64 * k];
     }
-#endif
     // verdicts of the prep launch (see gf_splat_render_mfma_kernel): the point scans' (GF_PTS_AUTO) and the records pass's range
     // verdicts (every call, GF_PTS_ASSUME_DENSE included).  All loads first, then the ballots: ONE memory round trip.  (The range
     // words: three clamped 16-byte reads per lane cover the <= 618 + 4 words of the rows this kernel takes -- no loop: as a loop
@@ -2191,27 +2154,11 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
 
     // B operands of the exponent MFMAs: monomials and one-hot coordinates of this lane's voxel in each of the four blocks (kPhiHot)
     h8 phi[4], hot[4];
-#if GF_PHITAB
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
         phi[b] = __builtin_bit_cast(h8, phihot_raw[b]);
         hot[b] = __builtin_bit_cast(h8, phihot_raw[4 + b]);
     }
-#else
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        const float ux_ = (float)(2 * (b & 1) + (n >> 4)) - 1.5f, uy_ = (float)((n >> 2) & 3) - 1.5f,
-                    uz_ = (float)(4 * (b >> 1) + (n & 3)) - 3.5f;
-        const float m0[8] = {1.f, ux_, uy_, uz_, ux_ * ux_, 0.f, 0.f, 0.f};
-        const float m1[8] = {uy_ * uy_, uz_ * uz_, ux_ * uy_, uy_ * uz_, ux_ * uz_, 0.f, 0.f, 0.f};
-        const int lx = 2 * (b & 1) + (n >> 4), ly = (n >> 2) & 3, zz = 4 * (b >> 1) + (n & 3);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            phi[b][j] = (_Float16)(h ? m1[j] : m0[j]);
-            hot[b][j] = (_Float16)((h ? zz == j : (j < 4 ? lx == j : ly == j - 4)) ? 1.f : 0.f);
-        }
-    }
-#endif
 
     auto request_records_at = [&](int qh, int start, int count) {
         const uint32_t id = q_id[(qh + start + (n < count ? n : 0)) & (kQCap - 1)];
@@ -2233,11 +2180,10 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     // by itself -- so rows that do not fit s_row stay with the tile kernel.)
     const int nchunk = (a.nwords + 63) >> 6;
     int nst_prev = 0;        // ... and this many store instructions were issued after that request
-    bool first_unit = true;
     while (true) {  // units of this wave
-        const int logical = INTER ? local : xcd * per_xcd + local;
+        const int logical = local;
         const int qs = (int)__umulhi((uint32_t)logical, m_ps);
-        if (!(local < per_xcd && (INTER ? 8 * qs + xcd < a.nsx * a.nsy : logical < nunits))) break;
+        if (!(local < per_xcd && 8 * qs + xcd < a.nsx * a.nsy)) break;
         bool next_row = false;
         int nst = -1;
         // The next unit is claimed first thing (workgroup scope: the counter of XCD x is only touched by workgroups running on
@@ -2245,7 +2191,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
         // divergent block that issued it).  The answer is waited for together with the bitmask row.
         uint32_t claimed = 0u;
         bool have_next = false;
-        const int s = INTER ? 8 * qs + xcd : qs, r = logical - qs * per_super;
+        const int s = 8 * qs + xcd, r = logical - qs * per_super;
         const int srow = a.nsy == 1 ? s : (int)__umulhi((uint32_t)s, m_nsy), scol = s - srow * a.nsy;   // (2^32 / 1 does not fit)
         const int Xw = srow * kSuper + 4 * (r & 1), Y0 = scol * kSuper + 4 * ((r >> 1) & 1), Zw = 8 * (r >> 2);
         if (Xw < a.H && Y0 < a.W) {
@@ -2614,7 +2560,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         // the unit's last group: NOW the next unit is claimed -- as late as its round trip can still hide (under
                         // this group's blocks): a unit claimed early is a unit no idle wave can take at the end of the launch
                         const bool last_group = final_batch && nnext == 0;
-                        if (last_group && lane == 0 && !(GF_STATIC2 && first_unit))
+                        if (last_group && lane == 0)
                             asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(claimed) : "v"(ctr), "v"(1u) : "memory");
                         {
                             // S' rows 8 h .. 8 h + 9 of column n: one instruction stream for both half-lanes (10 products and stores
@@ -2736,16 +2682,15 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
             tl[5] = wall_clock64();
 #endif
             // ---- the next unit (claimed during the last group) and its bitmask row: requested now, it travels under the epilogue
-            if (!have_next && lane == 0 && !(GF_STATIC2 && first_unit))   // a unit without a single hit
+            if (!have_next && lane == 0)   // a unit without a single hit
                 asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(claimed) : "v"(ctr), "v"(1u) : "memory");
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(claimed)::"memory");
-            if (GF_STATIC2 && first_unit) claimed = (uint32_t)local + (gridDim.x >> 3);
             have_next = true;
             {
-                const int nl = __builtin_amdgcn_readfirstlane((int)claimed), nlog = INTER ? nl : xcd * per_xcd + nl;
-                const int q2 = (int)__umulhi((uint32_t)nlog, m_ps);
-                if (nl < per_xcd && (INTER ? 8 * q2 + xcd < a.nsx * a.nsy : nlog < nunits)) {
-                    const int s2 = INTER ? 8 * q2 + xcd : q2, r2 = nlog - q2 * per_super;
+                const int nl = __builtin_amdgcn_readfirstlane((int)claimed);
+                const int q2 = (int)__umulhi((uint32_t)nl, m_ps);
+                if (nl < per_xcd && 8 * q2 + xcd < a.nsx * a.nsy) {
+                    const int s2 = 8 * q2 + xcd, r2 = nl - q2 * per_super;
                     const int srow2 = a.nsy == 1 ? s2 : (int)__umulhi((uint32_t)s2, m_nsy), scol2 = s2 - srow2 * a.nsy;
                     if (srow2 * kSuper + 4 * (r2 & 1) < a.H && scol2 * kSuper + 4 * ((r2 >> 1) & 1) < a.W) {
                         if (LONG) {
@@ -2879,14 +2824,12 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
 #endif
         }
         if (!have_next) {   // a unit outside the grid
-            if (lane == 0 && !(GF_STATIC2 && first_unit)) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(claimed) : "v"(ctr), "v"(1u) : "memory");
+            if (lane == 0) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(claimed) : "v"(ctr), "v"(1u) : "memory");
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(claimed)::"memory");
-            if (GF_STATIC2 && first_unit) claimed = (uint32_t)local + (gridDim.x >> 3);
         }
         local = __builtin_amdgcn_readfirstlane((int)claimed);
         row_there = next_row;
         nst_prev = nst;
-        first_unit = false;
     }
 }
 
@@ -2902,13 +2845,6 @@ static int mfma_wave_grid(int nunits)
     const int per_xcd = (nunits + 7) / 8;
     return 8 * std::min(per_xcd, std::max(1, 8 * cus / 8));
 }
-
-#if GF_DEV
-// (round 5: the pair, solo and fused kernels -- measured, correct, not faster than the wave kernel: DESIGN.md section 3.2c.  Development
-// build only, selected there with gf_set_option("dev.splat_pair" / "dev.splat_solo" / "dev.splat_fused", 1); the product holds none of them.)
-#include "splat_fwd_pair.inc"
-#include "splat_fwd_solo.inc"
-#endif
 
 // ---------------------------------------------------------------------------------------
 struct BoxVolArgs {
@@ -2965,38 +2901,20 @@ static bool mfma_by_wave(int nrow)
 // wave can read at its start); anything else stays with the tile kernel
 static bool mfma_by_wave_long(int nrow, int nwords, int flags)
 {
-    return GF_VD1 && nrow > kWRow && nwords <= kLongWords && (flags & GF_WORKSPACE_ZEROED) && option(kOptSplatTileKernel) == 0;
+    return nrow > kWRow && nwords <= kLongWords && (flags & GF_WORKSPACE_ZEROED) && option(kOptSplatTileKernel) == 0;
 }
 
-// kind of the forward's matrix-core kernel for a call: 0 tile, 1 wave (round 3); development build only: 2 pair, 3 solo (round 5).
-// The round-5 kernels take plain forwards only (no label epilogue, no backward preparation), rows of <= kPRowMax words, a depth that
-// is a multiple of 4 (16-byte output pieces) and ids that leave room for the box mask beside them.
-static int mfma_kind(int nrow, int D, int P, bool labels, bool prepare_backward, int flags = 0)
+// kind of the forward's matrix-core kernel for a call: 0 tile, 1 wave (round 3).  (The round-5 pair and solo kernels, kinds 2 and 3,
+// were removed after a5ba306: DESIGN.md section 3.2c.)
+static int mfma_kind(int nrow, int P, int flags = 0)
 {
-#if GF_DEV
-    const bool plain = !labels && !prepare_backward && nrow <= kPRowMax && (D & 3) == 0 && option(kOptSplatTileKernel) == 0;
-    if (plain && dev_option(kOptSplatPair) && P < (1 << 20)) return 2;
-    if (plain && dev_option(kOptSplatSolo) && P < (1 << 16)) return 3;
-#else
-    (void)D; (void)P; (void)labels; (void)prepare_backward;
-#endif
     return (mfma_by_wave(nrow) || mfma_by_wave_long(nrow, (P + 63) / 64, flags)) ? 1 : 0;
 }
-#if GF_DEV
-static int solo_waves() { return dev_option(kOptSplatSoloWaves) == 3 ? 3 : 2; }
-#endif
 
 // workgroups per XCD of the matrix-core kernel that renders a call (what the per-XCD unit counters start from)
-static uint32_t mfma_counter_init(int kind, int nsuper, int nrow, int D)
+static uint32_t mfma_counter_init(int kind, int nsuper, int D)
 {
-#if GF_DEV
-    if (kind == 3)
-        return (uint32_t)((solo_waves() == 3 ? mfma_solo_grid<3>(mfma_wave_units(nsuper, D), nrow) : mfma_solo_grid<2>(mfma_wave_units(nsuper, D), nrow)) / 8);
-    if (kind == 2) return (uint32_t)(mfma_pair_grid(mfma_wave_units(nsuper, D), nrow) / 8);
-#else
-    (void)nrow;
-#endif
-    return kind == 1 ? (uint32_t)((GF_STATIC2 ? 2 : 1) * (mfma_wave_grid(mfma_wave_units(nsuper, D)) / 8)) : (uint32_t)(mfma_grid(nsuper * kTilesPerSuper) / 8);
+    return kind == 1 ? (uint32_t)(mfma_wave_grid(mfma_wave_units(nsuper, D)) / 8) : (uint32_t)(mfma_grid(nsuper * kTilesPerSuper) / 8);
 }
 
 static void launch_render_mfma(const RenderArgs &r, int nsuper, hipStream_t stream)
@@ -3004,27 +2922,14 @@ static void launch_render_mfma(const RenderArgs &r, int nsuper, hipStream_t stre
     hipEvent_t ev0, ev1;
     const bool prof = profile_slot(&ev0, &ev1);
     if (prof) (void)hipEventRecord(ev0, stream);
-    const int kind = mfma_kind(r.nrow, r.D, r.P, r.out_labels != nullptr, r.rows_valid != 0u, r.summary ? GF_WORKSPACE_ZEROED : 0);
+    const int kind = mfma_kind(r.nrow, r.P, r.summary ? GF_WORKSPACE_ZEROED : 0);
     const int wave_grid = mfma_wave_grid(mfma_wave_units(nsuper, r.D));
-#if GF_DEV
-    if (kind == 3 && solo_waves() == 3)
-        hipLaunchKernelGGL((gf_splat_render_mfma_solo_kernel<3, false>), dim3(mfma_solo_grid<3>(mfma_wave_units(nsuper, r.D), r.nrow)), dim3(64), solo_lds_bytes(r.nrow), stream, r, FusedArgs{});
-    else if (kind == 3)
-        hipLaunchKernelGGL((gf_splat_render_mfma_solo_kernel<2, false>), dim3(mfma_solo_grid<2>(mfma_wave_units(nsuper, r.D), r.nrow)), dim3(64), solo_lds_bytes(r.nrow), stream, r, FusedArgs{});
-    else if (kind == 2)
-        hipLaunchKernelGGL(gf_splat_render_mfma_pair_kernel, dim3(mfma_pair_grid(mfma_wave_units(nsuper, r.D), r.nrow)), dim3(128), pair_lds_bytes(r.nrow), stream, r);
-    else if (kind == 1 && !r.out_labels && !r.rows_valid && dev_option(kOptUnitsBands))   // (comparison only: the unit -> XCD mapping of rounds 3 and 4)
-        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, false, false>), dim3(wave_grid), dim3(64), 0, stream, r);
-    else if (kind == 0 && dev_option(kOptUnitsBands))
-        hipLaunchKernelGGL((gf_splat_render_mfma_kernel<false, false>), dim3(mfma_grid(r.ntiles_total)), dim3(kBlock), 0, stream, r);
-    else
-#endif
     if (kind == 1 && r.nrow > kWRow && r.out_labels)
-        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<true, false, true, true>), dim3(wave_grid), dim3(64), 0, stream, r);
+        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<true, false, true>), dim3(wave_grid), dim3(64), 0, stream, r);
     else if (kind == 1 && r.nrow > kWRow && r.rows_valid)
-        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, true, true, true>), dim3(wave_grid), dim3(64), 0, stream, r);
+        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, true, true>), dim3(wave_grid), dim3(64), 0, stream, r);
     else if (kind == 1 && r.nrow > kWRow)
-        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, false, true, true>), dim3(wave_grid), dim3(64), 0, stream, r);
+        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, false, true>), dim3(wave_grid), dim3(64), 0, stream, r);
     else if (kind == 1 && r.out_labels)
         hipLaunchKernelGGL(gf_splat_render_mfma_wave_kernel<true>, dim3(wave_grid), dim3(64), 0, stream, r);
     else if (kind == 1 && r.rows_valid)
@@ -3040,7 +2945,7 @@ template <int VARIANT, int EXP, bool LABELS>
 static void launch_render(bool dense_candidate, const RenderArgs &r, hipStream_t stream)
 {
     if (dense_candidate) {
-        const int per_xcd = r.bands ? (r.ntiles_total + 7) / 8 : ((r.nsx * r.nsy + 7) / 8) * kTilesPerSuper;
+        const int per_xcd = ((r.nsx * r.nsy + 7) / 8) * kTilesPerSuper;
         // the embedded arbitrary-points body grid-strides, so the tile grid is enough
         hipEvent_t ev0, ev1;
         const bool prof = profile_slot(&ev0, &ev1);
@@ -3120,44 +3025,6 @@ extern "C" size_t gf_splat_workspace_bytes(int P, int N, int H, int W, int D)
 extern "C" size_t gf_splat_state_bytes(void) { return 256; }
 
 namespace gf {
-#if GF_DEV
-__global__ void gf_xcc_census_kernel(uint32_t *out)
-{
-    if (threadIdx.x == 0) out[blockIdx.x] = (uint32_t)physical_xcc();
-}
-// One-time check of what the fused forward's work partition relies on for COVERAGE (not for coherence): workgroups are dealt to the
-// XCDs round-robin (workgroup b on XCD (b + c) % 8), so every eight consecutive workgroups of a grid cover the eight XCDs.  HIP does not promise it; a device where the census
-// fails keeps the two-launch forward.  (Synchronises once, at the first call that could fuse.)
-static bool xcc_census_ok()
-{
-    static int state = 0;   // 0 unknown, 1 ok, -1 not ok
-    if (state == 0) {
-        state = -1;
-        uint32_t *d = nullptr;
-        constexpr int kBlocks = 256;
-        if (hipMalloc(&d, kBlocks * sizeof(uint32_t)) == hipSuccess) {
-            uint32_t h[kBlocks];
-            (void)hipDeviceSynchronize();   // (once: with other kernels in flight the dispatcher does not start a grid at XCD 0)
-            hipLaunchKernelGGL(gf_xcc_census_kernel, dim3(kBlocks), dim3(64), 0, 0, d);
-            if (hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
-                bool ok = true;
-                // (any rotation: the dispatcher's round-robin position carries over from the previous grid; what the fused pass
-                // needs is that every eight consecutive workgroups cover the eight XCDs)
-                for (int b = 0; b < kBlocks; ++b) ok = ok && h[b] < 8u && h[b] == ((h[0] + (uint32_t)b) & 7u);
-                state = ok ? 1 : -1;
-            }
-            (void)hipFree(d);
-        }
-    }
-    return state == 1;
-}
-static bool stream_is_capturing(hipStream_t stream)
-{
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &st) != hipSuccess) return true;   // (be conservative)
-    return st != hipStreamCaptureStatusNone;
-}
-#endif   // GF_DEV
 struct LabelOpts {
     long long *labels;  // null: plain forward
     int mode, empty_label;
@@ -3211,17 +3078,15 @@ static int splat_forward_impl(const char *fn, int variant, int radii_per_axis, i
     // W consecutive words of every row).  Small P: TWO, with the records still loaded and stored per lane (round 5: compiling parts
     // out of the pass showed 2.7 of its 9.5 us in the 625 scattered 8-byte stores of a single-wave workgroup; 16-byte runs:
     // 43.8 -> 41.9 us per step at P = 25 601; runs of 32 bytes 42.9, of 64 bytes 44.8 -- the workgroup barriers take over).
-    const int env_waves = dev_option(kOptPrepWaves);   // (development build: gf_set_option("dev.prep_waves", 1|2|4|8))
-    const bool env_ok = env_waves == 1 || env_waves == 2 || env_waves == 4 || env_waves == 8;
     // (long rows, round 6: four waves as well -- the row summaries are one byte per four-wave workgroup)
     const bool long_rows = ws.summary != nullptr && (flags & GF_WORKSPACE_ZEROED) != 0;
-    const bool staged = (P >= 65536 || long_rows) && !env_ok;   // (large P: the records through an LDS image, four waves per workgroup)
-    const int prep_waves = env_ok ? env_waves : (P >= 65536 || long_rows) ? 4 : 2;
+    const bool staged = P >= 65536 || long_rows;   // (large P: the records through an LDS image, four waves per workgroup)
+    const int prep_waves = staged ? 4 : 2;
     pa.variant = variant; pa.nprep_blocks = (ws.nwords + prep_waves - 1) / prep_waves; pa.verify = verify ? 1 : 0;
     // matrix-core kernel: the default wherever it applies (include/gf_hip.h, GF_MFMA_SPLAT / GF_EXACT_FP32)
     // (the label epilogue -- argmax mode -- is built into the wave-autonomous kernel only: rows of <= kWRow words)
     const bool mfma_ok = variant == GF_SPLAT_BASE && dense_candidate && P > 0 &&
-                         (!lab.labels || (lab.mode == GF_LABELS_ARGMAX && (mfma_by_wave(ws.nrow) || (mfma_by_wave_long(ws.nrow, ws.nwords, flags) && !env_ok))));
+                         (!lab.labels || (lab.mode == GF_LABELS_ARGMAX && (mfma_by_wave(ws.nrow) || mfma_by_wave_long(ws.nrow, ws.nwords, flags))));
     const bool mfma = mfma_ok && ((flags & GF_MFMA_SPLAT) ||
                                   !(flags & (GF_EXACT_FP32 | GF_FAST_EXP | GF_LIBM_EXP | GF_COMP_EXP)));
     pa.prescale = (!mfma && exp_flavour(variant, flags) == kExpFast) ? 1 : 0;  // the matrix-core kernel scales in fp64 itself
@@ -3243,41 +3108,19 @@ static int splat_forward_impl(const char *fn, int variant, int radii_per_axis, i
     pa.range_flags = mfma ? ws.range_flags : nullptr;
     pa.range_theta_here = (mfma && !verify) ? 1 : 0;   // (with the point scans running, their waves take the theta verdict)
     // one verdict word instead of one per prep wave: the wave kernel on a workspace that was handed over zeroed (see gf_splat_prep_kernel)
-    // (long rows on the wave kernel: with the four-wave records pass that writes the summaries -- not under a development override of it)
-    const int kind_flags = (long_rows && prep_waves == 4) ? GF_WORKSPACE_ZEROED : 0;
-    const int the_kind = mfma_kind(ws.nrow, D, P, lab.labels != nullptr, pa.unit_totals != nullptr, kind_flags);
+    // (long rows on the wave kernel: with the four-wave records pass that writes the summaries)
+    const int the_kind = mfma_kind(ws.nrow, P, long_rows ? GF_WORKSPACE_ZEROED : 0);
     const bool by_wave_long = mfma && the_kind == 1 && ws.nrow > kWRow;
-    uint32_t *const verdict_words = (GF_VD1 && mfma && (flags & GF_WORKSPACE_ZEROED) && the_kind == 1) ? ws.flags + kVerdictWords : nullptr;
+    uint32_t *const verdict_words = (mfma && (flags & GF_WORKSPACE_ZEROED) && the_kind == 1) ? ws.flags + kVerdictWords : nullptr;
     pa.verdict_words = verdict_words;
     pa.summary = by_wave_long ? ws.summary : nullptr; pa.sum_pitch = ws.sum_pitch;
-    pa.tile_counter_init = !mfma ? 0u : mfma_counter_init(the_kind, ws.nsuper, ws.nrow, D);
-#if GF_DEV
-    // The fused single-launch forward (splat_fwd_solo.inc, FusedArgs; development build only): plain base forward on a grid the caller
-    // vouches for, a workspace whose flag section was zeroed once, a shape the solo kernel takes, not under stream capture (a replayed
-    // launch would repeat its launch id), and a device whose workgroup -> XCD placement passed the one-time census.
-    // MEASURED AND NOT KEPT: correct, bit-identical to the two-launch solo kernel, but 57 against 43.5 us per
-    // step -- eight XCDs each reading and writing the whole record set land their first inputs at 8 us and hand off at 15 us, later
-    // than the separate records pass finishes.
-    const bool fused = mfma && !verify && (flags & GF_WORKSPACE_ZEROED) && ws.x_records != nullptr && dev_option(kOptSplatFused) &&
-                       !dev_option(kOptSplatPair) && option(kOptSplatTileKernel) == 0 &&
-                       !lab.labels && pa.unit_totals == nullptr && ws.nrow <= kPRowMax && (D & 3) == 0 && P < (1 << 16) &&
-                       !stream_is_capturing(stream) && xcc_census_ok();
-    if (!fused && dev_option(kOptSplatFused) && dev_option(kOptSplatFusedWhy))   // which precondition said no
-        fprintf(stderr, "dev.splat_fused not taken: mfma %d verify %d zeroed %d x_records %d labels %d unit_totals %d nrow %d D %d P %d capturing %d census %d\n",
-                (int)mfma, (int)verify, (int)((flags & GF_WORKSPACE_ZEROED) != 0), (int)(ws.x_records != nullptr), (int)(lab.labels != nullptr),
-                (int)(pa.unit_totals != nullptr), ws.nrow, D, P, (int)stream_is_capturing(stream), (int)xcc_census_ok());
-#else
-    constexpr bool fused = false;
-#endif
-    const int prep_grid = fused ? 0 : pa.nprep_blocks + (verify ? kVerifyBlocks / prep_waves : 0);
+    pa.tile_counter_init = !mfma ? 0u : mfma_counter_init(the_kind, ws.nsuper, D);
+    const int prep_grid = pa.nprep_blocks + (verify ? kVerifyBlocks / prep_waves : 0);
     if (prep_grid > 0) {
         const size_t bits_lds = sizeof(unsigned long long) * (size_t)std::min(ws.nsx * ws.nsy * prep_waves, kPrepSuperChunk);
         const size_t prep_lds = bits_lds + (staged ? (size_t)prep_waves * 64 * kRecDwords * sizeof(float) : 0);
-        if (prep_waves == 1) hipLaunchKernelGGL(gf_splat_prep_kernel<1>, dim3(prep_grid), dim3(64), prep_lds, stream, pa);
-        else if (staged) hipLaunchKernelGGL(gf_splat_prep_kernel<4>, dim3(prep_grid), dim3(256), prep_lds, stream, pa);
-        else if (prep_waves == 2) hipLaunchKernelGGL((gf_splat_prep_kernel<2, false>), dim3(prep_grid), dim3(128), prep_lds, stream, pa);
-        else if (prep_waves == 4) hipLaunchKernelGGL((gf_splat_prep_kernel<4, false>), dim3(prep_grid), dim3(256), prep_lds, stream, pa);
-        else hipLaunchKernelGGL((gf_splat_prep_kernel<8, false>), dim3(prep_grid), dim3(512), prep_lds, stream, pa);
+        if (staged) hipLaunchKernelGGL(gf_splat_prep_kernel<4>, dim3(prep_grid), dim3(256), prep_lds, stream, pa);
+        else hipLaunchKernelGGL((gf_splat_prep_kernel<2, false>), dim3(prep_grid), dim3(128), prep_lds, stream, pa);
         GF_CHECK_LAUNCH();
     }
     if (N == 0) return GF_OK;
@@ -3288,7 +3131,6 @@ static int splat_forward_impl(const char *fn, int variant, int radii_per_axis, i
     ra.verify_flags = ws.flags + 64; ra.state = (uint32_t *)state; ra.P = P; ra.N = N; ra.nwords = ws.nwords; ra.nrow = ws.nrow;
     ra.H = H; ra.W = W; ra.D = D; ra.nsx = ws.nsx; ra.nsy = ws.nsy; ra.ntiles_total = ws.nsuper * kTilesPerSuper;
     ra.verify_dense = verify ? 1 : 0;
-    ra.bands = dev_option(kOptUnitsBands) ? 1 : 0;
     ra.timeline = g_timeline;
     ra.tile_perm = g_tile_perm;
     ra.out_labels = lab.labels; ra.label_mode = lab.mode; ra.empty_label = lab.empty_label; ra.threshold = lab.threshold;
@@ -3306,28 +3148,6 @@ static int splat_forward_impl(const char *fn, int variant, int radii_per_axis, i
         ra.m_ps = (uint32_t)(((1ull << 32) + per_super - 1) / per_super);
         ra.m_nsy = (uint32_t)(((1ull << 32) + (unsigned)ws.nsy - 1) / (unsigned)ws.nsy);
     }
-#if GF_DEV
-    if (fused) {
-        // (unique per launch; the low 32 bits count from 1 -- the unit counters' tags must grow --, the bits above are a per-process
-        // salt, so that item flags a previous process left in recycled device memory cannot pass for this launch's)
-        static std::atomic<unsigned long long> launch_id{((unsigned long long)(std::chrono::steady_clock::now().time_since_epoch().count() & 0xFFFFFF) << 32) | 1ull};
-        FusedArgs fa;
-        fa.means3D = means3D; fa.means_int = means3D_int; fa.opacity = opacity; fa.semantics = semantics; fa.radii = radii; fa.cov3D = cov3D;
-        fa.x_records = ws.x_records; fa.x_boxes = ws.x_boxes; fa.x_bitmask = ws.x_bitmask; fa.x_flags = ws.x_flags;
-        fa.ctrs = reinterpret_cast<unsigned long long *>(ws.flags + kFusedCounters);
-        fa.gen_word = ws.flags + kGenWord;
-        fa.launch_id = launch_id.fetch_add(1ull) & 0x00FFFFFFFFFFFFFFull;
-        fa.per_axis = radii_per_axis ? 1 : 0;
-        ra.range_flags = nullptr; ra.verify_dense = 0;
-        hipEvent_t ev0, ev1;
-        const bool prof = profile_slot(&ev0, &ev1);
-        if (prof) (void)hipEventRecord(ev0, stream);
-        const int nunits = mfma_wave_units(ws.nsuper, D);
-        // (two waves per SIMD: the records pass stages through 20 KB of LDS per wave, eight waves per CU)
-        hipLaunchKernelGGL((gf_splat_render_mfma_solo_kernel<2, true>), dim3(mfma_solo_grid<2>(nunits, ws.nrow, true)), dim3(64), solo_lds_bytes(ws.nrow, true), stream, ra, fa);
-        if (prof) (void)hipEventRecord(ev1, stream);
-    } else
-#endif
     if (mfma)
         launch_render_mfma(ra, ws.nsuper, stream);
     else if (variant == GF_SPLAT_BASE)

@@ -47,21 +47,6 @@ class _Workspace:
         return buf
 
     FLAG_BYTES = 32768
-    _zeroed = {}
-
-    @classmethod
-    def get_zeroed(cls, device, nbytes, shape):
-        """A buffer of its own per (stream, problem shape), zeroed when created and never handed to another shape: what
-        the development build's fused forward needs (``dev.splat_fused``: its flags and counters are tagged per launch instead of
-        being reset, which only holds in memory no other layout has written)."""
-        key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream, nbytes, shape)
-        buf = cls._zeroed.get(key)
-        if buf is None:
-            if len(cls._zeroed) >= cls.MAX_STREAMS:
-                cls._zeroed.pop(next(iter(cls._zeroed)))
-            buf = cls._zeroed[key] = torch.zeros(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        cls._uses += 1
-        return buf
 
     @classmethod
     def stamp(cls, device):
@@ -151,10 +136,7 @@ def splat_forward(variant, pts, points_int, means3D, means3D_int, opacities, sem
         probability = torch.empty(N, dtype=f32, device=dev)
     state = torch.empty(lib.gf_splat_state_bytes(), dtype=torch.uint8, device=dev)
     nbytes = lib.gf_splat_workspace_bytes(P, N, H, W, D)
-    if _lib.is_development_build() and _lib.get_option("dev.splat_fused"):   # (tools/ only: see _Workspace.get_zeroed)
-        ws = _Workspace.get_zeroed(dev, nbytes, (P, N, H, W, D))
-    else:
-        ws = _Workspace.get(dev, nbytes)
+    ws = _Workspace.get(dev, nbytes)
     flags |= _lib.GF_WORKSPACE_ZEROED
     with torch.cuda.device(dev):
         rc = lib.gf_splat_forward(

@@ -103,8 +103,8 @@ extern "C" {
 #define GF_PATH_EXACT_TILE 0     /* exact-fp32 tile kernel (dense grid) */
 #define GF_PATH_MATRIX_CORE 1    /* split-f16 MFMA kernel (dense exact lattice), one workgroup per tile: P > 262 144, or P > 39 552 on a workspace without GF_WORKSPACE_ZEROED */
 #define GF_PATH_MATRIX_CORE_WAVE 3 /* the same arithmetic (equal bits), one wave per double brick: P <= 39 552, and (long-row instantiation, GF_WORKSPACE_ZEROED) P <= 262 144 */
-#define GF_PATH_MATRIX_CORE_PAIR 4 /* development build only (gf_is_development_build): round 5's two-waves-per-double-brick kernel -- measured, NOT the default, not in the product library */
-#define GF_PATH_MATRIX_CORE_SOLO 5 /* development build only: round 5's single-wave kernel with the opacity in the exponent -- measured, NOT the default, not in the product library */
+#define GF_PATH_MATRIX_CORE_PAIR 4 /* retired: round 5's two-waves-per-double-brick kernel (removed after a5ba306); never reported */
+#define GF_PATH_MATRIX_CORE_SOLO 5 /* retired: round 5's single-wave kernel with the opacity in the exponent (removed after a5ba306); never reported */
 #define GF_PATH_ARBITRARY 2      /* arbitrary-points body (pts not the dense grid, or a failed lattice / range verdict) */
 
 int gf_abi_version(void);
@@ -122,8 +122,7 @@ const char *gf_last_error(void);
  *                                (>= 32 tiles per offset on average: runs of eight tiles per workgroup otherwise); equal bits
  *   "fps.exhaustive"          1: gf_farthest_point_sampling updates every bucket on every pick instead of pruning by box bounds;
  *                                the same bits (the exactness cross-check and the brute-force baseline)
- * A development build (gf_is_development_build() == 1; built by tools/ with -DGF_DEV=1, never shipped as libgf_hip.so) also accepts
- * "dev.*" names for the measured-and-not-kept kernels of earlier rounds. */
+ * gf_is_development_build() always returns 0 (kept for ABI 8: the development build was removed after a5ba306). */
 int gf_set_option(const char *name, int value);
 int gf_get_option(const char *name, int *value);
 int gf_is_development_build(void);
@@ -339,7 +338,7 @@ int gf_daf_backward_sorted(int B, int num_cams, int num_feat, int C, int L, int 
  * durations in milliseconds, resets the ring and returns how many were written.
  * gf_profile_enable(0) disables and frees.  Not part of the reference interface.
  */
-int gf_profile_enable(int max_records);
+int gf_profile_enable(int max_pairs);
 /*
  * feature_maps_format (model/encoder/gaussian_encoder/ops/deformable_aggregation.py:77-117): L image-feature levels
  * [planes, C, hw_l] (planes = bs * cams, contiguous) <-> one channels-last table [planes, sum_l hw_l, C], level l

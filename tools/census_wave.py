@@ -1,4 +1,4 @@
-"""Static ISA census of the default forward kernel (gf_splat_render_mfma_wave_kernel<false, false, true>) by phase x trip count
+"""Static ISA census of the default forward kernel (gf_splat_render_mfma_wave_kernel<false, false, false>) by phase x trip count
 (VERDICT r5 #3c).  Finds the phase boundaries from the kernel's own comment markers, so it survives edits; trip counts per unit are
 the headline shape's (nuscenes_gs25600_solid: 2 048 waves for 5 000 units, 140 candidates and 2.16 groups per unit).
     python tools/census_wave.py > profiles/census_wave_r06.txt          (no GPU needed)"""
@@ -46,10 +46,10 @@ phases = [
 ]
 with tempfile.NamedTemporaryFile("w", suffix=".json", delete=False) as f:
     json.dump(phases, f)
-print("# tools/census_wave.py -- static instruction counts of gf_splat_render_mfma_wave_kernel<false,false,true> (gfx950, -Os: the product build since the second half of round 6; -O3 before: profiles/census_wave_O3_r06.txt) per source")
+print("# tools/census_wave.py -- static instruction counts of gf_splat_render_mfma_wave_kernel<false,false,false> (gfx950, -Os: the product build since the second half of round 6; -O3 before: profiles/census_wave_O3_r06.txt) per source")
 print("# phase, weighted by trips per unit at nuscenes_gs25600_solid.  Cycle weights: VALU 4, transcendental 16 (quarter rate), fp64 8")
 print("# (upper bound: v_fma_f64 issues at full rate on this part).  PMC of the same kernel (profiles/pmc_wave_vs_solo_r05.txt): 8.39 M VALU")
 print("# wave-instructions per launch = 1 680 per unit; SALU 3.86 M = 772 per unit.")
 sys.stdout.flush()
-subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_census.py"), "gf_splat_render_mfma_wave_kernelILb0ELb0ELb1E", "--phases", f.name], check=True)
+subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_census.py"), "gf_splat_render_mfma_wave_kernelILb0ELb0ELb0EE", "--phases", f.name], check=True)
 os.unlink(f.name)
