@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 8   /* 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 9   /* 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -656,6 +656,38 @@ int gf_pixel_loss_forward(int rows, int bins, int flags, const float *logits, co
                           void *workspace, size_t workspace_bytes, void *stream);
 int gf_pixel_loss_backward(int rows, int bins, int flags, const float *logits, const unsigned char *pixel_gt,
                            const float *grad_loss, float *grad_logits, void *stream);
+
+/* ---- modulated deformable convolution (DCNv2) -----------------------------------------------------------------------
+ * Replaces mmcv's modulated_deform_conv2d / ModulatedDeformConv2dPack (registered as 'DCNv2'; the reference's ResNet-101
+ * backbone with stage_with_dcn=(False, False, True, True) in every config), DESIGN.md §3.11.  Per output pixel (ho, wo), deform
+ * group g, tap k = i kw + j and input channel c of group g (c / (Cin / dg) == g):
+ *   dy = offset[n][g 2 kh kw + 2 k][ho][wo], dx = offset[n][g 2 kh kw + 2 k + 1][ho][wo], m = mask[n][g kh kw + k][ho][wo];
+ *   y = (ho sh - ph + i dh) + dy, x = (wo sw - pw + j dw) + dx (one fp32 add each);
+ *   col = m * bilinear(input[n][c], y, x) when -1 < y < H and -1 < x < W (corners outside the image add 0), else 0;
+ *   out[n][co][ho][wo] = sum_{c, k} weight[co][c][i][j] col + bias[co].
+ *   Ho = (H + 2 ph - (dh (kh - 1) + 1)) / sh + 1, likewise Wo.
+ * Layouts (fp32, contiguous): input [N][Cin][H][W], offset [N][2 dg kh kw][Ho][Wo], mask [N][dg kh kw][Ho][Wo], weight
+ * [Co][Cin][kh][kw], bias [Co] or NULL, out / grad_out [N][Co][Ho][Wo]; the gradients have their input's layout.
+ * Supported: N >= 0, kh, kw <= GF_DCN_MAX_KERNEL, stride and dilation >= 1, padding >= 0, groups == 1, Cin / dg and Co
+ * multiples of GF_DCN_CHANNEL_GRANULE; anything else returns GF_EINVAL before any HIP call.
+ *   workspace   gf_dcn_workspace_bytes(..., backward) bytes (0: unsupported shape); forward: a channels-last copy of the input
+ *               and a re-laid weight; backward adds a channels-last grad_input accumulator and the weight-gradient partials
+ *               (at most 16 copies of the weight): forward 36 / 26 MB, backward 88 / 61 MB at layer3 [6, 256, 54, 100] / layer4 [6, 512, 27, 50]
+ * gf_dcn_backward: each gradient pointer may be NULL (not wanted).  grad_input is summed with fp32 atomics and is not bitwise
+ * reproducible; the forward, grad_offset, grad_mask, grad_weight and grad_bias are (fixed-order sums).  Offset and mask
+ * gradients are 0 where the sample is outside the window, and use the one-sided derivative of floor at integer coordinates
+ * (mmcv's dmcn_get_coordinate_weight).  No host synchronisation: graph-capturable. */
+#define GF_DCN_MAX_KERNEL 7
+#define GF_DCN_CHANNEL_GRANULE 32
+size_t gf_dcn_workspace_bytes(int N, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                              int groups, int dg, int backward);
+int gf_dcn_forward(int N, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
+                   int dg, const float *input, const float *offset, const float *mask, const float *weight, const float *bias,
+                   float *out, void *workspace, size_t workspace_bytes, void *stream);
+int gf_dcn_backward(int N, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
+                    int dg, const float *input, const float *offset, const float *mask, const float *weight, const float *grad_out,
+                    float *grad_input, float *grad_offset, float *grad_mask, float *grad_weight, float *grad_bias,
+                    void *workspace, size_t workspace_bytes, void *stream);
 
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */
