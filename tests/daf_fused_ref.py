@@ -21,13 +21,19 @@ def project(key_points, projection_mat, image_wh=None):
     return uv, (cs[..., 2] > DEPTH_EPS) & (u > 0) & (u < 1) & (v > 0) & (v < 1)
 
 
-def bilinear(fmap, uv):
+def bilinear(fmap, uv, cell_uv=None):
     """fmap [b, cams, C, h, w], uv [b, N, cams, 2] -> [b, N, cams, C]: bilinear_sampling (cu:13-53) at (v h - 0.5, u w - 0.5),
-    zero where the location is outside (0, 1) (cu:166)."""
+    zero where the location is outside (0, 1) (cu:166).  ``cell_uv`` (like ``uv``, optional): the locations whose tap cells
+    (floor(v h - 0.5), floor(u w - 0.5), in their own dtype) are used -- the discrete choice of a float32 computation, with
+    the value and its derivative evaluated at ``uv`` on that cell's bilinear patch."""
     b, cams, C, h, w = fmap.shape
     h_im = uv[..., 1] * h - 0.5
     w_im = uv[..., 0] * w - 0.5
-    h0, w0 = torch.floor(h_im).detach(), torch.floor(w_im).detach()
+    if cell_uv is None:
+        h0, w0 = torch.floor(h_im).detach(), torch.floor(w_im).detach()
+    else:
+        h0 = torch.floor(cell_uv[..., 1].detach() * h - 0.5).to(uv.dtype)
+        w0 = torch.floor(cell_uv[..., 0].detach() * w - 0.5).to(uv.dtype)
     lh, lw = h_im - h0, w_im - w0
     flat = fmap.permute(0, 1, 3, 4, 2).reshape(b, cams, h * w, C)
     out = 0
@@ -41,14 +47,14 @@ def bilinear(fmap, uv):
     return out * inside[..., None]
 
 
-def daf(maps, uv, weights):
+def daf(maps, uv, weights, cell_uv=None):
     """The DAF of the reference: maps = per-level [b, cams, C, h, w], uv [b, N, cams, 2], weights [b, N, cams, L, G]
-    -> [b, N, C] (cu:125-187)."""
+    -> [b, N, C] (cu:125-187).  ``cell_uv``: see :func:`bilinear`."""
     out = 0
     C = maps[0].shape[2]
     G = weights.shape[-1]
     for l, fmap in enumerate(maps):
-        s = bilinear(fmap, uv)                                            # [b, N, cams, C]
+        s = bilinear(fmap, uv, cell_uv)                                            # [b, N, cams, C]
         wl = weights[:, :, :, l].repeat_interleave(C // G, dim=-1)        # [b, N, cams, C]
         out = out + (s * wl).sum(dim=2)
     return out
@@ -69,13 +75,15 @@ def softmax_weights(visible, raw, weight_mask=None):
     return w * (~all_miss).to(w.dtype)
 
 
-def block(key_points, projection_mat, image_wh, maps, raw, weight_mask=None):
-    """features [b, A, C] of DeformableFeatureAggregation.forward before output_proj (:174-242)."""
+def block(key_points, projection_mat, image_wh, maps, raw, weight_mask=None, cell_uv=None):
+    """features [b, A, C] of DeformableFeatureAggregation.forward before output_proj (:174-242).  ``cell_uv`` [b, A, pts, cams, 2]
+    (optional): the locations whose tap cells are used (:func:`bilinear`)."""
     uv, visible = project(key_points, projection_mat, image_wh)
     w = softmax_weights(visible, raw, weight_mask)
     b, A, pts, cams = visible.shape
     L, G = w.shape[4], w.shape[5]
-    out = daf(maps, uv.reshape(b, A * pts, cams, 2), w.reshape(b, A * pts, cams, L, G))
+    cu = None if cell_uv is None else cell_uv.reshape(b, A * pts, cams, 2)
+    out = daf(maps, uv.reshape(b, A * pts, cams, 2), w.reshape(b, A * pts, cams, L, G), cu)
     return out.reshape(b, A, pts, -1).sum(dim=2)
 
 
@@ -119,10 +127,11 @@ def daf_chunked(feat, spatial_shape, scale_start, loc, weights, grad_out, dtype=
 
 
 def block_chunked(key_points, projection_mat, image_wh, feat, spatial_shape, scale_start, grad_out, raw=None, raw_anchor=None,
-                  raw_cam=None, weight_mask=None, dtype=torch.float64, chunk=None):
+                  raw_cam=None, weight_mask=None, dtype=torch.float64, chunk=None, cell_uv=None):
     """The fused op (deformable_fused) by the restatement in ``dtype``, anchors in slices: key_points [b, A, pts, 3], feat the
     formatted table, logits ``raw`` [b, A, cams, L, pts, G] or ``raw_anchor`` [b, A, L, pts, G] + ``raw_cam`` [b, cams, L, pts, G],
-    grad_out [b, A, C] -> (out [b, A, C], dict of leaf gradients: kp, feat, and raw or ra and rc)."""
+    grad_out [b, A, C], ``cell_uv`` [b, A, pts, cams, 2] (optional, :func:`bilinear`) -> (out [b, A, C], dict of leaf gradients:
+    kp, feat, and raw or ra and rc)."""
     b, A, pts = key_points.shape[:3]
     cams, C, L = feat.shape[1], feat.shape[3], spatial_shape.shape[0]
     step = max(1, (chunk or slice_len(cams, C, L)) // pts)
@@ -140,7 +149,8 @@ def block_chunked(key_points, projection_mat, image_wh, feat, spatial_shape, sca
         lg = lead[:, s:e].detach().to(dtype).requires_grad_(True)
         x = lg if raw is not None else lg[:, :, None] + rc[:, None]
         wm = None if weight_mask is None else weight_mask[:, s:e]
-        o = block(kp, pm, wh, table_levels(ft, spatial_shape, scale_start), x, wm)
+        cu = None if cell_uv is None else cell_uv[:, s:e]
+        o = block(kp, pm, wh, table_levels(ft, spatial_shape, scale_start), x, wm, cu)
         o.backward(grad_out[:, s:e].to(dtype))
         out[:, s:e] = o.detach()
         grads["kp"][:, s:e] = kp.grad
@@ -172,3 +182,25 @@ def touched_rows(spatial_shape, scale_start, loc, num_feat, slack=1e-4):
                         ok = inside & (py >= 0) & (py < h) & (px >= 0) & (px < w)
                         hit[bi[ok], ci[ok], st + py[ok] * w + px[ok]] = True
     return hit
+
+
+def visible_pairs(loc):
+    """[b, N, cams]: the (point, camera) pairs whose sampling location is inside the strict (0, 1) window."""
+    return ((loc > 0) & (loc < 1)).all(-1)
+
+
+def edge_pairs(loc, ss, slack=None):
+    """[b, N, cams]: visible pairs whose tap coordinate ``loc * size - 0.5`` lies on a different side of a cell edge in float32
+    arithmetic (fused or not) than in exact arithmetic, at some level -- or, given ``slack`` (locations the kernel computes
+    itself, from the key points), within ``slack`` pixels of a cell edge.  The bilinear sample's derivative with respect to its
+    location jumps there, so such a pair's location gradient has no float32-resolvable truth."""
+    edge = torch.zeros(loc.shape[:3], dtype=torch.bool, device=loc.device)
+    for h, w in ss.tolist():
+        for v, n in ((loc[..., 1], h), (loc[..., 0], w)):
+            exact = v.double() * n - 0.5                                  # exact: a float32 times an integer below 2^11
+            if slack is not None:
+                edge |= (exact - torch.round(exact)).abs() < slack
+                continue
+            f = torch.floor(exact)
+            edge |= (torch.floor(exact.float()) != f) | (torch.floor(v * n - 0.5) != f)
+    return edge & visible_pairs(loc)

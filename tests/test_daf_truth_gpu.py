@@ -23,6 +23,7 @@ import pytest
 import torch
 
 import daf_fused_ref as ref
+from daf_fused_ref import edge_pairs as _edge_pairs, visible_pairs as _visible_pairs
 from util import assert_daf_rows_close
 
 pytestmark = pytest.mark.gpu
@@ -50,26 +51,6 @@ def _pyramid(levels, dev):
     sizes = ss[:, 0] * ss[:, 1]
     st = torch.cat([torch.zeros(1, dtype=torch.int32), torch.cumsum(sizes, 0)[:-1].to(torch.int32)])
     return ss.to(dev), st.to(dev), int(sizes.sum())
-
-
-def _visible_pairs(loc):
-    return ((loc > 0) & (loc < 1)).all(-1)
-
-
-def _edge_pairs(loc, ss, slack=None):
-    """[b, N, cams]: visible pairs whose tap coordinate ``loc * size - 0.5`` lies on a different side of a cell edge in float32
-    arithmetic (fused or not) than in exact arithmetic, at some level (see the module docstring) -- or, given ``slack`` (locations
-    the kernel computes itself, from the key points), within ``slack`` pixels of a cell edge."""
-    edge = torch.zeros(loc.shape[:3], dtype=torch.bool, device=loc.device)
-    for h, w in ss.tolist():
-        for v, n in ((loc[..., 1], h), (loc[..., 0], w)):
-            exact = v.double() * n - 0.5                                  # exact: a float32 times an integer below 2^11
-            if slack is not None:
-                edge |= (exact - torch.round(exact)).abs() < slack
-                continue
-            f = torch.floor(exact)
-            edge |= (torch.floor(exact.float()) != f) | (torch.floor(v * n - 0.5) != f)
-    return edge & _visible_pairs(loc)
 
 
 def _check_daf(name, got, truth, truth32, loc, ss, st, num_feat, forward_only=False):
