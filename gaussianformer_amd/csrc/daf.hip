@@ -265,45 +265,6 @@ __global__ __launch_bounds__(256) void gf_daf_fwd_grouped_kernel(DafArgs a, int 
     *reinterpret_cast<float4 *>(a.out + bp * a.C + c0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
-// butterfly sum over aligned groups of `width` lanes (power of two <= 64)
-__device__ __forceinline__ float group_sum(float v, int width)
-{
-    for (int d = width >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// DPP forms for the nuScenes layout (C = 128, 4 channels per lane, 4 groups: 8 lanes per group, 32 per point):
-// running sums inside a row of 16 lanes, the total lands in the LAST lane of every 8 / 32.
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float dpp_add(float v)
-{
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
-}
-
-__device__ __forceinline__ float sum8_last(float v)  // valid in lanes with (lane & 7) == 7
-{
-    v = dpp_add<0x111>(v);  // row_shr:1
-    v = dpp_add<0x112>(v);  // row_shr:2
-    return dpp_add<0x114>(v);  // row_shr:4
-}
-
-__device__ __forceinline__ float sum4_last(float v)  // valid in lanes with (lane & 3) == 3
-{
-    v = dpp_add<0x111>(v);  // row_shr:1
-    return dpp_add<0x112>(v);  // row_shr:2
-}
-
-__device__ __forceinline__ float sum16_last(float v)  // valid in lanes with (lane & 15) == 15 (a DPP row)
-{
-    return dpp_add<0x118>(sum8_last(v));  // row_shr:8
-}
-
-__device__ __forceinline__ float sum32_last(float v)  // valid in lanes 31 and 63
-{
-    v = dpp_add<0x118>(sum8_last(v));  // row_shr:8 -> lane 15 of each row holds the row
-    return dpp_add<0x142, 0xa>(v);     // row_bcast:15 into rows 1 and 3
-}
-
 // LPG = lanes per channel group, LPP = lanes per point (both powers of two <= 64 on the
 // fast path).  REDUCE = false falls back to the reference's per-lane atomics.
 // FEAT = false leaves grad_mc_ms_feat to the pixel-major kernels below (gf_daf_backward_sorted).
@@ -931,17 +892,6 @@ __global__ __launch_bounds__(1024) void gf_daf_regionscan_kernel(DafSortArgs a_)
     }
 }
 
-// memory -> LDS without passing registers (M0 = the wave's LDS base; lane i lands at base + i * size).  Issued from asm: the
-// compiler waits for every outstanding load before the next LDS access when it can see one of these in flight.
-__device__ __forceinline__ void daf_lds_dma16(const void *g, const void *l)
-{
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"((uint32_t)(uintptr_t)l) : "memory", "m0");
-}
-__device__ __forceinline__ void daf_lds_dma4(const void *g, const void *l)
-{
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(g), "s"((uint32_t)(uintptr_t)l) : "memory", "m0");
-}
-
 #ifdef GF_DAF_TL
 __device__ unsigned long long gf_daf_tl[8 * 16384];   // development: per item, wall-clock stamps of the accumulation's phases
 #define GF_DAF_STAMP(i) do { if (tid == 0 && item < 16384u) gf_daf_tl[8 * item + (i)] = wall_clock64(); } while (0)
@@ -1035,13 +985,13 @@ __global__ __launch_bounds__(512, 4) void gf_daf_raccumulate_kernel(DafRegionArg
                 const int sm = wv * SPW + 4 * u + (lane >> 4), j = lane & 15;
                 const uint32_t sid = s_sid[min(b0 + sm, kRegItem - 1)];
                 const size_t sample = (size_t)(sid >> a.s.cam_bits) * a.s.cams + (sid & cam_mask);
-                daf_lds_dma4(a.s.weights + sample * lg + min(j, lg - 1), s_w + (wv * SPW + 4 * u) * 16);
+                lds_dma4(a.s.weights + sample * lg + min(j, lg - 1), s_w + (wv * SPW + 4 * u) * 16);
             }
 #pragma unroll
             for (int u = 0; u < SPW / (64 / LPT); ++u) {   // rows: 64 / LPT samples per request
                 const int sm = wv * SPW + u * (64 / LPT) + lane / LPT;
                 const uint32_t pt = s_sid[min(b0 + sm, kRegItem - 1)] >> a.s.cam_bits;
-                daf_lds_dma16(a.s.grad_out + (size_t)pt * C + c0, s_rows + (wv * SPW + u * (64 / LPT)) * C);
+                lds_dma16(a.s.grad_out + (size_t)pt * C + c0, s_rows + (wv * SPW + u * (64 / LPT)) * C);
             }
         };
         GF_DAF_STAMP(1);

@@ -55,8 +55,6 @@ struct DafFusedArgs {
     const unsigned char *wmask;   // [B, A, cams, L, pts, G] attention-dropout keep-mask (read by the MASK instantiations only)
 };
 
-__device__ __forceinline__ float fu_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-
 // one workgroup = 4 waves = 4 consecutive anchors.  MASK: entries the keep-mask drops leave their group's maximum and sum and
 // weigh 0; a group with no visible, kept entry gives zero channels (all_miss, deformable_module.py:199-214).  The MASK = false
 // instantiation is the code of gf_daf_fused_forward.
@@ -161,9 +159,9 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
         for (int e = lane, k = 0; e < E; e += 64, ++k) {
             if (MASK) {
                 const float x = logit(e, k);   // (a dropped entry is -inf: its group's maximum may be -inf too)
-                s += x == -INFINITY ? 0.f : fu_exp(x - m);
+                s += x == -INFINITY ? 0.f : fast_exp(x - m);
             } else {
-                s += fu_exp(logit(e, k) - m);
+                s += fast_exp(logit(e, k) - m);
             }
         }
         for (int d = a.G; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
@@ -195,7 +193,7 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
                     *reinterpret_cast<float4 *>(v3 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc0) * a.C + j);
                     *reinterpret_cast<float4 *>(v4 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc1) * a.C + j);
                 }
-                const float wt = kept(pc, l, grp) ? fu_exp(logit_at(pc, l, grp) - mg) * inv : 0.f;
+                const float wt = kept(pc, l, grp) ? fast_exp(logit_at(pc, l, grp) - mg) * inv : 0.f;
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
                     const float x1 = ok1 ? v1[j] : 0.f, x2 = ok2 ? v2[j] : 0.f, x3 = ok3 ? v3[j] : 0.f, x4 = ok4 ? v4[j] : 0.f;
@@ -334,7 +332,7 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
         for (int e = lane; e < E; e += 64) {
             int pc, l;
             entry(e, pc, l);
-            if (kept(pc, l, gl)) s += fu_exp(logit_at(pc, l, gl) - m);
+            if (kept(pc, l, gl)) s += fast_exp(logit_at(pc, l, gl) - m);
         }
         for (int d = a.G; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
         const float inv_mine = s > 0.f ? 1.f / s : 0.f;
@@ -370,7 +368,7 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
                     *reinterpret_cast<float4 *>(v3 + j) = *reinterpret_cast<const float4 *>(base + p3 + j);
                     *reinterpret_cast<float4 *>(v4 + j) = *reinterpret_cast<const float4 *>(base + p4 + j);
                 }
-                const float wt = kept(pc, l, grp) ? fu_exp(logit_at(pc, l, grp) - mg) * inv : 0.f;
+                const float wt = kept(pc, l, grp) ? fast_exp(logit_at(pc, l, grp) - mg) * inv : 0.f;
                 float sv = 0.f, sw = 0.f, sh = 0.f;
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
@@ -413,13 +411,13 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
             for (int e = lane; e < E; e += 64) {
                 int pc, l;
                 entry(e, pc, l);
-                if (kept(pc, l, gl)) dot += fu_exp(logit_at(pc, l, gl) - m) * inv_mine * s_gw[e];
+                if (kept(pc, l, gl)) dot += fast_exp(logit_at(pc, l, gl) - m) * inv_mine * s_gw[e];
             }
             for (int d = a.G; d < 64; d <<= 1) dot += __shfl_xor(dot, d, 64);
             auto dlogit = [&](int pt, int cam, int l) -> float {   // group gl
                 const int v = s_pidx[pt * a.cams + cam], pc = (pt << 8) | cam;
                 if (v < 0 || !kept(pc, l, gl)) return 0.f;
-                return fu_exp(logit_at(pc, l, gl) - m) * inv_mine * (s_gw[v * LG + l * a.G + gl] - dot);
+                return fast_exp(logit_at(pc, l, gl) - m) * inv_mine * (s_gw[v * LG + l * a.G + gl] - dot);
             };
             if (args.grad_raw)   // [cams][L][pts][G], every entry written
                 for (int i = lane; i < J; i += 64) {

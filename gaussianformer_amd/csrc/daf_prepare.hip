@@ -28,16 +28,6 @@ struct DafPrepArgs {
     int B, A, pts, cams, L, G;
 };
 
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-
-// reduce over the lanes that share (lane % G): xor-butterfly on the lane bits above log2(G)
-template <typename F>
-__device__ __forceinline__ float group_reduce(float v, int G, F op)
-{
-    for (int d = G; d < 64; d <<= 1) v = op(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
 struct Proj {
     float x, y, z;
 };
@@ -160,8 +150,8 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_kernel(DafPrepArgs a)
                 if (ok[2]) m.z = fmaxf(m.z, x.z);
                 if (ok[3]) m.w = fmaxf(m.w, x.w);
             }
-            auto fmax2 = [](float p, float q) { return fmaxf(p, q); };
-            m.x = group_reduce(m.x, 1, fmax2); m.y = group_reduce(m.y, 1, fmax2); m.z = group_reduce(m.z, 1, fmax2); m.w = group_reduce(m.w, 1, fmax2);
+            m.x = wave_xor_reduce_strided(m.x, 1, Max()); m.y = wave_xor_reduce_strided(m.y, 1, Max());
+            m.z = wave_xor_reduce_strided(m.z, 1, Max()); m.w = wave_xor_reduce_strided(m.w, 1, Max());
             // exp once: the numerators overwrite the staged logits in place (the permutation is a bijection of pieces)
             float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
             for (int i4 = lane; i4 < E / 4; i4 += 64) {
@@ -204,7 +194,7 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_kernel(DafPrepArgs a)
             entry(i, x, ok);
             if (ok) m = fmaxf(m, x);
         }
-        m = group_reduce(m, a.G, [](float p, float q) { return fmaxf(p, q); });
+        m = wave_xor_reduce_strided(m, a.G, Max());
         const bool all_miss = m == -INFINITY;  // no visible, kept entry for this (anchor, group): weights = 0 (:196-213)
         float s = 0.f;
         for (int i = lane; i < E; i += 64) {
@@ -212,7 +202,7 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_kernel(DafPrepArgs a)
             entry(i, x, ok);
             if (ok) s += expf(x - m);
         }
-        s = group_reduce(s, a.G, [](float p, float q) { return p + q; });
+        s = wave_xor_reduce_strided(s, a.G, Sum());
         float *out = a.weights + anchor * E;
         for (int i = lane; i < E; i += 64) {
             float x; bool ok;
@@ -274,7 +264,7 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_bwd_kernel(DafPrepArgs a)
             } else {
                 float dot = 0.f;
                 for (int i = lane; i < E; i += 64) dot += y[i] * dy[i];
-                dot = group_reduce(dot, a.G, [](float p, float r) { return p + r; });
+                dot = wave_xor_reduce_strided(dot, a.G, Sum());
                 if (STAGE) {
                     for (int i = lane; i < E; i += 64) mine[s_tab[i]] = y[i] * (dy[i] - dot);
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");

@@ -20,8 +20,6 @@
 namespace gf {
 namespace dcn {   // a named namespace: every kernel has external linkage and a stable name
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kThreads = 256;
 constexpr int kGran = 32;          // channel granule: Cin / dg and Co are multiples of it
 constexpr int kFwdBM = 128;        // forward: output pixels per workgroup

@@ -61,23 +61,6 @@ __device__ __forceinline__ float fps_box_bound(float lx, float ly, float lz, flo
     return gx * gx + gy * gy + gz * gz;
 }
 
-// Wave-wide reduction of a 32-bit value: DPP within each row of 16 lanes, then the four row results.  Needs all 64 lanes active.
-template <class Op>
-__device__ __forceinline__ uint32_t wave_reduce(uint32_t v, Op op)
-{
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false));  // row_mirror
-    const uint32_t r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
-    const uint32_t r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
-    return op(op(r0, r1), op(r2, r3));
-}
-struct MaxU { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; } };
-struct MinU { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a < b ? a : b; } };
-struct MaxF { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return __float_as_uint(fmaxf(__uint_as_float(a), __uint_as_float(b))); } };
-struct MinF { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return __float_as_uint(fminf(__uint_as_float(a), __uint_as_float(b))); } };
-
 // A candidate: d as bits (d >= 0, so the bits order like the values), local index, coordinates.
 struct Key {
     uint32_t d, i;

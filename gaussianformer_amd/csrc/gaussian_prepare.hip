@@ -30,30 +30,6 @@ struct PrepareArgs {
     int P, H, W, D, radii_mode, radii_min, grad_is_full;
 };
 
-struct Quat {
-    float w, x, y, z, inv_norm;
-};
-
-// F.normalize(q, dim=-1) (model/utils/utils.py:23): q / max(||q||, 1e-12)
-__device__ __forceinline__ Quat load_unit_quat(const float *q)
-{
-    const float4 v = *reinterpret_cast<const float4 *>(q);
-    const float n = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w);
-    Quat r;
-    r.inv_norm = 1.f / fmaxf(n, 1e-12f);
-    r.w = v.x * r.inv_norm; r.x = v.y * r.inv_norm; r.y = v.z * r.inv_norm; r.z = v.w * r.inv_norm;
-    return r;
-}
-
-// mat1 @ mat2^T without the first row/column (model/utils/utils.py:24-69)
-__device__ __forceinline__ void rotation_of(const Quat &q, float (&R)[3][3])
-{
-    const float w = q.w, x = q.x, y = q.y, z = q.z;
-    R[0][0] = w * w + x * x - y * y - z * z; R[0][1] = 2.f * (x * y - w * z); R[0][2] = 2.f * (x * z + w * y);
-    R[1][0] = 2.f * (x * y + w * z); R[1][1] = w * w - x * x + y * y - z * z; R[1][2] = 2.f * (y * z - w * x);
-    R[2][0] = 2.f * (x * z - w * y); R[2][1] = 2.f * (y * z + w * x); R[2][2] = w * w - x * x - y * y + z * z;
-}
-
 __global__ __launch_bounds__(256) void gf_gaussian_prepare_kernel(PrepareArgs a)
 {
     const int g = blockIdx.x * 256 + threadIdx.x;
@@ -64,7 +40,7 @@ __global__ __launch_bounds__(256) void gf_gaussian_prepare_kernel(PrepareArgs a)
         // Cov = (S R)^T (S R) = R^T S^2 R (gaussian_head.py:111-118), so with R orthonormal
         // Cov^-1 = R^T S^-2 R: the closed form replaces the host LAPACK inverse (:119).
         float R[3][3];
-        rotation_of(load_unit_quat(a.rotations + 4 * (size_t)g), R);
+        rotation_of(unit_quat_aligned16(a.rotations + 4 * (size_t)g), R);
         const float i0 = 1.f / (sx * sx), i1 = 1.f / (sy * sy), i2 = 1.f / (sz * sz);
         float A[3][3];
 #pragma unroll
@@ -136,7 +112,7 @@ __global__ __launch_bounds__(256) void gf_gaussian_prepare_bwd_kernel(PrepareArg
         G[0][0] = c[0]; G[1][1] = c[1]; G[2][2] = c[2]; G[0][1] = c[3]; G[1][2] = c[4]; G[0][2] = c[5];
         G[1][0] = 0.f; G[2][1] = 0.f; G[2][0] = 0.f;
     }
-    const Quat q = load_unit_quat(a.rotations + 4 * (size_t)g);
+    const UnitQuat q = unit_quat_aligned16(a.rotations + 4 * (size_t)g);
     float R[3][3];
     rotation_of(q, R);
     const float s[3] = {a.scales[3 * (size_t)g], a.scales[3 * (size_t)g + 1], a.scales[3 * (size_t)g + 2]};

@@ -1,10 +1,13 @@
-// gf_common.hpp -- shared device/host helpers for libgf_hip.so (gfx950 only).
+// gf_common.hpp -- what is about the library and the splat workspace: options, constants, record layout, workspace carve-up,
+// error macros (gfx950 only).  The kernels' shared device helpers are in gf_wave.hpp and gf_math.hpp, included here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/gf_hip.h"
+#include "gf_math.hpp"
+#include "gf_wave.hpp"
 
 namespace gf {
 
@@ -205,30 +208,5 @@ bool profile_slot(hipEvent_t *before, hipEvent_t *after);  // gf_api.hip
             return GF_ELAUNCH;                                                 \
         }                                                                      \
     } while (0)
-
-// ---- wave-level helpers (wave64) ------------------------------------------------------
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
-
-// number of set bits of `mask` below this lane
-__device__ __forceinline__ int mbcnt(unsigned long long mask)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                          __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-// DPP add-reduce over the 64 lanes; the total ends up in lane 63 and is broadcast through
-// v_readlane.  row_shr 1,2,4(3 steps via 1+2, then 3), row_bcast15, row_bcast31.
-__device__ __forceinline__ float wave_sum(float v)
-{
-    // within each row of 16: inclusive prefix by row_shr, last lane of the row has the row sum
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true)); // row_shr:1
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xf, 0xf, true)); // row_shr:2
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, true)); // row_shr:4
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, true)); // row_shr:8
-    // lane 15 of each row now holds the row sum; combine rows
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xa, 0xf, true)); // row_bcast:15 -> rows 1,3
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xc, 0xf, true)); // row_bcast:31 -> rows 2,3
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 
 }  // namespace gf

@@ -38,27 +38,6 @@ __device__ __forceinline__ float safe_sigmoid_grad(float x, float s)
     return (x >= -kSigmoidClamp && x <= kSigmoidClamp) ? s * (1.f - s) : 0.f;
 }
 
-struct UnitQuat {
-    float w, x, y, z, inv_norm;
-};
-// F.normalize(q, dim=-1) (model/utils/utils.py:23)
-__device__ __forceinline__ UnitQuat unit_quat(const float *q)
-{
-    const float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    UnitQuat r;
-    r.inv_norm = 1.f / fmaxf(n, 1e-12f);
-    r.w = q[0] * r.inv_norm; r.x = q[1] * r.inv_norm; r.y = q[2] * r.inv_norm; r.z = q[3] * r.inv_norm;
-    return r;
-}
-// get_rotation_matrix (model/utils/utils.py:24-69)
-__device__ __forceinline__ void rotation_of(const UnitQuat &q, float (&R)[3][3])
-{
-    const float w = q.w, x = q.x, y = q.y, z = q.z;
-    R[0][0] = w * w + x * x - y * y - z * z; R[0][1] = 2.f * (x * y - w * z); R[0][2] = 2.f * (x * z + w * y);
-    R[1][0] = 2.f * (x * y + w * z); R[1][1] = w * w - x * x + y * y - z * z; R[1][2] = 2.f * (y * z - w * x);
-    R[2][0] = 2.f * (x * z - w * y); R[2][1] = 2.f * (y * z + w * x); R[2][2] = w * w - x * x - y * y + z * z;
-}
-
 template <bool BACKWARD>
 __global__ __launch_bounds__(128) void gf_key_points_kernel(KeyPointArgs a)
 {

@@ -65,79 +65,6 @@ inline size_t carve(LiftWs *w, void *base, int b, int npix, int a)
     return off;
 }
 
-__device__ __forceinline__ float wave_max_f(float v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-// butterfly sum: every lane ends with the same bits (each step adds the same two values in either order)
-__device__ __forceinline__ float wave_sum_f(float v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// (value, index) with the larger value; equal values -> the lower index.  Every lane ends with the same pair.
-__device__ __forceinline__ void wave_argmax(float &v, int &i)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const float ov = __shfl_xor(v, d, 64);
-        const int oi = __shfl_xor(i, d, 64);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-}
-
-__device__ __forceinline__ float wave_incl_scan_f(float v)
-{
-    const int lane = lane_id();
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int wave_incl_scan_i(int v)
-{
-    const int lane = lane_id();
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// exclusive scan over the 256 threads of a workgroup; `lds` holds kWaves ints; `total` gets the sum
-__device__ __forceinline__ int block_excl_scan(int v, int *lds, int &total)
-{
-    const int w = threadIdx.x >> 6, incl = wave_incl_scan_i(v);
-    if (lane_id() == 63) lds[w] = incl;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < kWaves; ++i) {
-        const int t = lds[i];
-        off += i < w ? t : 0;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return off + incl - v;
-}
-
 // img2lidar @ (u d, v d, d, 1), first three rows
 __device__ __forceinline__ void lift_point(const float *M, float ud, float vd, float d, float &x, float &y, float &z)
 {
@@ -180,14 +107,14 @@ __global__ void __launch_bounds__(kThreads) gf_lift_kernel(LiftParams a)
         float m = x[0];
 #pragma unroll
         for (int r = 1; r < R; ++r) m = fmaxf(m, x[r]);
-        m = wave_max_f(m);
+        m = wave_xor_reduce(m, Max());
         float p[R], s = 0.f;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             p[r] = lane + 64 * r < nb ? expf(x[r] - m) : 0.f;
             s += p[r];
         }
-        s = wave_sum_f(s);
+        s = wave_xor_reduce(s, Sum());
         float ps = 0.f;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -213,12 +140,12 @@ __global__ void __launch_bounds__(kThreads) gf_lift_kernel(LiftParams a)
         float cdf[R];
         if (a.uniforms) {
             // normalised pdf p / (eps + sum p), cdf by a wave scan per 64-entry chunk (fixed order)
-            ps = wave_sum_f(ps);
+            ps = wave_xor_reduce(ps, Sum());
             const float den = FLT_EPSILON + ps;
             float carry = 0.f;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const float incl = wave_incl_scan_f(p[r] / den) + carry;
+                const float incl = wave_incl_scan_shfl(p[r] / den) + carry;
                 cdf[r] = incl;
                 carry = __shfl(incl, 63, 64);
             }
@@ -302,7 +229,7 @@ __global__ void __launch_bounds__(kThreads) gf_lift_scan_kernel(int nblk, int *b
         const int i = base + threadIdx.x;
         const int v = i < nblk ? c[i] : 0;
         int total;
-        const int ex = block_excl_scan(v, lds, total);
+        const int ex = block_excl_scan<kWaves>(v, lds, total);
         if (i < nblk) c[i] = carry + ex;
         carry += total;
     }
@@ -325,7 +252,7 @@ __global__ void __launch_bounds__(kThreads) gf_lift_write_kernel(int npix, int A
         const long long s = c0 + threadIdx.x;
         const int k = s < s1 ? keep[base + s] : 0;
         int tot;
-        const int ex = block_excl_scan(k, lds, tot);
+        const int ex = block_excl_scan<kWaves>(k, lds, tot);
         if (s < s1) {
             // candidates in slot order at off + ..., the other slots in slot order behind all candidates
             const long long pos = k ? off + kept + ex : total + s - (off + kept + ex);
@@ -358,14 +285,14 @@ __device__ __forceinline__ void row_probs(const LossParams &a, const float *row,
             x[r] = lane + 64 * r < a.nb ? row[lane + 64 * r] : -INFINITY;
             m = fmaxf(m, x[r]);
         }
-        m = wave_max_f(m);
+        m = wave_xor_reduce(m, Max());
         float s = 0.f;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             p[r] = lane + 64 * r < a.nb ? expf(x[r] - m) : 0.f;
             s += p[r];
         }
-        s = wave_sum_f(s);
+        s = wave_xor_reduce(s, Sum());
 #pragma unroll
         for (int r = 0; r < R; ++r) p[r] = p[r] / s;
     } else {
@@ -399,7 +326,7 @@ __global__ void __launch_bounds__(kThreads) gf_pixel_loss_fwd_kernel(LossParams 
         }
         acc += (double)rs;
     }
-    acc = wave_sum_d(acc);
+    acc = wave_xor_reduce(acc, Sum());
     if (lane == 0) lds[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -449,7 +376,7 @@ __global__ void __launch_bounds__(kThreads) gf_pixel_loss_bwd_kernel(LossParams 
         }
         float *o = grad + q * a.nb;
         if (a.flags & GF_PIXEL_LOSS_SOFTMAX) {
-            dot = wave_sum_f(dot);
+            dot = wave_xor_reduce(dot, Sum());
 #pragma unroll
             for (int r = 0; r < R; ++r)
                 if (lane + 64 * r < a.nb) o[lane + 64 * r] = p[r] * (gp[r] - dot);

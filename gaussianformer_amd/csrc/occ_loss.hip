@@ -92,56 +92,6 @@ inline void carve(OccWs *w, void *workspace, void *scratch, int L, int N, size_t
     if (scratch_bytes) *scratch_bytes = b.off;
 }
 
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    const int lane = lane_id();
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// exclusive scan over a workgroup of NT threads; `lds` holds NT / 64 ints; `total` gets the sum
-template <int NT>
-__device__ __forceinline__ int block_excl_scan(int v, int *lds, int &total)
-{
-    const int w = threadIdx.x >> 6, incl = wave_incl_scan(v);
-    if (lane_id() == 63) lds[w] = incl;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) {
-        const int t = lds[i];
-        off += i < w ? t : 0;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return off + incl - v;
-}
-
-// fixed-order workgroup sum of 256 doubles (result in thread 0)
-__device__ __forceinline__ double block_sum256(double v, double *lds)
-{
-    lds[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) lds[threadIdx.x] += lds[threadIdx.x + s];
-        __syncthreads();
-    }
-    return lds[0];
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;   // lane 0
-}
-
 struct VoxelState { int y; bool kept, lov, ce; };
 
 __device__ __forceinline__ VoxelState voxel_state(const OccParams &a, int n)
@@ -210,7 +160,7 @@ __global__ void __launch_bounds__(1024) gf_occ_offsets_kernel(int NB, OccWs ws)
     for (int i = 0; i < per; ++i)
         if (b0 + i < NB) s += ws.blk[b0 + i];
     int total;
-    int run = block_excl_scan<1024>(s, lds, total);
+    int run = block_excl_scan<16>(s, lds, total);
     for (int i = 0; i < per; ++i)
         if (b0 + i < NB) {
             const int c = ws.blk[b0 + i];
@@ -307,7 +257,7 @@ __global__ void __launch_bounds__(kVox) gf_occ_main_kernel(OccParams a, OccPreds
         }
     }
     int total;
-    const int rank = block_excl_scan<kVox>(v.lov ? 1 : 0, lds, total);
+    const int rank = block_excl_scan<kVox / 64>(v.lov ? 1 : 0, lds, total);
     const int gpos = ws.blk[blockIdx.x] + rank;
     if (l == 0 && n < a.N) ws.pos[n] = v.lov ? gpos : (v.kept ? -1 : -2);
     if (v.lov) {
@@ -360,7 +310,7 @@ __global__ void __launch_bounds__(64) gf_occ_digit_scan_kernel(int T, OccWs ws)
     for (int t0 = 0; t0 < nt; t0 += 64) {
         const int t = t0 + lane_id();
         const int v = t < nt ? h[t] : 0;
-        const int incl = wave_incl_scan(v);
+        const int incl = wave_incl_scan_shfl(v);
         if (t < nt) h[t] = run + incl - v;
         run += __shfl(incl, 63, 64);
     }
@@ -376,7 +326,7 @@ __global__ void __launch_bounds__(256) gf_occ_downsweep_kernel(int N, int T, int
     if (ws.hdr[8 + c] == 0 || base >= M) return;
     const int tid = threadIdx.x, w = tid >> 6;
     int total;
-    const int dbase = block_excl_scan<256>(ws.tot[s * 256 + tid], lds, total);
+    const int dbase = block_excl_scan<4>(ws.tot[s * 256 + tid], lds, total);
     gbase[tid] = dbase + ws.hist[((size_t)s * 256 + tid) * T + t];
     const uint2 *src = in + (size_t)s * N;
     uint2 *dst = out + (size_t)s * N;
@@ -433,7 +383,7 @@ __global__ void __launch_bounds__(256) gf_occ_fg_count_kernel(int N, int T, cons
         if (i < M) f += seg[i].y >> 31;
     }
     int total;
-    block_excl_scan<256>(f, lds, total);
+    block_excl_scan<4>(f, lds, total);
     if (threadIdx.x == 0) ws.fgt[(size_t)s * T + t] = total;
 }
 
@@ -449,7 +399,7 @@ __global__ void __launch_bounds__(256) gf_occ_lovasz_kernel(int N, int T, const 
     int before = 0;
     for (int u = tid; u < t; u += 256) before += ws.fgt[(size_t)s * T + u];
     int total;
-    block_excl_scan<256>(before, lds, total);
+    block_excl_scan<4>(before, lds, total);
     before = total;
     // the tile's keys: coalesced loads into LDS, then eight consecutive keys per thread for the scan
     __shared__ uint2 keys[kTile];
@@ -468,7 +418,7 @@ __global__ void __launch_bounds__(256) gf_occ_lovasz_kernel(int N, int T, const 
         kv[k] = keys[tid * kItems + k];
         f += kv[k].y >> 31;
     }
-    int F = before + block_excl_scan<256>(f, lds, total);   // fg among sorted elements [0, i0)
+    int F = before + block_excl_scan<4>(f, lds, total);   // fg among sorted elements [0, i0)
     const float Gf = (float)G;
     float *deriv = ws.deriv + (size_t)l * N * kC + c;
     double acc = 0.0;

@@ -25,9 +25,6 @@
 
 namespace gf {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-
 struct BwdArgs {
     const float *pts;
     const int *points_int;
@@ -114,10 +111,6 @@ __device__ __forceinline__ void stage_finish(const float2 (&raw)[9], float (&row
     __builtin_amdgcn_wave_barrier();
 }
 
-// Gaussian parameters are read-only here: the constant address space turns the wave-uniform
-// fetches into scalar loads (SGPR operands, no VGPRs spent on them).
-using cfloat_t = const float __attribute__((address_space(4))) *;
-
 __device__ __forceinline__ void box_of(const BwdArgs &a, int g, int lo[3], int hi[3])
 {
     const int m0 = a.means_int[3 * g], m1 = a.means_int[3 * g + 1], m2 = a.means_int[3 * g + 2];
@@ -143,18 +136,6 @@ __device__ __forceinline__ bool pts_are_dense(const BwdArgs &a)
 // (BACKWARD::preprocessCUDA, model/head/localagg/src/backward.cu:8-20, is a racy
 // last-writer-wins scatter; any winner is a legal outcome, we pick a deterministic one).
 // Both steps ride along with the sort kernels below.
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan_u32(uint32_t v)
-{
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, true);
-    return (uint32_t)x;
-}
 
 // The range-partitioned kernel below walks the Gaussians in SPATIAL order: a stable counting
 // sort by grid cell (kSortCells = 8x8 cells over H x W) in three small kernels.  With that order
@@ -225,7 +206,7 @@ __global__ __launch_bounds__(256) void gf_bwd_sort_scan_kernel(BwdArgs a)
         c[k] = i < a.nblk ? row[i] : 0u;
         sum += c[k];
     }
-    const uint32_t incl = wave_inclusive_scan_u32(sum);
+    const uint32_t incl = (uint32_t)wave_incl_scan_dpp((int)sum);
     if (lane == 63) s_w[wave] = incl;
     __syncthreads();
     uint32_t run = incl - sum;
@@ -250,7 +231,7 @@ __global__ __launch_bounds__(256) void gf_bwd_sort_scatter_kernel(BwdArgs a)
     const int g = blockIdx.x * 256 + threadIdx.x, wave = threadIdx.x >> 6;
     if (threadIdx.x < 64) {  // exclusive prefix of the 64 cell totals
         const uint32_t t = a.sort_hist[(size_t)kSortCells * a.nblk + threadIdx.x];
-        s_base[threadIdx.x] = wave_inclusive_scan_u32(t) - t;
+        s_base[threadIdx.x] = (uint32_t)wave_incl_scan_dpp((int)t) - t;
     }
     const bool valid = g < a.P;
     const int cell = valid ? sort_cell(a, g) : 0;
@@ -355,8 +336,7 @@ __device__ __forceinline__ float wave_reduce32(float (&v)[32], int lane)
 #pragma unroll
     for (int j = 0; j < 2; ++j) z[j] = fold_add<0x141, 4>(y[2 * j], y[2 * j + 1], lane);  // row_half_mirror: l -> 7 - l
     float t = fold_add<0x4e, 2>(z[0], z[1], lane);                                         // quad_perm [2,3,0,1] = lane ^ 2
-    t += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, t), 0xb1, 0xf, 0xf, true));  // lane ^ 1
-    return t;
+    return dpp_add<0xb1>(t);  // quad_perm [1,0,3,2] = lane ^ 1
 }
 
 // index of the value a lane ends up with: value bit k is decided by the (k+1)-th step
@@ -424,7 +404,7 @@ __global__ __launch_bounds__(256, VARIANT == GF_SPLAT_BASE ? 4 : 3) void gf_spla
     for (int k = 0; k < 4; ++k) {
         const int gi = blo * 256 + k * 64 + lane;
         const uint32_t vv = gi < a.P ? a.vols[gi] : 0u;
-        const uint32_t incl = wave_inclusive_scan_u32(vv);
+        const uint32_t incl = (uint32_t)wave_incl_scan_dpp((int)vv);
         const uint32_t tot = __builtin_amdgcn_readlane(incl, 63);
         if (r0 - gstart < (unsigned long long)tot) {
             const unsigned long long m = __builtin_amdgcn_ballot_w64(gstart + incl > r0);

@@ -49,9 +49,6 @@
 
 namespace gf {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 union H8 {
     h8 v;
     fp16x2 p[4];
@@ -105,30 +102,6 @@ constexpr int kMRowAt = 768;
 static_assert(kMRowAt + 2 * kWRow <= 1536 + 3 * kMList, "the bitmask row fits over the slot's upper half and the list");
 static_assert(3 * kMList <= kMRowAt, "the dense-word compaction borrows the lower half of the record slot");
 static_assert(kMLdsDwords * 4 <= 20480, "eight single-wave workgroups per CU");
-
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, true);
-    return v;
-}
-
-// three f16 terms of an fp64 value (see splat_fwd.hip)
-__device__ __forceinline__ void split3(double t, _Float16 &a, _Float16 &b, _Float16 &c)
-{
-    float hi = (float)t;
-    asm volatile("" : "+v"(hi));
-    const float lo = (float)(t - (double)hi);
-    a = (_Float16)hi;
-    float r = (hi - (float)a) + lo;
-    asm volatile("" : "+v"(r));
-    b = (_Float16)r;
-    c = (_Float16)(r - (float)b);
-}
 
 // f16 hi + lo of sixteen fp32 values held as an MFMA D fragment: the two K chunks (registers 0..7, 8..15) of a B operand
 __device__ __forceinline__ void split16(const f32x16 &d, H8 (&hi)[2], H8 (&lo)[2])
@@ -307,12 +280,9 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
     const int per_super = 4 * ((a.D + 7) >> 3);
     const int per_xcd = ((a.nsx * a.nsy + 7) >> 3) * per_super;
     const uint32_t m_ps = a.m_ps, m_nsy = a.m_nsy;
-    using gptr = const __attribute__((address_space(1))) void *;
-    using lptr = __attribute__((address_space(3))) void *;
 
     // lattice of the voxel centres (fp64): position of voxel index i along an axis = p0 + i * step
-    using cflt_t = const float __attribute__((address_space(4))) *;
-    cflt_t cp = (cflt_t)(uintptr_t)a.pts;
+    cfloat_t cp = (cfloat_t)(uintptr_t)a.pts;
     const double p0x = cp[0], p0y = cp[1], p0z = cp[2];
     const double sx = a.H > 1 ? (double)cp[3 * (size_t)a.W * a.D] - p0x : 1.0;
     const double sy = a.W > 1 ? (double)cp[3 * (size_t)a.D + 1] - p0y : 1.0;
@@ -445,7 +415,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
                     wd[k] = (k < kw && w < a.nwords) ? wd[k] : 0ull;
                     mine += wd[k] != 0ull ? 1 : 0;
                 }
-                const int incl_nz = wave_incl_scan(mine);
+                const int incl_nz = wave_incl_scan_dpp(mine);
                 const int nd = __builtin_amdgcn_readlane(incl_nz, 63);
                 if (nd <= kWDense) {
                     int p = incl_nz - mine;
@@ -490,7 +460,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
                             cn[q] = __builtin_popcountll(bb[q]);
                         }
 #pragma unroll
-                        for (int q = 0; q < 3; ++q) in_[q] = wave_incl_scan(cn[q]);
+                        for (int q = 0; q < 3; ++q) in_[q] = wave_incl_scan_dpp(cn[q]);
 #pragma unroll
                         for (int q = 0; q < 3; ++q) tt[q] = __builtin_amdgcn_readlane(in_[q], 63);
                         tot = tt[0] + tt[1] + tt[2];
@@ -508,7 +478,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
                             const unsigned long long bits = i < nd ? s_db[i] : 0ull;
                             const uint32_t id0 = (i < nd ? s_dw[i] : 0u) * 64u;
                             const int cnt = __builtin_popcountll(bits);
-                            const int incl = wave_incl_scan(cnt);
+                            const int incl = wave_incl_scan_dpp(cnt);
                             const int t = __builtin_amdgcn_readlane(incl, 63);
                             if (tot + t > kMList) {
                                 fits = false;
@@ -679,7 +649,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
                     const int w = 64 * c + lane;
                     unsigned long long bits = w < a.nwords ? bm_row[w] : 0ull;
                     const int cnt = __builtin_popcountll(bits);
-                    const int incl = wave_incl_scan(cnt);
+                    const int incl = wave_incl_scan_dpp(cnt);
                     const int total = __builtin_amdgcn_readlane(incl, 63);
                     int pos = -1;
                     if (total <= kMList) {

@@ -68,8 +68,6 @@ struct PrepArgs {
                              // they are checked in the records pass on EVERY call, GF_PTS_ASSUME_DENSE included)
 };
 
-__device__ __forceinline__ int wave_inclusive_scan(int v);
-
 constexpr int kVerifyBlocks = 4096;    // verification waves; render thread t reads 16 verdicts
 constexpr int kPrepSuperChunk = 4096;  // bitmask words in LDS per pass of the prep kernel (32 KB)
 
@@ -363,7 +361,7 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
     if (a.unit_totals) {
         const int cnt = nonempty ? (((hi[0] - 1) >> 2) - (lo[0] >> 2) + 1) * (((hi[1] - 1) >> 2) - (lo[1] >> 2) + 1) *
                                        (((hi[2] - 1) >> 3) - (lo[2] >> 3) + 1) : 0;
-        const int incl = wave_inclusive_scan(cnt);
+        const int incl = wave_incl_scan_dpp(cnt);
         unit_first = (uint32_t)(incl - cnt);
         const bool any_big = __builtin_amdgcn_ballot_w64(cnt > kBwdBigRows) != 0ull;
         if (lane == 63) a.unit_totals[word] = (uint32_t)incl | (any_big ? 0x80000000u : 0u);
@@ -644,7 +642,7 @@ __device__ __forceinline__ bool finish_row_layout(const RenderArgs &a, uint32_t 
         t[k] = kPer * lane + k < nw ? (t[k] & 0x7FFFFFFFu) : 0u;
         mine += t[k];
     }
-    const uint32_t incl = (uint32_t)wave_inclusive_scan((int)mine);
+    const uint32_t incl = (uint32_t)wave_incl_scan_dpp((int)mine);
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     uint32_t run = incl - mine;
 #pragma unroll
@@ -687,7 +685,7 @@ __device__ __forceinline__ bool finish_row_layout_long(const RenderArgs &a, uint
             mine += v;
         }
     }
-    const uint32_t incl = (uint32_t)wave_inclusive_scan((int)mine);
+    const uint32_t incl = (uint32_t)wave_incl_scan_dpp((int)mine);
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     const uint32_t base = incl - mine;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -768,7 +766,6 @@ __device__ __forceinline__ float gauss_exp(RecPtr rec, float px, float py, float
 // compiles to packed VALU (v_pk_*_f32: 2 results per instruction; measured 4.9 vs 2 x 3.4-4.7
 // cycles per wave instruction on gfx950).  Lane-wise identical to gauss_exp (same operation
 // order), so the dense and the arbitrary-points bodies still agree bit for bit.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 
 template <int EXP, typename RecPtr>
@@ -863,22 +860,6 @@ __device__ __forceinline__ uint32_t mask_z32(int a, int b)
 {
     const uint32_t m4 = ((1u << b) - 1u) & ~((1u << a) - 1u);  // < 2^4
     return m4 * 0x11111111u;
-}
-
-// records are read-only for the render kernels: the constant address space makes the
-// wave-uniform record fetch a scalar (SMEM) load straight into SGPRs.
-using crec_t = const float __attribute__((address_space(4))) *;
-
-// wave-wide inclusive prefix sum with DPP adds (row_shr 1,2,4,8, row_bcast 15/31)
-__device__ __forceinline__ int wave_inclusive_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, true);
-    return v;
 }
 
 // Head epilogue on the accumulators (model/head/gaussian_head.py:164-185; same rules as
@@ -1111,7 +1092,7 @@ __global__ __launch_bounds__(kBlock, kRenderWavesPerSimd) void gf_splat_render_k
                 // box loads and its only memory round trip is the bitmask word itself
                 hits = word;
                 const int cnt = __builtin_popcountll(hits);
-                const int incl = wave_inclusive_scan(cnt);
+                const int incl = wave_incl_scan_dpp(cnt);
                 if (lane == 63) s_scan[wave] = (uint32_t)incl;
                 __syncthreads();
                 off = incl - cnt;
@@ -1178,7 +1159,7 @@ __global__ __launch_bounds__(kBlock, kRenderWavesPerSimd) void gf_splat_render_k
                     const unsigned long long mB =
                         ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(mBhi, j) << 32) |
                         (unsigned long long)(uint32_t)__builtin_amdgcn_readlane(mBlo, j);
-                    crec_t recp = (crec_t)(uintptr_t)(a.records + (size_t)g * kRecDwords);
+                    cfloat_t recp = (cfloat_t)(uintptr_t)(a.records + (size_t)g * kRecDwords);
                     float rec[kRecUsed];  // the whole record in SGPRs, one scalar round trip
 #pragma unroll
                     for (int q = 0; q < kRecUsed; ++q) rec[q] = recp[q];
@@ -1288,9 +1269,6 @@ __global__ __launch_bounds__(kBlock, kRenderWavesPerSimd) void gf_splat_render_k
 // Work decomposition as in gf_splat_render_kernel (tile = workgroup, double brick = wave, the supertile's candidates in
 // an LDS list); the hits of a wave are compacted into a per-wave LDS queue (id + the four 32-voxel masks) and leave it
 // in groups of 32.  A 32-voxel block b of the double brick = lanes [32 (b&1), 32 (b&1) + 32) of brick b >> 1.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 union H8 {
     h8 v;
     fp16x2 p[4];
@@ -1302,33 +1280,6 @@ constexpr int kListCapM = 2304;  // tile list entries of the matrix-core kernel:
 constexpr int kQCap = 128;  // hit queue entries per wave, a ring (power of two): <= 63 waiting + a batch of <= 64
 constexpr int kSRow = 36;  // floats per channel row of the staged opacity * semantics (32 Gaussians + pad: conflict-free b128 reads)
 
-// three f16 terms of an fp64 value (33 bits): the value as a (hi, lo) pair of floats, then exact fp32 residuals
-__device__ __forceinline__ void split3(double t, _Float16 &a, _Float16 &b, _Float16 &c)
-{
-    float hi = (float)t;
-    asm volatile("" : "+v"(hi));  // keeps (half)(float)double from becoming a software double -> half conversion
-    const float lo = (float)(t - (double)hi);
-    a = (_Float16)hi;
-    float r = (hi - (float)a) + lo;
-    asm volatile("" : "+v"(r));
-    b = (_Float16)r;
-    c = (_Float16)(r - (float)b);
-}
-
-// LDS-DMA issued from inline asm.  hipcc's waitcnt pass treats a global_load_lds it can see as a pending write to ALL of LDS and puts a
-// full `s_waitcnt vmcnt(0)` in front of the next LDS access -- in the wave-autonomous kernel that drained the record request of
-// group k + 1 before group k's S' rows were read, and the prefetched bitmask row before the epilogue's staging writes: the very
-// round trips those requests were issued early to hide (found in the ISA, round 5).  Issued from asm the request is invisible
-// to that pass, and every wait for it is an explicit `s_waitcnt vmcnt(N)` in the source.  The compiler's own vmcnt waits stay
-// safe: they count outstanding operations, which only makes them wait longer when these requests are in flight.
-__device__ __forceinline__ void lds_dma16(const __attribute__((address_space(1))) void *g, __attribute__((address_space(3))) void *l)
-{
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"((uint32_t)(uintptr_t)l) : "memory", "m0");
-}
-__device__ __forceinline__ void lds_dma4(const __attribute__((address_space(1))) void *g, __attribute__((address_space(3))) void *l)
-{
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(g), "s"((uint32_t)(uintptr_t)l) : "memory", "m0");
-}
 template <bool LABELS>
 __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderArgs a)
 {
@@ -1425,8 +1376,7 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
     for (int i = lane; i < (kC + 1) * kSRow; i += 64) S[i] = 0.f;
 
     // lattice of the voxel centres (fp64): position of voxel index i along an axis = p0 + i * step
-    using cflt_t = const float __attribute__((address_space(4))) *;
-    cflt_t cp = (cflt_t)(uintptr_t)a.pts;
+    cfloat_t cp = (cfloat_t)(uintptr_t)a.pts;
     const double p0x = cp[0], p0y = cp[1], p0z = cp[2];
     const double sx = a.H > 1 ? (double)cp[3 * (size_t)a.W * a.D] - p0x : 1.0;
     const double sy = a.W > 1 ? (double)cp[3 * (size_t)a.D + 1] - p0y : 1.0;
@@ -1465,8 +1415,6 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
         const char *rec = reinterpret_cast<const char *>(a.records + (size_t)id * kRecDwords);
         const int o3 = (3 + 3 * h) * 16, o4 = (4 + 3 * h) * 16, o5 = (h ? 7 : 5) * 16;
         char *dst = reinterpret_cast<char *>(slot);
-        using gptr = const __attribute__((address_space(1))) void *;
-        using lptr = __attribute__((address_space(3))) void *;
         lds_dma16((gptr)(rec), (lptr)(dst));
         lds_dma16((gptr)(rec + 16), (lptr)(dst + 1024));
         lds_dma16((gptr)(rec + 32), (lptr)(dst + 2048));
@@ -1530,7 +1478,7 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
             const int npieces = (a.nwords + 127) >> 7;
             for (int i = wave; i < npieces; i += 4) {
                 const int w0 = min(128 * i + 2 * lane, a.nrow - 2);
-                lds_dma16((const __attribute__((address_space(1))) void *)(bm + w0), (__attribute__((address_space(3))) void *)(s_row + 128 * i));
+                lds_dma16((gptr)(bm + w0), (lptr)(s_row + 128 * i));
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
@@ -1538,7 +1486,7 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
                 const int w = c * kBlock + tid;
                 const unsigned long long bits = w < a.nwords ? s_row[w] : 0ull;
                 const int cnt = __builtin_popcountll(bits);
-                const int incl = wave_inclusive_scan(cnt);
+                const int incl = wave_incl_scan_dpp(cnt);
                 if (lane == 63) s_tot[4 * c + wave] = (uint32_t)incl;
                 if (w < a.nwords) s_excl[w] = (uint16_t)(incl - cnt);   // < 64 * 64: hits of earlier lanes of this wave
             }
@@ -1608,7 +1556,7 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
                 w_next += kBlock;
                 hits = wi < a.nwords ? bm[wi] : 0ull;
                 const int cnt = __builtin_popcountll(hits);
-                const int incl = wave_inclusive_scan(cnt);
+                const int incl = wave_incl_scan_dpp(cnt);
                 if (lane == 63) s_scan[wave] = (uint32_t)incl;
                 __syncthreads();
                 off = incl - cnt;
@@ -1635,8 +1583,6 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
             // traffic of the accumulation are the record requests -- no `s_waitcnt vmcnt(0)` of a box load drains them.
             for (int b0 = wave * 64; b0 < list_len; b0 += kBlock) {
                 const uint32_t id = s_lg[min(b0 + lane, list_len - 1)];
-                using gptr = const __attribute__((address_space(1))) void *;
-                using lptr = __attribute__((address_space(3))) void *;
                 lds_dma4((gptr)(&a.boxes[id].x), (lptr)(s_blo + b0));
                 lds_dma4((gptr)(&a.boxes[id].y), (lptr)(s_bhi + b0));
             }
@@ -1827,9 +1773,6 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
         // ---- accumulators C[channel (r&3) + 8 (r>>2) + 4 h][voxel n of block b] -> out_logits.  Lane (n, h) holds, for its
         // voxel, channels 4h..4h+3 (r = 0..3), 8+4h..11+4h (r = 4..7) and -- h = 0 only -- 16, 17 (r = 8, 9).
         if (!LABELS || a.out_logits) {
-            typedef __attribute__((address_space(1))) float gfloat;   // global address space: keeps the stores global_store (not flat)
-            typedef float nt4v __attribute__((ext_vector_type(4), aligned(4)));
-            typedef __attribute__((address_space(1))) nt4v nt4;
             if ((a.D & 3) == 0) {
                 // Rows [voxel-in-brick][18] of both bricks go through the wave's (now idle) staging area with 8-byte LDS
                 // writes -- five per block -- and leave as 16-byte stores over the 16 runs of 288 contiguous bytes a brick
@@ -2037,8 +1980,6 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     // unit index -> (supertile, quarter, z brick) -> supertile row and column: divisions by launch constants, as multiplications
     // by rounded-up reciprocals (exact for the < 2^20 indices of a grid)
     const uint32_t m_ps = a.m_ps, m_nsy = a.m_nsy;
-    using gptr = const __attribute__((address_space(1))) void *;
-    using lptr = __attribute__((address_space(3))) void *;
     int local = (int)(blockIdx.x >> 3);
     bool row_there = false;  // the bitmask row of unit `local` has already been requested into s_row
     // The first unit's bitmask row is requested before anything else: its round trip then runs under the verdict loads and the
@@ -2254,7 +2195,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                     wd[k] = (k < kw && w < a.nwords) ? wd[k] : 0ull;
                     mine += wd[k] != 0ull ? 1 : 0;
                 }
-                const int incl_nz = wave_inclusive_scan(mine);
+                const int incl_nz = wave_incl_scan_dpp(mine);
                 const int nd = __builtin_amdgcn_readlane(incl_nz, 63);
                 if (nd <= kWDense) {
                     int p = incl_nz - mine;
@@ -2301,7 +2242,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                             cn[q] = __builtin_popcountll(bb[q]);
                         }
 #pragma unroll
-                        for (int q = 0; q < 3; ++q) in_[q] = wave_inclusive_scan(cn[q]);
+                        for (int q = 0; q < 3; ++q) in_[q] = wave_incl_scan_dpp(cn[q]);
 #pragma unroll
                         for (int q = 0; q < 3; ++q) tt[q] = __builtin_amdgcn_readlane(in_[q], 63);
                         tot = tt[0] + tt[1] + tt[2];
@@ -2318,7 +2259,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                             const unsigned long long bits = i < nd ? s_db[i] : 0ull;
                             const uint32_t id0 = (i < nd ? s_dw[i] : 0u) * 64u;
                             const int cnt = __builtin_popcountll(bits);
-                            const int incl = wave_inclusive_scan(cnt);
+                            const int incl = wave_incl_scan_dpp(cnt);
                             const int t = __builtin_amdgcn_readlane(incl, 63);
                             if (tot + t > kWList) {
                                 fits = false;
@@ -2362,7 +2303,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         sm = left >= 64 ? sm : (left > 0 ? sm & bits_below(left) : 0ull);
                     }
                     const int cw = __builtin_popcountll(sm);
-                    const int incl_w = wave_inclusive_scan(cw);
+                    const int incl_w = wave_incl_scan_dpp(cw);
                     const int nd = __builtin_amdgcn_readlane(incl_w, 63);
                     const int cnt = min(nd - long_lo, kLDense);
                     {   // word index of every rank in [long_lo, long_lo + cnt): each lane walks its own bits
@@ -2393,7 +2334,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         bits = in ? bits : 0ull;
                         const uint32_t id0 = (uint32_t)d_w[jc] * 64u;
                         const int cb = __builtin_popcountll(bits);
-                        const int incl = wave_inclusive_scan(cb);
+                        const int incl = wave_incl_scan_dpp(cb);
                         const int total = __builtin_amdgcn_readlane(incl, 63);
                         int pos = -1, adm = 64;
                         if (tot + total <= kLIds) {
@@ -2439,7 +2380,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                     const int w = 64 * c + lane;
                     unsigned long long bits = w < a.nwords ? s_row[w] : 0ull;
                     const int cnt = __builtin_popcountll(bits);
-                    const int incl = wave_inclusive_scan(cnt);
+                    const int incl = wave_incl_scan_dpp(cnt);
                     const int total = __builtin_amdgcn_readlane(incl, 63);
                     int pos = -1;
                     if (total <= kWList) {
@@ -2706,9 +2647,6 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                 }
             }
             // ---- accumulators C[channel (q&3) + 8 (q>>2) + 4 h][voxel n of block b] -> out_logits (see the tile kernel)
-            typedef __attribute__((address_space(1))) float gfloat;
-            typedef float nt4v __attribute__((ext_vector_type(4), aligned(4)));
-            typedef __attribute__((address_space(1))) nt4v nt4;
             if ((a.D & 3) == 0) {
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {

@@ -28,8 +28,6 @@ constexpr int kPairTile = 128;   // pairs per workgroup tile of the gather-GEMM 
 constexpr int kWgradChunk = 512;  // pairs per workgroup of the weight gradient
 constexpr int kGemmRun = 8;       // consecutive tiles of one offset a workgroup of the run kernel (gf_subm_gemm_bf16_run_kernel) walks
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 struct SubmTables {
     int *head;              // [cells]  first point of the cell's list, -1 = empty
     int *next;              // [N]      ... in insertion order (atomicExch: differs from run to run)
@@ -69,26 +67,24 @@ struct SubmArgs {
 
 constexpr unsigned long long kSubmOverCapacity = 4ull;  // bit of total[1]
 
-inline size_t subm_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static SubmTables subm_carve(void *base, int N, long long cells, int K3, size_t *bytes)
 {
     char *p = (char *)base;
     size_t off = 0;
     SubmTables t;
-    t.head = (int *)(p + off); off += subm_align((size_t)cells * 4);
-    t.next = (int *)(p + off); off += subm_align((size_t)N * 4);
-    t.next2 = (int *)(p + off); off += subm_align((size_t)N * 4);
-    t.first2 = (int *)(p + off); off += subm_align((size_t)N * 4);
-    t.slot_first = (int *)(p + off); off += subm_align((size_t)N * K3 * 4);
-    t.cnt = (unsigned short *)(p + off); off += subm_align((size_t)N * K3 * 2);
-    t.kcount = (unsigned long long *)(p + off); off += subm_align((size_t)K3 * 8);
-    t.kstart = (unsigned int *)(p + off); off += subm_align((size_t)(K3 + 1) * 4);
-    t.tile_start = (unsigned int *)(p + off); off += subm_align((size_t)(K3 + 1) * 4);
-    t.kcursor = (unsigned int *)(p + off); off += subm_align((size_t)K3 * 4);
-    t.kmask = (unsigned char *)(p + off); off += subm_align((size_t)N * 49);  // K <= 7
-    t.chunk_start = (unsigned int *)(p + off); off += subm_align((size_t)(K3 + 1) * 4);
-    t.run_start = (unsigned int *)(p + off); off += subm_align((size_t)(K3 + 1) * 4);
+    t.head = (int *)(p + off); off += align256((size_t)cells * 4);
+    t.next = (int *)(p + off); off += align256((size_t)N * 4);
+    t.next2 = (int *)(p + off); off += align256((size_t)N * 4);
+    t.first2 = (int *)(p + off); off += align256((size_t)N * 4);
+    t.slot_first = (int *)(p + off); off += align256((size_t)N * K3 * 4);
+    t.cnt = (unsigned short *)(p + off); off += align256((size_t)N * K3 * 2);
+    t.kcount = (unsigned long long *)(p + off); off += align256((size_t)K3 * 8);
+    t.kstart = (unsigned int *)(p + off); off += align256((size_t)(K3 + 1) * 4);
+    t.tile_start = (unsigned int *)(p + off); off += align256((size_t)(K3 + 1) * 4);
+    t.kcursor = (unsigned int *)(p + off); off += align256((size_t)K3 * 4);
+    t.kmask = (unsigned char *)(p + off); off += align256((size_t)N * 49);  // K <= 7
+    t.chunk_start = (unsigned int *)(p + off); off += align256((size_t)(K3 + 1) * 4);
+    t.run_start = (unsigned int *)(p + off); off += align256((size_t)(K3 + 1) * 4);
     t.total = (unsigned long long *)(p + off); off += 256;
     *bytes = off;
     return t;
@@ -393,7 +389,6 @@ __global__ __launch_bounds__(256, 4) void gf_subm_gemm_kernel(SubmArgs a)
 // chain of fp32 FMAs has per step.  The feature half-rows are split in registers (per K chunk), the weight slice is
 // split once per workgroup on its way into LDS, stored in B-operand order ([term][chunk][32-column group][K half][column]
 // x 8 bf16 = one ds_read_b128 per operand).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 union BF8 {
     bf16x8 v;
     __bf16 e[8];
@@ -608,7 +603,6 @@ __global__ __launch_bounds__(256, 2) void gf_subm_gemm_bf16_run_kernel(SubmArgs 
 // gather brings MFMA operands (16 bytes = 8 channels of one term) and the GEMM's vector work per tile is the epilogue.  With
 // bf16 this was built and lost (three terms = half again as many gathered bytes); two f16 terms are the fp32 row's bytes.
 // Error of a product ~ 2^-21 relative (measured against the fp64 definition in tests/test_subm_conv.py, same 3e-5 bound).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 union HF8 {
     f16x8 v;
     _Float16 e[8];
@@ -1235,7 +1229,7 @@ extern "C" int gf_subm_rulebook_build_range(int N, int batch, int X, int Y, int 
 
 extern "C" size_t gf_subm_apply_scratch_bytes(int N, int Cin)
 {
-    return N > 0 && Cin > 0 ? gf::subm_align((size_t)N * Cin * 4) + gf::subm_align((size_t)N * 4) : 0;
+    return N > 0 && Cin > 0 ? gf::align256((size_t)N * Cin * 4) + gf::align256((size_t)N * 4) : 0;
 }
 
 static int subm_conv_apply_impl(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
@@ -1271,7 +1265,7 @@ static int subm_conv_apply_impl(int N, int batch, int X, int Y, int Z, int K, in
         GF_CHECK_ARG(scratch_bytes >= gf_subm_apply_scratch_bytes(N, Cin) && ((uintptr_t)scratch & 15) == 0, "scratch too small or not 16-byte aligned");
         SubmSplit sp;
         uint4 *rows16 = (uint4 *)scratch;
-        int *row_exp = (int *)((char *)scratch + subm_align((size_t)N * Cin * 4));
+        int *row_exp = (int *)((char *)scratch + align256((size_t)N * Cin * 4));
         sp.rows16 = rows16; sp.row_exp = row_exp;
         const unsigned sblocks = (unsigned)(((long long)N * (Cin / 8) + 255) / 256);
         if (Cin == 128) hipLaunchKernelGGL(gf_subm_split_rows_kernel<128>, dim3(sblocks), dim3(256), 0, stream, features, N, rows16, row_exp);
