@@ -7,6 +7,8 @@ current HIP stream.
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GF_LIB selects an instrumentation build (-DGF_TIMELINE=1, -DGF_DAF_TL) made by build.build(lib_name=...) (tools/ only)
 LIB_PATH = os.environ.get("GF_LIB") or os.path.join(_HERE, "csrc", "libgf_hip.so")
@@ -175,5 +177,87 @@ def require_gpu(*tensors):
 
 
 def current_stream(device):
-    import torch
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def as_arg(t, dtype=torch.float32):
+    """An input as the library reads it: detached, of ``dtype`` (converted only when it differs) and contiguous; ``None`` stays
+    ``None``."""
+    if t is None:
+        return None
+    t = t.detach()
+    if t.dtype != dtype:
+        t = t.to(dtype)
+    return t.contiguous()
+
+
+_Tensor = torch.Tensor   # (a global of this module: call() tests every argument against it)
+
+
+def call(name, device, *args):
+    """The one way to launch: calls the entry point ``name`` of the loaded library with ``args`` -- every tensor as its data
+    pointer, ``None`` (NULL), numbers and ctypes objects as they are -- and torch's current stream of ``device`` appended, with
+    ``device`` current during the call (the launch goes to the tensors' device, not the current one; no guard is entered when
+    it is current already), and raises under that same name if it fails.  The callers have refused CPU tensors already
+    (``require_gpu``); a ``device`` that is not a GPU gets no guard and a NULL stream, for calls the library refuses before it
+    touches a device."""
+    fn = getattr(_lib or load(), name)
+    argv = [a.data_ptr() if isinstance(a, _Tensor) else a for a in args]
+    if device.type != "cuda":
+        rc = fn(*argv, None)
+    elif torch.cuda.current_device() == device.index:
+        rc = fn(*argv, torch.cuda.current_stream(device).cuda_stream)
+    else:
+        with torch.cuda.device(device):
+            rc = fn(*argv, torch.cuda.current_stream(device).cuda_stream)
+    if rc:
+        check(rc, name)
+
+
+def host_copy(words, device):
+    """``(host, event)``: the device tensor ``words`` copied to pinned host memory on ``device``'s current stream, and an event
+    behind the copy -- to be queried, never waited for.  ``(None, None)`` while the stream is being captured into a graph: no
+    host allocation there."""
+    if torch.cuda.is_current_stream_capturing():
+        return None, None
+    host = torch.empty(words.shape, dtype=words.dtype, pin_memory=True)
+    host.copy_(words, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record(torch.cuda.current_stream(device))
+    return host, event
+
+
+class StreamScratch:
+    """Scratch reused across calls, one grow-only buffer per (device, stream): the kernels of a call run on torch's current
+    stream, so two calls on different streams must not share it.  A buffer is allocated while its stream is current, so the
+    caching allocator frees it in that stream's order.  The cache is bounded: after a hand-out, while it holds more than
+    ``MAX_STREAMS`` buffers the least recently used one goes -- a process that keeps creating streams does not accumulate a
+    buffer per stream ever used, and a recycled stream handle meets at worst its own old buffer.  A new buffer has at least
+    ``min_bytes``, and its first ``zeroed_bytes`` are zeroed then and never afterwards."""
+    MAX_STREAMS = 8
+
+    def __init__(self, min_bytes=0, zeroed_bytes=0, stream_of=current_stream):
+        self.min_bytes, self.zeroed_bytes, self.stream_of = min_bytes, zeroed_bytes, stream_of
+        self._cache = {}
+        self._uses = 0
+
+    def get(self, device, nbytes):
+        """The current stream's buffer, at least ``nbytes`` long."""
+        key = (device.type, device.index, self.stream_of(device))
+        buf = self._cache.pop(key, None)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(max(nbytes, self.min_bytes), dtype=torch.uint8, device=device)
+            if self.zeroed_bytes:
+                buf[:self.zeroed_bytes].zero_()
+        self._cache[key] = buf              # most recently used last
+        while len(self._cache) > self.MAX_STREAMS:
+            self._cache.pop(next(iter(self._cache)))
+        self._uses += 1
+        return buf
+
+    def stamp(self, device):
+        """(stream, its buffer, number of hand-outs of this cache so far): equal stamps = nobody has been given this cache's
+        scratch in between, so the buffer still holds what the last call left in it."""
+        key = (device.type, device.index, self.stream_of(device))
+        buf = self._cache.get(key)
+        return (key, None if buf is None else buf.data_ptr(), self._uses)

@@ -77,13 +77,10 @@ class _ModulatedDeformConv2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, offset, mask, weight, bias, stride, padding, dilation, groups, deform_groups):
         geom, out_shape = _check(input, offset, mask, weight, bias, stride, padding, dilation, groups, deform_groups)
-        x, off, m, w = (t.detach().contiguous() for t in (input, offset, mask, weight))
-        b = None if bias is None else bias.detach().contiguous()
+        x, off, m, w, b = (_lib.as_arg(t) for t in (input, offset, mask, weight, bias))   # (fp32 already: _check)
         out = torch.empty(out_shape, dtype=torch.float32, device=input.device)
         ws, nbytes = _workspace(geom, False, input.device)
-        _lib.check(_lib.load().gf_dcn_forward(*geom, x.data_ptr(), off.data_ptr(), m.data_ptr(), w.data_ptr(), _lib.ptr(b),
-                                              out.data_ptr(), ws.data_ptr(), nbytes, _lib.current_stream(input.device)),
-                   "gf_dcn_forward")
+        _lib.call("gf_dcn_forward", input.device, *geom, x, off, m, w, b, out, ws, nbytes)
         ctx.geom = geom
         ctx.has_bias = bias is not None
         ctx.save_for_backward(x, off, m, w)
@@ -93,7 +90,7 @@ class _ModulatedDeformConv2d(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, off, m, w = ctx.saved_tensors
         need = ctx.needs_input_grad
-        go = grad_out.contiguous()
+        go = _lib.as_arg(grad_out)
         gi = torch.empty_like(x) if need[0] else None
         goff = torch.empty_like(off) if need[1] else None
         gm = torch.empty_like(m) if need[2] else None
@@ -101,10 +98,7 @@ class _ModulatedDeformConv2d(torch.autograd.Function):
         gb = torch.empty(w.shape[0], dtype=torch.float32, device=x.device) if (ctx.has_bias and need[4]) else None
         if any(t is not None for t in (gi, goff, gm, gw, gb)):
             ws, nbytes = _workspace(ctx.geom, True, x.device)
-            _lib.check(_lib.load().gf_dcn_backward(*ctx.geom, x.data_ptr(), off.data_ptr(), m.data_ptr(), w.data_ptr(),
-                                                   go.data_ptr(), _lib.ptr(gi), _lib.ptr(goff), _lib.ptr(gm), _lib.ptr(gw),
-                                                   _lib.ptr(gb), ws.data_ptr(), nbytes, _lib.current_stream(x.device)),
-                       "gf_dcn_backward")
+            _lib.call("gf_dcn_backward", x.device, *ctx.geom, x, off, m, w, go, gi, goff, gm, gw, gb, ws, nbytes)
         return gi, goff, gm, gw, gb, None, None, None, None, None
 
 

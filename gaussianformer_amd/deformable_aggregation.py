@@ -4,6 +4,8 @@
 dtype coercions, ``once_differentiable`` backward that accumulates into three zeroed
 buffers, ``feature_maps_format``) and calls the HIP kernels through the C ABI.
 """
+import ctypes
+
 import torch
 from torch.autograd.function import Function, once_differentiable
 
@@ -16,36 +18,16 @@ def deformable_aggregation_forward(mc_ms_feat, spatial_shape, scale_start_index,
     (ops/src/deformable_aggregation.cpp:41-71): dims are read from the tensor sizes.  ``pin_channel_groups`` (extra
     keyword) takes ``gf_daf_forward_pinned``: channel groups pinned to XCDs, bit-identical output, faster when every
     point is seen by several cameras at unrelated places, slower on projected geometry (include/gf_hip.h)."""
-    lib = _lib.load()
     _lib.require_gpu(mc_ms_feat, spatial_shape, scale_start_index, sampling_location, weights)
     B, cams, num_feat, C = mc_ms_feat.shape
     L, pts, G = spatial_shape.shape[0], sampling_location.shape[1], weights.shape[4]
     out = torch.empty((B, pts, C), dtype=torch.float32, device=mc_ms_feat.device)
-    with torch.cuda.device(mc_ms_feat.device):
-        fn = lib.gf_daf_forward_pinned if pin_channel_groups else lib.gf_daf_forward
-        rc = fn(B, cams, num_feat, C, L, pts, G, _lib.ptr(mc_ms_feat), _lib.ptr(spatial_shape),
-                _lib.ptr(scale_start_index), _lib.ptr(sampling_location), _lib.ptr(weights),
-                _lib.ptr(out), _lib.current_stream(mc_ms_feat.device))
-    _lib.check(rc, "gf_daf_forward")
+    _lib.call("gf_daf_forward_pinned" if pin_channel_groups else "gf_daf_forward", mc_ms_feat.device,
+              B, cams, num_feat, C, L, pts, G, mc_ms_feat, spatial_shape, scale_start_index, sampling_location, weights, out)
     return out
 
 
-_workspaces = {}
-
-
-def _workspace(device, nbytes):
-    """Grow-only scratch for the sorted backward (tap ids + counters), one per (device, stream): the kernels
-    run on torch's current stream and two streams must not share it."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _workspaces.pop(key, None)
-    while len(_workspaces) >= 8:             # bounded: least recently used entries go (a process that keeps creating streams)
-        _workspaces.pop(next(iter(_workspaces)))
-    if ws is not None:
-        _workspaces[key] = ws
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
-    return ws
+_scratch = _lib.StreamScratch()   # the sorted backward's tap ids + counters
 
 
 def deformable_aggregation_backward(mc_ms_feat, spatial_shape, scale_start_index, sampling_location, weights,
@@ -60,25 +42,14 @@ def deformable_aggregation_backward(mc_ms_feat, spatial_shape, scale_start_index
     _lib.require_gpu(mc_ms_feat, grad_output, grad_mc_ms_feat, grad_sampling_location, grad_weights)
     B, cams, num_feat, C = mc_ms_feat.shape
     L, pts, G = spatial_shape.shape[0], sampling_location.shape[1], weights.shape[4]
+    dev = mc_ms_feat.device
     nbytes = lib.gf_daf_backward_workspace_bytes(B, cams, num_feat, C, L, pts, G) if pixel_major else 0
+    args = (B, cams, num_feat, C, L, pts, G, mc_ms_feat, spatial_shape, scale_start_index, sampling_location, weights,
+            grad_output, grad_mc_ms_feat, grad_sampling_location, grad_weights)
     if nbytes:
-        with torch.cuda.device(mc_ms_feat.device):
-            ws = _workspace(mc_ms_feat.device, nbytes)
-            rc = lib.gf_daf_backward_sorted(B, cams, num_feat, C, L, pts, G, _lib.ptr(mc_ms_feat),
-                                            _lib.ptr(spatial_shape), _lib.ptr(scale_start_index),
-                                            _lib.ptr(sampling_location), _lib.ptr(weights), _lib.ptr(grad_output),
-                                            _lib.ptr(grad_mc_ms_feat), _lib.ptr(grad_sampling_location),
-                                            _lib.ptr(grad_weights), _lib.ptr(ws), nbytes,
-                                            _lib.current_stream(mc_ms_feat.device))
-        _lib.check(rc, "gf_daf_backward_sorted")
-        return
-    with torch.cuda.device(mc_ms_feat.device):
-        rc = lib.gf_daf_backward(B, cams, num_feat, C, L, pts, G, _lib.ptr(mc_ms_feat), _lib.ptr(spatial_shape),
-                                 _lib.ptr(scale_start_index), _lib.ptr(sampling_location), _lib.ptr(weights),
-                                 _lib.ptr(grad_output), _lib.ptr(grad_mc_ms_feat),
-                                 _lib.ptr(grad_sampling_location), _lib.ptr(grad_weights),
-                                 _lib.current_stream(mc_ms_feat.device))
-    _lib.check(rc, "gf_daf_backward")
+        _lib.call("gf_daf_backward_sorted", dev, *args, _scratch.get(dev, nbytes), nbytes)
+    else:
+        _lib.call("gf_daf_backward", dev, *args)
 
 
 _shape_tensors = {}   # (device, pyramid shapes) -> (spatial_shape, scale_start_index) int64 tensors
@@ -86,16 +57,12 @@ _shape_tensors = {}   # (device, pyramid shapes) -> (spatial_shape, scale_start_
 
 def _format_call(levels, table, inverse):
     """gf_feature_maps_format on contiguous fp32 CUDA tensors: levels [bs,cams,C,h,w], table [bs,cams,num_feat,C]."""
-    import ctypes
-    lib = _lib.load()
     bs, cams, C = levels[0].shape[:3]
     L = len(levels)
     hw = (ctypes.c_int * L)(*[int(f.shape[3] * f.shape[4]) for f in levels])
     ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in levels])
-    with torch.cuda.device(table.device):
-        rc = lib.gf_feature_maps_format(bs * cams, C, L, ctypes.cast(hw, ctypes.c_void_p), ctypes.cast(ptrs, ctypes.c_void_p),
-                                        _lib.ptr(table), int(inverse), _lib.current_stream(table.device))
-    _lib.check(rc, "gf_feature_maps_format")
+    _lib.call("gf_feature_maps_format", table.device, bs * cams, C, L, ctypes.cast(hw, ctypes.c_void_p),
+              ctypes.cast(ptrs, ctypes.c_void_p), table, int(inverse))
 
 
 class _FeatureMapsFormat(Function):
@@ -103,7 +70,7 @@ class _FeatureMapsFormat(Function):
 
     @staticmethod
     def forward(ctx, *feature_maps):
-        levels = [f.contiguous().float() for f in feature_maps]
+        levels = [_lib.as_arg(f) for f in feature_maps]
         bs, cams, C = levels[0].shape[:3]
         ctx.shapes = [tuple(f.shape) for f in levels]
         num_feat = sum(s[3] * s[4] for s in ctx.shapes)
@@ -115,7 +82,7 @@ class _FeatureMapsFormat(Function):
     @once_differentiable
     def backward(ctx, grad_table):
         grads = [torch.empty(s, dtype=torch.float32, device=grad_table.device) for s in ctx.shapes]
-        _format_call(grads, grad_table.contiguous().float(), inverse=True)
+        _format_call(grads, _lib.as_arg(grad_table), inverse=True)
         return tuple(grads)
 
 
@@ -125,11 +92,8 @@ class DeformableAggregationFunction(Function):
     @staticmethod
     def forward(ctx, mc_ms_feat, spatial_shape, scale_start_index, sampling_location, weights):
         # output: [bs, num_pts, num_embeds]
-        mc_ms_feat = mc_ms_feat.contiguous().float()
-        spatial_shape = spatial_shape.contiguous().int()
-        scale_start_index = scale_start_index.contiguous().int()
-        sampling_location = sampling_location.contiguous().float()
-        weights = weights.contiguous().float()
+        mc_ms_feat, sampling_location, weights = (_lib.as_arg(t) for t in (mc_ms_feat, sampling_location, weights))
+        spatial_shape, scale_start_index = (_lib.as_arg(t, torch.int32) for t in (spatial_shape, scale_start_index))
         output = deformable_aggregation_forward(mc_ms_feat, spatial_shape, scale_start_index,
                                                 sampling_location, weights)
         ctx.save_for_backward(mc_ms_feat, spatial_shape, scale_start_index, sampling_location, weights)
@@ -143,7 +107,7 @@ class DeformableAggregationFunction(Function):
         grad_sampling_location = torch.zeros_like(sampling_location)
         grad_weights = torch.zeros_like(weights)
         deformable_aggregation_backward(mc_ms_feat, spatial_shape, scale_start_index, sampling_location, weights,
-                                        grad_output.contiguous().float(), grad_mc_ms_feat, grad_sampling_location,
+                                        _lib.as_arg(grad_output), grad_mc_ms_feat, grad_sampling_location,
                                         grad_weights)
         return grad_mc_ms_feat, None, None, grad_sampling_location, grad_weights
 

@@ -11,12 +11,9 @@ import torch
 from torch.autograd.function import Function, once_differentiable
 
 from . import _lib
+from ._lib import as_arg
 
 f32 = torch.float32
-
-
-def _c(t, dtype=f32):
-    return None if t is None else t.detach().to(dtype).contiguous()
 
 
 class DeformablePrepareFunction(Function):
@@ -27,18 +24,14 @@ class DeformablePrepareFunction(Function):
     @staticmethod
     def forward(ctx, key_points, projection_mat, image_wh, raw_weights, weight_mask):
         _lib.require_gpu(key_points, projection_mat, image_wh, raw_weights, weight_mask)
-        lib = _lib.load()
-        kp, pm, wh, raw = _c(key_points), _c(projection_mat), _c(image_wh), _c(raw_weights)
-        wm = None if weight_mask is None else weight_mask.detach().to(torch.uint8).contiguous()
+        kp, pm, wh, raw = as_arg(key_points), as_arg(projection_mat), as_arg(image_wh), as_arg(raw_weights)
+        wm = as_arg(weight_mask, torch.uint8)
         B, A, pts = kp.shape[:3]
         cams, L, G = raw.shape[2], raw.shape[3], raw.shape[5]
         assert raw.shape == (B, A, cams, L, pts, G) and pm.shape == (B, cams, 4, 4)
         points_2d = torch.empty(B, A * pts, cams, 2, dtype=f32, device=kp.device)
         weights = torch.empty(B, A * pts, cams, L, G, dtype=f32, device=kp.device)
-        with torch.cuda.device(kp.device):
-            rc = lib.gf_daf_prepare(B, A, pts, cams, L, G, _lib.ptr(kp), _lib.ptr(pm), _lib.ptr(wh), _lib.ptr(raw),
-                                    _lib.ptr(wm), _lib.ptr(points_2d), _lib.ptr(weights), _lib.current_stream(kp.device))
-        _lib.check(rc, "gf_daf_prepare")
+        _lib.call("gf_daf_prepare", kp.device, B, A, pts, cams, L, G, kp, pm, wh, raw, wm, points_2d, weights)
         ctx.save_for_backward(kp, pm, wh if wh is not None else torch.empty(0, device=kp.device), weights)
         ctx.has_wh = wh is not None
         ctx.dims = (B, A, pts, cams, L, G)
@@ -49,17 +42,12 @@ class DeformablePrepareFunction(Function):
     @once_differentiable
     def backward(ctx, grad_points_2d, grad_weights):
         kp, pm, wh, weights = ctx.saved_tensors
-        lib = _lib.load()
         B, A, pts, cams, L, G = ctx.dims
         need_kp, need_raw = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
         g_kp = torch.empty_like(kp) if need_kp else None
         g_raw = torch.empty(B, A, cams, L, pts, G, dtype=f32, device=kp.device) if need_raw else None
-        with torch.cuda.device(kp.device):
-            rc = lib.gf_daf_prepare_backward(B, A, pts, cams, L, G, _lib.ptr(kp), _lib.ptr(pm),
-                                             _lib.ptr(wh) if ctx.has_wh else None, _lib.ptr(weights),
-                                             _lib.ptr(_c(grad_weights)), _lib.ptr(_c(grad_points_2d)), _lib.ptr(g_raw),
-                                             _lib.ptr(g_kp), _lib.current_stream(kp.device))
-        _lib.check(rc, "gf_daf_prepare_backward")
+        _lib.call("gf_daf_prepare_backward", kp.device, B, A, pts, cams, L, G, kp, pm, wh if ctx.has_wh else None, weights,
+                  as_arg(grad_weights), as_arg(grad_points_2d), g_raw, g_kp)
         return g_kp, None, None, g_raw, None
 
 
@@ -80,10 +68,9 @@ def deformable_fused_forward(key_points, projection_mat, image_wh, mc_ms_feat, s
     if any(t is not None and t.requires_grad for t in (key_points, mc_ms_feat, raw_weights, raw_anchor, raw_cam)) and torch.is_grad_enabled():
         raise RuntimeError("deformable_fused_forward computes no gradients: use deformable_prepare + DeformableAggregationFunction "
                            "for training, or call it under torch.no_grad()")
-    lib = _lib.load()
-    kp, pm, wh = _c(key_points), _c(projection_mat), _c(image_wh)
-    raw, ra, rc_ = _c(raw_weights), _c(raw_anchor), _c(raw_cam)
-    feat = _c(mc_ms_feat)
+    kp, pm, wh = as_arg(key_points), as_arg(projection_mat), as_arg(image_wh)
+    raw, ra, rc_ = as_arg(raw_weights), as_arg(raw_anchor), as_arg(raw_cam)
+    feat = as_arg(mc_ms_feat)
     B, A, pts = kp.shape[:3]
     cams, num_feat, C = feat.shape[1], feat.shape[2], feat.shape[3]
     L = spatial_shape.shape[0]
@@ -94,13 +81,9 @@ def deformable_fused_forward(key_points, projection_mat, image_wh, mc_ms_feat, s
         G = ra.shape[4]
         assert ra.shape == (B, A, L, pts, G) and rc_.shape == (B, cams, L, pts, G)
     assert pm.shape == (B, cams, 4, 4)
-    ss, st = spatial_shape.to(torch.int32).contiguous(), scale_start_index.to(torch.int32).contiguous()
+    ss, st = as_arg(spatial_shape, torch.int32), as_arg(scale_start_index, torch.int32)
     out = torch.empty(B, A, C, dtype=f32, device=kp.device)
-    with torch.cuda.device(kp.device):
-        rc = lib.gf_daf_fused_forward(B, A, pts, cams, L, G, C, num_feat, _lib.ptr(kp), _lib.ptr(pm), _lib.ptr(wh), _lib.ptr(raw),
-                                      _lib.ptr(ra), _lib.ptr(rc_), _lib.ptr(feat), _lib.ptr(ss), _lib.ptr(st), _lib.ptr(out),
-                                      _lib.current_stream(kp.device))
-    _lib.check(rc, "gf_daf_fused_forward")
+    _lib.call("gf_daf_fused_forward", kp.device, B, A, pts, cams, L, G, C, num_feat, kp, pm, wh, raw, ra, rc_, feat, ss, st, out)
     return out
 
 
@@ -123,10 +106,9 @@ class DeformableFusedFunction(Function):
                 raw_weights, raw_anchor, raw_cam, weight_mask):
         _lib.require_gpu(key_points, projection_mat, image_wh, mc_ms_feat, spatial_shape, scale_start_index, raw_weights,
                          raw_anchor, raw_cam, weight_mask)
-        lib = _lib.load()
-        kp, pm, wh = _c(key_points), _c(projection_mat), _c(image_wh)
-        raw, ra, rc_ = _c(raw_weights), _c(raw_anchor), _c(raw_cam)
-        feat, wm = _c(mc_ms_feat), _mask_u8(weight_mask)
+        kp, pm, wh = as_arg(key_points), as_arg(projection_mat), as_arg(image_wh)
+        raw, ra, rc_ = as_arg(raw_weights), as_arg(raw_anchor), as_arg(raw_cam)
+        feat, wm = as_arg(mc_ms_feat), _mask_u8(weight_mask)
         B, A, pts = kp.shape[:3]
         cams, num_feat, C = feat.shape[1], feat.shape[2], feat.shape[3]
         L = spatial_shape.shape[0]
@@ -142,13 +124,10 @@ class DeformableFusedFunction(Function):
             assert ra.shape == (B, A, L, pts, G) and rc_.shape == (B, cams, L, pts, G)
         assert pm.shape == (B, cams, 4, 4) and feat.shape[0] == B
         assert wm is None or wm.shape == (B, A, cams, L, pts, G)
-        ss, st = spatial_shape.to(torch.int32).contiguous(), scale_start_index.to(torch.int32).contiguous()
+        ss, st = as_arg(spatial_shape, torch.int32), as_arg(scale_start_index, torch.int32)
         out = torch.empty(B, A, C, dtype=f32, device=kp.device)
-        with torch.cuda.device(kp.device):
-            rc = lib.gf_daf_fused_forward_masked(B, A, pts, cams, L, G, C, num_feat, _lib.ptr(kp), _lib.ptr(pm), _lib.ptr(wh),
-                                                 _lib.ptr(raw), _lib.ptr(ra), _lib.ptr(rc_), _lib.ptr(wm), _lib.ptr(feat),
-                                                 _lib.ptr(ss), _lib.ptr(st), _lib.ptr(out), _lib.current_stream(kp.device))
-        _lib.check(rc, "gf_daf_fused_forward_masked")
+        _lib.call("gf_daf_fused_forward_masked", kp.device, B, A, pts, cams, L, G, C, num_feat, kp, pm, wh, raw, ra, rc_, wm,
+                  feat, ss, st, out)
         ctx.save_for_backward(kp, pm, wh, feat, ss, st, raw, ra, rc_, wm)
         ctx.dims = (B, A, pts, cams, L, G, C, num_feat)
         return out
@@ -168,15 +147,11 @@ class DeformableFusedFunction(Function):
         if not any(t is not None for t in (g_kp, g_feat, g_raw, g_ra, g_rc)):
             return (None,) * 10
         lib = _lib.load()
-        go = _c(grad_out)
+        go = as_arg(grad_out)
         ws_bytes = lib.gf_daf_fused_backward_workspace_bytes(B, A, pts, cams, L, G) if g_rc is not None else 0
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev) if g_rc is not None else None
-        with torch.cuda.device(dev):
-            rc = lib.gf_daf_fused_backward(B, A, pts, cams, L, G, C, num_feat, _lib.ptr(kp), _lib.ptr(pm), _lib.ptr(wh),
-                                           _lib.ptr(raw), _lib.ptr(ra), _lib.ptr(rc_), _lib.ptr(wm), _lib.ptr(feat), _lib.ptr(ss),
-                                           _lib.ptr(st), _lib.ptr(go), _lib.ptr(g_feat), _lib.ptr(g_kp), _lib.ptr(g_raw),
-                                           _lib.ptr(g_ra), _lib.ptr(g_rc), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
-        _lib.check(rc, "gf_daf_fused_backward")
+        _lib.call("gf_daf_fused_backward", dev, B, A, pts, cams, L, G, C, num_feat, kp, pm, wh, raw, ra, rc_, wm, feat, ss, st,
+                  go, g_feat, g_kp, g_raw, g_ra, g_rc, ws, ws_bytes)
         return g_kp, None, None, g_feat, None, None, g_raw, g_ra, g_rc, None
 
 

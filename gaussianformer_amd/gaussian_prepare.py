@@ -7,16 +7,15 @@ and of the integer path of ``LocalAggregator.forward``
 moves the covariances to the host for a LAPACK inverse and synchronises ~10 times per frame;
 here one kernel does it on the device and nothing synchronises.
 """
+import ctypes
+
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import as_arg
 
 f32, i32 = torch.float32, torch.int32
-
-
-def _c(t, dtype=f32):
-    return t.detach().to(dtype).contiguous()
 
 
 def gaussian_prepare(means3D, scales, rotations, pc_min, grid_size, scale_multiplier, H, W, D,
@@ -26,24 +25,27 @@ def gaussian_prepare(means3D, scales, rotations, pc_min, grid_size, scale_multip
     ``status`` (optional zeroed int32[1] device tensor) collects the GF_PREPARE_* bits that
     stand in for the reference's host-side asserts; no gradient is recorded here."""
     _lib.require_gpu(means3D, scales, rotations, status)
-    lib = _lib.load()
-    means3D, scales, rotations = _c(means3D), _c(scales), _c(rotations)
+    means3D, scales, rotations = as_arg(means3D), as_arg(scales), as_arg(rotations)
     P = means3D.shape[0]
     assert means3D.shape == (P, 3) and scales.shape == (P, 3) and rotations.shape == (P, 4)
     dev = means3D.device
     means_int = torch.empty(P, 3, dtype=i32, device=dev)
     radii = torch.empty((P, 3) if radii_mode == _lib.GF_RADII_PER_AXIS else (P,), dtype=i32, device=dev)
     cov = torch.empty((P, 3, 3) if full_cov else (P, 6), dtype=f32, device=dev)
-    import ctypes
     pc = (ctypes.c_float * 3)(*[float(v) for v in pc_min])
-    with torch.cuda.device(dev):
-        rc = lib.gf_gaussian_prepare(P, H, W, D, ctypes.cast(pc, ctypes.c_void_p), float(grid_size),
-                                     float(scale_multiplier), int(radii_mode), int(radii_min), _lib.ptr(means3D),
-                                     _lib.ptr(scales), _lib.ptr(rotations), _lib.ptr(means_int), _lib.ptr(radii),
-                                     None if full_cov else _lib.ptr(cov), _lib.ptr(cov) if full_cov else None,
-                                     _lib.ptr(status), _lib.current_stream(dev))
-    _lib.check(rc, "gf_gaussian_prepare")
+    _lib.call("gf_gaussian_prepare", dev, P, H, W, D, ctypes.cast(pc, ctypes.c_void_p), float(grid_size),
+              float(scale_multiplier), int(radii_mode), int(radii_min), means3D, scales, rotations, means_int, radii,
+              None if full_cov else cov, cov if full_cov else None, status)
     return means_int, radii, cov
+
+
+def _prepare_backward(s, q, cov_grad, full_cov):
+    """``gf_gaussian_prepare_backward``: the gradients of Sigma^-1 (packed ``[P,6]`` or ``[P,3,3]``) in ``scales`` and
+    ``rotations``."""
+    g = as_arg(cov_grad)
+    sg, qg = torch.empty_like(s), torch.empty_like(q)
+    _lib.call("gf_gaussian_prepare_backward", s.device, s.shape[0], int(full_cov), s, q, g, sg, qg)
+    return sg, qg
 
 
 class _CovInverse(torch.autograd.Function):
@@ -53,34 +55,19 @@ class _CovInverse(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scales, rotations, packed):
         _lib.require_gpu(scales, rotations)
-        lib = _lib.load()
-        s, q = _c(scales), _c(rotations)
+        s, q = as_arg(scales), as_arg(rotations)
         P = s.shape[0]
         cov = torch.empty((P, 6) if packed else (P, 3, 3), dtype=f32, device=s.device)
-        import ctypes
         pc = (ctypes.c_float * 3)(0.0, 0.0, 0.0)
-        with torch.cuda.device(s.device):
-            rc = lib.gf_gaussian_prepare(P, 1, 1, 1, ctypes.cast(pc, ctypes.c_void_p), 1.0, 1.0, _lib.GF_RADII_SCALAR, 1,
-                                         None, _lib.ptr(s), _lib.ptr(q), None, None,
-                                         _lib.ptr(cov) if packed else None, None if packed else _lib.ptr(cov), None,
-                                         _lib.current_stream(s.device))
-        _lib.check(rc, "gf_gaussian_prepare")
+        _lib.call("gf_gaussian_prepare", s.device, P, 1, 1, 1, ctypes.cast(pc, ctypes.c_void_p), 1.0, 1.0,
+                  _lib.GF_RADII_SCALAR, 1, None, s, q, None, None, cov if packed else None, None if packed else cov, None)
         ctx.save_for_backward(s, q)
         ctx.packed = packed
         return cov
 
     @staticmethod
     def backward(ctx, cov_grad):
-        s, q = ctx.saved_tensors
-        lib = _lib.load()
-        g = _c(cov_grad)
-        P = s.shape[0]
-        sg, qg = torch.empty_like(s), torch.empty_like(q)
-        with torch.cuda.device(s.device):
-            rc = lib.gf_gaussian_prepare_backward(P, 0 if ctx.packed else 1, _lib.ptr(s), _lib.ptr(q), _lib.ptr(g),
-                                                  _lib.ptr(sg), _lib.ptr(qg), _lib.current_stream(s.device))
-        _lib.check(rc, "gf_gaussian_prepare_backward")
-        return sg, qg, None
+        return (*_prepare_backward(*ctx.saved_tensors, cov_grad, full_cov=not ctx.packed), None)
 
 
 class _GaussianPrepare(torch.autograd.Function):
@@ -93,21 +80,13 @@ class _GaussianPrepare(torch.autograd.Function):
                 status):
         means_int, radii, cov6 = gaussian_prepare(means3D, scales, rotations, pc_min, grid_size, scale_multiplier,
                                                   H, W, D, radii_mode, radii_min, status=status)
-        ctx.save_for_backward(_c(scales), _c(rotations))
+        ctx.save_for_backward(as_arg(scales), as_arg(rotations))
         ctx.mark_non_differentiable(means_int, radii)
         return means_int, radii, cov6
 
     @staticmethod
     def backward(ctx, _gi, _gr, cov_grad):
-        s, q = ctx.saved_tensors
-        lib = _lib.load()
-        g = _c(cov_grad)
-        sg, qg = torch.empty_like(s), torch.empty_like(q)
-        with torch.cuda.device(s.device):
-            rc = lib.gf_gaussian_prepare_backward(s.shape[0], 0, _lib.ptr(s), _lib.ptr(q), _lib.ptr(g), _lib.ptr(sg),
-                                                  _lib.ptr(qg), _lib.current_stream(s.device))
-        _lib.check(rc, "gf_gaussian_prepare_backward")
-        return (None, sg, qg) + (None,) * 9
+        return (None, *_prepare_backward(*ctx.saved_tensors, cov_grad, full_cov=False)) + (None,) * 9
 
 
 def covariance_inverse(scales, rotations, packed=False):
@@ -126,10 +105,8 @@ class _GaussianPack(torch.autograd.Function):
     def forward(ctx, means, scales, rotations, sem, opa, empty_scalar, empty_host, cout, zero_first, with_empty, softmax,
                 empty_label):
         _lib.require_gpu(means, scales, rotations, sem, opa, empty_scalar)
-        lib = _lib.load()
-        import ctypes
-        m, s_, q, se = _c(means[0]), _c(scales[0]), _c(rotations[0]), _c(sem[0])
-        o = None if opa is None else _c(opa[0].reshape(-1))
+        m, s_, q, se = as_arg(means[0]), as_arg(scales[0]), as_arg(rotations[0]), as_arg(sem[0])
+        o = None if opa is None else as_arg(opa[0].reshape(-1))
         P, cin = m.shape[0], se.shape[1]
         Pout = P + (1 if with_empty else 0)
         dev = m.device
@@ -137,13 +114,9 @@ class _GaussianPack(torch.autograd.Function):
         host = [None, None, None]
         if with_empty:
             host = [(ctypes.c_float * len(v))(*v) for v in empty_host]
-        es = None if empty_scalar is None else _c(empty_scalar)
-        with torch.cuda.device(dev):
-            rc = lib.gf_gaussian_pack(P, cin, cout, int(zero_first), int(with_empty), int(softmax), int(empty_label),
-                                      _lib.ptr(m), _lib.ptr(s_), _lib.ptr(q), _lib.ptr(se), _lib.ptr(o),
-                                      *[None if h is None else ctypes.cast(h, ctypes.c_void_p) for h in host], _lib.ptr(es),
-                                      *[_lib.ptr(t) for t in outs], _lib.current_stream(dev))
-        _lib.check(rc, "gf_gaussian_pack")
+        _lib.call("gf_gaussian_pack", dev, P, cin, cout, int(zero_first), int(with_empty), int(softmax), int(empty_label),
+                  m, s_, q, se, o, *[None if h is None else ctypes.cast(h, ctypes.c_void_p) for h in host],
+                  as_arg(empty_scalar), *outs)
         ctx.meta = (P, cin, cout, zero_first, with_empty, softmax, empty_label, opa is not None and opa.requires_grad,
                     None if opa is None else opa.shape)
         if softmax:

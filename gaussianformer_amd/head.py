@@ -16,17 +16,12 @@ def occupancy_labels(logits, bin_logits=None, threshold=0.5, empty_label=17, com
     output, before the reference's ``[None].transpose(1, 2)``), ``bin_logits [N]`` for the prob
     head.  Returns int64 ``[N]``."""
     _lib.require_gpu(logits, bin_logits)
-    lib = _lib.load()
-    lg = logits.detach().to(torch.float32).contiguous()
-    bl = None if bin_logits is None else bin_logits.detach().to(torch.float32).contiguous()
+    lg, bl = _lib.as_arg(logits), _lib.as_arg(bin_logits)
     N, C = lg.shape
     mode = _lib.GF_LABELS_ARGMAX if bl is None else (
         _lib.GF_LABELS_PROB_GEOSEM if combine_geosem else _lib.GF_LABELS_PROB_THRESHOLD)
     labels = torch.empty(N, dtype=torch.int64, device=lg.device)
-    with torch.cuda.device(lg.device):
-        rc = lib.gf_head_labels(N, C, mode, _lib.ptr(lg), _lib.ptr(bl), float(threshold), int(empty_label),
-                                _lib.ptr(labels), _lib.current_stream(lg.device))
-    _lib.check(rc, "gf_head_labels")
+    _lib.call("gf_head_labels", lg.device, N, C, mode, lg, bl, float(threshold), int(empty_label), labels)
     return labels
 
 

@@ -22,21 +22,14 @@ class KeyPointsFunction(Function):
     @staticmethod
     def forward(ctx, anchor, learned, fix_scale, pc_range, scale_range, learnable_fixed_scale, identity_activations=0):
         _lib.require_gpu(anchor, learned, fix_scale)
-        lib = _lib.load()
         bs, A, D = anchor.shape
-        a = anchor.detach().to(f32).contiguous()
-        l = None if learned is None else learned.detach().to(f32).contiguous()
-        fix = fix_scale.detach().to(f32).contiguous()
+        a, l, fix = _lib.as_arg(anchor), _lib.as_arg(learned), _lib.as_arg(fix_scale)
         F, K = fix.shape[0], 0 if l is None else l.shape[2]
         out = torch.empty(bs, A, F + K, 3, dtype=f32, device=a.device)
         pc = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
         ctx.consts = (bs * A, D, F, K, pc, float(scale_range[0]), float(scale_range[1]), float(learnable_fixed_scale),
                       int(identity_activations))
-        with torch.cuda.device(a.device):
-            rc = lib.gf_key_points(bs * A, D, F, K, _lib.ptr(a), _lib.ptr(l), _lib.ptr(fix), ctypes.cast(pc, ctypes.c_void_p),
-                                   ctx.consts[5], ctx.consts[6], ctx.consts[7], ctx.consts[8], _lib.ptr(out),
-                                   _lib.current_stream(a.device))
-        _lib.check(rc, "gf_key_points")
+        _lib.call("gf_key_points", a.device, bs * A, D, F, K, a, l, fix, ctypes.cast(pc, ctypes.c_void_p), *ctx.consts[5:], out)
         ctx.save_for_backward(a, l if l is not None else torch.empty(0, device=a.device), fix)
         ctx.has_learned = l is not None
         return out
@@ -45,16 +38,12 @@ class KeyPointsFunction(Function):
     @once_differentiable
     def backward(ctx, grad_kp):
         a, l, fix = ctx.saved_tensors
-        lib = _lib.load()
         n, D, F, K, pc, lo, hi, lfs, ident = ctx.consts
-        g = grad_kp.detach().to(f32).contiguous()
+        g = _lib.as_arg(grad_kp)
         ga = torch.empty_like(a)
         gl = torch.empty_like(l) if ctx.has_learned else None
-        with torch.cuda.device(a.device):
-            rc = lib.gf_key_points_backward(n, D, F, K, _lib.ptr(a), _lib.ptr(l) if ctx.has_learned else None, _lib.ptr(fix),
-                                            ctypes.cast(pc, ctypes.c_void_p), lo, hi, lfs, ident, _lib.ptr(g), _lib.ptr(ga), _lib.ptr(gl),
-                                            _lib.current_stream(a.device))
-        _lib.check(rc, "gf_key_points_backward")
+        _lib.call("gf_key_points_backward", a.device, n, D, F, K, a, l if ctx.has_learned else None, fix,
+                  ctypes.cast(pc, ctypes.c_void_p), lo, hi, lfs, ident, g, ga, gl)
         return ga, gl, None, None, None, None, None
 
 

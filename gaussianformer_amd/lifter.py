@@ -68,11 +68,8 @@ def lift_pixels(logits, projection_mat, image_wh, *, depth_bins, pc_range, voxel
         raise ValueError(f"lift_pixels: uniforms must be [{b}, {n}, {h}, {w}, {a}], got {tuple(uniforms.shape)}")
     X, Y, Z = (int(r) for r in occ_resolution)
     lib = _lib.load()
-    x = logits.detach().to(torch.float32).contiguous()
-    img2lidar = projection_mat.detach().to(torch.float32).inverse().contiguous()
-    wh = image_wh.detach().to(torch.float32).contiguous()
-    d = depth_bins.detach().to(torch.float32).contiguous()
-    u = None if uniforms is None else uniforms.detach().to(torch.float32).contiguous()
+    x, wh, d, u = (_lib.as_arg(t) for t in (logits, image_wh, depth_bins, uniforms))
+    img2lidar = _lib.as_arg(projection_mat).inverse().contiguous()
     occ = gt = None
     if occ_label is not None:
         occ = pack_occupancy(occ_label, occ_cam_mask, empty_label)
@@ -88,11 +85,8 @@ def lift_pixels(logits, projection_mat, image_wh, *, depth_bins, pc_range, voxel
     counts = torch.empty(b, dtype=torch.int32, device=dev)
     src = torch.empty((b, npix * a), dtype=torch.int32, device=dev) if return_src else None
     pc = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
-    with torch.cuda.device(dev):
-        rc = lib.gf_lift_pixels(b, n, h, w, S, a, _lib.ptr(x), _lib.ptr(img2lidar), _lib.ptr(wh), _lib.ptr(d), pc,
-                                float(voxel_size), X, Y, Z, _lib.ptr(occ), _lib.ptr(u), _lib.ptr(points), _lib.ptr(counts),
-                                _lib.ptr(src), _lib.ptr(gt), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
-    _lib.check(rc, "gf_lift_pixels")
+    _lib.call("gf_lift_pixels", dev, b, n, h, w, S, a, x, img2lidar, wh, d, pc, float(voxel_size), X, Y, Z, occ, u, points,
+              counts, src, gt, ws, ws_bytes)
     cnt = counts.cpu().tolist()   # the one host synchronisation of the call
     scans = [points[i, :c] for i, c in enumerate(cnt)]
     pixel_gt = None if gt is None else gt.view(torch.bool)
@@ -113,10 +107,7 @@ class _PixelLoss(torch.autograd.Function):
             raise ValueError(f"pixel_distribution_loss: unsupported shape {tuple(logits.shape)} (last dim <= {MAX_BINS})")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.gf_pixel_loss_forward(rows, nb, flags, _lib.ptr(logits), _lib.ptr(gt), _lib.ptr(loss), _lib.ptr(ws),
-                                           ws_bytes, _lib.current_stream(dev))
-        _lib.check(rc, "gf_pixel_loss_forward")
+        _lib.call("gf_pixel_loss_forward", dev, rows, nb, flags, logits, gt, loss, ws, ws_bytes)
         ctx.flags = flags
         ctx.save_for_backward(logits, gt)
         return loss
@@ -124,15 +115,10 @@ class _PixelLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss):
         logits, gt = ctx.saved_tensors
-        lib = _lib.load()
-        dev = logits.device
         nb = logits.shape[-1]
-        g = grad_loss.detach().to(torch.float32).contiguous()
         grad = torch.empty_like(logits)
-        with torch.cuda.device(dev):
-            rc = lib.gf_pixel_loss_backward(logits.numel() // nb, nb, ctx.flags, _lib.ptr(logits), _lib.ptr(gt), _lib.ptr(g),
-                                            _lib.ptr(grad), _lib.current_stream(dev))
-        _lib.check(rc, "gf_pixel_loss_backward")
+        _lib.call("gf_pixel_loss_backward", logits.device, logits.numel() // nb, nb, ctx.flags, logits, gt,
+                  _lib.as_arg(grad_loss), grad)
         return grad, None, None
 
 

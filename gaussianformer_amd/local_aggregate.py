@@ -20,41 +20,13 @@ from . import _lib
 _C18 = _lib.GF_NUM_CHANNELS
 
 
-class _Workspace:
-    """Scratch reused across calls, one grow-only buffer per (device, stream): the kernels of a call run on torch's
-    current stream, so two calls on different streams must not share records / bitmask / verdict words.  A buffer
-    is allocated while its stream is current, so the caching allocator frees it in that stream's order.  The cache is
-    bounded (least recently used of ``MAX_STREAMS`` entries goes): a process that keeps creating streams does not
-    accumulate a megabyte-plus per stream ever used, and a recycled stream handle meets at worst its own old buffer."""
-    MAX_STREAMS = 8
-    _cache = {}
-    _uses = 0
-
-    @classmethod
-    def get(cls, device, nbytes):
-        """The stream's buffer.  Its first 32 KB -- the library's flag section, the same words whatever the call's shape -- are zeroed
-        when the buffer is allocated and afterwards only written by the library: what ``GF_WORKSPACE_ZEROED`` promises (the
-        matrix-core forward then keeps its fall-back verdict in one word instead of one per wave of the records pass)."""
-        key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
-        buf = cls._cache.pop(key, None)
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-            buf[:cls.FLAG_BYTES].zero_()
-        cls._cache[key] = buf              # most recently used last
-        while len(cls._cache) > cls.MAX_STREAMS:
-            cls._cache.pop(next(iter(cls._cache)))
-        cls._uses += 1
-        return buf
-
-    FLAG_BYTES = 32768
-
-    @classmethod
-    def stamp(cls, device):
-        """(stream's buffer, number of hand-outs so far): equal stamps = nobody has been given a workspace in between, so the
-        buffer still holds what the last call left in it (``GF_RECORDS_VALID``; the library checks it again on the device)."""
-        key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
-        buf = cls._cache.get(key)
-        return (key, None if buf is None else buf.data_ptr(), cls._uses)
+FLAG_BYTES = 32768
+# The splat's scratch (records / bitmask / verdict words).  Its first 32 KB -- the library's flag section, the same words whatever
+# the call's shape -- are zeroed when a buffer is allocated and afterwards only written by the library: what ``GF_WORKSPACE_ZEROED``
+# promises (the matrix-core forward then keeps its fall-back verdict in one word instead of one per wave of the records pass).
+# Equal ``stamp()``s: the buffer still holds what the last call left in it (``GF_RECORDS_VALID``; the library checks it again on
+# the device).
+_scratch = _lib.StreamScratch(min_bytes=1 << 20, zeroed_bytes=FLAG_BYTES)
 
 
 _lattice_cache = {}
@@ -105,10 +77,30 @@ def grid_is_exact_lattice(pc_min, grid_size, H, W, D):
     return True
 
 
-def _contig(t, dtype):
-    if t.dtype != dtype:
-        t = t.to(dtype)
-    return t.contiguous()
+def _bind(variant, tensors, H, W, D, flags, forward=True, own_workspace=False):
+    """What the raw entry points and the plan share.  Refuses CPU tensors, coerces the eight inputs ``(pts, points_int, means3D,
+    means3D_int, opacities, semantics, radii, cov3D)`` by position (fp32; int32 for the three integer ones; contiguous) and
+    returns ``(dev, N, P, C, prob, args, state, ws)``: ``args`` = the leading arguments of every ``gf_splat_*`` call (variant,
+    per-axis radii, flags, sizes, the eight inputs) and ``ws`` the workspace -- this stream's shared one, or with
+    ``own_workspace`` a zeroed one of the call's own.  For a forward, ``state`` is a fresh state block and the flags say
+    ``GF_WORKSPACE_ZEROED``."""
+    lib = _lib.load()
+    _lib.require_gpu(*tensors)
+    inputs = [_lib.as_arg(t, torch.int32 if i in (1, 3, 6) else torch.float32) for i, t in enumerate(tensors)]
+    dev = inputs[0].device
+    N, P, C = inputs[0].shape[0], inputs[2].shape[0], inputs[5].shape[1]
+    state = None
+    if forward:
+        state = torch.empty(lib.gf_splat_state_bytes(), dtype=torch.uint8, device=dev)
+        flags |= _lib.GF_WORKSPACE_ZEROED
+    nbytes = lib.gf_splat_workspace_bytes(P, N, H, W, D)
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev) if own_workspace else _scratch.get(dev, nbytes)
+    args = [variant, int(inputs[6].dim() == 2), flags, P, N, C, H, W, D, *inputs]
+    return dev, N, P, C, variant == _lib.GF_SPLAT_PROB, args, state, ws
+
+
+def _per_point(count, N, dev):
+    return [torch.empty(N, dtype=torch.float32, device=dev) for _ in range(count)]
 
 
 def splat_forward(variant, pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D,
@@ -117,35 +109,13 @@ def splat_forward(variant, pts, points_int, means3D, means3D_int, opacities, sem
     (model/head/localagg/local_aggregate.h:18-28; prob: localagg_prob/local_aggregate.cu:35-45).
     Returns ``(logits, bin_logits, density, probability, state)``; the last four are ``None``
     for the base variant except ``state`` (a small device block consumed by the backward)."""
-    lib = _lib.load()
-    _lib.require_gpu(pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D)
-    dev = pts.device
-    f32, i32 = torch.float32, torch.int32
-    pts, means3D, opacities, semantics, cov3D = (_contig(t, f32) for t in (pts, means3D, opacities, semantics, cov3D))
-    points_int, means3D_int, radii = (_contig(t, i32) for t in (points_int, means3D_int, radii))
-    N, P, C = pts.shape[0], means3D.shape[0], semantics.shape[1]
+    dev, N, P, C, prob, args, state, ws = _bind(
+        variant, (pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D), H, W, D, flags)
     if C != _C18:
         raise RuntimeError(f"semantics must have {_C18} channels (NUM_CHANNELS), got {C}")
-    per_axis = int(radii.dim() == 2)
-    prob = variant == _lib.GF_SPLAT_PROB
-    logits = torch.empty((N, C), dtype=f32, device=dev)
-    bin_logits = density = probability = None
-    if prob:
-        bin_logits = torch.empty(N, dtype=f32, device=dev)
-        density = torch.empty(N, dtype=f32, device=dev)
-        probability = torch.empty(N, dtype=f32, device=dev)
-    state = torch.empty(lib.gf_splat_state_bytes(), dtype=torch.uint8, device=dev)
-    nbytes = lib.gf_splat_workspace_bytes(P, N, H, W, D)
-    ws = _Workspace.get(dev, nbytes)
-    flags |= _lib.GF_WORKSPACE_ZEROED
-    with torch.cuda.device(dev):
-        rc = lib.gf_splat_forward(
-            variant, per_axis, flags, P, N, C, H, W, D,
-            _lib.ptr(pts), _lib.ptr(points_int), _lib.ptr(means3D), _lib.ptr(means3D_int), _lib.ptr(opacities),
-            _lib.ptr(semantics), _lib.ptr(radii), _lib.ptr(cov3D),
-            _lib.ptr(logits), _lib.ptr(bin_logits), _lib.ptr(density), _lib.ptr(probability), _lib.ptr(state),
-            _lib.ptr(ws), ws.numel(), _lib.current_stream(dev))
-    _lib.check(rc, "gf_splat_forward")
+    logits = torch.empty((N, C), dtype=torch.float32, device=dev)
+    bin_logits, density, probability = _per_point(3, N, dev) if prob else [None] * 3
+    _lib.call("gf_splat_forward", dev, *args, logits, bin_logits, density, probability, state, ws, ws.numel())
     return logits, bin_logits, density, probability, state
 
 
@@ -155,31 +125,15 @@ def splat_forward_labels(variant, pts, points_int, means3D, means3D_int, opaciti
     """Forward splat with the head epilogue folded in (``gf_splat_forward_labels``): returns
     ``labels`` (int64 ``[N]``), or ``(labels, logits[, bin_logits, density, probability])`` with
     ``keep_logits``.  Without ``keep_logits`` the 46 MB of logits are never written."""
-    lib = _lib.load()
-    _lib.require_gpu(pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D)
-    f32, i32 = torch.float32, torch.int32
-    pts, means3D, opacities, semantics, cov3D = (_contig(t, f32) for t in (pts, means3D, opacities, semantics, cov3D))
-    points_int, means3D_int, radii = (_contig(t, i32) for t in (points_int, means3D_int, radii))
-    N, P, C = pts.shape[0], means3D.shape[0], semantics.shape[1]
-    dev = pts.device
-    prob = variant == _lib.GF_SPLAT_PROB
+    dev, N, P, C, prob, args, state, ws = _bind(
+        variant, (pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D), H, W, D, flags)
     mode = _lib.GF_LABELS_ARGMAX if not prob else (
         _lib.GF_LABELS_PROB_GEOSEM if combine_geosem else _lib.GF_LABELS_PROB_THRESHOLD)
     labels = torch.empty(N, dtype=torch.int64, device=dev)
-    logits = torch.empty((N, C), dtype=f32, device=dev) if keep_logits else None
-    extra = [torch.empty(N, dtype=f32, device=dev) for _ in range(3)] if (prob and keep_logits) else [None] * 3
-    state = torch.empty(lib.gf_splat_state_bytes(), dtype=torch.uint8, device=dev)
-    nbytes = lib.gf_splat_workspace_bytes(P, N, H, W, D)
-    ws = _Workspace.get(dev, nbytes)
-    flags |= _lib.GF_WORKSPACE_ZEROED
-    with torch.cuda.device(dev):
-        rc = lib.gf_splat_forward_labels(variant, int(radii.dim() == 2), flags, P, N, C, H, W, D,
-                                         _lib.ptr(pts), _lib.ptr(points_int), _lib.ptr(means3D), _lib.ptr(means3D_int),
-                                         _lib.ptr(opacities), _lib.ptr(semantics), _lib.ptr(radii), _lib.ptr(cov3D),
-                                         _lib.ptr(logits), *[_lib.ptr(e) for e in extra], mode, float(threshold),
-                                         int(empty_label), _lib.ptr(labels), _lib.ptr(state), _lib.ptr(ws), nbytes,
-                                         _lib.current_stream(dev))
-    _lib.check(rc, "gf_splat_forward_labels")
+    logits = torch.empty((N, C), dtype=torch.float32, device=dev) if keep_logits else None
+    extra = _per_point(3, N, dev) if (prob and keep_logits) else [None] * 3
+    _lib.call("gf_splat_forward_labels", dev, *args, logits, *extra, mode, float(threshold), int(empty_label), labels, state,
+              ws, ws.numel())
     if not keep_logits:
         return labels
     return (labels, logits, *extra) if prob else (labels, logits)
@@ -193,25 +147,14 @@ class SplatForwardPlan:
     def __init__(self, variant, pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D,
                  H, W, D, flags=_lib.GF_PTS_AUTO):
         self.lib = _lib.load()
-        _lib.require_gpu(pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D)
-        f32, i32 = torch.float32, torch.int32
-        self.inputs = [_contig(t, f32) if t.is_floating_point() else _contig(t, i32)
-                       for t in (pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D)]
-        pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D = self.inputs
-        self.device = pts.device
-        N, P, C = pts.shape[0], means3D.shape[0], semantics.shape[1]
+        self.device, N, P, C, prob, args, self.state, self.workspace = _bind(
+            variant, (pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D), H, W, D, flags,
+            own_workspace=True)   # (zeroed once: GF_WORKSPACE_ZEROED)
+        self.inputs = args[9:]
         self.N, self.P = N, P
-        prob = variant == _lib.GF_SPLAT_PROB
-        self.logits = torch.empty((N, C), dtype=f32, device=self.device)
-        self.bin_logits = torch.empty(N, dtype=f32, device=self.device) if prob else None
-        self.density = torch.empty(N, dtype=f32, device=self.device) if prob else None
-        self.probability = torch.empty(N, dtype=f32, device=self.device) if prob else None
-        self.state = torch.empty(self.lib.gf_splat_state_bytes(), dtype=torch.uint8, device=self.device)
-        self.workspace = torch.zeros(self.lib.gf_splat_workspace_bytes(P, N, H, W, D), dtype=torch.uint8,
-                                     device=self.device)   # (zeroed once: GF_WORKSPACE_ZEROED)
-        flags |= _lib.GF_WORKSPACE_ZEROED
-        self.args = [variant, int(radii.dim() == 2), flags, P, N, C, H, W, D,
-                     *[_lib.ptr(t) for t in self.inputs],
+        self.logits = torch.empty((N, C), dtype=torch.float32, device=self.device)
+        self.bin_logits, self.density, self.probability = _per_point(3, N, self.device) if prob else [None] * 3
+        self.args = [*args[:9], *[_lib.ptr(t) for t in self.inputs],
                      _lib.ptr(self.logits), _lib.ptr(self.bin_logits), _lib.ptr(self.density),
                      _lib.ptr(self.probability), _lib.ptr(self.state), _lib.ptr(self.workspace),
                      self.workspace.numel()]
@@ -270,8 +213,6 @@ def splat_backward(variant, pts, points_int, means3D, means3D_int, opacities, se
     (model/head/localagg/local_aggregate.h:30-43).  ``fwd_outputs`` =
     ``(logits, bin_logits, density, probability)`` for the prob variant.
     Returns ``(means3D_grad, opacity_grad, semantics_grad, cov3D_grad)``."""
-    lib = _lib.load()
-    _lib.require_gpu(pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D, logits_grad)
     if means3D.shape[0] > BACKWARD_MAX_GAUSSIANS:
         # gf_splat_backward takes 262 144 Gaussians per call (include/gf_hip.h); the reference has no such limit, and gradients are
         # per Gaussian: a call per shard with the same out_grad (and the forward's per-point outputs) gives the same rows.  A shard
@@ -284,37 +225,19 @@ def splat_backward(variant, pts, points_int, means3D, means3D_int, opacities, se
                                         radii[sl], cov3D[sl], H, W, D, logits_grad, fwd_outputs=fwd_outputs,
                                         bin_logits_grad=bin_logits_grad, density_grad=density_grad, state=state, flags=sflags))
         return tuple(torch.cat(col, dim=0) for col in zip(*parts))
-    dev = pts.device
-    f32, i32 = torch.float32, torch.int32
     # the same coercions as the forward (the reference calls .contiguous().data<float>() on every backward
     # argument, local_aggregate.cu:116-127): autograd saves the caller's tensors, which may be strided views
     # or another dtype
-    pts, means3D, opacities, semantics, cov3D = (_contig(t, f32) for t in (pts, means3D, opacities, semantics, cov3D))
-    points_int, means3D_int, radii = (_contig(t, i32) for t in (points_int, means3D_int, radii))
-    N, P, C = pts.shape[0], means3D.shape[0], semantics.shape[1]
-    per_axis = int(radii.dim() == 2)
-    logits_grad = _contig(logits_grad, f32)
-    lg = bl = de = pr = None
-    if variant == _lib.GF_SPLAT_PROB:
-        lg, bl, de, pr = (_contig(t, f32) for t in fwd_outputs)
-        bin_logits_grad = None if bin_logits_grad is None else _contig(bin_logits_grad, f32)
-        density_grad = None if density_grad is None else _contig(density_grad, f32)
-    mg = torch.empty((P, 3), dtype=f32, device=dev)
-    og = torch.empty(P, dtype=f32, device=dev)
-    sg = torch.empty((P, C), dtype=f32, device=dev)
-    cg = torch.empty((P, 6), dtype=f32, device=dev)
-    nbytes = lib.gf_splat_workspace_bytes(P, N, H, W, D)
-    ws = _Workspace.get(dev, nbytes)
-    with torch.cuda.device(dev):
-        rc = lib.gf_splat_backward(
-            variant, per_axis, flags, P, N, C, H, W, D,
-            _lib.ptr(pts), _lib.ptr(points_int), _lib.ptr(means3D), _lib.ptr(means3D_int), _lib.ptr(opacities),
-            _lib.ptr(semantics), _lib.ptr(radii), _lib.ptr(cov3D),
-            _lib.ptr(lg), _lib.ptr(bl), _lib.ptr(de), _lib.ptr(pr),
-            _lib.ptr(logits_grad), _lib.ptr(bin_logits_grad), _lib.ptr(density_grad),
-            _lib.ptr(mg), _lib.ptr(og), _lib.ptr(sg), _lib.ptr(cg), _lib.ptr(state),
-            _lib.ptr(ws), ws.numel(), _lib.current_stream(dev))
-    _lib.check(rc, "gf_splat_backward")
+    _lib.require_gpu(logits_grad)
+    dev, N, P, C, prob, args, _, ws = _bind(
+        variant, (pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D), H, W, D, flags, forward=False)
+    fwd = [None] * 4
+    if prob:
+        fwd = [_lib.as_arg(t) for t in fwd_outputs]
+        bin_logits_grad, density_grad = _lib.as_arg(bin_logits_grad), _lib.as_arg(density_grad)
+    mg, og, sg, cg = (torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((P, 3), P, (P, C), (P, 6)))
+    _lib.call("gf_splat_backward", dev, *args, *fwd, _lib.as_arg(logits_grad), bin_logits_grad, density_grad,
+              mg, og, sg, cg, state, ws, ws.numel())
     return mg, og, sg, cg
 
 
@@ -323,18 +246,13 @@ def splat_box_volumes(means3D_int, radii, H, W, D):
     FORWARD::preprocessCUDA + the inclusive scan's last element
     (model/head/localagg/src/forward.cu:9-28, src/aggregator_impl.cu:193-197).
     Reading ``num_rendered`` synchronises the stream (the reference does too, :197)."""
-    lib = _lib.load()
     _lib.require_gpu(means3D_int, radii)
     dev = means3D_int.device
-    means3D_int = _contig(means3D_int, torch.int32)
-    radii = _contig(radii, torch.int32)
+    means3D_int, radii = _lib.as_arg(means3D_int, torch.int32), _lib.as_arg(radii, torch.int32)
     P = means3D_int.shape[0]
     touched = torch.zeros(P, dtype=torch.int32, device=dev)
     total = torch.zeros(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gf_splat_box_volumes(int(radii.dim() == 2), P, H, W, D, _lib.ptr(means3D_int), _lib.ptr(radii),
-                                      _lib.ptr(touched), _lib.ptr(total), _lib.current_stream(dev))
-    _lib.check(rc, "gf_splat_box_volumes")
+    _lib.call("gf_splat_box_volumes", dev, int(radii.dim() == 2), P, H, W, D, means3D_int, radii, touched, total)
     return touched.to(torch.int64) & 0xFFFFFFFF, int(total.item())
 
 
@@ -358,12 +276,9 @@ class _LocalAggregate(torch.autograd.Function):
         # to pinned host memory behind an event -- never waited for: by the time the backward runs the copy has usually landed
         # and exactly one pipeline is launched (not while a HIP graph is being captured: no host allocation there).
         ctx.state_host = ctx.state_event = None
-        ctx.ws_stamp = _Workspace.stamp(pts.device) if state.is_cuda else None
-        if any(ctx.needs_input_grad) and state.is_cuda and not torch.cuda.is_current_stream_capturing():
-            ctx.state_host = torch.empty(5, dtype=torch.int32, pin_memory=True)
-            ctx.state_host.copy_(state[:20].view(torch.int32), non_blocking=True)
-            ctx.state_event = torch.cuda.Event()
-            ctx.state_event.record(torch.cuda.current_stream(pts.device))
+        ctx.ws_stamp = _scratch.stamp(pts.device) if state.is_cuda else None
+        if wants_grad and state.is_cuda:
+            ctx.state_host, ctx.state_event = _lib.host_copy(state[:20].view(torch.int32), pts.device)
         ctx.save_for_backward(state, means3D, means3D_int, pts, points_int, cov3D, opacities, semantics, radii)
         _tls.last_state = state   # (this thread's last call: picked up by LocalAggregator._splat right after apply() returns)
         return logits
@@ -384,7 +299,7 @@ class _LocalAggregate(torch.autograd.Function):
             bflags = _lib.GF_MFMA_SPLAT if on_matrix_cores and not (words[4] & 2) else _lib.GF_EXACT_FP32
             # the forward's records pass laid out the backward's rows as well (word 4); if nobody has been handed this stream's
             # workspace since, the backward does not repeat that pass
-            if on_matrix_cores and (words[4] & 1) and ctx.ws_stamp == _Workspace.stamp(out_grad.device):
+            if on_matrix_cores and (words[4] & 1) and ctx.ws_stamp == _scratch.stamp(out_grad.device):
                 bflags |= _lib.GF_RECORDS_VALID
         else:
             bflags = _lib.GF_PTS_AUTO
@@ -422,6 +337,17 @@ class _LocalAggregateProb(torch.autograd.Function):
 
 class _AggregatorBase(nn.Module):
     """Shared pre-processing of the three ``LocalAggregator`` classes."""
+
+    def __init__(self, scale_multiplier, H, W, D, pc_min, grid_size, check_inputs):
+        super().__init__()
+        self.scale_multiplier = scale_multiplier
+        self.H = H
+        self.W = W
+        self.D = D
+        self.register_buffer('pc_min', torch.tensor(pc_min, dtype=torch.float).unsqueeze(0))
+        self.grid_size = grid_size
+        self.check_inputs = check_inputs
+        self._pc_min_host = [float(v) for v in pc_min]
 
     def _points_int(self, pts):
         """Voxel indices of the query points: fp32 subtract, fp32 true division, truncation (``.to(torch.int)``) --
@@ -466,6 +392,16 @@ class _AggregatorBase(nn.Module):
                 (means3D_int < 0).any() | (means3D_int >= hi).any()])
         return pts, points_int, means3D, means3D_int, opacities, semantics, scales, cov3D, violations
 
+    def _splat_inputs(self, pts, means3D, opacities, semantics, scales, cov3D):
+        """The splat's eight tensors ``(pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov6)`` from the
+        module's inputs, range-checked (``check_inputs``)."""
+        pts, points_int, means3D, means3D_int, opacities, semantics, scales, cov3D, violations = self._prepare(
+            pts, means3D, opacities, semantics, scales, cov3D)
+        radii = self._radii(scales)
+        self._raise_on_violation(violations, radii)
+        cov6 = cov3D.flatten(1)[:, [0, 4, 8, 1, 5, 2]]   # (xx, yy, zz, xy, yz, xz) of the 3x3, :143
+        return pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov6
+
     _radii_mode = _lib.GF_RADII_SCALAR
 
     def _radii(self, scales):
@@ -484,11 +420,8 @@ class _AggregatorBase(nn.Module):
         like ``forward``."""
         assert 0 <= x0 < x1 <= self.H and pts.shape[0] == 1 and pts.shape[1] == self.H * self.W * self.D
         n0, n1 = x0 * self.W * self.D, x1 * self.W * self.D
-        pts_s, points_int, means3D, means3D_int, opacities, semantics, scales, cov3D, violations = self._prepare(
+        pts_s, points_int, means3D, means3D_int, opacities, semantics, radii, cov6 = self._splat_inputs(
             pts[:, n0:n1], means3D, opacities, semantics, scales, cov3D)
-        radii = self._radii(scales)
-        self._raise_on_violation(violations, radii)
-        cov6 = cov3D.flatten(1)[:, [0, 4, 8, 1, 5, 2]]
         shift = points_int.new_tensor([x0, 0, 0])
         return self._splat(pts_s, points_int - shift, means3D, means3D_int - shift, opacities, semantics, radii, cov6, H=x1 - x0)
 
@@ -543,17 +476,9 @@ class LocalAggregator(_AggregatorBase):
     forward the exact Gaussian-major kernels."""
 
     def __init__(self, scale_multiplier, H, W, D, pc_min, grid_size, inv_softmax=False, check_inputs=True, matrix_cores=None):
-        super().__init__()
+        super().__init__(scale_multiplier, H, W, D, pc_min, grid_size, check_inputs)
         self.matrix_cores = matrix_cores
-        self.scale_multiplier = scale_multiplier
-        self.H = H
-        self.W = W
-        self.D = D
-        self.register_buffer('pc_min', torch.tensor(pc_min, dtype=torch.float).unsqueeze(0))
-        self.grid_size = grid_size
         self.inv_softmax = inv_softmax
-        self.check_inputs = check_inputs
-        self._pc_min_host = [float(v) for v in pc_min]
         self._grid_exact = None     # grid_is_exact_lattice(...) of this module's grid, judged on first use
         self._registered = None     # register_grid()
 
@@ -615,23 +540,14 @@ class LocalAggregator(_AggregatorBase):
                 self._grid_exact = False
             w["host"] = w["event"] = None
         w["calls"] += 1
-        if (w["event"] is None and state is not None and state.is_cuda and (w["calls"] <= 3 or w["calls"] % 64 == 0)
-                and not torch.cuda.is_current_stream_capturing()):
-            w["host"] = torch.empty(5, dtype=torch.int32, pin_memory=True)
-            w["host"].copy_(state[:20].view(torch.int32), non_blocking=True)
-            w["event"] = torch.cuda.Event()
-            w["event"].record(torch.cuda.current_stream(device))
+        if w["event"] is None and state is not None and state.is_cuda and (w["calls"] <= 3 or w["calls"] % 64 == 0):
+            w["host"], w["event"] = _lib.host_copy(state[:20].view(torch.int32), device)
 
     def _radii(self, scales):
         return torch.ceil(scales.max(dim=-1)[0] * self.scale_multiplier / self.grid_size).to(torch.int)
 
     def forward(self, pts, means3D, opacities, semantics, scales, cov3D):
-        pts, points_int, means3D, means3D_int, opacities, semantics, scales, cov3D, violations = self._prepare(
-            pts, means3D, opacities, semantics, scales, cov3D)
-        radii = self._radii(scales)
-        self._raise_on_violation(violations, radii)
-        cov3D = cov3D.flatten(1)[:, [0, 4, 8, 1, 5, 2]]   # (xx, yy, zz, xy, yz, xz) of the 3x3, :143
-        logits = self._splat(pts, points_int, means3D, means3D_int, opacities, semantics, radii, cov3D)
+        logits = self._splat(*self._splat_inputs(pts, means3D, opacities, semantics, scales, cov3D))
         assert not self.inv_softmax, "inv_softmax=True is an `assert False` in the reference too (:158-161)"
         return logits
 
@@ -643,16 +559,8 @@ class LocalAggregatorProb(_AggregatorBase):
     per_axis_radii = False
 
     def __init__(self, scale_multiplier, H, W, D, pc_min, grid_size, radii_min=1, check_inputs=True):
-        super().__init__()
-        self.scale_multiplier = scale_multiplier
-        self.H = H
-        self.W = W
-        self.D = D
-        self.register_buffer('pc_min', torch.tensor(pc_min, dtype=torch.float).unsqueeze(0))
-        self.grid_size = grid_size
+        super().__init__(scale_multiplier, H, W, D, pc_min, grid_size, check_inputs)
         self.radii_min = radii_min
-        self.check_inputs = check_inputs
-        self._pc_min_host = [float(v) for v in pc_min]
 
     @property
     def _radii_mode(self):
@@ -669,26 +577,15 @@ class LocalAggregatorProb(_AggregatorBase):
         return radii.clamp(min=self.radii_min)
 
     def forward(self, pts, means3D, opas, semantics, scales, cov3D):
-        pts, points_int, means3D, means3D_int, opas, semantics, scales, cov3D, violations = self._prepare(
-            pts, means3D, opas, semantics, scales, cov3D)
-        radii = self._radii(scales)
-        self._raise_on_violation(violations, radii)
-        cov3D = cov3D.flatten(1)[:, [0, 4, 8, 1, 5, 2]]
-        return _LocalAggregateProb.apply(pts, points_int, means3D, means3D_int, opas, semantics, radii, cov3D,
-                                         self.H, self.W, self.D)
+        return self._splat(*self._splat_inputs(pts, means3D, opas, semantics, scales, cov3D))
 
     @torch.no_grad()
     def forward_pieces(self, pts, means3D, opas, semantics, scales, cov3D):
         """Inference-only: ``(numerator [n,18], bin_logits [n], density [n], probability [n])`` with the
         un-normalised numerator (``GF_PROB_NUMERATOR``) -- what the shards of
         ``sharded.sharded_splat_forward_prob`` exchange before normalising."""
-        pts, points_int, means3D, means3D_int, opas, semantics, scales, cov3D, violations = self._prepare(
-            pts, means3D, opas, semantics, scales, cov3D)
-        radii = self._radii(scales)
-        self._raise_on_violation(violations, radii)
-        cov3D = cov3D.flatten(1)[:, [0, 4, 8, 1, 5, 2]]
         numerator, bin_logits, density, probability, _ = splat_forward(
-            _lib.GF_SPLAT_PROB, pts, points_int, means3D, means3D_int, opas, semantics, radii, cov3D,
+            _lib.GF_SPLAT_PROB, *self._splat_inputs(pts, means3D, opas, semantics, scales, cov3D),
             self.H, self.W, self.D, flags=_lib.GF_PTS_AUTO | _lib.GF_PROB_NUMERATOR)
         return numerator, bin_logits, density, probability
 

@@ -81,11 +81,9 @@ class _OccLoss(torch.autograd.Function):
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)     # the forward's own: freed when it returns
         loss = torch.empty((), dtype=torch.float32, device=dev)
         ptrs = (ctypes.c_void_p * L)(*[p.data_ptr() for p in preds])
-        _lib.check(lib.gf_occ_loss_forward(L, N, _C, cfg["flags"], ptrs, sc, sn, label.data_ptr(), _lib.ptr(mask),
-                                           class_weights.data_ptr(), cfg["ce_weight"], cfg["lovasz_weight"],
-                                           cfg["lovasz_ignore"], cfg["ignore_index"], cfg["empty_label"], loss.data_ptr(),
-                                           ws.data_ptr(), nbytes, scratch.data_ptr(), sbytes, _lib.current_stream(dev)),
-                   "gf_occ_loss_forward")
+        _lib.call("gf_occ_loss_forward", dev, L, N, _C, cfg["flags"], ptrs, sc, sn, label, mask, class_weights,
+                  cfg["ce_weight"], cfg["lovasz_weight"], cfg["lovasz_ignore"], cfg["ignore_index"], cfg["empty_label"], loss,
+                  ws, nbytes, scratch, sbytes)
         ctx.cfg, ctx.layout = cfg, (N, sc, sn)
         ctx.save_for_backward(label, mask, class_weights, ws, *preds)
         return loss
@@ -95,16 +93,14 @@ class _OccLoss(torch.autograd.Function):
         label, mask, class_weights, ws, *preds = ctx.saved_tensors
         cfg, (N, sc, sn) = ctx.cfg, ctx.layout
         L = len(preds)
-        lib = _lib.load()
         dev = preds[0].device
         grads = [torch.empty_strided(p.shape, p.stride(), dtype=torch.float32, device=dev) for p in preds]
-        g = grad_loss.to(dtype=torch.float32).contiguous()
+        g = _lib.as_arg(grad_loss)
         pp = (ctypes.c_void_p * L)(*[p.data_ptr() for p in preds])
         gp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in grads])
-        _lib.check(lib.gf_occ_loss_backward(L, N, _C, cfg["flags"], pp, sc, sn, label.data_ptr(), _lib.ptr(mask),
-                                            class_weights.data_ptr(), cfg["ce_weight"], cfg["lovasz_weight"],
-                                            cfg["lovasz_ignore"], cfg["ignore_index"], cfg["empty_label"], g.data_ptr(), gp,
-                                            ws.data_ptr(), ws.numel(), _lib.current_stream(dev)), "gf_occ_loss_backward")
+        _lib.call("gf_occ_loss_backward", dev, L, N, _C, cfg["flags"], pp, sc, sn, label, mask, class_weights,
+                  cfg["ce_weight"], cfg["lovasz_weight"], cfg["lovasz_ignore"], cfg["ignore_index"], cfg["empty_label"], g, gp,
+                  ws, ws.numel())
         return (None, None, None, None, *grads)
 
 

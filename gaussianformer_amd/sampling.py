@@ -38,15 +38,12 @@ def farthest_point_sampling(xyz, offset, new_offset):
         raise ValueError("farthest_point_sampling: offsets out of the int32 range")
     off_h, new_h = off_h.astype(np.int32), new_h.astype(np.int32)
     n, b, total = int(xyz.shape[0]), int(off_h.size), int(new_h[-1])
-    p = xyz.detach().to(torch.float32).contiguous()
+    p = _lib.as_arg(xyz)
     off_d = torch.from_numpy(off_h).to(dev)
     new_d = torch.from_numpy(new_h).to(dev)
     idx = torch.empty(max(total, 0), dtype=torch.int32, device=dev)
     ws_bytes = lib.gf_fps_workspace_bytes(n)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gf_farthest_point_sampling(n, b, off_h.ctypes.data_as(ctypes.c_void_p), new_h.ctypes.data_as(ctypes.c_void_p),
-                                            _lib.ptr(p), _lib.ptr(off_d), _lib.ptr(new_d), _lib.ptr(idx), _lib.ptr(ws), ws_bytes,
-                                            _lib.current_stream(dev))
-    _lib.check(rc, "gf_farthest_point_sampling")
+    _lib.call("gf_farthest_point_sampling", dev, n, b, off_h.ctypes.data_as(ctypes.c_void_p),
+              new_h.ctypes.data_as(ctypes.c_void_p), p, off_d, new_d, idx, ws, ws_bytes)
     return idx

@@ -34,13 +34,11 @@ class Rulebook:
         anchor-sharded rank owns, at ``(hi - lo) / N`` of the gather-GEMM work; the other rows of ``apply`` are zeros."""
         _lib.require_gpu(indices)
         lib = _lib.load()
-        self.indices = indices.detach().to(i32).contiguous()
+        self.indices = _lib.as_arg(indices, i32)
         self.N = self.indices.shape[0]
         self.out_range = None if out_range is None else (int(out_range[0]), int(out_range[1]))
         rng = () if self.out_range is None else self.out_range
-        count_fn = lib.gf_subm_rulebook_count if self.out_range is None else lib.gf_subm_rulebook_count_range
-        fill_fn = lib.gf_subm_rulebook_fill if self.out_range is None else lib.gf_subm_rulebook_fill_range
-        build_fn = lib.gf_subm_rulebook_build if self.out_range is None else lib.gf_subm_rulebook_build_range
+        suffix = "" if self.out_range is None else "_range"   # (the entry points used, so an error names the right one)
         self.dims = (self.N, int(batch_size), int(spatial_shape[0]), int(spatial_shape[1]), int(spatial_shape[2]),
                      int(kernel_size))
         dev = self.indices.device
@@ -50,32 +48,22 @@ class Rulebook:
         self.tables = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self._status = self.tables[nbytes - 256:nbytes - 240].view(torch.int64)   # (pair count, refusal bits)
         self.checked = pair_capacity is None
-        with torch.cuda.device(dev):
-            if pair_capacity is not None:
-                self.total = max(int(pair_capacity), 1)
-                self.pair_in = torch.empty(self.total, dtype=i32, device=dev)
-                self.pair_out = torch.empty(self.total, dtype=i32, device=dev)
-                rc = build_fn(*self.dims, *rng, _lib.ptr(self.indices), _lib.ptr(self.tables), nbytes,
-                                                _lib.ptr(self.pair_in), _lib.ptr(self.pair_out), self.total, _lib.current_stream(dev))
-                _lib.check(rc, "gf_subm_rulebook_build")
-                # deferred check: status -> pinned host memory on the same stream, event behind the copy
-                # (not while a HIP graph is being captured: no host allocation there; check() still works after a replay)
-                self._status_event = None
-                if not torch.cuda.is_current_stream_capturing():
-                    self._host_status = torch.empty(2, dtype=torch.int64, pin_memory=True)
-                    self._host_status.copy_(self._status, non_blocking=True)
-                    self._status_event = torch.cuda.Event()
-                    self._status_event.record(torch.cuda.current_stream(dev))
-                return
-            rc = count_fn(*self.dims, *rng, _lib.ptr(self.indices), _lib.ptr(self.tables), nbytes, _lib.current_stream(dev))
-            _lib.check(rc, "gf_subm_rulebook_count")
-            total = self.check()   # the one host read
-            self.total = int(total)
-            self.pair_in = torch.empty(max(self.total, 1), dtype=i32, device=dev)
-            self.pair_out = torch.empty(max(self.total, 1), dtype=i32, device=dev)
-            rc = fill_fn(*self.dims, *rng, _lib.ptr(self.indices), _lib.ptr(self.tables),
-                         _lib.ptr(self.pair_in), _lib.ptr(self.pair_out), _lib.current_stream(dev))
-            _lib.check(rc, "gf_subm_rulebook_fill")
+        if pair_capacity is not None:
+            self.total = max(int(pair_capacity), 1)
+            self.pair_in = torch.empty(self.total, dtype=i32, device=dev)
+            self.pair_out = torch.empty(self.total, dtype=i32, device=dev)
+            _lib.call("gf_subm_rulebook_build" + suffix, dev, *self.dims, *rng, self.indices, self.tables, nbytes,
+                      self.pair_in, self.pair_out, self.total)
+            # deferred check: status -> pinned host memory on the same stream, event behind the copy
+            # (not while a HIP graph is being captured: no host allocation there; check() still works after a replay)
+            self._host_status, self._status_event = _lib.host_copy(self._status, dev)
+            return
+        _lib.call("gf_subm_rulebook_count" + suffix, dev, *self.dims, *rng, self.indices, self.tables, nbytes)
+        total = self.check()   # the one host read
+        self.total = int(total)
+        self.pair_in = torch.empty(max(self.total, 1), dtype=i32, device=dev)
+        self.pair_out = torch.empty(max(self.total, 1), dtype=i32, device=dev)
+        _lib.call("gf_subm_rulebook_fill" + suffix, dev, *self.dims, *rng, self.indices, self.tables, self.pair_in, self.pair_out)
 
     def representative_mask(self):
         """``[N,1]`` fp32, 1 for the point with the LARGEST index of its cell (and for points outside the grid), 0 for the
@@ -125,7 +113,7 @@ class Rulebook:
     def apply(self, features, weight):
         """``out[N, Cout]`` for ``features [N, Cin]`` and ``weight [K^3, Cin, Cout]`` (no autograd)."""
         lib = _lib.load()
-        features, weight = features.detach().to(f32).contiguous(), weight.detach().to(f32).contiguous()
+        features, weight = _lib.as_arg(features), _lib.as_arg(weight)
         cin, cout = weight.shape[1], weight.shape[2]
         dev = features.device
         out = torch.empty(self.N, cout, dtype=f32, device=dev)
@@ -133,24 +121,17 @@ class Rulebook:
         # (the rows as two f16 terms under a power-of-two scale per row, split once per call: gf_subm_conv_apply_scratch)
         nscratch = int(lib.gf_subm_apply_scratch_bytes(self.N, cin))
         scratch = torch.empty(max(nscratch, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.gf_subm_conv_apply_scratch(*self.dims, cin, cout, self.total, _lib.ptr(features), _lib.ptr(weight), _lib.ptr(self.tables),
-                                                _lib.ptr(self.pair_in), _lib.ptr(partial), _lib.ptr(out), _lib.ptr(scratch), nscratch,
-                                                _lib.current_stream(dev))
-        _lib.check(rc, "gf_subm_conv_apply_scratch")
+        _lib.call("gf_subm_conv_apply_scratch", dev, *self.dims, cin, cout, self.total, features, weight, self.tables,
+                  self.pair_in, partial, out, scratch, nscratch)
         return out
 
     def weight_grad(self, features, grad_out):
-        lib = _lib.load()
-        features, grad_out = features.detach().to(f32).contiguous(), grad_out.detach().to(f32).contiguous()
+        features, grad_out = _lib.as_arg(features), _lib.as_arg(grad_out)
         cin, cout = features.shape[1], grad_out.shape[1]
         k3 = self.dims[5] ** 3
         gw = torch.empty(k3, cin, cout, dtype=f32, device=features.device)
-        with torch.cuda.device(features.device):
-            rc = lib.gf_subm_conv_weight_grad(*self.dims, cin, cout, self.total, _lib.ptr(features), _lib.ptr(grad_out),
-                                              _lib.ptr(self.tables), _lib.ptr(self.pair_in), _lib.ptr(self.pair_out),
-                                              _lib.ptr(gw), _lib.current_stream(features.device))
-        _lib.check(rc, "gf_subm_conv_weight_grad")
+        _lib.call("gf_subm_conv_weight_grad", features.device, *self.dims, cin, cout, self.total, features, grad_out,
+                  self.tables, self.pair_in, self.pair_out, gw)
         return gw
 
 
@@ -282,11 +263,7 @@ class SparseConv3D(nn.Module):
             arr = lambda v: (ctypes.c_float * 3)(*[float(np.float32(x)) for x in v])
             host = self._voxel_host = (key, arr([r[3 + a] - r[a] for a in range(3)]), arr([r[a] for a in range(3)]), arr(pc[:3]), arr(gs[:3]))
         out = torch.empty((bs * g, 4), dtype=torch.int32, device=anchor.device)
-        lib = _lib.load()
-        with torch.cuda.device(anchor.device):
-            rc = lib.gf_subm_voxelize(bs * g, g, a2.shape[1], int(self.use_sigmoid), _lib.ptr(a2), host[1], host[2], host[3], host[4],
-                                      _lib.ptr(out), _lib.current_stream(anchor.device))
-        _lib.check(rc, "gf_subm_voxelize")
+        _lib.call("gf_subm_voxelize", anchor.device, bs * g, g, a2.shape[1], int(self.use_sigmoid), a2, *host[1:], out)
         return out
 
     def _voxel_indices_torch(self, anchor):

@@ -111,3 +111,105 @@ def test_python_constants_match_the_header_defines():
     for n in mirrored:
         assert n in defines, f"{n} is not defined in include/gf_hip.h"
         assert defines[n] == getattr(_lib, n), (n, defines[n], getattr(_lib, n))
+
+
+def _streamed():
+    """The entry points that launch: their last parameter is ``void *stream`` (include/gf_hip.h)."""
+    text = open(os.path.join(ROOT, "include", "gf_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    protos = re.findall(r"\b(gf_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
+    names = sorted(n for n, args in protos if re.search(r"\bvoid\s*\*\s*stream\s*$", args))
+    assert len(names) >= 30 and all(_lib.SIGNATURES[n][1][-1] is ctypes.c_void_p for n in names)
+    return names
+
+
+def test_every_launch_goes_through_the_helper():
+    """No module of the package enters a device guard or calls a launching entry point itself: ``_lib.call`` does both, so
+    the guard, the stream and the name in the error cannot be forgotten or mistyped per op.  The one exception is
+    ``SplatForwardPlan.run`` (gaussianformer_amd/local_aggregate.py), the pre-bound call the benchmark times."""
+    import glob
+    direct = re.compile(r"\.\s*(" + "|".join(_streamed()) + r")\s*\(")
+    paths = sorted(glob.glob(os.path.join(ROOT, "gaussianformer_amd", "*.py")))
+    assert len(paths) >= 15
+    for path in paths:
+        if os.path.basename(path) == "_lib.py":
+            continue
+        src = open(path).read()
+        if os.path.basename(path) == "local_aggregate.py":
+            run = re.search(r"\n    def run\(self, stream=None\):\n.*?\n(?=    def )", src, flags=re.S)
+            assert run is not None and src.index("class SplatForwardPlan:") < run.start() < src.index("class SplatForwardPipeline:")
+            assert "self.lib.gf_splat_forward(*self.args, stream)" in run.group(0)
+            src = src[:run.start()] + src[run.end():]
+        assert "torch.cuda.device(" not in src, path
+        assert direct.search(src) is None, (path, direct.search(src).group(0))
+
+
+def test_call_marshals_and_names_the_entry_point():
+    """``_lib.call`` through the argument validation of ``gf_splat_forward`` (17 channels, as
+    test_argument_validation_without_gpu): the error carries the entry point's name and the library's message.  There is no
+    GPU here and ``torch.cuda.device`` cannot be entered for a CPU device, so ``call`` gives a device that is not a GPU no
+    guard and a NULL stream -- the library refuses these arguments before any HIP call."""
+    import pytest
+    import torch
+    cpu = torch.device("cpu")
+    with pytest.raises(RuntimeError, match=r"gf_splat_forward failed \(code -1\): .*18"):
+        _lib.call("gf_splat_forward", cpu, 0, 0, 0, 1, 1, 17, 8, 8, 8, *([None] * 13), None, 0)
+    with pytest.raises(RuntimeError, match=r"gf_daf_forward_pinned failed .*divisible"):
+        _lib.call("gf_daf_forward_pinned", cpu, 1, 6, 100, 128, 4, 10, 5, *([None] * 6))
+    with pytest.raises(AttributeError):
+        _lib.call("gf_no_such_entry_point", cpu)
+    # tensors cross as their data pointers (the library sees a non-NULL pts and still refuses the channel count)
+    t = torch.zeros(4)
+    with pytest.raises(RuntimeError, match="gf_splat_forward failed"):
+        _lib.call("gf_splat_forward", cpu, 0, 0, 0, 1, 1, 17, 8, 8, 8, t, *([None] * 12), None, 0)
+
+
+def test_as_arg():
+    import torch
+    assert _lib.as_arg(None) is None
+    x = torch.arange(12.0).reshape(3, 4).requires_grad_(True)
+    a = _lib.as_arg(x)
+    assert not a.requires_grad and a.data_ptr() == x.data_ptr()          # detached, no copy when nothing is to do
+    b = _lib.as_arg(x.t(), torch.int32)
+    assert b.dtype == torch.int32 and b.is_contiguous() and b.tolist() == x.t().int().tolist()
+    m = torch.ones(5, dtype=torch.bool)
+    assert _lib.as_arg(m, torch.bool).data_ptr() == m.data_ptr()
+
+
+def test_stream_scratch():
+    """The per-(device, stream) scratch cache, on CPU tensors with a stand-in for the current stream."""
+    import torch
+    cpu = torch.device("cpu")
+    stream = [0]
+    splat = _lib.StreamScratch(min_bytes=1 << 20, zeroed_bytes=32768, stream_of=lambda device: stream[0])
+    other = _lib.StreamScratch(stream_of=lambda device: stream[0])
+    a = splat.get(cpu, 100)
+    assert a.dtype == torch.uint8 and a.numel() == 1 << 20 and not a[:32768].any()     # minimum size, zeroed flag section
+    a[:32768] = 7
+    assert splat.get(cpu, 4096).data_ptr() == a.data_ptr() and bool((a[:32768] == 7).all())   # reused, never zeroed again
+    big = splat.get(cpu, (1 << 20) + 1)
+    assert big.numel() == (1 << 20) + 1 and not big[:32768].any()                       # grows ...
+    assert splat.get(cpu, 100).data_ptr() == big.data_ptr()                             # ... and never shrinks
+    assert other.get(cpu, 100).numel() == 100                                           # no minimum of its own
+    # stamp(): moved by any hand-out of the same cache, not by another cache's
+    s0 = splat.stamp(cpu)
+    assert s0 == splat.stamp(cpu) and s0[1] == big.data_ptr()
+    other.get(cpu, 100)
+    assert splat.stamp(cpu) == s0
+    splat.get(cpu, 100)
+    assert splat.stamp(cpu) != s0
+    # at most MAX_STREAMS buffers, the most recently used ones
+    assert _lib.StreamScratch.MAX_STREAMS == 8
+    for s in range(1, 8):
+        stream[0] = s
+        splat.get(cpu, 100)
+    assert len(splat._cache) == 8
+    stream[0] = 0
+    assert splat.get(cpu, 100).data_ptr() == big.data_ptr()      # stream 0 is the most recently used now
+    stream[0] = 8
+    splat.get(cpu, 100)                                          # a ninth stream: the least recently used (1) goes
+    assert len(splat._cache) == 8
+    kept = sorted(k[2] for k in splat._cache)
+    assert kept == [0, 2, 3, 4, 5, 6, 7, 8]
+    stream[0] = 0
+    assert splat.get(cpu, 100).data_ptr() == big.data_ptr()

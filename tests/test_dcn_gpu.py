@@ -235,3 +235,37 @@ def test_bottleneck_trains_one_step(gpu):
     opt.step()
     assert not torch.equal(before, dcn.conv_offset.weight)
     assert torch.isfinite((net(x) - x).square().mean())
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_launches_go_to_the_tensors_device_not_the_current_one(gpu):
+    """DCNv2 and the occupancy loss, forward and backward, on tensors of device 1 while device 0 is current, against the same
+    calls with device 1 current: the same bits, except ``grad_input`` (fp32 atomics), which is held to this file's row bound."""
+    from gaussianformer_amd.occupancy_loss import occupancy_loss
+    other = torch.device("cuda:1")
+    gen = torch.Generator(device="cpu").manual_seed(11)
+    c = make_case(other, 2, 32, 9, 11, 32, 3, 3, padding=1, seed=5)
+    gout = torch.randn(2, 32, 9, 11, generator=gen).to(other)
+    n = 4096
+    pred = [torch.randn(1, n, 18, generator=gen).to(other) for _ in range(2)]
+    label = torch.randint(0, 18, (1, n), generator=gen).to(other)
+    mask = (torch.rand(1, n, generator=gen) < 0.8).to(other)
+    weights = (torch.rand(18, generator=gen) + 0.5).to(other)
+
+    def run():
+        res = native(c, gout)
+        leaves = [p.clone().requires_grad_(True) for p in pred]
+        loss = occupancy_loss([t.transpose(1, 2) for t in leaves], label, mask, class_weights=weights, lovasz_ignore=17)
+        loss.backward()
+        torch.cuda.synchronize(other)
+        return res, [loss.detach()] + [t.grad for t in leaves]
+
+    with torch.cuda.device(1):
+        want_dcn, want_loss = run()
+    with torch.cuda.device(0):
+        got_dcn, got_loss = run()
+    for k in ("out", "goff", "gm", "gw", "gb"):
+        assert torch.equal(got_dcn[k], want_dcn[k]), k
+    assert_rows(got_dcn["gx"], want_dcn["gx"].double(), 2 * 32, "grad_input")
+    for g, w in zip(got_loss, want_loss):
+        assert g.device == other and torch.equal(g, w)
