@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GF_LIB selects an instrumentation build (-DGF_TIMELINE=1, -DGF_DAF_TL) made by build.build(lib_name=...) (tools/ only)
 LIB_PATH = os.environ.get("GF_LIB") or os.path.join(_HERE, "csrc", "libgf_hip.so")
 
-GF_ABI_VERSION = 9
+GF_ABI_VERSION = 10
 GF_SPLAT_BASE, GF_SPLAT_PROB = 0, 1
 GF_NUM_CHANNELS = 18
 GF_LABELS_ARGMAX, GF_LABELS_PROB_THRESHOLD, GF_LABELS_PROB_GEOSEM = 0, 1, 2
@@ -30,6 +30,7 @@ GF_WORKSPACE_ZEROED = 2048
 GF_OCC_PROB, GF_OCC_MASK, GF_OCC_LOVASZ_IGNORE, GF_OCC_IGNORE_EMPTY, GF_OCC_NO_LOVASZ, GF_OCC_MAX_LAYERS = 1, 2, 4, 8, 16, 8
 GF_LIFT_MAX_BINS, GF_LIFT_MAX_ANCHORS, GF_PIXEL_LOSS_SOFTMAX, GF_PIXEL_LOSS_SIGMOID = 256, 8, 1, 2
 GF_DCN_MAX_KERNEL, GF_DCN_CHANNEL_GRANULE = 7, 32
+GF_REFINE_RESTRICT_XYZ, GF_REFINE_XYZ_IDENTITY, GF_REFINE_OPACITY, GF_REFINE_SEM_SOFTMAX, GF_REFINE_SEM_SOFTPLUS = 1, 2, 4, 8, 16
 GF_PATH_EXACT_TILE, GF_PATH_MATRIX_CORE, GF_PATH_ARBITRARY, GF_PATH_MATRIX_CORE_WAVE, GF_PATH_MATRIX_CORE_PAIR, GF_PATH_MATRIX_CORE_SOLO = 0, 1, 2, 3, 4, 5
 GF_PATHS_MATRIX_CORE = (GF_PATH_MATRIX_CORE, GF_PATH_MATRIX_CORE_WAVE, GF_PATH_MATRIX_CORE_PAIR, GF_PATH_MATRIX_CORE_SOLO)
 
@@ -92,6 +93,8 @@ SIGNATURES = {
     "gf_dcn_workspace_bytes": (_sz, [_i] * 16),
     "gf_dcn_forward": (_i, [_i] * 15 + [_vp] * 6 + [_vp, _sz, _vp]),
     "gf_dcn_backward": (_i, [_i] * 15 + [_vp] * 10 + [_vp, _sz, _vp]),
+    "gf_refine_forward": (_i, [_i] * 7 + [_vp] * 11 + [_vp]),
+    "gf_refine_backward": (_i, [_i] * 7 + [_vp] * 13 + [_vp]),
     "gf_profile_enable": (_i, [_i]),
     "gf_profile_stride": (_i, [_i]),
     "gf_profile_read": (_i, [_vp, _i]),

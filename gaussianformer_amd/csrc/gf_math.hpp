@@ -41,6 +41,19 @@ __device__ __forceinline__ void split3(double t, _Float16 &a, _Float16 &b, _Floa
 // exp(x) as v_exp_f32 on x log2(e): relative error <= 1e-6 for |x| < 16
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
+// ---- safe_sigmoid (model/utils/safe_ops.py:7-9): clamp to +-9.21, then 1 / (1 + exp(-x)) with ocml's expf (key points, refine)
+constexpr float kSigmoidClamp = 9.21f;
+__device__ __forceinline__ float safe_sigmoid(float x)
+{
+    x = fminf(fmaxf(x, -kSigmoidClamp), kSigmoidClamp);
+    return 1.f / (1.f + expf(-x));
+}
+// d safe_sigmoid / dx given its value s (torch.clamp passes the gradient on [min, max], bounds included)
+__device__ __forceinline__ float safe_sigmoid_grad(float x, float s)
+{
+    return (x >= -kSigmoidClamp && x <= kSigmoidClamp) ? s * (1.f - s) : 0.f;
+}
+
 // ---- unit quaternion (w, x, y, z) = F.normalize(q, dim=-1) = q / max(||q||, 1e-12) (model/utils/utils.py:23) ------------------
 struct UnitQuat {
     float w, x, y, z, inv_norm;

@@ -24,19 +24,7 @@ struct KeyPointArgs {
     int identity;  // bit 0: xyz_activation != "sigmoid" (centre columns used as they are, :79-80), bit 1: the same for the scale columns (:66-67)
 };
 
-constexpr float kSigmoidClamp = 9.21f;  // safe_sigmoid, model/utils/safe_ops.py:7-9
-constexpr int kMaxFix = 16;
-
-__device__ __forceinline__ float safe_sigmoid(float x)
-{
-    x = fminf(fmaxf(x, -kSigmoidClamp), kSigmoidClamp);
-    return 1.f / (1.f + expf(-x));
-}
-// d safe_sigmoid / dx given its value s (torch.clamp passes the gradient on [min, max], bounds included)
-__device__ __forceinline__ float safe_sigmoid_grad(float x, float s)
-{
-    return (x >= -kSigmoidClamp && x <= kSigmoidClamp) ? s * (1.f - s) : 0.f;
-}
+constexpr int kMaxFix = 16;  // (safe_sigmoid and its gradient: gf_math.hpp)
 
 template <bool BACKWARD>
 __global__ __launch_bounds__(128) void gf_key_points_kernel(KeyPointArgs a)

@@ -1,0 +1,172 @@
+"""The encoder's Gaussian refinement step: host mirror of ``SparseGaussian3DRefinementModule``
+(model/encoder/gaussian_encoder/refine_module.py:11-123) and ``SparseGaussian3DRefinementModuleV2``
+(refine_module_v2.py:12-108).  The MLP (``layers``) stays torch; everything after it -- the 30-40 slices, stacks, cats, clamps,
+sigmoids and logs of :72-123 / v2 :62-107 -- is ``gf_refine_forward`` / ``gf_refine_backward`` (include/gf_hip.h): one launch
+each way."""
+import ctypes
+from collections import namedtuple
+from typing import NamedTuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+from torch.autograd.function import Function, once_differentiable
+
+from . import _lib
+
+f32 = torch.float32
+_SEMANTICS = {"softmax": _lib.GF_REFINE_SEM_SOFTMAX, "softplus": _lib.GF_REFINE_SEM_SOFTPLUS}
+
+
+# the reference's result type by its field names (model/encoder/gaussian_encoder/utils.py:62-69); the last two are version 2's
+GaussianPrediction = namedtuple("GaussianPrediction", "means scales rotations opacities semantics original_means delta_means",
+                                defaults=(None, None))
+
+
+class RefineConfig(NamedTuple):
+    """What the library call needs besides the tensors: ``consts`` = pc_range (6), scale_range (2), unit (3) as doubles."""
+    version: int
+    flags: int
+    R: int
+    S: int
+    consts: tuple
+
+
+def refine_config(version, pc_range, scale_range, unit=None, restrict_xyz=False, refine_manual=(), semantic_dim=0,
+                  include_opa=True, semantics_activation="softmax", xyz_activation="sigmoid"):
+    """``unit``: version 1 = the module's ``unit_sigmoid`` (needed with ``restrict_xyz`` only), version 2 = ``unit_xyz``."""
+    refine_manual = list(refine_manual)
+    if refine_manual != list(range(len(refine_manual))):
+        raise ValueError(f"refine_manual must be the prefix 0 .. R-1 (refine_module.py:57), got {refine_manual}")
+    flags = _SEMANTICS.get(semantics_activation, 0)
+    flags |= _lib.GF_REFINE_RESTRICT_XYZ if (version == 1 and restrict_xyz) else 0
+    flags |= 0 if xyz_activation == "sigmoid" else _lib.GF_REFINE_XYZ_IDENTITY
+    flags |= _lib.GF_REFINE_OPACITY if include_opa else 0
+    unit = (0.0, 0.0, 0.0) if unit is None else unit
+    consts = tuple(float(v) for v in (*pc_range, *scale_range, *unit))
+    assert len(consts) == 11
+    return RefineConfig(version, flags, len(refine_manual) if version == 1 else 0, int(semantic_dim), consts)
+
+
+class RefineFunction(Function):
+    """``anchor_out [n, D], means [n, 3], scales [n, 3], rotations [n, 4], opacities [n, 0 | 1], semantics [n, S],
+    original_means [n, 3], delta_means [n, 3] = apply(output [n, D], anchor [n, Da], cfg)``; the last two are empty in
+    version 1.  ``output`` is the MLP's result after ``Scale``."""
+
+    @staticmethod
+    def forward(ctx, output, anchor, cfg):
+        _lib.require_gpu(output, anchor)
+        ctx.set_materialize_grads(False)   # an unused output's gradient reaches the library as NULL, not as a tensor of zeros
+        o, a = _lib.as_arg(output), _lib.as_arg(anchor)
+        n, D = o.shape
+        Da = a.shape[1]
+        opa = 1 if cfg.flags & _lib.GF_REFINE_OPACITY else 0
+
+        def new(w):
+            return torch.empty(n, w, dtype=f32, device=o.device)
+
+        three = 3 if cfg.version == 2 else 0
+        outs = (new(D), new(3), new(3), new(4), new(opa), new(cfg.S), new(three), new(three))
+        consts = (ctypes.c_double * 11)(*cfg.consts)
+        ctx.call = (n, D, Da, cfg.version, cfg.flags, cfg.R, cfg.S, consts)
+        _lib.call("gf_refine_forward", o.device, n, D, Da, cfg.version, cfg.flags, cfg.R, cfg.S,
+                  ctypes.cast(consts, ctypes.c_void_p), o, a, *outs)
+        ctx.save_for_backward(o, a)
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        o, a = ctx.saved_tensors
+        n, D, Da, version, flags, R, S, consts = ctx.call
+        g = [None if t is None or t.numel() == 0 else _lib.as_arg(t) for t in grads]   # (an empty output's carries nothing)
+        go, ga = torch.empty_like(o), torch.empty_like(a)
+        _lib.call("gf_refine_backward", o.device, n, D, Da, version, flags, R, S, ctypes.cast(consts, ctypes.c_void_p), o, a, *g, go, ga)
+        return go, ga, None
+
+
+def refine(output, anchor, cfg):
+    """Functional form on any leading batch shape: ``(anchor_out [..., D], GaussianPrediction)``."""
+    lead = output.shape[:-1]
+    outs = RefineFunction.apply(output.reshape(-1, output.shape[-1]), anchor.reshape(-1, anchor.shape[-1]), cfg)
+    outs = [t.view(*lead, t.shape[-1]) for t in outs]
+    if cfg.version == 1:
+        return outs[0], GaussianPrediction(*outs[1:6])
+    return outs[0], GaussianPrediction(*outs[1:8])
+
+
+class Scale(nn.Module):
+    """One learnable factor per column, all ones at first: the parameter ``scale [width]`` that mmcv's ``Scale`` holds when the
+    reference builds it from a list."""
+
+    def __init__(self, width):
+        super().__init__()
+        self.scale = nn.Parameter(torch.ones(width))
+
+    def forward(self, x):
+        return x * self.scale
+
+
+def refinement_mlp(embed_dims, output_dim):
+    """The modules' ``layers``, with the reference's state_dict keys: Linear at 0, 2, 5, 7 and 10, LayerNorm at 4 and 9, the
+    ``Scale`` at 11 (ReLUs between)."""
+    E = embed_dims
+    return nn.Sequential(
+        nn.Linear(E, E), nn.ReLU(inplace=True), nn.Linear(E, E), nn.ReLU(inplace=True), nn.LayerNorm(E),
+        nn.Linear(E, E), nn.ReLU(inplace=True), nn.Linear(E, E), nn.ReLU(inplace=True), nn.LayerNorm(E),
+        nn.Linear(E, output_dim), Scale(output_dim))
+
+
+class _Refinement(nn.Module):
+    """What the two drop-ins share: the torch MLP, then one library call."""
+
+    def __init__(self, version, where, embed_dims, pc_range, scale_range, unit, restrict_xyz, refine_manual, semantics,
+                 semantic_dim, include_opa, semantics_activation, xyz_activation, scale_activation):
+        super().__init__()
+        if scale_activation != "sigmoid":
+            raise NotImplementedError(
+                f"scale_activation={scale_activation!r}: the reference leaves the scale unbound for anything but 'sigmoid' "
+                f"({where}) and raises; only 'sigmoid' is supported")
+        if semantics and semantic_dim is None:
+            raise ValueError("semantics=True needs semantic_dim")
+        S = int(semantic_dim) if semantics else 0
+        self.embed_dims, self.pc_range, self.scale_range = embed_dims, pc_range, scale_range
+        self.output_dim = 10 + (1 if include_opa else 0) + S
+        self._cfg = refine_config(version, pc_range, scale_range, unit, restrict_xyz, refine_manual, S, include_opa,
+                                  semantics_activation, xyz_activation)
+        self.layers = refinement_mlp(embed_dims, self.output_dim)
+
+    def forward(self, instance_feature, anchor, anchor_embed):
+        return refine(self.layers(instance_feature + anchor_embed), anchor, self._cfg)
+
+
+class SparseGaussian3DRefinementModule(_Refinement):
+    """Same constructor keys, parameters and ``forward(instance_feature, anchor, anchor_embed) -> (anchor,
+    GaussianPrediction)`` as the reference class (refine_module.py:11-123); further config keys go to ``**kwargs`` as there."""
+
+    def __init__(self, embed_dims=256, pc_range=None, scale_range=None, restrict_xyz=False, unit_xyz=None, refine_manual=None,
+                 semantics=False, semantic_dim=None, include_opa=True, semantics_activation="softmax",
+                 xyz_activation="sigmoid", scale_activation="sigmoid", **kwargs):
+        if not isinstance(refine_manual, list):
+            raise TypeError("refine_manual must be a list (refine_module.py:55)")
+        unit = None
+        if restrict_xyz:   # the step per axis as a share of the range; the sigmoid's slope at 0 is 1/4 (refine_module.py:48-53)
+            if unit_xyz is None:
+                raise ValueError("restrict_xyz=True needs unit_xyz")
+            gain = 4 if xyz_activation == "sigmoid" else 1
+            unit = [gain * (unit_xyz[i] / (pc_range[i + 3] - pc_range[i])) for i in range(3)]
+        super().__init__(1, "refine_module.py:106-108", embed_dims, pc_range, scale_range, unit, restrict_xyz, refine_manual,
+                         semantics, semantic_dim, include_opa, semantics_activation, xyz_activation, scale_activation)
+
+
+class SparseGaussian3DRefinementModuleV2(_Refinement):
+    """The same for refine_module_v2.py:12-108; ``unit_xyz`` is a non-persistent buffer as there."""
+
+    def __init__(self, embed_dims=256, pc_range=None, scale_range=None, unit_xyz=None, semantics=False, semantic_dim=None,
+                 include_opa=True, semantics_activation="softmax", xyz_activation="sigmoid", scale_activation="sigmoid",
+                 **kwargs):
+        # the library takes the buffer's values from the host: the constructor's, rounded to the buffer's float32
+        unit = [float(np.float32(v)) for v in unit_xyz]
+        super().__init__(2, "refine_module_v2.py:88-90", embed_dims, pc_range, scale_range, unit, False, (), semantics,
+                         semantic_dim, include_opa, semantics_activation, xyz_activation, scale_activation)
+        self.register_buffer("unit_xyz", torch.tensor(unit_xyz, dtype=torch.float), persistent=False)

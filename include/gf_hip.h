@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 9   /* 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward; 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -688,6 +688,50 @@ int gf_dcn_backward(int N, int C, int H, int W, int Co, int kh, int kw, int sh, 
                     int dg, const float *input, const float *offset, const float *mask, const float *weight, const float *grad_out,
                     float *grad_input, float *grad_offset, float *grad_mask, float *grad_weight, float *grad_bias,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the encoder's Gaussian refinement step ---------------------------------------------------------------------------
+ * Replaces what SparseGaussian3DRefinementModule.forward (version 1, model/encoder/gaussian_encoder/refine_module.py:72-123)
+ * and SparseGaussian3DRefinementModuleV2.forward (version 2, refine_module_v2.py:62-107) do after their MLP, with
+ * cartesian / reverse_cartesian (utils.py:26-47) and safe_sigmoid / safe_inverse_sigmoid (model/utils/safe_ops.py): one
+ * launch instead of 30-40 torch kernels, DESIGN.md §3.12.  Per row, o = output row (the MLP's result after Scale,
+ * D = 10 + opacity + S floats), a = anchor row (Da floats), ss = safe_sigmoid, span / lo from pc_range:
+ *   version 1: with GF_REFINE_RESTRICT_XYZ o[i] = (2 ss(o[i]) - 1) unit[i], i < 3 (:72-80; unit = the module's unit_sigmoid);
+ *              o[k] += a[k] for k < R (:82-84, refine_manual = 0 .. R - 1); xyz = o[0:3], clamped to [1e-6, 1 - 1e-6] with
+ *              GF_REFINE_XYZ_IDENTITY (:86-89); means = (ss(xyz) | xyz) span + lo (:99-104)
+ *   version 2: delta_means = (2 ss(o[0:3]) - 1) unit (:65; unit = unit_xyz); original_means = cartesian(a[0:3]) (:66);
+ *              xyz = reverse_cartesian(original_means + delta_means) (:67-68: clamp to [1 - 0.9999, 0.9999], log(t / (1 - t));
+ *              with GF_REFINE_XYZ_IDENTITY the clamp [1e-6, 1 - 1e-6] alone); means = cartesian(xyz) (:86); R is ignored
+ *   both:      anchor_out = (xyz, o[3:6], normalize(o[6:10]) (eps 1e-12), o[10:]); scales = scale_lo + (scale_hi - scale_lo)
+ *              ss(o[3:6]); rotations = normalize(o[6:10]); opacities = ss(o[10]) with GF_REFINE_OPACITY (else no column);
+ *              semantics = softmax / softplus (threshold 20) / the S columns as they are.
+ * A scale_activation other than "sigmoid" is not supported: both reference modules leave the scale unbound there (:106-108,
+ * v2 :88-90) and raise.
+ *   consts     11 doubles, HOST pointer: pc_range[6], scale_lo, scale_hi, unit[3] (differences are taken in double and
+ *              rounded once, as the reference's Python floats are)
+ *   output     f32 [n, D]      anchor f32 [n, Da]      anchor_out f32 [n, D]
+ *   means, scales f32 [n, 3]; rotations f32 [n, 4]; opacities f32 [n, 0 | 1]; semantics f32 [n, S];
+ *   original_means, delta_means f32 [n, 3] (version 2; ignored in version 1)
+ * GF_EINVAL before any HIP call: S > 32, D != 10 + opacity + S, Da smaller than the anchor columns read (R; 3 in version 2),
+ * unknown version or flags.  fp32 in the reference's operation order; no atomics, bitwise reproducible; no host
+ * synchronisation, no workspace: graph-capturable. */
+#define GF_REFINE_RESTRICT_XYZ 1   /* version 1: restrict_xyz */
+#define GF_REFINE_XYZ_IDENTITY 2   /* xyz_activation is not "sigmoid" */
+#define GF_REFINE_OPACITY 4        /* include_opa */
+#define GF_REFINE_SEM_SOFTMAX 8    /* semantics_activation "softmax" */
+#define GF_REFINE_SEM_SOFTPLUS 16  /* ... "softplus"; neither: the columns as they are */
+int gf_refine_forward(int n, int D, int Da, int version, int flags, int R, int S, const double *consts, const float *output,
+                      const float *anchor, float *anchor_out, float *means, float *scales, float *rotations, float *opacities,
+                      float *semantics, float *original_means, float *delta_means, void *stream);
+
+/* Its gradient, exactly torch autograd's of that composition (a clamp passes the gradient on [min, max], bounds included).
+ * The forward's values are recomputed from (output, anchor): no forward result is needed.  Each grad_* of a forward output
+ * may be NULL (= zero).  Every element of grad_output [n, D] and grad_anchor [n, Da] is written; grad_anchor is zero beyond
+ * the first R (version 1) or 3 (version 2) columns. */
+int gf_refine_backward(int n, int D, int Da, int version, int flags, int R, int S, const double *consts, const float *output,
+                       const float *anchor, const float *grad_anchor_out, const float *grad_means, const float *grad_scales,
+                       const float *grad_rotations, const float *grad_opacities, const float *grad_semantics,
+                       const float *grad_original_means, const float *grad_delta_means, float *grad_output, float *grad_anchor,
+                       void *stream);
 
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */

@@ -1,0 +1,124 @@
+"""Torch restatement of the encoder's refinement step, in the dtype of its inputs: the tail both reference modules apply to
+their MLP's output (SparseGaussian3DRefinementModule, model/encoder/gaussian_encoder/refine_module.py:72-123, ``version=1``;
+SparseGaussian3DRefinementModuleV2, refine_module_v2.py:62-107, ``version=2``) and the whole module from a state_dict.  In
+float64 it is the truth the GPU tests measure against, in float32 the comparator (what a user runs today) and what
+tools/bench_refine.py times.  Not a test module."""
+import torch
+import torch.nn.functional as F
+
+NAMES = ("anchor_out", "means", "scales", "rotations", "opacities", "semantics", "original_means", "delta_means")
+
+# the settings of the three shipped config families (config/nuscenes_gs25600_solid.py, config/nuscenes_gs144000.py,
+# config/prob/nuscenes_gs*.py), at a reduced embed_dims
+_PC = [-50.0, -50.0, -5.0, 50.0, 50.0, 3.0]
+FAMILIES = {
+    "solid": dict(version=1, pc_range=_PC, scale_range=[0.08, 0.64], restrict_xyz=True, unit_xyz=[4.0, 4.0, 1.0],
+                  refine_manual=[0, 1, 2], semantics=True, semantic_dim=17, include_opa=True, semantics_activation="softplus"),
+    "gs144000": dict(version=1, pc_range=_PC, scale_range=[0.08, 0.32], restrict_xyz=True, unit_xyz=[2.0, 2.0, 0.5],
+                     refine_manual=[0, 1, 2], semantics=True, semantic_dim=18, include_opa=False,
+                     semantics_activation="identity"),
+    "prob": dict(version=2, pc_range=_PC, scale_range=[0.01, 3.2], unit_xyz=[4.0, 4.0, 1.0], semantics=True, semantic_dim=17,
+                 include_opa=True, semantics_activation="identity"),
+}
+
+
+def safe_sigmoid(x):
+    return torch.sigmoid(torch.clamp(x, -9.21, 9.21))
+
+
+def _cartesian(x, pc_range, use_sigmoid):
+    x = safe_sigmoid(x) if use_sigmoid else x.clamp(min=1e-6, max=1 - 1e-6)
+    return torch.stack([x[..., i] * (pc_range[3 + i] - pc_range[i]) + pc_range[i] for i in range(3)], dim=-1)
+
+
+def _reverse_cartesian(xyz, pc_range, use_sigmoid):
+    u = torch.stack([(xyz[..., i] - pc_range[i]) / (pc_range[3 + i] - pc_range[i]) for i in range(3)], dim=-1)
+    if use_sigmoid:
+        t = torch.clamp(u, 1 - 0.9999, 0.9999)
+        return torch.log(t / (1 - t))
+    return u.clamp(min=1e-6, max=1 - 1e-6)
+
+
+def unit_of(cfg):
+    """The per-axis step the tail multiplies by: version 1's ``unit_sigmoid`` (Python floats, None without restrict_xyz),
+    version 2's ``unit_xyz`` as its float32 buffer holds it."""
+    if cfg["version"] == 2:
+        return [float(torch.tensor(v, dtype=torch.float32)) for v in cfg["unit_xyz"]]
+    if not cfg.get("restrict_xyz", False):
+        return None
+    pc = cfg["pc_range"]
+    unit = [cfg["unit_xyz"][i] / (pc[i + 3] - pc[i]) for i in range(3)]
+    return [4 * v for v in unit] if cfg.get("xyz_activation", "sigmoid") == "sigmoid" else unit
+
+
+def refine_tail(output, anchor, cfg, unit_xyz=None):
+    """dict of NAMES (the last two only in version 2) from the MLP's ``output [..., D]`` and ``anchor [..., Da]``.
+    ``unit_xyz``: version 2's buffer as a tensor of the inputs' dtype and device (the module holds one; made here when absent,
+    which a graph capture does not allow)."""
+    pc, sr = cfg["pc_range"], cfg["scale_range"]
+    sig = cfg.get("xyz_activation", "sigmoid") == "sigmoid"
+    opa = int(cfg.get("include_opa", True))
+    S = cfg["semantic_dim"] if cfg.get("semantics", False) else 0
+    unit = unit_of(cfg)
+    extra = {}
+    if cfg["version"] == 1:
+        if cfg.get("restrict_xyz", False):
+            prob = 2 * safe_sigmoid(output[..., :3]) - 1
+            output = torch.cat([torch.stack([prob[..., i] * unit[i] for i in range(3)], dim=-1), output[..., 3:]], dim=-1)
+        R = len(cfg["refine_manual"])
+        if R:
+            output = torch.cat([output[..., :R] + anchor[..., :R], output[..., R:]], dim=-1)
+        xyz = output[..., :3] if sig else output[..., :3].clamp(min=1e-6, max=1 - 1e-6)
+        act = safe_sigmoid(xyz) if sig else xyz
+        means = torch.stack([act[..., i] * (pc[3 + i] - pc[i]) + pc[i] for i in range(3)], dim=-1)
+    else:
+        if unit_xyz is None:
+            unit_xyz = torch.tensor(unit, dtype=output.dtype, device=output.device)
+        delta = (2 * safe_sigmoid(output[..., :3]) - 1.) * unit_xyz
+        original = _cartesian(anchor[..., :3], pc, sig)
+        xyz = _reverse_cartesian(original + delta, pc, sig)
+        means = _cartesian(xyz, pc, sig)
+        extra = dict(original_means=original, delta_means=delta)
+    scale = output[..., 3:6]
+    rot = F.normalize(output[..., 6:10], dim=-1)
+    anchor_out = torch.cat([xyz, scale, rot, output[..., 10:]], dim=-1)
+    scales = sr[0] + (sr[1] - sr[0]) * safe_sigmoid(scale)
+    sem = output[..., 10 + opa:10 + opa + S]
+    act_name = cfg.get("semantics_activation", "softmax")
+    if act_name == "softmax":
+        sem = sem.softmax(dim=-1)
+    elif act_name == "softplus":
+        sem = F.softplus(sem)
+    return dict(anchor_out=anchor_out, means=means, scales=scales, rotations=rot,
+                opacities=safe_sigmoid(output[..., 10:10 + opa]), semantics=sem, **extra)
+
+
+def mlp(state, x):
+    """The modules' ``layers``: two rounds of (Linear, ReLU, Linear, ReLU, LayerNorm), a Linear and mmcv's Scale, from a
+    state_dict with the reference's keys."""
+    for first in (0, 5):
+        for k in (first, first + 2):
+            x = F.relu(F.linear(x, state[f"layers.{k}.weight"], state[f"layers.{k}.bias"]))
+        ln = first + 4
+        x = F.layer_norm(x, x.shape[-1:], state[f"layers.{ln}.weight"], state[f"layers.{ln}.bias"])
+    return F.linear(x, state["layers.10.weight"], state["layers.10.bias"]) * state["layers.11.scale"]
+
+
+def refine_module(state, instance_feature, anchor, anchor_embed, cfg):
+    return refine_tail(mlp(state, instance_feature + anchor_embed), anchor, cfg)
+
+
+def fixed_weights(outs):
+    """The fixed weights of the fixture's scalar: per output, cos(0.37 i + k) over its elements i in memory order, k its
+    place in NAMES -- order-one values of both signs, exactly reproducible (computed in float64, rounded to the output's dtype)."""
+    w = {}
+    for k, name in enumerate(NAMES):
+        if name in outs:
+            t = outs[name]
+            w[name] = torch.cos(torch.arange(t.numel(), dtype=torch.float64) * 0.37 + k).reshape(t.shape).to(t.dtype).to(t.device)
+    return w
+
+
+def weighted_sum(outs, weights):
+    """The one scalar every gradient comes from: sum over the outputs of (output * its weight)."""
+    return sum((outs[k] * weights[k]).sum() for k in NAMES if k in outs and outs[k].numel())
