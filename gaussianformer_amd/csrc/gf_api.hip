@@ -76,6 +76,17 @@ extern "C" int gf_profile_read(float *ms_out, int capacity)
 }
 
 namespace gf {
+int cu_count()
+{
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus = n;
+    }
+    return cus;
+}
+
 static std::atomic<int> g_options[kOptCount];
 int option(int which) { return which >= 0 && which < kOptCount ? g_options[which].load(std::memory_order_relaxed) : 0; }
 static const struct { const char *name; int which; } kOptionNames[] = {

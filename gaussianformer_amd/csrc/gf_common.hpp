@@ -1,5 +1,5 @@
 // gf_common.hpp -- what is about the library and the splat workspace: options, constants, record layout, workspace carve-up,
-// error macros (gfx950 only).  The kernels' shared device helpers are in gf_wave.hpp and gf_math.hpp, included here.
+// error macros, a splat call's inputs and grid arithmetic on the host (gfx950 only).  The kernels' shared device helpers are in gf_wave.hpp and gf_math.hpp, included here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -170,43 +170,79 @@ __device__ __forceinline__ void prob_det_kdet(float c0, float c1, float c2, floa
     }
 }
 
-// ---- shared between splat_fwd.hip and splat_bwd_mfma.hip ----
+// ---- error reporting ----------------------------------------------------------------
+void set_error(const char *fmt, ...);
+bool profile_slot(hipEvent_t *before, hipEvent_t *after);  // gf_api.hip
+
+// (the _AS forms report under the name of the entry point that was called, where the check sits in a function it shares)
+#define GF_CHECK_ARG_AS(fn, cond, msg)         \
+    do {                                       \
+        if (!(cond)) {                         \
+            gf::set_error("%s: %s", fn, msg);  \
+            return GF_EINVAL;                  \
+        }                                      \
+    } while (0)
+#define GF_CHECK_ARG(cond, msg) GF_CHECK_ARG_AS(__func__, cond, msg)
+
+#define GF_CHECK_LAUNCH_AS(fn)                                                 \
+    do {                                                                       \
+        hipError_t e_ = hipGetLastError();                                     \
+        if (e_ != hipSuccess) {                                                \
+            gf::set_error("%s: HIP launch failed: %s", fn, hipGetErrorString(e_)); \
+            return GF_ELAUNCH;                                                 \
+        }                                                                      \
+    } while (0)
+#define GF_CHECK_LAUNCH() GF_CHECK_LAUNCH_AS(__func__)
+
+// ---- a splat call on the host (splat_fwd.hip, splat_bwd.hip, splat_bwd_mfma.hip): its sizes and inputs, filled once by the C entry point
+struct SplatInputs {
+    int per_axis, P, N, H, W, D;
+    const float *pts, *means3D, *opacity, *semantics, *cov3D;
+    const int *points_int, *means3D_int, *radii;
+};
+// The backward's gradient of the logits and the four gradients it writes.
+struct SplatGrads {
+    const float *out_grad;
+    float *means_grad, *opa_grad, *sem_grad, *cov_grad;
+};
+
+// The argument checks the forward and the backward share, reported under the entry point's name `fn`.
+inline int check_splat_shape(const char *fn, int variant, int C, const SplatInputs &in)
+{
+    GF_CHECK_ARG_AS(fn, variant == GF_SPLAT_BASE || variant == GF_SPLAT_PROB, "unknown variant");
+    GF_CHECK_ARG_AS(fn, C == kC, "only 18 semantic channels are supported (NUM_CHANNELS)");
+    GF_CHECK_ARG_AS(fn, in.P >= 0 && in.N >= 0, "negative size");
+    GF_CHECK_ARG_AS(fn, in.H > 0 && in.W > 0 && in.D > 0 && in.H <= 2047 && in.W <= 2047 && in.D <= 1023, "grid size out of range");
+    GF_CHECK_ARG_AS(fn, (long long)in.H * in.W * in.D < (1ll << 31), "grid too large");
+    return GF_OK;
+}
+
+int cu_count();   // gf_api.hip: compute units of the device current at the first call (cached); 256 if the query fails
+// workgroups for `items` work items dealt to the eight XCDs, `per_cu` resident per CU: a multiple of 8, at most one per item slot
+inline int xcd_grid(int items, int per_cu)
+{
+    const int per_xcd = (items + 7) / 8, resident = per_cu * cu_count() / 8, slots = resident > 1 ? resident : 1;
+    return 8 * (per_xcd < slots ? per_xcd : slots);
+}
+// units (double bricks of 4 x 4 x 8 voxels) of the wave-autonomous kernels, forward and backward, for a grid
+inline int splat_units(int nsuper, int D) { return nsuper * 4 * ((D + 7) / 8); }
+// ... and the workgroups (= waves) that claim them: eight per CU (one 20 KB LDS block and 256 VGPRs each).  The forward's wave kernel and
+// the backward's gradient kernel both launch with it, and the forward's records pass arms the backward's per-XCD unit counters with an
+// eighth of it (PrepArgs::bwd_counter_init)
+inline int splat_unit_grid(int nunits) { return xcd_grid(nunits, 8); }
+// ceil(2^32 / d): the launch constants the wave kernels decode a unit with (m_ps: d = units per supertile, m_nsy: d = nsy)
+inline uint32_t ceil_recip32(int d) { return (uint32_t)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
+
 // The records pass of the forward (gf_splat_prep_kernel: records, packed boxes, supertile bitmask) run for the matrix-core
 // backward: no point scans, no range verdicts, natural-log covariance; additionally every Gaussian is given its rows of
 // the partial-gradient buffer (record dword 31; splat_bwd_mfma.hip).  Launches one kernel on `stream`.
-void launch_prep_for_backward(int radii_per_axis, int P, int N, int H, int W, int D, const float *pts, const int *points_int,
-                              const float *means3D, const int *means3D_int, const float *opacity, const float *semantics,
-                              const int *radii, const float *cov3D, const uint32_t *state, const SplatWorkspace &ws, hipStream_t stream);
+void launch_prep_for_backward(const SplatInputs &in, const uint32_t *state, const SplatWorkspace &ws, hipStream_t stream);
 
 // The matrix-core backward of the base variant (splat_bwd_mfma.hip): [records pass ->] set-up -> gradient kernel -> row sums.
 // records_asserted: 1 = no records pass; every kernel checks the workspace's generation against the state block's instead.
 // gate: 0 = unconditional; 1 = stands down unless the forward's state block says a matrix-core body rendered the call;
 // 2 = writes NaN gradients in that case.
-void launch_splat_backward_mfma(int radii_per_axis, int P, int N, int H, int W, int D, const float *pts, const int *points_int,
-                                const float *means3D, const int *means3D_int, const float *opacity, const float *semantics,
-                                const int *radii, const float *cov3D, const float *out_grad, float *means_grad,
-                                float *opa_grad, float *sem_grad, float *cov_grad, const uint32_t *state,
-                                const SplatWorkspace &ws, int gate, int records_asserted, hipStream_t stream);
-
-// ---- error reporting ----------------------------------------------------------------
-void set_error(const char *fmt, ...);
-bool profile_slot(hipEvent_t *before, hipEvent_t *after);  // gf_api.hip
-
-#define GF_CHECK_ARG(cond, msg)                \
-    do {                                       \
-        if (!(cond)) {                         \
-            gf::set_error("%s: %s", __func__, msg); \
-            return GF_EINVAL;                  \
-        }                                      \
-    } while (0)
-
-#define GF_CHECK_LAUNCH()                                                      \
-    do {                                                                       \
-        hipError_t e_ = hipGetLastError();                                     \
-        if (e_ != hipSuccess) {                                                \
-            gf::set_error("%s: HIP launch failed: %s", __func__, hipGetErrorString(e_)); \
-            return GF_ELAUNCH;                                                 \
-        }                                                                      \
-    } while (0)
+void launch_splat_backward_mfma(const SplatInputs &in, const SplatGrads &g, const uint32_t *state, const SplatWorkspace &ws, int gate,
+                                int records_asserted, hipStream_t stream);
 
 }  // namespace gf

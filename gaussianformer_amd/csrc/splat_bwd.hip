@@ -659,11 +659,8 @@ extern "C" int gf_splat_backward(int variant, int radii_per_axis, int flags, int
     using namespace gf;
     (void)density;
     hipStream_t stream = (hipStream_t)stream_;
-    GF_CHECK_ARG(variant == GF_SPLAT_BASE || variant == GF_SPLAT_PROB, "unknown variant");
-    GF_CHECK_ARG(C == kC, "only 18 semantic channels are supported (NUM_CHANNELS)");
-    GF_CHECK_ARG(P >= 0 && N >= 0, "negative size");
-    GF_CHECK_ARG(H > 0 && W > 0 && D > 0 && H <= 2047 && W <= 2047 && D <= 1023, "grid size out of range");
-    GF_CHECK_ARG((long long)H * W * D < (1ll << 31), "grid too large");
+    const SplatInputs in{radii_per_axis ? 1 : 0, P, N, H, W, D, pts, means3D, opacity, semantics, cov3D, points_int, means3D_int, radii};
+    if (int rc = check_splat_shape(__func__, variant, C, in)) return rc;
     GF_CHECK_ARG(P <= 256 * kBwdMaxBlk, "too many Gaussians for the backward block prefix");
     GF_CHECK_ARG((long long)H * W * D < (1ll << 24), "grid too large for the backward (256-Gaussian volume sums are 32-bit)");
     if (P == 0) return GF_OK;
@@ -695,7 +692,7 @@ extern "C" int gf_splat_backward(int variant, int radii_per_axis, int flags, int
     a.means_grad = means3D_grad; a.opa_grad = opacity_grad; a.sem_grad = semantics_grad; a.cov_grad = cov3D_grad;
     a.state = (const uint32_t *)state; a.voxel2pts = ws.voxel2pts; a.vols = ws.vols; a.bsum = ws.bsum;
     a.vols_in = ws.vols_in; a.order = ws.order; a.seg = ws.seg; a.sort_hist = ws.sort_hist; a.dotlg = ws.dotlg;
-    a.P = P; a.N = N; a.H = H; a.W = W; a.D = D; a.per_axis = radii_per_axis ? 1 : 0; a.nblk = (P + 255) / 256;
+    a.P = P; a.N = N; a.H = H; a.W = W; a.D = D; a.per_axis = in.per_axis; a.nblk = (P + 255) / 256;
     const long long V = (long long)H * W * D;
     a.force_general = ((long long)N != V || (flags & GF_PTS_GENERAL)) ? 1 : 0;
     a.assume_dense = (!a.force_general && (flags & GF_PTS_ASSUME_DENSE)) ? 1 : 0;
@@ -715,8 +712,7 @@ extern "C" int gf_splat_backward(int variant, int radii_per_axis, int flags, int
         // GF_RECORDS_VALID: the caller vouches that `workspace` has not been used since the forward that wrote `state` -- its
         // records, boxes and bitmask are taken as they are (checked on the device: generation word; NaN gradients if not so).
         // Without the flag the records pass is launched and stands down by itself in that case.
-        launch_splat_backward_mfma(a.per_axis, P, N, H, W, D, pts, points_int, means3D, means3D_int, opacity, semantics, radii, cov3D,
-                                   logits_grad, means3D_grad, opacity_grad, semantics_grad, cov3D_grad, a.state, ws, gate,
+        launch_splat_backward_mfma(in, SplatGrads{logits_grad, means3D_grad, opacity_grad, semantics_grad, cov3D_grad}, a.state, ws, gate,
                                    (flags & GF_RECORDS_VALID) ? 1 : 0, stream);
         if (gate == 2) {
             GF_CHECK_LAUNCH();

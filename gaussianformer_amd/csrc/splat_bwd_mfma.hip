@@ -1232,61 +1232,40 @@ __global__ __launch_bounds__(256) void gf_splat_bwd_rows_kernel(BwdRowsArgs a)
 
 namespace gf {
 
-static int bwd_mfma_grid(int nunits)
-{
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus = n;
-    }
-    const int per_xcd = (nunits + 7) / 8;
-    return 8 * std::min(per_xcd, std::max(1, 8 * cus / 8));
-}
-
 static unsigned long long *g_bwd_timeline = nullptr;
 
 // Launches the matrix-core backward (zero -> records pass -> gradient kernel -> row sums) on `stream`.
 // gate: 0 = unconditional, 1 = every kernel stands down unless the forward's state says "matrix cores" (the caller launches
 // the Gaussian-major kernels gated the other way), 2 = NaN gradients in that case (the caller asserted it).
-void launch_splat_backward_mfma(int radii_per_axis, int P, int N, int H, int W, int D, const float *pts, const int *points_int,
-                                const float *means3D, const int *means3D_int, const float *opacity, const float *semantics,
-                                const int *radii, const float *cov3D, const float *out_grad, float *means_grad,
-                                float *opa_grad, float *sem_grad, float *cov_grad, const uint32_t *state,
-                                const SplatWorkspace &ws, int gate, int records_asserted, hipStream_t stream)
+void launch_splat_backward_mfma(const SplatInputs &in, const SplatGrads &g, const uint32_t *state, const SplatWorkspace &ws, int gate,
+                                int records_asserted, hipStream_t stream)
 {
     uint32_t *gen_word = ws.flags + kGenWord;
     // The records pass and the set-up kernel, unless the caller vouches for the forward's records: both stand down by themselves
     // if the workspace still holds them (then the forward's render kernel has laid out the rows as well).
     if (!records_asserted) {
-        launch_prep_for_backward(radii_per_axis, P, N, H, W, D, pts, points_int, means3D, means3D_int, opacity, semantics, radii,
-                                 cov3D, state, ws, stream);
-        BwdSetupArgs z{means_grad, opa_grad, sem_grad, cov_grad, ws.bwd_wave_total, ws.bwd_row_local, ws.bwd_row_first, gen_word, state,
-                       ws.bwd_cap, P};
-        hipLaunchKernelGGL(gf_splat_bwd_setup_kernel, dim3(std::max((P + 255) / 256, std::min(1024, (kC * P + 255) / 256))), dim3(256), 0,
+        launch_prep_for_backward(in, state, ws, stream);
+        BwdSetupArgs z{g.means_grad, g.opa_grad, g.sem_grad, g.cov_grad, ws.bwd_wave_total, ws.bwd_row_local, ws.bwd_row_first, gen_word, state,
+                       ws.bwd_cap, in.P};
+        hipLaunchKernelGGL(gf_splat_bwd_setup_kernel, dim3(std::max((in.P + 255) / 256, std::min(1024, (kC * in.P + 255) / 256))), dim3(256), 0,
                            stream, z);
     }
-    const int nunits = ws.nsuper * 4 * ((D + 7) / 8);
-    const int grid = bwd_mfma_grid(nunits);
+    const int grid = splat_unit_grid(splat_units(ws.nsuper, in.D));   // (what the forward's records pass armed the unit counters for)
     BwdMArgs a;
-    a.pts = pts; a.records = ws.records; a.boxes = ws.boxes; a.bitmask = ws.bitmask; a.out_grad = out_grad; a.rows = ws.bwd_rows;
-    a.means_grad = means_grad; a.opa_grad = opa_grad; a.sem_grad = sem_grad; a.cov_grad = cov_grad; a.state = state;
+    a.pts = in.pts; a.records = ws.records; a.boxes = ws.boxes; a.bitmask = ws.bitmask; a.out_grad = g.out_grad; a.rows = ws.bwd_rows;
+    a.means_grad = g.means_grad; a.opa_grad = g.opa_grad; a.sem_grad = g.sem_grad; a.cov_grad = g.cov_grad; a.state = state;
     a.tile_counters = ws.flags + kBwdCounters; a.gen_word = gen_word; a.row_first = ws.bwd_row_first; a.wave_total = ws.bwd_wave_total;
     a.big_table = ws.bwd_wave_total + kBwdBigTableAt;
     a.lists = ws.bwd_lists; a.list_len = ws.bwd_list_len; a.lists_bad = ws.flags + kListsBad;
-    a.P = P; a.N = N; a.nwords = ws.nwords; a.nrow = ws.nrow; a.H = H; a.W = W; a.D = D; a.nsx = ws.nsx; a.nsy = ws.nsy;
+    a.P = in.P; a.N = in.N; a.nwords = ws.nwords; a.nrow = ws.nrow; a.H = in.H; a.W = in.W; a.D = in.D; a.nsx = ws.nsx; a.nsy = ws.nsy;
     a.gate = gate ? 1 : 0; a.records_asserted = records_asserted;
     a.timeline = g_bwd_timeline;
     a.cap = ws.bwd_cap;
-    {
-        const unsigned per_super = 4u * (unsigned)((D + 7) >> 3);
-        a.m_ps = (uint32_t)(((1ull << 32) + per_super - 1) / per_super);
-        a.m_nsy = (uint32_t)(((1ull << 32) + (unsigned)ws.nsy - 1) / (unsigned)ws.nsy);
-    }
+    a.m_ps = ceil_recip32(splat_units(1, in.D)); a.m_nsy = ceil_recip32(ws.nsy);
     if (ws.nrow > kWRow) hipLaunchKernelGGL(gf_splat_bwd_mfma_kernel<true>, dim3(grid), dim3(64), 0, stream, a);
     else hipLaunchKernelGGL(gf_splat_bwd_mfma_kernel<false>, dim3(grid), dim3(64), 0, stream, a);
-    BwdRowsArgs r{ws.records, ws.bwd_rows, means_grad, opa_grad, sem_grad, cov_grad, ws.bwd_wave_total, ws.bwd_row_first, gen_word,
-                  ws.bwd_wave_total + kBwdBigTableAt, ws.flags + kBwdCounters, state, (uint32_t)(grid / 8), P, gate, (P + 31) / 32, records_asserted};
+    BwdRowsArgs r{ws.records, ws.bwd_rows, g.means_grad, g.opa_grad, g.sem_grad, g.cov_grad, ws.bwd_wave_total, ws.bwd_row_first, gen_word,
+                  ws.bwd_wave_total + kBwdBigTableAt, ws.flags + kBwdCounters, state, (uint32_t)(grid / 8), in.P, gate, (in.P + 31) / 32, records_asserted};
     hipLaunchKernelGGL(gf_splat_bwd_rows_kernel, dim3(r.ngauss_blocks + 256), dim3(256), 0, stream, r);
 }
 

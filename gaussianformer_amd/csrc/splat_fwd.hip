@@ -25,6 +25,8 @@
 //      If the prep kernel found pts is NOT the dense grid, the same launch runs the
 //      arbitrary-points body instead (one lane per point).
 //   3. gf_splat_render_general_kernel   arbitrary query points when N != H*W*D.
+#include <string.h>
+
 #include <algorithm>
 
 #include "gf_common.hpp"
@@ -2771,19 +2773,6 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     }
 }
 
-// workgroups (= waves) of the wave-autonomous kernel: eight per CU (one 20 KB LDS block and 256 VGPRs each), a multiple of 8
-static int mfma_wave_grid(int nunits)
-{
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus = n;
-    }
-    const int per_xcd = (nunits + 7) / 8;
-    return 8 * std::min(per_xcd, std::max(1, 8 * cus / 8));
-}
-
 // ---------------------------------------------------------------------------------------
 struct BoxVolArgs {
     const int *means_int;
@@ -2810,149 +2799,216 @@ __global__ __launch_bounds__(256) void gf_box_volumes_kernel(BoxVolArgs a)
     if (lane_id() == 0 && s) atomicAdd(a.num_rendered, s);
 }
 
-// workgroups of the persistent matrix-core kernel: two per CU (252 VGPRs), a multiple of 8, at most one per tile slot
-static int mfma_grid(int ntiles_total)
+// workgroups of the persistent matrix-core tile kernel: two per CU (252 VGPRs), every slot taken.  Whole rounds -- 53 workgroups per
+// XCD for 157 tiles, so that the third round has no idle slots -- measured the same at gs25600 and 6 % slower at gs144000:
+// throughput beats round arithmetic.
+static int mfma_grid(int ntiles_total) { return xcd_grid(ntiles_total, 2); }
+
+// ---- the route of a forward call: decided once (forward_route), filled into the two argument structs and launched by
+// splat_forward_impl, reported by gf_debug_splat_route -- which copies these 32-bit words out in this order and describes each
+enum RenderKernel { kRenderExactTile = 0, kRenderArbitrary, kRenderMfmaTile, kRenderMfmaWave, kRenderMfmaWaveLong };
+// Waves per workgroup of the records pass = the length of the runs the bitmask rows are written in (a workgroup of W waves owns W
+// consecutive words of every row).  TWO, with the records loaded and stored per lane (round 5: compiling parts out of the pass showed
+// 2.7 of its 9.5 us in the 625 scattered 8-byte stores of a single-wave workgroup; 16-byte runs: 43.8 -> 41.9 us per step at P = 25 601;
+// runs of 32 bytes 42.9, of 64 bytes 44.8 -- the workgroup barriers take over); staged: four, the records through an LDS image
+constexpr int prep_waves(bool staged) { return staged ? 4 : 2; }
+constexpr int prep_blocks(int nwords, bool staged) { return (nwords + prep_waves(staged) - 1) / prep_waves(staged); }
+struct ForwardRoute {
+    int kernel, labels, prep_backward, exp;
+    int prep_waves, prep_blocks, prep_grid;
+    int verify, lattice, prescale, range_theta_here, range_flags, one_verdict, summaries, row_layout;
+    uint32_t tile_counter_init, bwd_counter_init;
+    int render_grid;
+};
+constexpr int kRouteWords = sizeof(ForwardRoute) / sizeof(int);
+
+// Pure: reads the sizes of `ws` (not its pointers), the library options and the cached CU count.
+static ForwardRoute forward_route(int variant, int flags, const int *label_mode, const SplatInputs &in, const SplatWorkspace &ws)
 {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus = n;
+    ForwardRoute r{};
+    const bool labels = label_mode != nullptr;   // (null: no label epilogue)
+    const bool dense_candidate = ((long long)in.N == (long long)in.H * in.W * in.D) && !(flags & GF_PTS_GENERAL);
+    const bool verify = dense_candidate && !(flags & GF_PTS_ASSUME_DENSE);
+    r.labels = labels; r.verify = verify;
+    // rows the wave kernel's long-row instantiation takes: kWRow < nrow, nwords <= kLongWords (the workspace then has summaries), handed
+    // over zeroed (GF_WORKSPACE_ZEROED: the one-word verdict -- the per-wave verdict words of such a row are more than a render wave can
+    // read at its start)
+    const bool long_rows = ws.sum_pitch > 0 && (flags & GF_WORKSPACE_ZEROED);
+    // which of the two matrix-core kernels would render: the wave-autonomous one wherever a bitmask row fits its LDS block or is such a
+    // long row (gf_set_option("splat.mfma_tile_kernel", 1) keeps the tile kernel, for comparison: the two are bit-identical, tested)
+    const bool wave = (ws.nrow <= kWRow || long_rows) && option(kOptSplatTileKernel) == 0;
+    // matrix-core kernel: the default wherever it applies (include/gf_hip.h, GF_MFMA_SPLAT / GF_EXACT_FP32)
+    // (the label epilogue -- argmax mode -- is built into the wave-autonomous kernel only)
+    const bool mfma = variant == GF_SPLAT_BASE && dense_candidate && in.P > 0 && (!labels || (*label_mode == GF_LABELS_ARGMAX && wave)) &&
+                      ((flags & GF_MFMA_SPLAT) || !(flags & (GF_EXACT_FP32 | GF_FAST_EXP | GF_LIBM_EXP | GF_COMP_EXP)));
+    r.kernel = !mfma ? (dense_candidate ? kRenderExactTile : kRenderArbitrary)
+               : !wave ? kRenderMfmaTile : ws.nrow > kWRow ? kRenderMfmaWaveLong : kRenderMfmaWave;
+    // exp flavour: GF_LIBM_EXP > GF_COMP_EXP > GF_FAST_EXP > the variant's default -- the prescaled v_exp_f32 for the base splat; for
+    // the prob variant the compensated natural-log form, whose quadratic form is evaluated in the reference's own order (the Prob
+    // config's form cancels ~1e3 -> ~1e0, where the prescaled coefficients are 1e-4 away from the reference's density; measured
+    // against oracle/_ref)
+    r.exp = (flags & GF_LIBM_EXP) ? kExpLibm : (flags & GF_COMP_EXP) ? kExpComp : (flags & GF_FAST_EXP) ? kExpFast
+            : variant == GF_SPLAT_PROB ? kExpComp : kExpFast;
+    // (staged for large P; long rows, round 6, as well -- the row summaries are one byte per four-wave workgroup)
+    const bool staged = in.P >= 65536 || long_rows;
+    r.prep_waves = prep_waves(staged);
+    r.prep_blocks = prep_blocks(ws.nwords, staged);
+    r.prep_grid = r.prep_blocks + (verify ? kVerifyBlocks / r.prep_waves : 0);
+    r.lattice = mfma && verify;
+    r.prescale = !mfma && r.exp == kExpFast;
+    r.range_theta_here = mfma && !verify;
+    r.range_flags = mfma;
+    r.one_verdict = mfma && wave && (flags & GF_WORKSPACE_ZEROED);
+    r.summaries = r.kernel == kRenderMfmaWaveLong;
+    // GF_PREPARE_BACKWARD: the matrix-core backward's row layout rides along (a scan per wave of 64 Gaussians in the records pass, a
+    // prefix in eight waves of the render kernel); a backward that finds the workspace untouched (generation word) then starts with its
+    // gradient kernel.  The layout is finished by workgroups 0 .. kRowLayoutBlocks - 1 of the render launch (finish_row_layout): a grid
+    // with fewer workgroups -- a few supertiles -- would leave Gaussians without their first row, so such a call prepares nothing and
+    // the backward lays its rows out itself
+    const int unit_grid = splat_unit_grid(splat_units(ws.nsuper, in.D));
+    r.row_layout = mfma && ws.bwd_cap > 0u && !labels && (flags & GF_PREPARE_BACKWARD) && unit_grid >= kRowLayoutBlocks;
+    r.prep_backward = r.row_layout && wave;
+    r.bwd_counter_init = (uint32_t)(unit_grid / 8);
+    // (the exact tile kernel's embedded arbitrary-points body grid-strides, so the tile grid is enough)
+    r.render_grid = r.kernel == kRenderExactTile  ? ((ws.nsuper + 7) / 8) * kTilesPerSuper * 8
+                    : r.kernel == kRenderArbitrary ? (int)std::min((long long)4096, ((long long)in.N + kBlock - 1) / kBlock)
+                    : r.kernel == kRenderMfmaTile  ? mfma_grid(ws.nsuper * kTilesPerSuper)
+                                                   : unit_grid;
+    r.tile_counter_init = mfma ? (uint32_t)(r.render_grid / 8) : 0u;
+    return r;
+}
+
+static void launch_render_mfma(const ForwardRoute &rt, const RenderArgs &r, hipStream_t stream)
+{
+    const dim3 grid(rt.render_grid);
+    switch (rt.kernel) {
+    case kRenderMfmaWaveLong:
+        if (rt.labels) hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<true, false, true>), grid, dim3(64), 0, stream, r);
+        else if (rt.prep_backward) hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, true, true>), grid, dim3(64), 0, stream, r);
+        else hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, false, true>), grid, dim3(64), 0, stream, r);
+        break;
+    case kRenderMfmaWave:
+        if (rt.labels) hipLaunchKernelGGL(gf_splat_render_mfma_wave_kernel<true>, grid, dim3(64), 0, stream, r);
+        else if (rt.prep_backward) hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, true>), grid, dim3(64), 0, stream, r);
+        else hipLaunchKernelGGL(gf_splat_render_mfma_wave_kernel<false>, grid, dim3(64), 0, stream, r);
+        break;
+    default:
+        hipLaunchKernelGGL(gf_splat_render_mfma_kernel<false>, grid, dim3(kBlock), 0, stream, r);
     }
-    const int per_xcd = (ntiles_total + 7) / 8;
-    // every slot taken (two workgroups per CU).  Whole rounds -- 53 workgroups per XCD for 157 tiles, so that the third round
-    // has no idle slots -- measured the same at gs25600 and 6 % slower at gs144000: throughput beats round arithmetic.
-    return 8 * std::min(per_xcd, std::max(1, 2 * cus / 8));
 }
 
-// units (double bricks) of the wave-autonomous kernel for a grid
-static int mfma_wave_units(int nsuper, int D) { return nsuper * 4 * ((D + 7) / 8); }
-
-// which of the two matrix-core kernels renders a call: the wave-autonomous one wherever a bitmask row fits its LDS block
-// (gf_set_option("splat.mfma_tile_kernel", 1) keeps the tile kernel, for comparison: the two are bit-identical, tested)
-static bool mfma_by_wave(int nrow)
+// The fields both records passes (the forward's and the matrix-core backward's) fill alike; everything else is zero / null.
+static PrepArgs fill_prep_args(const SplatInputs &in, const SplatWorkspace &ws)
 {
-    return nrow <= kWRow && option(kOptSplatTileKernel) == 0;
-}
-// ... and its long-row instantiation (round 6) for the rows that do not: kWRow < nrow, nwords <= kLongWords, on a workspace that was
-// handed over zeroed (GF_WORKSPACE_ZEROED: the one-word verdict -- the per-wave verdict words of such a row are more than a render
-// wave can read at its start); anything else stays with the tile kernel
-static bool mfma_by_wave_long(int nrow, int nwords, int flags)
-{
-    return nrow > kWRow && nwords <= kLongWords && (flags & GF_WORKSPACE_ZEROED) && option(kOptSplatTileKernel) == 0;
+    PrepArgs pa{};
+    pa.means3D = in.means3D; pa.means_int = in.means3D_int; pa.opacity = in.opacity; pa.semantics = in.semantics;
+    pa.radii = in.radii; pa.cov3D = in.cov3D; pa.points_int = in.points_int; pa.pts = in.pts; pa.records = ws.records; pa.boxes = ws.boxes;
+    pa.bitmask = ws.bitmask; pa.verify_flags = ws.flags + 64; pa.P = in.P; pa.N = in.N; pa.H = in.H; pa.W = in.W; pa.D = in.D;
+    pa.nwords = ws.nwords; pa.nrow = ws.nrow; pa.nsx = ws.nsx; pa.nsy = ws.nsy; pa.per_axis = in.per_axis;
+    pa.unit_local = ws.bwd_row_local; pa.bwd_counters = ws.flags + kBwdCounters; pa.gen_word = ws.flags + kGenWord;
+    return pa;
 }
 
-// kind of the forward's matrix-core kernel for a call: 0 tile, 1 wave (round 3).  (The round-5 pair and solo kernels, kinds 2 and 3,
-// were removed after a5ba306: DESIGN.md section 3.2c.)
-static int mfma_kind(int nrow, int P, int flags = 0)
+// The records pass: `staged` = four waves per workgroup and the records through an LDS image, else two waves and per-lane records.
+static void launch_prep(const PrepArgs &pa, bool staged, int grid, hipStream_t stream)
 {
-    return (mfma_by_wave(nrow) || mfma_by_wave_long(nrow, (P + 63) / 64, flags)) ? 1 : 0;
+    const int waves = prep_waves(staged);
+    const size_t lds = sizeof(unsigned long long) * (size_t)std::min(pa.nsx * pa.nsy * waves, kPrepSuperChunk) +
+                       (staged ? (size_t)waves * 64 * kRecDwords * sizeof(float) : 0);
+    if (staged) hipLaunchKernelGGL(gf_splat_prep_kernel<4>, dim3(grid), dim3(256), lds, stream, pa);
+    else hipLaunchKernelGGL((gf_splat_prep_kernel<2, false>), dim3(grid), dim3(128), lds, stream, pa);
 }
 
-// workgroups per XCD of the matrix-core kernel that renders a call (what the per-XCD unit counters start from)
-static uint32_t mfma_counter_init(int kind, int nsuper, int D)
+void launch_prep_for_backward(const SplatInputs &in, const uint32_t *state, const SplatWorkspace &ws, hipStream_t stream)
 {
-    return kind == 1 ? (uint32_t)(mfma_wave_grid(mfma_wave_units(nsuper, D)) / 8) : (uint32_t)(mfma_grid(nsuper * kTilesPerSuper) / 8);
-}
-
-static void launch_render_mfma(const RenderArgs &r, int nsuper, hipStream_t stream)
-{
-    hipEvent_t ev0, ev1;
-    const bool prof = profile_slot(&ev0, &ev1);
-    if (prof) (void)hipEventRecord(ev0, stream);
-    const int kind = mfma_kind(r.nrow, r.P, r.summary ? GF_WORKSPACE_ZEROED : 0);
-    const int wave_grid = mfma_wave_grid(mfma_wave_units(nsuper, r.D));
-    if (kind == 1 && r.nrow > kWRow && r.out_labels)
-        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<true, false, true>), dim3(wave_grid), dim3(64), 0, stream, r);
-    else if (kind == 1 && r.nrow > kWRow && r.rows_valid)
-        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, true, true>), dim3(wave_grid), dim3(64), 0, stream, r);
-    else if (kind == 1 && r.nrow > kWRow)
-        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, false, true>), dim3(wave_grid), dim3(64), 0, stream, r);
-    else if (kind == 1 && r.out_labels)
-        hipLaunchKernelGGL(gf_splat_render_mfma_wave_kernel<true>, dim3(wave_grid), dim3(64), 0, stream, r);
-    else if (kind == 1 && r.rows_valid)
-        hipLaunchKernelGGL((gf_splat_render_mfma_wave_kernel<false, true>), dim3(wave_grid), dim3(64), 0, stream, r);
-    else if (kind == 1)
-        hipLaunchKernelGGL(gf_splat_render_mfma_wave_kernel<false>, dim3(wave_grid), dim3(64), 0, stream, r);
-    else
-        hipLaunchKernelGGL(gf_splat_render_mfma_kernel<false>, dim3(mfma_grid(r.ntiles_total)), dim3(kBlock), 0, stream, r);
-    if (prof) (void)hipEventRecord(ev1, stream);
+    PrepArgs pa = fill_prep_args(in, ws);   // (tile counters stay null: the backward's set-up kernel arms the unit counters)
+    const bool staged = in.P >= 65536;   // by P alone: this pass writes no row summaries, the forward's reason to stage long rows below that
+    pa.variant = GF_SPLAT_BASE; pa.nprep_blocks = prep_blocks(ws.nwords, staged);
+    pa.unit_totals = ws.bwd_wave_total; pa.gate_state = state;
+    pa.bwd_counter_init = (uint32_t)(splat_unit_grid(splat_units(ws.nsuper, in.D)) / 8);   // the grid launch_splat_backward_mfma launches with
+    launch_prep(pa, staged, pa.nprep_blocks, stream);
 }
 
 template <int VARIANT, int EXP, bool LABELS>
-static void launch_render(bool dense_candidate, const RenderArgs &r, hipStream_t stream)
+static void launch_render_exact(const ForwardRoute &rt, const RenderArgs &r, hipStream_t stream)
 {
-    if (dense_candidate) {
-        const int per_xcd = ((r.nsx * r.nsy + 7) / 8) * kTilesPerSuper;
-        // the embedded arbitrary-points body grid-strides, so the tile grid is enough
-        hipEvent_t ev0, ev1;
-        const bool prof = profile_slot(&ev0, &ev1);
-        if (prof) (void)hipEventRecord(ev0, stream);
-        hipLaunchKernelGGL((gf_splat_render_kernel<VARIANT, EXP, LABELS>), dim3(per_xcd * 8), dim3(kBlock), 0, stream, r);
-        if (prof) (void)hipEventRecord(ev1, stream);
-    } else {
-        const int blocks = (int)min((long long)4096, ((long long)r.N + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL((gf_splat_render_general_kernel<VARIANT, EXP, LABELS>), dim3(blocks), dim3(kBlock), 0, stream, r);
+    if (rt.kernel == kRenderExactTile)
+        hipLaunchKernelGGL((gf_splat_render_kernel<VARIANT, EXP, LABELS>), dim3(rt.render_grid), dim3(kBlock), 0, stream, r);
+    else
+        hipLaunchKernelGGL((gf_splat_render_general_kernel<VARIANT, EXP, LABELS>), dim3(rt.render_grid), dim3(kBlock), 0, stream, r);
+}
+
+template <int VARIANT, bool LABELS>
+static void launch_render_exact(const ForwardRoute &rt, const RenderArgs &r, hipStream_t stream)
+{
+    if (rt.exp == kExpLibm) launch_render_exact<VARIANT, kExpLibm, LABELS>(rt, r, stream);
+    else if (rt.exp == kExpComp) launch_render_exact<VARIANT, kExpComp, LABELS>(rt, r, stream);
+    else launch_render_exact<VARIANT, kExpFast, LABELS>(rt, r, stream);
+}
+
+// What a forward writes: the four outputs, the optional label epilogue and the state block.
+struct ForwardOutputs {
+    float *logits, *bin_logits, *density, *probability;
+    long long *labels;  // null: plain forward
+    int label_mode, empty_label;
+    float threshold;
+    void *state;
+};
+
+// The forward's checks on variant, flags and label mode (null: no label epilogue), reported under the entry point's name `fn`.
+static int check_forward_modes(const char *fn, int variant, int flags, const int *label_mode)
+{
+    if (label_mode) {
+        GF_CHECK_ARG_AS(fn, *label_mode == GF_LABELS_ARGMAX || *label_mode == GF_LABELS_PROB_THRESHOLD || *label_mode == GF_LABELS_PROB_GEOSEM,
+                        "unknown label mode");
+        GF_CHECK_ARG_AS(fn, *label_mode == GF_LABELS_ARGMAX || variant == GF_SPLAT_PROB, "the prob label modes need the prob variant");
     }
+    GF_CHECK_ARG_AS(fn, !(flags & GF_PROB_NUMERATOR) || (variant == GF_SPLAT_PROB && !label_mode),
+                    "GF_PROB_NUMERATOR is a prob-variant flag and excludes the label epilogue");
+    return GF_OK;
 }
 
-// exp flavour of a call: GF_LIBM_EXP > GF_COMP_EXP > GF_FAST_EXP > the variant's default -- the prescaled
-// v_exp_f32 for the base splat; for the prob variant the compensated natural-log form, whose quadratic form is
-// evaluated in the reference's own order (the Prob config's form cancels ~1e3 -> ~1e0, where the prescaled
-// coefficients are 1e-4 away from the reference's density; measured against oracle/_ref)
-static int exp_flavour(int variant, int flags)
-{
-    if (flags & GF_LIBM_EXP) return kExpLibm;
-    if (flags & GF_COMP_EXP) return kExpComp;
-    if (flags & GF_FAST_EXP) return kExpFast;
-    return variant == GF_SPLAT_PROB ? kExpComp : kExpFast;
-}
-
-template <int VARIANT>
-static void launch_render_exp(int flags, bool dense_candidate, const RenderArgs &r, hipStream_t stream)
-{
-    const int ex = exp_flavour(VARIANT, flags);
-    if (r.out_labels) {
-        if (ex == kExpLibm) launch_render<VARIANT, kExpLibm, true>(dense_candidate, r, stream);
-        else if (ex == kExpComp) launch_render<VARIANT, kExpComp, true>(dense_candidate, r, stream);
-        else launch_render<VARIANT, kExpFast, true>(dense_candidate, r, stream);
-        return;
-    }
-    if (ex == kExpLibm) launch_render<VARIANT, kExpLibm, false>(dense_candidate, r, stream);
-    else if (ex == kExpComp) launch_render<VARIANT, kExpComp, false>(dense_candidate, r, stream);
-    else launch_render<VARIANT, kExpFast, false>(dense_candidate, r, stream);
-}
-
-void launch_prep_for_backward(int radii_per_axis, int P, int N, int H, int W, int D, const float *pts, const int *points_int,
-                              const float *means3D, const int *means3D_int, const float *opacity, const float *semantics,
-                              const int *radii, const float *cov3D, const uint32_t *state, const SplatWorkspace &ws, hipStream_t stream)
-{
-    PrepArgs pa;
-    pa.means3D = means3D; pa.means_int = means3D_int; pa.opacity = opacity; pa.semantics = semantics;
-    pa.radii = radii; pa.cov3D = cov3D; pa.points_int = points_int; pa.pts = pts; pa.records = ws.records; pa.boxes = ws.boxes;
-    pa.bitmask = ws.bitmask; pa.verify_flags = ws.flags + 64; pa.P = P; pa.N = N; pa.H = H; pa.W = W; pa.D = D;
-    pa.nwords = ws.nwords; pa.nrow = ws.nrow; pa.nsx = ws.nsx; pa.nsy = ws.nsy; pa.per_axis = radii_per_axis ? 1 : 0;
-    const int prep_waves = P >= 65536 ? 4 : 2;   // (as in the forward)
-    pa.variant = GF_SPLAT_BASE; pa.nprep_blocks = (ws.nwords + prep_waves - 1) / prep_waves; pa.verify = 0;
-    pa.prescale = 0; pa.exact_det = 0; pa.lattice = 0;
-    pa.tile_counters = nullptr; pa.tile_counter_init = 0u;   // (the backward's set-up kernel arms the unit counters)
-    pa.range_flags = nullptr; pa.range_theta_here = 0; pa.verdict_words = nullptr;
-    pa.summary = nullptr; pa.sum_pitch = 0;
-    pa.unit_totals = ws.bwd_wave_total; pa.unit_local = ws.bwd_row_local; pa.bwd_counters = ws.flags + kBwdCounters;
-    pa.bwd_counter_init = (uint32_t)(mfma_wave_grid(mfma_wave_units(ws.nsuper, D)) / 8);
-    pa.gen_word = ws.flags + kGenWord; pa.gate_state = state;
-    const size_t prep_lds = sizeof(unsigned long long) * (size_t)std::min(ws.nsx * ws.nsy * prep_waves, kPrepSuperChunk) +
-                            (P >= 65536 ? (size_t)prep_waves * 64 * kRecDwords * sizeof(float) : 0);
-    if (P >= 65536) hipLaunchKernelGGL(gf_splat_prep_kernel<4>, dim3(pa.nprep_blocks), dim3(256), prep_lds, stream, pa);
-    else hipLaunchKernelGGL((gf_splat_prep_kernel<2, false>), dim3(pa.nprep_blocks), dim3(128), prep_lds, stream, pa);
-}
+static unsigned long long *g_timeline = nullptr; static const int *g_tile_perm = nullptr;
 
 }  // namespace gf
 
-namespace gf { static unsigned long long *g_timeline = nullptr; static const int *g_tile_perm = nullptr; }
-// debug hook (not in the public header): per-workgroup timestamps of the render kernel
+// debug hooks (not in the public header): per-workgroup timestamps of the render kernel, a workgroup -> tile permutation
 extern "C" void gf_debug_set_timeline(void *dev_ptr) { gf::g_timeline = (unsigned long long *)dev_ptr; }
 extern "C" void gf_debug_set_tile_perm(const void *dev_ptr) { gf::g_tile_perm = (const int *)dev_ptr; }
+
+// ... and the route gf_splat_forward (label_mode -1) or gf_splat_forward_labels (label_mode GF_LABELS_*) takes for these sizes, flags
+// and the library options in force.  Launches nothing and needs no GPU (without one the CU count is the fall-back, 256).  Writes up to
+// `nwords` ints to `route`, gf::ForwardRoute's fields in order:
+//    0 kernel            0 exact-fp32 tile, 1 arbitrary points, 2 matrix-core tile, 3 wave, 4 wave long-row
+//    1 labels            the render kernel's label epilogue
+//    2 prep_backward     the wave kernel's instantiation that finishes the backward's row layout
+//    3 exp               flavour of the two exact-fp32 kernels: 0 libm, 1 compensated, 2 fast
+//    4 prep_waves, 5 prep_blocks, 6 prep_grid   records pass: waves per workgroup (4: the records through an LDS image), workgroups
+//                        that write records, and the grid with the point scans' workgroups (0: no launch)
+//    7 verify            the point scans run (dense candidate without GF_PTS_ASSUME_DENSE)
+//    8 lattice           ... and check the exact lattice the matrix cores need
+//    9 prescale          records with the quadratic form times log2(e) (the matrix-core kernels scale in fp64 themselves)
+//   10 range_theta_here  the records pass checks theta (with the point scans running, their waves take that verdict)
+//   11 range_flags       a matrix-core kernel renders: range verdicts and tile counters in both launches
+//   12 one_verdict       one verdict word instead of one per records-pass wave (wave kernels, GF_WORKSPACE_ZEROED)
+//   13 summaries         the records pass writes the row summaries the long-row instantiation reads
+//   14 row_layout        the records pass lays out the matrix-core backward's rows (GF_PREPARE_BACKWARD)
+//   15 tile_counter_init, 16 bwd_counter_init   what the per-XCD unit counters start from, the workgroups per XCD: the render kernel's,
+//                        and the backward's gradient kernel's = splat_unit_grid / 8, the grid that kernel is launched with
+//   17 render_grid       workgroups of the render launch
+// Returns the number of route words, or GF_EINVAL for sizes, flags or a label mode the forward refuses.
+extern "C" int gf_debug_splat_route(int variant, int flags, int label_mode, int P, int N, int H, int W, int D, int *route, int nwords)
+{
+    using namespace gf;
+    GF_CHECK_ARG(route != nullptr, "null route");
+    const SplatInputs in{0, P, N, H, W, D};
+    if (int rc = check_splat_shape(__func__, variant, kC, in)) return rc;
+    const int *mode = label_mode == -1 ? nullptr : &label_mode;
+    if (int rc = check_forward_modes(__func__, variant, flags, mode)) return rc;
+    const ForwardRoute r = forward_route(variant, flags, mode, in, carve_workspace(nullptr, P, N, H, W, D));
+    memcpy(route, &r, sizeof(int) * (size_t)std::max(0, std::min(nwords, kRouteWords)));
+    return kRouteWords;
+}
 
 extern "C" size_t gf_splat_workspace_bytes(int P, int N, int H, int W, int D)
 {
@@ -2962,137 +3018,71 @@ extern "C" size_t gf_splat_workspace_bytes(int P, int N, int H, int W, int D)
 
 extern "C" size_t gf_splat_state_bytes(void) { return 256; }
 
-namespace gf {
-struct LabelOpts {
-    long long *labels;  // null: plain forward
-    int mode, empty_label;
-    float threshold;
-};
-}  // namespace gf
-
-static int splat_forward_impl(const char *fn, int variant, int radii_per_axis, int flags, int P, int N, int C, int H,
-                              int W, int D, const float *pts, const int *points_int,
-                              const float *means3D, const int *means3D_int, const float *opacity,
-                              const float *semantics, const int *radii, const float *cov3D,
-                              float *out_logits, float *out_bin_logits, float *out_density,
-                              float *out_probability, const gf::LabelOpts &lab, void *state, void *workspace,
-                              size_t workspace_bytes, void *stream_)
+static int splat_forward_impl(const char *fn, int variant, int flags, int C, const gf::SplatInputs &in, const gf::ForwardOutputs &out,
+                              void *workspace, size_t workspace_bytes, void *stream_)
 {
     using namespace gf;
-    (void)fn;
     hipStream_t stream = (hipStream_t)stream_;
-    GF_CHECK_ARG(variant == GF_SPLAT_BASE || variant == GF_SPLAT_PROB, "unknown variant");
-    GF_CHECK_ARG(C == kC, "only 18 semantic channels are supported (NUM_CHANNELS)");
-    GF_CHECK_ARG(P >= 0 && N >= 0, "negative size");
-    GF_CHECK_ARG(H > 0 && W > 0 && D > 0 && H <= 2047 && W <= 2047 && D <= 1023, "grid size out of range");
-    GF_CHECK_ARG((long long)H * W * D < (1ll << 31), "grid too large");
-    GF_CHECK_ARG(N == 0 || (pts && points_int && (out_logits || lab.labels)), "null point/output pointer");
-    GF_CHECK_ARG(P == 0 || (means3D && means3D_int && opacity && semantics && radii && cov3D), "null Gaussian pointer");
-    GF_CHECK_ARG(variant == GF_SPLAT_BASE || N == 0 || (out_bin_logits && out_density && out_probability) ||
-                     (lab.labels && !out_logits && !out_bin_logits && !out_density && !out_probability),
-                 "prob variant needs bin_logits/density/probability outputs (all three, or none in labels-only mode)");
-    if (lab.labels) {
-        GF_CHECK_ARG(lab.mode == GF_LABELS_ARGMAX || lab.mode == GF_LABELS_PROB_THRESHOLD || lab.mode == GF_LABELS_PROB_GEOSEM,
-                     "unknown label mode");
-        GF_CHECK_ARG(lab.mode == GF_LABELS_ARGMAX || variant == GF_SPLAT_PROB, "the prob label modes need the prob variant");
-    }
-    GF_CHECK_ARG(!(flags & GF_PROB_NUMERATOR) || (variant == GF_SPLAT_PROB && !lab.labels),
-                 "GF_PROB_NUMERATOR is a prob-variant flag and excludes the label epilogue");
-    GF_CHECK_ARG(workspace != nullptr, "null workspace");
-    SplatWorkspace ws = carve_workspace(workspace, P, N, H, W, D);
+    const int *label_mode = out.labels ? &out.label_mode : nullptr;   // (whatever the caller's mode: checked below)
+    if (int rc = check_splat_shape(fn, variant, C, in)) return rc;
+    GF_CHECK_ARG_AS(fn, in.N == 0 || (in.pts && in.points_int && (out.logits || out.labels)), "null point/output pointer");
+    GF_CHECK_ARG_AS(fn, in.P == 0 || (in.means3D && in.means3D_int && in.opacity && in.semantics && in.radii && in.cov3D),
+                    "null Gaussian pointer");
+    GF_CHECK_ARG_AS(fn, variant == GF_SPLAT_BASE || in.N == 0 || (out.bin_logits && out.density && out.probability) ||
+                            (out.labels && !out.logits && !out.bin_logits && !out.density && !out.probability),
+                    "prob variant needs bin_logits/density/probability outputs (all three, or none in labels-only mode)");
+    if (int rc = check_forward_modes(fn, variant, flags, label_mode)) return rc;
+    GF_CHECK_ARG_AS(fn, workspace != nullptr, "null workspace");
+    const SplatWorkspace ws = carve_workspace(workspace, in.P, in.N, in.H, in.W, in.D);
     if (workspace_bytes < ws.total_bytes) {
-        set_error("gf_splat_forward: workspace too small (%zu < %zu)", workspace_bytes, ws.total_bytes);
+        set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, ws.total_bytes);
         return GF_EWORKSPACE;
     }
-    const bool dense_candidate = ((long long)N == (long long)H * W * D) && !(flags & GF_PTS_GENERAL);
-    const bool verify = dense_candidate && !(flags & GF_PTS_ASSUME_DENSE);
+    const ForwardRoute rt = forward_route(variant, flags, label_mode, in, ws);
+    uint32_t *const tile_counters = ws.flags + 4608;  // [64 x], x < 8: inside the 32 KB flag section, past the verdicts
+    uint32_t *const verdict_words = rt.one_verdict ? ws.flags + kVerdictWords : nullptr;
+    unsigned char *const summary = rt.summaries ? ws.summary : nullptr;
 
-    PrepArgs pa;
-    pa.means3D = means3D; pa.means_int = means3D_int; pa.opacity = opacity; pa.semantics = semantics;
-    pa.radii = radii; pa.cov3D = cov3D; pa.points_int = points_int; pa.pts = pts; pa.records = ws.records; pa.boxes = ws.boxes;
-    pa.bitmask = ws.bitmask; pa.verify_flags = ws.flags + 64; pa.P = P; pa.N = N; pa.H = H; pa.W = W; pa.D = D;
-    pa.nwords = ws.nwords; pa.nrow = ws.nrow; pa.nsx = ws.nsx; pa.nsy = ws.nsy; pa.per_axis = radii_per_axis ? 1 : 0;
-    // Waves per workgroup of the records pass = the length of the runs the bitmask rows are written in (a workgroup of W waves owns
-    // W consecutive words of every row).  Small P: TWO, with the records still loaded and stored per lane (round 5: compiling parts
-    // out of the pass showed 2.7 of its 9.5 us in the 625 scattered 8-byte stores of a single-wave workgroup; 16-byte runs:
-    // 43.8 -> 41.9 us per step at P = 25 601; runs of 32 bytes 42.9, of 64 bytes 44.8 -- the workgroup barriers take over).
-    // (long rows, round 6: four waves as well -- the row summaries are one byte per four-wave workgroup)
-    const bool long_rows = ws.summary != nullptr && (flags & GF_WORKSPACE_ZEROED) != 0;
-    const bool staged = P >= 65536 || long_rows;   // (large P: the records through an LDS image, four waves per workgroup)
-    const int prep_waves = staged ? 4 : 2;
-    pa.variant = variant; pa.nprep_blocks = (ws.nwords + prep_waves - 1) / prep_waves; pa.verify = verify ? 1 : 0;
-    // matrix-core kernel: the default wherever it applies (include/gf_hip.h, GF_MFMA_SPLAT / GF_EXACT_FP32)
-    // (the label epilogue -- argmax mode -- is built into the wave-autonomous kernel only: rows of <= kWRow words)
-    const bool mfma_ok = variant == GF_SPLAT_BASE && dense_candidate && P > 0 &&
-                         (!lab.labels || (lab.mode == GF_LABELS_ARGMAX && (mfma_by_wave(ws.nrow) || mfma_by_wave_long(ws.nrow, ws.nwords, flags))));
-    const bool mfma = mfma_ok && ((flags & GF_MFMA_SPLAT) ||
-                                  !(flags & (GF_EXACT_FP32 | GF_FAST_EXP | GF_LIBM_EXP | GF_COMP_EXP)));
-    pa.prescale = (!mfma && exp_flavour(variant, flags) == kExpFast) ? 1 : 0;  // the matrix-core kernel scales in fp64 itself
-    pa.exact_det = (flags & GF_PROB_EXACT_DET) ? 1 : 0;
-    pa.lattice = (mfma && verify) ? 1 : 0;
-    uint32_t *tile_counters = ws.flags + 4608;  // [64 x], x < 8: inside the 32 KB flag section, past the verdicts
-    // GF_PREPARE_BACKWARD: the matrix-core backward's row layout rides along (a scan per wave of 64 Gaussians here, a prefix in
-    // eight waves of the render kernel); a backward that finds the workspace untouched (generation word) then starts with its
-    // gradient kernel
-    // (the layout is finished by workgroups 0 .. kRowLayoutBlocks - 1 of the render launch, finish_row_layout: a grid with fewer
-    // workgroups -- a few supertiles -- would leave Gaussians without their first row, so such a call prepares nothing and the
-    // backward lays its rows out itself)
-    const bool layout_ok = mfma_wave_grid(mfma_wave_units(ws.nsuper, D)) >= kRowLayoutBlocks;
-    pa.unit_totals = (mfma && ws.bwd_cap > 0u && !lab.labels && (flags & GF_PREPARE_BACKWARD) && layout_ok) ? ws.bwd_wave_total : nullptr;
-    pa.unit_local = ws.bwd_row_local; pa.bwd_counters = ws.flags + kBwdCounters;
-    pa.bwd_counter_init = (uint32_t)(mfma_wave_grid(mfma_wave_units(ws.nsuper, D)) / 8);   // (the backward kernel's grid is the forward's)
-    pa.gen_word = ws.flags + kGenWord; pa.gate_state = nullptr;
-    pa.tile_counters = mfma ? tile_counters : nullptr;
-    pa.range_flags = mfma ? ws.range_flags : nullptr;
-    pa.range_theta_here = (mfma && !verify) ? 1 : 0;   // (with the point scans running, their waves take the theta verdict)
-    // one verdict word instead of one per prep wave: the wave kernel on a workspace that was handed over zeroed (see gf_splat_prep_kernel)
-    // (long rows on the wave kernel: with the four-wave records pass that writes the summaries)
-    const int the_kind = mfma_kind(ws.nrow, P, long_rows ? GF_WORKSPACE_ZEROED : 0);
-    const bool by_wave_long = mfma && the_kind == 1 && ws.nrow > kWRow;
-    uint32_t *const verdict_words = (mfma && (flags & GF_WORKSPACE_ZEROED) && the_kind == 1) ? ws.flags + kVerdictWords : nullptr;
-    pa.verdict_words = verdict_words;
-    pa.summary = by_wave_long ? ws.summary : nullptr; pa.sum_pitch = ws.sum_pitch;
-    pa.tile_counter_init = !mfma ? 0u : mfma_counter_init(the_kind, ws.nsuper, D);
-    const int prep_grid = pa.nprep_blocks + (verify ? kVerifyBlocks / prep_waves : 0);
-    if (prep_grid > 0) {
-        const size_t bits_lds = sizeof(unsigned long long) * (size_t)std::min(ws.nsx * ws.nsy * prep_waves, kPrepSuperChunk);
-        const size_t prep_lds = bits_lds + (staged ? (size_t)prep_waves * 64 * kRecDwords * sizeof(float) : 0);
-        if (staged) hipLaunchKernelGGL(gf_splat_prep_kernel<4>, dim3(prep_grid), dim3(256), prep_lds, stream, pa);
-        else hipLaunchKernelGGL((gf_splat_prep_kernel<2, false>), dim3(prep_grid), dim3(128), prep_lds, stream, pa);
-        GF_CHECK_LAUNCH();
+    PrepArgs pa = fill_prep_args(in, ws);
+    pa.variant = variant; pa.nprep_blocks = rt.prep_blocks; pa.verify = rt.verify; pa.prescale = rt.prescale;
+    pa.exact_det = (flags & GF_PROB_EXACT_DET) ? 1 : 0; pa.lattice = rt.lattice;
+    pa.unit_totals = rt.row_layout ? ws.bwd_wave_total : nullptr; pa.bwd_counter_init = rt.bwd_counter_init;
+    pa.tile_counters = rt.range_flags ? tile_counters : nullptr; pa.tile_counter_init = rt.tile_counter_init;
+    pa.range_flags = rt.range_flags ? ws.range_flags : nullptr; pa.range_theta_here = rt.range_theta_here;
+    pa.verdict_words = verdict_words; pa.summary = summary; pa.sum_pitch = ws.sum_pitch;
+    if (rt.prep_grid > 0) {
+        launch_prep(pa, rt.prep_waves == 4, rt.prep_grid, stream);   // staged also for long rows: their summaries are written per four-wave workgroup
+        GF_CHECK_LAUNCH_AS(fn);
     }
-    if (N == 0) return GF_OK;
+    if (in.N == 0) return GF_OK;
 
     RenderArgs ra;
-    ra.pts = pts; ra.points_int = points_int; ra.records = ws.records; ra.boxes = ws.boxes; ra.bitmask = ws.bitmask;
-    ra.out_logits = out_logits; ra.out_bin = out_bin_logits; ra.out_density = out_density; ra.out_prob = out_probability;
-    ra.verify_flags = ws.flags + 64; ra.state = (uint32_t *)state; ra.P = P; ra.N = N; ra.nwords = ws.nwords; ra.nrow = ws.nrow;
-    ra.H = H; ra.W = W; ra.D = D; ra.nsx = ws.nsx; ra.nsy = ws.nsy; ra.ntiles_total = ws.nsuper * kTilesPerSuper;
-    ra.verify_dense = verify ? 1 : 0;
+    ra.pts = in.pts; ra.points_int = in.points_int; ra.records = ws.records; ra.boxes = ws.boxes; ra.bitmask = ws.bitmask;
+    ra.out_logits = out.logits; ra.out_bin = out.bin_logits; ra.out_density = out.density; ra.out_prob = out.probability;
+    ra.verify_flags = ws.flags + 64; ra.state = (uint32_t *)out.state; ra.P = in.P; ra.N = in.N; ra.nwords = ws.nwords; ra.nrow = ws.nrow;
+    ra.H = in.H; ra.W = in.W; ra.D = in.D; ra.nsx = ws.nsx; ra.nsy = ws.nsy; ra.ntiles_total = ws.nsuper * kTilesPerSuper;
+    ra.verify_dense = rt.verify;
     ra.timeline = g_timeline;
     ra.tile_perm = g_tile_perm;
-    ra.out_labels = lab.labels; ra.label_mode = lab.mode; ra.empty_label = lab.empty_label; ra.threshold = lab.threshold;
+    ra.out_labels = out.labels; ra.label_mode = out.label_mode; ra.empty_label = out.empty_label; ra.threshold = out.threshold;
     ra.raw_numerator = (flags & GF_PROB_NUMERATOR) ? 1 : 0;
     ra.tile_counters = tile_counters;
-    ra.range_flags = mfma ? ws.range_flags : nullptr;
+    ra.range_flags = pa.range_flags;
     ra.nrange4 = (ws.nwords + 3) / 4;
-    ra.rows_valid = pa.unit_totals ? 1u : 0u;
+    ra.rows_valid = rt.row_layout ? 1u : 0u;
     ra.unit_totals = ws.bwd_wave_total; ra.unit_local = ws.bwd_row_local; ra.unit_first = ws.bwd_row_first; ra.unit_cap = ws.bwd_cap;
     ra.pub_lists = ws.bwd_lists; ra.pub_len = ws.bwd_list_len;
     ra.verdict_words = verdict_words;
-    ra.summary = by_wave_long ? ws.summary : nullptr; ra.sum_pitch = ws.sum_pitch;
-    {
-        const unsigned per_super = 4u * (unsigned)((D + 7) >> 3);
-        ra.m_ps = (uint32_t)(((1ull << 32) + per_super - 1) / per_super);
-        ra.m_nsy = (uint32_t)(((1ull << 32) + (unsigned)ws.nsy - 1) / (unsigned)ws.nsy);
-    }
-    if (mfma)
-        launch_render_mfma(ra, ws.nsuper, stream);
-    else if (variant == GF_SPLAT_BASE)
-        launch_render_exp<GF_SPLAT_BASE>(flags, dense_candidate, ra, stream);
-    else
-        launch_render_exp<GF_SPLAT_PROB>(flags, dense_candidate, ra, stream);
-    GF_CHECK_LAUNCH();
+    ra.summary = summary; ra.sum_pitch = ws.sum_pitch;
+    ra.m_ps = ceil_recip32(splat_units(1, in.D)); ra.m_nsy = ceil_recip32(ws.nsy);
+    hipEvent_t ev0, ev1;
+    const bool prof = rt.kernel != kRenderArbitrary && profile_slot(&ev0, &ev1);   // (profiled calls time the tile and unit kernels)
+    if (prof) (void)hipEventRecord(ev0, stream);
+    if (rt.kernel >= kRenderMfmaTile) launch_render_mfma(rt, ra, stream);
+    else if (variant == GF_SPLAT_BASE) rt.labels ? launch_render_exact<GF_SPLAT_BASE, true>(rt, ra, stream) : launch_render_exact<GF_SPLAT_BASE, false>(rt, ra, stream);
+    else rt.labels ? launch_render_exact<GF_SPLAT_PROB, true>(rt, ra, stream) : launch_render_exact<GF_SPLAT_PROB, false>(rt, ra, stream);
+    if (prof) (void)hipEventRecord(ev1, stream);
+    GF_CHECK_LAUNCH_AS(fn);
     return GF_OK;
 }
 
@@ -3104,10 +3094,9 @@ extern "C" int gf_splat_forward(int variant, int radii_per_axis, int flags, int 
                                 float *out_probability, void *state, void *workspace,
                                 size_t workspace_bytes, void *stream)
 {
-    const gf::LabelOpts none{nullptr, 0, 0, 0.f};
-    return splat_forward_impl(__func__, variant, radii_per_axis, flags, P, N, C, H, W, D, pts, points_int, means3D,
-                              means3D_int, opacity, semantics, radii, cov3D, out_logits, out_bin_logits, out_density,
-                              out_probability, none, state, workspace, workspace_bytes, stream);
+    const gf::SplatInputs in{radii_per_axis ? 1 : 0, P, N, H, W, D, pts, means3D, opacity, semantics, cov3D, points_int, means3D_int, radii};
+    const gf::ForwardOutputs out{out_logits, out_bin_logits, out_density, out_probability, nullptr, 0, 0, 0.f, state};
+    return splat_forward_impl(__func__, variant, flags, C, in, out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gf_splat_forward_labels(int variant, int radii_per_axis, int flags, int P, int N, int C, int H,
@@ -3119,10 +3108,9 @@ extern "C" int gf_splat_forward_labels(int variant, int radii_per_axis, int flag
                                        long long *out_labels, void *state, void *workspace, size_t workspace_bytes,
                                        void *stream)
 {
-    const gf::LabelOpts lab{out_labels, label_mode, empty_label, threshold};  // out_labels NULL = plain forward
-    return splat_forward_impl(__func__, variant, radii_per_axis, flags, P, N, C, H, W, D, pts, points_int, means3D,
-                              means3D_int, opacity, semantics, radii, cov3D, out_logits, out_bin_logits, out_density,
-                              out_probability, lab, state, workspace, workspace_bytes, stream);
+    const gf::SplatInputs in{radii_per_axis ? 1 : 0, P, N, H, W, D, pts, means3D, opacity, semantics, cov3D, points_int, means3D_int, radii};
+    const gf::ForwardOutputs out{out_logits, out_bin_logits, out_density, out_probability, out_labels, label_mode, empty_label, threshold, state};
+    return splat_forward_impl(__func__, variant, flags, C, in, out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gf_splat_box_volumes(int radii_per_axis, int P, int H, int W, int D,

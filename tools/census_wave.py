@@ -31,7 +31,7 @@ pair = find("auto pair = [&](int b0) {", k0)
 brk = find("if (last) break;", k0)
 nxt = find("// ---- the next unit (claimed during the last group)", k0)
 epi = find("// ---- accumulators C[channel (q&3)", k0)
-end = find("static int mfma_wave_grid", k0)
+end = find("struct BoxVolArgs {", k0) - 1   # (the separator line before it: what follows the kernel)
 phases = [
     ["start-up, per wave (2 048 waves / 5 000 units; includes the never-taken arbitrary-points body: 151 VALU)", k0, ctr - 1, 2048 / 5000],
     ["unit head: decode, row request, wait", ctr, fast - 1, 1.0],
