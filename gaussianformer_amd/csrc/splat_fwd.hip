@@ -2117,6 +2117,21 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
         lds_dma16((gptr)(rec + o5), (lptr)(dst + 5120));
     };
 
+    // Output rows of a unit as the epilogue stores them: float4 i = lane + 64 j (j < 5) of a brick's 16 runs x 18 floats: run i / 18 =
+    // column (run >> 2, run & 3) of the unit, piece i % 18; the upper brick's rows lie 4 voxels = 72 floats further on.  Where a piece
+    // lies relative to the unit's first voxel depends on the lane alone: five byte offsets, computed once per wave (they were
+    // rebuilt by every unit: a division, a 64-bit product and the bounds selects of ten addresses); a unit adds its uniform base.
+    uint32_t st_off[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int i = lane + 64 * j;
+        const int run = i / kC, k = i - run * kC;
+        st_off[j] = i < 16 * kC ? (uint32_t)(((((size_t)(run >> 2) * a.W + (run & 3)) * a.D) * kC + 4 * k) * sizeof(float)) : 0u;
+    }
+    const bool st_tail = lane + 64 * 4 < 16 * kC;   // the fifth float4 of a brick exists in half of the lanes
+    // (the offsets are 32-bit: a grid whose four columns' rows span more than that keeps the per-unit addresses below)
+    const bool st_fits = (3 * (size_t)a.W + 4) * a.D * kC * sizeof(float) < ((size_t)1 << 32);
+
     uint32_t *ctr = a.tile_counters + 64 * xcd;
     // (Longer rows, walked in pieces of kWRow words with the next piece requested while the current one is consumed, were built
     // and measured at P = 144 000 -- four pieces: 94 against the tile kernel's 84 us per step, every wave scanning 2 250 words
@@ -2681,42 +2696,45 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                     __builtin_amdgcn_wave_barrier();
                     labels_from_stage();
                 }
-                if (!LABELS || a.out_logits) {
-                // float4 i = lane + 64 j (j < 5) of a brick's 16 runs x 18: run i / 18 = column (run >> 2, run & 3), piece i % 18; the
-                // upper brick's rows lie 4 voxels = 72 floats further on.  Ten 32-bit element offsets from the uniform base, all
-                // computed first (hipcc makes a store's address registers wait for the store to COMPLETE before they are rewritten).
-                uint32_t off[10];
-                uint32_t okbits = 0u;
-#pragma unroll
-                for (int j = 0; j < 5; ++j) {
-                    const int i = lane + 64 * j;
-                    const int run = i / kC, k = i - run * kC;
-                    const int cx = Xw + (run >> 2), cy = Y0 + (run & 3);
-                    const bool okc = i < 16 * kC && cx < a.H && cy < a.W;
-                    const uint32_t o = (uint32_t)((((size_t)cx * a.W + cy) * a.D + Zw) * kC + 4 * k);
-#pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        const bool ok = okc && Zw + 4 * half < a.D;
-                        okbits |= ok ? (1u << (5 * half + j)) : 0u;
-                        off[5 * half + j] = ok ? o + 4 * kC * half : 0u;
-                    }
-                }
                 // (a unit inside the grid issues all ten store instructions: the count the next unit's row wait relies on)
-                nst = ((!LABELS) && Xw + 4 <= a.H && Y0 + 4 <= a.W && Zw + 8 <= a.D) ? 10 : -1;
-                asm volatile("" : "+v"(off[0]), "+v"(off[1]), "+v"(off[2]), "+v"(off[3]), "+v"(off[4]), "+v"(off[5]), "+v"(off[6]),
-                             "+v"(off[7]), "+v"(off[8]), "+v"(off[9]));
+                const bool inside = Xw + 4 <= a.H && Y0 + 4 <= a.W && Zw + 8 <= a.D;
+                nst = ((!LABELS) && inside) ? 10 : -1;
+                if (!LABELS || a.out_logits) {
+                typedef __attribute__((address_space(1))) char gchar;
+                gchar *ubase = (gchar *)a.out_logits + ((((size_t)Xw * a.W + Y0) * a.D + Zw) * kC) * sizeof(float);   // the unit's first voxel
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-                gfloat *obase = (gfloat *)a.out_logits;
                 // all ten LDS reads first (unconditional: a lane without a store reads a row it will not use), then the stores
                 float4 val[10];
 #pragma unroll
                 for (int it = 0; it < 10; ++it)
                     val[it] = *reinterpret_cast<const float4 *>(stage + (it / 5) * 64 * kC + 4 * (lane + 64 * (it % 5)));
+                if (inside && st_fits) {
+                    // wholly inside the grid (every unit at 200 x 200 x 16): the uniform base + the wave's per-lane offsets, no bounds
 #pragma unroll
-                for (int it = 0; it < 10; ++it) {
-                    if (okbits & (1u << it))
-                        __builtin_nontemporal_store((nt4v){val[it].x, val[it].y, val[it].z, val[it].w}, (nt4 *)(obase + off[it]));
+                    for (int it = 0; it < 10; ++it) {
+                        if (it % 5 < 4 || st_tail)
+                            __builtin_nontemporal_store((nt4v){val[it].x, val[it].y, val[it].z, val[it].w},
+                                                        (nt4 *)(ubase + st_off[it % 5] + (it / 5) * 4 * kC * sizeof(float)));
+                    }
+                } else {
+                    // a unit that crosses the grid's edge: every piece's column and brick are tested.  Its lane arithmetic is kept
+                    // in here (hoisted out of the unit loop by the compiler it would hold registers of every unit for the few at the edge).
+                    int l = lane;
+                    asm volatile("" : "+v"(l));
+#pragma unroll
+                    for (int j = 0; j < 5; ++j) {
+                        const int i = l + 64 * j;
+                        const int run = i / kC, k = i - run * kC;
+                        const bool okc = i < 16 * kC && Xw + (run >> 2) < a.H && Y0 + (run & 3) < a.W;
+                        const size_t o = ((((size_t)(run >> 2) * a.W + (run & 3)) * a.D) * kC + 4 * k) * sizeof(float);
+#pragma unroll
+                        for (int half = 0; half < 2; ++half) {
+                            const float4 v = val[5 * half + j];
+                            if (okc && Zw + 4 * half < a.D)
+                                __builtin_nontemporal_store((nt4v){v.x, v.y, v.z, v.w}, (nt4 *)(ubase + o + half * 4 * kC * sizeof(float)));
+                        }
+                    }
                 }
                 }
             } else {

@@ -31,6 +31,8 @@ pair = find("auto pair = [&](int b0) {", k0)
 brk = find("if (last) break;", k0)
 nxt = find("// ---- the next unit (claimed during the last group)", k0)
 epi = find("// ---- accumulators C[channel (q&3)", k0)
+edge = find("// a unit that crosses the grid's edge", k0)
+odd = find("// depths that are not a multiple of 4", edge) - 1
 end = find("struct BoxVolArgs {", k0) - 1   # (the separator line before it: what follows the kernel)
 phases = [
     ["start-up, per wave (2 048 waves / 5 000 units; includes the never-taken arbitrary-points body: 151 VALU)", k0, ctr - 1, 2048 / 5000],
@@ -42,7 +44,9 @@ phases = [
     ["group: operands (theta in fp64 -> 3 x f16, one-hot, S' transpose + split)", oper, pair - 1, 2.16],
     ["group: two pairs of blocks (64 exp, hi/lo split, 40 MFMA)", pair, brk - 1, 2.16],
     ["next claim + next row request", brk, epi - 1, 1.0],
-    ["epilogue: stage, ten addresses, ten stores", epi, end - 1, 1.0],
+    ["epilogue: stage, ten stores from the wave's offsets", epi, edge - 1, 1.0],
+    ["epilogue, units that cross the grid's edge (none at 200 x 200 x 16): addresses and bounds per piece", edge, odd - 1, 0.0],
+    ["epilogue, depths that are no multiple of 4 (counted as run, as in the censuses before)", odd, end - 1, 1.0],
 ]
 with tempfile.NamedTemporaryFile("w", suffix=".json", delete=False) as f:
     json.dump(phases, f)
