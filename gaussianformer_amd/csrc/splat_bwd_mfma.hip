@@ -42,18 +42,13 @@
 
 
 #include "gf_common.hpp"
+#include "splat_mfma.hpp"
 
 #ifndef GF_TIMELINE
 #define GF_TIMELINE 0  // -DGF_TIMELINE=1: per-unit timestamps of the gradient kernel (tools/timeline_bwd.py)
 #endif
 
 namespace gf {
-
-union H8 {
-    h8 v;
-    fp16x2 p[4];
-    _Float16 e[8];
-};
 
 // The Gaussians with more than kBwdBigRows rows (normally one: the whole-grid "empty" Gaussian), as a table the gradient kernel's
 // zeroing wave leaves for the row-sum kernel: [0] = count (0xFFFFFFFF: more than kBwdBigTable, the row-sum kernel finds them itself),

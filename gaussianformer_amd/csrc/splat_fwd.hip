@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "gf_common.hpp"
+#include "splat_mfma.hpp"
 
 #ifndef GF_TIMELINE
 #define GF_TIMELINE 0  // -DGF_TIMELINE=1: per-workgroup timestamps of the render kernel (tools/timeline.py)
@@ -1271,12 +1272,6 @@ __global__ __launch_bounds__(kBlock, kRenderWavesPerSimd) void gf_splat_render_k
 // Work decomposition as in gf_splat_render_kernel (tile = workgroup, double brick = wave, the supertile's candidates in
 // an LDS list); the hits of a wave are compacted into a per-wave LDS queue (id + the four 32-voxel masks) and leave it
 // in groups of 32.  A 32-voxel block b of the double brick = lanes [32 (b&1), 32 (b&1) + 32) of brick b >> 1.
-union H8 {
-    h8 v;
-    fp16x2 p[4];
-    _Float16 e[8];
-    uint32_t u[4];
-};
 constexpr int kRowWords = 3072;  // bitmask row length up to which the matrix-core kernel's producer stages the whole row in LDS (P <= 196 608)
 constexpr int kListCapM = 2304;  // tile list entries of the matrix-core kernel: ids (4 B) + packed boxes (8 B) in LDS
 constexpr int kQCap = 128;  // hit queue entries per wave, a ring (power of two): <= 63 waiting + a batch of <= 64
@@ -1416,13 +1411,7 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
         const uint32_t id = q_id[(qh + start + (n < count ? n : 0)) & (kQCap - 1)];
         const char *rec = reinterpret_cast<const char *>(a.records + (size_t)id * kRecDwords);
         const int o3 = (3 + 3 * h) * 16, o4 = (4 + 3 * h) * 16, o5 = (h ? 7 : 5) * 16;
-        char *dst = reinterpret_cast<char *>(slot);
-        lds_dma16((gptr)(rec), (lptr)(dst));
-        lds_dma16((gptr)(rec + 16), (lptr)(dst + 1024));
-        lds_dma16((gptr)(rec + 32), (lptr)(dst + 2048));
-        lds_dma16((gptr)(rec + o3), (lptr)(dst + 3072));
-        lds_dma16((gptr)(rec + o4), (lptr)(dst + 4096));
-        lds_dma16((gptr)(rec + o5), (lptr)(dst + 5120));
+        request_record_pieces(rec, reinterpret_cast<char *>(slot), o3, o4, o5);
     };
     for (;;) {  // tiles of this workgroup
 #if GF_TIMELINE
@@ -1707,45 +1696,8 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
                     // ---- the four 32-voxel blocks, two at a time: exponents of a pair (two independent MFMA chains alternate), exp +
                     // split of each (VALU), accumulation of the pair -- which drains in the matrix pipe under the next pair's
                     // VALU work, the last one under the next group's operand preparation.
-                    auto pair = [&](int b0) {
-                        f32x16 d0, d1;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) { d0[r] = 0.f; d1[r] = 0.f; }
-                        d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t3.v, phi[b0], d0, 0, 0, 0);
-                        d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t3.v, phi[b0 + 1], d1, 0, 0, 0);
-                        d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t2.v, phi[b0], d0, 0, 0, 0);
-                        d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t2.v, phi[b0 + 1], d1, 0, 0, 0);
-                        d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t1.v, phi[b0], d0, 0, 0, 0);
-                        d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t1.v, phi[b0 + 1], d1, 0, 0, 0);
-                        d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tb.v, hot[b0], d0, 0, 0, 0);
-                        d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tb.v, hot[b0 + 1], d1, 0, 0, 0);
-                        H8 wh[2][2], wl[2][2];
-                        auto weights = [&](const f32x16 &d, int k) {
-#pragma unroll
-                            for (int r = 0; r < 16; r += 2) {
-                                const float w0 = __builtin_amdgcn_exp2f(d[r]), w1 = __builtin_amdgcn_exp2f(d[r + 1]);
-                                const fp16x2 hi = __builtin_amdgcn_cvt_pkrtz(w0, w1);
-                                float r0, r1;  // exact residuals w - hi, the f16 halves read in place (v_fma_mix_f32)
-                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(w0));
-                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(w1));
-                                wh[k][r >> 3].p[(r & 7) >> 1] = hi;
-                                wl[k][r >> 3].p[(r & 7) >> 1] = __builtin_amdgcn_cvt_pkrtz(r0, r1);
-                            }
-                        };
-                        weights(d0, 0);
-                        weights(d1, 1);
-#pragma unroll
-                        for (int kh = 0; kh < 2; ++kh) {
-#pragma unroll
-                            for (int k = 0; k < 2; ++k) acc[b0 + k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sl[kh].v, wh[k][kh].v, acc[b0 + k], 0, 0, 0);
-#pragma unroll
-                            for (int k = 0; k < 2; ++k) acc[b0 + k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sh[kh].v, wl[k][kh].v, acc[b0 + k], 0, 0, 0);
-#pragma unroll
-                            for (int k = 0; k < 2; ++k) acc[b0 + k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sh[kh].v, wh[k][kh].v, acc[b0 + k], 0, 0, 0);
-                        }
-                    };
-                    pair(0);
-                    pair(2);
+                    exp_accumulate_pair(t1, t2, t3, tb, phi[0], phi[1], hot[0], hot[1], sh, sl, acc[0], acc[1]);
+                    exp_accumulate_pair(t1, t2, t3, tb, phi[2], phi[3], hot[2], hot[3], sh, sl, acc[2], acc[3]);
 #if GF_TIMELINE
                     asm volatile("" :: "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]));
                     const unsigned long long tg3 = __builtin_amdgcn_s_memtime();
@@ -2108,13 +2060,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
         const char *rec = reinterpret_cast<const char *>(a.records + (size_t)id * kRecDwords);
         // (semantics: lane h = 0 takes pieces 3..5 = channels 0..11, lane h = 1 pieces 5..7 = channels 8..19 -- see S' below)
         const int o3 = (3 + 2 * h) * 16, o4 = (4 + 2 * h) * 16, o5 = (5 + 2 * h) * 16;
-        char *dst = reinterpret_cast<char *>(slot);
-        lds_dma16((gptr)(rec), (lptr)(dst));
-        lds_dma16((gptr)(rec + 16), (lptr)(dst + 1024));
-        lds_dma16((gptr)(rec + 32), (lptr)(dst + 2048));
-        lds_dma16((gptr)(rec + o3), (lptr)(dst + 3072));
-        lds_dma16((gptr)(rec + o4), (lptr)(dst + 4096));
-        lds_dma16((gptr)(rec + o5), (lptr)(dst + 5120));
+        request_record_pieces(rec, reinterpret_cast<char *>(slot), o3, o4, o5);
     };
 
     // Output rows of a unit as the epilogue stores them: float4 i = lane + 64 j (j < 5) of a brick's 16 runs x 18 floats: run i / 18 =
@@ -2587,45 +2533,8 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                             sh[q >> 1].p[2 * (q & 1)] = ha; sh[q >> 1].p[2 * (q & 1) + 1] = hb;
                             sl[q >> 1].p[2 * (q & 1)] = __builtin_amdgcn_cvt_pkrtz(ra0, ra1); sl[q >> 1].p[2 * (q & 1) + 1] = __builtin_amdgcn_cvt_pkrtz(rb0, rb1);
                         }
-                        auto pair = [&](int b0) {
-                            f32x16 d0, d1;
-#pragma unroll
-                            for (int q = 0; q < 16; ++q) { d0[q] = 0.f; d1[q] = 0.f; }
-                            d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t3.v, phi[b0], d0, 0, 0, 0);
-                            d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t3.v, phi[b0 + 1], d1, 0, 0, 0);
-                            d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t2.v, phi[b0], d0, 0, 0, 0);
-                            d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t2.v, phi[b0 + 1], d1, 0, 0, 0);
-                            d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t1.v, phi[b0], d0, 0, 0, 0);
-                            d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(t1.v, phi[b0 + 1], d1, 0, 0, 0);
-                            d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tb.v, hot[b0], d0, 0, 0, 0);
-                            d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tb.v, hot[b0 + 1], d1, 0, 0, 0);
-                            H8 wh[2][2], wl[2][2];
-                            auto weights = [&](const f32x16 &d, int k) {
-#pragma unroll
-                                for (int q = 0; q < 16; q += 2) {
-                                    const float w0 = __builtin_amdgcn_exp2f(d[q]), w1 = __builtin_amdgcn_exp2f(d[q + 1]);
-                                    const fp16x2 hi = __builtin_amdgcn_cvt_pkrtz(w0, w1);
-                                    float q0, q1;  // exact residuals w - hi, the f16 halves read in place (v_fma_mix_f32)
-                                    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(q0) : "v"(hi), "v"(w0));
-                                    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(q1) : "v"(hi), "v"(w1));
-                                    wh[k][q >> 3].p[(q & 7) >> 1] = hi;
-                                    wl[k][q >> 3].p[(q & 7) >> 1] = __builtin_amdgcn_cvt_pkrtz(q0, q1);
-                                }
-                            };
-                            weights(d0, 0);
-                            weights(d1, 1);
-#pragma unroll
-                            for (int kh = 0; kh < 2; ++kh) {
-#pragma unroll
-                                for (int k = 0; k < 2; ++k) acc[b0 + k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sl[kh].v, wh[k][kh].v, acc[b0 + k], 0, 0, 0);
-#pragma unroll
-                                for (int k = 0; k < 2; ++k) acc[b0 + k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sh[kh].v, wl[k][kh].v, acc[b0 + k], 0, 0, 0);
-#pragma unroll
-                                for (int k = 0; k < 2; ++k) acc[b0 + k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sh[kh].v, wh[k][kh].v, acc[b0 + k], 0, 0, 0);
-                            }
-                        };
-                        pair(0);
-                        pair(2);
+                        exp_accumulate_pair(t1, t2, t3, tb, phi[0], phi[1], hot[0], hot[1], sh, sl, acc[0], acc[1]);
+                        exp_accumulate_pair(t1, t2, t3, tb, phi[2], phi[3], hot[2], hot[3], sh, sl, acc[2], acc[3]);
                         have_next = have_next || last_group;
                         qhead = (qhead + qn) & (kQCap - 1);
                         qlen -= qn;

@@ -792,3 +792,80 @@ def test_one_verdict_word_follows_the_inputs_call_after_call(gpu, assume_dense):
         torch.cuda.synchronize()
         assert plan.state_words()[1:3] == ([arb, 8] if poison else [wave, 0]), (poison, plan.state_words()[:3])
         assert_logits_close(plan.logits.cpu().numpy(), exact.run().cpu().numpy(), tol=1e-4)
+
+
+def _list_builder_scene(side=16):
+    """Grid side x side x 8 (16: four supertiles, one z brick; 32: the same Gaussians in the same places, twelve more supertiles
+    that hold the whole-grid Gaussian alone), 16 000 Gaussians (250 bitmask words: 15 999 + the whole-grid one, which is
+    bit 63 of word 249 in every row), all of radius 1 (scales 0.08 .. 0.16 m, boxes of three voxels a side, kept inside their
+    supertile).  Supertile (0, 0): Gaussians 64 k, k < 230 -- 231 non-zero words of one bit each: more than 192 and at most 256, the
+    fast path's loop branch in both kernels.  Supertile (0, 1): Gaussians 64 k + 1, k < 40 -- 41 non-zero words, the three-round
+    branch.  Supertile (1, 1): all the others, ~15 700 -- every word dense, every 64-word chunk holds ~4 000 candidates: the chunked
+    fill goes in by lane groups and `sg` carries over between passes.  Supertile (1, 0): the whole-grid Gaussian alone.
+    Semantics are softplus (positive: sums of thousands of terms without cancellation) and opacities uniform, as the config draws
+    them; nothing had to be thinned for the oracle bounds."""
+    from gaussianformer_amd.synthetic import cov_inverse
+    P = 15999
+    si = make_splat_inputs("nuscenes_gs25600_solid", seed=41, P=P, H=side, W=side, D=8)
+    rng = np.random.default_rng(42)
+    lo = np.asarray(si.pc_min, dtype=np.float64)
+    idx = np.arange(P)
+    sparse = (idx % 64 == 0) & (idx < 64 * 230)
+    few = (idx % 64 == 1) & (idx < 64 * 40)
+    x0 = np.where(sparse | few, 0.0, 8.0)
+    y0 = np.where(sparse, 0.0, 8.0)
+    # centre cells 2 .. 5 of the supertile: the box of radius 1 stays inside it
+    si.means3D[:-1, 0] = (lo[0] + (x0 + 2.0 + 4.0 * rng.random(P)) * si.grid_size).astype(np.float32)
+    si.means3D[:-1, 1] = (lo[1] + (y0 + 2.0 + 4.0 * rng.random(P)) * si.grid_size).astype(np.float32)
+    si.scales[:-1] = (0.08 + 0.08 * rng.random((P, 3))).astype(np.float32)
+    quats = np.tile(np.array([[1.0, 0.0, 0.0, 0.0]]), (si.scales.shape[0], 1))
+    si.cov3D = cov_inverse(si.scales, quats).astype(np.float32)
+    return si
+
+
+@pytest.mark.parametrize("side", [16, 32])
+def test_list_builder_regimes_agree_across_kernels_and_with_the_oracle(gpu, side):
+    """One small scene (_list_builder_scene) takes the candidate-list code of the wave kernel and of the matrix-core backward --
+    the same text in both, kept in each kernel -- through all its regimes: three rounds side by side (<= 192 non-zero words), the
+    loop branch (231 words), and the chunked fill by lane groups with `sg` carried between passes.  Wave and tile kernel give equal
+    bits; the backward behind a plain forward, behind a GF_PREPARE_BACKWARD forward and with GF_RECORDS_VALID gives equal bits;
+    both meet the oracle at the bounds of test_mfma_crowded_tile (1e-4 scaled) and of
+    test_backward_when_a_supertile_has_more_candidates_than_a_published_list_holds (2e-4 of the largest gradient).
+    GF_RECORDS_VALID may only be asserted behind a forward that says "prepared" (word 4 of the state block; the library answers
+    NaN otherwise, test_backward_takes_the_forward_records_when_the_workspace_still_holds_them).  At 16 x 16 x 8 the render launch
+    has 16 workgroups, fewer than the 64 that finish the row layout of 250 waves of Gaussians, so that forward prepares nothing
+    (test_backward_after_a_prepared_forward_on_a_grid_of_few_workgroups) and the third backward cannot be asked for; side = 32
+    puts the same Gaussians on a grid of 64 units, where it is prepared and all three are compared.
+    Measured on an MI355X at side 16: forward 9.5e-6 scaled, gradients 9.3e-6 of the largest."""
+    from gaussianformer_amd import _lib
+    si = _list_builder_scene(side)
+    pi, mi, radii, cov6 = prep(si)
+    assert si.means3D.shape[0] == 16000 and (radii[:-1] == 1).all()
+    wave, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
+    assert state0.view(torch.int32)[:5].tolist()[1] == _lib.GF_PATH_MATRIX_CORE_WAVE   # (otherwise the scene fell back and proved nothing)
+    with _lib.option("splat.mfma_tile_kernel", 1):
+        tile, _, tstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
+    assert tstate.view(torch.int32)[:5].tolist()[1] == _lib.GF_PATH_MATRIX_CORE
+    assert np.array_equal(wave["logits"], tile["logits"])
+    ref = _oracle_logits(si, pi, mi, radii, cov6)
+    err = np.abs(wave["logits"].astype(np.float64) - ref) / np.maximum(1.0, np.abs(ref))
+    print("forward: max scaled error", err.max(), "max |logit|", np.abs(ref).max())
+    assert_logits_close(wave["logits"], ref, tol=1e-4)
+
+    g = np.random.default_rng(43).standard_normal((si.pts.shape[0], 18)).astype(np.float32)
+    gref = oracle.splat_backward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D, g)
+    _, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
+    assert state0.view(torch.int32)[:5].tolist()[1] == _lib.GF_PATH_MATRIX_CORE_WAVE
+    plain = _bwd(gpu, si, t, state0, g)
+    _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
+    words = state.view(torch.int32)[:5].tolist()
+    print("prepared forward: state words", words)
+    assert words[1] == _lib.GF_PATH_MATRIX_CORE_WAVE
+    assert (words[4] & 1) == (1 if side == 32 else 0)
+    prepared = _bwd(gpu, si, t, state, g)
+    asserted = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if words[4] & 1 else prepared
+    for a, b, c, r in zip(plain, prepared, asserted, gref):
+        print("backward: max error / max |ref|", np.abs(a - r.reshape(a.shape)).max() / max(np.abs(r).max(), 1e-30))
+        assert np.isfinite(a).all()
+        assert np.array_equal(a, b) and np.array_equal(a, c)
+        assert np.abs(a - r.reshape(a.shape)).max() <= 2e-4 * max(np.abs(r).max(), 1e-30)

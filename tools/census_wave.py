@@ -27,7 +27,7 @@ slow = find("while (true) {  // fill the list from the row", k0)
 boxes = find("// ---- the packed boxes of the listed Gaussians", k0)
 cons = find("// ---- consume: hits of the double brick", k0)
 oper = find("// ---- operands of the group: lane", k0)
-pair = find("auto pair = [&](int b0) {", k0)
+pair = find("exp_accumulate_pair(t1, t2, t3, tb, phi[0]", k0)
 brk = find("if (last) break;", k0)
 nxt = find("// ---- the next unit (claimed during the last group)", k0)
 epi = find("// ---- accumulators C[channel (q&3)", k0)
