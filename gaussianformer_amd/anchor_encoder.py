@@ -1,0 +1,124 @@
+"""The anchor encoder: drop-in for ``SparseGaussian3DEncoder`` (model/encoder/gaussian_encoder/anchor_encoder_module.py:7-53,
+its layers from ``linear_relu_ln``, utils.py:49-59).  Five input branches (xyz, scale, rotation, opacity, semantics), each
+``Linear(k -> E), ReLU, LayerNorm, Linear(E -> E), ReLU, LayerNorm``, their sum, then ``output_fc`` with two more such stages:
+about 40 torch kernels, and ``gf_anchor_embed_forward`` (include/gf_hip.h) in one launch.  The native op is
+a forward only: training keeps the module's torch layers."""
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+f32 = torch.float32
+E_NATIVE, MAX_S = _lib.GF_ANCHOR_EMBED_DIMS, _lib.GF_ANCHOR_EMBED_MAX_S
+STAGES = ("xyz_fc", "scale_fc", "rot_fc", "opacity_fc", "semantics_fc", "output_fc")
+_SLOTS = ("0.weight", "0.bias", "2.weight", "2.bias", "3.weight", "3.bias", "5.weight", "5.bias")   # state_dict order
+
+
+def embedding_layer(embed_dims, input_dims):
+    """``nn.Sequential(*linear_relu_ln(embed_dims, 1, 2, input_dims))``: Linear at 0 and 3, LayerNorm at 2 and 5."""
+    E = embed_dims
+    return nn.Sequential(nn.Linear(input_dims, E), nn.ReLU(inplace=True), nn.LayerNorm(E),
+                         nn.Linear(E, E), nn.ReLU(inplace=True), nn.LayerNorm(E))
+
+
+def _param_list(module_or_params):
+    """The 48 parameters in the library's order (``None`` for an absent branch), from a module with the reference's submodule
+    names or from a mapping with its state_dict keys."""
+    if isinstance(module_or_params, nn.Module):
+        def get(stage, slot):
+            sub = getattr(module_or_params, stage, None)
+            if sub is None:
+                return None
+            i, name = slot.split(".")
+            return getattr(sub[int(i)], name)
+    else:
+        def get(stage, slot):
+            return module_or_params.get(f"{stage}.{slot}")
+    return [get(stage, slot) for stage in STAGES for slot in _SLOTS]
+
+
+def _needs_grad(tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _launch(anchor, params):
+    """The library call on the 48-entry parameter list; the callers have settled autograd."""
+    _lib.require_gpu(anchor, *params)
+    if params[0] is None or params[40] is None:
+        raise ValueError("anchor_embed needs at least xyz_fc, scale_fc, rot_fc and output_fc")
+    E = params[0].shape[0]
+    opa = 1 if params[24] is not None else 0
+    S = 0 if params[32] is None else params[32].shape[1]
+    a = _lib.as_arg(anchor)
+    lead, Da = a.shape[:-1], a.shape[-1]
+    a = a.reshape(-1, Da)
+    table = (ctypes.c_void_p * _lib.GF_ANCHOR_EMBED_PARAMS)()
+    held = []   # converted copies stay alive until the launch is queued (the caching allocator orders their reuse)
+    for i, p in enumerate(params):
+        if p is None:
+            continue
+        if p.dtype != f32 or not p.is_contiguous() or p.data_ptr() % 16:   # (a module's own parameters: never)
+            p = _lib.as_arg(p)
+            p = p.clone() if p.data_ptr() % 16 else p
+            held.append(p)
+        table[i] = p.data_ptr()
+    out = torch.empty(a.shape[0], E, dtype=f32, device=a.device)
+    _lib.call("gf_anchor_embed_forward", a.device, a.shape[0], Da, E, opa, S, a, ctypes.cast(table, ctypes.c_void_p), out)
+    return out.view(*lead, E)
+
+
+def anchor_embed(anchor, module_or_params):
+    """``out [..., 128] = SparseGaussian3DEncoder.forward(anchor [..., Da])`` by the native op, on any leading batch shape.
+    ``module_or_params``: a module with the reference's submodules, or a mapping with its state_dict keys
+    (``xyz_fc.0.weight`` ... ``output_fc.5.bias``); which branches exist says ``include_opa`` and the semantic width.  The
+    parameters are read in place at every call.  Forward only: inputs that need autograd are refused."""
+    params = _param_list(module_or_params)
+    if _needs_grad([anchor, *params]):
+        raise RuntimeError(
+            "anchor_embed is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters "
+            "that do not require grad (the SparseGaussian3DEncoder module routes training to its torch layers)")
+    return _launch(anchor, params)
+
+
+class SparseGaussian3DEncoder(nn.Module):
+    """Same constructor keys and defaults, attributes, submodule names, ``state_dict`` keys and ``forward(box_3d)`` as the
+    reference class (anchor_encoder_module.py:7-53), so its checkpoints load with ``strict=True``.  The native op runs when the
+    input is an fp32 GPU tensor, ``embed_dims == 128``, the semantic width is at most 32 and nothing needs autograd; everything
+    else (training, CPU tensors, other widths or dtypes) runs the module's own torch layers, the reference's composition."""
+
+    def __init__(self, embed_dims=256, include_opa=True, semantics=False, semantic_dim=None):
+        super().__init__()
+        self.embed_dims = embed_dims
+        self.include_opa = include_opa
+        self.semantics = semantics
+        self.xyz_fc = embedding_layer(embed_dims, 3)
+        self.scale_fc = embedding_layer(embed_dims, 3)
+        self.rot_fc = embedding_layer(embed_dims, 4)
+        if include_opa:
+            self.opacity_fc = embedding_layer(embed_dims, 1)
+        if semantics:
+            assert semantic_dim is not None
+            self.semantics_fc = embedding_layer(embed_dims, semantic_dim)
+            self.semantic_start = 10 + int(include_opa)
+        else:
+            semantic_dim = 0
+        self.semantic_dim = semantic_dim
+        self.output_fc = embedding_layer(embed_dims, embed_dims)
+
+    def forward(self, box_3d):
+        if box_3d.is_cuda and box_3d.dtype == f32 and self.embed_dims == E_NATIVE and self.semantic_dim <= MAX_S:
+            params = _param_list(self)
+            if params[0].is_cuda and params[0].dtype == f32 and not _needs_grad([box_3d, *params]):
+                return _launch(box_3d, params)
+        return self.forward_torch(box_3d)
+
+    def forward_torch(self, box_3d):
+        """The reference's composition (:38-53) on the module's torch layers."""
+        output = self.xyz_fc(box_3d[..., :3]) + self.scale_fc(box_3d[..., 3:6]) + self.rot_fc(box_3d[..., 6:10])
+        if self.include_opa:
+            output = output + self.opacity_fc(box_3d[..., 10:11])
+        if self.semantics:
+            output = output + self.semantics_fc(box_3d[..., self.semantic_start:self.semantic_start + self.semantic_dim])
+        return self.output_fc(output)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward; 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward (added without a bump: a library without it fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -732,6 +732,38 @@ int gf_refine_backward(int n, int D, int Da, int version, int flags, int R, int 
                        const float *grad_rotations, const float *grad_opacities, const float *grad_semantics,
                        const float *grad_original_means, const float *grad_delta_means, float *grad_output, float *grad_anchor,
                        void *stream);
+
+/* ---- the anchor encoder ---------------------------------------------------------------------------------------------------
+ * Replaces SparseGaussian3DEncoder.forward (model/encoder/gaussian_encoder/anchor_encoder_module.py:38-53; its layers are
+ * linear_relu_ln(embed_dims, 1, 2, input_dims), utils.py:49-59): one launch instead of about 40 torch kernels, DESIGN.md
+ * §3.13.  Per anchor row a (Da floats), E = 128, opa = include_opa != 0, ss = 10 + opa:
+ *   branch inputs, in this order: a[0:3] (:39), a[3:6] (:40), a[6:10] (:41), a[10:11] when opa (:42-43), a[ss:ss+S] when
+ *              S > 0 (:46-47)
+ *   f_b      = LN2(relu(W2 LN1(relu(W1 x_b + b1)) + b2)); LayerNorm over the 128 features, biased variance, eps 1e-5, affine
+ *   s        = xyz + scale + rot (+ opacity) (+ semantics), summed left to right (:51)
+ *   out      = LN(relu(Wo2 LN(relu(Wo1 s + bo1)) + bo2))  (:52), f32 [n, 128]
+ * Columns of a that no branch reads are never loaded: they cannot influence the result, NaN and Inf included.
+ *   anchor     f32 [n, Da] (any 4-byte alignment)         out f32 [n, 128], 16-byte aligned (it is written 16 bytes at a time)
+ *   params     HOST table of GF_ANCHOR_EMBED_PARAMS = 6 x 8 device pointers, the modules' own tensors in torch's layout,
+ *              contiguous f32.  Stage s = 0 .. 5 is xyz_fc, scale_fc, rot_fc, opacity_fc, semantics_fc, output_fc; within a
+ *              stage, in state_dict order:
+ *                8 s + 0  .0.weight [128, k]  (k = 3, 3, 4, 1, S; 128 for output_fc)      8 s + 1  .0.bias [128]
+ *                8 s + 2  .2.weight [128]  (LayerNorm)                                    8 s + 3  .2.bias [128]
+ *                8 s + 4  .3.weight [128, 128]                                            8 s + 5  .3.bias [128]
+ *                8 s + 6  .5.weight [128]  (LayerNorm)                                    8 s + 7  .5.bias [128]
+ *              The eight of an absent branch (opacity_fc without opa, semantics_fc with S = 0) are ignored; pass NULL.
+ *              Every pointer but a branch's .0.weight must be 16-byte aligned (torch's allocations are).
+ * The table is read during the call and the weights by the kernel, in place: every call uses the parameters' current values,
+ * nothing is cached or re-laid out, and there is no workspace.
+ * GF_EINVAL before any HIP call: E != 128, S > 32, Da < 10 + opa + S, a null or misaligned parameter of a stage that is
+ * present, a misaligned out.  n == 0 returns GF_OK without a launch.  Exact fp32 products (v_mfma_f32_32x32x2_f32), no atomics, bitwise
+ * reproducible; a row's result does not depend on n or on the row's position; no host synchronisation, no allocation:
+ * graph-capturable. */
+#define GF_ANCHOR_EMBED_DIMS 128
+#define GF_ANCHOR_EMBED_MAX_S 32
+#define GF_ANCHOR_EMBED_PARAMS 48
+int gf_anchor_embed_forward(int n, int Da, int E, int include_opa, int S, const float *anchor, const void *const *params,
+                            float *out, void *stream);
 
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */

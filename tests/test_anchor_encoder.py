@@ -1,0 +1,124 @@
+"""The anchor encoder without a GPU: the float64 restatement against the reference's recorded float64 output
+(tests/golden/anchor_embed.npz, tools/make_golden_anchor_embed.py), the drop-in's state_dict against the reference's, and the
+drop-in's torch route -- the one a CPU tensor takes -- with its gradients against the float64 truth."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import anchor_embed_ref as ref
+from gaussianformer_amd import anchor_encoder
+from gaussianformer_amd.anchor_encoder import SparseGaussian3DEncoder, anchor_embed
+
+GOLDEN = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_embed.npz"))
+EPS32 = float(np.finfo(np.float32).eps)
+FAMILIES = list(ref.FAMILIES)
+
+
+def _family(name):
+    cfg = ref.FAMILIES[name]
+    opa, S = bool(cfg["include_opa"]), cfg["semantic_dim"] or 0
+    g = {k: GOLDEN[f"{name}.{k}"] for k in ("keys", "shapes", "seed", "input", "out32", "out64")}
+    return cfg, opa, S, g
+
+
+@pytest.mark.parametrize("name", FAMILIES)
+def test_float64_restatement_equals_the_reference(name):
+    """Rounding of a 12-stage, K <= 128 float64 chain is about 1e-13; a wrong slice, order, eps or variance is >= 1e-3."""
+    cfg, opa, S, g = _family(name)
+    sd = ref.fixed_weights(opa, S, seed=int(g["seed"]), dtype=torch.float64)
+    out = ref.anchor_embed_ref(torch.from_numpy(g["input"]).double(), sd).numpy()
+    truth = g["out64"]
+    assert out.shape == truth.shape == (ref.GOLDEN_ROWS, 128)
+    assert np.abs(out - truth).max() <= 1e-10 * np.abs(truth).max()
+
+
+@pytest.mark.parametrize("name", FAMILIES)
+def test_state_dict_keys_and_shapes_are_the_reference_s(name):
+    cfg, opa, S, g = _family(name)
+    module = SparseGaussian3DEncoder(embed_dims=128, **cfg)
+    sd = module.state_dict()
+    assert list(sd.keys()) == [str(k) for k in g["keys"]]
+    assert [list(v.shape) + [0] * (2 - v.dim()) for v in sd.values()] == g["shapes"].tolist()
+    assert list(ref.shapes(opa, S).keys()) == list(sd.keys())
+    module.load_state_dict(ref.fixed_weights(opa, S, seed=int(g["seed"])), strict=True)
+    assert (module.embed_dims, module.include_opa, module.semantics, module.semantic_dim) == (128, opa, cfg["semantics"], S)
+    if cfg["semantics"]:
+        assert module.semantic_start == 10 + int(opa)
+
+
+def test_constructor_defaults_are_the_reference_s():
+    import inspect
+    sig = inspect.signature(SparseGaussian3DEncoder.__init__)
+    assert [(k, p.default) for k, p in list(sig.parameters.items())[1:]] == [
+        ("embed_dims", 256), ("include_opa", True), ("semantics", False), ("semantic_dim", None)]
+    m = SparseGaussian3DEncoder(embed_dims=16)
+    assert m.semantic_dim == 0 and not hasattr(m, "semantics_fc") and hasattr(m, "opacity_fc")
+    assert not hasattr(SparseGaussian3DEncoder(embed_dims=16, include_opa=False), "opacity_fc")
+
+
+@pytest.mark.parametrize("name", FAMILIES)
+def test_cpu_route_is_torch_and_meets_the_truth_with_its_gradients(name, monkeypatch):
+    """Per tensor: |value - truth| <= 2 max|reference fp32 - truth| + 4 eps32 max|truth|.  The yardstick is the reference's own
+    float32 result recorded in the fixture: the output, the input's gradient and every parameter's gradient but the seven square
+    weights' (those alone would be 1.4 MB of fixture).  A square weight's yardstick is the float32 restatement's gradient -- the
+    composition a user of the reference runs today, whose forward and other gradients the fixture pins."""
+    cfg, opa, S, g = _family(name)
+    monkeypatch.setattr(anchor_encoder._lib, "call", lambda *a, **k: pytest.fail("the CPU route called the library"))
+    seed = int(g["seed"])
+    module = SparseGaussian3DEncoder(embed_dims=128, **cfg)
+    module.load_state_dict(ref.fixed_weights(opa, S, seed=seed), strict=True)
+    x = torch.from_numpy(g["input"]).requires_grad_(True)
+    out = module(x)
+    w = ref.output_weights(out.shape)
+    (out * w.float()).sum().backward()
+
+    def grads(dtype):
+        sd = {k: v.requires_grad_(True) for k, v in ref.fixed_weights(opa, S, seed=seed, dtype=dtype).items()}
+        xi = torch.from_numpy(g["input"]).to(dtype).requires_grad_(True)
+        o = ref.anchor_embed_ref(xi, sd)
+        (o * w.to(dtype)).sum().backward()
+        return o.detach(), {"input": xi.grad, **{k: v.grad for k, v in sd.items()}}
+
+    _, g64 = grads(torch.float64)
+    _, g32 = grads(torch.float32)
+
+    def held(what, got, truth, yard):
+        truth = truth.double()
+        bound = 2 * (yard.double() - truth).abs().max().item() + 4 * EPS32 * truth.abs().max().item()
+        err = (got.double() - truth).abs().max().item()
+        assert err <= bound, (what, err, bound)
+
+    held("output", out.detach(), torch.from_numpy(g["out64"]), torch.from_numpy(g["out32"]))
+    def yard(k):
+        key = f"{name}.grad32.{k}"
+        recorded = key in GOLDEN.files
+        assert recorded == (tuple(g64[k].shape) != (128, 128)), k
+        return torch.from_numpy(GOLDEN[key]) if recorded else g32[k]
+
+    held("input", x.grad, g64["input"], yard("input"))
+    named = dict(module.named_parameters())
+    assert set(named) == set(g64) - {"input"}
+    for k, p in named.items():
+        assert p.grad is not None, k
+        held(k, p.grad, g64[k], yard(k))
+
+
+def test_anchor_embed_refuses_a_cpu_tensor():
+    module = SparseGaussian3DEncoder(embed_dims=128)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        with torch.no_grad():
+            anchor_embed(torch.zeros(4, 11), module)
+
+
+def test_anchor_embed_refuses_autograd():
+    """A forward without a backward must not hand autograd a result that silently carries no gradient.  The refusal comes
+    before the device check, so it is tested here."""
+    module = SparseGaussian3DEncoder(embed_dims=128)
+    with pytest.raises(RuntimeError, match="without a native backward"):
+        anchor_embed(torch.zeros(4, 11), module)                       # the parameters require grad
+    for p in module.parameters():
+        p.requires_grad_(False)
+    with pytest.raises(RuntimeError, match="without a native backward"):
+        anchor_embed(torch.zeros(4, 11, requires_grad=True), module)   # the input does
