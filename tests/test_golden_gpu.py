@@ -7,7 +7,10 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from util import assert_grad_close, assert_logits_close, hip_splat_backward, hip_splat_forward, to_dev
+import oracle
+
+from util import (GRAD_RTOL, assert_grad_close, assert_grad_rows_close, assert_logits_close, assert_prob_grad_rows_close,
+                  hip_splat_backward, hip_splat_forward, print_grad_rows, splat_truth_grads, to_dev, whole_grid_rows)
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -24,6 +27,14 @@ def test_splat_matches_reference_fixture(gpu, name):
                          semantics=d["semantics"], H=int(d["H"]), W=int(d["W"]), D=int(d["D"]))
     pi, mi, radii, cov6 = d["points_int"], d["means_int"], d["radii"], d["cov6"]
     prob = si.variant == "prob"
+    whole = whole_grid_rows(mi, radii, si.H, si.W, si.D)
+    if prob:   # the fixture's own gradients cancel in fp32 like any: float64 truth, the oracle's error on the row as the yardstick
+        og = oracle.splat_backward("prob", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D,
+                                   d["out_grad"], bin_grad=d["bin_grad"], density_grad=d["density_grad"],
+                                   fwd=oracle.splat_forward("prob", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii,
+                                                            cov6, si.H, si.W, si.D))
+        truth = splat_truth_grads(si, pi, mi, radii, cov6, d["out_grad"], d["bin_grad"], d["density_grad"])
+    print()
     # default flags (base variant on the dense grid: the matrix-core kernel, north_star's 1e-4 bound), the exact-fp32
     # tile kernel and the arbitrary-points kernel (both 1e-5)
     for flags, tol in ((0, 1e-5 if prob else 1e-4), (_lib.GF_EXACT_FP32, 1e-5), (_lib.GF_PTS_GENERAL, 1e-5)):
@@ -34,6 +45,12 @@ def test_splat_matches_reference_fixture(gpu, name):
                                    d["density_grad"] if prob else None, flags=flags)
         for k, g in zip(("means3D_grad", "opacity_grad", "semantics_grad", "cov3D_grad"), grads):
             assert_grad_close(g, d[k], what=f"{name}: {k} vs reference fixture", rtol=1e-4)
+        for i, (k, g) in enumerate(zip(("means3D_grad", "opacity_grad", "semantics_grad", "cov3D_grad"), grads)):
+            if prob:
+                assert_prob_grad_rows_close(g, truth[i], og[i], what=f"{name}: {k} vs float64 (flags {flags})")
+            else:
+                print_grad_rows(f"{name}: {k} vs fixture (flags {flags})",
+                                assert_grad_rows_close(g, d[k], whole, what=f"{name}: {k} vs reference fixture", rtol=GRAD_RTOL))
     vols, R = splat_box_volumes(torch.from_numpy(mi).to(gpu), torch.from_numpy(radii).to(gpu), si.H, si.W, si.D)
     assert R == int(d["num_rendered"]) and np.array_equal(vols.cpu().numpy().astype(np.uint32), d["tiles_touched"])
 

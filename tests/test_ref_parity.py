@@ -8,7 +8,8 @@ Two things are pinned here:
    list of ``duplicateWithKeys`` and the radix-sorted per-voxel lists), values and gradients within the
    rounding of a different FMA contraction;
 2. the HIP product path, through the C ABI, directly against the reference: integer outputs bit-exact,
-   logits ``|err| <= 1e-4 * max(1, |ref|)``, gradients ``<= 1e-3`` of the tensor's largest magnitude —
+   logits ``|err| <= 1e-4 * max(1, |ref|)``, gradients ``<= 1e-3`` of the tensor's largest magnitude and, base variant,
+   of every Gaussian's own row (prob: row by row against float64 autograd, the reference held to the same bound) —
    small shapes with the edge cases and all three BASELINE shapes at full size.
 """
 import numpy as np
@@ -18,8 +19,9 @@ import oracle
 from oracle import ref
 from gaussianformer_amd.synthetic import make_daf_inputs, make_splat_inputs
 
-from util import (assert_grad_close, assert_grad_rows_close, assert_logits_abs, assert_logits_close, grad_row_errors,
-                  hip_splat_backward, hip_splat_forward, prep, to_dev, whole_grid_rows)
+from util import (GRAD_RTOL, assert_grad_close, assert_grad_rows_close, assert_logits_abs, assert_logits_close,
+                  assert_prob_grad_rows_close, grad_row_errors, hip_splat_backward, hip_splat_forward, prep, print_grad_rows,
+                  prob_row_errors, splat_truth_grads, to_dev, whole_grid_rows)
 
 pytestmark = pytest.mark.gpu
 
@@ -145,6 +147,16 @@ def test_oracle_daf_vs_reference(reflib):
 # 2. the HIP path against the reference
 # ------------------------------------------------------------------------------------------------
 
+def _rows_vs_ref(si, per_axis, grads, rgrads, what):
+    """Every Gaussian's gradient row against the reference's, by its own magnitude (tests/util.py); printed."""
+    _, mi, radii, _ = prep(si, per_axis)
+    whole = whole_grid_rows(mi, radii, si.H, si.W, si.D)
+    print()
+    for name, a, b in zip(GRAD_NAMES, grads, rgrads):
+        print_grad_rows(f"HIP {name} vs reference ({what})",
+                        assert_grad_rows_close(a, b, whole, what=f"HIP {name} vs reference ({what})", rtol=GRAD_RTOL))
+
+
 def _hip_vs_ref(gpu, reflib, si, per_axis, seed, flags=0, logit_tol=1e-4):
     pi, mi, radii, cov6 = prep(si, per_axis)
     g, gb, gd = _rand_grads(si, seed)
@@ -173,6 +185,35 @@ def test_hip_small_vs_reference(gpu, reflib, config, P, H, W, D, per_axis):
         if prob and not np.isfinite(b).all():
             continue
         assert_grad_close(a, b, what=f"HIP {name} vs reference", rtol=1e-3)
+    if not prob:
+        _rows_vs_ref(si, per_axis, grads, rgrads, f"{config} P={P} {H}x{W}x{D}")
+        return
+    # prob: the reference's fp32 quadratic form cancels like any other, so the truth is float64 autograd and the yardstick the
+    # oracle's own error on the row (tests/util.py); the reference is held to the same bound as the HIP path.  Seed 47 does not
+    # qualify for that judgement by the oracle alone -- oracle vs float64 there: means3D tensor-wide 3.9e-2 (scalar radii) and
+    # 1.4e-2 (per-axis), past the sweep's 1e-2; rows on the fp32 term 15.8 / 61.7 / 65.0 / 11.7 % and 5.8 / 35.0 / 30.0 / 4.2 % --
+    # so its rows are printed, and the rows that are judged are those of test_backward_small's input (seeds 11 / 12), which
+    # tests/test_grad_rows_judge.py pins on the CPU: at most 2.5 % of its rows on the fp32 term.
+    for seed, gseed, judged in ((47, 48, False), (11, 12, True)):
+        sj = make_splat_inputs(config, seed=seed, P=P, H=H, W=W, D=D)
+        pi, mi, radii, cov6 = prep(sj, per_axis)
+        g, gb, gd = _rand_grads(sj, gseed)
+        if judged:
+            _, rgrads, _ = reflib.splat_forward_backward(*_args(sj, pi, mi, radii, cov6), g, gb, gd)
+            _, t, state, fwd_t = hip_splat_forward(gpu, sj, pi, mi, radii, cov6)
+            grads = hip_splat_backward(gpu, sj, t, state, fwd_t, g, gb, gd)
+        ograds = oracle.splat_backward(*_args(sj, pi, mi, radii, cov6), g, fwd=oracle.splat_forward(*_args(sj, pi, mi, radii, cov6)),
+                                       bin_grad=gb, density_grad=gd)
+        print()
+        for name, a, b, o, tr in zip(GRAD_NAMES, grads, rgrads, ograds, splat_truth_grads(sj, pi, mi, radii, cov6, g, gb, gd)):
+            for who, x in (("HIP", a), ("reference", b)):
+                what = f"{who} {name} vs float64 (seed {seed}, per_axis={per_axis})"
+                if judged:
+                    assert_prob_grad_rows_close(x, tr, o, what=what)
+                elif np.isfinite(o).all():
+                    e = prob_row_errors(x, tr, o, GRAD_RTOL)
+                    print(f"  {what:40s} NOT JUDGED: worst row {e['row']}: err / bound {e['ratio']:.3f} ({e['term']}), rows on the "
+                          f"fp32 term {e['fp32_rows']} ({e['fp32_share']:.3f})")
 
 
 def test_hip_arbitrary_points_vs_reference(gpu, reflib):
@@ -185,6 +226,7 @@ def test_hip_arbitrary_points_vs_reference(gpu, reflib):
     rf, rgrads, grads, _ = _hip_vs_ref(gpu, reflib, si, False, 52)
     for name, a, b in zip(GRAD_NAMES, grads, rgrads):
         assert_grad_close(a, b, what=f"HIP {name} vs reference")
+    _rows_vs_ref(si, False, grads, rgrads, "arbitrary points")
 
 
 def test_hip_edge_cases_vs_reference(gpu, reflib):
@@ -193,12 +235,14 @@ def test_hip_edge_cases_vs_reference(gpu, reflib):
     rf, rgrads, grads, _ = _hip_vs_ref(gpu, reflib, si, False, 54)
     for name, a, b in zip(GRAD_NAMES, grads, rgrads):
         assert_grad_close(a, b, what=f"HIP {name} vs reference (empty Gaussian only)")
+    _rows_vs_ref(si, False, grads, rgrads, "empty Gaussian only")
     # centres outside the grid: the wrapper asserts (local_aggregate/__init__.py:140); the kernels clip like getRect
     si = make_splat_inputs("nuscenes_gs25600_solid", seed=55, P=100, H=16, W=16, D=8)
     si.means3D[:50] += np.float32(3.0)
     rf, rgrads, grads, _ = _hip_vs_ref(gpu, reflib, si, False, 56)
     for name, a, b in zip(GRAD_NAMES, grads, rgrads):
         assert_grad_close(a, b, what=f"HIP {name} vs reference (outside centres)")
+    _rows_vs_ref(si, False, grads, rgrads, "outside centres")
     # membership: Sigma^-1 = 0, opacity = semantics = 1 -> logits are integer Gaussian counts, bit-exact
     si = make_splat_inputs("nuscenes_gs25600_solid", seed=57, P=2000, H=40, W=36, D=16)
     pi, mi, radii, cov6 = prep(si)

@@ -6,10 +6,13 @@ import pytest
 import oracle
 from gaussianformer_amd.synthetic import make_splat_inputs
 
-from util import (assert_grad_close, assert_grad_rows_close, assert_logits_abs, assert_logits_close, hip_splat_backward, hip_splat_forward, prep,
-                  whole_grid_rows)
+from util import (GRAD_RTOL, assert_grad_close, assert_grad_rows_close, assert_logits_abs, assert_logits_close,
+                  assert_prob_grad_rows_close, grad_row_errors, hip_splat_backward, hip_splat_forward, prep, print_grad_rows,
+                  splat_truth_grads, whole_grid_rows)
 
 pytestmark = pytest.mark.gpu
+
+GRAD_NAMES = ("means3D_grad", "opacity_grad", "semantics_grad", "cov3D_grad")
 
 SMALL = [
     # config, P, H, W, D, per_axis
@@ -175,8 +178,19 @@ def test_backward_small(gpu, config, P, H, W, D, per_axis):
                                 si.H, si.W, si.D, g, fwd=fwd, bin_grad=gb, density_grad=gd)
     _, t, state, fwd_t = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
     got = hip_splat_backward(gpu, si, t, state, fwd_t, g, gb, gd)
-    for name, a, b in zip(("means3D_grad", "opacity_grad", "semantics_grad", "cov3D_grad"), got, ref):
+    for name, a, b in zip(GRAD_NAMES, got, ref):
         assert_grad_close(a, b, what=name)
+    # row by row: every Gaussian against its own magnitude (tests/util.py) -- the base variant against the oracle, the prob
+    # variant (whose fp32 quadratic form cancels, in the oracle as in any fp32 evaluation) against float64 autograd with the
+    # oracle's own error on the row as the yardstick
+    print()
+    if si.variant == "prob":
+        for name, a, b, tr in zip(GRAD_NAMES, got, ref, splat_truth_grads(si, pi, mi, radii, cov6, g, gb, gd)):
+            assert_prob_grad_rows_close(a, tr, b, what=f"{name} [{config} per_axis={per_axis}]")
+    else:
+        whole = whole_grid_rows(mi, radii, si.H, si.W, si.D)
+        for name, a, b in zip(GRAD_NAMES, got, ref):
+            print_grad_rows(f"{name} [{config} P={P} {H}x{W}x{D}]", assert_grad_rows_close(a, b, whole, what=name, rtol=GRAD_RTOL))
 
 
 def test_backward_arbitrary_points(gpu):
@@ -189,8 +203,45 @@ def test_backward_arbitrary_points(gpu):
                                 si.H, si.W, si.D, g)
     _, t, state, fwd_t = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
     got = hip_splat_backward(gpu, si, t, state, fwd_t, g)
-    for name, a, b in zip(("means3D_grad", "opacity_grad", "semantics_grad", "cov3D_grad"), got, ref):
+    whole = whole_grid_rows(mi, radii, si.H, si.W, si.D)
+    print()
+    for name, a, b in zip(GRAD_NAMES, got, ref):
         assert_grad_close(a, b, what=name)
+        print_grad_rows(f"{name} [arbitrary points]", assert_grad_rows_close(a, b, whole, what=name, rtol=GRAD_RTOL))
+
+
+@pytest.mark.parametrize("per_axis", [False, True])
+def test_backward_arbitrary_points_prob(gpu, per_axis):
+    """The prob variant's backward (localagg_prob / localagg_prob_fast) on random query points: several per voxel, only the
+    highest-index point of a voxel feeds the gradient (voxel2pts), most voxels empty; with bin_grad and density_grad.  Judged row
+    by row against float64 autograd with the oracle's own error on the row as the yardstick (tests/util.py).
+
+    The seed is the first from 37 on at which the oracle ALONE qualifies for both radius flavours (chosen on the CPU, no HIP result
+    involved; 37, 38 do not, 39, 42 and 45 do): its forward is finite, each of its gradients is within 1e-2 of the truth
+    tensor-wide (the sweep's criterion) and at most 5 % of the rows are on the fp32 term.  Seed 39 (gradients: seed 40), P = 120,
+    oracle vs float64, (means3D, opacity, semantics, cov3D):
+      scalar radii    tensor-wide 4.0e-5, 9.9e-5, 2.6e-4, 5e-6; rows on the fp32 term 1.7 %, 0.8 %, 0.8 %, 0
+      per-axis radii  tensor-wide 4.4e-5, 5.7e-5, 1.0e-4, 5e-6; rows on the fp32 term 0.8 %, 2.5 %, 0.8 %, 0"""
+    si = make_splat_inputs("prob_gs6400", seed=39, P=120, H=20, W=24, D=16, dense_pts=False, N=5000)
+    pi, mi, radii, cov6 = prep(si, per_axis)
+    rng = np.random.default_rng(40)
+    N = si.pts.shape[0]
+    g = rng.standard_normal((N, 18)).astype(np.float32)
+    gb = rng.standard_normal(N).astype(np.float32)
+    gd = rng.standard_normal(N).astype(np.float32)
+    fwd = _oracle_fwd(si, pi, mi, radii, cov6)
+    assert all(np.isfinite(v).all() for v in fwd.values() if isinstance(v, np.ndarray))
+    ref = oracle.splat_backward("prob", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6,
+                                si.H, si.W, si.D, g, fwd=fwd, bin_grad=gb, density_grad=gd)
+    truth = splat_truth_grads(si, pi, mi, radii, cov6, g, gb, gd)
+    for name, b, tr in zip(GRAD_NAMES, ref, truth):     # the oracle qualifies (the figures of the docstring)
+        assert np.isfinite(b).all() and np.abs(b - tr).max() <= 1e-2 * max(np.abs(tr).max(), 1e-6), name
+    got_f, t, state, fwd_t = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
+    _check_fwd(got_f, fwd, "prob", _truth(si, pi, mi, radii, cov6))
+    got = hip_splat_backward(gpu, si, t, state, fwd_t, g, gb, gd)
+    print()
+    for name, a, b, tr in zip(GRAD_NAMES, got, ref, truth):
+        assert_prob_grad_rows_close(a, tr, b, what=f"{name} [prob, arbitrary points, per_axis={per_axis}]")
 
 
 def test_module_autograd_matches_oracle(gpu):
@@ -217,6 +268,11 @@ def test_module_autograd_matches_oracle(gpu):
     assert_grad_close(sem.grad[0].cpu().numpy(), rg[2], "semantics.grad")
     cg = cov.grad[0].cpu().numpy().reshape(-1, 9)
     assert_grad_close(cg[:, [0, 4, 8, 1, 5, 2]], rg[3], "cov3D.grad (packed entries)")
+    whole = whole_grid_rows(mi, radii, si.H, si.W, si.D)
+    print()
+    for name, a, b in zip(("means3D.grad", "opacities.grad", "semantics.grad", "cov3D.grad (packed entries)"),
+                          (means.grad[0].cpu().numpy(), opa.grad[0].cpu().numpy(), sem.grad[0].cpu().numpy(), cg[:, [0, 4, 8, 1, 5, 2]]), rg):
+        print_grad_rows(f"{name} [module]", assert_grad_rows_close(a, b, whole, what=name, rtol=GRAD_RTOL))
     assert np.abs(cg[:, [3, 6, 7]]).max() == 0.0  # lower triangle receives nothing
 
 
@@ -304,31 +360,19 @@ def test_backward_channel_major_gradient(gpu):
         else:
             logits.backward(wgt[0].t().contiguous())
         grads.append([t.grad.clone() for t in (means, opa, sem, cov)])
-    for a, b in zip(*grads):
+    pi, mi, radii, cov6 = prep(si)
+    whole = whole_grid_rows(mi, radii, si.H, si.W, si.D)
+    print()
+    for name, a, b in zip(GRAD_NAMES, *grads):
         assert torch.allclose(a, b, rtol=1e-5, atol=1e-6 * float(b.abs().max()))
-
-
-def _truth_grads(si, pi, mi, radii, cov6, g, gb, gd):
-    """fp64 autograd gradients of the dense formulation (small cases).  With several points per
-    voxel only the highest-index point of a voxel feeds the backward (voxel2pts)."""
-    import torch
-    from oracle import dense_ref
-    t = lambda a, grad=False: torch.tensor(a, dtype=torch.float64, requires_grad=grad)
-    key = (pi[:, 0].astype(np.int64) * si.W + pi[:, 1]) * si.D + pi[:, 2]
-    last = {}
-    for n, k in enumerate(key):
-        last[int(k)] = n
-    winner = np.zeros(len(key))
-    winner[list(last.values())] = 1.0
-    m, o, s, c = t(si.means3D, True), t(si.opacities, True), t(si.semantics, True), t(cov6, True)
-    out = dense_ref.splat_dense(si.variant, t(si.pts), torch.tensor(pi), m, torch.tensor(mi), o, s, torch.tensor(radii), c,
-                                si.H, si.W, si.D)
-    w = t(winner)
-    if si.variant == "prob":
-        ((out[0] * t(g) * w[:, None]).sum() + (out[1] * t(gb) * w).sum() + (out[2] * t(gd) * w).sum()).backward()
-    else:
-        (out * t(g) * w[:, None]).sum().backward()
-    return [x.grad.numpy() for x in (m, o, s, c)]
+        # ... and row by row: |a - b| <= 1e-6 * max|row| + 1e-5 * |b|, the row's maximum floored at the median ordinary row's
+        a2, b2 = (x[0].reshape(b.shape[1], -1).double().cpu().numpy() for x in (a, b))
+        rowmax = np.abs(b2).max(axis=1)
+        floor = float(np.median(rowmax[~whole]))
+        excess = np.abs(a2 - b2) - (1e-6 * np.maximum(rowmax, floor)[:, None] + 1e-5 * np.abs(b2))
+        e = grad_row_errors(a2, b2, whole)
+        print_grad_rows(f"{name} [transposed vs contiguous gradient]", e)
+        assert excess.max() <= 0.0, (name, int(excess.max(axis=1).argmax()), float(excess.max()))
 
 
 def test_random_shapes_sweep(gpu):
@@ -339,6 +383,8 @@ def test_random_shapes_sweep(gpu):
     path and the oracle are judged against fp64 autograd instead of against each other."""
     import os
     rng = np.random.default_rng(int(os.environ.get("GF_SWEEP_SEED", "2025")))
+    fwd_skipped, prob_trials, grad_skipped = [], 0, []        # what the sweep did NOT check: counted, printed, bounded
+    print()
     for trial in range(int(os.environ.get("GF_SWEEP_TRIALS", "14"))):
         config = ["nuscenes_gs25600_solid", "nuscenes_gs144000", "prob_gs6400"][trial % 3]
         prob = config == "prob_gs6400"
@@ -356,6 +402,7 @@ def test_random_shapes_sweep(gpu):
             # prob config, scales down to 0.01 m: det(Sigma^-1) can round to a negative fp32 and
             # the reference's powf(deter, 0.5) (localagg_prob/src/forward.cu:78) is then NaN --
             # no defined result to compare against
+            fwd_skipped.append(trial)
             continue
         got, t, state, fwd_t = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
         try:
@@ -367,20 +414,30 @@ def test_random_shapes_sweep(gpu):
             refg = oracle.splat_backward(si.variant, si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6,
                                          si.H, si.W, si.D, g, fwd=ref, bin_grad=gb, density_grad=gd)
             gotg = hip_splat_backward(gpu, si, t, state, fwd_t, g, gb, gd)
-            names = ("means3D_grad", "opacity_grad", "semantics_grad", "cov3D_grad")
+            names = GRAD_NAMES
             if not prob:
+                whole = whole_grid_rows(mi, radii, si.H, si.W, si.D)
                 for name, a, b in zip(names, gotg, refg):
                     assert_grad_close(a, b, what=name)
+                    print_grad_rows(f"trial {trial} {name} [{config} P={P} {H}x{W}x{D} dense={dense}]",
+                                    assert_grad_rows_close(a, b, whole, what=name, rtol=GRAD_RTOL))
             else:
-                for name, a, b, tr in zip(names, gotg, refg, _truth_grads(si, pi, mi, radii, cov6, g, gb, gd)):
+                prob_trials += 1
+                for name, a, b, tr in zip(names, gotg, refg, splat_truth_grads(si, pi, mi, radii, cov6, g, gb, gd)):
                     scale = max(np.abs(tr).max(), 1e-6)
                     e_orc = np.abs(b - tr).max() / scale
-                    if not np.isfinite(b).all() or e_orc > 1e-2:
+                    if not np.isfinite(b).all() or e_orc > 1e-2:    # (reads the oracle and the truth only)
+                        grad_skipped.append((trial, name))
                         continue  # the reference's own fp32 formula breaks down on this input
                     e_hip = np.abs(a - tr).max() / scale
                     assert e_hip <= max(3 * e_orc, 1e-3), f"{name}: HIP err {e_hip:.2e}, oracle err {e_orc:.2e} (vs fp64)"
         except AssertionError as e:
             raise AssertionError(f"trial {trial}: {config} P={P} grid {H}x{W}x{D} per_axis={per_axis} dense={dense}: {e}")
+    print(f"  sweep: forward not compared in trials {fwd_skipped} (oracle not finite); prob gradient tensors not compared: "
+          f"{len(grad_skipped)} of {4 * prob_trials} {grad_skipped}")
+    # default seed, 14 trials: 4 of 16, all in trial 2 (P=13, 21x14x8, arbitrary points -- test_backward_arbitrary_points_prob
+    # covers that path on an input the oracle can judge)
+    assert 4 * len(grad_skipped) <= 4 * prob_trials, f"the sweep skipped {len(grad_skipped)} of {4 * prob_trials} prob gradient tensors: {grad_skipped}"
 
 
 def test_forward_pipeline_two_streams(gpu):

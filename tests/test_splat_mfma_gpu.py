@@ -8,7 +8,17 @@ import torch
 import oracle
 from gaussianformer_amd.synthetic import make_splat_inputs
 
-from util import assert_logits_close, hip_splat_forward, prep
+from util import GRAD_RTOL, assert_grad_rows_close, assert_logits_close, hip_splat_forward, prep, print_grad_rows, whole_grid_rows
+
+GRAD_NAMES = ("means3D_grad", "opacity_grad", "semantics_grad", "cov3D_grad")
+
+
+def _rows_close(got, ref, whole, what):
+    """Every Gaussian's gradient row against its own magnitude (tests/util.py), next to the tensor-wide bounds; printed."""
+    print()
+    for name, a, b in zip(GRAD_NAMES, got, ref):
+        a, b = np.asarray(a), np.asarray(b)
+        print_grad_rows(f"{name} [{what}]", assert_grad_rows_close(a, b.reshape(a.shape), whole, what=f"{name} [{what}]", rtol=GRAD_RTOL))
 
 pytestmark = pytest.mark.gpu
 
@@ -224,6 +234,9 @@ def test_mfma_module_keyword_and_autograd(gpu):
         # matrix-core backward after the matrix-core forward (~1e-5 of the tensor's maximum apart; the bound against the
         # reference is 1e-3)
         assert float((a - b).abs().max()) <= 1e-4 * float(a.abs().max())
+    _, mi, radii, _ = prep(si)
+    _rows_close([x[0].cpu().numpy() for x in grads[1]], [x[0].cpu().numpy() for x in grads[0]],
+                whole_grid_rows(mi, radii, si.H, si.W, si.D), "matrix-core module vs exact module")
 
 
 # ---- round 4: the verdicts of the records pass (every call) and inputs at the edge of what stays on the matrix cores
@@ -415,6 +428,7 @@ def test_backward_takes_the_forward_records_when_the_workspace_still_holds_them(
     ref = oracle.splat_backward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D, g)
     for a, b in zip(base, ref):
         assert np.abs(a - b.reshape(a.shape)).max() <= 1e-4 * max(np.abs(b).max(), 1e-30)
+    _rows_close(base, ref, whole_grid_rows(mi, radii, si.H, si.W, si.D), "records of the forward, P=1500 40x36x16")
     again = _bwd(gpu, si, t, state, g)                                   # a second backward of the same forward
     asserted = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
     for a, b, c, d in zip(base, again, asserted, plain):
@@ -463,6 +477,7 @@ def test_backward_after_a_prepared_forward_on_a_grid_of_few_workgroups(gpu, shap
         for a, b in zip(got, ref):
             assert np.isfinite(a).all()
             assert np.abs(a - b.reshape(a.shape)).max() <= 2e-4 * max(np.abs(b).max(), 1e-30)
+        _rows_close(got, ref, whole_grid_rows(mi, radii, H, W, D), f"few workgroups {shape}, forward flags {fflags}")
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
 
@@ -494,6 +509,7 @@ def test_backward_rows_of_whole_grid_gaussians_and_of_a_full_buffer(gpu, case):
         for a, b in zip(got, ref):
             assert np.isfinite(a).all()
             assert np.abs(a - b.reshape(a.shape)).max() <= 2e-4 * max(np.abs(b).max(), 1e-30)
+        _rows_close(got, ref, whole_grid_rows(mi, radii, si.H, si.W, si.D), f"{case}, forward flags {fflags}")
 
 
 @pytest.mark.gpu
@@ -521,6 +537,7 @@ def test_backward_when_a_supertile_has_more_candidates_than_a_published_list_hol
     for a, b, c in zip(got, plain, ref):
         assert np.isfinite(a).all() and np.array_equal(a, b)
         assert np.abs(a - c.reshape(a.shape)).max() <= 2e-4 * max(np.abs(c).max(), 1e-30)
+    _rows_close(got, ref, whole_grid_rows(mi, radii, si.H, si.W, si.D), "unpublished candidate list, P=2000 40x40x16")
 
 
 @pytest.mark.gpu

@@ -6,7 +6,20 @@ used at the BASELINE shapes against oracle/_ref); gradients <= 1e-3 -- ``assert_
 relative to the tensor's largest magnitude (small shapes), ``assert_grad_rows_close`` ROW BY ROW
 (every Gaussian against its own magnitude, with a floor taken from the ordinary rows and the
 whole-grid "empty" Gaussian, gaussian_head.py:90-102, judged separately: at nuscenes_gs25600_solid
-its row is 1e4 times an ordinary one and would make a tensor-wide scale vacuous)."""
+its row is 1e4 times an ordinary one and would make a tensor-wide scale vacuous).
+
+The small-shape tests (the kernels' layout edges) judge ROW BY ROW as well, next to their tensor-wide lines: with the whole-grid
+Gaussian present the tensor-wide 1e-3 let EVERY ordinary Gaussian's cov3D_grad row be zero (tests/test_grad_rows_judge.py pins
+that on the CPU, and pins the oracle to float64 autograd row by row: worst ordinary row 6.7e-6, worst whole-grid row 6.5e-5).
+Row by row a zeroed row passes only if its magnitude is below 1e-3 of the median row's.  Measured on an MI355X over every touched
+small-shape test (profiles/parity_rows_small.txt): worst ordinary row 7.3e-5, worst whole-grid row 9.0e-5, bound 1e-3.
+
+The prob variant's fp32 quadratic form cancels (terms ~1e3 to a result ~1e0), in the oracle as in every fp32 evaluation: on the
+``SMALL`` prob inputs the oracle's own worst row is 6.4e-3 from the truth.  Its rows are therefore judged against float64 autograd of
+oracle/dense_ref.splat_dense (``splat_truth_grads``) by ``assert_prob_grad_rows_close``: row r within max(1e-3 * max(|truth_r|,
+median row), 4 * the oracle's own error on r), and at most 5 % of the rows on the second term -- a share computed from the oracle
+and the truth alone, so an input on which fp32 breaks down fails the test instead of excusing the kernel (measured: at most 2.5 %
+of the rows, HIP error / bound at most 0.251)."""
 import numpy as np
 
 import oracle
@@ -149,6 +162,88 @@ def assert_daf_rows_close(got, ref, ref32, what, row_dims, rtol=GRAD_RTOL, touch
     assert e["ratio"] <= 1.0, (f"{what}: row {e['row']}: err {e['err']:.3e} > bound {e['bound']:.3e} ({e['term']}) "
                                f"= max({rtol:g} x max(|ref row|, floor {e.get('floor', 0):.3e}), 4 x fp32 restatement's error)")
     return e
+
+
+PROB_FP32_SHARE_CAP = 0.05
+
+
+def prob_row_errors(got, truth, oracle32, rtol):
+    """Row-by-row error record of a prob-variant splat gradient against its float64 truth (:func:`splat_truth_grads`), with the
+    fp32 restatement ``oracle32`` (oracle.splat_backward on the same inputs) as the yardstick of plain float32 arithmetic -- the
+    idiom of :func:`daf_row_errors` on numpy arrays, one row per Gaussian.  Row r is bounded by
+    max(rtol * max(max|truth_r|, floor), 4 * max|oracle32_r - truth_r|), floor = the median of max|truth_r|.  A row on which the
+    restatement itself is not finite has no bound (infinite) and counts as a row on the fp32 term.  ``fp32_share`` = the share
+    of rows whose bound came from the fp32 term: it reads the restatement and the truth only, never ``got``."""
+    got, truth, oracle32 = (np.asarray(a, dtype=np.float64) for a in (got, truth, oracle32))
+    P = truth.shape[0]
+    g2, t2, o2 = got.reshape(P, -1), truth.reshape(P, -1), oracle32.reshape(P, -1)
+    out = {"rows": P, "ratio": 0.0, "row": -1, "err": 0.0, "bound": 0.0, "rel": 0.0, "term": "-", "fp32_rel": 0.0,
+           "fp32_share": 0.0, "fp32_rows": 0, "floor": 0.0, "tensor": 0.0}
+    if P == 0:
+        return out
+    rowmax = np.abs(t2).max(axis=1)
+    defined = np.isfinite(o2).all(axis=1)
+    err32 = np.where(defined, np.abs(np.where(np.isfinite(o2), o2, 0.0) - t2).max(axis=1), np.inf)
+    floor = max(float(np.median(rowmax)), 1e-30)
+    scale = np.maximum(rowmax, floor)
+    tol_term, f32_term = rtol * scale, 4.0 * err32
+    on_fp32 = f32_term > tol_term
+    bound = np.maximum(tol_term, f32_term)
+    with np.errstate(invalid="ignore"):
+        err = np.where(defined, np.abs(g2 - t2).max(axis=1), 0.0)
+    err = np.where(np.isnan(err), np.inf, err)           # a non-finite result on a row the restatement defines
+    ratio = err / bound
+    i = int(ratio.argmax())
+    out.update(floor=floor, ratio=float(ratio[i]), row=i, err=float(err[i]), bound=float(bound[i]),
+               rel=float((err / scale).max()), fp32_rel=float((err32[defined] / scale[defined]).max()) if defined.any() else 0.0,
+               term="fp32" if on_fp32[i] else f"{rtol:g} x row", fp32_share=float(on_fp32.mean()), fp32_rows=int(on_fp32.sum()),
+               tensor=float(err.max() / max(rowmax.max(), 1e-30)))
+    return out
+
+
+def assert_prob_grad_rows_close(got, truth, oracle32, what="grad", rtol=GRAD_RTOL, cap=PROB_FP32_SHARE_CAP):
+    """:func:`prob_row_errors`, printed and asserted: every row within its bound, and at most ``cap`` of the rows on the fp32 term
+    (so the fp32 term cannot quietly become the whole check).  Returns the record."""
+    assert np.asarray(got).shape == np.asarray(truth).shape == np.asarray(oracle32).shape, \
+        (what, np.asarray(got).shape, np.asarray(truth).shape, np.asarray(oracle32).shape)
+    e = prob_row_errors(got, truth, oracle32, rtol)
+    print(f"  {what:40s} rows {e['rows']:>5d} worst row {e['row']:>5d}: err {e['err']:.2e} <= bound {e['bound']:.2e} ({e['term']}), "
+          f"ratio {e['ratio']:.3f} | max row err / max(|truth row|, floor) {e['rel']:.2e} (fp32 restatement {e['fp32_rel']:.2e}) | "
+          f"rows on the fp32 term {e['fp32_rows']} ({e['fp32_share']:.3f}) | tensor-wide {e['tensor']:.2e}")
+    assert e["fp32_share"] <= cap, (f"{what}: {e['fp32_rows']} of {e['rows']} rows ({e['fp32_share']:.3f}) are judged by the fp32 "
+                                    f"restatement's own error, more than {cap:g}")
+    assert e["ratio"] <= 1.0, (f"{what}: row {e['row']}: err {e['err']:.3e} > bound {e['bound']:.3e} ({e['term']}) "
+                               f"= max({rtol:g} x max(|truth row|, floor {e['floor']:.3e}), 4 x fp32 restatement's error)")
+    return e
+
+
+def print_grad_rows(what, e):
+    """One line of a row-by-row record of :func:`assert_grad_rows_close` (the figures of profiles/parity_rows_small.txt)."""
+    print(f"  {what:40s} worst ordinary row {e['ordinary']:.2e} (row {e['worst_row']}, floor {e['floor']:.2e}, absolute "
+          f"{e['abs']:.2e}) | whole-grid row {e['whole_grid']:.2e} | tensor-wide {e['tensor']:.2e}")
+
+
+def splat_truth_grads(si, pi, mi, radii, cov6, g, gb=None, gd=None):
+    """fp64 autograd gradients of the dense formulation oracle/dense_ref.splat_dense (small cases: O(N P) work).  With several
+    points per voxel only the highest-index point of a voxel feeds the backward (voxel2pts)."""
+    import torch
+    from oracle import dense_ref
+    t = lambda a, grad=False: torch.tensor(a, dtype=torch.float64, requires_grad=grad)
+    key = (pi[:, 0].astype(np.int64) * si.W + pi[:, 1]) * si.D + pi[:, 2]
+    last = {}
+    for n, k in enumerate(key):
+        last[int(k)] = n
+    winner = np.zeros(len(key))
+    winner[list(last.values())] = 1.0
+    m, o, s, c = t(si.means3D, True), t(si.opacities, True), t(si.semantics, True), t(cov6, True)
+    out = dense_ref.splat_dense(si.variant, t(si.pts), torch.tensor(pi), m, torch.tensor(mi), o, s, torch.tensor(radii), c,
+                                si.H, si.W, si.D)
+    w = t(winner)
+    if si.variant == "prob":
+        ((out[0] * t(g) * w[:, None]).sum() + (out[1] * t(gb) * w).sum() + (out[2] * t(gd) * w).sum()).backward()
+    else:
+        (out * t(g) * w[:, None]).sum().backward()
+    return [x.grad.numpy() for x in (m, o, s, c)]
 
 
 def to_dev(dev, *arrays):
