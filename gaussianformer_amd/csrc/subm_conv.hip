@@ -26,7 +26,7 @@ namespace gf {
 
 constexpr int kPairTile = 128;   // pairs per workgroup tile of the gather-GEMM (32 per wave)
 constexpr int kWgradChunk = 512;  // pairs per workgroup of the weight gradient
-constexpr int kGemmRun = 8;       // consecutive tiles of one offset a workgroup of the run kernel (gf_subm_gemm_bf16_run_kernel) walks
+constexpr int kGemmRun = 8;       // consecutive tiles of one offset a workgroup of gf_subm_gemm_kernel's run form walks
 
 struct SubmTables {
     int *head;              // [cells]  first point of the cell's list, -1 = empty
@@ -41,7 +41,7 @@ struct SubmTables {
     unsigned int *kcursor;  // [K3]
     unsigned char *kmask;   // [K*K][N] bit kz: offset (kxy, kz) of the point has a neighbour cell with points (count pass -> fill pass)
     unsigned int *chunk_start;  // [K3+1] weight-gradient chunks before segment k
-    unsigned int *run_start;    // [K3+1] runs of kGemmRun tiles before segment k (gf_subm_gemm_bf16_run_kernel)
+    unsigned int *run_start;    // [K3+1] runs of kGemmRun tiles before segment k (gf_subm_gemm_kernel's run form)
     unsigned long long *total;  // [0] total pairs, [1] non-zero if a cell is too crowded for the 16-bit counts
 };
 
@@ -59,7 +59,7 @@ struct SubmArgs {
     int N, batch, X, Y, Z, K, K3, Cin, Cout;
     long long cells;
     long long pair_capacity;  // > 0: the pair arrays hold this many entries; a larger rulebook raises total[1] bit 2 and stays empty
-    int gate;                 // f16 gather-GEMM kernels: 0 = run; 1 = run only if the DEVICE's pair count says "long segments", 2 = only if it
+    int gate;                 // gf_subm_gemm_kernel (set for the f16 format only): 0 = run; 1 = run only if the DEVICE's pair count says "long segments", 2 = only if it
                               // says "short" (a rulebook sized by a capacity: the host knows an upper bound of the pair count, not the count)
     int out_lo, out_hi;       // output points [out_lo, out_hi): only they get pairs; EVERY point is a neighbour (anchor-sharded frame: a rank
                               // computes its own anchors' rows from the all-gathered set, spconv3d_module.py:10-83 run 1/world times)
@@ -313,82 +313,140 @@ __device__ __forceinline__ int subm_segment_of(const unsigned int *start, int K3
     return lo;
 }
 
-// partial[slot] = feat[pair_in[slot]] . W[k] on the matrix cores (v_mfma_f32_32x32x2_f32: f32 in, f32
-// accumulate, bitwise an fmaf chain).  A workgroup takes one tile of kPairTile pairs of one offset k and
-// one slice of SW output channels (blockIdx.y) and stages W[k][:, slice] (CIN x SW, 32 KB at 128 x 64 --
-// four workgroups per CU, so one workgroup's staging hides under the MFMAs of the others) in LDS; each
-// of its four waves owns 32 of the pairs.  A operand: lane (i = lane & 31, h = lane >> 5) keeps half h
-// of the gathered feature row of pair i in registers (CIN/2 contiguous floats, 16-byte loads, no LDS
-// round trip); MFMA step s multiplies input channels {s, CIN/2 + s} -- the k order of an MFMA is free
-// as long as A and B agree -- so the B operand is W[k][h CIN/2 + s][32 g + i], one conflict-free
-// ds_read_b32 per 64-cycle MFMA.
-template <int CIN, int COUT, int SW>
-__global__ __launch_bounds__(256, 4) void gf_subm_gemm_kernel(SubmArgs a)
+// ---------------------------------------------------------------------------------------
+// The gather-GEMM, partial[slot] = feat[pair_in[slot]] . W[k], on the matrix cores.  A workgroup takes tiles of kPairTile pairs of
+// one offset k and one slice of SW output channels (blockIdx.y) and stages W[k][:, slice] in LDS; each of its four waves owns 32
+// of a tile's pairs, and lane (i = lane & 31, h = lane >> 5) keeps half h of the K dimension of pair i's gathered row in
+// registers as the A operand (no LDS round trip).  ONE kernel, gf_subm_gemm_kernel below, owns the walk: segment search, exits,
+// slot arithmetic, index fetch and the gather pipeline.  What the operands are is an operand FORMAT, a struct over
+// <CIN, COUT, RUN> that says
+//     SW            the slice of output channels a workgroup takes,
+//     Row, load()   a lane's gathered row (a register array) and how it is loaded,
+//     stage_w()     how W[k][:, slice] goes into LDS (ends with a barrier),
+//     lds_bytes()   the dynamic LDS that takes (the host's launch reads the same function),
+//     tile()        one gathered row set -> the tile's accumulators -> subm_store_tile,
+// and kMinBlocks, the workgroups per CU the kernel is compiled for.
+
+// the f16 format's rows, split once per call by gf_subm_split_rows_kernel (null for the other formats)
+struct SubmSplit {
+    const uint4 *rows16;
+    const int *row_exp;
+};
+
+// the slice of output channels a workgroup takes unless the format says otherwise: 64 channels, or all 32
+constexpr int subm_slice_width(int cout) { return cout >= 64 ? 64 : 32; }
+
+// what a lane knows of its wave's tile: pair / output column i, K half h, the slice's first channel, the end of the segment
+struct SubmLane {
+    int i, h, c_lo;
+    unsigned int seg_end;
+};
+
+// the bf16 and f16 formats' W slice in LDS, in B-operand order: [term][chunk of 16 input channels][32-column group][K half][column]
+// operands of 16 bytes (8 input channels of one output column: one ds_read_b128 per operand); NG = SW / 32
+template <int NG>
+__device__ __forceinline__ int subm_b_index(int chunk, int g, int half, int col)
 {
-    extern __shared__ float s_w[];  // [CIN][SW]
-    constexpr int HALF = CIN / 2, NG = SW / 32;
-    constexpr int WQ = CIN * SW / 4 / 256;  // float4 of the W slice per thread
-    static_assert(COUT % SW == 0 && SW % 32 == 0 && WQ >= 1, "unsupported slice");
-    __shared__ unsigned int s_start[kSubmMaxK3 + 1];
-    const unsigned int t = blockIdx.x;
-    const int k = subm_segment_of(a.t.tile_start, a.K3, t, s_start);
-    if (t >= s_start[a.K3]) return;  // workgroup-uniform
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 31, h = lane >> 5;
-    const int c_lo = blockIdx.y * SW;
-    const unsigned int slot0 = a.t.kstart[k] + (t - s_start[k]) * kPairTile + wave * 32;
-    const unsigned int seg_end = a.t.kstart[k + 1];
-    // gathered feature half-row and the W slice: every load is issued before the first use
-    const unsigned int myslot = slot0 + i;
-    const int row = a.pair_in[min(myslot, seg_end - 1)];  // padding lanes repeat the segment's last pair; never stored
-    const float *wsrc = a.weight + (size_t)k * CIN * COUT + c_lo;
-    float4 wv[WQ];
-#pragma unroll
-    for (int u = 0; u < WQ; ++u) {
-        const int e = tid + 256 * u, ci = e / (SW / 4), c4 = e % (SW / 4);
-        wv[u] = reinterpret_cast<const float4 *>(wsrc + (size_t)ci * COUT)[c4];
-    }
-    const float4 *src = reinterpret_cast<const float4 *>(a.feat + (size_t)row * CIN + h * HALF);
-    float4 av[HALF / 4];
-#pragma unroll
-    for (int q = 0; q < HALF / 4; ++q) av[q] = src[q];
-#pragma unroll
-    for (int u = 0; u < WQ; ++u) reinterpret_cast<float4 *>(s_w)[tid + 256 * u] = wv[u];
-    __syncthreads();
-    if (slot0 >= seg_end) return;  // wave-uniform: this wave's 32 pairs lie past the segment
-    f32x16 acc[NG];
+    return ((chunk * NG + g) * 2 + half) * 32 + col;
+}
+
+template <int NG>
+__device__ __forceinline__ void subm_zero(f32x16 (&acc)[NG])
+{
 #pragma unroll
     for (int g = 0; g < NG; ++g)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
-    const float *wb = s_w + (size_t)h * HALF * SW + i;
-#pragma unroll
-    for (int s = 0; s < HALF; ++s) {
-        const float4 a4 = av[s / 4];
-        const float aval = (s & 3) == 0 ? a4.x : (s & 3) == 1 ? a4.y : (s & 3) == 2 ? a4.z : a4.w;
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-            acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(aval, wb[s * SW + 32 * g], acc[g], 0, 0, 0);
-    }
-    // D layout: column = lane & 31 (output channel), row = (r & 3) + 8 (r >> 2) + 4 h (pair)
+}
+
+// accumulators -> partial rows.  D layout of a 32x32 MFMA: column = lane & 31 (output channel), row = (r & 3) + 8 (r >> 2) + 4 h
+// (pair).  SCALED: the element of pair `row` and column group g is multiplied by 2^-(e_row + ec[g]); er is the exponent of THIS
+// lane's pair, so the row's exponent sits in lane `row`.
+template <int COUT, bool SCALED, int NG>
+__device__ __forceinline__ void subm_store_tile(float *partial, const f32x16 (&acc)[NG], const SubmLane &l, unsigned int slot0, int er = 0,
+                                                const int *ec = nullptr)
+{
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const unsigned int slot = slot0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (slot < seg_end) {
+        const int rho = (r & 3) + 8 * (r >> 2) + 4 * l.h;
+        int e_row = 0;
+        if constexpr (SCALED) e_row = __shfl(er, rho);
+        const unsigned int slot = slot0 + rho;
+        if (slot < l.seg_end) {
 #pragma unroll
-            for (int g = 0; g < NG; ++g) a.partial[(size_t)slot * COUT + c_lo + 32 * g + i] = acc[g][r];
+            for (int g = 0; g < NG; ++g) {
+                float v = acc[g][r];
+                if constexpr (SCALED) v = ldexpf(v, -(e_row + ec[g]));
+                partial[(size_t)slot * COUT + l.c_lo + 32 * g + l.i] = v;
+            }
         }
     }
 }
 
-// The same gather-GEMM on the bf16 matrix cores with fp32-equivalent operands.  f32 MFMA runs at 1/16 of the bf16 rate on
-// gfx950, so every fp32 value is split into three bf16 terms (8 + 8 + 8 significant bits, exact: x = x1 + x2 + x3 up to
-// 2^-24 |x|) and a product a.b is the six terms a1b1 + a1b2 + a2b1 + a2b2 + a1b3 + a3b1 (the dropped ones are <= 2^-24 |ab|
+// Format 1 (option "subm.f32_mfma"): v_mfma_f32_32x32x2_f32 -- f32 in, f32 accumulate, bitwise an fmaf chain.  The W slice is
+// [CIN][SW] floats (32 KB at 128 x 64 -- four workgroups per CU, so one workgroup's staging hides under the MFMAs of the others).
+// A operand: the lane keeps CIN/2 contiguous floats of its row (16-byte loads); MFMA step s multiplies input channels
+// {s, CIN/2 + s} -- the k order of an MFMA is free as long as A and B agree -- so the B operand is
+// W[k][h CIN/2 + s][32 g + i], one conflict-free ds_read_b32 per 64-cycle MFMA.
+template <int CIN, int COUT, bool RUN>
+struct SubmF32 {
+    static constexpr int SW = subm_slice_width(COUT);
+    static constexpr int HALF = CIN / 2, NG = SW / 32;
+    static constexpr int WQ = CIN * SW / 4 / 256;  // float4 of the W slice per thread
+    static_assert(WQ >= 1 && !RUN, "unsupported slice; no run form");
+    static constexpr int kMinBlocks = 4;
+    struct Row { float4 v[HALF / 4]; };
+    static constexpr size_t lds_bytes() { return (size_t)CIN * SW * sizeof(float); }
+
+    static __device__ __forceinline__ Row load(const SubmArgs &a, const SubmSplit &, int row, int h)
+    {
+        const float4 *src = reinterpret_cast<const float4 *>(a.feat + (size_t)row * CIN + h * HALF);
+        Row r;
+#pragma unroll
+        for (int q = 0; q < HALF / 4; ++q) r.v[q] = src[q];
+        return r;
+    }
+
+    static __device__ __forceinline__ void stage_w(const float *wsrc, uint4 *lds)
+    {
+        float4 wv[WQ];   // every load is issued before the first store
+#pragma unroll
+        for (int u = 0; u < WQ; ++u) {
+            const int e = threadIdx.x + 256 * u, ci = e / (SW / 4), c4 = e % (SW / 4);
+            wv[u] = reinterpret_cast<const float4 *>(wsrc + (size_t)ci * COUT)[c4];
+        }
+#pragma unroll
+        for (int u = 0; u < WQ; ++u) reinterpret_cast<float4 *>(lds)[threadIdx.x + 256 * u] = wv[u];
+        __syncthreads();
+    }
+
+    static __device__ __forceinline__ void tile(const SubmArgs &a, const Row &av, const uint4 *lds, const SubmLane &l, unsigned int slot0)
+    {
+        f32x16 acc[NG];
+        subm_zero(acc);
+        const float *wb = reinterpret_cast<const float *>(lds) + (size_t)l.h * HALF * SW + l.i;
+#pragma unroll
+        for (int s = 0; s < HALF; ++s) {
+            const float4 a4 = av.v[s / 4];
+            const float aval = (s & 3) == 0 ? a4.x : (s & 3) == 1 ? a4.y : (s & 3) == 2 ? a4.z : a4.w;
+#pragma unroll
+            for (int g = 0; g < NG; ++g)
+                acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(aval, wb[s * SW + 32 * g], acc[g], 0, 0, 0);
+        }
+        subm_store_tile<COUT, false>(a.partial, acc, l, slot0);
+    }
+};
+
+// Format 2 (gf_subm_conv_apply, option "subm.bf16x3"): the bf16 matrix cores with fp32-equivalent operands.  f32 MFMA runs at 1/16
+// of the bf16 rate on gfx950, so every fp32 value is split into three bf16 terms (8 + 8 + 8 significant bits, exact: x = x1 + x2 + x3
+// up to 2^-24 |x|) and a product a.b is the six terms a1b1 + a1b2 + a2b1 + a2b2 + a1b3 + a3b1 (the dropped ones are <= 2^-24 |ab|
 // each), accumulated in fp32 by v_mfma_f32_32x32x16_bf16 with the small terms first: six MFMAs of 8 passes per K = 16
 // instead of eight of 16 passes, 2.7x less time in the matrix pipe, and the error of a product (~1.2e-7 relative) is what a
-// chain of fp32 FMAs has per step.  The feature half-rows are split in registers (per K chunk), the weight slice is
-// split once per workgroup on its way into LDS, stored in B-operand order ([term][chunk][32-column group][K half][column]
-// x 8 bf16 = one ds_read_b128 per operand).
+// chain of fp32 FMAs has per step.  The feature half-rows are split in registers (per K chunk), the weight slice is split once
+// per workgroup on its way into LDS (a third of a one-tile workgroup's vector-ALU work), stored in B-operand order.
+// Built, measured and removed again (round 6): the feature rows split into their bf16 terms ONCE per call by a kernel of its own (a
+// row takes part in ~41 pairs) and gathered as three 256-byte pieces -- 1.935 against 1.493 ms at A = 144 000: half again as many
+// bytes per gathered row and 244 registers cost more than the ~350 vector instructions per tile saved.
 union BF8 {
     bf16x8 v;
     __bf16 e[8];
@@ -402,197 +460,90 @@ __device__ __forceinline__ void split3_bf16(float x, __bf16 &x1, __bf16 &x2, __b
     x3 = (__bf16)(r - (float)x2);
 }
 
-template <int CIN, int COUT, int SW>
-__global__ __launch_bounds__(256, 3) void gf_subm_gemm_bf16_kernel(SubmArgs a)
-{
-    extern __shared__ uint4 s_wb[];  // [3][CIN/16][SW/32][2][32] operands of 16 B
-    constexpr int NC = CIN / 16, NG = SW / 32, NB = CIN / 8, TPB = 256 / SW;
-    static_assert(COUT % SW == 0 && SW % 32 == 0 && CIN % 16 == 0, "unsupported slice");
-    __shared__ unsigned int s_start[kSubmMaxK3 + 1];
-    const unsigned int t = blockIdx.x;
-    const int k = subm_segment_of(a.t.tile_start, a.K3, t, s_start);
-    if (t >= s_start[a.K3]) return;  // workgroup-uniform
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 31, h = lane >> 5;
-    const int c_lo = blockIdx.y * SW;
-    const unsigned int slot0 = a.t.kstart[k] + (t - s_start[k]) * kPairTile + wave * 32;
-    const unsigned int seg_end = a.t.kstart[k + 1];
-    const unsigned int myslot = slot0 + i;
-    const int row = a.pair_in[min(myslot, seg_end - 1)];  // padding lanes repeat the segment's last pair; never stored
-    // gathered feature row: lane (pair i, K half h) holds channels 16 c + 8 h .. + 7 of every chunk c
-    const float4 *src = reinterpret_cast<const float4 *>(a.feat + (size_t)row * CIN + 8 * h);
-    float4 av[NC][2];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) { av[c][0] = src[4 * c]; av[c][1] = src[4 * c + 1]; }
-    // W slice -> LDS: a thread converts 8 consecutive input channels of one output column at a time
-    {
-        const float *wsrc = a.weight + (size_t)k * CIN * COUT + c_lo;
-        const int co = tid % SW, g = co >> 5, n = co & 31;
-#pragma unroll
-        for (int blk = tid / SW; blk < NB; blk += TPB) {
-            BF8 w1, w2, w3;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) split3_bf16(wsrc[(size_t)(8 * blk + j) * COUT + co], w1.e[j], w2.e[j], w3.e[j]);
-            const int idx = (((blk >> 1) * NG + g) * 2 + (blk & 1)) * 32 + n;
-            s_wb[idx] = w1.u;
-            s_wb[NC * NG * 64 + idx] = w2.u;
-            s_wb[2 * NC * NG * 64 + idx] = w3.u;
-        }
-    }
-    __syncthreads();
-    if (slot0 >= seg_end) return;  // wave-uniform: this wave's 32 pairs lie past the segment
-    f32x16 acc[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const float x[8] = {av[c][0].x, av[c][0].y, av[c][0].z, av[c][0].w, av[c][1].x, av[c][1].y, av[c][1].z, av[c][1].w};
-        BF8 a1, a2, a3;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) split3_bf16(x[j], a1.e[j], a2.e[j], a3.e[j]);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int idx = ((c * NG + g) * 2 + h) * 32 + i;
-            BF8 b1, b2, b3;
-            b1.u = s_wb[idx]; b2.u = s_wb[NC * NG * 64 + idx]; b3.u = s_wb[2 * NC * NG * 64 + idx];
-            acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3.v, b1.v, acc[g], 0, 0, 0);
-            acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.v, b3.v, acc[g], 0, 0, 0);
-            acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2.v, b2.v, acc[g], 0, 0, 0);
-            acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2.v, b1.v, acc[g], 0, 0, 0);
-            acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.v, b2.v, acc[g], 0, 0, 0);
-            acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.v, b1.v, acc[g], 0, 0, 0);
-        }
-    }
-    // D layout: column = lane & 31 (output channel), row = (r & 3) + 8 (r >> 2) + 4 h (pair)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const unsigned int slot = slot0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (slot < seg_end) {
-#pragma unroll
-            for (int g = 0; g < NG; ++g) a.partial[(size_t)slot * COUT + c_lo + 32 * g + i] = acc[g][r];
-        }
-    }
-}
+template <int CIN, int COUT, bool RUN>
+struct SubmBf16x3 {
+    static constexpr int SW = subm_slice_width(COUT);
+    static constexpr int NC = CIN / 16, NG = SW / 32, NB = CIN / 8, TPB = 256 / SW;
+    static constexpr int TERM = NC * NG * 64;   // operands of one term
+    static constexpr int GS = RUN ? NG : 1;     // column groups whose MFMA chains run side by side (tile())
+    static_assert(CIN % 16 == 0, "unsupported slice");
+    static constexpr int kMinBlocks = RUN ? 2 : 3;   // (the run form: two register sets of gathered rows)
+    struct Row { uint4 v[2 * NC]; };   // channels 16 c + 8 h .. + 7 of every chunk c, fp32
+    static constexpr size_t lds_bytes() { return (size_t)3 * TERM * 16; }
 
-// The same kernel for LONG segments (round 6): a workgroup walks a RUN of kGemmRun consecutive tiles of one offset.
-// Per tile the kernel above pays the whole start-up -- 32 KB of W[k] read, split into three bf16 terms and stored to LDS (a third
-// of its vector-ALU work), a barrier, the gather's two dependent round trips (pair index, then the feature row) -- in front of
-// 1.5 us of MFMAs: at A = 144 000 (5.9 M pairs, 369 tiles per offset) the matrix pipe was busy 29 % of 1.60 ms.  Here the W
-// slice is converted ONCE per run, and the gather is a two-stage pipeline: the pair indices of tile j + 2 and the feature rows of
-// tile j + 1 are requested before tile j's MFMAs.  Same operands, same order of the six terms, same partial rows: bit-identical
-// to the kernel above (tests/test_subm_conv.py).  Two workgroups per CU (two register sets of gathered rows).
-// Measured at A = 144 000 (profiles/subm_run_r06.txt): 1.595 -> 1.493 ms.  With the memory traffic taken out (rows gathered from a
-// handful of addresses: 1.457; no partial stores: 1.297; both: 1.218 ms) the kernel keeps 80 % of its time: it is bound inside the
-// CU -- 96 MFMAs (3 072 matrix cycles) and ~450 vector instructions per wave and tile that two waves per SIMD overlap little -- not
-// by the 3 GB of partial rows.  Built, measured and removed again: the feature rows split into their bf16 terms ONCE per call by a
-// kernel of its own (a row takes part in ~41 pairs) and gathered as three 256-byte pieces -- 1.935 ms: half again as many bytes
-// per gathered row and 244 registers cost more than the ~350 vector instructions per tile saved.
-template <int CIN, int COUT, int SW>
-__global__ __launch_bounds__(256, 2) void gf_subm_gemm_bf16_run_kernel(SubmArgs a)
-{
-    extern __shared__ uint4 s_wb[];  // [3][CIN/16][SW/32][2][32] operands of 16 B
-    constexpr int NC = CIN / 16, NG = SW / 32, NB = CIN / 8, TPB = 256 / SW;
-    static_assert(COUT % SW == 0 && SW % 32 == 0 && CIN % 16 == 0, "unsupported slice");
-    __shared__ unsigned int s_start[kSubmMaxK3 + 1];
-    const unsigned int t = blockIdx.x;
-    const int k = subm_segment_of(a.t.run_start, a.K3, t, s_start);
-    if (t >= s_start[a.K3]) return;  // workgroup-uniform
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 31, h = lane >> 5;
-    const int c_lo = blockIdx.y * SW;
-    const unsigned int seg_end = a.t.kstart[k + 1];
-    const unsigned int run0 = a.t.kstart[k] + (t - s_start[k]) * (unsigned int)(kGemmRun * kPairTile);   // first slot of the run
-    const int ntiles = (int)min((unsigned int)kGemmRun, (seg_end - run0 + kPairTile - 1) / kPairTile);
-    const unsigned int wslot0 = run0 + wave * 32;   // this wave's first slot in tile 0; tile j: + j kPairTile
-    // pair indices of tiles 0 and 1, feature rows of tile 0: requested before the W slice is converted
-    int row_next = a.pair_in[min(wslot0 + i, seg_end - 1)];                      // (padding lanes repeat the segment's last pair; never stored)
-    int row_next2 = a.pair_in[min(wslot0 + kPairTile + i, seg_end - 1)];
-    constexpr int NA = 2 * NC;   // 16-byte pieces of a gathered row per lane
-    uint4 av[NA];
-    auto gather = [&](uint4 (&dst)[NA], int row) {
+    static __device__ __forceinline__ Row load(const SubmArgs &a, const SubmSplit &, int row, int h)
+    {
         const uint4 *src = reinterpret_cast<const uint4 *>(a.feat + (size_t)row * CIN + 8 * h);
+        Row r;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) { dst[2 * c] = src[4 * c]; dst[2 * c + 1] = src[4 * c + 1]; }
-    };
-    gather(av, row_next);
+        for (int c = 0; c < NC; ++c) { r.v[2 * c] = src[4 * c]; r.v[2 * c + 1] = src[4 * c + 1]; }
+        return r;
+    }
+
+    // a thread converts 8 consecutive input channels of one output column at a time
+    static __device__ __forceinline__ void stage_w(const float *wsrc, uint4 *s_wb)
     {
-        const float *wsrc = a.weight + (size_t)k * CIN * COUT + c_lo;
-        const int co = tid % SW, g = co >> 5, n = co & 31;
+        const int tid = threadIdx.x, co = tid % SW, g = co >> 5, n = co & 31;
 #pragma unroll
         for (int blk = tid / SW; blk < NB; blk += TPB) {
             BF8 w1, w2, w3;
 #pragma unroll
             for (int j = 0; j < 8; ++j) split3_bf16(wsrc[(size_t)(8 * blk + j) * COUT + co], w1.e[j], w2.e[j], w3.e[j]);
-            const int idx = (((blk >> 1) * NG + g) * 2 + (blk & 1)) * 32 + n;
+            const int idx = subm_b_index<NG>(blk >> 1, g, blk & 1, n);
             s_wb[idx] = w1.u;
-            s_wb[NC * NG * 64 + idx] = w2.u;
-            s_wb[2 * NC * NG * 64 + idx] = w3.u;
+            s_wb[TERM + idx] = w2.u;
+            s_wb[2 * TERM + idx] = w3.u;
         }
+        __syncthreads();
     }
-    __syncthreads();
-    for (int j = 0; j < ntiles; ++j) {
-        const unsigned int slot0 = wslot0 + (unsigned int)j * kPairTile;
-        // stage 1: the feature rows of tile j + 1 (its indices arrived during tile j - 1); stage 2: the indices of tile j + 2
-        uint4 an[NA];
-        gather(an, row_next2);
-        const int row_next3 = a.pair_in[min(slot0 + 2 * kPairTile + i, seg_end - 1)];
-        if (slot0 < seg_end) {   // wave-uniform: else this wave's 32 pairs lie past the segment (the last tile of a segment)
-            f32x16 acc[NG];
-#pragma unroll
-            for (int g = 0; g < NG; ++g)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                BF8 a1, a2, a3;
-                const float x[8] = {__uint_as_float(av[2 * c].x), __uint_as_float(av[2 * c].y), __uint_as_float(av[2 * c].z), __uint_as_float(av[2 * c].w),
-                                    __uint_as_float(av[2 * c + 1].x), __uint_as_float(av[2 * c + 1].y), __uint_as_float(av[2 * c + 1].z), __uint_as_float(av[2 * c + 1].w)};
-#pragma unroll
-                for (int q = 0; q < 8; ++q) split3_bf16(x[q], a1.e[q], a2.e[q], a3.e[q]);
-                // (the column groups' chains side by side: a group's six terms keep their order -- small terms first -- but consecutive
-                // MFMAs belong to different accumulators, so none waits for its predecessor's result)
-                BF8 b1[NG], b2[NG], b3[NG];
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    const int idx = ((c * NG + g) * 2 + h) * 32 + i;
-                    b1[g].u = s_wb[idx]; b2[g].u = s_wb[NC * NG * 64 + idx]; b3[g].u = s_wb[2 * NC * NG * 64 + idx];
-                }
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3.v, b1[g].v, acc[g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.v, b3[g].v, acc[g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2.v, b2[g].v, acc[g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2.v, b1[g].v, acc[g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.v, b2[g].v, acc[g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.v, b1[g].v, acc[g], 0, 0, 0);
-            }
-            // D layout: column = lane & 31 (output channel), row = (r & 3) + 8 (r >> 2) + 4 h (pair)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const unsigned int slot = slot0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (slot < seg_end) {
-#pragma unroll
-                    for (int g = 0; g < NG; ++g) a.partial[(size_t)slot * COUT + c_lo + 32 * g + i] = acc[g][r];
-                }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < NA; ++q) av[q] = an[q];
-        row_next2 = row_next3;
-    }
-}
 
-// ---------------------------------------------------------------------------------------
-// Round 6, second half: fp32-equivalent operands as TWO f16 terms (hi + lo, 11 + 11 significant bits) and THREE products per
-// fp32 product (lo hi + hi lo + hi hi; the dropped lo lo is <= 2^-22 |ab|) instead of three bf16 terms and six products: the
-// gather-GEMM above is bound by its six MFMAs per product (0.83 of 1.49 ms at 144 000 anchors, §3.7), and the matrix cores run
-// f16 at the bf16 rate.  What f16 lacks is range, so both operands are scaled by powers of two -- exactly, and undone exactly:
+    static __device__ __forceinline__ void tile(const SubmArgs &a, const Row &av, const uint4 *s_wb, const SubmLane &l, unsigned int slot0)
+    {
+        f32x16 acc[NG];
+        subm_zero(acc);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            BF8 a1, a2, a3;
+            const float x[8] = {__uint_as_float(av.v[2 * c].x), __uint_as_float(av.v[2 * c].y), __uint_as_float(av.v[2 * c].z), __uint_as_float(av.v[2 * c].w),
+                                __uint_as_float(av.v[2 * c + 1].x), __uint_as_float(av.v[2 * c + 1].y), __uint_as_float(av.v[2 * c + 1].z), __uint_as_float(av.v[2 * c + 1].w)};
+#pragma unroll
+            for (int q = 0; q < 8; ++q) split3_bf16(x[q], a1.e[q], a2.e[q], a3.e[q]);
+            // The six terms of a product, small terms first: every accumulator's own chain has this order.  GS column groups' chains
+            // go side by side -- consecutive MFMAs belong to different accumulators, so none waits for its predecessor's result: all
+            // NG in the run form (1.544 -> 1.486 ms at A = 144 000), one at a time in the one-tile form, where three workgroups per
+            // CU fill the gaps and NG sets of B operands held at once cost 3 % (apply 101.7 -> 104.6 us at A = 25 600).  Same chains, same bits.
+#pragma unroll
+            for (int g0 = 0; g0 < NG; g0 += GS) {
+                BF8 b1[GS], b2[GS], b3[GS];
+                f32x16 *ac = acc + g0;
+#pragma unroll
+                for (int g = 0; g < GS; ++g) {
+                    const int idx = subm_b_index<NG>(c, g0 + g, l.h, l.i);
+                    b1[g].u = s_wb[idx]; b2[g].u = s_wb[TERM + idx]; b3[g].u = s_wb[2 * TERM + idx];
+                }
+#pragma unroll
+                for (int g = 0; g < GS; ++g) ac[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3.v, b1[g].v, ac[g], 0, 0, 0);
+#pragma unroll
+                for (int g = 0; g < GS; ++g) ac[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.v, b3[g].v, ac[g], 0, 0, 0);
+#pragma unroll
+                for (int g = 0; g < GS; ++g) ac[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2.v, b2[g].v, ac[g], 0, 0, 0);
+#pragma unroll
+                for (int g = 0; g < GS; ++g) ac[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2.v, b1[g].v, ac[g], 0, 0, 0);
+#pragma unroll
+                for (int g = 0; g < GS; ++g) ac[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.v, b2[g].v, ac[g], 0, 0, 0);
+#pragma unroll
+                for (int g = 0; g < GS; ++g) ac[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.v, b1[g].v, ac[g], 0, 0, 0);
+            }
+        }
+        subm_store_tile<COUT, false>(a.partial, acc, l, slot0);
+    }
+};
+
+// Format 3 (the default, gf_subm_conv_apply_scratch; round 6, second half): fp32-equivalent operands as TWO f16 terms (hi + lo,
+// 11 + 11 significant bits) and THREE products per fp32 product (lo hi + hi lo + hi hi; the dropped lo lo is <= 2^-22 |ab|) instead
+// of three bf16 terms and six products: the bf16 format is bound by its six MFMAs per product (0.83 of 1.49 ms at 144 000 anchors,
+// §3.7), and the matrix cores run f16 at the bf16 rate.  What f16 lacks is range, so both operands are scaled by powers of two --
+// exactly, and undone exactly:
 //   * a feature row is multiplied by 2^e with its largest |x| brought to [2^14, 2^15): the hi term has 11 significant bits, the
 //     lo term = x 2^e - hi another 11 unless it falls below f16's smallest normal (elements 2^17 times smaller than the row's
 //     largest; the absolute error of such an element is <= 2^-25 where the row's largest is 2^14, i.e. 2^-39 of it).  Scaling a
@@ -650,94 +601,100 @@ __global__ __launch_bounds__(256) void gf_subm_split_rows_kernel(const float *fe
     }
 }
 
-struct SubmSplit {
-    const uint4 *rows16;   // gf_subm_split_rows_kernel's output
-    const int *row_exp;
+template <int CIN, int COUT, bool RUN>
+struct SubmF16x2 {
+    // 128 -> 128 (the encoder's layers): ONE workgroup takes all 128 output channels of its pairs -- a row is gathered once instead of
+    // once per 64-channel slice (the gather, not the matrix pipe, is what this format waits for: 1.52 -> 1.15 ms at 144 000 anchors);
+    // the same MFMA chains per output element, so the same bits as the 64-channel slices
+    static constexpr int SW = CIN == 128 && COUT == 128 ? 128 : subm_slice_width(COUT);
+    static constexpr int NC = CIN / 16, NG = SW / 32, NB = CIN / 8, TPB = 256 / SW, PER = (NB + TPB - 1) / TPB;
+    static constexpr int TERM = NC * NG * 64;   // operands of one term
+    static_assert(CIN % 16 == 0, "unsupported slice");
+    static constexpr int kMinBlocks = RUN || SW == 128 ? 2 : 3;   // (two register sets of gathered rows; 64 KB of W)
+    struct Row {
+        uint4 v[2 * NC];   // [chunk][hi, lo] operands of this lane's pair
+        int e;             // its row exponent
+    };
+    // the format's static LDS (function-local, so one array per instantiation; as members of a struct in LDS handed to stage_w and
+    // tile by reference they cost the run form two VGPRs and a v_add per tile, and 0.5 % of the apply at 144 000 anchors)
+    static __device__ __forceinline__ float *cmax() { __shared__ float s[256]; return s; }   // largest |w| of a column, per thread of the column
+    static __device__ __forceinline__ int *ecol() { __shared__ int s[SW]; return s; }        // one exponent per column of the slice
+    static constexpr size_t lds_bytes() { return (size_t)2 * TERM * 16; }
+
+    static __device__ __forceinline__ Row load(const SubmArgs &, const SubmSplit &sp, int row, int h)
+    {
+        const uint4 *src = sp.rows16 + (size_t)row * (CIN / 4);
+        Row r;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { r.v[2 * c] = src[2 * c + h]; r.v[2 * c + 1] = src[CIN / 8 + 2 * c + h]; }
+        r.e = sp.row_exp[row];
+        return r;
+    }
+
+    // A thread converts 8 consecutive input channels of one output column at a time; the TPB threads of a column agree on its
+    // largest |w| through cmax.
+    static __device__ __forceinline__ void stage_w(const float *wsrc, uint4 *s_wb)
+    {
+        const int tid = threadIdx.x, co = tid % SW, g = co >> 5, n = co & 31, b0 = tid / SW;
+        float w[PER][8];
+        float m = 0.f;
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int blk = min(b0 + TPB * u, NB - 1);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                w[u][j] = wsrc[(size_t)(8 * blk + j) * COUT + co];
+                m = fmaxf(m, fabsf(w[u][j]));
+            }
+        }
+        cmax()[b0 * SW + co] = m;
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < TPB; ++u) m = fmaxf(m, cmax()[u * SW + co]);
+        const int e = subm_scale_exp(m);
+        if (b0 == 0) ecol()[co] = e;
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int blk = b0 + TPB * u;
+            if (blk < NB) {
+                HF8 w1, w2;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) split2_f16(w[u][j], e, w1.e[j], w2.e[j]);
+                const int idx = subm_b_index<NG>(blk >> 1, g, blk & 1, n);
+                s_wb[idx] = w1.u;
+                s_wb[TERM + idx] = w2.u;
+            }
+        }
+        __syncthreads();
+    }
+
+    static __device__ __forceinline__ void tile(const SubmArgs &a, const Row &av, const uint4 *s_wb, const SubmLane &l, unsigned int slot0)
+    {
+        f32x16 acc[NG];
+        subm_zero(acc);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            HF8 ah, al, bh[NG], bl[NG];
+            ah.u = av.v[2 * c]; al.u = av.v[2 * c + 1];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                const int idx = subm_b_index<NG>(c, g, l.h, l.i);
+                bh[g].u = s_wb[idx]; bl[g].u = s_wb[TERM + idx];
+            }
+            // (small terms first; the column groups' chains side by side, as in the bf16 format's run form)
+#pragma unroll
+            for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al.v, bh[g].v, acc[g], 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bl[g].v, acc[g], 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bh[g].v, acc[g], 0, 0, 0);
+        }
+        int ec[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) ec[g] = ecol()[32 * g + l.i];
+        subm_store_tile<COUT, true>(a.partial, acc, l, slot0, av.e, ec);
+    }
 };
-
-// W slice -> LDS as two f16 terms in B-operand order ([term][chunk][32-column group][K half][column] x 8 f16), one exponent per
-// column of the slice (s_ecol).  A thread converts 8 consecutive input channels of one output column at a time; the TPB threads
-// of a column agree on its largest |w| through s_cmax.
-template <int CIN, int COUT, int SW>
-__device__ __forceinline__ void subm_stage_w_f16(const float *wsrc, uint4 *s_wb, float *s_cmax, int *s_ecol)
-{
-    constexpr int NC = CIN / 16, NG = SW / 32, NB = CIN / 8, TPB = 256 / SW, PER = (NB + TPB - 1) / TPB;
-    const int tid = threadIdx.x, co = tid % SW, g = co >> 5, n = co & 31, b0 = tid / SW;
-    float w[PER][8];
-    float m = 0.f;
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        const int blk = min(b0 + TPB * u, NB - 1);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            w[u][j] = wsrc[(size_t)(8 * blk + j) * COUT + co];
-            m = fmaxf(m, fabsf(w[u][j]));
-        }
-    }
-    s_cmax[b0 * SW + co] = m;
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < TPB; ++u) m = fmaxf(m, s_cmax[u * SW + co]);
-    const int e = subm_scale_exp(m);
-    if (b0 == 0) s_ecol[co] = e;
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        const int blk = b0 + TPB * u;
-        if (blk < NB) {
-            HF8 w1, w2;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) split2_f16(w[u][j], e, w1.e[j], w2.e[j]);
-            const int idx = (((blk >> 1) * NG + g) * 2 + (blk & 1)) * 32 + n;
-            s_wb[idx] = w1.u;
-            s_wb[NC * NG * 64 + idx] = w2.u;
-        }
-    }
-    __syncthreads();
-}
-
-// one tile's MFMAs and partial rows: av = [chunk][hi, lo] operands of this lane's pair, er = its row exponent
-template <int CIN, int COUT, int SW>
-__device__ __forceinline__ void subm_tile_f16(const SubmArgs &a, const uint4 (&av)[CIN / 8], int er, const uint4 *s_wb, const int *s_ecol,
-                                              unsigned int slot0, unsigned int seg_end, int c_lo, int i, int h)
-{
-    constexpr int NC = CIN / 16, NG = SW / 32;
-    f32x16 acc[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        HF8 ah, al, bh[NG], bl[NG];
-        ah.u = av[2 * c]; al.u = av[2 * c + 1];
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int idx = ((c * NG + g) * 2 + h) * 32 + i;
-            bh[g].u = s_wb[idx]; bl[g].u = s_wb[NC * NG * 64 + idx];
-        }
-        // (small terms first; the column groups' chains side by side, as in the bf16 kernels)
-#pragma unroll
-        for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al.v, bh[g].v, acc[g], 0, 0, 0);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bl[g].v, acc[g], 0, 0, 0);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bh[g].v, acc[g], 0, 0, 0);
-    }
-    int ec[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) ec[g] = s_ecol[32 * g + i];
-    // D layout: column = lane & 31 (output channel), row = (r & 3) + 8 (r >> 2) + 4 h (pair); the row's exponent sits in lane `row`
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int rho = (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int e_row = __shfl(er, rho);
-        const unsigned int slot = slot0 + rho;
-        if (slot < seg_end) {
-#pragma unroll
-            for (int g = 0; g < NG; ++g) a.partial[(size_t)slot * COUT + c_lo + 32 * g + i] = ldexpf(acc[g][r], -(e_row + ec[g]));
-        }
-    }
-}
 
 // "long segments" = at least 4 runs of kGemmRun tiles per offset on average -- by the rulebook's own pair count
 __device__ __forceinline__ bool subm_gate_passes(const SubmArgs &a)
@@ -748,82 +705,59 @@ __device__ __forceinline__ bool subm_gate_passes(const SubmArgs &a)
     return long_segments == (a.gate == 1);
 }
 
-template <int CIN, int COUT, int SW, int MINB = 3>
-__global__ __launch_bounds__(256, MINB) void gf_subm_gemm_f16_kernel(SubmArgs a, SubmSplit sp)
+// The walk.  RUN = false: one tile per workgroup (blockIdx.x counts tiles) -- one register set of rows, idle waves leave after
+// the staging barrier.  RUN = true, for LONG segments (round 6): a workgroup walks a RUN of kGemmRun consecutive
+// tiles of one offset (blockIdx.x counts runs).  Per tile the one-tile form pays the whole start-up -- 32 KB of W[k] read, converted
+// and stored to LDS, a barrier, the gather's two dependent round trips (pair index, then the feature row) -- in front of 1.5 us of
+// MFMAs: at A = 144 000 (5.9 M pairs, 369 tiles per offset) the matrix pipe was busy 29 % of 1.60 ms.  Here the W slice is converted
+// ONCE per run, and the gather is a two-stage pipeline: the pair indices of tile j + 2 and the feature rows of tile j + 1 are
+// requested before tile j's MFMAs.  Both forms call the same Format::tile on the same operands: bit-identical
+// (tests/test_subm_conv.py).  Two workgroups per CU (two register sets of gathered rows).
+// Measured with the bf16 format at A = 144 000 (profiles/subm_run_r06.txt): 1.595 -> 1.493 ms.  With the memory traffic taken out
+// (rows gathered from a handful of addresses: 1.457; no partial stores: 1.297; both: 1.218 ms) the kernel keeps 80 % of its time: it
+// is bound inside the CU -- 96 MFMAs (3 072 matrix cycles) and ~450 vector instructions per wave and tile that two waves per SIMD
+// overlap little -- not by the 3 GB of partial rows.
+template <template <int, int, bool> class Format, int CIN, int COUT, bool RUN>
+__global__ __launch_bounds__(256, (Format<CIN, COUT, RUN>::kMinBlocks)) void gf_subm_gemm_kernel(SubmArgs a, SubmSplit sp)
 {
+    using F = Format<CIN, COUT, RUN>;
+    constexpr int SW = F::SW;
+    using Row = typename F::Row;
+    static_assert(COUT % SW == 0 && SW % 32 == 0, "unsupported slice");
     if (!subm_gate_passes(a)) return;   // workgroup-uniform
-    extern __shared__ uint4 s_wb[];  // [2][CIN/16][SW/32][2][32] operands of 16 B
-    constexpr int NC = CIN / 16;
-    static_assert(COUT % SW == 0 && SW % 32 == 0 && CIN % 16 == 0, "unsupported slice");
+    extern __shared__ uint4 s_w[];      // the format's W slice, F::lds_bytes()
     __shared__ unsigned int s_start[kSubmMaxK3 + 1];
-    __shared__ float s_cmax[256];
-    __shared__ int s_ecol[SW];
+    constexpr unsigned int kSpan = (RUN ? kGemmRun : 1) * kPairTile;   // slots per workgroup
     const unsigned int t = blockIdx.x;
-    const int k = subm_segment_of(a.t.tile_start, a.K3, t, s_start);
+    const int k = subm_segment_of(RUN ? a.t.run_start : a.t.tile_start, a.K3, t, s_start);
     if (t >= s_start[a.K3]) return;  // workgroup-uniform
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 31, h = lane >> 5;
-    const int c_lo = blockIdx.y * SW;
-    const unsigned int slot0 = a.t.kstart[k] + (t - s_start[k]) * kPairTile + wave * 32;
-    const unsigned int seg_end = a.t.kstart[k + 1];
-    const int row = a.pair_in[min(slot0 + i, seg_end - 1)];  // padding lanes repeat the segment's last pair; never stored
-    const uint4 *src = sp.rows16 + (size_t)row * (CIN / 4);
-    uint4 av[2 * NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) { av[2 * c] = src[2 * c + h]; av[2 * c + 1] = src[CIN / 8 + 2 * c + h]; }
-    const int er = sp.row_exp[row];
-    subm_stage_w_f16<CIN, COUT, SW>(a.weight + (size_t)k * CIN * COUT + c_lo, s_wb, s_cmax, s_ecol);
-    if (slot0 >= seg_end) return;  // wave-uniform: this wave's 32 pairs lie past the segment
-    subm_tile_f16<CIN, COUT, SW>(a, av, er, s_wb, s_ecol, slot0, seg_end, c_lo, i, h);
-}
-
-// ... and in runs of kGemmRun tiles on long segments (gf_subm_gemm_bf16_run_kernel's pipeline: indices two tiles ahead, rows one)
-template <int CIN, int COUT, int SW>
-__global__ __launch_bounds__(256, 2) void gf_subm_gemm_f16_run_kernel(SubmArgs a, SubmSplit sp)
-{
-    if (!subm_gate_passes(a)) return;   // workgroup-uniform
-    extern __shared__ uint4 s_wb[];
-    constexpr int NC = CIN / 16, NA = 2 * NC;
-    static_assert(COUT % SW == 0 && SW % 32 == 0 && CIN % 16 == 0, "unsupported slice");
-    __shared__ unsigned int s_start[kSubmMaxK3 + 1];
-    __shared__ float s_cmax[256];
-    __shared__ int s_ecol[SW];
-    const unsigned int t = blockIdx.x;
-    const int k = subm_segment_of(a.t.run_start, a.K3, t, s_start);
-    if (t >= s_start[a.K3]) return;  // workgroup-uniform
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 31, h = lane >> 5;
-    const int c_lo = blockIdx.y * SW;
-    const unsigned int seg_end = a.t.kstart[k + 1];
-    const unsigned int run0 = a.t.kstart[k] + (t - s_start[k]) * (unsigned int)(kGemmRun * kPairTile);   // first slot of the run
-    const int ntiles = (int)min((unsigned int)kGemmRun, (seg_end - run0 + kPairTile - 1) / kPairTile);
-    const unsigned int wslot0 = run0 + wave * 32;   // this wave's first slot in tile 0; tile j: + j kPairTile
-    int row_next = a.pair_in[min(wslot0 + i, seg_end - 1)];                      // (padding lanes repeat the segment's last pair; never stored)
-    int row_next2 = a.pair_in[min(wslot0 + kPairTile + i, seg_end - 1)];
-    uint4 av[NA];
-    auto gather = [&](uint4 (&dst)[NA], int &e, int row) {
-        const uint4 *src = sp.rows16 + (size_t)row * (CIN / 4);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { dst[2 * c] = src[2 * c + h]; dst[2 * c + 1] = src[CIN / 8 + 2 * c + h]; }
-        e = sp.row_exp[row];
-    };
-    int er;
-    gather(av, er, row_next);
-    subm_stage_w_f16<CIN, COUT, SW>(a.weight + (size_t)k * CIN * COUT + c_lo, s_wb, s_cmax, s_ecol);
-    for (int j = 0; j < ntiles; ++j) {
-        const unsigned int slot0 = wslot0 + (unsigned int)j * kPairTile;
-        // (built and measured, round 6: ONE register set of rows at three or four workgroups per CU instead of this pipeline -- 1.52 and
-        // 1.64 against 1.52 ms: more waves do not hide what is a request rate, not a latency)
-        uint4 an[NA];
-        int en;
-        gather(an, en, row_next2);
-        const int row_next3 = a.pair_in[min(slot0 + 2 * kPairTile + i, seg_end - 1)];
-        if (slot0 < seg_end)   // wave-uniform: else this wave's 32 pairs lie past the segment (the last tile of a segment)
-            subm_tile_f16<CIN, COUT, SW>(a, av, er, s_wb, s_ecol, slot0, seg_end, c_lo, i, h);
-#pragma unroll
-        for (int q = 0; q < NA; ++q) av[q] = an[q];
-        er = en;
-        row_next2 = row_next3;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const SubmLane l = {lane & 31, lane >> 5, (int)blockIdx.y * SW, a.t.kstart[k + 1]};
+    const unsigned int run0 = a.t.kstart[k] + (t - s_start[k]) * kSpan;   // the workgroup's first slot
+    const unsigned int wslot0 = run0 + wave * 32;                         // this wave's first slot in tile 0; tile j: + j kPairTile
+    auto row_at = [&](unsigned int slot) { return a.pair_in[min(slot + l.i, l.seg_end - 1)]; };   // (padding lanes repeat the segment's last pair; never stored)
+    // pair indices of tile 0 (and 1), feature rows of tile 0: requested before the W slice is converted
+    const int row0 = row_at(wslot0);
+    int row_next = 0;
+    if constexpr (RUN) row_next = row_at(wslot0 + kPairTile);
+    Row av = F::load(a, sp, row0, l.h);
+    F::stage_w(a.weight + (size_t)k * CIN * COUT + l.c_lo, s_w);
+    if constexpr (!RUN) {
+        if (wslot0 >= l.seg_end) return;  // wave-uniform: this wave's 32 pairs lie past the segment
+        F::tile(a, av, s_w, l, wslot0);
+    } else {
+        const int ntiles = (int)min((unsigned int)kGemmRun, (l.seg_end - run0 + kPairTile - 1) / kPairTile);
+        for (int j = 0; j < ntiles; ++j) {
+            const unsigned int slot0 = wslot0 + (unsigned int)j * kPairTile;
+            // stage 1: the feature rows of tile j + 1 (its indices arrived during tile j - 1); stage 2: the indices of tile j + 2
+            // (built and measured, round 6, f16 format: ONE register set of rows at three or four workgroups per CU instead of this
+            // pipeline -- 1.52 and 1.64 against 1.52 ms: more waves do not hide what is a request rate, not a latency)
+            const Row an = F::load(a, sp, row_next, l.h);
+            row_next = row_at(slot0 + 2 * kPairTile);
+            if (slot0 < l.seg_end)   // wave-uniform: else this wave's 32 pairs lie past the segment (the last tile of a segment)
+                F::tile(a, av, s_w, l, slot0);
+            av = an;
+        }
     }
 }
 
@@ -1227,6 +1161,21 @@ extern "C" int gf_subm_rulebook_build_range(int N, int batch, int X, int Y, int 
         else CALL(32, 32);                                            \
     } while (0)
 
+// one launch of the gather-GEMM: `blocks` workgroups (tiles, or runs of tiles) per slice of output channels.  Every format's kernel
+// takes `sp`; only the f16 format reads it (the others are handed an empty one).
+template <template <int, int, bool> class Format, bool RUN>
+static void launch_gemm(int Cin, int Cout, unsigned blocks, hipStream_t stream, gf::SubmArgs a, const gf::SubmSplit &sp, int gate)
+{
+    a.gate = gate;
+#define GF_GEMM(CI, CO)                                                                                                  \
+    do {                                                                                                                 \
+        using F = Format<CI, CO, RUN>;                                                                                   \
+        hipLaunchKernelGGL((gf::gf_subm_gemm_kernel<Format, CI, CO, RUN>), dim3(blocks, CO / F::SW), dim3(256), F::lds_bytes(), stream, a, sp); \
+    } while (0)
+    GF_SUBM_DISPATCH(GF_GEMM);
+#undef GF_GEMM
+}
+
 extern "C" size_t gf_subm_apply_scratch_bytes(int N, int Cin)
 {
     return N > 0 && Cin > 0 ? gf::align256((size_t)N * Cin * 4) + gf::align256((size_t)N * 4) : 0;
@@ -1247,69 +1196,36 @@ static int subm_conv_apply_impl(int N, int batch, int X, int Y, int Z, int K, in
     SubmArgs a = subm_args(N, batch, X, Y, Z, K, nullptr, const_cast<void *>(tables));
     a.Cin = Cin; a.Cout = Cout; a.feat = features; a.weight = weight; a.pair_in = const_cast<int *>(pair_in);
     a.partial = partial; a.out = out;
-    const int SW = Cout >= 64 ? 64 : 32;  // output-channel slice per workgroup
-    const size_t lds = (size_t)Cin * SW * sizeof(float);
-    const dim3 gemm_grid((unsigned)(total_pairs / kPairTile + K3), Cout / SW);  // x >= the number of tiles, whatever the split over the segments
+    const unsigned tiles = (unsigned)(total_pairs / kPairTile + K3);   // >= the number of tiles, whatever the split over the segments
+    const unsigned runs = tiles / kGemmRun + K3 + 1;                    // >= the number of runs
     const int rows = 256 / (Cout / 4);
-    const bool exact_f32 = option(kOptSubmF32Mfma) != 0;  // gf_set_option("subm.f32_mfma", 1): the exact-f32 MFMA kernel
     // long segments (>= 4 runs of kGemmRun tiles per offset on average, by the pair count the caller sized the arrays for): runs of
     // tiles per workgroup; gf_set_option("subm.tile_gemm", 1) keeps one tile per workgroup
     const bool by_runs = total_pairs / kPairTile >= (long long)K3 * 4 * kGemmRun && option(kOptSubmTileGemm) == 0;
-    const dim3 run_grid((unsigned)((total_pairs / kPairTile + K3) / kGemmRun + K3 + 1), Cout / SW);   // x >= the number of runs
-    if (exact_f32) {
-#define GF_GEMM(CI, CO) hipLaunchKernelGGL((gf_subm_gemm_kernel<CI, CO, (CO >= 64 ? 64 : 32)>), gemm_grid, dim3(256), lds, stream, a)
-        GF_SUBM_DISPATCH(GF_GEMM);
-#undef GF_GEMM
+    if (option(kOptSubmF32Mfma) != 0) {  // gf_set_option("subm.f32_mfma", 1): the exact-f32 MFMA format
+        launch_gemm<SubmF32, false>(Cin, Cout, tiles, stream, a, SubmSplit{}, 0);
     } else if (scratch && option(kOptSubmBf16x3) == 0) {
         // two f16 terms, three products (round 6): rows split once into the caller's scratch, then the gather-GEMM on them
         GF_CHECK_ARG(scratch_bytes >= gf_subm_apply_scratch_bytes(N, Cin) && ((uintptr_t)scratch & 15) == 0, "scratch too small or not 16-byte aligned");
-        SubmSplit sp;
         uint4 *rows16 = (uint4 *)scratch;
         int *row_exp = (int *)((char *)scratch + align256((size_t)N * Cin * 4));
-        sp.rows16 = rows16; sp.row_exp = row_exp;
+        const SubmSplit sp = {rows16, row_exp};
         const unsigned sblocks = (unsigned)(((long long)N * (Cin / 8) + 255) / 256);
         if (Cin == 128) hipLaunchKernelGGL(gf_subm_split_rows_kernel<128>, dim3(sblocks), dim3(256), 0, stream, features, N, rows16, row_exp);
         else if (Cin == 64) hipLaunchKernelGGL(gf_subm_split_rows_kernel<64>, dim3(sblocks), dim3(256), 0, stream, features, N, rows16, row_exp);
         else hipLaunchKernelGGL(gf_subm_split_rows_kernel<32>, dim3(sblocks), dim3(256), 0, stream, features, N, rows16, row_exp);
-        const size_t lds_h = (size_t)2 * (Cin / 16) * (SW / 32) * 64 * 16;
-        // 128 -> 128 (the encoder's layers): ONE workgroup takes all 128 output channels of its pairs -- a row is gathered once instead
-        // of once per 64-channel slice (the gather, not the matrix pipe, is what the f16 kernels wait for: 1.52 -> 1.15 ms at 144 000
-        // anchors); the same MFMA chains per output element, so the same bits as the 64-channel slices
         // `total_pairs` is an UPPER bound of the pair count when the rulebook was sized by a capacity (pairs_per_point = 64 where the
-        // encoder's 25 600 anchors have 8): deciding by it sent such a call to the run kernel with a fifth of the workgroups the chip
+        // encoder's 25 600 anchors have 8): deciding by it sent such a call to the run form with a fifth of the workgroups the chip
         // has CUs (74 against 54 us).  So when the bound says "long segments" BOTH organisations are launched and the rulebook's own
         // count, on the device, lets exactly one of them run (the other's workgroups leave after one load; the tile grid of that
         // launch is capped at the most tiles a "short" rulebook can have).  A bound that says "short" needs no second launch.
-        SubmArgs a_run = a, a_tile = a;
-        a_run.gate = 1;
-        a_tile.gate = by_runs ? 2 : 0;
-        const bool force_tile = option(kOptSubmTileGemm) != 0;
-        const unsigned tile_blocks = by_runs && !force_tile ? (unsigned)min((long long)gemm_grid.x, (long long)K3 * 4 * kGemmRun + K3) : gemm_grid.x;
-        if (force_tile) a_tile.gate = 0;
-        if (Cin == 128 && Cout == 128) {
-            if (by_runs) hipLaunchKernelGGL((gf_subm_gemm_f16_run_kernel<128, 128, 128>), dim3(run_grid.x, 1), dim3(256), 2 * lds_h, stream, a_run, sp);
-            hipLaunchKernelGGL((gf_subm_gemm_f16_kernel<128, 128, 128, 2>), dim3(tile_blocks, 1), dim3(256), 2 * lds_h, stream, a_tile, sp);
-        } else {
-            if (by_runs) {
-#define GF_GEMM(CI, CO) hipLaunchKernelGGL((gf_subm_gemm_f16_run_kernel<CI, CO, (CO >= 64 ? 64 : 32)>), run_grid, dim3(256), lds_h, stream, a_run, sp)
-                GF_SUBM_DISPATCH(GF_GEMM);
-#undef GF_GEMM
-            }
-#define GF_GEMM(CI, CO) hipLaunchKernelGGL((gf_subm_gemm_f16_kernel<CI, CO, (CO >= 64 ? 64 : 32)>), dim3(tile_blocks, gemm_grid.y), dim3(256), lds_h, stream, a_tile, sp)
-            GF_SUBM_DISPATCH(GF_GEMM);
-#undef GF_GEMM
-        }
+        if (by_runs) launch_gemm<SubmF16x2, true>(Cin, Cout, runs, stream, a, sp, 1);
+        const unsigned tile_blocks = by_runs ? (unsigned)min((long long)tiles, (long long)K3 * 4 * kGemmRun + K3) : tiles;
+        launch_gemm<SubmF16x2, false>(Cin, Cout, tile_blocks, stream, a, sp, by_runs ? 2 : 0);
+    } else if (by_runs) {
+        launch_gemm<SubmBf16x3, true>(Cin, Cout, runs, stream, a, SubmSplit{}, 0);
     } else {
-        const size_t lds_bf = (size_t)3 * (Cin / 16) * (SW / 32) * 64 * 16;
-        if (by_runs) {
-#define GF_GEMM(CI, CO) hipLaunchKernelGGL((gf_subm_gemm_bf16_run_kernel<CI, CO, (CO >= 64 ? 64 : 32)>), run_grid, dim3(256), lds_bf, stream, a)
-            GF_SUBM_DISPATCH(GF_GEMM);
-#undef GF_GEMM
-        } else {
-#define GF_GEMM(CI, CO) hipLaunchKernelGGL((gf_subm_gemm_bf16_kernel<CI, CO, (CO >= 64 ? 64 : 32)>), gemm_grid, dim3(256), lds_bf, stream, a)
-            GF_SUBM_DISPATCH(GF_GEMM);
-#undef GF_GEMM
-        }
+        launch_gemm<SubmBf16x3, false>(Cin, Cout, tiles, stream, a, SubmSplit{}, 0);
     }
     if (Cout == 128) hipLaunchKernelGGL(gf_subm_reduce_kernel<128>, dim3((N + rows - 1) / rows), dim3(256), 0, stream, a);
     else if (Cout == 64) hipLaunchKernelGGL(gf_subm_reduce_kernel<64>, dim3((N + rows - 1) / rows), dim3(256), 0, stream, a);
