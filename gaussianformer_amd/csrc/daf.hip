@@ -59,23 +59,48 @@ __device__ __forceinline__ void vload(const float *p, float (&v)[VEC])
     for (int j = 0; j < VEC; ++j) v[j] = f[j];
 }
 
-// Bilinear tap geometry: bilinear_sampling, deformable_aggregation_cuda.cu:13-29,51.
-struct Taps {
+template <int VEC>
+__device__ __forceinline__ void vstore(float *p, const float (&v)[VEC])
+{
+    using T = typename VecT<VEC>::type;
+    T t;
+    float *f = reinterpret_cast<float *>(&t);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) f[j] = v[j];
+    *reinterpret_cast<T *>(p) = t;
+}
+
+// The bilinear cell of a tap position (bilinear_sampling, deformable_aggregation_cuda.cu:13-29,51): its low pixel, the
+// fractions and the four coefficients; of corner k (0 .. 3: k >> 1 the row step, k & 1 the column step) coefficient and pixel.
+struct Cell {
     int h_low, w_low;
     float w1, w2, w3, w4, lh, lw, hh, hw;
-    bool ok1, ok2, ok3, ok4;
+    __device__ __forceinline__ float coef(int k) const { return k == 0 ? w1 : k == 1 ? w2 : k == 2 ? w3 : w4; }
+    __device__ __forceinline__ int py(int k) const { return h_low + (k >> 1); }
+    __device__ __forceinline__ int px(int k) const { return w_low + (k & 1); }
 };
-__device__ __forceinline__ Taps make_taps(float h_im, float w_im, int height, int width)
+__device__ __forceinline__ Cell make_cell(float h_im, float w_im)
 {
-    Taps t;
+    Cell t;
     t.h_low = (int)floorf(h_im);
     t.w_low = (int)floorf(w_im);
-    const int h_high = t.h_low + 1, w_high = t.w_low + 1;
     t.lh = h_im - t.h_low;
     t.lw = w_im - t.w_low;
     t.hh = 1 - t.lh;
     t.hw = 1 - t.lw;
     t.w1 = t.hh * t.hw; t.w2 = t.hh * t.lw; t.w3 = t.lh * t.hw; t.w4 = t.lh * t.lw;
+    return t;
+}
+
+// ... and which of the corners lie in the image
+struct Taps : Cell {
+    bool ok1, ok2, ok3, ok4;
+};
+__device__ __forceinline__ Taps make_taps(float h_im, float w_im, int height, int width)
+{
+    Taps t;
+    static_cast<Cell &>(t) = make_cell(h_im, w_im);
+    const int h_high = t.h_low + 1, w_high = t.w_low + 1;
     t.ok1 = t.h_low >= 0 && t.w_low >= 0;
     t.ok2 = t.h_low >= 0 && w_high <= width - 1;
     t.ok3 = h_high <= height - 1 && t.w_low >= 0;
@@ -93,6 +118,23 @@ __device__ __forceinline__ Corners clamp_corners(const Taps &t, int height, int 
     const int h0 = max(t.h_low, 0), h1 = min(t.h_low + 1, height - 1);
     const int w0 = max(t.w_low, 0), w1 = min(t.w_low + 1, width - 1);
     return {h0 * width + w0, h0 * width + w1, h1 * width + w0, h1 * width + w1};
+}
+
+// The four corner values of a level (base = its first pixel row, this lane's channels).  All four taps are loaded
+// unconditionally from clamped (always valid) pixels and the out-of-image ones are replaced by zero BY THE CALLER: a load under
+// `if (ok)` is followed by its own s_waitcnt inside the branch, which made the sixteen taps of a camera a serial chain.  (The
+// zeroing stays with the callers' arithmetic: moved in here, the selects come before the forward's sums in another order and
+// the compiler contracts a different product of val = w1 x1 + .. + w4 x4 into the FMAs -- other last bits, and not the same
+// ones in the three forward kernels.)
+template <int VEC>
+__device__ __forceinline__ void load_corners(const float *base, int C, const Taps &t, int height, int width,
+                                             float (&v1)[VEC], float (&v2)[VEC], float (&v3)[VEC], float (&v4)[VEC])
+{
+    const Corners c = clamp_corners(t, height, width);
+    vload<VEC>(base + (size_t)c.r1 * C, v1);
+    vload<VEC>(base + (size_t)c.r2 * C, v2);
+    vload<VEC>(base + (size_t)c.r3 * C, v3);
+    vload<VEC>(base + (size_t)c.r4 * C, v4);
 }
 
 template <int VEC>
@@ -121,15 +163,8 @@ __global__ __launch_bounds__(256) void gf_daf_fwd_kernel(DafArgs a)
             const float h_im = loc_h * h - 0.5f, w_im = loc_w * w - 0.5f;  // :174-175
             const Taps t = make_taps(h_im, w_im, h, w);
             const float *base = fcam + (size_t)a.scale_start[s] * a.C;
-            // All four taps are loaded unconditionally from clamped (always valid) pixels and the
-            // out-of-image ones are replaced by zero: a load under `if (ok)` is followed by its own
-            // s_waitcnt inside the branch, which made the sixteen taps of a camera a serial chain.
-            const Corners c = clamp_corners(t, h, w);
             float v1[VEC], v2[VEC], v3[VEC], v4[VEC];
-            vload<VEC>(base + (size_t)c.r1 * a.C, v1);
-            vload<VEC>(base + (size_t)c.r2 * a.C, v2);
-            vload<VEC>(base + (size_t)c.r3 * a.C, v3);
-            vload<VEC>(base + (size_t)c.r4 * a.C, v4);
+            load_corners<VEC>(base, a.C, t, h, w, v1, v2, v3, v4);
             const float wt = wts[(cam * a.L + s) * a.G];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
@@ -140,13 +175,7 @@ __global__ __launch_bounds__(256) void gf_daf_fwd_kernel(DafArgs a)
             }
         }
     }
-    float *o = a.out + bp * a.C + c0;
-    using T = typename VecT<VEC>::type;
-    T ov;
-    float *of = reinterpret_cast<float *>(&ov);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) of[j] = acc[j];
-    *reinterpret_cast<T *>(o) = ov;
+    vstore<VEC>(a.out + bp * a.C + c0, acc);
 }
 
 // The same forward for <= 8 cameras with every camera's sampling location loaded up front: the kernel above walks the cameras
@@ -191,12 +220,8 @@ __global__ __launch_bounds__(256) void gf_daf_fwd4_kernel(DafArgs a)
             const float h_im = loc_h * h - 0.5f, w_im = loc_w * w - 0.5f;  // :174-175
             const Taps t = make_taps(h_im, w_im, h, w);
             const float *base = fcam + (size_t)a.scale_start[s] * a.C;
-            const Corners c = clamp_corners(t, h, w);
             float v1[VEC], v2[VEC], v3[VEC], v4[VEC];
-            vload<VEC>(base + (size_t)c.r1 * a.C, v1);
-            vload<VEC>(base + (size_t)c.r2 * a.C, v2);
-            vload<VEC>(base + (size_t)c.r3 * a.C, v3);
-            vload<VEC>(base + (size_t)c.r4 * a.C, v4);
+            load_corners<VEC>(base, a.C, t, h, w, v1, v2, v3, v4);
             const float wt = wts[(cam * a.L + s) * a.G];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
@@ -206,13 +231,7 @@ __global__ __launch_bounds__(256) void gf_daf_fwd4_kernel(DafArgs a)
             }
         }
     }
-    float *o = a.out + bp * a.C + c0;
-    using T = typename VecT<VEC>::type;
-    T ov;
-    float *of = reinterpret_cast<float *>(&ov);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) of[j] = acc[j];
-    *reinterpret_cast<T *>(o) = ov;
+    vstore<VEC>(a.out + bp * a.C + c0, acc);
 }
 
 // The same forward with the channel groups pinned to XCDs.  A block b runs on XCD b % 8 (observed placement, used for
@@ -247,12 +266,8 @@ __global__ __launch_bounds__(256) void gf_daf_fwd_grouped_kernel(DafArgs a, int 
             const float h_im = loc_h * h - 0.5f, w_im = loc_w * w - 0.5f;  // :174-175
             const Taps t = make_taps(h_im, w_im, h, w);
             const float *base = fcam + (size_t)a.scale_start[s] * a.C;
-            const Corners c = clamp_corners(t, h, w);
             float v1[4], v2[4], v3[4], v4[4];
-            vload<4>(base + (size_t)c.r1 * a.C, v1);
-            vload<4>(base + (size_t)c.r2 * a.C, v2);
-            vload<4>(base + (size_t)c.r3 * a.C, v3);
-            vload<4>(base + (size_t)c.r4 * a.C, v4);
+            load_corners<4>(base, a.C, t, h, w, v1, v2, v3, v4);
             const float wt = wts[(cam * a.L + s) * a.G];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -262,7 +277,7 @@ __global__ __launch_bounds__(256) void gf_daf_fwd_grouped_kernel(DafArgs a, int 
             }
         }
     }
-    *reinterpret_cast<float4 *>(a.out + bp * a.C + c0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    vstore<4>(a.out + bp * a.C + c0, acc);
 }
 
 // LPG = lanes per channel group, LPP = lanes per point (both powers of two <= 64 on the
@@ -313,15 +328,8 @@ __global__ __launch_bounds__(256) void gf_daf_bwd_kernel(DafArgs a, int lpg, int
             const Taps t = make_taps(h_im, w_im, h, w);
             const size_t o1 = cam_off + (size_t)a.scale_start[s] * a.C + ((long long)t.h_low * w + t.w_low) * a.C;
             const size_t o2 = o1 + a.C, o3 = o1 + (size_t)w * a.C, o4 = o3 + a.C;
-            // unconditional loads from clamped pixels, then zeroed where the tap is outside the image
-            // (see gf_daf_fwd_kernel: a load under `if (ok)` waits for itself inside the branch)
-            const Corners cc = clamp_corners(t, h, w);
-            const size_t lvl_off = cam_off + (size_t)a.scale_start[s] * a.C;
             float v1[VEC], v2[VEC], v3[VEC], v4[VEC];
-            vload<VEC>(feat + lvl_off + (size_t)cc.r1 * a.C, v1);
-            vload<VEC>(feat + lvl_off + (size_t)cc.r2 * a.C, v2);
-            vload<VEC>(feat + lvl_off + (size_t)cc.r3 * a.C, v3);
-            vload<VEC>(feat + lvl_off + (size_t)cc.r4 * a.C, v4);
+            load_corners<VEC>(feat + (cam_off + (size_t)a.scale_start[s] * a.C), a.C, t, h, w, v1, v2, v3, v4);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
                 v1[j] = t.ok1 ? v1[j] : 0.f; v2[j] = t.ok2 ? v2[j] : 0.f;
@@ -439,63 +447,77 @@ struct DafSortArgs {
     long long samples;        // pts * cams
 };
 
-// Visits the in-bounds taps of samples [s0, s1): f(tile, id).
-template <typename F>
-__device__ __forceinline__ void daf_for_each_tap(const DafSortArgs &a, long long s0, long long s1, F &&f)
-{
-    for (long long q = s0 + threadIdx.x; q < s1; q += blockDim.x) {
-        const float loc_w = a.loc[2 * q], loc_h = a.loc[2 * q + 1];
-        if (!(loc_w > 0 && loc_w < 1 && loc_h > 0 && loc_h < 1)) continue;  // deformable_aggregation_cuda.cu:166
-        const uint32_t pt = (uint32_t)(q / a.cams);
-        const uint32_t cam = (uint32_t)(q - (long long)pt * a.cams);
-        const uint32_t row_cam = cam * (uint32_t)a.num_feat;
-        const uint32_t id_base = (pt << a.cam_bits | cam) << a.lvl_bits;
-        for (int s = 0; s < a.L; ++s) {
-            const int h = a.spatial_shape[2 * s], w = a.spatial_shape[2 * s + 1];
-            const Taps t = make_taps(loc_h * h - 0.5f, loc_w * w - 0.5f, h, w);
-            const uint32_t r1 = row_cam + (uint32_t)a.scale_start[s] + (uint32_t)(t.h_low * w + t.w_low);
-            const uint32_t rows[4] = {r1, r1 + 1u, r1 + (uint32_t)w, r1 + (uint32_t)w + 1u};
-            const bool ok[4] = {t.ok1, t.ok2, t.ok3, t.ok4};
+// What a bucket pass visits and how it keys it: Args = the kernels' argument, sort(a) = its DafSortArgs, bins(a) = the bin
+// count, stride(a) = the row stride of M, visit(a, s0, s1, f) = f(bin, id) for what samples [s0, s1) put into the bins.
+// DafByTile: the in-bounds taps of a sample, by tile; bins and stride known to the host.
+struct DafByTile {
+    using Args = DafSortArgs;
+    static __device__ __forceinline__ const DafSortArgs &sort(const Args &a) { return a; }
+    static __device__ __forceinline__ int bins(const Args &a) { return a.ntiles; }
+    static __device__ __forceinline__ int stride(const Args &a) { return a.ntiles; }
+    template <typename F>
+    static __device__ __forceinline__ void visit(const Args &a, long long s0, long long s1, F &&f)
+    {
+        for (long long q = s0 + threadIdx.x; q < s1; q += blockDim.x) {
+            const float loc_w = a.loc[2 * q], loc_h = a.loc[2 * q + 1];
+            if (!(loc_w > 0 && loc_w < 1 && loc_h > 0 && loc_h < 1)) continue;  // deformable_aggregation_cuda.cu:166
+            const uint32_t pt = (uint32_t)(q / a.cams);
+            const uint32_t cam = (uint32_t)(q - (long long)pt * a.cams);
+            const uint32_t row_cam = cam * (uint32_t)a.num_feat;
+            const uint32_t id_base = (pt << a.cam_bits | cam) << a.lvl_bits;
+            for (int s = 0; s < a.L; ++s) {
+                const int h = a.spatial_shape[2 * s], w = a.spatial_shape[2 * s + 1];
+                const Taps t = make_taps(loc_h * h - 0.5f, loc_w * w - 0.5f, h, w);
+                const uint32_t r1 = row_cam + (uint32_t)a.scale_start[s] + (uint32_t)(t.h_low * w + t.w_low);
+                const uint32_t rows[4] = {r1, r1 + 1u, r1 + (uint32_t)w, r1 + (uint32_t)w + 1u};
+                const bool ok[4] = {t.ok1, t.ok2, t.ok3, t.ok4};
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (ok[k]) f(rows[k] / (uint32_t)a.tile_rows, ((id_base | (uint32_t)s) << 2) | (uint32_t)k);
+                for (int k = 0; k < 4; ++k)
+                    if (ok[k]) f(rows[k] / (uint32_t)a.tile_rows, ((id_base | (uint32_t)s) << 2) | (uint32_t)k);
+            }
         }
     }
-}
+};
 
-template <bool FILL>
-__global__ __launch_bounds__(1024) void gf_daf_bucket_kernel(DafSortArgs a)
+template <typename KEY, bool FILL>
+__global__ __launch_bounds__(1024) void gf_daf_bucket_kernel(typename KEY::Args ka)
 {
     __shared__ uint32_t s_bin[kDafMaxTiles];
+    const DafSortArgs &a = KEY::sort(ka);
+    const int nbins = KEY::bins(ka);
     const int wg = blockIdx.x;
-    uint32_t *row = a.M + (size_t)wg * a.ntiles;
-    for (int t = threadIdx.x; t < a.ntiles; t += blockDim.x) s_bin[t] = FILL ? a.tile_start[t] + row[t] : 0u;
+    uint32_t *row = a.M + (size_t)wg * KEY::stride(ka);
+    for (int t = threadIdx.x; t < nbins; t += blockDim.x) s_bin[t] = FILL ? a.tile_start[t] + row[t] : 0u;
     __syncthreads();
     const long long per = (a.samples + gridDim.x - 1) / gridDim.x;
     const long long s0 = min(a.samples, (long long)wg * per), s1 = min(a.samples, s0 + per);
-    daf_for_each_tap(a, s0, s1, [&](uint32_t tile, uint32_t id) {
-        if (FILL) a.taps[atomicAdd(&s_bin[tile], 1u)] = id;
-        else atomicAdd(&s_bin[tile], 1u);
+    KEY::visit(ka, s0, s1, [&](uint32_t bin, uint32_t id) {
+        if (FILL) a.taps[atomicAdd(&s_bin[bin], 1u)] = id;
+        else atomicAdd(&s_bin[bin], 1u);
     });
     if (!FILL) {
         __syncthreads();
-        for (int t = threadIdx.x; t < a.ntiles; t += blockDim.x) row[t] = s_bin[t];
+        for (int t = threadIdx.x; t < nbins; t += blockDim.x) row[t] = s_bin[t];
     }
 }
 
 // Exclusive prefix of M[.][tile] over the bucket workgroups; total -> tile_start[tile].  Eight lanes per tile,
 // each with 32 consecutive workgroups in registers (32 independent loads), combined by an 8-lane scan: one thread
 // per tile walking all 256 rows was a chain of 256 dependent read-modify-writes on eleven workgroups' worth of threads.
-__global__ __launch_bounds__(256) void gf_daf_colscan_kernel(DafSortArgs a)
+template <typename KEY>
+__global__ __launch_bounds__(256) void gf_daf_colscan_kernel(typename KEY::Args ka)
 {
     constexpr int kParts = 8, kPer = kDafBucketWgs / kParts;
+    const DafSortArgs &a = KEY::sort(ka);
+    const int ntiles = KEY::bins(ka);
+    const size_t stride = (size_t)KEY::stride(ka);
     const int gidx = blockIdx.x * 256 + threadIdx.x;
     const int t = gidx / kParts, part = gidx % kParts;
-    const bool live = t < a.ntiles;
-    const int tc = live ? t : a.ntiles - 1;
+    const bool live = t < ntiles;
+    const int tc = live ? t : ntiles - 1;
     uint32_t c[kPer];
 #pragma unroll
-    for (int j = 0; j < kPer; ++j) c[j] = a.M[(size_t)(part * kPer + j) * a.ntiles + tc];
+    for (int j = 0; j < kPer; ++j) c[j] = a.M[(size_t)(part * kPer + j) * stride + tc];
     uint32_t sum = 0;
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
@@ -512,32 +534,78 @@ __global__ __launch_bounds__(256) void gf_daf_colscan_kernel(DafSortArgs a)
     const uint32_t base = incl - sum;
     if (!live) return;
 #pragma unroll
-    for (int j = 0; j < kPer; ++j) a.M[(size_t)(part * kPer + j) * a.ntiles + t] = base + c[j];
-    if (part == kParts - 1) a.tile_start[t] = incl;  // per-tile total; turned into a prefix by gf_daf_tilescan_kernel
+    for (int j = 0; j < kPer; ++j) a.M[(size_t)(part * kPer + j) * stride + t] = base + c[j];
+    if (part == kParts - 1) a.tile_start[t] = incl;  // per-bin total; turned into a prefix by the scan kernel of the formulation
+}
+
+// Inclusive scan of N running sums over the 1 024 threads of a workgroup (Hillis-Steele): v[] = the thread's sums in, the
+// inclusive prefixes out; total[] = the sums over all threads.
+template <int N>
+__device__ __forceinline__ void daf_block_scan(uint32_t (&v)[N], uint32_t (&total)[N])
+{
+    __shared__ uint32_t s[N][1024];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int n = 0; n < N; ++n) s[n][tid] = v[n];
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        uint32_t u[N];
+#pragma unroll
+        for (int n = 0; n < N; ++n) u[n] = tid >= d ? s[n][tid - d] : 0u;
+        __syncthreads();
+#pragma unroll
+        for (int n = 0; n < N; ++n) s[n][tid] += u[n];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        v[n] = s[n][tid];
+        total[n] = s[n][1023];
+    }
+}
+
+// Exclusive scan, by the workgroup's first wave, of 64 * PER_LANE row counts (PER_LANE consecutive ones per lane): the counts
+// become the rows' first positions, cnt[64 * PER_LANE] the total.
+template <int PER_LANE>
+__device__ __forceinline__ void daf_row_offsets(uint32_t *cnt, int tid)
+{
+    if (tid >= 64) return;
+    uint32_t c[PER_LANE], own = 0;
+#pragma unroll
+    for (int j = 0; j < PER_LANE; ++j) {
+        c[j] = cnt[PER_LANE * tid + j];
+        own += c[j];
+    }
+    uint32_t incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (tid >= d) incl += up;
+    }
+    uint32_t run = incl - own;
+#pragma unroll
+    for (int j = 0; j < PER_LANE; ++j) {
+        cnt[PER_LANE * tid + j] = run;
+        run += c[j];
+    }
+    if (tid == 63) cnt[64 * PER_LANE] = incl;
 }
 
 // Single workgroup: prefix over the tiles, work-item table.
 __global__ __launch_bounds__(1024) void gf_daf_tilescan_kernel(DafSortArgs a)
 {
-    __shared__ uint32_t s_t[1024], s_i[1024];
     const int tid = threadIdx.x;
     const int per = (a.ntiles + 1023) / 1024;
     const int t0 = min(a.ntiles, tid * per), t1 = min(a.ntiles, t0 + per);
-    uint32_t st = 0, si = 0;
+    uint32_t own[2] = {0u, 0u};   // taps, items
     for (int t = t0; t < t1; ++t) {
         const uint32_t c = a.tile_start[t];
-        st += c;
-        si += (c + kDafChunk - 1) / kDafChunk;
+        own[0] += c;
+        own[1] += (c + kDafChunk - 1) / kDafChunk;
     }
-    s_t[tid] = st; s_i[tid] = si;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {  // Hillis-Steele inclusive scan
-        const uint32_t ut = tid >= d ? s_t[tid - d] : 0u, ui = tid >= d ? s_i[tid - d] : 0u;
-        __syncthreads();
-        s_t[tid] += ut; s_i[tid] += ui;
-        __syncthreads();
-    }
-    uint32_t run_t = s_t[tid] - st, run_i = s_i[tid] - si;
+    uint32_t incl[2] = {own[0], own[1]}, total[2];
+    daf_block_scan<2>(incl, total);
+    uint32_t run_t = incl[0] - own[0], run_i = incl[1] - own[1];
     for (int t = t0; t < t1; ++t) {
         const uint32_t c = a.tile_start[t];
         const uint32_t ni = (c + kDafChunk - 1) / kDafChunk;
@@ -548,9 +616,9 @@ __global__ __launch_bounds__(1024) void gf_daf_tilescan_kernel(DafSortArgs a)
         run_i += ni;
     }
     if (tid == 1023) {
-        a.tile_start[a.ntiles] = s_t[1023];
-        a.item_start[a.ntiles] = s_i[1023];
-        a.header[0] = s_i[1023];
+        a.tile_start[a.ntiles] = total[0];
+        a.item_start[a.ntiles] = total[1];
+        a.header[0] = total[1];
     }
 }
 
@@ -619,6 +687,7 @@ __global__ __launch_bounds__(256) void gf_daf_accumulate_kernel(DafSortArgs a)
             const float loc_w = lc[j].x, loc_h = lc[j].y;
             const int h = s_lvl[3 * s], w = s_lvl[3 * s + 1];
             const float h_im = loc_h * h - 0.5f, w_im = loc_w * w - 0.5f;
+            // (the cell's arithmetic in place, not make_cell: with the helper this kernel takes 96 VGPRs for 92 -- profiles/daf_shared_pieces.txt)
             const float fh = floorf(h_im), fw = floorf(w_im);
             const float lh = h_im - fh, lw = w_im - fw, hh = 1 - lh, hw = 1 - lw;
             cw[j] = k == 0 ? hh * hw : k == 1 ? hh * lw : k == 2 ? lh * hw : lh * lw;
@@ -630,19 +699,7 @@ __global__ __launch_bounds__(256) void gf_daf_accumulate_kernel(DafSortArgs a)
             }
         }
         __syncthreads();
-        if (tid < 64) {  // exclusive scan of the <= 128 row counts: two per lane
-            const uint32_t c0r = s_cnt[2 * tid], c1r = s_cnt[2 * tid + 1];
-            uint32_t incl = c0r + c1r;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d, 64);
-                if (tid >= d) incl += up;
-            }
-            const uint32_t excl = incl - (c0r + c1r);
-            s_cnt[2 * tid] = excl;
-            s_cnt[2 * tid + 1] = excl + c0r;
-            if (tid == 63) s_cnt[kDafMaxTileRows] = incl;
-        }
+        daf_row_offsets<kDafMaxTileRows / 64>(s_cnt, tid);  // exclusive scan of the <= 128 row counts: two per lane
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
@@ -780,72 +837,29 @@ __global__ void gf_daf_region_geom_kernel(DafRegionArgs a)
     a.s.header[1] = (uint32_t)g.nregions;
 }
 
-__device__ __forceinline__ int daf_region_of(const DafRegionGeom &g, const DafSortArgs &a, float loc_w, float loc_h, uint32_t cam)
-{
-    const int h0 = a.spatial_shape[0], w0 = a.spatial_shape[1];
-    const int wl = (int)floorf(loc_w * w0 - 0.5f), hl = (int)floorf(loc_h * h0 - 0.5f);   // the level-0 tap's own arithmetic
-    const int rx = min(max(wl + 1, 0) >> (3 + g.shift), g.RX - 1);
-    const int ry = min(max(hl + 1, 0) >> (3 + g.shift), g.RY - 1);
-    return ((int)cam * g.RY + ry) * g.RX + rx;
-}
-
-template <bool FILL>
-__global__ __launch_bounds__(1024) void gf_daf_rbucket_kernel(DafRegionArgs a)
-{
-    __shared__ uint32_t s_bin[kDafMaxTiles];
-    const DafRegionGeom g = *a.geom;
-    const int ntiles = g.nregions;
-    const int wg = blockIdx.x;
-    uint32_t *row = a.s.M + (size_t)wg * kDafMaxTiles;   // (rows of kDafMaxTiles entries: the region count is not known to the host)
-    for (int t = threadIdx.x; t < ntiles; t += blockDim.x) s_bin[t] = FILL ? a.s.tile_start[t] + row[t] : 0u;
-    __syncthreads();
-    const long long per = (a.s.samples + gridDim.x - 1) / gridDim.x;
-    const long long s0 = min(a.s.samples, (long long)wg * per), s1 = min(a.s.samples, s0 + per);
-    for (long long q = s0 + threadIdx.x; q < s1; q += blockDim.x) {
-        const float2 lc = *reinterpret_cast<const float2 *>(a.s.loc + 2 * q);
-        if (!(lc.x > 0 && lc.x < 1 && lc.y > 0 && lc.y < 1)) continue;  // deformable_aggregation_cuda.cu:166
-        const uint32_t pt = (uint32_t)(q / a.s.cams), cam = (uint32_t)(q - (long long)pt * a.s.cams);
-        const int reg = daf_region_of(g, a.s, lc.x, lc.y, cam);
-        if (FILL) a.s.taps[atomicAdd(&s_bin[reg], 1u)] = (pt << a.s.cam_bits) | cam;
-        else atomicAdd(&s_bin[reg], 1u);
+// DafByRegion: the visible samples, by region; the region count is known to the device only, so M has rows of kDafMaxTiles entries.
+struct DafByRegion {
+    using Args = DafRegionArgs;
+    static __device__ __forceinline__ const DafSortArgs &sort(const Args &a) { return a.s; }
+    static __device__ __forceinline__ int bins(const Args &a) { return a.geom->nregions; }
+    static __device__ __forceinline__ int stride(const Args &) { return kDafMaxTiles; }
+    template <typename F>
+    static __device__ __forceinline__ void visit(const Args &ra, long long s0, long long s1, F &&f)
+    {
+        const DafSortArgs &a = ra.s;
+        const DafRegionGeom g = *ra.geom;
+        const int h0 = a.spatial_shape[0], w0 = a.spatial_shape[1];
+        for (long long q = s0 + threadIdx.x; q < s1; q += blockDim.x) {
+            const float2 lc = *reinterpret_cast<const float2 *>(a.loc + 2 * q);
+            if (!(lc.x > 0 && lc.x < 1 && lc.y > 0 && lc.y < 1)) continue;  // deformable_aggregation_cuda.cu:166
+            const uint32_t pt = (uint32_t)(q / a.cams), cam = (uint32_t)(q - (long long)pt * a.cams);
+            const int wl = (int)floorf(lc.x * w0 - 0.5f), hl = (int)floorf(lc.y * h0 - 0.5f);   // the level-0 tap's own arithmetic
+            const int rx = min(max(wl + 1, 0) >> (3 + g.shift), g.RX - 1);
+            const int ry = min(max(hl + 1, 0) >> (3 + g.shift), g.RY - 1);
+            f((uint32_t)(((int)cam * g.RY + ry) * g.RX + rx), (pt << a.cam_bits) | cam);
+        }
     }
-    if (!FILL) {
-        __syncthreads();
-        for (int t = threadIdx.x; t < ntiles; t += blockDim.x) row[t] = s_bin[t];
-    }
-}
-
-// gf_daf_colscan_kernel for the regions (rows of kDafMaxTiles entries, the region count read from the device)
-__global__ __launch_bounds__(256) void gf_daf_rcolscan_kernel(DafSortArgs a)
-{
-    constexpr int kParts = 8, kPer = kDafBucketWgs / kParts;
-    const int ntiles = (int)a.header[1];
-    const int gidx = blockIdx.x * 256 + threadIdx.x;
-    const int t = gidx / kParts, part = gidx % kParts;
-    const bool live = t < ntiles;
-    const int tc = live ? t : ntiles - 1;
-    uint32_t c[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) c[j] = a.M[(size_t)(part * kPer + j) * kDafMaxTiles + tc];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-        const uint32_t v = c[j];
-        c[j] = sum;
-        sum += v;
-    }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < kParts; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, kParts);
-        if (part >= d) incl += up;
-    }
-    const uint32_t base = incl - sum;
-    if (!live) return;
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) a.M[(size_t)(part * kPer + j) * kDafMaxTiles + t] = base + c[j];
-    if (part == kParts - 1) a.tile_start[t] = incl;
-}
+};
 
 // prefix over the regions and the work-item table.  Items hold up to kRegItem samples of one region; the table lists the FULL
 // items first and the regions' remainders after them, both in region order (the accumulation claims items in table order: full
@@ -855,27 +869,20 @@ __global__ __launch_bounds__(1024) void gf_daf_regionscan_kernel(DafSortArgs a_)
 {
     DafSortArgs a = a_;
     a.ntiles = (int)a.header[1];
-    __shared__ uint32_t s_t[1024], s_f[1024], s_p[1024];
     const int tid = threadIdx.x;
     const int per = (a.ntiles + 1023) / 1024;
     const int t0 = min(a.ntiles, tid * per), t1 = min(a.ntiles, t0 + per);
-    uint32_t st = 0, sf = 0, sp = 0;
+    uint32_t own[3] = {0u, 0u, 0u};   // samples, full items, remainders
     for (int t = t0; t < t1; ++t) {
         const uint32_t c = a.tile_start[t];
-        st += c;
-        sf += c / kRegItem;
-        sp += c % kRegItem ? 1u : 0u;
+        own[0] += c;
+        own[1] += c / kRegItem;
+        own[2] += c % kRegItem ? 1u : 0u;
     }
-    s_t[tid] = st; s_f[tid] = sf; s_p[tid] = sp;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const uint32_t ut = tid >= d ? s_t[tid - d] : 0u, uf = tid >= d ? s_f[tid - d] : 0u, up = tid >= d ? s_p[tid - d] : 0u;
-        __syncthreads();
-        s_t[tid] += ut; s_f[tid] += uf; s_p[tid] += up;
-        __syncthreads();
-    }
-    const uint32_t nfull = s_f[1023];
-    uint32_t run_t = s_t[tid] - st, run_f = s_f[tid] - sf, run_p = nfull + s_p[tid] - sp;
+    uint32_t incl[3] = {own[0], own[1], own[2]}, total[3];
+    daf_block_scan<3>(incl, total);
+    const uint32_t nfull = total[1];
+    uint32_t run_t = incl[0] - own[0], run_f = incl[1] - own[1], run_p = nfull + incl[2] - own[2];
     for (int t = t0; t < t1; ++t) {
         const uint32_t c = a.tile_start[t];
         const uint32_t nf = c / kRegItem;
@@ -886,8 +893,8 @@ __global__ __launch_bounds__(1024) void gf_daf_regionscan_kernel(DafSortArgs a_)
         run_f += nf;
     }
     if (tid == 1023) {
-        a.tile_start[a.ntiles] = s_t[1023];
-        a.header[0] = nfull + s_p[1023];
+        a.tile_start[a.ntiles] = total[0];
+        a.header[0] = nfull + total[2];
         a.header[2] = 0u;   // the accumulation's item counter
     }
 }
@@ -895,12 +902,9 @@ __global__ __launch_bounds__(1024) void gf_daf_regionscan_kernel(DafSortArgs a_)
 #ifdef GF_DAF_TL
 __device__ unsigned long long gf_daf_tl[8 * 16384];   // development: per item, wall-clock stamps of the accumulation's phases
 #define GF_DAF_STAMP(i) do { if (tid == 0 && item < 16384u) gf_daf_tl[8 * item + (i)] = wall_clock64(); } while (0)
-#else
-#define GF_DAF_STAMP(i) do { } while (0)
-#endif
-#ifdef GF_DAF_TL
 #define GF_DAF_PH(i) do { const unsigned long long now_ = wall_clock64(); ph[i] += now_ - phl; phl = now_; } while (0)
 #else
+#define GF_DAF_STAMP(i) do { } while (0)
 #define GF_DAF_PH(i) do { } while (0)
 #endif
 
@@ -1020,10 +1024,9 @@ __global__ __launch_bounds__(512, 4) void gf_daf_raccumulate_kernel(DafRegionArg
                 if (sm < ns && sl < L) {
                     const int h = s_geo[8 * sl + 5], w = s_geo[8 * sl + 6];
                     const float h_im = lc.y * h - 0.5f, w_im = lc.x * w - 0.5f;
-                    const float fh = floorf(h_im), fw = floorf(w_im);
-                    const float lh = h_im - fh, lw = w_im - fw, hh = 1 - lh, hw = 1 - lw;
-                    cw[j] = k == 0 ? hh * hw : k == 1 ? hh * lw : k == 2 ? lh * hw : lh * lw;
-                    const int py = (int)fh + (k >> 1), px = (int)fw + (k & 1);
+                    const Cell cell = make_cell(h_im, w_im);
+                    cw[j] = cell.coef(k);
+                    const int py = cell.py(k), px = cell.px(k);
                     if (py >= 0 && py <= h - 1 && px >= 0 && px <= w - 1) {      // ok1 .. ok4 of make_taps
                         const int lx = px - s_geo[8 * sl], ly = py - s_geo[8 * sl + 1], rw = s_geo[8 * sl + 2];
                         if (lx >= 0 && lx < rw && ly >= 0 && ly < s_geo[8 * sl + 3]) {
@@ -1045,20 +1048,7 @@ __global__ __launch_bounds__(512, 4) void gf_daf_raccumulate_kernel(DafRegionArg
             }
             __syncthreads();
             GF_DAF_PH(1);
-            if (tid < 64) {   // exclusive scan of the <= 192 row counts: three per lane
-                const uint32_t ca = cnt[3 * tid], cb = cnt[3 * tid + 1], cc = cnt[3 * tid + 2];
-                uint32_t incl = ca + cb + cc;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t up = __shfl_up(incl, d, 64);
-                    if (tid >= d) incl += up;
-                }
-                const uint32_t excl = incl - (ca + cb + cc);
-                cnt[3 * tid] = excl;
-                cnt[3 * tid + 1] = excl + ca;
-                cnt[3 * tid + 2] = excl + ca + cb;
-                if (tid == 63) cnt[kRegRows] = incl;
-            }
+            daf_row_offsets<kRegRows / 64>(cnt, tid);   // exclusive scan of the <= 192 row counts: three per lane
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRegSub / (T / 64) / (64 / LPT)) : "memory");   // the weights have landed
             __syncthreads();
             if (tid <= kRegRows + 1) cnt_next[tid] = 0u;   // (last read by the previous batch's row walks)
@@ -1203,14 +1193,22 @@ static DafSortPlan daf_sort_plan(int cams, int num_feat, int C, int L, int pts, 
     return p;
 }
 
-static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
-static int daf_check(int B, int cams, int num_feat, int C, int L, int pts, int G)
+// the plan's tables in a workspace, for ONE batch element: loc / weights / grad_out / grad_feat are set per element
+static DafSortArgs daf_sort_args(const DafSortPlan &p, char *ws, const int *spatial_shape, const int *scale_start, int cams, int num_feat,
+                                 int C, int L, int pts, int G)
 {
-    GF_CHECK_ARG(B >= 0 && cams > 0 && num_feat > 0 && C > 0 && L > 0 && pts >= 0 && G > 0, "bad size");
-    GF_CHECK_ARG(C % G == 0, "num_embeds must be divisible by num_groups");
-    return GF_OK;
+    DafSortArgs sa{};
+    sa.spatial_shape = spatial_shape; sa.scale_start = scale_start;
+    sa.header = (uint32_t *)ws; sa.M = (uint32_t *)(ws + p.off_M); sa.tile_start = (uint32_t *)(ws + p.off_tile_start);
+    sa.item_start = (uint32_t *)(ws + p.off_item_start); sa.item_tile = (uint32_t *)(ws + p.off_item_tile);
+    sa.taps = (uint32_t *)(ws + p.off_taps);
+    sa.cams = cams; sa.num_feat = num_feat; sa.C = C; sa.L = L; sa.pts = pts; sa.G = G;
+    sa.cam_bits = p.cam_bits; sa.lvl_bits = p.lvl_bits; sa.tile_rows = p.tile_rows; sa.ntiles = p.ntiles;
+    sa.samples = (long long)pts * cams;
+    return sa;
 }
+
+static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 static int pick_vec(int C, int G)
 {
@@ -1220,25 +1218,50 @@ static int pick_vec(int C, int G)
     return 1;
 }
 
+// The arguments of an entry point as the kernels take them (the forward passes no gradients, the backward no output), checked:
+// GF_OK and *empty set where there is nothing to do.  total is for `vec` channels per lane.
+static int daf_args(const char *fn, DafArgs &a, bool *empty, int vec, int B, int cams, int num_feat, int C, int L, int pts, int G,
+                    const float *feat, const int *spatial_shape, const int *scale_start, const float *loc, const float *weights,
+                    float *out, const float *grad_out, float *grad_feat, float *grad_loc, float *grad_weights)
+{
+    GF_CHECK_ARG_AS(fn, B >= 0 && cams > 0 && num_feat > 0 && C > 0 && L > 0 && pts >= 0 && G > 0, "bad size");
+    GF_CHECK_ARG_AS(fn, C % G == 0, "num_embeds must be divisible by num_groups");
+    *empty = (long long)B * pts == 0;
+    if (*empty) return GF_OK;
+    GF_CHECK_ARG_AS(fn, feat && spatial_shape && scale_start && loc && weights &&
+                            (out || (grad_out && grad_feat && grad_loc && grad_weights)), "null pointer");
+    a = DafArgs{feat, spatial_shape, scale_start, loc, weights, grad_out, out, grad_feat, grad_loc, grad_weights,
+                B, cams, num_feat, C, L, pts, G, 0};
+    a.total = (long long)B * pts * (C / (vec ? vec : pick_vec(C, G)));
+    GF_CHECK_ARG_AS(fn, (a.total + 255) / 256 < (1ll << 31), "problem too large");
+    return GF_OK;
+}
+
+static unsigned daf_blocks(const DafArgs &a) { return (unsigned)((a.total + 255) / 256); }
+
+// f(integral constant VEC) for the runtime vec (1, 2 or 4): the launches templated on the channels per lane
+template <typename F>
+static void daf_with_vec(int vec, F &&f)
+{
+    if (vec == 4) f(std::integral_constant<int, 4>{});
+    else if (vec == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 1>{});
+}
+
 }  // namespace gf
 
-static int daf_forward_impl(bool pin_groups, int B, int num_cams, int num_feat, int C, int L, int num_pts, int G,
+static int daf_forward_impl(const char *fn, bool pin_groups, int B, int num_cams, int num_feat, int C, int L, int num_pts, int G,
                             const float *mc_ms_feat, const int *spatial_shape, const int *scale_start_index,
                             const float *sampling_location, const float *weights, float *output, void *stream_)
 {
     using namespace gf;
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = daf_check(B, num_cams, num_feat, C, L, num_pts, G)) return rc;
-    if ((long long)B * num_pts == 0) return GF_OK;
-    GF_CHECK_ARG(mc_ms_feat && spatial_shape && scale_start_index && sampling_location && weights && output, "null pointer");
     DafArgs a{};
-    a.feat = mc_ms_feat; a.spatial_shape = spatial_shape; a.scale_start = scale_start_index; a.loc = sampling_location;
-    a.weights = weights; a.out = output; a.B = B; a.cams = num_cams; a.num_feat = num_feat; a.C = C; a.L = L;
-    a.pts = num_pts; a.G = G;
+    bool empty;
+    if (int rc = daf_args(fn, a, &empty, 0, B, num_cams, num_feat, C, L, num_pts, G, mc_ms_feat, spatial_shape, scale_start_index,
+                          sampling_location, weights, output, nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (empty) return GF_OK;
     const int vec = pick_vec(C, G);
-    a.total = (long long)B * num_pts * (C / vec);
-    const long long blocks = (a.total + 255) / 256;
-    GF_CHECK_ARG(blocks < (1ll << 31), "problem too large");
     // channel groups pinned to XCDs (gf_daf_fwd_grouped_kernel) on request, where the layout allows: 4 channels per lane,
     // 1 / 2 / 4 / 8 groups of 32 channels (8 lanes)
     if (pin_groups && vec == 4 && (G == 1 || G == 2 || G == 4 || G == 8) && C / G == 32) {
@@ -1251,13 +1274,13 @@ static int daf_forward_impl(bool pin_groups, int B, int num_cams, int num_feat, 
         // level) is computed by every lane of the point, so half the lanes per point is half of that work -- 139 -> 117 us with
         // projected geometry at 230 400 points, where the kernel is bound by vector-ALU issue (uniform locations: unchanged)
         a.total = (long long)B * num_pts * (C / 8);
-        hipLaunchKernelGGL(gf_daf_fwd4_kernel<8>, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(gf_daf_fwd4_kernel<8>, dim3(daf_blocks(a)), dim3(256), 0, stream, a);
     } else if (vec == 4 && num_cams <= 8)
-        hipLaunchKernelGGL(gf_daf_fwd4_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else if (vec == 4) hipLaunchKernelGGL(gf_daf_fwd_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else if (vec == 2) hipLaunchKernelGGL(gf_daf_fwd_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(gf_daf_fwd_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    GF_CHECK_LAUNCH();
+        hipLaunchKernelGGL(gf_daf_fwd4_kernel<4>, dim3(daf_blocks(a)), dim3(256), 0, stream, a);
+    else daf_with_vec(vec, [&](auto v) {
+        hipLaunchKernelGGL(gf_daf_fwd_kernel<decltype(v)::value>, dim3(daf_blocks(a)), dim3(256), 0, stream, a);
+    });
+    GF_CHECK_LAUNCH_AS(fn);
     return GF_OK;
 }
 
@@ -1266,7 +1289,7 @@ extern "C" int gf_daf_forward(int B, int num_cams, int num_feat, int C, int L, i
                               const int *scale_start_index, const float *sampling_location,
                               const float *weights, float *output, void *stream_)
 {
-    return daf_forward_impl(false, B, num_cams, num_feat, C, L, num_pts, G, mc_ms_feat, spatial_shape, scale_start_index,
+    return daf_forward_impl(__func__, false, B, num_cams, num_feat, C, L, num_pts, G, mc_ms_feat, spatial_shape, scale_start_index,
                             sampling_location, weights, output, stream_);
 }
 
@@ -1275,7 +1298,7 @@ extern "C" int gf_daf_forward_pinned(int B, int num_cams, int num_feat, int C, i
                                      const int *scale_start_index, const float *sampling_location,
                                      const float *weights, float *output, void *stream_)
 {
-    return daf_forward_impl(true, B, num_cams, num_feat, C, L, num_pts, G, mc_ms_feat, spatial_shape, scale_start_index,
+    return daf_forward_impl(__func__, true, B, num_cams, num_feat, C, L, num_pts, G, mc_ms_feat, spatial_shape, scale_start_index,
                             sampling_location, weights, output, stream_);
 }
 
@@ -1287,31 +1310,20 @@ extern "C" int gf_daf_backward(int B, int num_cams, int num_feat, int C, int L, 
 {
     using namespace gf;
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = daf_check(B, num_cams, num_feat, C, L, num_pts, G)) return rc;
-    if ((long long)B * num_pts == 0) return GF_OK;
-    GF_CHECK_ARG(mc_ms_feat && spatial_shape && scale_start_index && sampling_location && weights && grad_output &&
-                     grad_mc_ms_feat && grad_sampling_location && grad_weights, "null pointer");
     DafArgs a{};
-    a.feat = mc_ms_feat; a.spatial_shape = spatial_shape; a.scale_start = scale_start_index; a.loc = sampling_location;
-    a.weights = weights; a.grad_out = grad_output; a.grad_feat = grad_mc_ms_feat; a.grad_loc = grad_sampling_location;
-    a.grad_weights = grad_weights; a.B = B; a.cams = num_cams; a.num_feat = num_feat; a.C = C; a.L = L;
-    a.pts = num_pts; a.G = G;
+    bool empty;
+    if (int rc = daf_args(__func__, a, &empty, 0, B, num_cams, num_feat, C, L, num_pts, G, mc_ms_feat, spatial_shape, scale_start_index,
+                          sampling_location, weights, nullptr, grad_output, grad_mc_ms_feat, grad_sampling_location, grad_weights)) return rc;
+    if (empty) return GF_OK;
     const int vec = pick_vec(C, G);
-    a.total = (long long)B * num_pts * (C / vec);
-    const long long blocks = (a.total + 255) / 256;
-    GF_CHECK_ARG(blocks < (1ll << 31), "problem too large");
     const int lpp = C / vec, lpg = (C / G) / vec;
     // wave-level ownership needs every point / group to be an aligned power-of-two run of lanes
     const bool reduce = is_pow2(lpp) && is_pow2(lpg) && lpp <= 64;
-    if (reduce) {
-        if (vec == 4) hipLaunchKernelGGL((gf_daf_bwd_kernel<4, true>), dim3((unsigned)blocks), dim3(256), 0, stream, a, lpg, lpp);
-        else if (vec == 2) hipLaunchKernelGGL((gf_daf_bwd_kernel<2, true>), dim3((unsigned)blocks), dim3(256), 0, stream, a, lpg, lpp);
-        else hipLaunchKernelGGL((gf_daf_bwd_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, stream, a, lpg, lpp);
-    } else {
-        if (vec == 4) hipLaunchKernelGGL((gf_daf_bwd_kernel<4, false>), dim3((unsigned)blocks), dim3(256), 0, stream, a, 1, 1);
-        else if (vec == 2) hipLaunchKernelGGL((gf_daf_bwd_kernel<2, false>), dim3((unsigned)blocks), dim3(256), 0, stream, a, 1, 1);
-        else hipLaunchKernelGGL((gf_daf_bwd_kernel<1, false>), dim3((unsigned)blocks), dim3(256), 0, stream, a, 1, 1);
-    }
+    daf_with_vec(vec, [&](auto v) {
+        constexpr int VEC = decltype(v)::value;
+        if (reduce) hipLaunchKernelGGL((gf_daf_bwd_kernel<VEC, true>), dim3(daf_blocks(a)), dim3(256), 0, stream, a, lpg, lpp);
+        else hipLaunchKernelGGL((gf_daf_bwd_kernel<VEC, false>), dim3(daf_blocks(a)), dim3(256), 0, stream, a, 1, 1);
+    });
     GF_CHECK_LAUNCH();
     return GF_OK;
 }
@@ -1333,45 +1345,31 @@ extern "C" int gf_daf_backward_sorted(int B, int num_cams, int num_feat, int C, 
 {
     using namespace gf;
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = daf_check(B, num_cams, num_feat, C, L, num_pts, G)) return rc;
-    if ((long long)B * num_pts == 0) return GF_OK;
-    GF_CHECK_ARG(mc_ms_feat && spatial_shape && scale_start_index && sampling_location && weights && grad_output &&
-                     grad_mc_ms_feat && grad_sampling_location && grad_weights, "null pointer");
+    // (1) grad_weights / grad_sampling_location: point-major, reduced in-wave, no atomics
+    DafArgs a{};
+    bool empty;
+    if (int rc = daf_args(__func__, a, &empty, 4, B, num_cams, num_feat, C, L, num_pts, G, mc_ms_feat, spatial_shape, scale_start_index,
+                          sampling_location, weights, nullptr, grad_output, grad_mc_ms_feat, grad_sampling_location, grad_weights)) return rc;
+    if (empty) return GF_OK;
     const DafSortPlan p = daf_sort_plan(num_cams, num_feat, C, L, num_pts, G);
     GF_CHECK_ARG(p.eligible, "shape not supported by the pixel-major backward (gf_daf_backward_workspace_bytes == 0): use gf_daf_backward");
     GF_CHECK_ARG(workspace && workspace_bytes >= p.bytes, "workspace too small (gf_daf_backward_workspace_bytes)");
     GF_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
 
-    // (1) grad_weights / grad_sampling_location: point-major, reduced in-wave, no atomics
-    DafArgs a{};
-    a.feat = mc_ms_feat; a.spatial_shape = spatial_shape; a.scale_start = scale_start_index; a.loc = sampling_location;
-    a.weights = weights; a.grad_out = grad_output; a.grad_feat = grad_mc_ms_feat; a.grad_loc = grad_sampling_location;
-    a.grad_weights = grad_weights; a.B = B; a.cams = num_cams; a.num_feat = num_feat; a.C = C; a.L = L;
-    a.pts = num_pts; a.G = G;
-    a.total = (long long)B * num_pts * (C / 4);
-    const long long blocks = (a.total + 255) / 256;
-    GF_CHECK_ARG(blocks < (1ll << 31), "problem too large");
     const int lpp = C / 4, lpg = (C / G) / 4;
     // eight channels per lane where the layout allows (both kernels are bound by vector-ALU issue with projected geometry, and
     // the tap geometry is computed by every lane of a point: half the lanes, half of that work per point)
     const bool vec8 = C % 8 == 0 && (C / G) % 8 == 0 && is_pow2(C / 8) && is_pow2((C / G) / 8) && C / 8 <= 64;
     if (vec8) {
         a.total = (long long)B * num_pts * (C / 8);
-        hipLaunchKernelGGL((gf_daf_bwd_kernel<8, true, false>), dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, stream, a, (C / G) / 8, C / 8);
-    } else if (is_pow2(lpg)) hipLaunchKernelGGL((gf_daf_bwd_kernel<4, true, false>), dim3((unsigned)blocks), dim3(256), 0, stream, a, lpg, lpp);
-    else hipLaunchKernelGGL((gf_daf_bwd_kernel<4, false, false>), dim3((unsigned)blocks), dim3(256), 0, stream, a, 1, 1);
+        hipLaunchKernelGGL((gf_daf_bwd_kernel<8, true, false>), dim3(daf_blocks(a)), dim3(256), 0, stream, a, (C / G) / 8, C / 8);
+    } else if (is_pow2(lpg)) hipLaunchKernelGGL((gf_daf_bwd_kernel<4, true, false>), dim3(daf_blocks(a)), dim3(256), 0, stream, a, lpg, lpp);
+    else hipLaunchKernelGGL((gf_daf_bwd_kernel<4, false, false>), dim3(daf_blocks(a)), dim3(256), 0, stream, a, 1, 1);
     GF_CHECK_LAUNCH();
 
     // (2) grad_mc_ms_feat, one batch element at a time: bucket the taps by tile, accumulate per tile in LDS
     char *ws = (char *)workspace;
-    DafSortArgs sa{};
-    sa.spatial_shape = spatial_shape; sa.scale_start = scale_start_index;
-    sa.header = (uint32_t *)ws; sa.M = (uint32_t *)(ws + p.off_M); sa.tile_start = (uint32_t *)(ws + p.off_tile_start);
-    sa.item_start = (uint32_t *)(ws + p.off_item_start); sa.item_tile = (uint32_t *)(ws + p.off_item_tile);
-    sa.taps = (uint32_t *)(ws + p.off_taps);
-    sa.cams = num_cams; sa.num_feat = num_feat; sa.C = C; sa.L = L; sa.pts = num_pts; sa.G = G;
-    sa.cam_bits = p.cam_bits; sa.lvl_bits = p.lvl_bits; sa.tile_rows = p.tile_rows; sa.ntiles = p.ntiles;
-    sa.samples = (long long)num_pts * num_cams;
+    DafSortArgs sa = daf_sort_args(p, ws, spatial_shape, scale_start_index, num_cams, num_feat, C, L, num_pts, G);
     static_assert(sizeof(DafRegionGeom) <= 192, "the regions' geometry fits the workspace header");
     const bool by_region = p.region_ok && option(kOptDafBackwardTiles) == 0;   // (gf_set_option("daf.backward_tiles", 1): the tile formulation of round 1 -- also the path of shapes the regions do not take)
     for (int b = 0; b < B; ++b) {
@@ -1382,20 +1380,20 @@ extern "C" int gf_daf_backward_sorted(int B, int num_cams, int num_feat, int C, 
         if (by_region) {
             DafRegionArgs ra{sa, reinterpret_cast<DafRegionGeom *>(ws + 64)};
             hipLaunchKernelGGL(gf_daf_region_geom_kernel, dim3(1), dim3(64), 0, stream, ra);
-            hipLaunchKernelGGL(gf_daf_rbucket_kernel<false>, dim3(kDafBucketWgs), dim3(1024), 0, stream, ra);
-            hipLaunchKernelGGL(gf_daf_rcolscan_kernel, dim3((kDafMaxTiles * 8 + 255) / 256), dim3(256), 0, stream, sa);
+            hipLaunchKernelGGL((gf_daf_bucket_kernel<DafByRegion, false>), dim3(kDafBucketWgs), dim3(1024), 0, stream, ra);
+            hipLaunchKernelGGL(gf_daf_colscan_kernel<DafByRegion>, dim3((kDafMaxTiles * 8 + 255) / 256), dim3(256), 0, stream, ra);
             hipLaunchKernelGGL(gf_daf_regionscan_kernel, dim3(1), dim3(1024), 0, stream, sa);
-            hipLaunchKernelGGL(gf_daf_rbucket_kernel<true>, dim3(kDafBucketWgs), dim3(1024), 0, stream, ra);
+            hipLaunchKernelGGL((gf_daf_bucket_kernel<DafByRegion, true>), dim3(kDafBucketWgs), dim3(1024), 0, stream, ra);
             const unsigned rblocks = 256 * 2;   // persistent, item-strided: two 512-thread workgroups per CU (54 KB of LDS, <= 128 VGPRs)
             if (lpp == 16) hipLaunchKernelGGL(gf_daf_raccumulate_kernel<16>, dim3(rblocks), dim3(512), 0, stream, ra);
             else hipLaunchKernelGGL(gf_daf_raccumulate_kernel<32>, dim3(rblocks), dim3(512), 0, stream, ra);
             GF_CHECK_LAUNCH();
             continue;
         }
-        hipLaunchKernelGGL(gf_daf_bucket_kernel<false>, dim3(kDafBucketWgs), dim3(1024), 0, stream, sa);
-        hipLaunchKernelGGL(gf_daf_colscan_kernel, dim3((p.ntiles * 8 + 255) / 256), dim3(256), 0, stream, sa);
+        hipLaunchKernelGGL((gf_daf_bucket_kernel<DafByTile, false>), dim3(kDafBucketWgs), dim3(1024), 0, stream, sa);
+        hipLaunchKernelGGL(gf_daf_colscan_kernel<DafByTile>, dim3((p.ntiles * 8 + 255) / 256), dim3(256), 0, stream, sa);
         hipLaunchKernelGGL(gf_daf_tilescan_kernel, dim3(1), dim3(1024), 0, stream, sa);
-        hipLaunchKernelGGL(gf_daf_bucket_kernel<true>, dim3(kDafBucketWgs), dim3(1024), 0, stream, sa);
+        hipLaunchKernelGGL((gf_daf_bucket_kernel<DafByTile, true>), dim3(kDafBucketWgs), dim3(1024), 0, stream, sa);
         const unsigned gblocks = 256 * 4;  // persistent, item-strided; the kernel runs at the same rate from 2 to 8 workgroups per CU (bound by row fetches from Infinity Cache)
         if (lpp == 16) hipLaunchKernelGGL(gf_daf_accumulate_kernel<16>, dim3(gblocks), dim3(256), 0, stream, sa);
         else if (lpp == 32) hipLaunchKernelGGL(gf_daf_accumulate_kernel<32>, dim3(gblocks), dim3(256), 0, stream, sa);
