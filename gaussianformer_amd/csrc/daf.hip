@@ -1182,14 +1182,14 @@ static DafSortPlan daf_sort_plan(int cams, int num_feat, int C, int L, int pts, 
     // (one workspace serves both formulations: the region count is only known on the device, so its tables are sized for kDafMaxTiles)
     const unsigned long long nt_max = p.region_ok ? std::max<unsigned long long>(ntiles, kDafMaxTiles) : ntiles;
     const unsigned long long items_max = p.region_ok ? std::max<unsigned long long>(p.max_items, (unsigned long long)pts * cams / kRegItem + kDafMaxTiles + 1) : p.max_items;
-    size_t off = 256;  // header: [0] work items, [1] regions, [2] the region accumulation's item counter; the regions' geometry from byte 64
-    auto take = [&](size_t n) { const size_t o = off; off += (n + 255) & ~(size_t)255; return o; };
-    p.off_M = take((size_t)kDafBucketWgs * nt_max * 4);
-    p.off_tile_start = take((nt_max + 1) * 4);
-    p.off_item_start = take((nt_max + 1) * 4);
-    p.off_item_tile = take(items_max * 4);
-    p.off_taps = take(p.max_taps * 4);
-    p.bytes = off;
+    Carver c(nullptr);  // offsets only: the entry point adds them to the workspace, once per batch element
+    c.skip(256);  // header: [0] work items, [1] regions, [2] the region accumulation's item counter; the regions' geometry from byte 64
+    p.off_M = c.bytes(); c.take<uint32_t>((size_t)kDafBucketWgs * nt_max);
+    p.off_tile_start = c.bytes(); c.take<uint32_t>(nt_max + 1);
+    p.off_item_start = c.bytes(); c.take<uint32_t>(nt_max + 1);
+    p.off_item_tile = c.bytes(); c.take<uint32_t>(items_max);
+    p.off_taps = c.bytes(); c.take<uint32_t>(p.max_taps);
+    p.bytes = c.bytes();
     return p;
 }
 

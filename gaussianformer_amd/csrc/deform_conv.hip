@@ -55,15 +55,14 @@ struct Ws {
 
 inline Ws carve(void *base, const Geom &g, int backward)
 {
-    char *p = (char *)base;
-    size_t off = 0;
+    Carver c(base);
     Ws w;
-    const size_t x = (size_t)g.N * g.H * g.W * g.C * 4, wt = (size_t)g.kk * g.C * g.Co * 4;
-    w.xn = (float *)(p + off); off += align256(x);
-    w.wr = (float *)(p + off); off += align256(wt);
-    w.gin = backward ? (float *)(p + off) : nullptr; off += backward ? align256(x) : 0;
-    w.part = backward ? (float *)(p + off) : nullptr; off += backward ? align256(wt * (size_t)wg_slices(g)) : 0;
-    w.total = off;
+    const size_t x = (size_t)g.N * g.H * g.W * g.C, wt = (size_t)g.kk * g.C * g.Co;
+    w.xn = c.take<float>(x);
+    w.wr = c.take<float>(wt);
+    w.gin = backward ? c.take<float>(x) : nullptr;
+    w.part = backward ? c.take<float>(wt * (size_t)wg_slices(g)) : nullptr;
+    w.total = c.bytes();
     return w;
 }
 
@@ -520,10 +519,8 @@ extern "C" int gf_dcn_forward(int N, int C, int H, int W, int Co, int kh, int kw
     GF_CHECK_ARG(weight, "null weight");
     GF_CHECK_ARG(N == 0 || (input && offset && mask && out), "null input, offset, mask or output");
     const Ws w = carve(workspace, g, 0);
-    if (workspace_bytes < w.total || !workspace) {
-        set_error("%s: workspace of %zu bytes, %zu needed", __func__, workspace_bytes, w.total);
-        return GF_EWORKSPACE;
-    }
+    if (!workspace) return refuse_workspace(__func__, "workspace", workspace_bytes, w.total);  // (a null one: refused like a short one)
+    GF_CHECK_WORKSPACE(workspace_bytes, w.total);
     if (N == 0) return GF_OK;
     const hipStream_t stream = (hipStream_t)stream_;
     relayout(g, input, weight, w, 1, stream);
@@ -547,10 +544,8 @@ extern "C" int gf_dcn_backward(int N, int C, int H, int W, int Co, int kh, int k
     GF_CHECK_ARG(weight, "null weight");
     GF_CHECK_ARG(N == 0 || (input && offset && mask && grad_out), "null input, offset, mask or grad_out");
     const Ws w = carve(workspace, g, 1);
-    if (workspace_bytes < w.total || !workspace) {
-        set_error("%s: workspace of %zu bytes, %zu needed", __func__, workspace_bytes, w.total);
-        return GF_EWORKSPACE;
-    }
+    if (!workspace) return refuse_workspace(__func__, "workspace", workspace_bytes, w.total);  // (a null one: refused like a short one)
+    GF_CHECK_WORKSPACE(workspace_bytes, w.total);
     const hipStream_t stream = (hipStream_t)stream_;
     if (N == 0) {
         if ((grad_weight && hipMemsetAsync(grad_weight, 0, (size_t)Co * C * kh * kw * 4, stream) != hipSuccess) ||

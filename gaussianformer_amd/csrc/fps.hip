@@ -256,10 +256,18 @@ __global__ __launch_bounds__(kFpsThreads) void gf_fps_kernel(FpsArgs a)
 
 }  // namespace gf
 
+// the workspace is ONE section: the points as float4 and, where they end (no rounding up in between), their distances
+static size_t fps_carve(void *workspace, int n, gf::FpsArgs *a)
+{
+    gf::Carver c(workspace);
+    char *s = c.take<char>((size_t)n * (sizeof(float4) + sizeof(float)));
+    if (s) { a->pts = (float4 *)s; a->d = (float *)(s + (size_t)n * sizeof(float4)); }
+    return c.bytes();
+}
+
 extern "C" size_t gf_fps_workspace_bytes(int n)
 {
-    if (n < 0) return 0;
-    return ((size_t)n * (sizeof(float4) + sizeof(float)) + 255) & ~(size_t)255;
+    return n < 0 ? 0 : fps_carve(nullptr, n, nullptr);
 }
 
 extern "C" int gf_farthest_point_sampling(int n, int b, const int *offset_host, const int *new_offset_host, const float *xyz,
@@ -291,14 +299,10 @@ extern "C" int gf_farthest_point_sampling(int n, int b, const int *offset_host, 
     GF_CHECK_ARG(prev == n, "offset[b-1] must equal n");
     if (prev_new == 0) return GF_OK;
     GF_CHECK_ARG(xyz && offset && new_offset && idx && workspace, "null pointer");
-    if (workspace_bytes < gf_fps_workspace_bytes(n)) {
-        set_error("gf_farthest_point_sampling: workspace of %zu bytes, %zu needed", workspace_bytes, gf_fps_workspace_bytes(n));
-        return GF_EWORKSPACE;
-    }
     FpsArgs a{};
+    const size_t need = fps_carve(workspace, n, &a);
+    GF_CHECK_WORKSPACE(workspace_bytes, need);
     a.xyz = xyz; a.offset = offset; a.new_offset = new_offset; a.idx = idx;
-    a.pts = (float4 *)workspace;
-    a.d = (float *)((char *)workspace + (size_t)n * sizeof(float4));
     a.exhaustive = option(kOptFpsExhaustive) != 0;
     hipLaunchKernelGGL(gf_fps_kernel, dim3(b), dim3(kFpsThreads), 0, (hipStream_t)stream_, a);
     GF_CHECK_LAUNCH();

@@ -94,6 +94,17 @@ struct SplatWorkspace {
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// How every op cuts a caller-allocated region into 256-byte aligned sections, in ONE function that both sizes and carves: with a
+// null base (a *_bytes size query) every section is null and only bytes() counts -- no arithmetic is done on a null pointer.
+struct Carver {
+    char *base;
+    size_t off = 0;
+    explicit Carver(void *region) : base((char *)region) {}
+    template <class T> T *take(size_t count) { T *r = base ? (T *)(base + off) : nullptr; off += align256(count * sizeof(T)); return r; }
+    void skip(size_t nbytes) { off += nbytes; }  // a fixed header, taken as it is (not rounded up)
+    size_t bytes() const { return off; }
+};
+
 inline SplatWorkspace carve_workspace(void *base, int P, int N, int H, int W, int D)
 {
     SplatWorkspace ws;
@@ -102,26 +113,25 @@ inline SplatWorkspace carve_workspace(void *base, int P, int N, int H, int W, in
     ws.nsx = (H + kSuper - 1) / kSuper;
     ws.nsy = (W + kSuper - 1) / kSuper;
     ws.nsuper = ws.nsx * ws.nsy;
-    char *p = (char *)base;
-    size_t off = 0;
-    ws.flags = (uint32_t *)(p + off); off += 32768;
-    ws.records = (float *)(p + off); off += align256((size_t)P * kRecDwords * 4);
-    ws.boxes = (uint2 *)(p + off); off += align256((size_t)P * 8);
-    ws.bitmask = (unsigned long long *)(p + off); off += align256((size_t)ws.nsuper * ws.nrow * 8);
+    Carver c(base);
+    ws.flags = c.take<uint32_t>(0); c.skip(32768);
+    ws.records = c.take<float>((size_t)P * kRecDwords);
+    ws.boxes = c.take<uint2>((size_t)P);
+    ws.bitmask = c.take<unsigned long long>((size_t)ws.nsuper * ws.nrow);
     {
         const bool long_rows = ws.nrow > kWRow && ws.nwords <= kLongWords;
         ws.sum_pitch = long_rows ? (((ws.nwords + 3) / 4 + 15) & ~15) : 0;
-        ws.summary = long_rows ? (unsigned char *)(p + off) : nullptr; off += align256((size_t)ws.nsuper * ws.sum_pitch);
+        ws.summary = long_rows ? c.take<unsigned char>((size_t)ws.nsuper * ws.sum_pitch) : nullptr;
     }
-    ws.voxel2pts = (int *)(p + off); off += align256((size_t)H * W * D * 4);
-    ws.vols = (uint32_t *)(p + off); off += align256((size_t)P * 4);
-    ws.bsum = (uint32_t *)(p + off); off += align256((size_t)((P + 255) / 256) * 4);
-    ws.vols_in = (uint32_t *)(p + off); off += align256((size_t)P * 4);
-    ws.order = (int *)(p + off); off += align256((size_t)P * 4);
-    ws.seg = (int *)(p + off); off += align256((size_t)P * 32);
-    ws.sort_hist = (uint32_t *)(p + off); off += align256(((size_t)64 * ((P + 255) / 256) + 64) * 4);
-    ws.dotlg = (float *)(p + off); off += align256((size_t)(N > 0 ? N : 0) * 4);
-    ws.range_flags = (uint32_t *)(p + off); off += align256((size_t)(ws.nwords + 4) * 4);
+    ws.voxel2pts = c.take<int>((size_t)H * W * D);
+    ws.vols = c.take<uint32_t>((size_t)P);
+    ws.bsum = c.take<uint32_t>((size_t)((P + 255) / 256));
+    ws.vols_in = c.take<uint32_t>((size_t)P);
+    ws.order = c.take<int>((size_t)P);
+    ws.seg = c.take<int>((size_t)P * 8);
+    ws.sort_hist = c.take<uint32_t>((size_t)64 * ((P + 255) / 256) + 64);
+    ws.dotlg = c.take<float>((size_t)(N > 0 ? N : 0));
+    ws.range_flags = c.take<uint32_t>((size_t)(ws.nwords + 4));
     // matrix-core backward (rows of <= kWRow bitmask words): a Gaussian whose box meets k double bricks (4 x 4 x 8 voxels)
     // owns k rows; 16 per Gaussian on average plus two whole-grid Gaussians are provided for (the nuScenes configs need
     // ~13.5), what does not fit is accumulated with atomics instead
@@ -131,14 +141,14 @@ inline SplatWorkspace carve_workspace(void *base, int P, int N, int H, int W, in
         const long long cap = ws.nrow <= kWRow ? 16ll * P + 2 * nunits + 1024 : ws.nwords <= kLongWords ? 10ll * P + 2 * nunits + 1024 : 0;
         ws.bwd_cap = (uint32_t)(cap < (1ll << 31) ? cap : (1ll << 31) - 1);
     }
-    ws.bwd_wave_total = (uint32_t *)(p + off); off += align256((size_t)kBwdBigCap * 4);
-    ws.bwd_row_local = (uint32_t *)(p + off); off += align256((size_t)(ws.bwd_cap ? P : 0) * 4);
-    ws.bwd_row_first = (uint32_t *)(p + off); off += align256((size_t)(ws.bwd_cap ? P : 0) * 4);
+    ws.bwd_wave_total = c.take<uint32_t>((size_t)kBwdBigCap);
+    ws.bwd_row_local = c.take<uint32_t>((size_t)(ws.bwd_cap ? P : 0));
+    ws.bwd_row_first = c.take<uint32_t>((size_t)(ws.bwd_cap ? P : 0));
     ws.bwd_pub = ws.nrow <= kWRow ? kBwdList : kBwdPubLong;
-    ws.bwd_lists = (uint32_t *)(p + off); off += align256((size_t)(ws.bwd_cap ? ws.nsuper : 0) * 3 * ws.bwd_pub * 4);
-    ws.bwd_list_len = (uint32_t *)(p + off); off += align256((size_t)(ws.bwd_cap ? ws.nsuper : 0) * 4);
-    ws.bwd_rows = (float *)(p + off); off += align256((size_t)ws.bwd_cap * kBwdRowDwords * 4);
-    ws.total_bytes = off;
+    ws.bwd_lists = c.take<uint32_t>((size_t)(ws.bwd_cap ? ws.nsuper : 0) * 3 * ws.bwd_pub);
+    ws.bwd_list_len = c.take<uint32_t>((size_t)(ws.bwd_cap ? ws.nsuper : 0));
+    ws.bwd_rows = c.take<float>((size_t)ws.bwd_cap * kBwdRowDwords);
+    ws.total_bytes = c.bytes();
     return ws;
 }
 
@@ -193,6 +203,11 @@ bool profile_slot(hipEvent_t *before, hipEvent_t *after);  // gf_api.hip
         }                                                                      \
     } while (0)
 #define GF_CHECK_LAUNCH() GF_CHECK_LAUNCH_AS(__func__)
+
+// a caller-allocated region (`what`: "workspace", "scratch") shorter than the op's carve needs
+inline int refuse_workspace(const char *fn, const char *what, size_t have, size_t need) { set_error("%s: %s of %zu bytes, %zu needed", fn, what, have, need); return GF_EWORKSPACE; }
+#define GF_CHECK_WORKSPACE_AS(fn, what, have, need) do { if ((have) < (need)) return gf::refuse_workspace(fn, what, have, need); } while (0)
+#define GF_CHECK_WORKSPACE(have, need) GF_CHECK_WORKSPACE_AS(__func__, "workspace", have, need)
 
 // ---- a splat call on the host (splat_fwd.hip, splat_bwd.hip, splat_bwd_mfma.hip): its sizes and inputs, filled once by the C entry point
 struct SplatInputs {

@@ -46,23 +46,16 @@ struct LiftParams {
     int *blk;                    // workspace [b][nblk]
 };
 
-struct LiftWs {
-    float *pts;
-    unsigned char *keep;
-    int *blk;
-};
-
-inline size_t carve(LiftWs *w, void *base, int b, int npix, int a)
+// the workspace's size; with a base, its sections as the kernels' parameters hold them
+inline size_t carve(LiftParams *p, void *base, int b, int npix, int a)
 {
-    char *p = (char *)base;
-    size_t off = 0;
     const size_t slots = (size_t)b * npix * a, nb = (size_t)b * num_blocks(npix);
-    LiftWs ws;
-    ws.pts = p ? (float *)(p + off) : nullptr; off += align256(slots * 3 * sizeof(float));
-    ws.keep = p ? (unsigned char *)(p + off) : nullptr; off += align256(slots);
-    ws.blk = p ? (int *)(p + off) : nullptr; off += align256(nb * sizeof(int));
-    if (w) *w = ws;
-    return off;
+    Carver c(base);
+    float *pts = c.take<float>(slots * 3);
+    unsigned char *keep = c.take<unsigned char>(slots);
+    int *blk = c.take<int>(nb);
+    if (p) { p->pts = pts; p->keep = keep; p->blk = blk; }
+    return c.bytes();
 }
 
 // img2lidar @ (u d, v d, d, 1), first three rows
@@ -389,6 +382,7 @@ __global__ void __launch_bounds__(kThreads) gf_pixel_loss_bwd_kernel(LossParams 
 }
 
 inline int loss_parts(int rows) { return (rows + kPixPerBlock - 1) / kPixPerBlock; }
+inline double *loss_carve(Carver &c, int rows) { return c.take<double>((size_t)loss_parts(rows)); }  // the pixel loss's workspace: a partial sum per block
 
 int check_loss(const char *fn, int rows, int nb, int flags, const float *logits, const unsigned char *gt)
 {
@@ -459,28 +453,22 @@ extern "C" int gf_lift_pixels(int b, int n, int h, int w, int S, int a, const fl
             return GF_EINVAL;
         }
     }
-    const size_t need = carve(nullptr, nullptr, b, npix, a);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed", __func__, workspace_bytes, need);
-        return GF_EWORKSPACE;
-    }
-    LiftWs ws;
-    carve(&ws, workspace, b, npix, a);
     LiftParams p{};
+    const size_t need = carve(&p, workspace, b, npix, a);
+    GF_CHECK_WORKSPACE(workspace_bytes, need);
     p.npix = npix; p.hw = h * w; p.w = w; p.h = h; p.S = S; p.a = a;
     for (int i = 0; i < 6; ++i) p.pc[i] = pc_range_host[i];
     p.vs = voxel_size; p.X = X; p.Y = Y; p.Z = Z;
     p.logits = logits; p.img2lidar = img2lidar; p.image_wh = image_wh; p.depth = depth_bins;
     p.occ = occ; p.uniforms = uniforms; p.gt = pixel_gt;
-    p.pts = ws.pts; p.keep = ws.keep; p.blk = ws.blk;
     const hipStream_t stream = (hipStream_t)stream_;
     const int nblk = num_blocks(npix), R = (S + 1 + 63) / 64;
 #define GF_LIFT_LAUNCH(r) hipLaunchKernelGGL(gf_lift_kernel<r>, dim3(nblk, b), dim3(kThreads), 0, stream, p)
     GF_LIFT_DISPATCH(R, GF_LIFT_LAUNCH)
 #undef GF_LIFT_LAUNCH
     if (points) {
-        hipLaunchKernelGGL(gf_lift_scan_kernel, dim3(b), dim3(kThreads), 0, stream, nblk, ws.blk, counts);
-        hipLaunchKernelGGL(gf_lift_write_kernel, dim3(nblk, b), dim3(kThreads), 0, stream, npix, a, ws.pts, ws.keep, ws.blk,
+        hipLaunchKernelGGL(gf_lift_scan_kernel, dim3(b), dim3(kThreads), 0, stream, nblk, p.blk, counts);
+        hipLaunchKernelGGL(gf_lift_write_kernel, dim3(nblk, b), dim3(kThreads), 0, stream, npix, a, p.pts, p.keep, p.blk,
                            counts, points, src);
     }
     GF_CHECK_LAUNCH();
@@ -490,7 +478,9 @@ extern "C" int gf_lift_pixels(int b, int n, int h, int w, int S, int a, const fl
 extern "C" size_t gf_pixel_loss_workspace_bytes(int rows, int bins)
 {
     if (rows < 1 || bins < 1 || bins > GF_LIFT_MAX_BINS) return 0;
-    return gf::align256((size_t)gf::lift::loss_parts(rows) * sizeof(double));
+    gf::Carver c(nullptr);
+    gf::lift::loss_carve(c, rows);
+    return c.bytes();
 }
 
 extern "C" int gf_pixel_loss_forward(int rows, int bins, int flags, const float *logits, const unsigned char *pixel_gt,
@@ -501,15 +491,12 @@ extern "C" int gf_pixel_loss_forward(int rows, int bins, int flags, const float 
     int rc = check_loss(__func__, rows, bins, flags, logits, pixel_gt);
     if (rc != GF_OK) return rc;
     GF_CHECK_ARG(loss && workspace, "null loss or workspace pointer");
-    const size_t need = gf_pixel_loss_workspace_bytes(rows, bins);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed", __func__, workspace_bytes, need);
-        return GF_EWORKSPACE;
-    }
+    Carver c(workspace);
+    double *part = loss_carve(c, rows);
+    GF_CHECK_WORKSPACE(workspace_bytes, c.bytes());
     const hipStream_t stream = (hipStream_t)stream_;
     const LossParams a{rows, bins, flags, logits, pixel_gt};
     const int np = loss_parts(rows), R = (bins + 63) / 64;
-    double *part = (double *)workspace;
 #define GF_LOSS_FWD(r) hipLaunchKernelGGL(gf_pixel_loss_fwd_kernel<r>, dim3(np), dim3(kThreads), 0, stream, a, part)
     GF_LIFT_DISPATCH(R, GF_LOSS_FWD)
 #undef GF_LOSS_FWD

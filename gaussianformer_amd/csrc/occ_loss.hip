@@ -61,35 +61,29 @@ struct OccWs {
 inline int num_blocks(int N) { return (N + kVox - 1) / kVox; }
 inline int num_tiles(int N) { return (N + kTile - 1) / kTile; }
 
-struct Carver {
-    char *p;
-    size_t off = 0;
-    void *take(size_t bytes) { char *r = p ? p + off : nullptr; off += align256(bytes); return r; }
-};
-
-// sizes of both regions; with non-null bases, the section pointers too
-inline void carve(OccWs *w, void *workspace, void *scratch, int L, int N, size_t *workspace_bytes, size_t *scratch_bytes)
+// the sections of both regions (null for a null base) and, where asked for, the regions' sizes
+inline OccWs carve(void *workspace, void *scratch, int L, int N, size_t *workspace_bytes = nullptr, size_t *scratch_bytes = nullptr)
 {
     const size_t S = (size_t)L * kC, NB = num_blocks(N), T = num_tiles(N);
     OccWs ws;
-    Carver a{(char *)workspace};
-    ws.hdr = (int *)a.take(64 * sizeof(int));
-    ws.pos = (int *)a.take((size_t)N * sizeof(int));
-    ws.deriv = (float *)a.take((size_t)L * N * kC * sizeof(float));
-    ws.res = (double *)a.take((2 * (size_t)L + S) * sizeof(double));
-    Carver b{(char *)scratch};
-    ws.blk = (int *)b.take(NB * sizeof(int));
-    ws.blkg = (int *)b.take(NB * kC * sizeof(int));
-    ws.ce_part = (double *)b.take((size_t)L * NB * 2 * sizeof(double));
-    ws.keys[0] = (uint2 *)b.take(S * N * sizeof(uint2));
-    ws.keys[1] = (uint2 *)b.take(S * N * sizeof(uint2));
-    ws.hist = (int *)b.take(S * 256 * T * sizeof(int));
-    ws.tot = (int *)b.take(S * 256 * sizeof(int));
-    ws.fgt = (int *)b.take(S * T * sizeof(int));
-    ws.lov_part = (double *)b.take(S * T * sizeof(double));
-    if (w) *w = ws;
-    if (workspace_bytes) *workspace_bytes = a.off;
-    if (scratch_bytes) *scratch_bytes = b.off;
+    Carver a(workspace);
+    ws.hdr = a.take<int>(64);
+    ws.pos = a.take<int>((size_t)N);
+    ws.deriv = a.take<float>((size_t)L * N * kC);
+    ws.res = a.take<double>(2 * (size_t)L + S);
+    Carver b(scratch);
+    ws.blk = b.take<int>(NB);
+    ws.blkg = b.take<int>(NB * kC);
+    ws.ce_part = b.take<double>((size_t)L * NB * 2);
+    ws.keys[0] = b.take<uint2>(S * N);
+    ws.keys[1] = b.take<uint2>(S * N);
+    ws.hist = b.take<int>(S * 256 * T);
+    ws.tot = b.take<int>(S * 256);
+    ws.fgt = b.take<int>(S * T);
+    ws.lov_part = b.take<double>(S * T);
+    if (workspace_bytes) *workspace_bytes = a.bytes();
+    if (scratch_bytes) *scratch_bytes = b.bytes();
+    return ws;
 }
 
 struct VoxelState { int y; bool kept, lov, ce; };
@@ -568,11 +562,8 @@ int check_common(const char *fn, int L, int N, int C, int flags, const float *co
         if (!pred[l]) { set_error("%s: null prediction pointer of layer %d", fn, l); return GF_EINVAL; }
     if ((flags & GF_OCC_MASK) && !mask) { set_error("%s: GF_OCC_MASK without a mask", fn); return GF_EINVAL; }
     size_t need = 0;
-    carve(nullptr, nullptr, nullptr, L, N, &need, nullptr);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
-        return GF_EWORKSPACE;
-    }
+    carve(nullptr, nullptr, L, N, &need);
+    GF_CHECK_WORKSPACE_AS(fn, "workspace", workspace_bytes, need);
     return GF_OK;
 }
 
@@ -594,7 +585,7 @@ extern "C" size_t gf_occ_loss_workspace_bytes(int L, int N, int C, int flags)
     (void)flags;
     if (C != GF_NUM_CHANNELS || L < 1 || L > GF_OCC_MAX_LAYERS || N < 1 || N > (1 << 28)) return 0;
     size_t w = 0;
-    gf::occ::carve(nullptr, nullptr, nullptr, L, N, &w, nullptr);
+    gf::occ::carve(nullptr, nullptr, L, N, &w);
     return w;
 }
 
@@ -603,7 +594,7 @@ extern "C" size_t gf_occ_loss_scratch_bytes(int L, int N, int C, int flags)
     (void)flags;
     if (C != GF_NUM_CHANNELS || L < 1 || L > GF_OCC_MAX_LAYERS || N < 1 || N > (1 << 28)) return 0;
     size_t b = 0;
-    gf::occ::carve(nullptr, nullptr, nullptr, L, N, nullptr, &b);
+    gf::occ::carve(nullptr, nullptr, L, N, nullptr, &b);
     return b;
 }
 
@@ -621,14 +612,9 @@ extern "C" int gf_occ_loss_forward(int L, int N, int C, int flags, const float *
     GF_CHECK_ARG(loss, "null loss pointer");
     GF_CHECK_ARG(scratch, "null scratch pointer");
     size_t need = 0;
-    carve(nullptr, nullptr, nullptr, L, N, nullptr, &need);
-    if (scratch_bytes < need) {
-        set_error("%s: scratch of %zu bytes, %zu needed", __func__, scratch_bytes, need);
-        return GF_EWORKSPACE;
-    }
+    const OccWs ws = carve(workspace, scratch, L, N, nullptr, &need);
+    GF_CHECK_WORKSPACE_AS(__func__, "scratch", scratch_bytes, need);
     const hipStream_t stream = (hipStream_t)stream_;
-    OccWs ws;
-    carve(&ws, workspace, scratch, L, N, nullptr, nullptr);
     const OccParams a = make_params(L, N, flags, stride_c, stride_n, label, mask, class_weights, ce_weight, lovasz_weight,
                                     lovasz_ignore, ignore_index, empty_label);
     OccPreds preds{};
@@ -669,8 +655,7 @@ extern "C" int gf_occ_loss_backward(int L, int N, int C, int flags, const float 
     if (rc != GF_OK) return rc;
     GF_CHECK_ARG(grad_loss && grad_pred, "null gradient pointer");
     for (int l = 0; l < L; ++l) GF_CHECK_ARG(grad_pred[l], "null gradient pointer of a layer");
-    OccWs ws;
-    carve(&ws, workspace, nullptr, L, N, nullptr, nullptr);
+    const OccWs ws = carve(workspace, nullptr, L, N);
     const OccParams a = make_params(L, N, flags, stride_c, stride_n, label, mask, class_weights, ce_weight, lovasz_weight,
                                     lovasz_ignore, ignore_index, empty_label);
     OccPreds preds{};

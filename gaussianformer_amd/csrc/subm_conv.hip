@@ -67,26 +67,25 @@ struct SubmArgs {
 
 constexpr unsigned long long kSubmOverCapacity = 4ull;  // bit of total[1]
 
-static SubmTables subm_carve(void *base, int N, long long cells, int K3, size_t *bytes)
+static SubmTables subm_carve(void *base, int N, long long cells, int K3, size_t *bytes = nullptr)
 {
-    char *p = (char *)base;
-    size_t off = 0;
+    Carver c(base);
     SubmTables t;
-    t.head = (int *)(p + off); off += align256((size_t)cells * 4);
-    t.next = (int *)(p + off); off += align256((size_t)N * 4);
-    t.next2 = (int *)(p + off); off += align256((size_t)N * 4);
-    t.first2 = (int *)(p + off); off += align256((size_t)N * 4);
-    t.slot_first = (int *)(p + off); off += align256((size_t)N * K3 * 4);
-    t.cnt = (unsigned short *)(p + off); off += align256((size_t)N * K3 * 2);
-    t.kcount = (unsigned long long *)(p + off); off += align256((size_t)K3 * 8);
-    t.kstart = (unsigned int *)(p + off); off += align256((size_t)(K3 + 1) * 4);
-    t.tile_start = (unsigned int *)(p + off); off += align256((size_t)(K3 + 1) * 4);
-    t.kcursor = (unsigned int *)(p + off); off += align256((size_t)K3 * 4);
-    t.kmask = (unsigned char *)(p + off); off += align256((size_t)N * 49);  // K <= 7
-    t.chunk_start = (unsigned int *)(p + off); off += align256((size_t)(K3 + 1) * 4);
-    t.run_start = (unsigned int *)(p + off); off += align256((size_t)(K3 + 1) * 4);
-    t.total = (unsigned long long *)(p + off); off += 256;
-    *bytes = off;
+    t.head = c.take<int>((size_t)cells);
+    t.next = c.take<int>((size_t)N);
+    t.next2 = c.take<int>((size_t)N);
+    t.first2 = c.take<int>((size_t)N);
+    t.slot_first = c.take<int>((size_t)N * K3);
+    t.cnt = c.take<unsigned short>((size_t)N * K3);
+    t.kcount = c.take<unsigned long long>((size_t)K3);
+    t.kstart = c.take<unsigned int>((size_t)(K3 + 1));
+    t.tile_start = c.take<unsigned int>((size_t)(K3 + 1));
+    t.kcursor = c.take<unsigned int>((size_t)K3);
+    t.kmask = c.take<unsigned char>((size_t)N * 49);  // K <= 7
+    t.chunk_start = c.take<unsigned int>((size_t)(K3 + 1));
+    t.run_start = c.take<unsigned int>((size_t)(K3 + 1));
+    t.total = c.take<unsigned long long>(0); c.skip(256);  // the status words: the last 256 bytes
+    if (bytes) *bytes = c.bytes();
     return t;
 }
 
@@ -947,8 +946,7 @@ static SubmArgs subm_args(int N, int batch, int X, int Y, int Z, int K, const in
     a.cells = (long long)batch * X * Y * Z;
     a.indices = indices;
     a.out_lo = 0; a.out_hi = N;
-    size_t bytes;
-    a.t = subm_carve(tables, N, a.cells, a.K3, &bytes);
+    a.t = subm_carve(tables, N, a.cells, a.K3);
     return a;
 }
 
@@ -1176,9 +1174,19 @@ static void launch_gemm(int Cin, int Cout, unsigned blocks, hipStream_t stream, 
 #undef GF_GEMM
 }
 
+// the apply's scratch: every row split into two f16 terms (four bytes per feature), then one exponent per row
+struct SubmScratch { uint4 *rows16; int *row_exp; size_t bytes; };
+static SubmScratch subm_scratch_carve(void *scratch, int N, int Cin)
+{
+    gf::Carver c(scratch);
+    uint4 *rows16 = (uint4 *)c.take<uint32_t>((size_t)N * Cin);
+    int *row_exp = c.take<int>((size_t)N);
+    return {rows16, row_exp, c.bytes()};
+}
+
 extern "C" size_t gf_subm_apply_scratch_bytes(int N, int Cin)
 {
-    return N > 0 && Cin > 0 ? gf::align256((size_t)N * Cin * 4) + gf::align256((size_t)N * 4) : 0;
+    return N > 0 && Cin > 0 ? subm_scratch_carve(nullptr, N, Cin).bytes : 0;
 }
 
 static int subm_conv_apply_impl(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
@@ -1206,9 +1214,10 @@ static int subm_conv_apply_impl(int N, int batch, int X, int Y, int Z, int K, in
         launch_gemm<SubmF32, false>(Cin, Cout, tiles, stream, a, SubmSplit{}, 0);
     } else if (scratch && option(kOptSubmBf16x3) == 0) {
         // two f16 terms, three products (round 6): rows split once into the caller's scratch, then the gather-GEMM on them
-        GF_CHECK_ARG(scratch_bytes >= gf_subm_apply_scratch_bytes(N, Cin) && ((uintptr_t)scratch & 15) == 0, "scratch too small or not 16-byte aligned");
-        uint4 *rows16 = (uint4 *)scratch;
-        int *row_exp = (int *)((char *)scratch + align256((size_t)N * Cin * 4));
+        const SubmScratch sc = subm_scratch_carve(scratch, N, Cin);
+        GF_CHECK_ARG(scratch_bytes >= sc.bytes && ((uintptr_t)scratch & 15) == 0, "scratch too small or not 16-byte aligned");
+        uint4 *rows16 = sc.rows16;
+        int *row_exp = sc.row_exp;
         const SubmSplit sp = {rows16, row_exp};
         const unsigned sblocks = (unsigned)(((long long)N * (Cin / 8) + 255) / 256);
         if (Cin == 128) hipLaunchKernelGGL(gf_subm_split_rows_kernel<128>, dim3(sblocks), dim3(256), 0, stream, features, N, rows16, row_exp);
