@@ -4,6 +4,7 @@ There is NO fallback: if the library is missing or a call fails, a ``RuntimeErro
 raised.  Tensors cross the boundary as raw device pointers + sizes; the stream is torch's
 current HIP stream.
 """
+import collections
 import ctypes
 import os
 
@@ -34,6 +35,11 @@ GF_REFINE_RESTRICT_XYZ, GF_REFINE_XYZ_IDENTITY, GF_REFINE_OPACITY, GF_REFINE_SEM
 GF_ANCHOR_EMBED_DIMS, GF_ANCHOR_EMBED_MAX_S, GF_ANCHOR_EMBED_PARAMS = 128, 32, 48
 GF_PATH_EXACT_TILE, GF_PATH_MATRIX_CORE, GF_PATH_ARBITRARY, GF_PATH_MATRIX_CORE_WAVE, GF_PATH_MATRIX_CORE_PAIR, GF_PATH_MATRIX_CORE_SOLO = 0, 1, 2, 3, 4, 5
 GF_PATHS_MATRIX_CORE = (GF_PATH_MATRIX_CORE, GF_PATH_MATRIX_CORE_WAVE, GF_PATH_MATRIX_CORE_PAIR, GF_PATH_MATRIX_CORE_SOLO)
+GF_STATE_NOT_DENSE, GF_STATE_PATH, GF_STATE_VERDICT, GF_STATE_GENERATION, GF_STATE_ROWS, GF_STATE_WORDS = 0, 1, 2, 3, 4, 5
+GF_VERDICT_POINT, GF_VERDICT_LATTICE, GF_VERDICT_THETA, GF_VERDICT_OPASEM = 1, 2, 4, 8
+GF_ROWS_READY, GF_ROWS_OVERFLOW = 1, 2
+GF_SPLAT_FLAG_BYTES = 32 * 1024
+STATE_USED_BYTES = 4 * GF_STATE_WORDS   # the part of the state block (gf_splat_state_bytes) that carries words
 
 _vp, _i, _sz, _f, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_longlong
 
@@ -230,6 +236,20 @@ def host_copy(words, device):
     event = torch.cuda.Event()
     event.record(torch.cuda.current_stream(device))
     return host, event
+
+
+class SplatState(collections.namedtuple("SplatState", "not_dense path verdict generation rows_ready rows_overflow on_matrix_cores")):
+    """A forward's state block decoded (``include/gf_hip.h``, ``gf_splat_state_bytes``): the ``GF_PATH_*`` value, the ``GF_VERDICT_*``
+    bits, the two ``GF_ROWS_*`` bits as bools; ``on_matrix_cores`` = dense pts and one of ``GF_PATHS_MATRIX_CORE`` rendered."""
+
+    @classmethod
+    def of(cls, src):
+        """From the words as a list of ints (words a caller did not read count as 0), or from a state tensor -- the uint8 block or
+        an int32 view of it: a device tensor is copied to the host here, which SYNCHRONISES with the device."""
+        if isinstance(src, _Tensor):
+            src = (src[:STATE_USED_BYTES].view(torch.int32) if src.dtype == torch.uint8 else src).tolist()
+        nd, path, verdict, gen, rows = ([int(x) for x in src] + [0] * GF_STATE_WORDS)[:GF_STATE_WORDS]
+        return cls(nd != 0, path, verdict, gen, bool(rows & GF_ROWS_READY), bool(rows & GF_ROWS_OVERFLOW), nd == 0 and path in GF_PATHS_MATRIX_CORE)
 
 
 class StreamScratch:

@@ -36,15 +36,50 @@ constexpr int kLongWords = 4096;     // ... and the longest rows (P <= 262 144) 
 constexpr int kBwdRowDwords = 32;    // matrix-core backward: one 128-B row of partial gradients per (Gaussian, double brick)
 constexpr int kBwdBigRows = 512;     // ... a Gaussian with more rows than this is summed by whole workgroups (big list)
 constexpr int kBwdBigCap = 4608;     // ... layout words: one per wave of 64 Gaussians (<= kLongWords), then the table of big Gaussians (splat_bwd_mfma.hip)
-constexpr int kBwdCounters = 5632;   // flag-section index of the matrix-core backward's per-XCD unit counters ([+ 64 x]; the forward's: 4608)
 constexpr int kBwdList = 256;       // candidate-list entries of the matrix-core backward (and of a list the forward publishes for it)
 constexpr int kBwdPubLong = 896;    // ... entries of a list the forward's long-row instantiation publishes (its whole one-pass list; the backward
                                     // takes it in pieces of kBwdList)
-constexpr int kListsBad = 8101;      // flag-section word: a supertile's list did not fit kBwdList (the backward then scans the bitmask rows itself)
-constexpr int kVerdictWords = 8104;  // flag-section index (16-byte aligned) of the single-word verdict block [A, B, V0, V1] of a workspace that was
-                                     // handed over zeroed (GF_WORKSPACE_ZEROED; splat_fwd.hip, "one verdict word")
-constexpr int kGenWord = 8100;       // generation word of a workspace: index into its flag section -- the same word whatever the call's
-                                     // shape; every launch that rewrites the records (or the sections they share with other shapes) bumps it
+
+// ---- protocol words: the splat's state block and the workspace's flag section, each named here once (the two tables: DESIGN.md §3.3d)
+// The state block (include/gf_hip.h, gf_splat_state_bytes): thread 0 of the forward's render kernel writes it, the backward's kernels read it.
+constexpr int kStateNotDense = GF_STATE_NOT_DENSE, kStatePath = GF_STATE_PATH, kStateVerdict = GF_STATE_VERDICT, kStateGen = GF_STATE_GENERATION, kStateRows = GF_STATE_ROWS;
+constexpr uint32_t kRowsReady = GF_ROWS_READY, kRowsOverflow = GF_ROWS_OVERFLOW;
+constexpr uint32_t kVerdictPoint = GF_VERDICT_POINT, kVerdictLattice = GF_VERDICT_LATTICE, kVerdictTheta = GF_VERDICT_THETA, kVerdictOpaSem = GF_VERDICT_OPASEM;
+constexpr uint32_t kVerdictRange = kVerdictTheta | kVerdictOpaSem, kVerdictAll = kVerdictPoint | kVerdictLattice | kVerdictRange;  // every call's; with the point scans'
+// Two predicates on VALUES: a kernel that requests all its words in one round trip and pins them (asm volatile "+s") calls them on what
+// it loaded.  "A matrix-core body rendered the forward" (the two retired paths included: the kernels compare against all four) ...
+constexpr __host__ __device__ __forceinline__ bool on_matrix_cores(uint32_t not_dense, uint32_t path)
+{
+    return not_dense == 0u && (path == (uint32_t)GF_PATH_MATRIX_CORE || path == (uint32_t)GF_PATH_MATRIX_CORE_WAVE ||
+                               path == (uint32_t)GF_PATH_MATRIX_CORE_PAIR || path == (uint32_t)GF_PATH_MATRIX_CORE_SOLO);
+}
+static_assert(!on_matrix_cores(0, 0) && on_matrix_cores(0, 1) && !on_matrix_cores(0, 2) && on_matrix_cores(0, 3) && on_matrix_cores(0, 4) &&
+              on_matrix_cores(0, 5) && !on_matrix_cores(1, 1) && !on_matrix_cores(1, 3), "GF_PATH_* 0..5: all but the exact tile and the arbitrary-points body");
+// ... and "the workspace still holds the records and rows of the forward that wrote this state block" (words kStateGen, kStateRows; kGenWord)
+constexpr __host__ __device__ __forceinline__ bool records_still_there(uint32_t state_gen, uint32_t state_rows, uint32_t gen) { return state_gen == gen && (state_rows & kRowsReady) != 0u; }
+// The same on the words where they lie, for the two kernels that decide on nothing else (the records pass run for a backward, the backward's
+// set-up kernel).  Not a wrapper: it asks for word kStateRows only once the generations agree, and three eager loads are another instruction
+// stream (profiles/splat_protocol_words.txt).
+__device__ __forceinline__ bool records_still_there(const uint32_t *state, const uint32_t *gen_word) { return state[kStateGen] == *gen_word && (state[kStateRows] & kRowsReady) != 0u; }
+
+// The flag section: the first kFlagWords uint32 of a workspace (SplatWorkspace::flags).  Word indices; what lies between the regions is unused.
+constexpr int kFlagWords = GF_SPLAT_FLAG_BYTES / 4;   // 8192
+constexpr int kVerifyBase = 64, kVerifyBlocks = 4096;  // [base, + blocks): one dense-grid verdict word (bits 1 | 2 | 4) per verification wave of the records
+                                                       // pass, render thread t reads 16 of them; PrepArgs / RenderArgs::verify_flags point at the base
+constexpr int kCounterWords = 8 * 64;  // a block of per-XCD counters: XCD x's at [+ 64 x] (one cache line each) ...
+constexpr int kFwdCounters = 4608;     // ... the matrix-core forward's tiles / units (armed by the records pass)
+constexpr int kBwdCounters = 5632;     // ... the matrix-core backward's units (armed by the records pass that lays out its rows, re-armed by its last kernel)
+constexpr int kGenWord = 8100;         // the workspace's generation -- the same word whatever the call's shape; every launch that rewrites the records (or
+                                       // the sections they share with other shapes) bumps it
+constexpr int kListsBad = 8101;        // a supertile's list did not fit kBwdList (the backward then scans the bitmask rows itself)
+constexpr int kVerdictWords = 8104, kVerdictA = 0, kVerdictB = 1, kVerdictV = 2;   // the verdict block [A, B, V0, V1] of a workspace that was handed over
+                                                                                   // zeroed (GF_WORKSPACE_ZEROED; splat_fwd.hip, "one verdict word")
+static_assert(kVerifyBase + kVerifyBlocks <= kFwdCounters && kFwdCounters + kCounterWords <= kBwdCounters && kBwdCounters + kCounterWords <= kGenWord &&
+              kGenWord < kListsBad && kListsBad < kVerdictWords && kVerdictWords + 4 <= kFlagWords, "flag-section regions are disjoint and inside the section");
+static_assert(kVerdictWords % 4 == 0, "the verdict block is read with one 16-byte load");
+constexpr __host__ __device__ uint32_t verdict_slot_after(uint32_t a) { return kVerdictV + ((a + 1u) & 1u); }   // V[(a + 1) & 1]: collects the violations found while A == a
+// flag word k seen through the pointer to the verify region: how the kernels that hold it reach kGenWord and kListsBad without a further argument
+template <class T> __host__ __device__ __forceinline__ T *flag_word_via_verify(T *verify_flags, int k) { return verify_flags + (k - kVerifyBase); }
 
 // record layout (dwords)
 //  0..2 mean xyz | 3 opacity | 4..9 cov (xx,yy,zz,xy,yz,xz) | 10 box lo | 11 box hi (excl.)
@@ -64,7 +99,7 @@ __host__ __device__ __forceinline__ int uz(uint32_t p) { return (int)(p >> 22); 
 
 // workspace carve-up (all sections 256-B aligned)
 struct SplatWorkspace {
-    uint32_t *flags;        // [8192] [64..4160) = dense-grid verdicts, [4608 + 64 x] = tile counter of XCD x
+    uint32_t *flags;        // [kFlagWords] the flag section: see the map above ("protocol words")
     float *records;         // [P][32]
     uint2 *boxes;           // [P]  (lo, hi) packed
     unsigned long long *bitmask;  // [nsuper][nrow]: rows of nwords words, padded to an even count (16-byte aligned rows)
@@ -114,7 +149,7 @@ inline SplatWorkspace carve_workspace(void *base, int P, int N, int H, int W, in
     ws.nsy = (W + kSuper - 1) / kSuper;
     ws.nsuper = ws.nsx * ws.nsy;
     Carver c(base);
-    ws.flags = c.take<uint32_t>(0); c.skip(32768);
+    ws.flags = c.take<uint32_t>(0); c.skip((size_t)kFlagWords * 4);
     ws.records = c.take<float>((size_t)P * kRecDwords);
     ws.boxes = c.take<uint2>((size_t)P);
     ws.bitmask = c.take<unsigned long long>((size_t)ws.nsuper * ws.nrow);

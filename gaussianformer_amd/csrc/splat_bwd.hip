@@ -62,8 +62,7 @@ struct BwdArgs {
 __device__ __forceinline__ bool gated_off(const BwdArgs &a)
 {
     if (!a.gate || a.state == nullptr) return false;
-    const uint32_t w = a.state[1];
-    return a.state[0] == 0u && (w == (uint32_t)GF_PATH_MATRIX_CORE || w == (uint32_t)GF_PATH_MATRIX_CORE_WAVE || w == (uint32_t)GF_PATH_MATRIX_CORE_PAIR || w == (uint32_t)GF_PATH_MATRIX_CORE_SOLO);
+    return on_matrix_cores(a.state[kStateNotDense], a.state[kStatePath]);
 }
 
 constexpr int kBwdMaxBlk = 1024;  // LDS prefix capacity: P <= 262 144 Gaussians
@@ -129,7 +128,7 @@ __device__ __forceinline__ bool pts_are_dense(const BwdArgs &a)
 {
     if (a.force_general) return false;
     if (a.assume_dense) return true;
-    return a.state != nullptr && a.state[0] == 0u;
+    return a.state != nullptr && a.state[kStateNotDense] == 0u;
 }
 
 // voxel2pts = -1, then voxel2pts[voxel(n)] = n with the highest point index winning

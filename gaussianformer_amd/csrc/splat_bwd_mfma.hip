@@ -113,18 +113,6 @@ __device__ __forceinline__ void split16(const f32x16 &d, H8 (&hi)[2], H8 (&lo)[2
     }
 }
 
-__device__ __forceinline__ bool state_is_matrix_core(const uint32_t *state)
-{
-    const uint32_t w = state[1];
-    return state[0] == 0u && (w == (uint32_t)GF_PATH_MATRIX_CORE || w == (uint32_t)GF_PATH_MATRIX_CORE_WAVE || w == (uint32_t)GF_PATH_MATRIX_CORE_PAIR || w == (uint32_t)GF_PATH_MATRIX_CORE_SOLO);
-}
-
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ bool records_still_there(const uint32_t *state, const uint32_t *gen_word)
-{
-    return state[3] == *gen_word && (state[4] & 1u) != 0u;
-}
-
 // ---------------------------------------------------------------------------------------
 // Behind the backward's own records pass (i.e. only when the workspace no longer held the forward's): the first row of every
 // Gaussian from the pass's layout words (prefix of the per-wave totals + the Gaussian's offset in its wave; 0xFFFFFFFF = the
@@ -143,7 +131,7 @@ struct BwdSetupArgs {
 
 __global__ __launch_bounds__(256) void gf_splat_bwd_setup_kernel(BwdSetupArgs a)
 {
-    if (!state_is_matrix_core(a.state)) return;
+    if (!on_matrix_cores(a.state[kStateNotDense], a.state[kStatePath])) return;
     // (the generation word is bumped by the LAST kernel of such a backward, gf_splat_bwd_rows_kernel: every workgroup here
     // compares it with the state block's copy)
     if (records_still_there(a.state, a.gen_word)) return;
@@ -258,12 +246,13 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
 
     // (all the words the start of a wave decides on in ONE round trip -- gate, asserted records, published lists: as three
     // conditions in a row each was a scalar load of its own, waited for before the next was requested)
-    uint32_t st0 = a.state[0], st1 = a.state[1], st3 = a.state[3], st4 = a.state[4], gen = *a.gen_word;
+    uint32_t st0 = a.state[kStateNotDense], st1 = a.state[kStatePath], st3 = a.state[kStateGen], st4 = a.state[kStateRows], gen = *a.gen_word;
     uint32_t lbad = a.lists ? *a.lists_bad : 1u;
     asm volatile("" : "+s"(st0), "+s"(st1), "+s"(st3), "+s"(st4), "+s"(gen), "+s"(lbad));
-    const bool mc_fwd = st0 == 0u && (st1 == (uint32_t)GF_PATH_MATRIX_CORE || st1 == (uint32_t)GF_PATH_MATRIX_CORE_WAVE ||
-                                      st1 == (uint32_t)GF_PATH_MATRIX_CORE_PAIR || st1 == (uint32_t)GF_PATH_MATRIX_CORE_SOLO);
-    const bool still_there = st3 == gen && (st4 & 1u) != 0u;   // (records_still_there)
+    const bool mc_fwd = on_matrix_cores(st0, st1);
+    // (records_still_there(st3, st4, gen), spelled out: through the call this kernel's scalar code comes out four bytes longer --
+    // the one site that keeps its own text, profiles/splat_protocol_words.txt)
+    const bool still_there = st3 == gen && (st4 & kRowsReady) != 0u;
     if (a.gate && !mc_fwd) return;
     if (a.records_asserted && !still_there) return;
 
@@ -1052,15 +1041,13 @@ __global__ __launch_bounds__(256) void gf_splat_bwd_rows_kernel(BwdRowsArgs a)
     const int tid = threadIdx.x;
     const bool gauss_range = (int)blockIdx.x < a.ngauss_blocks;
     const int g_own = min((int)blockIdx.x * 32 + (tid >> 3), a.P - 1);
-    uint32_t st0 = a.state[0], st1 = a.state[1], st3 = a.state[3], st4 = a.state[4], gen = *a.gen_word;
+    uint32_t st0 = a.state[kStateNotDense], st1 = a.state[kStatePath], st3 = a.state[kStateGen], st4 = a.state[kStateRows], gen = *a.gen_word;
     // (the workgroups past the Gaussian range: the gradient kernel's table of big Gaussians, one word per thread)
     uint32_t tab_n = gauss_range ? 0u : a.big_table[0], tab_w = gauss_range ? 0u : a.big_table[1 + min(tid, 3 * 64 - 1)];
     uint32_t first_own = a.row_first[gauss_range ? g_own : 0];
     float4 rec2_own = *reinterpret_cast<const float4 *>(a.records + (size_t)(gauss_range ? g_own : 0) * kRecDwords + 8);
     asm volatile("" : "+s"(st0), "+s"(st1), "+s"(st3), "+s"(st4), "+s"(gen), "+v"(first_own), "+v"(rec2_own.z), "+v"(rec2_own.w), "+v"(tab_n), "+v"(tab_w));
-    const bool mc = st0 == 0u && (st1 == (uint32_t)GF_PATH_MATRIX_CORE || st1 == (uint32_t)GF_PATH_MATRIX_CORE_WAVE ||
-                                  st1 == (uint32_t)GF_PATH_MATRIX_CORE_PAIR || st1 == (uint32_t)GF_PATH_MATRIX_CORE_SOLO);
-    const bool still_there = st3 == gen && (st4 & 1u) != 0u;   // (records_still_there)
+    const bool mc = on_matrix_cores(st0, st1), still_there = records_still_there(st3, st4, gen);
     if (a.gate == 1 && !mc) return;
     // a caller's assertion that does not hold (not a matrix-core forward, or the workspace has been used since): NaN, not numbers
     const bool bad = (a.gate == 2 && !mc) || (a.records_asserted && !still_there);

@@ -50,7 +50,7 @@ struct PrepArgs {
     float *records;
     uint2 *boxes;
     unsigned long long *bitmask;
-    uint32_t *verify_flags;  // [kVerifyBlocks]: bit 0 = a point is not in its voxel, bit 1 = pts is not an exact affine lattice
+    uint32_t *verify_flags;  // [kVerifyBlocks] (flags + kVerifyBase): kVerdictPoint = a point is not in its voxel, kVerdictLattice = pts is not an exact affine lattice
     int P, N, H, W, D, nwords, nrow, nsx, nsy, per_axis, variant, nprep_blocks, verify, prescale, exact_det, lattice;
     uint32_t *tile_counters;  // null, or the eight per-XCD tile counters of the matrix-core render kernel ...
     uint32_t tile_counter_init;  // ... and the value they start from (the workgroups per XCD: those tiles are taken)
@@ -71,7 +71,6 @@ struct PrepArgs {
                              // they are checked in the records pass on EVERY call, GF_PTS_ASSUME_DENSE included)
 };
 
-constexpr int kVerifyBlocks = 4096;    // verification waves; render thread t reads 16 verdicts
 constexpr int kPrepSuperChunk = 4096;  // bitmask words in LDS per pass of the prep kernel (32 KB)
 
 // Integer box of Gaussian g: model/head/localagg/src/auxiliary.h:8-20 (scalar radius) and
@@ -120,7 +119,7 @@ __device__ __forceinline__ uint32_t range_bits_of(const float *c, const float *s
         snan |= !(v == v);
         smax = fmaxf(smax, v);
     }
-    return ((!(bound < 3.0e4f) || !(Q < 1331.4f)) ? 4u : 0u) | ((snan || !(smax < kSemRangeMax)) ? 8u : 0u);
+    return ((!(bound < 3.0e4f) || !(Q < 1331.4f)) ? kVerdictTheta : 0u) | ((snan || !(smax < kSemRangeMax)) ? kVerdictOpaSem : 0u);
 }
 
 // STAGED: the records of a wave's 64 Gaussians pass through an LDS image (coalesced loads and stores: large P); !STAGED: each lane
@@ -140,9 +139,8 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
     if (a.gate_state) {
         // backward: the records of the forward that wrote this state block are still in the workspace (same generation) --
         // nothing to redo; or that forward was not rendered on the matrix cores -- the Gaussian-major kernels need no records
-        const bool mc = a.gate_state[0] == 0u && (a.gate_state[1] == (uint32_t)GF_PATH_MATRIX_CORE || a.gate_state[1] == (uint32_t)GF_PATH_MATRIX_CORE_WAVE ||
-                                                  a.gate_state[1] == (uint32_t)GF_PATH_MATRIX_CORE_PAIR || a.gate_state[1] == (uint32_t)GF_PATH_MATRIX_CORE_SOLO);
-        if (!mc || (a.gate_state[3] == *a.gen_word && (a.gate_state[4] & 1u))) return;
+        if (!on_matrix_cores(a.gate_state[kStateNotDense], a.gate_state[kStatePath]) ||
+            records_still_there(a.gate_state, a.gen_word)) return;
     } else if (a.gen_word && blockIdx.x == 0 && threadIdx.x == 0) {
         *a.gen_word = *a.gen_word + 1u;   // (any start value will do: the word only has to change)
     }
@@ -228,7 +226,7 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
         if (a.lattice) {
             const float lx_ = fabsf((float)sx), ly_ = fabsf((float)sy), lz_ = fabsf((float)sz);
             const float zero[kC] = {0.f};
-            if (has_g) rbits |= range_bits_of(c0, zero, 0.f, rr0, rr1, rr2, a.H, a.W, a.D, lx_, ly_, lz_) & 4u;
+            if (has_g) rbits |= range_bits_of(c0, zero, 0.f, rr0, rr1, rr2, a.H, a.W, a.D, lx_, ly_, lz_) & kVerdictTheta;
 #pragma nounroll
             for (int g = g0 + kVerifyBlocks * 64; g < a.P; g += kVerifyBlocks * 64) {   // (P > 262 144 only)
                 const float *cv = a.cov3D + 6 * (size_t)g;
@@ -236,14 +234,14 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
                 float c[6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) c[j] = cv[j];
-                rbits |= range_bits_of(c, zero, 0.f, r0, r1, r2, a.H, a.W, a.D, lx_, ly_, lz_) & 4u;
+                rbits |= range_bits_of(c, zero, 0.f, r0, r1, r2, a.H, a.W, a.D, lx_, ly_, lz_) & kVerdictTheta;
             }
         }
         const unsigned long long any = __builtin_amdgcn_ballot_w64(bad), any2 = __builtin_amdgcn_ballot_w64(bad_lattice),
-                                 any3 = __builtin_amdgcn_ballot_w64((rbits & 4u) != 0u);
-        const uint32_t vbits = (any ? 1u : 0u) | (any2 ? 2u : 0u) | (any3 ? 4u : 0u);
+                                 any3 = __builtin_amdgcn_ballot_w64((rbits & kVerdictTheta) != 0u);
+        const uint32_t vbits = (any ? kVerdictPoint : 0u) | (any2 ? kVerdictLattice : 0u) | (any3 ? kVerdictTheta : 0u);
         if (lane == 0) a.verify_flags[vb] = vbits;
-        if (a.verdict_words && vbits && lane == 0) atomicOr(a.verdict_words + 2 + ((a.verdict_words[0] + 1u) & 1u), vbits);   // (rare)
+        if (a.verdict_words && vbits && lane == 0) atomicOr(a.verdict_words + verdict_slot_after(a.verdict_words[kVerdictA]), vbits);   // (rare)
         return;
     }
     if (a.tile_counters && blockIdx.x == 0 && threadIdx.x < 8) a.tile_counters[64 * threadIdx.x] = a.tile_counter_init;
@@ -255,7 +253,7 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
     // every render wave reads the block with one load and takes V[B & 1] (B is not written during the render launch), render
     // workgroup 0 stores A = B and clears the OTHER word, V[(B + 1) & 1] -- the one the next call's violators will use.  All the
     // state lives on the device, so a replayed HIP graph behaves like an eager call.
-    if (a.verdict_words && blockIdx.x == 0 && threadIdx.x == 0) a.verdict_words[1] = a.verdict_words[0] + 1u;
+    if (a.verdict_words && blockIdx.x == 0 && threadIdx.x == 0) a.verdict_words[kVerdictB] = a.verdict_words[kVerdictA] + 1u;
     const int word = blockIdx.x * WAVES + wave;  // bitmask word of this wave
     const int g = word * 64 + lane;
     const bool valid = g < a.P;
@@ -370,7 +368,7 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
         if (lane == 63) a.unit_totals[word] = (uint32_t)incl | (any_big ? 0x80000000u : 0u);
         if (valid) a.unit_local[g] = unit_first;
         if (blockIdx.x == 0 && threadIdx.x < 8) a.bwd_counters[64 * threadIdx.x] = a.bwd_counter_init;
-        if (blockIdx.x == 0 && threadIdx.x == 8) a.verify_flags[kListsBad - 64] = 0u;   // (verify_flags = flags + 64)
+        if (blockIdx.x == 0 && threadIdx.x == 8) *flag_word_via_verify(a.verify_flags, kListsBad) = 0u;
     }
     // supertile range touched by the box
     const int sx_lo = lo[0] / kSuper, sx_hi = nonempty ? (hi[0] - 1) / kSuper : -1;
@@ -515,11 +513,11 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
     if (a.range_flags) {
         // one word per wave of 64 Gaussians, stored unconditionally (nothing to zero); the last wave also clears the
         // padding the render kernels' 16-byte reads cover
-        const unsigned long long b2 = __builtin_amdgcn_ballot_w64((range_bits & 4u) != 0u),
-                                 b3 = __builtin_amdgcn_ballot_w64((range_bits & 8u) != 0u);
-        if (lane == 0 && word < a.nwords) a.range_flags[word] = (b2 ? 4u : 0u) | (b3 ? 8u : 0u);
+        const unsigned long long b2 = __builtin_amdgcn_ballot_w64((range_bits & kVerdictTheta) != 0u),
+                                 b3 = __builtin_amdgcn_ballot_w64((range_bits & kVerdictOpaSem) != 0u);
+        if (lane == 0 && word < a.nwords) a.range_flags[word] = (b2 ? kVerdictTheta : 0u) | (b3 ? kVerdictOpaSem : 0u);
         if (a.verdict_words && (b2 | b3) && lane == 0)   // (rare)
-            atomicOr(a.verdict_words + 2 + ((a.verdict_words[0] + 1u) & 1u), (b2 ? 4u : 0u) | (b3 ? 8u : 0u));
+            atomicOr(a.verdict_words + verdict_slot_after(a.verdict_words[kVerdictA]), (b2 ? kVerdictTheta : 0u) | (b3 ? kVerdictOpaSem : 0u));
         if (word == a.nwords - 1 && lane >= 1 && lane <= 3) a.range_flags[a.nwords - 1 + lane] = 0u;
     }
     const unsigned long long mybit = 1ull << lane;
@@ -612,9 +610,9 @@ struct RenderArgs {
 // boxes and bitmask are still there and the records pass is not repeated.
 __device__ __forceinline__ void stamp_state(const RenderArgs &a, uint32_t rows_ready = 0u)
 {
-    a.state[3] = a.verify_flags[kGenWord - 64];   // (verify_flags = flags + 64)
-    a.state[4] = rows_ready;   // bit 0: every Gaussian's first row is in the workspace and the rows fit the buffer; bit 1: the layout was
-                               // taken and the rows do NOT fit (a caller does better with the Gaussian-major backward then)
+    a.state[kStateGen] = *flag_word_via_verify(a.verify_flags, kGenWord);
+    a.state[kStateRows] = rows_ready;   // kRowsReady: every Gaussian's first row is in the workspace and the rows fit the buffer; kRowsOverflow: the
+                                        // layout was taken and the rows do NOT fit (a caller does better with the Gaussian-major backward then)
 }
 
 // The matrix-core backward's row layout, finished inside the forward: the records pass left the rows each wave of 64 Gaussians
@@ -943,9 +941,9 @@ template <int VARIANT, int EXP, bool LABELS>
 __global__ __launch_bounds__(kBlock) void gf_splat_render_general_kernel(RenderArgs a)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.state) {
-        a.state[0] = 1u;
-        a.state[1] = GF_PATH_ARBITRARY;
-        a.state[2] = 0u;
+        a.state[kStateNotDense] = 1u;
+        a.state[kStatePath] = GF_PATH_ARBITRARY;
+        a.state[kStateVerdict] = 0u;
         stamp_state(a);
     }
     general_body<VARIANT, EXP, LABELS>(a);
@@ -1005,9 +1003,9 @@ __global__ __launch_bounds__(kBlock, kRenderWavesPerSimd) void gf_splat_render_k
     int nondense = 0;
     if (a.verify_dense) nondense = __syncthreads_or(((vf.x | vf.y | vf.z | vf.w) & 1u) != 0u);
     if (blockIdx.x == 0 && tid == 0 && a.state) {
-        a.state[0] = nondense ? 1u : 0u;
-        a.state[1] = nondense ? GF_PATH_ARBITRARY : GF_PATH_EXACT_TILE;
-        a.state[2] = nondense ? 1u : 0u;
+        a.state[kStateNotDense] = nondense ? 1u : 0u;
+        a.state[kStatePath] = nondense ? GF_PATH_ARBITRARY : GF_PATH_EXACT_TILE;
+        a.state[kStateVerdict] = nondense ? kVerdictPoint : 0u;
         stamp_state(a);
     }
     if (nondense) {
@@ -1340,26 +1338,26 @@ __global__ __launch_bounds__(kBlock, 2) void gf_splat_render_mfma_kernel(RenderA
     int verdict = 0;
     if (a.verify_dense) {
         const uint32_t v = vf.x | vf.y | vf.z | vf.w;
-        verdict = (__syncthreads_or((v & 1u) != 0u) ? 1 : 0) | (__syncthreads_or((v & 2u) != 0u) ? 2 : 0);
+        verdict = (__syncthreads_or((v & kVerdictPoint) != 0u) ? kVerdictPoint : 0) | (__syncthreads_or((v & kVerdictLattice) != 0u) ? kVerdictLattice : 0);
     }
     // ... and of its records pass (every call): bit 2 = a Gaussian's theta, bit 3 = its opacity * semantics may leave the f16 range
     int range_bits = 0;
     if (a.verify_dense) rangev |= vf.x | vf.y | vf.z | vf.w;   // (the verification waves report the range bits themselves when they run)
     if (a.range_flags || a.verify_dense)
-        range_bits = (__syncthreads_or((rangev & 4u) != 0u) ? 4 : 0) | (__syncthreads_or((rangev & 8u) != 0u) ? 8 : 0);
+        range_bits = (__syncthreads_or((rangev & kVerdictTheta) != 0u) ? kVerdictTheta : 0) | (__syncthreads_or((rangev & kVerdictOpaSem) != 0u) ? kVerdictOpaSem : 0);
     const int nondense = verdict | range_bits;
     if (blockIdx.x == 0 && tid == 0 && a.state) {
-        a.state[0] = (verdict & 1) ? 1u : 0u;
-        a.state[1] = nondense ? GF_PATH_ARBITRARY : GF_PATH_MATRIX_CORE;
+        a.state[kStateNotDense] = (verdict & kVerdictPoint) ? 1u : 0u;
+        a.state[kStatePath] = nondense ? GF_PATH_ARBITRARY : GF_PATH_MATRIX_CORE;
         stamp_state(a);
     }
     if (blockIdx.x == 0 && a.state && a.verify_dense) {
         // the exact verdict bits, for the caller's diagnostics
         const uint32_t v = vf.x | vf.y | vf.z | vf.w;
-        const int b1 = __syncthreads_or((v & 2u) != 0u);
-        if (tid == 0) a.state[2] = (uint32_t)((verdict & 1) | (b1 ? 2 : 0) | range_bits);
+        const int b1 = __syncthreads_or((v & kVerdictLattice) != 0u);
+        if (tid == 0) a.state[kStateVerdict] = (uint32_t)((verdict & kVerdictPoint) | (b1 ? kVerdictLattice : 0) | range_bits);
     } else if (blockIdx.x == 0 && tid == 0 && a.state) {
-        a.state[2] = (uint32_t)range_bits;
+        a.state[kStateVerdict] = (uint32_t)range_bits;
     }
     if (nondense) {
         general_body<GF_SPLAT_BASE, kExpComp, LABELS>(a);
@@ -1986,11 +1984,11 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     if (a.verdict_words) {
         // one verdict word (gf_splat_prep_kernel): [A, B, V0, V1], one 16-byte load, the same address in every lane
         const uint4 vw = *reinterpret_cast<const uint4 *>(a.verdict_words);
-        const uint32_t vv = (vw.y & 1u) ? vw.w : vw.z;
-        verdict = __builtin_amdgcn_readfirstlane((int)(vv & (a.verify_dense ? 15u : 12u)));
+        const uint32_t vv = (vw.y & 1u) ? vw.w : vw.z;   // V[B & 1]
+        verdict = __builtin_amdgcn_readfirstlane((int)(vv & (a.verify_dense ? kVerdictAll : kVerdictRange)));
         if (blockIdx.x == 0 && lane == 0) {   // A = B; the word the NEXT call's violators will use starts from zero
-            a.verdict_words[0] = vw.y;
-            a.verdict_words[2 + ((vw.y + 1u) & 1u)] = 0u;
+            a.verdict_words[kVerdictA] = vw.y;
+            a.verdict_words[verdict_slot_after(vw.y)] = 0u;
         }
     } else {
         uint32_t v = 0u, rv = 0u;
@@ -2010,21 +2008,21 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
         }
         rv = r0.x | r0.y | r0.z | r0.w | r1.x | r1.y | r1.z | r1.w | r2.x | r2.y | r2.z | r2.w;
         rv |= v;   // (the verification waves report the range bits themselves when they run)
-        verdict = (__builtin_amdgcn_ballot_w64((v & 1u) != 0u) ? 1 : 0) | (__builtin_amdgcn_ballot_w64((v & 2u) != 0u) ? 2 : 0) |
-                  (__builtin_amdgcn_ballot_w64((rv & 4u) != 0u) ? 4 : 0) | (__builtin_amdgcn_ballot_w64((rv & 8u) != 0u) ? 8 : 0);
+        verdict = (__builtin_amdgcn_ballot_w64((v & kVerdictPoint) != 0u) ? kVerdictPoint : 0) | (__builtin_amdgcn_ballot_w64((v & kVerdictLattice) != 0u) ? kVerdictLattice : 0) |
+                  (__builtin_amdgcn_ballot_w64((rv & kVerdictTheta) != 0u) ? kVerdictTheta : 0) | (__builtin_amdgcn_ballot_w64((rv & kVerdictOpaSem) != 0u) ? kVerdictOpaSem : 0);
     }
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(q0x), "+v"(q0y), "+v"(q0z), "+v"(q1x), "+v"(q1y), "+v"(q1z)::"memory");   // (landed with the verdict words)
     uint32_t rows_ready = 0u;
     if (PREP && blockIdx.x < (unsigned)kRowLayoutBlocks && a.rows_valid && !verdict) {   // (slot area of the LDS block: idle until the first list is built)
-        rows_ready = (LONG ? finish_row_layout_long(a, s_u, lane) : finish_row_layout(a, s_u, lane)) ? 1u : 2u;
+        rows_ready = (LONG ? finish_row_layout_long(a, s_u, lane) : finish_row_layout(a, s_u, lane)) ? kRowsReady : kRowsOverflow;
         // (long rows: the prefix took s_u[0, nwords), over the prefetched summary row past kLSumAt words -- landed before the
         // prefix was written, by the wait above -- so the first unit requests it again, like any later unit)
         if (LONG && a.nwords > kLSumAt) row_there = false;
     }
     if (blockIdx.x == 0 && lane == 0 && a.state) {
-        a.state[0] = (verdict & 1) ? 1u : 0u;
-        a.state[1] = verdict ? GF_PATH_ARBITRARY : GF_PATH_MATRIX_CORE_WAVE;
-        a.state[2] = (uint32_t)verdict;
+        a.state[kStateNotDense] = (verdict & kVerdictPoint) ? 1u : 0u;
+        a.state[kStatePath] = verdict ? GF_PATH_ARBITRARY : GF_PATH_MATRIX_CORE_WAVE;
+        a.state[kStateVerdict] = (uint32_t)verdict;
         stamp_state(a, rows_ready);
     }
     if (verdict) {
@@ -2414,7 +2412,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         if (lane == 0) a.pub_len[s] = (uint32_t)list_len;
                     } else if (lane == 0) {
                         if (LONG) a.pub_len[s] = 0xFFFFFFFFu;   // (this supertile only: its units of the backward read the row themselves)
-                        else atomicOr(const_cast<uint32_t *>(a.verify_flags) + (kListsBad - 64), 1u);
+                        else atomicOr(const_cast<uint32_t *>(flag_word_via_verify(a.verify_flags, kListsBad)), 1u);
                     }
                 }
 #if GF_TIMELINE
@@ -2830,7 +2828,7 @@ static PrepArgs fill_prep_args(const SplatInputs &in, const SplatWorkspace &ws)
     PrepArgs pa{};
     pa.means3D = in.means3D; pa.means_int = in.means3D_int; pa.opacity = in.opacity; pa.semantics = in.semantics;
     pa.radii = in.radii; pa.cov3D = in.cov3D; pa.points_int = in.points_int; pa.pts = in.pts; pa.records = ws.records; pa.boxes = ws.boxes;
-    pa.bitmask = ws.bitmask; pa.verify_flags = ws.flags + 64; pa.P = in.P; pa.N = in.N; pa.H = in.H; pa.W = in.W; pa.D = in.D;
+    pa.bitmask = ws.bitmask; pa.verify_flags = ws.flags + kVerifyBase; pa.P = in.P; pa.N = in.N; pa.H = in.H; pa.W = in.W; pa.D = in.D;
     pa.nwords = ws.nwords; pa.nrow = ws.nrow; pa.nsx = ws.nsx; pa.nsy = ws.nsy; pa.per_axis = in.per_axis;
     pa.unit_local = ws.bwd_row_local; pa.bwd_counters = ws.flags + kBwdCounters; pa.gen_word = ws.flags + kGenWord;
     return pa;
@@ -2966,7 +2964,7 @@ static int splat_forward_impl(const char *fn, int variant, int flags, int C, con
         return GF_EWORKSPACE;
     }
     const ForwardRoute rt = forward_route(variant, flags, label_mode, in, ws);
-    uint32_t *const tile_counters = ws.flags + 4608;  // [64 x], x < 8: inside the 32 KB flag section, past the verdicts
+    uint32_t *const tile_counters = ws.flags + kFwdCounters;  // [64 x], x < 8
     uint32_t *const verdict_words = rt.one_verdict ? ws.flags + kVerdictWords : nullptr;
     unsigned char *const summary = rt.summaries ? ws.summary : nullptr;
 
@@ -2986,7 +2984,7 @@ static int splat_forward_impl(const char *fn, int variant, int flags, int C, con
     RenderArgs ra;
     ra.pts = in.pts; ra.points_int = in.points_int; ra.records = ws.records; ra.boxes = ws.boxes; ra.bitmask = ws.bitmask;
     ra.out_logits = out.logits; ra.out_bin = out.bin_logits; ra.out_density = out.density; ra.out_prob = out.probability;
-    ra.verify_flags = ws.flags + 64; ra.state = (uint32_t *)out.state; ra.P = in.P; ra.N = in.N; ra.nwords = ws.nwords; ra.nrow = ws.nrow;
+    ra.verify_flags = ws.flags + kVerifyBase; ra.state = (uint32_t *)out.state; ra.P = in.P; ra.N = in.N; ra.nwords = ws.nwords; ra.nrow = ws.nrow;
     ra.H = in.H; ra.W = in.W; ra.D = in.D; ra.nsx = ws.nsx; ra.nsy = ws.nsy; ra.ntiles_total = ws.nsuper * kTilesPerSuper;
     ra.verify_dense = rt.verify;
     ra.timeline = g_timeline;

@@ -20,7 +20,7 @@ from . import _lib
 _C18 = _lib.GF_NUM_CHANNELS
 
 
-FLAG_BYTES = 32768
+FLAG_BYTES = _lib.GF_SPLAT_FLAG_BYTES
 # The splat's scratch (records / bitmask / verdict words).  Its first 32 KB -- the library's flag section, the same words whatever
 # the call's shape -- are zeroed when a buffer is allocated and afterwards only written by the library: what ``GF_WORKSPACE_ZEROED``
 # promises (the matrix-core forward then keeps its fall-back verdict in one word instead of one per wave of the records pass).
@@ -278,7 +278,7 @@ class _LocalAggregate(torch.autograd.Function):
         ctx.state_host = ctx.state_event = None
         ctx.ws_stamp = _scratch.stamp(pts.device) if state.is_cuda else None
         if wants_grad and state.is_cuda:
-            ctx.state_host, ctx.state_event = _lib.host_copy(state[:20].view(torch.int32), pts.device)
+            ctx.state_host, ctx.state_event = _lib.host_copy(state[:_lib.STATE_USED_BYTES].view(torch.int32), pts.device)
         ctx.save_for_backward(state, means3D, means3D_int, pts, points_int, cov3D, opacities, semantics, radii)
         _tls.last_state = state   # (this thread's last call: picked up by LocalAggregator._splat right after apply() returns)
         return logits
@@ -292,14 +292,13 @@ class _LocalAggregate(torch.autograd.Function):
         if ctx.fwd_flags & _lib.GF_EXACT_FP32:
             bflags = _lib.GF_EXACT_FP32
         elif ctx.state_event is not None and ctx.state_event.query():
-            words = ctx.state_host.tolist()
-            on_matrix_cores = words[0] == 0 and words[1] in _lib.GF_PATHS_MATRIX_CORE
-            # (word 4, bit 1: the forward took the matrix-core backward's row layout and the rows do not fit its buffer -- many
+            st = _lib.SplatState.of(ctx.state_host)   # (a pinned host copy that has landed: nothing to wait for)
+            # (rows_overflow: the forward took the matrix-core backward's row layout and the rows do not fit its buffer -- many
             # large Gaussians; what does not fit would be added with atomics, tens of times slower than the Gaussian-major kernels)
-            bflags = _lib.GF_MFMA_SPLAT if on_matrix_cores and not (words[4] & 2) else _lib.GF_EXACT_FP32
-            # the forward's records pass laid out the backward's rows as well (word 4); if nobody has been handed this stream's
+            bflags = _lib.GF_MFMA_SPLAT if st.on_matrix_cores and not st.rows_overflow else _lib.GF_EXACT_FP32
+            # rows_ready: the forward's records pass laid out the backward's rows as well; if nobody has been handed this stream's
             # workspace since, the backward does not repeat that pass
-            if on_matrix_cores and (words[4] & 1) and ctx.ws_stamp == _scratch.stamp(out_grad.device):
+            if st.on_matrix_cores and st.rows_ready and ctx.ws_stamp == _scratch.stamp(out_grad.device):
                 bflags |= _lib.GF_RECORDS_VALID
         else:
             bflags = _lib.GF_PTS_AUTO
@@ -533,7 +532,7 @@ class LocalAggregator(_AggregatorBase):
         if w is None:
             w = self._path_watch = {"calls": 0, "host": None, "event": None}
         if w["event"] is not None and w["event"].query():
-            if int(w["host"][1]) == _lib.GF_PATH_ARBITRARY:
+            if _lib.SplatState.of(w["host"]).path == _lib.GF_PATH_ARBITRARY:
                 warnings.warn("LocalAggregator: pts is a dense grid but not the exact fp32 lattice of (pc_min, grid_size): the "
                               "matrix-core kernel's device verdict sends every frame to the arbitrary-points body; using the "
                               "exact-fp32 kernel from now on (matrix_cores=False selects it up front)")
@@ -541,7 +540,7 @@ class LocalAggregator(_AggregatorBase):
             w["host"] = w["event"] = None
         w["calls"] += 1
         if w["event"] is None and state is not None and state.is_cuda and (w["calls"] <= 3 or w["calls"] % 64 == 0):
-            w["host"], w["event"] = _lib.host_copy(state[:20].view(torch.int32), device)
+            w["host"], w["event"] = _lib.host_copy(state[:_lib.STATE_USED_BYTES].view(torch.int32), device)
 
     def _radii(self, scales):
         return torch.ceil(scales.max(dim=-1)[0] * self.scale_multiplier / self.grid_size).to(torch.int)

@@ -77,7 +77,7 @@ extern "C" {
 /* gf_splat_backward only: the caller vouches that no other gf_splat_* call has used `workspace` since the forward that wrote
  * `state` (and that the inputs are the ones that forward saw).  The forward's records pass lays out everything the matrix-core
  * backward needs, so that pass is then not launched again (about 11 us at P = 25 601).  Checked on the device: the
- * workspace carries a generation word (bumped by every call that rewrites it) and the state block a copy of it (word 3); if
+ * workspace carries a generation word (bumped by every call that rewrites it) and the state block a copy of it (word GF_STATE_GENERATION); if
  * they differ the gradients are NaN, never wrong.  Without the flag the pass is launched and stands down by itself when
  * the generations agree (an empty launch).  Ignored where the matrix-core backward does not apply. */
 #define GF_RECORDS_VALID 512
@@ -86,20 +86,34 @@ extern "C" {
  * <= 618 totals, one word per Gaussian) and one unit per supertile publishes the supertile's candidate list -- about 1.3 us of the
  * forward at P = 25 601 -- so that gf_splat_backward starts with its gradient kernel, whose units read those lists instead of
  * scanning bitmask rows: no records pass, no set-up launch (GF_RECORDS_VALID), 25 us less.  Without it the forward does none of this and
- * the backward prepares everything itself.  Word 4 of the state block, bit 0: the layout is there and every row fits the
- * buffer; bit 1: the layout was taken and the rows do NOT fit (many large Gaussians: the matrix-core backward would add what does
- * not fit with atomics -- correct, but the Gaussian-major backward, GF_EXACT_FP32, is the faster one then; the Python module
- * follows this bit).  Rows of more than 618 words (39 552 < P <= 262 144, round 6) publish a supertile's whole one-pass list (up to
+ * the backward prepares everything itself.  The outcome is word GF_STATE_ROWS of the state block (gf_splat_state_bytes); with
+ * GF_ROWS_OVERFLOW (many large Gaussians) the matrix-core backward would add what does not fit with atomics -- correct, but the
+ * Gaussian-major backward, GF_EXACT_FP32, is the faster one then; the Python module follows this bit.  Rows of more than 618 words (39 552 < P <= 262 144, round 6) publish a supertile's whole one-pass list (up to
  * 896 entries).  Ignored where the matrix-core backward does not apply. */
 #define GF_PREPARE_BACKWARD 1024
-/* The caller promises that the workspace's first 32 KB (its flag section) were zero when the workspace was first handed to the
- * library (e.g. allocated with hipMemset / torch.zeros) and have since only been written by the library.  The matrix-core forward
+/* The caller promises that the workspace's first GF_SPLAT_FLAG_BYTES bytes (32 KB, its flag section) were zero when the workspace
+ * was first handed to the library (e.g. allocated with hipMemset / torch.zeros) and have since only been written by the library.  The matrix-core forward
  * on the wave kernel then keeps its fall-back verdict in ONE word of that section (a double-buffered block maintained on the
  * device, so a replayed HIP graph behaves like an eager call) instead of one word per wave of the records pass that every render
  * wave has to read (19 KB per wave).  Same results; without the flag nothing changes. */
 #define GF_WORKSPACE_ZEROED 2048
 
-/* values of word 1 of the state block after gf_splat_forward: which body rendered the call */
+/* The state block (gf_splat_state_bytes): indices of its uint32 words, the words in use, and the bits of two of them. */
+#define GF_STATE_NOT_DENSE 0     /* word indices */
+#define GF_STATE_PATH 1
+#define GF_STATE_VERDICT 2
+#define GF_STATE_GENERATION 3
+#define GF_STATE_ROWS 4
+#define GF_STATE_WORDS 5
+#define GF_VERDICT_POINT 1       /* word GF_STATE_VERDICT: a point is not in its voxel */
+#define GF_VERDICT_LATTICE 2     /* ... pts is not an exact affine lattice */
+#define GF_VERDICT_THETA 4       /* ... a Gaussian's quadratic-form coefficients may leave the range the kernel is accurate in */
+#define GF_VERDICT_OPASEM 8      /* ... a Gaussian's |opacity * semantics| is 64 or more (4 and 8: matrix-core kernels only, every call) */
+#define GF_ROWS_READY 1          /* word GF_STATE_ROWS: the matrix-core backward's rows are laid out in the workspace and all fit */
+#define GF_ROWS_OVERFLOW 2       /* ... they were laid out and do NOT fit */
+#define GF_SPLAT_FLAG_BYTES 32768 /* the flag section at the start of a splat workspace (GF_WORKSPACE_ZEROED: what the caller zeroes once) */
+
+/* values of word GF_STATE_PATH after gf_splat_forward: which body rendered the call */
 #define GF_PATH_EXACT_TILE 0     /* exact-fp32 tile kernel (dense grid) */
 #define GF_PATH_MATRIX_CORE 1    /* split-f16 MFMA kernel (dense exact lattice), one workgroup per tile: P > 262 144, or P > 39 552 on a workspace without GF_WORKSPACE_ZEROED */
 #define GF_PATH_MATRIX_CORE_WAVE 3 /* the same arithmetic (equal bits), one wave per double brick: P <= 39 552, and (long-row instantiation, GF_WORKSPACE_ZEROED) P <= 262 144 */
@@ -132,13 +146,14 @@ size_t gf_splat_workspace_bytes(int P, int N, int H, int W, int D);
 
 /* Bytes of the small per-call state block written by gf_splat_forward and read by
  * gf_splat_backward (replaces the geomBuffer/binningBuffer/imgBuffer triple the reference
- * saves in ctx: model/head/localagg/local_aggregate/__init__.py:52-62).  uint32 words:
- *   [0] 1 = pts is NOT the dense voxel-centre grid (the backward then builds voxel2pts), 0 = it is
- *   [1] GF_PATH_* -- the body that rendered the forward (a GF_PATH_ARBITRARY on an N == H*W*D call is the slow
- *       fall-back of a failed verdict: visible to the caller after its next synchronisation)
- *   [2] verdict bits of the device-side checks: 1 = a point is not in its voxel, 2 = pts is not an exact affine
- *       lattice, 4 = a Gaussian's quadratic-form coefficients may leave the range the kernel is accurate in, 8 = a Gaussian's
- *       |opacity * semantics| is 64 or more (4 and 8: matrix-core kernel only, checked on every call) */
+ * saves in ctx: model/head/localagg/local_aggregate/__init__.py:52-62).  Its first GF_STATE_WORDS uint32 words after a forward:
+ *   [GF_STATE_NOT_DENSE]  1 = pts is NOT the dense voxel-centre grid (the backward then builds voxel2pts), 0 = it is
+ *   [GF_STATE_PATH]       GF_PATH_* -- the body that rendered the forward (a GF_PATH_ARBITRARY on an N == H*W*D call is the slow
+ *                         fall-back of a failed verdict: visible to the caller after its next synchronisation)
+ *   [GF_STATE_VERDICT]    GF_VERDICT_* bits of the device-side checks
+ *   [GF_STATE_GENERATION] the workspace's generation at that forward: every launch that rewrites the workspace's records bumps
+ *                         the workspace's own generation word, so equal = the forward's records are still there (GF_RECORDS_VALID)
+ *   [GF_STATE_ROWS]       GF_ROWS_* bits (GF_PREPARE_BACKWARD; 0 without it) */
 size_t gf_splat_state_bytes(void);
 
 /*
@@ -178,7 +193,7 @@ int gf_splat_forward(int variant, int radii_per_axis, int flags, int P, int N, i
  *
  * Two implementations.  (1) The Gaussian-major exact-fp32 kernels (every variant, arbitrary points; gradients ~1e-6 of the
  * tensor's maximum from the reference's own kernels).  (2) For the base variant after a forward that one of the matrix-core
- * kernels rendered (word 1 of `state`) and bitmask rows of <= 4 096 words (P <= 262 144; rows of more than 618 words, P > 39 552,
+ * kernels rendered (word GF_STATE_PATH of `state`) and bitmask rows of <= 4 096 words (P <= 262 144; rows of more than 618 words, P > 39 552,
  * since round 6: they take the forward's published lists in pieces): the voxel-major matrix-core backward --
  * every double brick loads its gradient rows once, the sums over voxels are contractions on the MFMAs (split-f16 operands,
  * fp32 accumulate), per-(Gaussian, brick) partial rows are added up in a fixed order
@@ -189,9 +204,7 @@ int gf_splat_forward(int variant, int radii_per_axis, int flags, int P, int N, i
  *                   otherwise every gradient comes out NaN (never silently wrong).  Ignored where (2) does not apply.
  *   GF_RECORDS_VALID  (2) without its records pass and set-up launch: see the flag (pairs with GF_PREPARE_BACKWARD in the forward).
  *   GF_PTS_ASSUME_DENSE / GF_PTS_GENERAL as in the forward (they select (1)'s body; (2) takes its verdict from `state`).
- * State block after a forward: word 0 = pts is not the dense grid, 1 = GF_PATH_*, 2 = verdict bits, 3 = the workspace's
- * generation at that forward, 4 bit 0 = the matrix-core backward's rows are laid out in the workspace and all fit, bit 1 = they
- * were laid out and do NOT fit.
+ * The words of `state` it reads are described at gf_splat_state_bytes.
  * Limit: P <= 262 144 Gaussians per call (the block prefix of (1) lives in LDS); more is refused with GF_EINVAL -- shard the set
  * (gradients are per Gaussian: a backward per shard with the same out_grad gives the same rows; the Python op does so by itself).
  * The forward has no such limit.

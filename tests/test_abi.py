@@ -108,6 +108,9 @@ def test_python_constants_match_the_header_defines():
     assert defines["GF_ABI_VERSION"] == _lib.GF_ABI_VERSION
     mirrored = [n for n in dir(_lib) if n.startswith("GF_") and isinstance(getattr(_lib, n), int)]
     assert len(mirrored) >= 15
+    protocol = ("GF_STATE_NOT_DENSE GF_STATE_PATH GF_STATE_VERDICT GF_STATE_GENERATION GF_STATE_ROWS GF_STATE_WORDS GF_VERDICT_POINT "
+                "GF_VERDICT_LATTICE GF_VERDICT_THETA GF_VERDICT_OPASEM GF_ROWS_READY GF_ROWS_OVERFLOW GF_SPLAT_FLAG_BYTES").split()
+    assert set(protocol) <= set(mirrored)   # the state block's words and bits, the flag section's size
     for n in mirrored:
         assert n in defines, f"{n} is not defined in include/gf_hip.h"
         assert defines[n] == getattr(_lib, n), (n, defines[n], getattr(_lib, n))
@@ -181,14 +184,14 @@ def test_stream_scratch():
     import torch
     cpu = torch.device("cpu")
     stream = [0]
-    splat = _lib.StreamScratch(min_bytes=1 << 20, zeroed_bytes=32768, stream_of=lambda device: stream[0])
+    splat = _lib.StreamScratch(min_bytes=1 << 20, zeroed_bytes=_lib.GF_SPLAT_FLAG_BYTES, stream_of=lambda device: stream[0])
     other = _lib.StreamScratch(stream_of=lambda device: stream[0])
     a = splat.get(cpu, 100)
-    assert a.dtype == torch.uint8 and a.numel() == 1 << 20 and not a[:32768].any()     # minimum size, zeroed flag section
-    a[:32768] = 7
-    assert splat.get(cpu, 4096).data_ptr() == a.data_ptr() and bool((a[:32768] == 7).all())   # reused, never zeroed again
+    assert a.dtype == torch.uint8 and a.numel() == 1 << 20 and not a[:_lib.GF_SPLAT_FLAG_BYTES].any()     # minimum size, zeroed flag section
+    a[:_lib.GF_SPLAT_FLAG_BYTES] = 7
+    assert splat.get(cpu, 4096).data_ptr() == a.data_ptr() and bool((a[:_lib.GF_SPLAT_FLAG_BYTES] == 7).all())   # reused, never zeroed again
     big = splat.get(cpu, (1 << 20) + 1)
-    assert big.numel() == (1 << 20) + 1 and not big[:32768].any()                       # grows ...
+    assert big.numel() == (1 << 20) + 1 and not big[:_lib.GF_SPLAT_FLAG_BYTES].any()                       # grows ...
     assert splat.get(cpu, 100).data_ptr() == big.data_ptr()                             # ... and never shrinks
     assert other.get(cpu, 100).numel() == 100                                           # no minimum of its own
     # stamp(): moved by any hand-out of the same cache, not by another cache's

@@ -134,7 +134,7 @@ def test_fused_label_epilogue_matches_separate_kernels(config, per_axis, dense):
     for fl in flag_sets:
         logits, bl, de, pr, state = splat_forward(variant, *t, si.H, si.W, si.D, flags=fl)
         if fl == 0:
-            assert state.view(torch.int32)[1].item() == _lib.GF_PATH_MATRIX_CORE_WAVE
+            assert _lib.SplatState.of(state).path == _lib.GF_PATH_MATRIX_CORE_WAVE
         for kw in ([dict()] if not prob else [dict(threshold=0.3), dict(combine_geosem=True)]):
             want = occupancy_labels(logits, bin_logits=bl, empty_label=17, **kw)
             got = splat_forward_labels(variant, *t, si.H, si.W, si.D, flags=fl, **kw)

@@ -96,8 +96,8 @@ def test_mfma_wave_and_tile_kernels_agree_bit_for_bit(gpu, config, kw):
     wave, _, wstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
     with _lib.option("splat.mfma_tile_kernel", 1):
         tile, _, tstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
-    assert wstate[:12].view(torch.int32).cpu().tolist()[1] == _lib.GF_PATH_MATRIX_CORE_WAVE
-    assert tstate[:12].view(torch.int32).cpu().tolist()[1] == _lib.GF_PATH_MATRIX_CORE
+    assert _lib.SplatState.of(wstate).path == _lib.GF_PATH_MATRIX_CORE_WAVE
+    assert _lib.SplatState.of(tstate).path == _lib.GF_PATH_MATRIX_CORE
     assert np.isfinite(wave["logits"]).all()
     assert np.array_equal(wave["logits"], tile["logits"])
     ref = _oracle_logits(si, pi, mi, radii, cov6)
@@ -121,7 +121,7 @@ def test_mfma_inexact_lattice_falls_back(gpu):
     logits, _, _, _, state = splat_forward(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, flags=_lib.GF_MFMA_SPLAT)
     # state block: the points ARE in their voxels (word 0 = 0, the backward keeps its dense path), the call was rendered
     # by the arbitrary-points body (word 1) because the lattice verdict (bit 1 of word 2) failed
-    assert state.view(torch.int32)[:3].tolist() == [0, _lib.GF_PATH_ARBITRARY, 2]
+    assert state.view(torch.int32)[:3].tolist() == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_LATTICE]
     assert_logits_close(logits.cpu().numpy(), ref, tol=1e-4)
     # the thinnest Gaussians make one ulp visible: the result must be the one for the given positions, bit for bit the
     # arbitrary-points kernel's
@@ -143,7 +143,7 @@ def test_mfma_coefficient_range_verdict(gpu):
     ref = _oracle_logits(si, pi, mi, radii, cov6)
     t = [torch.from_numpy(np.ascontiguousarray(a)).to(gpu) for a in (si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6)]
     logits, _, _, _, state = splat_forward(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D)
-    assert state.view(torch.int32)[:3].tolist() == [0, _lib.GF_PATH_ARBITRARY, 4]
+    assert state.view(torch.int32)[:3].tolist() == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_THETA]
     assert bool(torch.isfinite(logits).all())
     assert_logits_close(logits.cpu().numpy(), ref, tol=1e-4)
     # with an ordinary covariance in its place the same call stays on the matrix cores
@@ -282,13 +282,13 @@ def test_mfma_large_semantics_fall_back(gpu, assume_dense):
     want = _reference_logits(si, pi, mi, radii, cov6)
     flags = _lib.GF_PTS_ASSUME_DENSE if assume_dense else 0
     got, state = _run_default(gpu, si, pi, mi, radii, cov6, flags)
-    assert state == [0, _lib.GF_PATH_ARBITRARY, 8]
+    assert state == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_OPASEM]
     assert_logits_close(got, want, tol=1e-4)
     # one Gaussian is enough, and so is a NaN
     si.semantics /= np.float32(1e5)
     si.semantics[123, 4] = np.float32(7e4)
     got, state = _run_default(gpu, si, pi, mi, radii, cov6, flags)
-    assert state[1:] == [_lib.GF_PATH_ARBITRARY, 8]
+    assert state[1:] == [_lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_OPASEM]
     assert_logits_close(got, _reference_logits(si, pi, mi, radii, cov6), tol=1e-4)
     # ... and just inside the bound (|opacity * semantics| < 64) the call stays on the matrix cores, still within the tolerance
     si.opacities[123] = np.float32(1.0)
@@ -307,7 +307,7 @@ def test_mfma_coefficient_range_verdict_under_assume_dense(gpu):
     cov6[5] = (np.float32(1.0 / 0.004 ** 2), np.float32(1.0), np.float32(1.0), 0, 0, 0)
     radii[5] = 12
     got, state = _run_default(gpu, si, pi, mi, radii, cov6, _lib.GF_PTS_ASSUME_DENSE)
-    assert state == [0, _lib.GF_PATH_ARBITRARY, 4]
+    assert state == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_THETA]
     assert_logits_close(got, _reference_logits(si, pi, mi, radii, cov6), tol=1e-4)
 
 
@@ -359,7 +359,7 @@ def test_mfma_adversarial_inputs_just_inside_the_verdicts(gpu, seed):
     cov6[g] *= np.float32(2.0)
     assert _range_bounds(cov6[g][None], radii[g:g + 1], si.H, si.W, si.D)[1][0] > 1200
     got, state = _run_default(gpu, si, pi, mi, radii, cov6)
-    assert state == [0, _lib.GF_PATH_ARBITRARY, 4]
+    assert state == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_THETA]
     assert_logits_close(got, _reference_logits(si, pi, mi, radii, cov6), tol=1e-4)
 
 
@@ -373,7 +373,7 @@ def test_mfma_very_thin_far_reaching_gaussians(gpu):
         cov6[g] = (np.float32(1e4), np.float32(4.0), np.float32(1.0), np.float32(3.0), 0, 0)
         radii[g] = r
     got, state = _run_default(gpu, si, pi, mi, radii, cov6)
-    assert state == [0, _lib.GF_PATH_ARBITRARY, 4]
+    assert state == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_THETA]
     assert_logits_close(got, _reference_logits(si, pi, mi, radii, cov6), tol=1e-4)
 
 
@@ -419,11 +419,11 @@ def test_backward_takes_the_forward_records_when_the_workspace_still_holds_them(
     pi, mi, radii, cov6 = prep(si)
     g = np.random.default_rng(5).standard_normal((si.pts.shape[0], 18)).astype(np.float32)
     _, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
-    assert (state0.view(torch.int32)[4].item() & 1) == 0                 # a forward that was not told of a backward prepares nothing
+    assert not _lib.SplatState.of(state0).rows_ready                 # a forward that was not told of a backward prepares nothing
     plain = _bwd(gpu, si, t, state0, g)
     _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
-    words = state.view(torch.int32)[:5].tolist()
-    assert words[1] == _lib.GF_PATH_MATRIX_CORE_WAVE and (words[4] & 1) == 1
+    words = _lib.SplatState.of(state)
+    assert words.path == _lib.GF_PATH_MATRIX_CORE_WAVE and words.rows_ready
     base = _bwd(gpu, si, t, state, g)                                    # records still there
     ref = oracle.splat_backward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D, g)
     for a, b in zip(base, ref):
@@ -468,10 +468,10 @@ def test_backward_after_a_prepared_forward_on_a_grid_of_few_workgroups(gpu, shap
     outs = []
     for fflags in (0, _lib.GF_PREPARE_BACKWARD):
         _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=fflags)
-        words = state.view(torch.int32)[:5].tolist()
+        words = _lib.SplatState.of(state)
         nwg = 8 * -(-(-(-H // 8) * -(-W // 8) * 4 * -(-D // 8)) // 8)
         if fflags and nwg < 64:
-            assert (words[4] & 1) == 0, words
+            assert not words.rows_ready, words
         got = _bwd(gpu, si, t, state, g)
         outs.append(got)
         for a, b in zip(got, ref):
@@ -504,7 +504,7 @@ def test_backward_rows_of_whole_grid_gaussians_and_of_a_full_buffer(gpu, case):
     for fflags in (0, _lib.GF_PREPARE_BACKWARD):
         _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=fflags)
         if fflags:   # the forward reports whether every row fitted
-            assert (state.view(torch.int32)[4].item() & 1) == (1 if case == "several_whole_grid" else 0)
+            assert _lib.SplatState.of(state).rows_ready == (case == "several_whole_grid")
         got = _bwd(gpu, si, t, state, g)
         for a, b in zip(got, ref):
             assert np.isfinite(a).all()
@@ -531,8 +531,8 @@ def test_backward_when_a_supertile_has_more_candidates_than_a_published_list_hol
     _, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
     plain = _bwd(gpu, si, t, state0, g)
     _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
-    words = state.view(torch.int32)[:5].tolist()
-    assert words[1] == _lib.GF_PATH_MATRIX_CORE_WAVE and (words[4] & 1) == 1
+    words = _lib.SplatState.of(state)
+    assert words.path == _lib.GF_PATH_MATRIX_CORE_WAVE and words.rows_ready
     got = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
     for a, b, c in zip(got, plain, ref):
         assert np.isfinite(a).all() and np.array_equal(a, b)
@@ -564,12 +564,12 @@ def test_backward_on_long_rows(gpu, config, kw):
     plain = _bwd(gpu, si, t, state0, g)                                  # the backward lays its rows out itself, scans the rows
     exact = _bwd(gpu, si, t, state0, g, flags=_lib.GF_EXACT_FP32)
     _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
-    words = state.view(torch.int32)[:5].tolist()
-    assert words[0] == 0 and words[1] == _lib.GF_PATH_MATRIX_CORE_WAVE, words
-    prepared = bool(words[4] & 1)
+    words = _lib.SplatState.of(state)
+    assert not words.not_dense and words.path == _lib.GF_PATH_MATRIX_CORE_WAVE, words
+    prepared = words.rows_ready
     assert prepared == (config == "nuscenes_gs144000"), words
     # "the rows do not fit": the module takes the Gaussian-major backward then
-    assert bool(words[4] & 2) == (not prepared and si.H > 16), words
+    assert words.rows_overflow == (not prepared and si.H > 16), words
     got = _bwd(gpu, si, t, state, g, flags=(_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if prepared else 0)
     for a, b, c, name in zip(got, plain, exact, ("means", "opacity", "semantics", "cov")):
         if prepared:   # (rows that do not fit are added with atomics, in no fixed order)
@@ -589,8 +589,8 @@ def test_forward_and_backward_past_the_longest_rows(gpu):
     g = np.random.default_rng(2).standard_normal((si.pts.shape[0], 18)).astype(np.float32)
     exact_out, t, state_e, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_EXACT_FP32)
     out, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
-    words = state.view(torch.int32)[:5].tolist()
-    assert words[0] == 0 and words[1] == _lib.GF_PATH_MATRIX_CORE and (words[4] & 3) == 0, words
+    words = _lib.SplatState.of(state)
+    assert not words.not_dense and words.path == _lib.GF_PATH_MATRIX_CORE and not words.rows_ready and not words.rows_overflow, words
     assert np.abs(out["logits"] - exact_out["logits"]).max() <= 1e-4
     whole = _bwd(gpu, si, t, state, g)          # the Python op shards the set for the C entry point (262 144 per call)
     from gaussianformer_amd.local_aggregate import BACKWARD_MAX_GAUSSIANS
@@ -602,9 +602,9 @@ def test_forward_and_backward_past_the_longest_rows(gpu):
         sh.means3D, sh.opacities, sh.semantics, sh.scales, sh.cov3D = (a[lo:hi] for a in (si.means3D, si.opacities, si.semantics, si.scales, si.cov3D))
         spi, smi, sradii, scov6 = pi, mi[lo:hi], radii[lo:hi], cov6[lo:hi]
         _, ts, sts, _ = hip_splat_forward(gpu, sh, spi, smi, sradii, scov6, flags=_lib.GF_PREPARE_BACKWARD)
-        ws = sts.view(torch.int32)[:5].tolist()
+        ws = _lib.SplatState.of(sts)
         assert ws[1] == _lib.GF_PATH_MATRIX_CORE_WAVE, ws
-        got = _bwd(gpu, sh, ts, sts, g, flags=(_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if ws[4] & 1 else 0)
+        got = _bwd(gpu, sh, ts, sts, g, flags=(_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if ws.rows_ready else 0)
         ex = _bwd(gpu, sh, ts, sts, g, flags=_lib.GF_EXACT_FP32)
         from util import assert_grad_rows_close
         for a, b, w, name in zip(got, ex, whole, ("means", "opacity", "semantics", "cov")):
@@ -679,7 +679,7 @@ def test_product_library_is_not_a_development_build_and_reads_no_environment(gpu
     for k in ("GF_MFMA_TILE", "GF_MFMA_PAIR", "GF_MFMA_SOLO", "GF_FUSED", "GF_UNITS_BANDS", "GF_PREP_WAVES"):
         monkeypatch.setenv(k, "1")
     got, _, state2, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
-    assert state2[:12].view(torch.int32).cpu().tolist()[1] == _lib.GF_PATH_MATRIX_CORE_WAVE
+    assert _lib.SplatState.of(state2).path == _lib.GF_PATH_MATRIX_CORE_WAVE
     assert np.array_equal(got["logits"], want["logits"])
     with pytest.raises(RuntimeError):
         _lib.set_option("dev.splat_solo", 1)
@@ -704,14 +704,14 @@ def test_module_notices_a_dense_grid_that_is_not_its_lattice(gpu):
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter("always")
         first = m(*args)
-        assert m.last_state.view(torch.int32)[1].item() == _lib.GF_PATH_ARBITRARY
+        assert _lib.SplatState.of(m.last_state).path == _lib.GF_PATH_ARBITRARY
         torch.cuda.synchronize()
         time.sleep(0.05)
         for _ in range(3):
             out = m(*args)
         torch.cuda.synchronize()
     assert m._grid_exact is False and any("exact-fp32" in str(w.message) for w in caught)
-    assert m.last_state.view(torch.int32)[1].item() == _lib.GF_PATH_EXACT_TILE
+    assert _lib.SplatState.of(m.last_state).path == _lib.GF_PATH_EXACT_TILE
     assert float(((out - first).abs() / first.abs().clamp(min=1.0)).max()) <= 1e-4
     # the module's own lattice is left alone
     m2 = LocalAggregator(si.scale_multiplier, si.H, si.W, si.D, list(si.pc_min), si.grid_size).to(gpu)
@@ -772,25 +772,26 @@ def test_one_verdict_word_follows_the_inputs_call_after_call(gpu, assume_dense):
         assert_logits_close(got.cpu().numpy(), want.cpu().numpy(), tol=1e-4)
 
     wave, arb = _lib.GF_PATH_MATRIX_CORE_WAVE, _lib.GF_PATH_ARBITRARY
+    lattice, theta, opasem = _lib.GF_VERDICT_LATTICE, _lib.GF_VERDICT_THETA, _lib.GF_VERDICT_OPASEM
     for _ in range(2):
         step(wave, 0)
     sem[17, 3] = 7e4                                        # |opacity * semantics| >= 64
     for _ in range(2):
-        step(arb, 8)
+        step(arb, opasem)
     sem.copy_(sem0)
     for _ in range(3):
         step(wave, 0)
     cov[5] = torch.tensor([1.0 / 0.004 ** 2, 1.0, 1.0, 0, 0, 0], device=gpu)   # theta out of range
     rad[5] = 12
-    step(arb, 4)
+    step(arb, theta)
     sem[40, 0] = 9e4                                        # both at once
-    step(arb, 12)
+    step(arb, theta | opasem)
     cov.copy_(cov0); rad.copy_(rad0); sem.copy_(sem0)
     step(wave, 0)
     if not assume_dense:
         pts[1000, 2] += 1e-3                                # not the exact lattice any more (the point is still in its voxel)
         for _ in range(2):
-            step(arb, 2)
+            step(arb, lattice)
         pts.copy_(pts0)
         for _ in range(2):
             step(wave, 0)
@@ -807,7 +808,7 @@ def test_one_verdict_word_follows_the_inputs_call_after_call(gpu, assume_dense):
             sem[17, 3] = 7e4
         g.replay()
         torch.cuda.synchronize()
-        assert plan.state_words()[1:3] == ([arb, 8] if poison else [wave, 0]), (poison, plan.state_words()[:3])
+        assert plan.state_words()[1:3] == ([arb, opasem] if poison else [wave, 0]), (poison, plan.state_words()[:3])
         assert_logits_close(plan.logits.cpu().numpy(), exact.run().cpu().numpy(), tol=1e-4)
 
 
@@ -859,10 +860,10 @@ def test_list_builder_regimes_agree_across_kernels_and_with_the_oracle(gpu, side
     pi, mi, radii, cov6 = prep(si)
     assert si.means3D.shape[0] == 16000 and (radii[:-1] == 1).all()
     wave, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
-    assert state0.view(torch.int32)[:5].tolist()[1] == _lib.GF_PATH_MATRIX_CORE_WAVE   # (otherwise the scene fell back and proved nothing)
+    assert _lib.SplatState.of(state0).path == _lib.GF_PATH_MATRIX_CORE_WAVE   # (otherwise the scene fell back and proved nothing)
     with _lib.option("splat.mfma_tile_kernel", 1):
         tile, _, tstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
-    assert tstate.view(torch.int32)[:5].tolist()[1] == _lib.GF_PATH_MATRIX_CORE
+    assert _lib.SplatState.of(tstate).path == _lib.GF_PATH_MATRIX_CORE
     assert np.array_equal(wave["logits"], tile["logits"])
     ref = _oracle_logits(si, pi, mi, radii, cov6)
     err = np.abs(wave["logits"].astype(np.float64) - ref) / np.maximum(1.0, np.abs(ref))
@@ -872,15 +873,15 @@ def test_list_builder_regimes_agree_across_kernels_and_with_the_oracle(gpu, side
     g = np.random.default_rng(43).standard_normal((si.pts.shape[0], 18)).astype(np.float32)
     gref = oracle.splat_backward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D, g)
     _, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
-    assert state0.view(torch.int32)[:5].tolist()[1] == _lib.GF_PATH_MATRIX_CORE_WAVE
+    assert _lib.SplatState.of(state0).path == _lib.GF_PATH_MATRIX_CORE_WAVE
     plain = _bwd(gpu, si, t, state0, g)
     _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
-    words = state.view(torch.int32)[:5].tolist()
+    words = _lib.SplatState.of(state)
     print("prepared forward: state words", words)
-    assert words[1] == _lib.GF_PATH_MATRIX_CORE_WAVE
-    assert (words[4] & 1) == (1 if side == 32 else 0)
+    assert words.path == _lib.GF_PATH_MATRIX_CORE_WAVE
+    assert words.rows_ready == (side == 32)
     prepared = _bwd(gpu, si, t, state, g)
-    asserted = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if words[4] & 1 else prepared
+    asserted = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if words.rows_ready else prepared
     for a, b, c, r in zip(plain, prepared, asserted, gref):
         print("backward: max error / max |ref|", np.abs(a - r.reshape(a.shape)).max() / max(np.abs(r).max(), 1e-30))
         assert np.isfinite(a).all()

@@ -25,7 +25,7 @@ def test_wave_and_tile_kernels_agree_on_the_operand_phase(gpu, config, kw):
     wave, _, wstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
     with _lib.option("splat.mfma_tile_kernel", 1):
         tile, _, tstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
-    assert wstate[:12].view(torch.int32).cpu().tolist()[1] == _lib.GF_PATH_MATRIX_CORE_WAVE
-    assert tstate[:12].view(torch.int32).cpu().tolist()[1] == _lib.GF_PATH_MATRIX_CORE
+    assert _lib.SplatState.of(wstate).path == _lib.GF_PATH_MATRIX_CORE_WAVE
+    assert _lib.SplatState.of(tstate).path == _lib.GF_PATH_MATRIX_CORE
     assert np.isfinite(wave["logits"]).all()
     assert np.array_equal(wave["logits"], tile["logits"])

@@ -222,7 +222,7 @@ def test_the_route_is_the_body_the_state_block_reports(gpu):
         torch.cuda.synchronize(gpu)
         # (splat_forward hands over a zeroed workspace and says so)
         r = route(flags=flags | GF_WORKSPACE_ZEROED, P=P, N=n, grid=(g, g, g))
-        return r["kernel"], state.view(torch.int32)[1].item()
+        return r["kernel"], _lib.SplatState.of(state).path
 
     for want, (kernel, path) in ((WAVE, both()), (EXACT_TILE, both(GF_EXACT_FP32)), (ARBITRARY, both(drop=1))):
         assert kernel == want and path == path_of[kernel], (want, kernel, path)

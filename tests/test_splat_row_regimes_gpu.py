@@ -146,7 +146,8 @@ def _bwd(gpu, si, t, state, g, flags=0):
 
 
 def _words(state):
-    return state.view(torch.int32)[:5].tolist()
+    from gaussianformer_amd import _lib
+    return _lib.SplatState.of(state)
 
 
 @pytest.mark.gpu
@@ -166,17 +167,18 @@ def test_prepared_forward_and_backward_at_row_regime(gpu, name, P, nwords):
 
     prepared, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
     words = _words(state)
-    assert words[0] == 0, words
+    assert not words.not_dense, words
     if on_wave:
-        assert words[1] == _lib.GF_PATH_MATRIX_CORE_WAVE and (words[4] & 3) == 1, words
+        assert words.path == _lib.GF_PATH_MATRIX_CORE_WAVE and words.rows_ready and not words.rows_overflow, words
         # (right after its forward: the workspace still holds the records and the layout)
         got = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
     else:
-        assert words[1] == _lib.GF_PATH_MATRIX_CORE and (words[4] & 3) == 0, words
+        assert words.path == _lib.GF_PATH_MATRIX_CORE and not words.rows_ready and not words.rows_overflow, words
 
     plain, t0, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
     words0 = _words(state0)
-    assert words0[:2] == [0, _lib.GF_PATH_MATRIX_CORE_WAVE if on_wave else _lib.GF_PATH_MATRIX_CORE] and (words0[4] & 3) == 0, words0
+    assert not words0.not_dense and words0.path == (_lib.GF_PATH_MATRIX_CORE_WAVE if on_wave else _lib.GF_PATH_MATRIX_CORE), words0
+    assert not words0.rows_ready and not words0.rows_overflow, words0
     if on_wave:
         unprepared = _bwd(gpu, si, t0, state0, g, flags=_lib.GF_MFMA_SPLAT)
         exact = _bwd(gpu, si, t0, state0, g, flags=_lib.GF_EXACT_FP32)
@@ -185,7 +187,7 @@ def test_prepared_forward_and_backward_at_row_regime(gpu, name, P, nwords):
         tile_p, _, tstate_p, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
         tile, _, tstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
     for tw in (_words(tstate_p), _words(tstate)):
-        assert tw[:2] == [0, _lib.GF_PATH_MATRIX_CORE], tw
+        assert not tw.not_dense and tw.path == _lib.GF_PATH_MATRIX_CORE, tw
 
     assert np.isfinite(prepared["logits"]).all()
     for other, what in ((plain, "plain forward"), (tile_p, "tile kernel, prepared"), (tile, "tile kernel")):
@@ -236,7 +238,8 @@ def test_module_training_step_at_the_longest_rows(gpu):
     m = mk(None)
     with torch.no_grad():
         ref = m(dev(si.pts), dev(si.means3D), dev(si.opacities), dev(si.semantics), dev(si.scales), dev(si.cov3D))
-    assert (_words(m.last_state)[4] & 3) == 0
+    words = _words(m.last_state)
+    assert not words.rows_ready and not words.rows_overflow
     grads = []
     for mod in (m, mk(False)):
         leaves = [dev(a).requires_grad_(True) for a in (si.means3D, si.opacities, si.semantics, si.cov3D)]
@@ -244,7 +247,7 @@ def test_module_training_step_at_the_longest_rows(gpu):
         torch.cuda.synchronize(gpu)
         if mod is m:
             words = _words(mod.last_state)
-            assert words[:2] == [0, _lib.GF_PATH_MATRIX_CORE_WAVE] and (words[4] & 3) == 1, words
+            assert not words.not_dense and words.path == _lib.GF_PATH_MATRIX_CORE_WAVE and words.rows_ready and not words.rows_overflow, words
             diff = (out != ref).any(dim=-1)
             assert not bool(diff.any()), (f"prepared forward vs torch.no_grad(): {int(diff.sum())} voxels differ, "
                                           f"max |diff| {float((out - ref).abs().max()):.3e}")

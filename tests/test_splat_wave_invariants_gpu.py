@@ -47,16 +47,16 @@ def test_wave_routes_and_tile_kernel_agree_bit_for_bit(gpu, P, H, W, D):
 
     def run(flags):
         logits, _, _, _, state = splat_forward(V, *t, H, W, D, flags=flags)
-        return logits.cpu().numpy(), state.view(torch.int32)[:3].tolist()
+        return logits.cpu().numpy(), _lib.SplatState.of(state)
 
     wave, wstate = run(0)
-    assert wstate == [0, _lib.GF_PATH_MATRIX_CORE_WAVE, 0], wstate
+    assert (wstate.not_dense, wstate.path, wstate.verdict) == (False, _lib.GF_PATH_MATRIX_CORE_WAVE, 0), wstate
     assert np.isfinite(wave).all()
     with _lib.option("splat.mfma_tile_kernel", 1):
         tile, tstate = run(_lib.GF_MFMA_SPLAT)
-    assert tstate[1] == _lib.GF_PATH_MATRIX_CORE, tstate
+    assert tstate.path == _lib.GF_PATH_MATRIX_CORE, tstate
     prepared, pstate = run(_lib.GF_PREPARE_BACKWARD)
-    assert pstate[1] == _lib.GF_PATH_MATRIX_CORE_WAVE, pstate
+    assert pstate.path == _lib.GF_PATH_MATRIX_CORE_WAVE, pstate
     bits = lambda x: x.view(np.int32)
     assert np.array_equal(bits(wave), bits(tile)), "wave kernel vs tile kernel"
     assert np.array_equal(bits(wave), bits(prepared)), "default vs GF_PREPARE_BACKWARD"
@@ -70,5 +70,5 @@ def test_wave_routes_and_tile_kernel_agree_bit_for_bit(gpu, P, H, W, D):
     assert np.array_equal(only.cpu().numpy(), want)
 
     exact, estate = run(_lib.GF_EXACT_FP32)
-    assert estate[1] not in (_lib.GF_PATH_MATRIX_CORE_WAVE, _lib.GF_PATH_MATRIX_CORE), estate
+    assert estate.path not in (_lib.GF_PATH_MATRIX_CORE_WAVE, _lib.GF_PATH_MATRIX_CORE), estate
     assert_logits_close(wave, exact, tol=1e-4)

@@ -82,11 +82,12 @@ def _redraw_gates(s):
 
 
 def _path_word(s, outs):
+    from gaussianformer_amd import _lib
     if s.const["head"] == "prob":
         state = s.prob_state
     else:
         state = s.agg.last_state
-    return int(state[:20].view(torch.int32)[1])
+    return _lib.SplatState.of(state).path
 
 
 def _edge_anchors(kps, const, ss):

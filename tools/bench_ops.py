@@ -60,8 +60,8 @@ for config, clustered in (("nuscenes_gs25600_solid", False), ("nuscenes_gs25600_
     # forward's state block says (matrix cores, rows laid out -> GF_MFMA_SPLAT | GF_RECORDS_VALID)
     logits, bl, de, pr, state = splat_forward(variant, *t, si.H, si.W, si.D, flags=_lib.GF_PREPARE_BACKWARD)
     torch.cuda.synchronize()
-    words = state.view(torch.int32)[:5].tolist()
-    fast = words[0] == 0 and words[1] in _lib.GF_PATHS_MATRIX_CORE and (words[4] & 1)
+    st = _lib.SplatState.of(state)
+    fast = st.on_matrix_cores and st.rows_ready
     g = torch.randn(N, 18, device=dev)
     gb = torch.randn(N, device=dev) if variant else None
     sec = timed(lambda: splat_backward(variant, *t, si.H, si.W, si.D, g, fwd_outputs=(logits, bl, de, pr) if variant else None,

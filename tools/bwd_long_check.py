@@ -19,8 +19,8 @@ for cfg, kw in cases:
     g = torch.randn(N, 18, generator=torch.Generator().manual_seed(1)).to(dev)
     logits, _, _, _, state = splat_forward(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, flags=_lib.GF_PREPARE_BACKWARD)
     torch.cuda.synchronize()
-    words = state.view(torch.int32)[:5].tolist()
-    fast = words[0] == 0 and words[1] in _lib.GF_PATHS_MATRIX_CORE and (words[4] & 1)
+    words = _lib.SplatState.of(state)
+    fast = words.on_matrix_cores and words.rows_ready
     mc = splat_backward(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, g, state=state, flags=(_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if fast else 0)
     mc = [x.clone() for x in mc]
     def timed(fn, n=20):

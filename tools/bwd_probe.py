@@ -26,7 +26,7 @@ def run(si, tag, grad_scale=1.0):
     t = to_dev(dev, si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6)
     logits, _, _, _, state = splat_forward(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D)
     torch.cuda.synchronize()
-    words = state.view(torch.int32)[:3].tolist()
+    words = _lib.SplatState.of(state)
     g = (torch.randn(logits.shape, generator=torch.Generator().manual_seed(1)) * grad_scale).to(dev)
     outs = {}
     for name, flags in (("exact", _lib.GF_EXACT_FP32), ("auto", 0), ("mfma", _lib.GF_MFMA_SPLAT)):

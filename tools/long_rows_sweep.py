@@ -31,8 +31,8 @@ for it in range(n):
         lgt = lgt.clone()
     lg, _, _, _, st = splat_forward(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, flags=_lib.GF_PREPARE_BACKWARD)
     torch.cuda.synchronize()
-    words = st.view(torch.int32)[:5].tolist()
-    prepared = bool(words[4] & 1)
+    words = _lib.SplatState.of(st)
+    prepared = words.rows_ready
     got = splat_backward(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, g, state=st, flags=(_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if prepared else 0)
     torch.cuda.synchronize()
     fwd_equal = bool(torch.equal(lg0, lgt)) and bool(torch.equal(lg, lg0))

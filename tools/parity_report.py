@@ -33,8 +33,8 @@ def report(config, per_axis=False, flags=0, tag=""):
     rf, rgrads, _ = ref.splat_forward_backward(si.variant, si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6,
                                                si.H, si.W, si.D, g, gb, gd)
     got, t, state, fwd_t = hip_splat_forward(dev, si, pi, mi, radii, cov6, flags=flags)
-    words = state.view(torch.int32)[:3].tolist()
-    print(f"== {config}{tag}: P = {si.means3D.shape[0]}, R = {rf['num_rendered']}, state words (general pts, path, verdicts) {words}")
+    words = _lib.SplatState.of(state)
+    print(f"== {config}{tag}: P = {si.means3D.shape[0]}, R = {rf['num_rendered']}, state {words}")
     for k in (("logits", "bin_logits", "density", "probability") if si.variant == "prob" else ("logits",)):
         fin = np.isfinite(rf[k]) if rf[k].ndim == 1 else np.isfinite(rf[k]).all(axis=1)
         a, b = got[k][fin].astype(np.float64), rf[k][fin].astype(np.float64)

@@ -20,7 +20,7 @@ def verdict(mask):
     tt = to_dev(dev, si.pts, pi, si.means3D[idx], mi[idx], si.opacities[idx], si.semantics[idx], np.ascontiguousarray(r1[idx].astype(np.int32)), cov6[idx])
     lg, _, _, _, st = splat_forward(_lib.GF_SPLAT_BASE, *tt, si.H, si.W, si.D, flags=_lib.GF_MFMA_SPLAT)
     torch.cuda.synchronize()
-    return st.view(torch.int32)[:3].tolist()
+    return _lib.SplatState.of(st)
 print("all:", verdict(np.ones(len(r1), bool)))
 smin = si.scales.min(axis=1)
 for thr in (0.02, 0.05, 0.08, 0.1, 0.15, 0.2, 0.3):

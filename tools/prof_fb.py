@@ -29,7 +29,7 @@ for i in range(iters + 3):
     torch.cuda.synchronize()
     if i >= 3:
         tf.append(ev[0].elapsed_time(ev[1]) * 1e3); tb.append(ev[1].elapsed_time(ev[2]) * 1e3)
-print(config, "state", st.view(torch.int32)[:5].tolist(), f"forward(prepared) {np.median(tf):.1f} us, backward {np.median(tb):.1f} us (events, one pair per sync)")
+print(config, "state", _lib.SplatState.of(st), f"forward(prepared) {np.median(tf):.1f} us, backward {np.median(tb):.1f} us (events, one pair per sync)")
 ex = splat_backward(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, g, state=st, flags=_lib.GF_EXACT_FP32)
 for name, a, b in zip(("means", "opacity", "semantics", "cov"), out, ex):
     d = (a - b).abs().max().item(); m = b.abs().max().item()
