@@ -30,6 +30,13 @@ struct PrepareArgs {
     int P, H, W, D, radii_mode, radii_min, grad_is_full;
 };
 
+// Below F.normalize's clamp (||q|| < 1e-12) q^ = q / 1e-12 is no unit quaternion, R(q^) no rotation and R^T S^-2 R the inverse
+// of nothing (n^4 / s^2 with n = ||q|| / 1e-12, while the reference inverts a Cov of n^4 s^2).  Such a quaternion has no
+// direction and is taken as the zero quaternion: Sigma^-1 = 0 and zero gradients, everything finite.  The kernels write zeros
+// over what they stored for such a Gaussian, in a branch of its own: the arithmetic of every other Gaussian, and the way the
+// compiler fuses it, is what it was.
+__device__ __forceinline__ bool no_direction(const UnitQuat &q) { return q.norm < 1e-12f; }
+
 __global__ __launch_bounds__(256) void gf_gaussian_prepare_kernel(PrepareArgs a)
 {
     const int g = blockIdx.x * 256 + threadIdx.x;
@@ -40,7 +47,8 @@ __global__ __launch_bounds__(256) void gf_gaussian_prepare_kernel(PrepareArgs a)
         // Cov = (S R)^T (S R) = R^T S^2 R (gaussian_head.py:111-118), so with R orthonormal
         // Cov^-1 = R^T S^-2 R: the closed form replaces the host LAPACK inverse (:119).
         float R[3][3];
-        rotation_of(unit_quat_aligned16(a.rotations + 4 * (size_t)g), R);
+        const UnitQuat q = unit_quat_aligned16(a.rotations + 4 * (size_t)g);
+        rotation_of(q, R);
         const float i0 = 1.f / (sx * sx), i1 = 1.f / (sy * sy), i2 = 1.f / (sz * sz);
         float A[3][3];
 #pragma unroll
@@ -57,6 +65,12 @@ __global__ __launch_bounds__(256) void gf_gaussian_prepare_kernel(PrepareArgs a)
             for (int i = 0; i < 3; ++i)
 #pragma unroll
                 for (int j = 0; j < 3; ++j) c[3 * i + j] = A[i][j];
+        }
+        if (no_direction(q)) {
+            if (a.cov6)
+                for (int i = 0; i < 6; ++i) a.cov6[6 * (size_t)g + i] = 0.f;
+            if (a.cov9)
+                for (int i = 0; i < 9; ++i) a.cov9[9 * (size_t)g + i] = 0.f;
         }
     }
     if (a.means_int) {
@@ -140,6 +154,10 @@ __global__ __launch_bounds__(256) void gf_gaussian_prepare_bwd_kernel(PrepareArg
     out.x = (gw - w * dot) * q.inv_norm; out.y = (gx - x * dot) * q.inv_norm;
     out.z = (gy - y * dot) * q.inv_norm; out.w = (gz - z * dot) * q.inv_norm;
     *reinterpret_cast<float4 *>(a.rot_grad + 4 * (size_t)g) = out;
+    if (no_direction(q)) {
+        *reinterpret_cast<float4 *>(a.rot_grad + 4 * (size_t)g) = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int k = 0; k < 3; ++k) a.scales_grad[3 * (size_t)g + k] = 0.f;
+    }
 }
 
 // ---------------------------------------------------------------------------------------

@@ -56,12 +56,13 @@ __device__ __forceinline__ float safe_sigmoid_grad(float x, float s)
 
 // ---- unit quaternion (w, x, y, z) = F.normalize(q, dim=-1) = q / max(||q||, 1e-12) (model/utils/utils.py:23) ------------------
 struct UnitQuat {
-    float w, x, y, z, inv_norm;
+    float w, x, y, z, inv_norm, norm;   // norm = ||q|| before the clamp
 };
 __device__ __forceinline__ UnitQuat unit_quat(float q0, float q1, float q2, float q3)
 {
     const float n = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
     UnitQuat r;
+    r.norm = n;
     r.inv_norm = 1.f / fmaxf(n, 1e-12f);
     r.w = q0 * r.inv_norm; r.x = q1 * r.inv_norm; r.y = q2 * r.inv_norm; r.z = q3 * r.inv_norm;
     return r;

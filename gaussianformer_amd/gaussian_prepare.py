@@ -18,6 +18,13 @@ from ._lib import as_arg
 f32, i32 = torch.float32, torch.int32
 
 
+def _rotations_arg(rotations):
+    """``as_arg`` for the quaternions, which the kernels load 16 bytes at a time: a contiguous view that starts off a
+    16-byte boundary (a slice of an anchor tensor) is copied -- the library itself refuses such a pointer."""
+    q = as_arg(rotations)
+    return q.clone() if q.data_ptr() % 16 else q
+
+
 def gaussian_prepare(means3D, scales, rotations, pc_min, grid_size, scale_multiplier, H, W, D,
                      radii_mode=_lib.GF_RADII_SCALAR, radii_min=1, full_cov=False, status=None):
     """One launch: ``(means3D_int [P,3] i32, radii [P] | [P,3] i32, cov)`` with ``cov`` =
@@ -25,7 +32,7 @@ def gaussian_prepare(means3D, scales, rotations, pc_min, grid_size, scale_multip
     ``status`` (optional zeroed int32[1] device tensor) collects the GF_PREPARE_* bits that
     stand in for the reference's host-side asserts; no gradient is recorded here."""
     _lib.require_gpu(means3D, scales, rotations, status)
-    means3D, scales, rotations = as_arg(means3D), as_arg(scales), as_arg(rotations)
+    means3D, scales, rotations = as_arg(means3D), as_arg(scales), _rotations_arg(rotations)
     P = means3D.shape[0]
     assert means3D.shape == (P, 3) and scales.shape == (P, 3) and rotations.shape == (P, 4)
     dev = means3D.device
@@ -55,7 +62,7 @@ class _CovInverse(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scales, rotations, packed):
         _lib.require_gpu(scales, rotations)
-        s, q = as_arg(scales), as_arg(rotations)
+        s, q = as_arg(scales), _rotations_arg(rotations)
         P = s.shape[0]
         cov = torch.empty((P, 6) if packed else (P, 3, 3), dtype=f32, device=s.device)
         pc = (ctypes.c_float * 3)(0.0, 0.0, 0.0)
@@ -78,9 +85,10 @@ class _GaussianPrepare(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, scales, rotations, pc_min, grid_size, scale_multiplier, H, W, D, radii_mode, radii_min,
                 status):
+        scales, rotations = as_arg(scales), _rotations_arg(rotations)   # (once: what the launch reads is what is saved)
         means_int, radii, cov6 = gaussian_prepare(means3D, scales, rotations, pc_min, grid_size, scale_multiplier,
                                                   H, W, D, radii_mode, radii_min, status=status)
-        ctx.save_for_backward(as_arg(scales), as_arg(rotations))
+        ctx.save_for_backward(scales, rotations)
         ctx.mark_non_differentiable(means_int, radii)
         return means_int, radii, cov6
 

@@ -35,14 +35,15 @@ _lattice_cache = {}
 def pts_is_exact_lattice(pts, H, W, D):
     """Host-side twin of the device lattice verdict (``gf_splat_prep_kernel``): is ``pts [N,3]`` exactly
     ``p0 + index * step`` per axis (fp64 comparison) in x-major / z-fastest order?  Evaluated once per tensor
-    (data pointer, version counter, shape) and cached -- the voxel grid of a model does not change between frames.
+    (data pointer, version counter, shape) and cached, with a strong reference to the tensor so that its address cannot be
+    recycled by another grid while the verdict is kept -- the voxel grid of a model does not change between frames.
     The modules use it to route grids whose centres are NOT exactly representable (e.g. a 0.4 m cell) to the
     exact-fp32 kernel instead of letting the matrix-core kernel's device verdict send every frame to the slow
     arbitrary-points body.  One host read on a cache miss."""
     key = (pts.device.index, pts.data_ptr(), pts._version, tuple(pts.shape), H, W, D)
     hit = _lattice_cache.get(key)
     if hit is not None:
-        return hit
+        return hit[1]
     ok = False
     if pts.dim() == 2 and pts.shape[0] == H * W * D and pts.shape[1] == 3:
         g = pts.detach().reshape(H, W, D, 3).double()
@@ -55,9 +56,9 @@ def pts_is_exact_lattice(pts, H, W, D):
         iz = torch.arange(D, device=pts.device, dtype=torch.float64)[None, None, :]
         ok = bool(((g[..., 0] == p0[0] + ix * step[0]) & (g[..., 1] == p0[1] + iy * step[1]) &
                    (g[..., 2] == p0[2] + iz * step[2])).all().item())
-    if len(_lattice_cache) > 16:
+    if len(_lattice_cache) >= 4:
         _lattice_cache.clear()
-    _lattice_cache[key] = ok
+    _lattice_cache[key] = (pts, ok)
     return ok
 
 
@@ -345,12 +346,32 @@ class _AggregatorBase(nn.Module):
         self.D = D
         self.register_buffer('pc_min', torch.tensor(pc_min, dtype=torch.float).unsqueeze(0))
         self.grid_size = grid_size
+        # fl32(grid_size) on the device, the divisor of the integer path (_cell_of / _radius_of).  Not persistent: the
+        # state_dict stays the reference's; it follows .to() like pc_min.
+        self.register_buffer('_cell', torch.tensor(float(grid_size), dtype=torch.float), persistent=False)
         self.check_inputs = check_inputs
         self._pc_min_host = [float(v) for v in pc_min]
 
+    def _cell_of(self, x):
+        """Integer cell of fp32 positions ``x [..., 3]``: fp32 subtract, correctly rounded fp32 division, truncation
+        (``.to(torch.int)``) -- model/head/localagg/local_aggregate/__init__.py:137-141 as the CPU evaluates it, and as
+        ``gf_gaussian_prepare`` and the checker (oracle.prepare_splat_inputs) do.  The divisor is a 0-dim device TENSOR: torch
+        divides two tensors with a true fp32 division, whereas dividing by the Python float ``grid_size`` on the device
+        multiplies by ``fl32(1 / grid_size)``, which is a bit off wherever the cell is no power of two and moves positions
+        on a cell face into the neighbouring cell ("The integer path")."""
+        pc_min, cell = self.pc_min, self._cell
+        if pc_min.device != x.device:
+            pc_min, cell = pc_min.to(x.device), cell.to(x.device)
+        return ((x - pc_min) / cell).to(torch.int)
+
+    def _radius_of(self, extent):
+        """Integer radius of fp32 extents (a scale, or a Gaussian's largest): ``ceil(extent * scale_multiplier / cell)`` with
+        the same correctly rounded division as ``_cell_of`` (local_aggregate/__init__.py:141)."""
+        return torch.ceil(extent * self.scale_multiplier / self._cell.to(extent.device)).to(torch.int)
+
     def _points_int(self, pts):
-        """Voxel indices of the query points: fp32 subtract, fp32 true division, truncation (``.to(torch.int)``) --
-        model/head/localagg/local_aggregate/__init__.py:137-141.  The voxel grid of a model does not change between frames: the
+        """Voxel indices of the query points (``_cell_of``: fp32 subtract, fp32 true division -- by a device tensor, so that it
+        is one on the device too -- and truncation; model/head/localagg/local_aggregate/__init__.py:137-141).  The voxel grid of a model does not change between frames: the
         result is kept for the LAST ``pts`` tensor seen (same storage, shape and version counter, same ``pc_min`` / cell; a strong
         reference, so the address cannot be recycled) -- three passes over 640 000 points and their launches per frame otherwise.
         A caller that builds a new tensor per frame simply recomputes.  Two caveats: a buffer rewritten behind autograd's back
@@ -362,7 +383,7 @@ class _AggregatorBase(nn.Module):
         hit = getattr(self, "_points_int_cache", None)
         if not capturing and hit is not None and hit[0] == key and hit[1]._version == key[1]:
             return hit[2]
-        points_int = ((pts - self.pc_min) / self.grid_size).to(torch.int)
+        points_int = self._cell_of(pts)
         if pts.is_cuda and not capturing:
             self._points_int_cache = (key, pts, points_int)
         return points_int
@@ -376,10 +397,10 @@ class _AggregatorBase(nn.Module):
         semantics = semantics.squeeze(0)
         scales = scales.detach().squeeze(0)
         cov3D = cov3D.squeeze(0)
-        # integer path: fp32 subtract, fp32 true division, truncation (.to(torch.int)) --
-        # model/head/localagg/local_aggregate/__init__.py:137-141
+        # integer path (_cell_of): fp32 subtract, correctly rounded fp32 division by the cell held as a device tensor,
+        # truncation (.to(torch.int)) -- model/head/localagg/local_aggregate/__init__.py:137-141
         points_int = self._points_int(pts)
-        means3D_int = ((means3D.detach() - self.pc_min) / self.grid_size).to(torch.int)
+        means3D_int = self._cell_of(means3D.detach())
         violations = None
         if self.check_inputs:
             # the reference's range asserts (:138-140), evaluated on the device and read back ONCE per call by
@@ -492,7 +513,7 @@ class LocalAggregator(_AggregatorBase):
         flat = pts.detach().reshape(-1, 3)
         ok = flat.shape[0] == self.H * self.W * self.D and pts_is_exact_lattice(flat, self.H, self.W, self.D)
         if ok:
-            pi = ((flat - self.pc_min.to(flat.device)) / self.grid_size).to(torch.int).long()
+            pi = self._cell_of(flat).long()
             key = (pi[:, 0] * self.W + pi[:, 1]) * self.D + pi[:, 2]
             ok = bool(((pi[:, 1] >= 0) & (pi[:, 1] < self.W) & (pi[:, 2] >= 0) & (pi[:, 2] < self.D) &
                        (key == torch.arange(flat.shape[0], device=flat.device))).all().item())
@@ -543,7 +564,7 @@ class LocalAggregator(_AggregatorBase):
             w["host"], w["event"] = _lib.host_copy(state[:_lib.STATE_USED_BYTES].view(torch.int32), device)
 
     def _radii(self, scales):
-        return torch.ceil(scales.max(dim=-1)[0] * self.scale_multiplier / self.grid_size).to(torch.int)
+        return self._radius_of(scales.max(dim=-1)[0])
 
     def forward(self, pts, means3D, opacities, semantics, scales, cov3D):
         logits = self._splat(*self._splat_inputs(pts, means3D, opacities, semantics, scales, cov3D))
@@ -569,10 +590,7 @@ class LocalAggregatorProb(_AggregatorBase):
         return _LocalAggregateProb.apply(*args, self.H if H is None else H, self.W, self.D)
 
     def _radii(self, scales):
-        if self.per_axis_radii:
-            radii = torch.ceil(scales * self.scale_multiplier / self.grid_size).to(torch.int)
-        else:
-            radii = torch.ceil(scales.max(dim=-1)[0] * self.scale_multiplier / self.grid_size).to(torch.int)
+        radii = self._radius_of(scales if self.per_axis_radii else scales.max(dim=-1)[0])
         return radii.clamp(min=self.radii_min)
 
     def forward(self, pts, means3D, opas, semantics, scales, cov3D):

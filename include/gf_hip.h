@@ -251,7 +251,8 @@ int gf_splat_box_volumes(int radii_per_axis, int P, int H, int W, int D,
  *   cov6 f32 [P,6] = Sigma^-1 as (xx,yy,zz,xy,yz,xz)   cov9 f32 [P,9] = full Sigma^-1
  *   status i32 [1] (device, caller-zeroed): GF_PREPARE_* bits, checked by the caller when it wants to
  * Sigma^-1 = R^T S^-2 R in closed form; differs from the reference's fp32 LAPACK inverse by
- * O(cond(Sigma) * 2^-24) relative.
+ * O(cond(Sigma) * 2^-24) relative.  A quaternion of norm below 1e-12 (the clamp of F.normalize) has no direction and
+ * is taken as the zero quaternion: Sigma^-1 = 0, and a zero rotation gradient in gf_gaussian_prepare_backward.
  */
 int gf_gaussian_prepare(int P, int H, int W, int D, const float *pc_min, float grid_size,
                         float scale_multiplier, int radii_mode, int radii_min,
