@@ -900,14 +900,25 @@ __global__ __launch_bounds__(256, 3) void gf_subm_wgrad_kernel(SubmArgs a)
             wgrad_fetch_idx<COUT, GQ>(gi, a.pair_out, pb + 2 * kBatch, p1);
         }
         if (active) {
+            // Blocked summation: a step's 32 pairs are summed from zero and the step's sum is added to the chunk's.  One chain
+            // through all 512 pairs of a chunk rounds at the size of the running sum after EVERY pair; where a few products
+            // dominate sum |a||b| (one huge channel per row) that is 512 roundings of the full sum -- 21 - 43 units of
+            // 2^-24 sum |a||b| measured on such operands (tests/test_subm_truth_gpu.py) -- and this way 32 + 16: 6.7 - 13.4
+            // units there, 6.3 -> 3.6 on ordinary operands.  128 -> 128 at 25 600 / 144 000 anchors: 86.7 -> 88.0 us / 1.716 ->
+            // 1.726 ms; 128 -> 64 and 64 -> 128: 51.9 -> 49.6 us.
 #pragma unroll
-            for (int s = 0; s < kBatch / 2; ++s) {
+            for (int b = 0; b < NBW; ++b) {
+                const int blk = wave * NBW + b, mi = blk / NJ, nj = blk % NJ;
+                f32x16 part;
 #pragma unroll
-                for (int b = 0; b < NBW; ++b) {
-                    const int blk = wave * NBW + b, mi = blk / NJ, nj = blk % NJ;
-                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_f[(2 * s + h) * FS + 32 * mi + i], s_g[(2 * s + h) * GS + 32 * nj + i],
-                                                                  acc[b], 0, 0, 0);
-                }
+                for (int r = 0; r < 16; ++r) part[r] = 0.f;
+#pragma unroll
+                for (int s = 0; s < kBatch / 2; ++s)
+                    part = __builtin_amdgcn_mfma_f32_32x32x2f32(s_f[(2 * s + h) * FS + 32 * mi + i], s_g[(2 * s + h) * GS + 32 * nj + i],
+                                                                part, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[b][r] += part[r];
+                __builtin_amdgcn_sched_barrier(0);   // one block's chain at a time: ONE extra accumulator, not NBW (98 spills at 128 x 128)
             }
         }
     }

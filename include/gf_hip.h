@@ -388,13 +388,22 @@ int gf_feature_maps_format(int planes, int C, int L, const int *hw, float *const
  * bf16 matrix cores with fp32-EQUIVALENT operands: every fp32 value is split into three bf16 terms and a product is
  * six v_mfma_f32_32x32x16_bf16 partial products accumulated in fp32 (the dropped terms are <= 2^-24 relative each);
  * gf_set_option("subm.f32_mfma", 1) selects the f32-MFMA kernel instead (v_mfma_f32_32x32x2_f32: bitwise an fmaf
- * chain, ~13 % slower).  The weight gradient runs on f32 MFMAs.  Results are deterministic except the weight gradient
+ * chain, ~13 % slower).  The weight gradient runs on f32 MFMAs with blocked summation (32 pairs summed from zero, the
+ * blocks added per chunk of 512 pairs, float atomics between the chunks of a segment): measured <= 3.6 * 2^-24 sum|a||b| per
+ * element on ordinary operands and <= 13.4 * 2^-24 where a few products dominate a sum.  Results are deterministic except the weight gradient
  * of segments longer than 512 pairs (float atomics between their chunks).
  * gf_subm_conv_apply_scratch (round 6) is the same operator with `scratch` of gf_subm_apply_scratch_bytes(N, Cin) bytes (device,
  * 16-byte aligned, contents irrelevant before and after the call): the feature rows are split once per call into TWO f16 terms
  * under an exact power-of-two scale per row (the weight slices likewise, per output column) and a product is THREE
  * v_mfma_f32_32x32x16_f16 partial products (dropped term <= 2^-22 relative) -- half the matrix-core work of the bf16 form,
- * ~2^-21 per product instead of 2^-24 (both far inside 3e-5 of the fp64 definition, tests/test_subm_conv.py).  The Python
+ * ~2^-21 per product instead of 2^-24 (both far inside 3e-5 of the fp64 definition, tests/test_subm_conv.py).  f16 has less
+ * RANGE than fp32, and that is part of the contract: a row (column) is scaled so that its largest |x| lies in [2^14, 2^15), so an
+ * element more than 2^17 times smaller than its row's (column's) largest loses its lo term to f16's subnormal spacing -- each
+ * operand errs by at most 2^-22 |x| + 2^-39 max|row or column|, and an output element by at most
+ *     2^-20 sum|a||b|  +  2 * 2^-39 (sum_pairs max|a_row| sum_c |b_c|  +  sum_pairs sum_c |a_c| max|b_column|)
+ * (tests/subm_judge.py holds every element of the output and of the input gradient to exactly this, and the
+ * bf16 and f32 formats, which have fp32's range, to the first term alone).  The second term matters only where a row's or a
+ * column's large elements do not dominate sum|a||b|.  The Python
  * module calls this one; gf_set_option("subm.bf16x3", 1) makes it take the three-term bf16 kernels (= gf_subm_conv_apply),
  * "subm.f32_mfma" the exact-f32 MFMA kernel.
  */
