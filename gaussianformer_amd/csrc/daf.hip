@@ -18,7 +18,7 @@
 // of a row's taps follows integer LDS atomics, so the last bits may differ between runs);
 // shapes the sort does not cover fall back to the reference's atomicAdd scatter.
 
-#include "gf_common.hpp"
+#include "gf_daf.hpp"
 
 namespace gf {
 
@@ -36,106 +36,6 @@ struct DafArgs {
     int B, cams, num_feat, C, L, pts, G;
     long long total;  // B * pts * (C / VEC)
 };
-
-template <int VEC>
-struct VecT;
-struct alignas(16) Float8 { float4 lo, hi; };
-template <>
-struct VecT<8> { using type = Float8; };
-template <>
-struct VecT<4> { using type = float4; };
-template <>
-struct VecT<2> { using type = float2; };
-template <>
-struct VecT<1> { using type = float; };
-
-template <int VEC>
-__device__ __forceinline__ void vload(const float *p, float (&v)[VEC])
-{
-    using T = typename VecT<VEC>::type;
-    const T t = *reinterpret_cast<const T *>(p);
-    const float *f = reinterpret_cast<const float *>(&t);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) v[j] = f[j];
-}
-
-template <int VEC>
-__device__ __forceinline__ void vstore(float *p, const float (&v)[VEC])
-{
-    using T = typename VecT<VEC>::type;
-    T t;
-    float *f = reinterpret_cast<float *>(&t);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) f[j] = v[j];
-    *reinterpret_cast<T *>(p) = t;
-}
-
-// The bilinear cell of a tap position (bilinear_sampling, deformable_aggregation_cuda.cu:13-29,51): its low pixel, the
-// fractions and the four coefficients; of corner k (0 .. 3: k >> 1 the row step, k & 1 the column step) coefficient and pixel.
-struct Cell {
-    int h_low, w_low;
-    float w1, w2, w3, w4, lh, lw, hh, hw;
-    __device__ __forceinline__ float coef(int k) const { return k == 0 ? w1 : k == 1 ? w2 : k == 2 ? w3 : w4; }
-    __device__ __forceinline__ int py(int k) const { return h_low + (k >> 1); }
-    __device__ __forceinline__ int px(int k) const { return w_low + (k & 1); }
-};
-__device__ __forceinline__ Cell make_cell(float h_im, float w_im)
-{
-    Cell t;
-    t.h_low = (int)floorf(h_im);
-    t.w_low = (int)floorf(w_im);
-    t.lh = h_im - t.h_low;
-    t.lw = w_im - t.w_low;
-    t.hh = 1 - t.lh;
-    t.hw = 1 - t.lw;
-    t.w1 = t.hh * t.hw; t.w2 = t.hh * t.lw; t.w3 = t.lh * t.hw; t.w4 = t.lh * t.lw;
-    return t;
-}
-
-// ... and which of the corners lie in the image
-struct Taps : Cell {
-    bool ok1, ok2, ok3, ok4;
-};
-__device__ __forceinline__ Taps make_taps(float h_im, float w_im, int height, int width)
-{
-    Taps t;
-    static_cast<Cell &>(t) = make_cell(h_im, w_im);
-    const int h_high = t.h_low + 1, w_high = t.w_low + 1;
-    t.ok1 = t.h_low >= 0 && t.w_low >= 0;
-    t.ok2 = t.h_low >= 0 && w_high <= width - 1;
-    t.ok3 = h_high <= height - 1 && t.w_low >= 0;
-    t.ok4 = h_high <= height - 1 && w_high <= width - 1;
-    return t;
-}
-
-// pixel rows (h * width + w) of the four taps with out-of-image coordinates clamped to the nearest
-// valid pixel; such taps carry a zero coefficient (ok1..ok4 false), their value is never used
-struct Corners {
-    int r1, r2, r3, r4;
-};
-__device__ __forceinline__ Corners clamp_corners(const Taps &t, int height, int width)
-{
-    const int h0 = max(t.h_low, 0), h1 = min(t.h_low + 1, height - 1);
-    const int w0 = max(t.w_low, 0), w1 = min(t.w_low + 1, width - 1);
-    return {h0 * width + w0, h0 * width + w1, h1 * width + w0, h1 * width + w1};
-}
-
-// The four corner values of a level (base = its first pixel row, this lane's channels).  All four taps are loaded
-// unconditionally from clamped (always valid) pixels and the out-of-image ones are replaced by zero BY THE CALLER: a load under
-// `if (ok)` is followed by its own s_waitcnt inside the branch, which made the sixteen taps of a camera a serial chain.  (The
-// zeroing stays with the callers' arithmetic: moved in here, the selects come before the forward's sums in another order and
-// the compiler contracts a different product of val = w1 x1 + .. + w4 x4 into the FMAs -- other last bits, and not the same
-// ones in the three forward kernels.)
-template <int VEC>
-__device__ __forceinline__ void load_corners(const float *base, int C, const Taps &t, int height, int width,
-                                             float (&v1)[VEC], float (&v2)[VEC], float (&v3)[VEC], float (&v4)[VEC])
-{
-    const Corners c = clamp_corners(t, height, width);
-    vload<VEC>(base + (size_t)c.r1 * C, v1);
-    vload<VEC>(base + (size_t)c.r2 * C, v2);
-    vload<VEC>(base + (size_t)c.r3 * C, v3);
-    vload<VEC>(base + (size_t)c.r4 * C, v4);
-}
 
 template <int VEC>
 __global__ __launch_bounds__(256) void gf_daf_fwd_kernel(DafArgs a)

@@ -20,7 +20,7 @@
 //      entry); the four partial rows are added across the lane groups and ONE 512-byte row leaves per anchor.
 // Results: the same products as the three-step path, summed in a different order (pairs are dealt to four lane groups and the key
 // points are not summed last): equal to ~1e-6 of the row's magnitude, tests/test_daf_fused.py holds them to 1e-5.
-#include "gf_common.hpp"
+#include "gf_daf.hpp"
 
 #ifndef GF_FU_UNROLL
 #define GF_FU_UNROLL 1   // levels of a visible pair whose row pieces are in flight together (measured, round 6: 2 -> 126 registers, four waves
@@ -95,51 +95,17 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
     // ---- 1. projection (project_points, deformable_module.py:268-285) and the list of visible pairs
     if (!a.raw)
         for (int i = lane; i < LPG; i += 64) s_anc[i] = a.raw_anchor[anchor * LPG + i];
-    int nvis_total = 0;
-    for (int q0 = 0; q0 < npair; q0 += 64) {
-        const int q = q0 + lane;
-        bool vis = false;
-        if (q < npair) {
-            const int pt = q / a.cams, cam = q - pt * a.cams;
-            const float *kp = a.key_points + (anchor * a.pts + pt) * 3;
-            const float *M = a.proj + ((size_t)b * a.cams + cam) * 16;
-            const float X = kp[0], Y = kp[1], Z = kp[2];
-            const float px = M[0] * X + M[1] * Y + M[2] * Z + M[3];
-            const float py = M[4] * X + M[5] * Y + M[6] * Z + M[7];
-            const float pz = M[8] * X + M[9] * Y + M[10] * Z + M[11];
-            const float zc = fmaxf(pz, 1e-5f);  // torch.clamp(points_2d[..., 2:3], min=1e-5)
-            float u = px / zc, v = py / zc;
-            if (a.image_wh) {
-                u /= a.image_wh[((size_t)b * a.cams + cam) * 2];
-                v /= a.image_wh[((size_t)b * a.cams + cam) * 2 + 1];
-            }
-            vis = (pz > 1e-5f) && (u > 0) && (u < 1) && (v > 0) && (v < 1);
-            s_uv[q] = make_float2(u, v);
-        }
-        const unsigned long long bal = __builtin_amdgcn_ballot_w64(vis);
-        const int pos = nvis_total + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-        if (vis) s_list[pos] = ((q / a.cams) << 8) | (q % a.cams);   // (key point, camera): pts * cams <= 256
-        nvis_total += __builtin_popcountll(bal);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
+    const int nvis = visible_pairs<false>(a.key_points, anchor, a.proj, a.image_wh, (size_t)b * a.cams, a.pts, a.cams, lane, s_uv, s_list,
+                                          nullptr, nullptr);
+    wave_lds_handover();
     float acc[CPL];
 #pragma unroll
     for (int j = 0; j < CPL; ++j) acc[j] = 0.f;
-    const int nvis = nvis_total;
     if (nvis > 0) {
         // ---- 2. softmax over the visible (pair, level) entries per group; entry e = (v * L + l) * G + g, so g = lane % G
         const int E = nvis * LG;
-        auto logit_at = [&](int pc, int l, int g) -> float {   // pc = (key point << 8) | camera
-            const int pt = pc >> 8, cam = pc & 255;
-            const int o = (l * a.pts + pt) * a.G + g;
-            if (a.raw) return a.raw[(anchor * a.cams + cam) * LPG + o];
-            return s_anc[o] + (s_cam ? s_cam[cam * LPG + o] : a.raw_cam[((size_t)b * a.cams + cam) * LPG + o]);
-        };
-        auto kept = [&](int pc, int l, int g) -> bool {
-            if (!MASK) return true;
-            return a.wmask[(anchor * a.cams + (pc & 255)) * LPG + (l * a.pts + (pc >> 8)) * a.G + g] != 0;
-        };
+        const FusedLogits<MASK> lg{a.raw, s_anc, s_cam, a.raw_cam + (size_t)b * a.cams * LPG, a.wmask, (size_t)anchor * a.cams * LPG,
+                                   a.pts, a.G, LPG};
         // (entries of a lane: e = lane + 64 k.  Where L G divides 64 -- the usual 4 x 4 -- the lane keeps its (level, group) and walks
         // the pairs in steps of 64 / (L G): no division per entry)
         const bool stepped = (64 % LG) == 0;
@@ -147,14 +113,14 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
         auto logit = [&](int e, int k) -> float {
             if (stepped) {
                 const int pc = s_list[dv + k * vstep];
-                return kept(pc, l0, g0) ? logit_at(pc, l0, g0) : -INFINITY;
+                return lg.kept(pc, l0, g0) ? lg.at(pc, l0, g0) : -INFINITY;
             }
             const int v = e / LG, r = e - v * LG, l = r / a.G;
-            return kept(s_list[v], l, r - l * a.G) ? logit_at(s_list[v], l, r - l * a.G) : -INFINITY;
+            return lg.kept(s_list[v], l, r - l * a.G) ? lg.at(s_list[v], l, r - l * a.G) : -INFINITY;
         };
         float m = -INFINITY;
         for (int e = lane, k = 0; e < E; e += 64, ++k) m = fmaxf(m, logit(e, k));
-        for (int d = a.G; d < 64; d <<= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+        m = wave_xor_reduce_strided(m, a.G, Max());
         float s = 0.f;
         for (int e = lane, k = 0; e < E; e += 64, ++k) {
             if (MASK) {
@@ -164,7 +130,7 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
                 s += fast_exp(logit(e, k) - m);
             }
         }
-        for (int d = a.G; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
+        s = wave_xor_reduce_strided(s, a.G, Sum());
         // (lane % G == g holds group g's maximum and sum; a sampling lane needs those of ITS channel group: lane grp < G has them)
         const float inv_mine = s > 0.f ? 1.f / s : 0.f;
         const float inv = __shfl(inv_mine, grp, 64), mg = __shfl(m, grp, 64);
@@ -178,31 +144,19 @@ __global__ __launch_bounds__(256, GF_FU_MINB) void gf_daf_fused_kernel(DafFusedA
                 const int h = a.spatial_shape[2 * l], w = a.spatial_shape[2 * l + 1];
                 const float h_im = uv.y * h - 0.5f, w_im = uv.x * w - 0.5f;   // deformable_aggregation_cuda.cu:174-175
                 // bilinear_sampling, :13-53: four taps from clamped pixels, out-of-image ones contribute exactly 0
-                const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-                const float lh = h_im - h_low, lw = w_im - w_low, hh = 1 - lh, hw = 1 - lw;
-                const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
-                const bool ok1 = h_low >= 0 && w_low >= 0, ok2 = h_low >= 0 && w_low + 1 <= w - 1;
-                const bool ok3 = h_low + 1 <= h - 1 && w_low >= 0, ok4 = h_low + 1 <= h - 1 && w_low + 1 <= w - 1;
-                const int hc0 = max(h_low, 0), hc1 = min(h_low + 1, h - 1), wc0 = max(w_low, 0), wc1 = min(w_low + 1, w - 1);
-                const float *base = fcam + (size_t)a.scale_start[l] * a.C;
+                const Taps t = make_taps(h_im, w_im, h, w);
                 float v1[CPL], v2[CPL], v3[CPL], v4[CPL];
-#pragma unroll
-                for (int j = 0; j < CPL; j += 4) {
-                    *reinterpret_cast<float4 *>(v1 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc0 * w + wc0) * a.C + j);
-                    *reinterpret_cast<float4 *>(v2 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc0 * w + wc1) * a.C + j);
-                    *reinterpret_cast<float4 *>(v3 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc0) * a.C + j);
-                    *reinterpret_cast<float4 *>(v4 + j) = *reinterpret_cast<const float4 *>(base + (size_t)(hc1 * w + wc1) * a.C + j);
-                }
-                const float wt = kept(pc, l, grp) ? fast_exp(logit_at(pc, l, grp) - mg) * inv : 0.f;
+                load_corners<CPL>(fcam + (size_t)a.scale_start[l] * a.C, a.C, t, h, w, v1, v2, v3, v4);
+                const float wt = lg.kept(pc, l, grp) ? fast_exp(lg.at(pc, l, grp) - mg) * inv : 0.f;
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
-                    const float x1 = ok1 ? v1[j] : 0.f, x2 = ok2 ? v2[j] : 0.f, x3 = ok3 ? v3[j] : 0.f, x4 = ok4 ? v4[j] : 0.f;
-                    acc[j] += (w1 * x1 + w2 * x2 + w3 * x3 + w4 * x4) * wt;
+                    const float x1 = t.ok1 ? v1[j] : 0.f, x2 = t.ok2 ? v2[j] : 0.f, x3 = t.ok3 ? v3[j] : 0.f, x4 = t.ok4 ? v4[j] : 0.f;
+                    acc[j] += (t.w1 * x1 + t.w2 * x2 + t.w3 * x3 + t.w4 * x4) * wt;
                 }
             }
         }
     }
-    // ---- the lane groups' partial rows -> one row per anchor
+    // ---- the lane groups' partial rows -> one row per anchor (wave_xor_reduce_strided's order, all channels in ONE loop over d)
     for (int d = CV; d < 64; d <<= 1)
 #pragma unroll
         for (int j = 0; j < CPL; ++j) acc[j] += __shfl_xor(acc[j], d, 64);
@@ -274,36 +228,10 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
         // ---- 1. projection and the list of visible pairs (as the forward)
         if (split)
             for (int i = lane; i < LPG; i += 64) s_anc[i] = a.raw_anchor[anchor * LPG + i];
-        int nvis = 0;
-        for (int q0 = 0; q0 < npair; q0 += 64) {
-            const int q = q0 + lane;
-            bool vis = false;
-            if (q < npair) {
-                const int pt = q / a.cams, cam = q - pt * a.cams;
-                const float *kp = a.key_points + (anchor * a.pts + pt) * 3;
-                const float *M = a.proj + ((size_t)b * a.cams + cam) * 16;
-                const float X = kp[0], Y = kp[1], Z = kp[2];
-                const float px = M[0] * X + M[1] * Y + M[2] * Z + M[3];
-                const float py = M[4] * X + M[5] * Y + M[6] * Z + M[7];
-                const float pz = M[8] * X + M[9] * Y + M[10] * Z + M[11];
-                const float zc = fmaxf(pz, 1e-5f);
-                float u = px / zc, v = py / zc;
-                if (a.image_wh) {
-                    u /= a.image_wh[((size_t)b * a.cams + cam) * 2];
-                    v /= a.image_wh[((size_t)b * a.cams + cam) * 2 + 1];
-                }
-                vis = (pz > 1e-5f) && (u > 0) && (u < 1) && (v > 0) && (v < 1);
-                s_uv[q] = make_float2(u, v);
-                s_guv[q] = make_float2(0.f, 0.f);
-            }
-            const unsigned long long bal = __builtin_amdgcn_ballot_w64(vis);
-            const int pos = nvis + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            if (q < npair) s_pidx[q] = vis ? pos : -1;
-            if (vis) s_list[pos] = ((q / a.cams) << 8) | (q % a.cams);
-            nvis += __builtin_popcountll(bal);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        const int nvis = visible_pairs<true>(a.key_points, anchor, a.proj, a.image_wh, (size_t)b * a.cams, a.pts, a.cams, lane, s_uv, s_list,
+                                             s_guv, s_pidx);
+        wave_lds_handover();
+        // (FusedLogits here: 46 -> 47 spilled SGPRs, so this kernel keeps its own view of the logits; profiles/daf_block_pieces.txt)
         auto logit_at = [&](int pc, int l, int g) -> float {
             const int pt = pc >> 8, cam = pc & 255;
             const int o = (l * a.pts + pt) * a.G + g;
@@ -327,14 +255,14 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
             entry(e, pc, l);
             if (kept(pc, l, gl)) m = fmaxf(m, logit_at(pc, l, gl));
         }
-        for (int d = a.G; d < 64; d <<= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+        m = wave_xor_reduce_strided(m, a.G, Max());
         float s = 0.f;
         for (int e = lane; e < E; e += 64) {
             int pc, l;
             entry(e, pc, l);
             if (kept(pc, l, gl)) s += fast_exp(logit_at(pc, l, gl) - m);
         }
-        for (int d = a.G; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
+        s = wave_xor_reduce_strided(s, a.G, Sum());
         const float inv_mine = s > 0.f ? 1.f / s : 0.f;
         const float inv = __shfl(inv_mine, grp, 64), mg = __shfl(m, grp, 64);
         // ---- 3. the forward's taps again: gw, d (u, v), d mc_ms_feat
@@ -351,14 +279,9 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
             for (int l = 0; l < a.L; ++l) {
                 const int h = a.spatial_shape[2 * l], w = a.spatial_shape[2 * l + 1];
                 const float h_im = uv.y * h - 0.5f, w_im = uv.x * w - 0.5f;
-                const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-                const float lh = h_im - h_low, lw = w_im - w_low, hh = 1 - lh, hw = 1 - lw;
-                const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
-                const bool ok1 = h_low >= 0 && w_low >= 0, ok2 = h_low >= 0 && w_low + 1 <= w - 1;
-                const bool ok3 = h_low + 1 <= h - 1 && w_low >= 0, ok4 = h_low + 1 <= h - 1 && w_low + 1 <= w - 1;
-                const int hc0 = max(h_low, 0), hc1 = min(h_low + 1, h - 1), wc0 = max(w_low, 0), wc1 = min(w_low + 1, w - 1);
-                const size_t p1 = (size_t)(hc0 * w + wc0) * a.C, p2 = (size_t)(hc0 * w + wc1) * a.C;
-                const size_t p3 = (size_t)(hc1 * w + wc0) * a.C, p4 = (size_t)(hc1 * w + wc1) * a.C;
+                const Taps t = make_taps(h_im, w_im, h, w);
+                const Corners c = clamp_corners(t, h, w);   // (load_corners below: 2 223 instructions for 2 222)
+                const size_t p1 = (size_t)c.r1 * a.C, p2 = (size_t)c.r2 * a.C, p3 = (size_t)c.r3 * a.C, p4 = (size_t)c.r4 * a.C;
                 const float *base = fcam + (size_t)a.scale_start[l] * a.C;
                 float v1[CPL], v2[CPL], v3[CPL], v4[CPL];
 #pragma unroll
@@ -372,12 +295,13 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
                 float sv = 0.f, sw = 0.f, sh = 0.f;
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
-                    const float x1 = ok1 ? v1[j] : 0.f, x2 = ok2 ? v2[j] : 0.f, x3 = ok3 ? v3[j] : 0.f, x4 = ok4 ? v4[j] : 0.f;
-                    sv += go[j] * (w1 * x1 + w2 * x2 + w3 * x3 + w4 * x4);
-                    sw += go[j] * (hh * (x2 - x1) + lh * (x4 - x3));   // grad_w_weight, :84-110
-                    sh += go[j] * (hw * (x3 - x1) + lw * (x4 - x2));   // grad_h_weight
+                    const float x1 = t.ok1 ? v1[j] : 0.f, x2 = t.ok2 ? v2[j] : 0.f, x3 = t.ok3 ? v3[j] : 0.f, x4 = t.ok4 ? v4[j] : 0.f;
+                    sv += go[j] * (t.w1 * x1 + t.w2 * x2 + t.w3 * x3 + t.w4 * x4);
+                    sw += go[j] * (t.hh * (x2 - x1) + t.lh * (x4 - x3));   // grad_w_weight, :84-110
+                    sh += go[j] * (t.hw * (x3 - x1) + t.lw * (x4 - x2));   // grad_h_weight
                 }
                 if (need_gw) {
+                    // (xor 1 .. ASCENDING, here and for gu, gv below: group_sum adds in descending order -- other last bits)
                     for (int d = 1; d < lanes_per_group; d <<= 1) sv += __shfl_xor(sv, d, 64);
                     if (cv % lanes_per_group == 0) s_gw[v * LG + l * a.G + grp] = sv;
                 }
@@ -385,9 +309,9 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
                 gv += (float)h * wt * sh;
                 if (args.grad_feat && wt != 0.f) {
                     float *gbase = args.grad_feat + (row0 + a.scale_start[l]) * a.C + c0;
-                    const bool ok[4] = {ok1, ok2, ok3, ok4};
+                    const bool ok[4] = {t.ok1, t.ok2, t.ok3, t.ok4};
                     const size_t po[4] = {p1, p2, p3, p4};
-                    const float cw[4] = {w1 * wt, w2 * wt, w3 * wt, w4 * wt};
+                    const float cw[4] = {t.w1 * wt, t.w2 * wt, t.w3 * wt, t.w4 * wt};
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
                         if (ok[k])
@@ -403,8 +327,7 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
                 if (cv == 0) s_guv[pt * a.cams + cam] = make_float2(gu, gv);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_handover();
         // ---- 4. softmax backward: d logit_e = w_e (gw_e - sum_e' w_e' gw_e'), written in the logits' layouts
         if (need_gw) {
             float dot = 0.f;
@@ -413,7 +336,7 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
                 entry(e, pc, l);
                 if (kept(pc, l, gl)) dot += fast_exp(logit_at(pc, l, gl) - m) * inv_mine * s_gw[e];
             }
-            for (int d = a.G; d < 64; d <<= 1) dot += __shfl_xor(dot, d, 64);
+            dot = wave_xor_reduce_strided(dot, a.G, Sum());
             auto dlogit = [&](int pt, int cam, int l) -> float {   // group gl
                 const int v = s_pidx[pt * a.cams + cam], pc = (pt << 8) | cam;
                 if (v < 0 || !kept(pc, l, gl)) return 0.f;
@@ -439,31 +362,28 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
                     if (args.grad_raw_anchor) args.grad_raw_anchor[anchor * LPG + i] = sum;
                 }
         }
-        // ---- 5. projection backward (gf_daf_prepare_backward's arithmetic): u = x / max(z, 1e-5) / w_img
+        // ---- 5. projection backward (gf_daf_prepare_backward's arithmetic), u = x / max(z, 1e-5) / w_img.  (Its text, not a helper
+        // shared with gf_daf_prepare_bwd_kernel: 7 instructions and a 47th spilled SGPR here, other FMA contractions there.)
         if (args.grad_kp) {
             for (int q = lane; q < npair; q += 64) {
                 const int pt = q / a.cams, cam = q - pt * a.cams;
                 const float *kp = a.key_points + (anchor * a.pts + pt) * 3;
                 const float *M = a.proj + ((size_t)b * a.cams + cam) * 16;
-                const float X = kp[0], Y = kp[1], Z = kp[2];
-                const float px = M[0] * X + M[1] * Y + M[2] * Z + M[3];
-                const float py = M[4] * X + M[5] * Y + M[6] * Z + M[7];
-                const float pz = M[8] * X + M[9] * Y + M[10] * Z + M[11];
-                const float zc = fmaxf(pz, 1e-5f), iz = 1.f / zc;
+                const Proj p = project(M, kp[0], kp[1], kp[2]);
+                const float zc = fmaxf(p.z, 1e-5f), iz = 1.f / zc;
                 const float2 g2 = s_guv[q];
                 float gu = g2.x, gv = g2.y;
                 if (a.image_wh) {
                     gu /= a.image_wh[((size_t)b * a.cams + cam) * 2];
                     gv /= a.image_wh[((size_t)b * a.cams + cam) * 2 + 1];
                 }
-                const float cz = pz > 1e-5f ? -(gu * px + gv * py) * iz * iz : 0.f;
+                const float cz = p.z > 1e-5f ? -(gu * p.x + gv * p.y) * iz * iz : 0.f;
                 const float cx = gu * iz, cy = gv * iz;
                 s_part[3 * q] = cx * M[0] + cy * M[4] + cz * M[8];
                 s_part[3 * q + 1] = cx * M[1] + cy * M[5] + cz * M[9];
                 s_part[3 * q + 2] = cx * M[2] + cy * M[6] + cz * M[10];
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handover();
             for (int pt = lane; pt < a.pts; pt += 64) {
                 float gx = 0.f, gy = 0.f, gz = 0.f;
                 for (int cam = 0; cam < a.cams; ++cam) {
@@ -474,8 +394,7 @@ __global__ __launch_bounds__(256) void gf_daf_fused_bwd_kernel(DafFusedBwdArgs a
                 o[0] = gx; o[1] = gy; o[2] = gz;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();   // the wave's LDS is reused by its next anchor
+        wave_lds_handover();   // the wave's LDS is reused by its next anchor
     }
     if (args.part_cam) {
         __syncthreads();

@@ -7,7 +7,7 @@
 //     no camera sees.
 // The reference runs ~15 elementwise / permute / softmax kernels over the 88-498 MB weights tensor;
 // here one wave per anchor reads the raw logits once and writes the DAF-layout weights once.
-#include "gf_common.hpp"
+#include "gf_daf.hpp"
 
 namespace gf {
 
@@ -27,18 +27,6 @@ struct DafPrepArgs {
     float *grad_key_points;      // backward: [B, A, pts, 3]
     int B, A, pts, cams, L, G;
 };
-
-struct Proj {
-    float x, y, z;
-};
-__device__ __forceinline__ Proj project(const float *M, float X, float Y, float Z)
-{
-    Proj p;
-    p.x = M[0] * X + M[1] * Y + M[2] * Z + M[3];
-    p.y = M[4] * X + M[5] * Y + M[6] * Z + M[7];
-    p.z = M[8] * X + M[9] * Y + M[10] * Z + M[11];
-    return p;
-}
 
 // s_tab[i] for output element i = ((pt * cams + cam) * L + l) * G + g: the input offset
 // ((cam * L + l) * pts + pt) * G + g, with (pt * cams + cam) << 20 on top when PAIR.  A thread splits its
@@ -95,19 +83,11 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_kernel(DafPrepArgs a)
         // ---- projection (project_points, deformable_module.py:268-285)
         for (int q = lane; q < npair; q += 64) {
             const int pt = q / a.cams, cam = q - pt * a.cams;
-            const float *kp = a.key_points + (anchor * a.pts + pt) * 3;
-            const Proj p = project(a.proj + ((size_t)b * a.cams + cam) * 16, kp[0], kp[1], kp[2]);
-            const float zc = fmaxf(p.z, 1e-5f);  // torch.clamp(points_2d[..., 2:3], min=1e-5)
-            float u = p.x / zc, v = p.y / zc;
-            if (a.image_wh) {
-                u /= a.image_wh[((size_t)b * a.cams + cam) * 2];
-                v /= a.image_wh[((size_t)b * a.cams + cam) * 2 + 1];
-            }
-            s_valid[wave][q] = (p.z > 1e-5f) && (u > 0) && (u < 1) && (v > 0) && (v < 1);
-            *reinterpret_cast<float2 *>(a.points_2d + ((anchor * a.pts + pt) * a.cams + cam) * 2) = make_float2(u, v);
+            const PairProj r = project_pair(a.key_points + (anchor * a.pts + pt) * 3, a.proj, a.image_wh, (size_t)b * a.cams + cam);
+            s_valid[wave][q] = r.vis;
+            *reinterpret_cast<float2 *>(a.points_2d + ((anchor * a.pts + pt) * a.cams + cam) * 2) = make_float2(r.u, r.v);
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_handover();
         // ---- masked softmax over (pts, cams, L) per group; i runs in OUTPUT order [pt][cam][l][g]
         const int E = npair * a.L * a.G;
         const float *raw = a.raw + anchor * E;
@@ -118,8 +98,7 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_kernel(DafPrepArgs a)
             } else {
                 for (int i = lane; i < E; i += 64) mine[i] = raw[i];
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handover();
         }
         const unsigned char *wm = a.wmask ? a.wmask + anchor * E : nullptr;
         if (STAGE && a.G == 4) {
@@ -165,8 +144,7 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_kernel(DafPrepArgs a)
                 sum.x += e.x; sum.y += e.y; sum.z += e.z; sum.w += e.w;
             }
             sum.x = wave_sum(sum.x); sum.y = wave_sum(sum.y); sum.z = wave_sum(sum.z); sum.w = wave_sum(sum.w);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handover();
             const float4 inv = make_float4(sum.x > 0.f ? 1.f / sum.x : 0.f, sum.y > 0.f ? 1.f / sum.y : 0.f,
                                            sum.z > 0.f ? 1.f / sum.z : 0.f, sum.w > 0.f ? 1.f / sum.w : 0.f);
             float4 *out4 = reinterpret_cast<float4 *>(a.weights + anchor * E);
@@ -175,8 +153,7 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_kernel(DafPrepArgs a)
                 // groups without a visible, kept entry have e = 0 everywhere: weights = 0 (:196-213)
                 out4[i4] = make_float4(e.x * inv.x, e.y * inv.y, e.z * inv.z, e.w * inv.w);
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();  // LDS copies are reused by the wave's next anchor
+            wave_lds_handover();  // LDS copies are reused by the wave's next anchor
             continue;
         }
         // s_tab[i] = input offset | (pt * cams + cam) << 20 of output element i, shared by the
@@ -209,8 +186,7 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_kernel(DafPrepArgs a)
             entry(i, x, ok);
             out[i] = (ok && !all_miss) ? expf(x - m) / s : 0.f;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_handover();
     }
 }
 
@@ -256,22 +232,18 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_bwd_kernel(DafPrepArgs a)
                     reinterpret_cast<float4 *>(mine)[s_tab[4 * i] >> 2] =
                         make_float4(p.x * (r.x - dot.x), p.y * (r.y - dot.y), p.z * (r.z - dot.z), p.w * (r.w - dot.w));
                 }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                __builtin_amdgcn_wave_barrier();
+                wave_lds_handover();
                 for (int i = lane; i < E / 4; i += 64) reinterpret_cast<float4 *>(graw)[i] = reinterpret_cast<const float4 *>(mine)[i];
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                __builtin_amdgcn_wave_barrier();  // the copy is read before the next anchor overwrites it
+                wave_lds_handover();  // the copy is read before the next anchor overwrites it
             } else {
                 float dot = 0.f;
                 for (int i = lane; i < E; i += 64) dot += y[i] * dy[i];
                 dot = wave_xor_reduce_strided(dot, a.G, Sum());
                 if (STAGE) {
                     for (int i = lane; i < E; i += 64) mine[s_tab[i]] = y[i] * (dy[i] - dot);
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                    __builtin_amdgcn_wave_barrier();
+                    wave_lds_handover();
                     for (int i = lane; i < E / 4; i += 64) reinterpret_cast<float4 *>(graw)[i] = reinterpret_cast<const float4 *>(mine)[i];
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                    __builtin_amdgcn_wave_barrier();
+                    wave_lds_handover();
                 } else {
                     for (int i = lane; i < E; i += 64) graw[s_tab[i]] = y[i] * (dy[i] - dot);
                 }
@@ -279,7 +251,8 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_bwd_kernel(DafPrepArgs a)
         }
         // ---- projection backward: u = x / max(z, 1e-5) / w_img (the clamp has zero slope below 1e-5).
         // One lane per (point, camera) pair -- the pairs' loads are independent, the cameras of a point in
-        // one lane were a serial chain -- then one lane per point adds its cameras up in camera order.
+        // one lane were a serial chain -- then one lane per point adds its cameras up in camera order.  (Its text, not a helper
+        // shared with gf_daf_fused_bwd_kernel's step 5: as one, other products were contracted into the FMAs below -- other bits.)
         if (a.grad_key_points) {
             for (int q2 = lane; q2 < npair; q2 += 64) {
                 const int pt = q2 / a.cams, cam = q2 - pt * a.cams;
@@ -300,8 +273,7 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_bwd_kernel(DafPrepArgs a)
                 s_part[3 * q2 + 1] = cx * M[1] + cy * M[5] + cz * M[9];
                 s_part[3 * q2 + 2] = cx * M[2] + cy * M[6] + cz * M[10];
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handover();
             for (int pt = lane; pt < a.pts; pt += 64) {
                 float gx = 0.f, gy = 0.f, gz = 0.f;
                 for (int cam = 0; cam < a.cams; ++cam) {
@@ -311,8 +283,7 @@ __global__ __launch_bounds__(256) void gf_daf_prepare_bwd_kernel(DafPrepArgs a)
                 float *o = a.grad_key_points + (anchor * a.pts + pt) * 3;
                 o[0] = gx; o[1] = gy; o[2] = gz;
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();  // partials consumed before the next anchor's overwrite them
+            wave_lds_handover();  // partials consumed before the next anchor's overwrite them
         }
     }
 }

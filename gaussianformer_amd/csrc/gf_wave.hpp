@@ -16,6 +16,15 @@ __device__ __forceinline__ int mbcnt(unsigned long long mask)
                                           __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// This wave's LDS writes before the call are visible to its own lanes after it: a workgroup-scope fence (the writes are
+// complete, and the compiler moves no LDS access across it) and a wave barrier (a scheduling point for the wave's lanes, no
+// instruction).  Where one wave owns a piece of LDS it stands in for __syncthreads(); it does NOT order other waves.
+__device__ __forceinline__ void wave_lds_handover()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
 // ---- DPP running sums: all 64 lanes active (bound_ctrl gives an inactive or out-of-row source 0) ----------------------------
 // v + v of the lane that CTRL selects, in the rows of ROW_MASK
 template <int CTRL, int ROW_MASK = 0xf>

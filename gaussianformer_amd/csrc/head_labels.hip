@@ -49,8 +49,7 @@ __global__ __launch_bounds__(256) void gf_head_labels_kernel(LabelArgs a)
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_handover();
     if (lane >= rows) return;
     const float *row = mine + lane * kC;
     float best = 0.f;
