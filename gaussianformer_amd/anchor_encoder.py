@@ -1,8 +1,9 @@
 """The anchor encoder: drop-in for ``SparseGaussian3DEncoder`` (model/encoder/gaussian_encoder/anchor_encoder_module.py:7-53,
 its layers from ``linear_relu_ln``, utils.py:49-59).  Five input branches (xyz, scale, rotation, opacity, semantics), each
 ``Linear(k -> E), ReLU, LayerNorm, Linear(E -> E), ReLU, LayerNorm``, their sum, then ``output_fc`` with two more such stages:
-about 40 torch kernels, and ``gf_anchor_embed_forward`` (include/gf_hip.h) in one launch.  The native op is
-a forward only: training keeps the module's torch layers."""
+about 40 torch kernels, and ``gf_anchor_embed_forward`` (include/gf_hip.h) in one launch.  Training keeps
+the module's torch layers unless asked otherwise: ``anchor_embed_autograd`` and a module with ``native_training = True`` run the native training
+step (``gf_anchor_embed_forward_train`` / ``gf_anchor_embed_backward``)."""
 import ctypes
 
 import torch
@@ -43,30 +44,109 @@ def _needs_grad(tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
-def _launch(anchor, params):
-    """The library call on the 48-entry parameter list; the callers have settled autograd."""
+def _shape(anchor, params):
+    """``(a [n, Da] as the library reads it, leading shape, E, opa, S)`` of a call on the 48-entry parameter list."""
     _lib.require_gpu(anchor, *params)
     if params[0] is None or params[40] is None:
         raise ValueError("anchor_embed needs at least xyz_fc, scale_fc, rot_fc and output_fc")
-    E = params[0].shape[0]
-    opa = 1 if params[24] is not None else 0
-    S = 0 if params[32] is None else params[32].shape[1]
     a = _lib.as_arg(anchor)
-    lead, Da = a.shape[:-1], a.shape[-1]
-    a = a.reshape(-1, Da)
+    return a.reshape(-1, a.shape[-1]), a.shape[:-1], params[0].shape[0], 1 if params[24] is not None else 0, 0 if params[32] is None else params[32].shape[1]
+
+
+def _table(params):
+    """The library's host table of the 48 INPUT pointers, and the tensors it points into, in the list's order without the
+    ``None``s: a parameter as it is, or its converted copy (another dtype, not contiguous, misaligned), which the caller keeps
+    alive until the launch is queued (the caching allocator orders its reuse)."""
     table = (ctypes.c_void_p * _lib.GF_ANCHOR_EMBED_PARAMS)()
-    held = []   # converted copies stay alive until the launch is queued (the caching allocator orders their reuse)
+    held = []
     for i, p in enumerate(params):
         if p is None:
             continue
         if p.dtype != f32 or not p.is_contiguous() or p.data_ptr() % 16:   # (a module's own parameters: never)
             p = _lib.as_arg(p)
             p = p.clone() if p.data_ptr() % 16 else p
-            held.append(p)
+        held.append(p)
         table[i] = p.data_ptr()
+    return ctypes.cast(table, ctypes.c_void_p), held
+
+
+def _out_table(tensors):
+    """The host table of 48 OUTPUT pointers: the tensors themselves, never a copy -- what the library writes must land in
+    them -- so each has to be what the library writes already."""
+    table = (ctypes.c_void_p * _lib.GF_ANCHOR_EMBED_PARAMS)()
+    for i, t in enumerate(tensors):
+        if t is not None:
+            if t.dtype != f32 or not t.is_contiguous() or t.data_ptr() % 16:
+                raise ValueError("a gradient buffer must be a contiguous, 16-byte aligned float32 tensor")
+            table[i] = t.data_ptr()
+    return ctypes.cast(table, ctypes.c_void_p)
+
+
+def _launch(anchor, params):
+    """The library call on the 48-entry parameter list; the callers have settled autograd."""
+    a, lead, E, opa, S = _shape(anchor, params)
+    table, held = _table(params)
     out = torch.empty(a.shape[0], E, dtype=f32, device=a.device)
-    _lib.call("gf_anchor_embed_forward", a.device, a.shape[0], Da, E, opa, S, a, ctypes.cast(table, ctypes.c_void_p), out)
+    _lib.call("gf_anchor_embed_forward", a.device, a.shape[0], a.shape[1], E, opa, S, a, table, out)
     return out.view(*lead, E)
+
+
+def train_sizes(n, include_opa, S):
+    """``(saved_bytes, workspace_bytes)`` of the training step on ``n`` rows (``gf_anchor_embed_train_sizes``)."""
+    saved, work = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(_lib.load().gf_anchor_embed_train_sizes(n, int(bool(include_opa)), S, ctypes.addressof(saved), ctypes.addressof(work)),
+               "gf_anchor_embed_train_sizes")
+    return saved.value, work.value
+
+
+class AnchorEmbedFunction(torch.autograd.Function):
+    """``out = AnchorEmbedFunction.apply(anchor, *params)`` on the 48-entry parameter list (``None`` for an absent branch):
+    ``gf_anchor_embed_forward_train`` keeps every stage's post-ReLU row and LayerNorm statistics, ``gf_anchor_embed_backward``
+    returns the gradients of the anchor and of every parameter that requires one.  Once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, anchor, *params):
+        a, lead, E, opa, S = _shape(anchor, params)
+        table, held = _table(params)
+        n, Da = a.shape
+        saved_bytes, _ = train_sizes(n, opa, S)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=a.device)
+        out = torch.empty(n, E, dtype=f32, device=a.device)
+        _lib.call("gf_anchor_embed_forward_train", a.device, n, Da, E, opa, S, a, table, out, saved, saved_bytes)
+        ctx.save_for_backward(a, saved, *held)
+        ctx.shape = (lead, E, opa, S, anchor.dtype, [None if p is None else p.dtype for p in params])
+        return out.view(*lead, E)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        a, saved, *held = ctx.saved_tensors
+        lead, E, opa, S, anchor_dtype, dtypes = ctx.shape
+        n, Da = a.shape
+        params, grads, it = [], [], iter(held)
+        for d in dtypes:
+            params.append(None if d is None else next(it))
+            grads.append(None if d is None else torch.empty_like(params[-1]))
+        table, _ = _table(params)
+        gtable = _out_table(grads)
+        _, work_bytes = train_sizes(n, opa, S)
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=a.device)
+        grad_anchor = torch.empty(n, Da, dtype=f32, device=a.device)
+        go = _lib.as_arg(grad_out).reshape(n, E)
+        _lib.call("gf_anchor_embed_backward", a.device, n, Da, E, opa, S, a, table, saved, go, grad_anchor, gtable, work, work_bytes)
+        need = ctx.needs_input_grad
+        return (grad_anchor.view(*lead, Da).to(anchor_dtype) if need[0] else None,
+                *[g.to(d) if g is not None and need[1 + i] else None for i, (g, d) in enumerate(zip(grads, dtypes))])
+
+
+def anchor_embed_autograd(anchor, module_or_params):
+    """``anchor_embed`` with a native backward: ``out [..., 128]`` carries the graph of ``AnchorEmbedFunction``, so the anchor and
+    every parameter that requires grad receive their gradients (the others ``None``).  Under ``torch.no_grad()``, or when
+    nothing requires grad, it is the plain forward."""
+    params = _param_list(module_or_params)
+    if not _needs_grad([anchor, *params]):
+        return _launch(anchor, params)
+    return AnchorEmbedFunction.apply(anchor, *params)
 
 
 def anchor_embed(anchor, module_or_params):
@@ -78,7 +158,8 @@ def anchor_embed(anchor, module_or_params):
     if _needs_grad([anchor, *params]):
         raise RuntimeError(
             "anchor_embed is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters "
-            "that do not require grad (the SparseGaussian3DEncoder module routes training to its torch layers)")
+            "that do not require grad (the SparseGaussian3DEncoder module routes training to its torch layers), or call "
+            "anchor_embed_autograd, which has one")
     return _launch(anchor, params)
 
 
@@ -86,7 +167,12 @@ class SparseGaussian3DEncoder(nn.Module):
     """Same constructor keys and defaults, attributes, submodule names, ``state_dict`` keys and ``forward(box_3d)`` as the
     reference class (anchor_encoder_module.py:7-53), so its checkpoints load with ``strict=True``.  The native op runs when the
     input is an fp32 GPU tensor, ``embed_dims == 128``, the semantic width is at most 32 and nothing needs autograd; everything
-    else (training, CPU tensors, other widths or dtypes) runs the module's own torch layers, the reference's composition."""
+    else (training, CPU tensors, other widths or dtypes) runs the module's own torch layers, the reference's composition.
+    ``native_training`` is an attribute, not a constructor key (the constructor stays the reference's), off by default and not
+    part of the ``state_dict``: set ``module.native_training = True`` and, under the same conditions, a call that needs autograd
+    runs ``AnchorEmbedFunction`` instead of the torch layers."""
+
+    native_training = False
 
     def __init__(self, embed_dims=256, include_opa=True, semantics=False, semantic_dim=None):
         super().__init__()
@@ -110,8 +196,11 @@ class SparseGaussian3DEncoder(nn.Module):
     def forward(self, box_3d):
         if box_3d.is_cuda and box_3d.dtype == f32 and self.embed_dims == E_NATIVE and self.semantic_dim <= MAX_S:
             params = _param_list(self)
-            if params[0].is_cuda and params[0].dtype == f32 and not _needs_grad([box_3d, *params]):
-                return _launch(box_3d, params)
+            if params[0].is_cuda and params[0].dtype == f32:
+                if not _needs_grad([box_3d, *params]):
+                    return _launch(box_3d, params)
+                if self.native_training:
+                    return AnchorEmbedFunction.apply(box_3d, *params)
         return self.forward_torch(box_3d)
 
     def forward_torch(self, box_3d):

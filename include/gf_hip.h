@@ -788,6 +788,40 @@ int gf_refine_backward(int n, int D, int Da, int version, int flags, int R, int 
 int gf_anchor_embed_forward(int n, int Da, int E, int include_opa, int S, const float *anchor, const void *const *params,
                             float *out, void *stream);
 
+/* The anchor encoder's training step: a forward that also saves what the backward needs, and the full
+ * backward.  E, S, Da, the alignment limits and the 48-pointer params table are gf_anchor_embed_forward's.
+ *
+ * gf_anchor_embed_train_sizes: host code; the bytes of the two caller-allocated regions for n rows of a module with
+ * include_opa and S (both 0 for n == 0).  GF_EINVAL: n < 0, S outside 0 .. 32, a null result pointer.
+ *
+ * gf_anchor_embed_forward_train: the forward, with out BITWISE gf_anchor_embed_forward's, plus `saved` (16-byte aligned, at
+ * least the queried saved_bytes; opaque: every stage's post-ReLU row and LayerNorm (mean, rstd), and the branches' sum).
+ *
+ * gf_anchor_embed_backward: from grad_out f32 [n, 128] (16-byte aligned), the anchor, the parameters and `saved` of the
+ * forward_train call on the same inputs,
+ *   grad_anchor  f32 [n, Da], written in full: columns no branch reads (>= 10 + opa + S) are exactly 0.0
+ *   grad_params  HOST table of 48 device pointers laid out like params, each tensor of its parameter's shape: every present
+ *                parameter's gradient is STORED, not accumulated -- the caller zeroes nothing.  The eight of an absent
+ *                branch are ignored.
+ *   workspace    16-byte aligned, at least the queried workspace_bytes; scratch, nothing survives the call
+ * Three kernels and a fixed-order sum: no atomics, bitwise reproducible; a row of grad_anchor does not depend on n or on the
+ * row's position; no host synchronisation, no allocation: graph-capturable.  A read column that is NaN makes that row of
+ * grad_anchor and the parameter gradients NaN (as torch's are); unread columns are never loaded.
+ * GF_EINVAL as the forward, and for a null gradient of a present stage or a misaligned region; GF_EWORKSPACE for a region
+ * shorter than the op's carve.  n == 0 returns GF_OK with the parameter gradients zero-filled.
+ * GF_ANCHOR_EMBED_WGRAD_ROWS: the rows one workgroup of the weight-gradient kernel sums (the workspace holds one partial per
+ * block of that many rows).  GF_ANCHOR_EMBED_CHUNK_ROWS: the backward walks the rows in chunks of this many, one after the
+ * other on the stream, and the workspace holds the per-row intermediates of one chunk only.  Both are exported for tests that
+ * place n at their edges. */
+#define GF_ANCHOR_EMBED_WGRAD_ROWS 512
+#define GF_ANCHOR_EMBED_CHUNK_ROWS 65536
+int gf_anchor_embed_train_sizes(int n, int include_opa, int S, size_t *saved_bytes, size_t *workspace_bytes);
+int gf_anchor_embed_forward_train(int n, int Da, int E, int include_opa, int S, const float *anchor, const void *const *params,
+                                  float *out, void *saved, size_t saved_bytes, void *stream);
+int gf_anchor_embed_backward(int n, int Da, int E, int include_opa, int S, const float *anchor, const void *const *params,
+                             const void *saved, const float *grad_out, float *grad_anchor, void *const *grad_params,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */
 int gf_profile_stride(int every);
