@@ -28,16 +28,14 @@
 //
 // Rows past n in the last tile compute on row n - 1 and are not stored.  The result leaves through LDS (the weight buffers,
 // idle by then) so that a store instruction writes runs of 256 bytes.
-#include "gf_common.hpp"
+#include "gf_rows.hpp"
 
 namespace gf {
 
 constexpr int kAeE = 128;        // features (embed_dims); every shipped config
 constexpr int kAeMaxS = 32;      // semantic columns (gf_refine_*'s limit)
-constexpr int kAeTile = 128;     // anchors per workgroup, 32 per wave
-constexpr int kAePitch4 = 9;     // float4 per staged weight row: 32 floats + 4 of padding
-constexpr int kAeOutPitch = 68;  // floats per row of the output staging tile: 64 features + 4 of padding
-constexpr float kAeLnEps = 1e-5f;
+constexpr int kAeTile = kRowTile;   // anchors per workgroup, 32 per wave (gf_rows.hpp: the layout and the helpers on it)
+constexpr int kAePitch4 = kRowPitch4;
 constexpr int kAeVecs = 36;      // (5 thin + 7 square stages) x (bias, LayerNorm weight, LayerNorm bias), 128 floats each
 
 struct AeThin { const float *w; int col0, k; };   // a branch's Linear(k -> 128): reads anchor columns col0 .. col0 + k
@@ -58,8 +56,6 @@ struct AnchorEmbedSaveArgs : AnchorEmbedArgs {
 };
 template <bool SAVE> struct AeFwdArgs { using type = AnchorEmbedArgs; };
 template <> struct AeFwdArgs<true> { using type = AnchorEmbedSaveArgs; };
-
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 
 // v <- LayerNorm(relu(v + bias)) over the 128 features of the lane's anchor (biased variance, two passes); p: the stage's
 // three vectors in LDS (32 float4 each: bias, LayerNorm weight, LayerNorm bias).  SAVE: the lane also stores its 64 post-ReLU
@@ -90,47 +86,7 @@ __device__ __forceinline__ void relu_ln(f32x16 (&v)[4], const float4 *p, int h, 
         }
         part[b] = s;
     }
-    const float mean = wave_xor_reduce_strided((part[0] + part[1]) + (part[2] + part[3]), 32, Sum()) * (1.f / kAeE);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        float s = 0.f, d0 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float d = v[b][r] - mean;
-            v[b][r] = d;
-            // SAVE spells out the fusions the plain forward's build makes -- d0 d0 + (d1 d1) rounds the SECOND product, every
-            // later term is one FMA -- because its stores change what gets vectorised, and a packed multiply followed by a
-            // scalar add is not contracted.  The plain forward keeps the expressions its instruction stream was built from:
-            // spelled out there too, the same bits come 5 % slower (another register allocation: 470.7 against 448.0 us at
-            // A = 144 000, 96.2 against 93.4 at 6 400).  tests/test_anchor_encoder_train_gpu.py holds the two together
-            if constexpr (SAVE) {
-                if (r == 0) d0 = d;
-                else if (r == 1) s = __builtin_fmaf(d0, d0, d * d);
-                else s = __builtin_fmaf(d, d, s);
-            } else {
-                s += d * d;
-            }
-        }
-        part[b] = s;
-    }
-    const float var = wave_xor_reduce_strided((part[0] + part[1]) + (part[2] + part[3]), 32, Sum()) * (1.f / kAeE);
-    const float rstd = 1.f / sqrtf(var + kAeLnEps);
-    if constexpr (SAVE) {
-        if (rrow && h == 0) *reinterpret_cast<float2 *>(st2) = make_float2(mean, rstd);
-    }
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float4 gg = p[32 + 8 * b + 2 * m + h], ee = p[64 + 8 * b + 2 * m + h];
-            const float gv[4] = {gg.x, gg.y, gg.z, gg.w}, ev[4] = {ee.x, ee.y, ee.z, ee.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if constexpr (SAVE) v[b][4 * m + i] = __builtin_fmaf(v[b][4 * m + i] * rstd, gv[i], ev[i]);
-                else v[b][4 * m + i] = v[b][4 * m + i] * rstd * gv[i] + ev[i];
-            }
-        }
-    }
+    ln_rows<SAVE, 4>(v, (part[0] + part[1]) + (part[2] + part[3]), p + 32, p + 64, h, rrow ? st2 : nullptr);
 }
 
 // acc <- W1 x^T for a thin first layer: step s takes k = 2 s (lanes 0-31) and 2 s + 1 (lanes 32-63)
@@ -181,17 +137,9 @@ __global__ __launch_bounds__(256) void gf_anchor_embed_kernel(typename AeFwdArgs
         else return nullptr;
     };
 
-    // staging of a weight chunk: thread -> rows ff + 32 i, float4 fq of the chunk's 8
-    const int ff = t >> 3, fq = t & 7;
     float4 pre[4];
-    auto fetch = [&](const float *w, int c) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pre[i] = ld4(w + (size_t)(ff + 32 * i) * kAeE + 32 * c + 4 * fq);
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s_w[buf][(ff + 32 * i) * kAePitch4 + fq] = pre[i];
-    };
+    auto fetch = [&](const float *w, int c) { chunk_fetch(pre, w, kAeE, 32 * c, t); };
+    auto stash = [&](int buf) { chunk_stash(s_w[buf], pre, t); };
 
     f32x16 x[4], acc[4], sum[4];
     fetch(a.sq[0], 0);
@@ -227,17 +175,7 @@ __global__ __launch_bounds__(256) void gf_anchor_embed_kernel(typename AeFwdArgs
         for (int c = 0; c < 4; ++c) {
             const bool more = c < 3 || q + 1 < nsq;
             if (more) fetch(c < 3 ? a.sq[q] : a.sq[q + 1], (c + 1) & 3);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-#pragma unroll
-                for (int fb = 0; fb < 4; ++fb) {
-                    const float4 w4 = s_w[c & 1][(32 * fb + j) * kAePitch4 + 2 * m + h];
-                    acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.x, x[c][4 * m + 0], acc[fb], 0, 0, 0);
-                    acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.y, x[c][4 * m + 1], acc[fb], 0, 0, 0);
-                    acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.z, x[c][4 * m + 2], acc[fb], 0, 0, 0);
-                    acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.w, x[c][4 * m + 3], acc[fb], 0, 0, 0);
-                }
-            }
+            chunk_mfma(acc, x[c], s_w[c & 1], j, h);
             if (more) stash((c + 1) & 1);
             __syncthreads();
         }
@@ -271,30 +209,9 @@ __global__ __launch_bounds__(256) void gf_anchor_embed_kernel(typename AeFwdArgs
         }
     }
 
-    // x = the result.  Through the (idle) weight buffers, 64 features at a time: the lane writes its anchor's float4s, the wave
-    // reads four rows per instruction back and stores them
-    float *so = reinterpret_cast<float *>(&s_w[0][0]) + wv * (32 * kAeOutPitch);
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-#pragma unroll
-        for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const f32x16 &v = x[2 * half + bb];
-                *reinterpret_cast<float4 *>(so + j * kAeOutPitch + 32 * bb + 8 * m + 4 * h) =
-                    make_float4(v[4 * m], v[4 * m + 1], v[4 * m + 2], v[4 * m + 3]);
-            }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int r = 4 * i + (l >> 4), col = 4 * (l & 15);
-            const float4 v = *reinterpret_cast<const float4 *>(so + r * kAeOutPitch + col);
-            if (row0 + r < a.n) *reinterpret_cast<float4 *>(a.out + (size_t)(row0 + r) * kAeE + 64 * half + col) = v;
-        }
-        __syncthreads();
-    }
+    // x = the result, through the (idle) weight buffers
+    store_rows(reinterpret_cast<float *>(&s_w[0][0]) + wv * (32 * kRowOutPitch), x, a.out, row0, a.n, l, j, h);
 }
-static_assert(4 * 32 * kAeOutPitch <= 2 * kAeE * kAePitch4 * 4, "the output staging tiles fit the weight buffers");
 
 // ---- the backward (gf_anchor_embed_backward) ---------------------------------------------------------------
 // Three kernels, no atomics.  (1) The data backward: the forward's tile and register layout, the stages in reverse.  A stage's

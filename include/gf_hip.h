@@ -822,6 +822,32 @@ int gf_anchor_embed_backward(int n, int Da, int E, int include_opa, int S, const
                              const void *saved, const float *grad_out, float *grad_anchor, void *const *grad_params,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* The encoder's feed-forward block in one launch: AsymmetricFFN.forward
+ * (model/encoder/gaussian_encoder/ffn_module.py:66-75) with the "add" and "norm" that follow it in the encoder's
+ * operation_order.  For every row x [Cin] of x f32 [n, Cin]:
+ *   u   = LN_pre(x)                          if pre_norm is given, else x
+ *   y   = W2 relu(W1 u + b1) + b2            W1 = layers.0.0.weight [F, Cin], W2 = layers.1.weight [E, F]
+ *   y  += Wid u + bid                        if identity_fc is given (Wid [E, Cin])
+ *   y  += residual                           if residual f32 [n, E] is given (added last: zeros change no bit)
+ *   out = LN_post(y)                         if the post norm is given, else y;   out f32 [n, E]
+ * Both LayerNorms: eps = 1e-5, biased variance, mean first, then the squared deviations.  ReLU keeps a NaN.
+ *   params     HOST table of GF_FFN_PARAMS = 10 device pointers, the modules' own tensors in torch's layout, contiguous f32:
+ *                0, 1  pre_norm.weight, .bias [Cin]          2, 3  layers.0.0.weight [F, Cin], .bias [F]
+ *                4, 5  layers.1.weight [E, F], .bias [E]     6, 7  identity_fc.weight [E, Cin], .bias [E]
+ *                8, 9  the post norm's weight, bias [E]
+ *              A NULL pair = that part is absent; layers.* must be present.
+ * Every pointer is 16-byte aligned; out aliases no input.  Nothing is read beyond x[n Cin] or residual[n E].
+ * GF_EINVAL before any HIP call, the message naming the offending value: E != 128, F != 512, Cin not 128 or 256, n < 0, a
+ * missing layers.* pointer, a half-present pair, a misaligned pointer.  n == 0 returns GF_OK without a launch.  Exact fp32
+ * products (v_mfma_f32_32x32x2_f32), the F-wide hidden row never reaches memory; no workspace, no atomics, bitwise
+ * reproducible; a row's result does not depend on n or on the row's position (up to 32 rows per compute unit a workgroup
+ * owns 32 rows, beyond that 128: two kernels, the same bits); no host synchronisation, no allocation: graph-capturable. */
+#define GF_FFN_PARAMS 10
+#define GF_FFN_EMBED_DIMS 128
+#define GF_FFN_HIDDEN 512
+int gf_ffn_forward(int n, int Cin, int F, int E, const float *x, const void *const *params, const float *residual, float *out,
+                   void *stream);
+
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */
 int gf_profile_stride(int every);
