@@ -372,7 +372,8 @@ __global__ __launch_bounds__(64, 2) void gf_splat_bwd_mfma_kernel(BwdMArgs a)
             int pub_done = 0;          // LONG: entries of the published list taken so far
             bool pub_fetch = false;    // LONG: the next piece has to be fetched (the first one came with the unit's requests)
             if (pub_unit) {
-                list_len = min((int)published_len, kMList);
+                // (short rows: the forward's wave kernel may carry its call tag in the upper half of the word)
+                list_len = min((int)(LONG ? published_len : (published_len & 0xFFFFu)), kMList);
                 c = nchunk;
                 have_boxes = true;
             } else if (!LONG) {

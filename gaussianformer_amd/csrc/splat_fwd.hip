@@ -69,6 +69,9 @@ struct PrepArgs {
     uint32_t *range_flags;   // null, or [nwords + 4]: per wave of 64 Gaussians, bit 2 = a Gaussian's theta may leave the f16
                              // range, bit 3 = |opacity * semantics| may (matrix-core render kernel: both change per frame, so
                              // they are checked in the records pass on EVERY call, GF_PTS_ASSUME_DENSE included)
+    uint32_t *pub_len;       // null, or [nsx * nsy]: the length words of the lists the short-row wave kernel's first units publish for the
+                             // supertile's other units -- cleared here, so that no word of an earlier call (or of whatever the memory held
+                             // before it became this workspace) can carry this call's tag
 };
 
 constexpr int kPrepSuperChunk = 4096;  // bitmask words in LDS per pass of the prep kernel (32 KB)
@@ -254,6 +257,8 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
     // workgroup 0 stores A = B and clears the OTHER word, V[(B + 1) & 1] -- the one the next call's violators will use.  All the
     // state lives on the device, so a replayed HIP graph behaves like an eager call.
     if (a.verdict_words && blockIdx.x == 0 && threadIdx.x == 0) a.verdict_words[kVerdictB] = a.verdict_words[kVerdictA] + 1u;
+    if (a.pub_len && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < a.nsx * a.nsy; i += 64 * WAVES) a.pub_len[i] = 0u;
     const int word = blockIdx.x * WAVES + wave;  // bitmask word of this wave
     const int g = word * 64 + lane;
     const bool valid = g < a.P;
@@ -596,6 +601,7 @@ struct RenderArgs {
     uint32_t *unit_first;                       // ... [P] first row of every Gaussian, written by the wave kernel
     uint32_t unit_cap;                          // ... rows available
     uint32_t *pub_lists, *pub_len;              // ... [nsuper][3][kBwdList] / [nsuper]: the candidate lists, published for the backward
+                                                // (and, short rows with a verdict block, for the supertile's later units of the same launch)
     uint32_t *verdict_words;   // null, or the workspace's verdict block [A, B, V0, V1] (gf_splat_prep_kernel, "one verdict word"): the wave
                                // kernel reads it with ONE load instead of every prep wave's verdict word
     const unsigned char *summary;   // long rows (gf_splat_render_mfma_wave_kernel<..., LONG = true>): the records pass's row summaries
@@ -603,6 +609,7 @@ struct RenderArgs {
     uint32_t m_ps, m_nsy;      // wave kernel: ceil(2^32 / units per supertile), ceil(2^32 / nsy) -- launch constants, computed on the host
                                // (on the device the two 64-bit divisions were 220 scalar instructions at the start of every wave:
                                // round-6 census, profiles/census_wave_r06.txt)
+    uint32_t m_nx;             // short-row wave kernel: ceil(2^32 / (units per supertile - 1)) -- the units behind the supertiles' units 0
 };
 
 // Words 3 and 4 of the state block: the workspace's generation (gf_splat_prep_kernel bumped it) and whether the records carry
@@ -1927,19 +1934,39 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     const int lane = threadIdx.x;
     const int xcd = (int)(blockIdx.x & 7u);
     const int per_super = 4 * ((a.D + 7) >> 3);          // units of a supertile: 2 x 2 column quarters x z bricks
-    const int per_xcd = ((a.nsx * a.nsy + 7) >> 3) * per_super;
+    const int nsuper_xcd = (a.nsx * a.nsy + 7) >> 3;     // supertiles of an XCD (supertile 8 q + x on XCD x)
+    const int per_xcd = nsuper_xcd * per_super;
 
     // unit index -> (supertile, quarter, z brick) -> supertile row and column: divisions by launch constants, as multiplications
     // by rounded-up reciprocals (exact for the < 2^20 indices of a grid)
-    const uint32_t m_ps = a.m_ps, m_nsy = a.m_nsy;
+    const uint32_t m_ps = a.m_ps, m_nsy = a.m_nsy, m_nx = a.m_nx;
+    // Short rows: the first nsuper_xcd indices of an XCD are unit 0 of every supertile -- static first units of waves that start
+    // with the launch: they publish the supertile's list (below) about one list time into the launch --, then come the supertiles'
+    // other units, supertile by supertile as before.  (All units r-major, index = r * nsuper_xcd + q, was measured: 1.5 us per step
+    // slower without any sharing -- every supertile's row, boxes and records are wanted at once, at the start, and a supertile's
+    // units no longer run side by side on its lines.)  Long rows: q-major, as before.
+    auto unit_qr = [&](int u, int &q, int &r) {
+        if (LONG) {
+            q = (int)__umulhi((uint32_t)u, m_ps);
+            r = u - q * per_super;
+        } else if (u < nsuper_xcd) {
+            q = u;
+            r = 0;
+        } else {
+            const int v = u - nsuper_xcd;
+            q = (int)__umulhi((uint32_t)v, m_nx);
+            r = 1 + v - q * (per_super - 1);
+        }
+    };
     int local = (int)(blockIdx.x >> 3);
     bool row_there = false;  // the bitmask row of unit `local` has already been requested into s_row
     // The first unit's bitmask row is requested before anything else: its round trip then runs under the verdict loads and the
     // set-up below instead of behind them (a failed verdict wastes one LDS-DMA).
     {
-        const int q0 = (int)__umulhi((uint32_t)local, m_ps);
+        int q0, r0;
+        unit_qr(local, q0, r0);
         if (local < per_xcd && 8 * q0 + xcd < a.nsx * a.nsy) {
-            const int s0 = 8 * q0 + xcd, r0 = local - q0 * per_super;
+            const int s0 = 8 * q0 + xcd;
             const int srow0 = a.nsy == 1 ? s0 : (int)__umulhi((uint32_t)s0, m_nsy), scol0 = s0 - srow0 * a.nsy;
             if (srow0 * kSuper + 4 * (r0 & 1) < a.H && scol0 * kSuper + 4 * ((r0 >> 1) & 1) < a.W) {
                 if (LONG) {
@@ -1981,11 +2008,18 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     // words: three clamped 16-byte reads per lane cover the <= 618 + 4 words of the rows this kernel takes -- no loop: as a loop
     // every iteration was a round trip of its own at the start of every wave, +4.6 us per launch.)
     int verdict = 0;
+    // Short rows, one verdict word: unit 0 of every supertile publishes the supertile's candidate list (pub_lists / pub_len, the
+    // lists GF_PREPARE_BACKWARD leaves for the backward), and a later unit of the supertile that finds it there takes it instead of
+    // scanning the row and fetching the boxes.  Nobody waits: a unit that does not find the list builds its own.  pub_tag marks the
+    // length words of THIS call: the verdict block's call counter B (it changes on the device with every call, replayed graphs
+    // included) in the upper half, bit 31 set; the records pass cleared the words.  0: the feature is off.
+    uint32_t pub_tag = 0u;
     if (a.verdict_words) {
         // one verdict word (gf_splat_prep_kernel): [A, B, V0, V1], one 16-byte load, the same address in every lane
         const uint4 vw = *reinterpret_cast<const uint4 *>(a.verdict_words);
         const uint32_t vv = (vw.y & 1u) ? vw.w : vw.z;   // V[B & 1]
         verdict = __builtin_amdgcn_readfirstlane((int)(vv & (a.verify_dense ? kVerdictAll : kVerdictRange)));
+        if (!LONG) pub_tag = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((vw.y & 0x7FFFu) | 0x8000u) << 16));
         if (blockIdx.x == 0 && lane == 0) {   // A = B; the word the NEXT call's violators will use starts from zero
             a.verdict_words[kVerdictA] = vw.y;
             a.verdict_words[verdict_slot_after(vw.y)] = 0u;
@@ -2082,9 +2116,13 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     // by itself -- so rows that do not fit s_row stay with the tile kernel.)
     const int nchunk = (a.nwords + 63) >> 6;
     int nst_prev = 0;        // ... and this many store instructions were issued after that request
+    bool pl_there = false;   // the supertile's pub_len word was requested with the prefetched row, into q_id[0 .. 63] (the hit queue is
+                             // empty between units) -- not for a wave's first unit, not for a unit 0.  (In LDS, not in a register: a
+                             // VGPR carried from unit to unit changed how the group step's MFMAs are scheduled, 11 -> 46 s_nop.)
     while (true) {  // units of this wave
         const int logical = local;
-        const int qs = (int)__umulhi((uint32_t)logical, m_ps);
+        int qs, r;
+        unit_qr(logical, qs, r);
         if (!(local < per_xcd && 8 * qs + xcd < a.nsx * a.nsy)) break;
         bool next_row = false;
         int nst = -1;
@@ -2093,7 +2131,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
         // divergent block that issued it).  The answer is waited for together with the bitmask row.
         uint32_t claimed = 0u;
         bool have_next = false;
-        const int s = 8 * qs + xcd, r = logical - qs * per_super;
+        const int s = 8 * qs + xcd;
         const int srow = a.nsy == 1 ? s : (int)__umulhi((uint32_t)s, m_nsy), scol = s - srow * a.nsy;   // (2^32 / 1 does not fit)
         const int Xw = srow * kSuper + 4 * (r & 1), Y0 = scol * kSuper + 4 * ((r >> 1) & 1), Zw = 8 * (r >> 2);
         if (Xw < a.H && Y0 < a.W) {
@@ -2127,6 +2165,38 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
             tl[1] = wall_clock64();
 #endif
             int c = 0, sg = 0;
+            // ---- the supertile's list as its unit 0 published it in THIS call (tag): ids, box lo, box hi, one 16-byte LDS-DMA each
+            // (kBwdList entries = 64 lanes x 4: what lies past the length is not read by the filter) -- one round trip in place
+            // of the row scan and the box round trip.
+            // ONE L2 for unit 0 and its readers is what makes this correct: unit 0 uses plain stores, vmcnt(0), a plain store of
+            // the word, and writes nothing back from its L2; the word is read past the L1 (sc1), the list by ordinary LDS-DMA.  All
+            // units of a supertile run on XCD s % 8 because workgroup b runs on XCD b & 7 -- the assumption the per-XCD unit
+            // counters make as well, but with another price here: counters in the wrong L2 claim a unit twice or not at all, which
+            // shows; a reader in another L2 can see the tagged word (once that line has been written back) next to list lines
+            // that have not, and renders a WRONG LIST SILENTLY.  A dispatch or partition mode where blockIdx.x & 7 is not the XCD
+            // has to switch this off (pub_tag = 0) or publish through memory (write-back before the word, sc1 on the list reads).
+            bool have_boxes = false;   // the list in LDS came with its boxes (taken from unit 0, or unit 0's own: fetched to be published)
+            if (!LONG && pl_there) {
+                const uint32_t plv = (uint32_t)__builtin_amdgcn_readfirstlane((int)q_id[0]);
+                if ((plv & 0xFFFF0000u) == pub_tag && (plv & 0xFFFFu) <= (uint32_t)kBwdList) {
+                    int wl = lane;   // (the lane's offset is formed here: hoisted out of the unit loop it is spilled to scratch)
+                    asm volatile("" : "+v"(wl));
+                    const uint32_t *src = a.pub_lists + (size_t)s * (3 * kBwdList) + 4 * wl;
+                    lds_dma16((gptr)src, (lptr)s_lg);
+                    lds_dma16((gptr)(src + kBwdList), (lptr)s_blo);
+                    lds_dma16((gptr)(src + 2 * kBwdList), (lptr)s_bhi);
+                    // (counted for the tests and the timeline -- word 32 of the XCD's counter block: the other 128-byte line, so that the
+                    // count does not queue with the claims on the line of word 0)
+                    if (lane == 0) asm volatile("global_atomic_add %0, %1, off" ::"v"(ctr + 32), "v"(1u) : "memory");
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    list_len = (int)(plv & 0xFFFFu);
+                    c = nchunk;
+                    have_boxes = true;
+#if GF_TIMELINE
+                    tl[7] += 1000;   // (the groups are counted below 1000)
+#endif
+                }
+            }
             int long_lo = 0;       // LONG: rank (among the row's non-zero words) of the first word not yet listed
             bool long_first = true;  // LONG: the summary in s_sum is the prefetched one
             // ---- fill, fast path (the whole row at once).  Extracting ids bit by bit costs one loop iteration per set bit of the
@@ -2134,7 +2204,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
             // have none (0.6 % of the bits are set): 35 iterations of a dependent 64-bit chain per row, 2.3 us.  So the NONZERO
             // words are first compacted (one scan of per-lane counts, no loop) into a dense array -- it borrows the record slot, idle
             // until the first group -- and the bits are extracted from that: three rounds of two or three iterations.
-            if (!LONG) {
+            if (!LONG && !have_boxes) {
                 constexpr int kWDense = kWList;
                 uint32_t *s_dw = s_u;                                                               // [kWDense] word index
                 unsigned long long *s_db = reinterpret_cast<unsigned long long *>(s_u + kWDense);  // [kWDense] its bits
@@ -2234,6 +2304,46 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         list_len = tot;
                         c = nchunk;
                     }
+                }
+            }
+            // ---- short rows: unit 0 of a supertile leaves the list (ids and packed boxes, as it stands in LDS) in pub_lists -- for the
+            // matrix-core backward (GF_PREPARE_BACKWARD: a later kernel) and, with a tag, for the supertile's other units of THIS
+            // launch.  Those read the length word while the launch runs, so it is stored (tag | length) only after the list's stores
+            // have completed: a wait of unit 0's own, one store round trip in one unit of eight, all of them in the first round.
+            // Two conditions, neither implied by the other's code path: the list came out of the row in one piece (c >= nchunk: the
+            // fast path took it -- what the fast path refuses has more than kWList = 512 entries), AND it fits the list area
+            // (list_len <= kBwdList = 256: the fast path also delivers lists of 257 .. 512 entries, which are not published
+            // either).  Otherwise the length word stays as the records pass cleared it and
+            // GF_PREPARE_BACKWARD raises its flag: the backward scans the rows itself.
+            // (Here, not behind the box fetch of the refill loop below, where GF_PREPARE_BACKWARD had it: whatever that loop uses
+            // lives through the groups -- the supertile, the tag and two pointers there cost the group step 35 more s_nop and the
+            // step 2.2 us.)
+            const bool for_backward = PREP && a.rows_valid;
+            if (!LONG && r == 0 && (for_backward || pub_tag != 0u)) {
+                if (c >= nchunk && list_len <= kBwdList) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    int wl = lane;   // (what depends on the lane is formed in here: hoisted out of the unit loop it lives through the groups)
+                    asm volatile("" : "+v"(wl));
+                    for (int b0 = 0; b0 < list_len; b0 += 64) {
+                        const uint32_t id = s_lg[min(b0 + wl, list_len - 1)];
+                        lds_dma4((gptr)(&a.boxes[id].x), (lptr)(s_blo + b0));
+                        lds_dma4((gptr)(&a.boxes[id].y), (lptr)(s_bhi + b0));
+                    }
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    have_boxes = true;
+                    uint32_t *dst = a.pub_lists + (size_t)s * (3 * kBwdList);
+                    for (int i = wl; i < list_len; i += 64) {
+                        dst[i] = s_lg[i]; dst[kBwdList + i] = s_blo[i]; dst[2 * kBwdList + i] = s_bhi[i];
+                    }
+                    uint32_t word = (uint32_t)list_len;
+                    if (pub_tag != 0u) {
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        word |= pub_tag;
+                    }
+                    if (wl == 0) a.pub_len[s] = word;
+                } else if (for_backward && lane == 0) {
+                    atomicOr(const_cast<uint32_t *>(flag_word_via_verify(a.verify_flags, kListsBad)), 1u);
                 }
             }
             while (true) {  // fill the list from the row, consume it, until the row is exhausted
@@ -2391,28 +2501,27 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                 if (!tl[2]) tl[2] = wall_clock64();
 #endif
                 // ---- the packed boxes of the listed Gaussians, by LDS-DMA (two 4-byte pieces per entry, gathered by id)
-                for (int b0 = 0; b0 < list_len; b0 += 64) {
+                for (int b0 = 0; b0 < list_len && !have_boxes; b0 += 64) {
                     const uint32_t id = s_lg[min(b0 + lane, list_len - 1)];
                     lds_dma4((gptr)(&a.boxes[id].x), (lptr)(s_blo + b0));
                     lds_dma4((gptr)(&a.boxes[id].y), (lptr)(s_bhi + b0));
                 }
+                have_boxes = false;   // (not carried round the refill loop, through the groups)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                // GF_PREPARE_BACKWARD: quarter 0 / brick 0 of every supertile leaves the supertile's candidate list (ids and packed
-                // boxes, as it stands in LDS) for the matrix-core backward, whose units then skip the row scan and the box round
-                // trip -- a later kernel, so nothing has to be synchronised.  A list that did not come out of the row in one piece,
-                // or is longer than the backward's list area, raises a flag instead and the backward scans the rows itself.
-                if (PREP && a.rows_valid && r == 0 && !published) {
+                // GF_PREPARE_BACKWARD, long rows: quarter 0 / brick 0 of every supertile leaves the supertile's candidate list (ids and
+                // packed boxes, as it stands in LDS) for the matrix-core backward, whose units then skip the row scan and the box
+                // round trip -- a later kernel, so nothing has to be synchronised.  A list that did not come out of the row in one
+                // piece, or is longer than the list area, is marked instead and the backward scans the row itself.  (Short rows: above.)
+                if (LONG && PREP && a.rows_valid && r == 0 && !published) {
                     published = true;
-                    constexpr int kPub = LONG ? kBwdPubLong : kBwdList;   // (long rows: the whole one-pass list; the backward takes it in pieces)
-                    if (last && list_len <= kPub) {
-                        uint32_t *dst = a.pub_lists + (size_t)s * (3 * kPub);
+                    if (last && list_len <= kBwdPubLong) {   // (the whole one-pass list; the backward takes it in pieces)
+                        uint32_t *dst = a.pub_lists + (size_t)s * (3 * kBwdPubLong);
                         for (int i = lane; i < list_len; i += 64) {
-                            dst[i] = s_lg[i]; dst[kPub + i] = s_blo[i]; dst[2 * kPub + i] = s_bhi[i];
+                            dst[i] = s_lg[i]; dst[kBwdPubLong + i] = s_blo[i]; dst[2 * kBwdPubLong + i] = s_bhi[i];
                         }
                         if (lane == 0) a.pub_len[s] = (uint32_t)list_len;
                     } else if (lane == 0) {
-                        if (LONG) a.pub_len[s] = 0xFFFFFFFFu;   // (this supertile only: its units of the backward read the row themselves)
-                        else atomicOr(const_cast<uint32_t *>(flag_word_via_verify(a.verify_flags, kListsBad)), 1u);
+                        a.pub_len[s] = 0xFFFFFFFFu;   // (this supertile only: its units of the backward read the row themselves)
                     }
                 }
 #if GF_TIMELINE
@@ -2551,11 +2660,13 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                 asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(claimed) : "v"(ctr), "v"(1u) : "memory");
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(claimed)::"memory");
             have_next = true;
+            pl_there = false;
             {
                 const int nl = __builtin_amdgcn_readfirstlane((int)claimed);
-                const int q2 = (int)__umulhi((uint32_t)nl, m_ps);
+                int q2, r2;
+                unit_qr(nl, q2, r2);
                 if (nl < per_xcd && 8 * q2 + xcd < a.nsx * a.nsy) {
-                    const int s2 = 8 * q2 + xcd, r2 = nl - q2 * per_super;
+                    const int s2 = 8 * q2 + xcd;
                     const int srow2 = a.nsy == 1 ? s2 : (int)__umulhi((uint32_t)s2, m_nsy), scol2 = s2 - srow2 * a.nsy;
                     if (srow2 * kSuper + 4 * (r2 & 1) < a.H && scol2 * kSuper + 4 * ((r2 >> 1) & 1) < a.W) {
                         if (LONG) {
@@ -2565,6 +2676,15 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                             for (int i = 0; 128 * i < a.nrow; ++i)
                                 if (128 * i + 2 * lane < a.nrow)
                                     lds_dma16((gptr)(bm2 + 128 * i + 2 * lane), (lptr)(s_row + 128 * i));
+                            // ... and, for a unit that is not its supertile's unit 0, the word that says whether unit 0's list is
+                            // there, into the hit queue (empty between units): read in the XCD's L2 (sc1: a line this CU read
+                            // earlier would still say "not yet"), no ordering asked for -- the word is used after the wait the row
+                            // has anyway
+                            if (pub_tag != 0u && r2 != 0) {
+                                const uint32_t *lp = a.pub_len + s2;
+                                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off sc1" ::"v"(lp), "s"((uint32_t)(uintptr_t)(lptr)q_id) : "memory", "m0");
+                                pl_there = true;
+                            }
                         }
                         next_row = true;
                     }
@@ -2975,6 +3095,7 @@ static int splat_forward_impl(const char *fn, int variant, int flags, int C, con
     pa.tile_counters = rt.range_flags ? tile_counters : nullptr; pa.tile_counter_init = rt.tile_counter_init;
     pa.range_flags = rt.range_flags ? ws.range_flags : nullptr; pa.range_theta_here = rt.range_theta_here;
     pa.verdict_words = verdict_words; pa.summary = summary; pa.sum_pitch = ws.sum_pitch;
+    pa.pub_len = (rt.kernel == kRenderMfmaWave && verdict_words) ? ws.bwd_list_len : nullptr;   // (the shared lists need the verdict block's call counter)
     if (rt.prep_grid > 0) {
         launch_prep(pa, rt.prep_waves == 4, rt.prep_grid, stream);   // staged also for long rows: their summaries are written per four-wave workgroup
         GF_CHECK_LAUNCH_AS(fn);
@@ -3000,6 +3121,7 @@ static int splat_forward_impl(const char *fn, int variant, int flags, int C, con
     ra.verdict_words = verdict_words;
     ra.summary = summary; ra.sum_pitch = ws.sum_pitch;
     ra.m_ps = ceil_recip32(splat_units(1, in.D)); ra.m_nsy = ceil_recip32(ws.nsy);
+    ra.m_nx = ceil_recip32(splat_units(1, in.D) - 1);
     hipEvent_t ev0, ev1;
     const bool prof = rt.kernel != kRenderArbitrary && profile_slot(&ev0, &ev1);   // (profiled calls time the tile and unit kernels)
     if (prof) (void)hipEventRecord(ev0, stream);

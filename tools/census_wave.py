@@ -1,7 +1,8 @@
 """Static ISA census of the default forward kernel (gf_splat_render_mfma_wave_kernel<false, false, false>) by phase x trip count
 (VERDICT r5 #3c).  Finds the phase boundaries from the kernel's own comment markers, so it survives edits; trip counts per unit are
-the headline shape's (nuscenes_gs25600_solid: 2 048 waves for 5 000 units, 140 candidates and 2.16 groups per unit).
-    python tools/census_wave.py > profiles/census_wave_r06.txt          (no GPU needed)"""
+the headline shape's (nuscenes_gs25600_solid: 2 048 waves for 5 000 units, 140 candidates and 2.16 groups per unit; 59.5 % of the
+units take their supertile's list from its unit 0, one unit in eight is such a unit 0).
+    python tools/census_wave.py > profiles/census_wave_r09.txt          (no GPU needed)"""
 import json
 import os
 import subprocess
@@ -22,7 +23,9 @@ def find(marker, after=0):
 
 k0 = find("void gf_splat_render_mfma_wave_kernel(RenderArgs a)")
 ctr = find("uint32_t *ctr = a.tile_counters + 64 * xcd;", k0)
+take = find("// ---- the supertile's list as its unit 0 published it", k0)
 fast = find("// ---- fill, fast path", k0)
+pub = find("// ---- short rows: unit 0 of a supertile leaves the list", k0)
 slow = find("while (true) {  // fill the list from the row", k0)
 boxes = find("// ---- the packed boxes of the listed Gaussians", k0)
 cons = find("// ---- consume: hits of the double brick", k0)
@@ -36,10 +39,12 @@ odd = find("// depths that are not a multiple of 4", edge) - 1
 end = find("struct BoxVolArgs {", k0) - 1   # (the separator line before it: what follows the kernel)
 phases = [
     ["start-up, per wave (2 048 waves / 5 000 units; includes the never-taken arbitrary-points body: 151 VALU)", k0, ctr - 1, 2048 / 5000],
-    ["unit head: decode, row request, wait", ctr, fast - 1, 1.0],
-    ["list, fast path: dense-word compaction + three-round id extraction", fast, slow - 1, 1.0],
+    ["unit head: decode, row request, wait", ctr, take - 1, 1.0],
+    ["list taken from the supertile's unit 0 (0.595 of the units: profiles/timeline_wave_r09.txt)", take, fast - 1, 0.595],
+    ["list, fast path: dense-word compaction + three-round id extraction (the other units)", fast, pub - 1, 0.405],
+    ["unit 0: boxes, list published (one unit in eight)", pub, slow - 1, 0.125],
     ["list, chunked refill path (crowded rows only)", slow, boxes - 1, 0.0],
-    ["boxes by LDS-DMA (64 candidates per trip)", boxes, cons - 1, 140 / 64 + 0.5],
+    ["boxes by LDS-DMA (64 candidates per trip; the units that built their own list and are not unit 0)", boxes, cons - 1, 0.28 * (140 / 64 + 0.5) + 0.72],
     ["filter batch (64 candidates per trip)", cons, oper - 1, 140 / 64 + 0.5],
     ["group: operands (theta in fp64 -> 3 x f16, one-hot, S' transpose + split)", oper, pair - 1, 2.16],
     ["group: two pairs of blocks (64 exp, hi/lo split, 40 MFMA)", pair, brk - 1, 2.16],

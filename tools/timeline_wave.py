@@ -31,8 +31,11 @@ lib.gf_debug_set_timeline(None)
 T = tl.cpu().numpy().reshape(nu, 8).astype(np.float64)
 os.makedirs("gpurun_out", exist_ok=True)
 np.save("gpurun_out/timeline_wave_%s.npy" % config, T)
-T = T[T[:, 0] > 0]
-groups = T[:, 7].copy()
+idx = np.nonzero(T[:, 0] > 0)[0]   # unit index inside an XCD (the eight XCDs write the same rows: the last one stays)
+T = T[idx]
+took = T[:, 7] >= 1000             # short rows: the unit took its supertile's list from unit 0 (the groups are counted below 1000)
+groups = T[:, 7] % 1000
+first = idx // (((si.H + 7) // 8) * ((si.W + 7) // 8) + 7 >> 3) == 0   # ... dealt r-major: the first ceil(nsuper / 8) are the units 0
 t0 = T[:, 0].min()
 T = (T[:, :7] - t0) / 100.0
 print("units", len(T), "kernel span us %.2f" % T[:, 6].max(), " groups per unit %.2f" % groups.mean())
@@ -43,6 +46,12 @@ for k, nme in enumerate(names, 1):
     d = cur - prev
     print(f"{nme:22s} +{d.mean():6.2f} us (p50 {np.median(d):5.2f}, p90 {np.percentile(d, 90):5.2f}, max {d.max():5.2f})")
     prev = cur
+lb = np.where(T[:, 2] > 0, T[:, 2], T[:, 1]) - T[:, 1]
+bx = np.where(T[:, 3] > 0, T[:, 3], T[:, 2]) - T[:, 1]
+for nme, m in (("units 0 (publish)", first), ("took unit 0's list", took), ("built their own list", ~took & ~first)):
+    if m.any():
+        print(f"{nme:22s} {m.sum():5d} units ({100.0 * m.mean():4.1f} %): list built +{lb[m].mean():5.2f} us, row landed -> boxes landed {bx[m].mean():5.2f} us, "
+              f"unit total {(T[m, 6] - T[m, 0]).mean():5.2f} us, started p50 {np.median(T[m, 0]):5.2f} us")
 tot = T[:, 6] - T[:, 0]
 print("unit total mean %.2f p50 %.2f p90 %.2f max %.2f" % (tot.mean(), np.median(tot), np.percentile(tot, 90), tot.max()))
 st = np.sort(T[:, 0]); en = np.sort(T[:, 6])
