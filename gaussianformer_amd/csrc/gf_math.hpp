@@ -24,6 +24,17 @@ using cfloat_t = const float __attribute__((address_space(4))) *;
 typedef __attribute__((address_space(1))) float gfloat;
 typedef float nt4v __attribute__((ext_vector_type(4), aligned(4)));
 typedef __attribute__((address_space(1))) nt4v nt4;
+// write-through 16-byte store (`sc1`) of four floats at a wave-uniform base + a 32-bit per-lane byte offset + the constant IMM: the
+// line leaves the XCD's L2 with the store instead of staying there, dirty, until the kernel's end drains it (plain and nt stores
+// keep it).  Issued from inline asm, so hipcc does not count it: the asm `s_waitcnt vmcnt(N)` around such stores
+// count them by hand (`s_nop 1`: the data registers may be rewritten before a 16-byte store has read them).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) char gchar;
+template <int IMM>
+__device__ __forceinline__ void store16_wt(gchar *sbase, uint32_t voff, f32x4 v)
+{
+    asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc1\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase), "i"(IMM) : "memory");
+}
 
 // three f16 terms of an fp64 value (33 bits): the value as a (hi, lo) pair of floats, then exact fp32 residuals
 __device__ __forceinline__ void split3(double t, _Float16 &a, _Float16 &b, _Float16 &c)

@@ -72,6 +72,9 @@ struct PrepArgs {
     uint32_t *pub_len;       // null, or [nsx * nsy]: the length words of the lists the short-row wave kernel's first units publish for the
                              // supertile's other units -- cleared here, so that no word of an earlier call (or of whatever the memory held
                              // before it became this workspace) can carry this call's tag
+#if GF_TIMELINE
+    unsigned long long *timeline;   // debug: [2 * waves of the launch] start and end stamp of every wave (null = off; tools/timeline_wave.py)
+#endif
 };
 
 constexpr int kPrepSuperChunk = 4096;  // bitmask words in LDS per pass of the prep kernel (32 KB)
@@ -139,6 +142,15 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
     // LDS is sized at launch: [min(#supertiles, chunk)][WAVES] words.
     extern __shared__ unsigned long long s_bits[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#if GF_TIMELINE
+    const unsigned long long tp0 = wall_clock64();
+    auto stamp_end = [&]() {
+        if (a.timeline && lane == 0) {
+            a.timeline[2 * ((size_t)blockIdx.x * WAVES + wave)] = tp0;
+            a.timeline[2 * ((size_t)blockIdx.x * WAVES + wave) + 1] = wall_clock64();
+        }
+    };
+#endif
     if (a.gate_state) {
         // backward: the records of the forward that wrote this state block are still in the workspace (same generation) --
         // nothing to redo; or that forward was not rendered on the matrix cores -- the Gaussian-major kernels need no records
@@ -245,6 +257,9 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
         const uint32_t vbits = (any ? kVerdictPoint : 0u) | (any2 ? kVerdictLattice : 0u) | (any3 ? kVerdictTheta : 0u);
         if (lane == 0) a.verify_flags[vb] = vbits;
         if (a.verdict_words && vbits && lane == 0) atomicOr(a.verdict_words + verdict_slot_after(a.verdict_words[kVerdictA]), vbits);   // (rare)
+#if GF_TIMELINE
+        stamp_end();
+#endif
         return;
     }
     if (a.tile_counters && blockIdx.x == 0 && threadIdx.x < 8) a.tile_counters[64 * threadIdx.x] = a.tile_counter_init;
@@ -570,6 +585,9 @@ __global__ __launch_bounds__(64 * WAVES) void gf_splat_prep_kernel(PrepArgs a)
             }
         }
     }
+#if GF_TIMELINE
+    stamp_end();   // (the stores above are issued, not drained: what they leave dirty shows in the boundary, not in this span)
+#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1883,6 +1901,10 @@ __device__ const PhiHotTable kPhiHot = make_phi_hot_table();
 //   [17744, 20480)  opacity * semantics of the current group, [channel][Gaussian]
 constexpr int kWList = 512;
 constexpr int kWLdsDwords = 5120;
+// Store instructions of a unit inside the grid.  They are issued from inline asm, which hipcc does not count, and the next unit's row
+// wait is "at most this many operations outstanding": `nst` is set from this constant and the `s_waitcnt vmcnt(N)` is written with
+// it.  A count that differs from the instructions issued is a silent race on the prefetched row, not an error.
+constexpr int kUnitStores = 10;
 static_assert(3072 + 2 * kWRow + kQCap + (kC + 1) * kSRow == kWLdsDwords, "LDS map of the wave-autonomous kernel");
 static_assert((kWRow + 4 + 3) / 4 <= 3 * 64, "the wave kernel reads its range verdicts with three 16-byte loads per lane");
 static_assert(2 * 64 * kC <= 1536 + 3 * kWList, "output staging fits over the slot and the list");
@@ -2158,8 +2180,9 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
             bool published = false;
             int list_len = 0, qlen = 0, qhead = 0, npend = 0;
             // A prefetched row is older than the previous unit's output stores and memory operations complete in order: with
-            // exactly ten stores behind it, "at most ten outstanding" means the row has landed -- without waiting for the stores.
-            if (row_there && nst_prev == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+            // exactly kUnitStores stores behind it, "at most kUnitStores outstanding" means the row has landed -- without waiting for
+            // the stores (write-through ones are acknowledged later than stores the L2 keeps).
+            if (row_there && nst_prev == kUnitStores) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kUnitStores) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if GF_TIMELINE
             tl[1] = wall_clock64();
@@ -2723,26 +2746,30 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                     __builtin_amdgcn_wave_barrier();
                     labels_from_stage();
                 }
-                // (a unit inside the grid issues all ten store instructions: the count the next unit's row wait relies on)
+                // (a unit inside the grid issues all kUnitStores store instructions: the count the next unit's row wait relies on)
                 const bool inside = Xw + 4 <= a.H && Y0 + 4 <= a.W && Zw + 8 <= a.D;
-                nst = ((!LABELS) && inside) ? 10 : -1;
+                nst = ((!LABELS) && inside) ? kUnitStores : -1;
                 if (!LABELS || a.out_logits) {
-                typedef __attribute__((address_space(1))) char gchar;
                 gchar *ubase = (gchar *)a.out_logits + ((((size_t)Xw * a.W + Y0) * a.D + Zw) * kC) * sizeof(float);   // the unit's first voxel
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 // all ten LDS reads first (unconditional: a lane without a store reads a row it will not use), then the stores
-                float4 val[10];
+                float4 val[kUnitStores];
 #pragma unroll
-                for (int it = 0; it < 10; ++it)
+                for (int it = 0; it < kUnitStores; ++it)
                     val[it] = *reinterpret_cast<const float4 *>(stage + (it / 5) * 64 * kC + 4 * (lane + 64 * (it % 5)));
                 if (inside && st_fits) {
-                    // wholly inside the grid (every unit at 200 x 200 x 16): the uniform base + the wave's per-lane offsets, no bounds
+                    // wholly inside the grid (every unit at 200 x 200 x 16): the uniform base + the wave's per-lane offsets, no bounds.
+                    // Write-through: an nt store leaves its line dirty in the XCD's L2, 46 MB per launch through 32 MB of L2 -- next to
+                    // the records, rows and lists the units re-read, and for the end of the launch to drain (-0.5 us per step, 3.2d).
+                    static_assert(kUnitStores == 10, "two bricks of five store instructions");
 #pragma unroll
-                    for (int it = 0; it < 10; ++it) {
-                        if (it % 5 < 4 || st_tail)
-                            __builtin_nontemporal_store((nt4v){val[it].x, val[it].y, val[it].z, val[it].w},
-                                                        (nt4 *)(ubase + st_off[it % 5] + (it / 5) * 4 * kC * sizeof(float)));
+                    for (int it = 0; it < kUnitStores; ++it) {
+                        if (it % 5 < 4 || st_tail) {
+                            const f32x4 v = {val[it].x, val[it].y, val[it].z, val[it].w};
+                            if (it < 5) store16_wt<0>(ubase, st_off[it % 5], v);
+                            else store16_wt<4 * kC * (int)sizeof(float)>(ubase, st_off[it % 5], v);
+                        }
                     }
                 } else {
                     // a unit that crosses the grid's edge: every piece's column and brick are tested.  Its lane arithmetic is kept
@@ -3014,12 +3041,15 @@ static int check_forward_modes(const char *fn, int variant, int flags, const int
 }
 
 static unsigned long long *g_timeline = nullptr; static const int *g_tile_perm = nullptr;
+static unsigned long long *g_prep_timeline = nullptr;
 
 }  // namespace gf
 
 // debug hooks (not in the public header): per-workgroup timestamps of the render kernel, a workgroup -> tile permutation
 extern "C" void gf_debug_set_timeline(void *dev_ptr) { gf::g_timeline = (unsigned long long *)dev_ptr; }
 extern "C" void gf_debug_set_tile_perm(const void *dev_ptr) { gf::g_tile_perm = (const int *)dev_ptr; }
+// ... and a start and an end stamp per wave of the records pass (read by GF_TIMELINE builds only)
+extern "C" void gf_debug_set_prep_timeline(void *dev_ptr) { gf::g_prep_timeline = (unsigned long long *)dev_ptr; }
 
 // ... and the route gf_splat_forward (label_mode -1) or gf_splat_forward_labels (label_mode GF_LABELS_*) takes for these sizes, flags
 // and the library options in force.  Launches nothing and needs no GPU (without one the CU count is the fall-back, 256).  Writes up to
@@ -3096,6 +3126,9 @@ static int splat_forward_impl(const char *fn, int variant, int flags, int C, con
     pa.range_flags = rt.range_flags ? ws.range_flags : nullptr; pa.range_theta_here = rt.range_theta_here;
     pa.verdict_words = verdict_words; pa.summary = summary; pa.sum_pitch = ws.sum_pitch;
     pa.pub_len = (rt.kernel == kRenderMfmaWave && verdict_words) ? ws.bwd_list_len : nullptr;   // (the shared lists need the verdict block's call counter)
+#if GF_TIMELINE
+    pa.timeline = g_prep_timeline;
+#endif
     if (rt.prep_grid > 0) {
         launch_prep(pa, rt.prep_waves == 4, rt.prep_grid, stream);   // staged also for long rows: their summaries are written per four-wave workgroup
         GF_CHECK_LAUNCH_AS(fn);

@@ -4,9 +4,9 @@ import ctypes, os, sys
 import numpy as np, torch
 sys.path.insert(0, ".")
 from gaussianformer_amd import build as _b
-_tl = os.path.join(_b.CSRC, "libgf_hip_timeline.so")
+_tl = os.environ.get("GF_TIMELINE_LIB") or os.path.join(_b.CSRC, "libgf_hip_timeline.so")   # (another -DGF_TIMELINE=1 build: an A/B)
 _deps = [os.path.join(_b.CSRC, f) for f in _b.SOURCES + _b.HEADERS]
-if not os.path.exists(_tl) or any(os.path.getmtime(d) > os.path.getmtime(_tl) for d in _deps if os.path.exists(d)):
+if "GF_TIMELINE_LIB" not in os.environ and (not os.path.exists(_tl) or any(os.path.getmtime(d) > os.path.getmtime(_tl) for d in _deps if os.path.exists(d))):
     _b.build(extra_flags=("-DGF_TIMELINE=1",), lib_name="libgf_hip_timeline.so")
 os.environ["GF_LIB"] = _tl
 from gaussianformer_amd import _lib
@@ -26,8 +26,15 @@ nu = 8 * ((si.H + 7) // 8) * ((si.W + 7) // 8) * 4 * ((si.D + 7) // 8) // 8 + 64
 tl = torch.zeros(8 * nu, dtype=torch.int64, device=dev)
 lib.gf_debug_set_timeline.argtypes = [ctypes.c_void_p]
 lib.gf_debug_set_timeline(tl.data_ptr())
+# ... and of the records pass: a start and an end stamp per wave (P / 64 record waves + the point scans' waves), same clock
+ptl = torch.zeros(2 * (plan.P // 64 + 8192), dtype=torch.int64, device=dev)
+lib.gf_debug_set_prep_timeline.argtypes = [ctypes.c_void_p]
+lib.gf_debug_set_prep_timeline(ptl.data_ptr())
 plan.run(); torch.cuda.synchronize()
 lib.gf_debug_set_timeline(None)
+lib.gf_debug_set_prep_timeline(None)
+PT = ptl.cpu().numpy().reshape(-1, 2).astype(np.float64)
+PT = PT[PT[:, 0] > 0]
 T = tl.cpu().numpy().reshape(nu, 8).astype(np.float64)
 os.makedirs("gpurun_out", exist_ok=True)
 np.save("gpurun_out/timeline_wave_%s.npy" % config, T)
@@ -39,6 +46,11 @@ first = idx // (((si.H + 7) // 8) * ((si.W + 7) // 8) + 7 >> 3) == 0   # ... dea
 t0 = T[:, 0].min()
 T = (T[:, :7] - t0) / 100.0
 print("units", len(T), "kernel span us %.2f" % T[:, 6].max(), " groups per unit %.2f" % groups.mean())
+if len(PT):
+    # the step's pieces inside one call: records pass span, the boundary behind it, render span (min start to max end, 100 MHz clock)
+    print("records pass: waves %d, span us %.2f (wave mean %.2f, p90 %.2f); last end -> first render start us %.2f" % (
+        len(PT), (PT[:, 1].max() - PT[:, 0].min()) / 100.0, ((PT[:, 1] - PT[:, 0]) / 100.0).mean(),
+        np.percentile((PT[:, 1] - PT[:, 0]) / 100.0, 90), (t0 - PT[:, 1].max()) / 100.0))
 names = ["row landed", "list built", "boxes landed", "first records landed", "consumed", "stored"]
 prev = T[:, 0]
 for k, nme in enumerate(names, 1):
