@@ -30,159 +30,13 @@
 // output element is the same chain of MFMAs over the same k in the same order as in the tile kernel, and the LayerNorms are
 // written with their fusions spelled out (ln_rows<true>) in both, so the two kernels give the same bits: which one runs is
 // a matter of speed only, and a row's result does not depend on n.
-#include "gf_rows.hpp"
+//
+// The tile kernel itself (gf_ffn_kernel) and the argument checks are in gf_ffn.hpp, which the training step (ffn_train.hip,
+// DESIGN.md §3.13d) shares; this file instantiates the plain build only and stays a translation unit of its own, so that its
+// four kernels are compiled as they were before the training step existed.
+#include "gf_ffn.hpp"
 
 namespace gf {
-
-constexpr int kFfnE = GF_FFN_EMBED_DIMS, kFfnF = GF_FFN_HIDDEN;
-static_assert(kFfnE == 128 && kFfnF % 128 == 0, "the output is one block of gf_rows.hpp, the hidden row whole slices of it");
-constexpr int kFfnSlices = kFfnF / 128;
-
-struct FfnArgs {
-    const float *x, *residual;
-    float *out;
-    const float *pre_g, *pre_b, *w1, *b1, *w2, *b2, *wid, *bid, *post_g, *post_b;
-    int n;
-};
-
-template <int CIN>
-__global__ __launch_bounds__(256) void gf_ffn_kernel(FfnArgs a)
-{
-    constexpr int NB = CIN / 32;            // register blocks of u = chunks of a product over u
-    constexpr int PER = NB + 4;             // chunks per hidden slice: W1's, then W2's
-    static_assert(NB % 2 == 0, "a slice's chunks start on LDS buffer 0");
-    // LDS vectors, in float4: LN_pre weight, bias | b1 | b2 | bid | LN_post weight, bias
-    constexpr int vPre = 0, vB1 = 2 * CIN / 4, vB2 = vB1 + kFfnF / 4, vBid = vB2 + 32, vPost = vBid + 32, vEnd = vPost + 64;
-    __shared__ float4 s_w[2][128 * kRowPitch4];
-    __shared__ float4 s_vec[vEnd];
-    const int t = threadIdx.x, l = t & 63, wv = t >> 6, j = l & 31, h = l >> 5;
-    const int row0 = blockIdx.x * kRowTile + wv * 32;
-    const size_t row = (size_t)min(row0 + j, a.n - 1);
-    const int G = kFfnSlices * PER + (a.wid ? NB : 0);
-
-    float4 pre[4];
-    auto fetch = [&](int g) {     // chunk g of the walk (g is uniform)
-        const int s = g / PER, c = g - s * PER;
-        if (s == kFfnSlices) chunk_fetch(pre, a.wid, CIN, 32 * c, t);
-        else if (c < NB) chunk_fetch(pre, a.w1 + (size_t)(128 * s) * CIN, CIN, 32 * c, t);
-        else chunk_fetch(pre, a.w2, kFfnF, 128 * s + 32 * (c - NB), t);
-    };
-    // one chunk: the next one is fetched before this one's 64 MFMAs and written to the other buffer after them
-    auto step = [&](f32x16 (&acc)[4], const f32x16 &xb, int g, int buf) {
-        const bool more = g + 1 < G;
-        if (more) fetch(g + 1);
-        chunk_mfma(acc, xb, s_w[buf], j, h);
-        if (more) chunk_stash(s_w[buf ^ 1], pre, t);
-        __syncthreads();
-    };
-
-    fetch(0);
-    {
-        auto put = [&](int at, const float *src, int count4) {
-            if (src)
-                for (int e = t; e < count4; e += 256) s_vec[at + e] = ld4(src + 4 * e);
-        };
-        put(vPre, a.pre_g, CIN / 4);
-        put(vPre + CIN / 4, a.pre_b, CIN / 4);
-        put(vB1, a.b1, kFfnF / 4);
-        put(vB2, a.b2, 32);
-        put(vBid, a.bid, 32);
-        put(vPost, a.post_g, 32);
-        put(vPost + 32, a.post_b, 32);
-    }
-    f32x16 u[NB];
-    {
-        const float *xrow = a.x + row * CIN;
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float4 v = ld4(xrow + 32 * b + 8 * m + 4 * h);
-                u[b][4 * m] = v.x; u[b][4 * m + 1] = v.y; u[b][4 * m + 2] = v.z; u[b][4 * m + 3] = v.w;
-            }
-    }
-    chunk_stash(s_w[0], pre, t);
-    __syncthreads();
-    if (a.pre_g) {
-        float part[NB];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            float s = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s += u[b][r];
-            part[b] = s;
-        }
-        ln_rows<true, NB>(u, tree_sum<NB>(part), s_vec + vPre, s_vec + vPre + CIN / 4, h);
-    }
-
-    f32x16 hid[4], y[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) y[b][r] = 0.f;
-    int g = 0;
-#pragma unroll 1
-    for (int s = 0; s < kFfnSlices; ++s) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) hid[b][r] = 0.f;
-#pragma unroll
-        for (int c = 0; c < NB; ++c) step(hid, u[c], g++, c & 1);
-        const float4 *b1 = s_vec + vB1 + 32 * s;
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float4 bb = b1[8 * b + 2 * m + h];
-                const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float v = hid[b][4 * m + i] + bv[i];
-                    hid[b][4 * m + i] = v < 0.f ? 0.f : v;     // (not fmaxf: a NaN stays a NaN, as torch's relu keeps it)
-                }
-            }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) step(y, hid[c], g++, c & 1);
-    }
-    if (a.wid) {
-#pragma unroll
-        for (int c = 0; c < NB; ++c) step(y, u[c], g++, c & 1);
-    }
-
-    // y + b2 (+ bid) (+ residual), the lane's sum of it for LN_post
-    const float *rrow = a.residual ? a.residual + row * kFfnE : nullptr;
-    float part[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        float s = 0.f;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float4 bb = s_vec[vB2 + 8 * b + 2 * m + h];
-            float add[4] = {bb.x, bb.y, bb.z, bb.w};
-            float v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = y[b][4 * m + i] + add[i];
-            if (a.wid) {
-                const float4 ii = s_vec[vBid + 8 * b + 2 * m + h];
-                v[0] += ii.x; v[1] += ii.y; v[2] += ii.z; v[3] += ii.w;
-            }
-            if (a.residual) {   // last, so that a residual of zeros changes nothing
-                const float4 rr = ld4(rrow + 32 * b + 8 * m + 4 * h);
-                v[0] += rr.x; v[1] += rr.y; v[2] += rr.z; v[3] += rr.w;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                y[b][4 * m + i] = v[i];
-                s += v[i];
-            }
-        }
-        part[b] = s;
-    }
-    if (a.post_g) ln_rows<true, 4>(y, tree_sum<4>(part), s_vec + vPost, s_vec + vPost + 32, h);
-    // through the (idle) weight buffers: the last chunk's barrier is behind every wave's reads of them
-    store_rows(reinterpret_cast<float *>(&s_w[0][0]) + wv * (32 * kRowOutPitch), y, a.out, row0, a.n, l, j, h);
-}
 
 // n <= 32 CUs' worth of rows: 32 rows per workgroup, wave w owns feature block w of every product (see the top)
 template <int CIN>
@@ -363,36 +217,11 @@ extern "C" int gf_ffn_forward(int n, int Cin, int F, int E, const float *x, cons
                               float *out, void *stream_)
 {
     using namespace gf;
-    static const char *const kName[GF_FFN_PARAMS] = {"pre_norm.weight", "pre_norm.bias", "layers.0.0.weight", "layers.0.0.bias", "layers.1.weight",
-                                                     "layers.1.bias", "identity_fc.weight", "identity_fc.bias", "norm.weight", "norm.bias"};
-#define GF_FFN_REFUSE(cond, ...)                                   \
-    do {                                                           \
-        if (!(cond)) {                                             \
-            gf::set_error("gf_ffn_forward: " __VA_ARGS__);         \
-            return GF_EINVAL;                                      \
-        }                                                          \
-    } while (0)
-    auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-    GF_FFN_REFUSE(E == kFfnE, "E = %d: only embed_dims = 128 is supported", E);
-    GF_FFN_REFUSE(F == kFfnF, "F = %d: only feedforward_channels = 512 is supported", F);
-    GF_FFN_REFUSE(Cin == 128 || Cin == 256, "Cin = %d: only in_channels = 128 or 256 is supported", Cin);
-    GF_FFN_REFUSE(n >= 0, "n = %d is negative", n);
-    GF_FFN_REFUSE(params, "null params");
-    const float *const *p = reinterpret_cast<const float *const *>(params);
-    for (int i = 0; i < GF_FFN_PARAMS; i += 2) {
-        if (i == 2 || i == 4) {
-            GF_FFN_REFUSE(p[i], "%s is missing", kName[i]);
-            GF_FFN_REFUSE(p[i + 1], "%s is missing", kName[i + 1]);
-        }
-        GF_FFN_REFUSE(!p[i] == !p[i + 1], "a half-present pair: %s is null and %s is not", kName[p[i] ? i + 1 : i], kName[p[i] ? i : i + 1]);
-        for (int k = i; k < i + 2; ++k) GF_FFN_REFUSE(!misaligned(p[k]), "%s is not 16-byte aligned", kName[k]);
-    }
-    GF_FFN_REFUSE(!misaligned(x), "x is not 16-byte aligned");
-    GF_FFN_REFUSE(!misaligned(residual), "residual is not 16-byte aligned");
-    GF_FFN_REFUSE(!misaligned(out), "out is not 16-byte aligned");
+    const char *fn = __func__;
+    if (int rc = ffn_check(fn, n, Cin, F, E, x, params, residual, out)) return rc;
     if (n == 0) return GF_OK;
     GF_FFN_REFUSE(x && out, "null pointer");
-#undef GF_FFN_REFUSE
+    const float *const *p = reinterpret_cast<const float *const *>(params);
     FfnArgs a{x, residual, out, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], n};
     hipStream_t stream = (hipStream_t)stream_;
     if ((n + 31) / 32 <= cu_count()) {   // at most one 32-row workgroup per CU: the same bits, sooner
@@ -401,8 +230,8 @@ extern "C" int gf_ffn_forward(int n, int Cin, int F, int E, const float *x, cons
         else hipLaunchKernelGGL(gf_ffn_rows32_kernel<128>, grid, dim3(256), 0, stream, a);
     } else {
         const dim3 grid((n + kRowTile - 1) / kRowTile);
-        if (Cin == 256) hipLaunchKernelGGL(gf_ffn_kernel<256>, grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(gf_ffn_kernel<128>, grid, dim3(256), 0, stream, a);
+        if (Cin == 256) hipLaunchKernelGGL((gf_ffn_kernel<256, false>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((gf_ffn_kernel<128, false>), grid, dim3(256), 0, stream, a);
     }
     GF_CHECK_LAUNCH();
     return GF_OK;

@@ -1,8 +1,10 @@
 """The encoder's feed-forward block: drop-in for ``AsymmetricFFN`` (model/encoder/gaussian_encoder/ffn_module.py:8-75) and the
 one-launch form of the ``"ffn", "norm"`` and ``"identity", "ffn", "add", "norm"`` runs of the encoder's ``operation_order``.
 torch runs a block as two LayerNorms, three GEMMs, a ReLU and an add around an ``[A, 512]`` hidden tensor;
-``gf_ffn_forward`` (include/gf_hip.h) is one launch in which the hidden row never reaches memory.  Forward
-only: training, dropout and everything the native op does not cover run the module's own torch layers."""
+``gf_ffn_forward`` (include/gf_hip.h) is one launch in which the hidden row never reaches memory.  The
+training step -- the module's two dropouts, a saving forward and the full backward (``gf_ffn_forward_train``,
+``gf_ffn_backward``) -- is ``ffn_block_autograd`` and, on the module, the opt-in ``native_training``; without
+it training, dropout and everything the native op does not cover run the module's own torch layers."""
 import ctypes
 
 import torch
@@ -76,8 +78,8 @@ def _aligned(t):
     return t.clone() if t is not None and t.data_ptr() % 16 else t
 
 
-def _launch(x, params, residual):
-    """The library call on the 10-entry parameter list; the callers have settled autograd."""
+def _shape(x, params, residual):
+    """``(x [n, Cin], residual [n, E] or None, leading shape, Cin, F, E)`` as the library reads them, the shapes checked."""
     _lib.require_gpu(x, residual, *params)
     w1, w2 = params[2], params[4]
     if w1 is None or w2 is None or params[3] is None or params[5] is None:
@@ -98,6 +100,12 @@ def _launch(x, params, residual):
         if tuple(residual.shape) != (*lead, E):
             raise ValueError(f"ffn_block: residual {tuple(residual.shape)} is not {(*lead, E)}")
         res = _aligned(residual).reshape(-1, E)
+    return xa, res, lead, Cin, F, E
+
+
+def _launch(x, params, residual):
+    """The library call on the 10-entry parameter list; the callers have settled autograd."""
+    xa, res, lead, Cin, F, E = _shape(x, params, residual)
     table, held = _table(params)
     out = torch.empty(xa.shape[0], E, dtype=f32, device=xa.device)
     _lib.call("gf_ffn_forward", xa.device, xa.shape[0], Cin, F, E, xa, table, res, out)
@@ -117,6 +125,107 @@ def ffn_block(x, ffn, norm=None, residual=None):
             "ffn_block is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters "
             "that do not require grad (the AsymmetricFFN module routes training to its torch layers)")
     return _launch(x, params, residual)
+
+
+def train_sizes(n, cin):
+    """``(saved_bytes, workspace_bytes)`` of the training step on ``n`` rows of width ``cin`` (``gf_ffn_train_sizes``)."""
+    saved, work = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(_lib.load().gf_ffn_train_sizes(n, cin, ctypes.addressof(saved), ctypes.addressof(work)), "gf_ffn_train_sizes")
+    return saved.value, work.value
+
+
+def _keep_mask(keep, p, shape, device, what):
+    """``(mask, scale)`` of one dropout: the caller's keep mask as it is where it has one byte per entry (bool, uint8), any
+    other dtype as ``!= 0``; without one and with ``p > 0``, a mask drawn on the current generator straight into uint8 (no
+    float32 transient, capturable); ``(None, 1.0)`` when there is no dropout.  The scale is ``1 / (1 - p)``."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"ffn_block_autograd: {what} = {p} is not in [0, 1)")
+    if keep is None:
+        if p == 0.0:
+            return None, 1.0
+        keep = torch.empty(shape, dtype=torch.uint8, device=device).bernoulli_(1.0 - p)
+    else:
+        _lib.require_gpu(keep)
+        if tuple(keep.shape) != tuple(shape):
+            raise ValueError(f"ffn_block_autograd: the mask of {what} has shape {tuple(keep.shape)}, not {tuple(shape)}")
+        keep = keep.detach()
+        if keep.dtype == torch.bool:
+            keep = keep.contiguous().view(torch.uint8)
+        elif keep.dtype != torch.uint8:
+            keep = (keep != 0).to(torch.uint8)
+        keep = keep.contiguous()
+    return keep, 1.0 / (1.0 - p)
+
+
+def _out_table(tensors):
+    """The host table of the 10 OUTPUT pointers: the tensors themselves, never a copy."""
+    table = (ctypes.c_void_p * _lib.GF_FFN_PARAMS)()
+    for i, t in enumerate(tensors):
+        if t is not None:
+            table[i] = t.data_ptr()
+    return ctypes.cast(table, ctypes.c_void_p)
+
+
+class FFNBlockFunction(torch.autograd.Function):
+    """``out = FFNBlockFunction.apply(x, residual, keep_hidden, scale_hidden, keep_out, scale_out, *params)`` on the 10-entry
+    parameter list (``None`` for an absent part) and the two keep masks (uint8, ``None``: no dropout there):
+    ``gf_ffn_forward_train`` keeps the row before the post norm and the norms' statistics, ``gf_ffn_backward`` returns the
+    gradients of ``x``, the residual and every parameter that requires one.  Once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, residual, keep_hidden, scale_hidden, keep_out, scale_out, *params):
+        xa, res, lead, Cin, F, E = _shape(x, params, residual)
+        table, held = _table(params)
+        n = xa.shape[0]
+        saved_bytes, _ = train_sizes(n, Cin)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=xa.device)
+        out = torch.empty(n, E, dtype=f32, device=xa.device)
+        _lib.call("gf_ffn_forward_train", xa.device, n, Cin, F, E, xa, table, res, keep_hidden, scale_hidden, keep_out, scale_out,
+                  out, saved, saved_bytes)
+        ctx.save_for_backward(xa, saved, keep_hidden, keep_out, *held)
+        ctx.shape = (lead, Cin, F, E, scale_hidden, scale_out, x.dtype, None if residual is None else residual.dtype,
+                     [None if p is None else p.dtype for p in params])
+        return out.view(*lead, E)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xa, saved, keep_hidden, keep_out, *held = ctx.saved_tensors
+        lead, Cin, F, E, scale_hidden, scale_out, x_dtype, res_dtype, dtypes = ctx.shape
+        n = xa.shape[0]
+        params, grads, it = [], [], iter(held)
+        for d in dtypes:
+            params.append(None if d is None else next(it))
+            grads.append(None if d is None else torch.empty_like(params[-1]))
+        table, _ = _table(params)
+        _, work_bytes = train_sizes(n, Cin)
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=xa.device)
+        grad_x = torch.empty(n, Cin, dtype=f32, device=xa.device)
+        need = ctx.needs_input_grad
+        grad_res = torch.empty(n, E, dtype=f32, device=xa.device) if res_dtype is not None and need[1] else None
+        go = _aligned(grad_out).reshape(n, E)
+        _lib.call("gf_ffn_backward", xa.device, n, Cin, F, E, xa, table, keep_hidden, scale_hidden, keep_out, scale_out, saved, go,
+                  grad_x, grad_res, _out_table(grads), work, work_bytes)
+        return (grad_x.view(*lead, Cin).to(x_dtype) if need[0] else None,
+                None if grad_res is None else grad_res.view(*lead, E).to(res_dtype), None, None, None, None,
+                *[g.to(d) if g is not None and need[6 + i] else None for i, (g, d) in enumerate(zip(grads, dtypes))])
+
+
+def ffn_block_autograd(x, ffn, norm=None, residual=None, p_hidden=0.0, p_out=0.0, keep_hidden=None, keep_out=None):
+    """``ffn_block`` with the module's two dropouts and a native backward: ``out [..., 128]`` carries the graph of
+    ``FFNBlockFunction``, so ``x``, the residual and every parameter that requires grad receive their gradients (the others
+    ``None``).  ``p_hidden`` / ``p_out``: the probabilities of the dropout behind the ReLU (``layers.0.2``) and behind
+    ``layers.1`` (``layers.2``); the kept entries are scaled by ``1 / (1 - p)``.  ``keep_hidden [..., 512]`` / ``keep_out
+    [..., 128]``: the keep masks (nonzero = keep), used as they are where bool or uint8; without one and with ``p > 0`` the mask
+    is drawn here, as uint8, on the current generator.  Without any dropout and with nothing that needs autograd (or under
+    ``torch.no_grad()``) it is ``ffn_block``."""
+    params = _param_list(ffn, norm)
+    lead = tuple(x.shape[:-1])
+    keep_hidden, scale_hidden = _keep_mask(keep_hidden, p_hidden, (*lead, F_NATIVE), x.device, "p_hidden")
+    keep_out, scale_out = _keep_mask(keep_out, p_out, (*lead, E_NATIVE), x.device, "p_out")
+    if keep_hidden is None and keep_out is None and not _needs_grad([x, residual, *params]):
+        return _launch(x, params, residual)
+    return FFNBlockFunction.apply(x, residual, keep_hidden, scale_hidden, keep_out, scale_out, *params)
 
 
 def _build_norm(cfg, width):
@@ -157,7 +266,14 @@ class AsymmetricFFN(nn.Module):
     The native op runs when ``x`` is an fp32 GPU tensor, ``identity is None``, ``num_fcs == 2`` with ReLU, ``embed_dims == 128``,
     ``feedforward_channels == 512``, the input width is 128 or 256, nothing needs autograd, and the module is in eval mode or
     every dropout probability is 0.  Everything else runs ``forward_torch``, the reference's composition on the module's own
-    layers."""
+    layers.
+
+    ``native_training`` is an attribute, not a constructor key (the constructor stays the reference's), off by default and not
+    part of the ``state_dict``: set ``module.native_training = True`` and, under the same conditions, a call that needs autograd
+    or has an active ``ffn_drop`` runs ``FFNBlockFunction`` (the masks drawn with ``layers[0][2].p`` and ``layers[2].p``)
+    instead of the torch layers.  An active ``dropout_layer`` still goes to torch."""
+
+    native_training = False
 
     def __init__(self, in_channels=None, pre_norm=None, embed_dims=256, feedforward_channels=1024, num_fcs=2,
                  act_cfg=dict(type="ReLU", inplace=True), ffn_drop=0.0, dropout_layer=None, add_identity=True, init_cfg=None,
@@ -198,7 +314,7 @@ class AsymmetricFFN(nn.Module):
         first = self.layers[0][0]
         if self.embed_dims != E_NATIVE or self.feedforward_channels != F_NATIVE or first.in_features not in CIN_NATIVE:
             return False
-        if not (first.weight.is_cuda and first.weight.dtype == f32) or self._dropout_active():
+        if not (first.weight.is_cuda and first.weight.dtype == f32):
             return False
         if self.pre_norm is not None and (self.pre_norm.eps != 1e-5 or self.pre_norm.weight is None or self.pre_norm.bias is None):
             return False
@@ -207,8 +323,15 @@ class AsymmetricFFN(nn.Module):
     def forward(self, x, identity=None):
         if self._native(x, identity):
             params = _param_list(self, None)
-            if not _needs_grad([x, *params]):
-                return _launch(x, params, None)
+            if not self._dropout_active():
+                if not _needs_grad([x, *params]):
+                    return _launch(x, params, None)
+                if self.native_training:
+                    return FFNBlockFunction.apply(x, None, None, 1.0, None, 1.0, *params)
+            elif self.native_training and not (isinstance(self.dropout_layer, nn.Dropout) and self.dropout_layer.p > 0):
+                p_hidden, p_out = self.layers[0][2].p, self.layers[2].p
+                if p_hidden < 1.0 and p_out < 1.0:
+                    return ffn_block_autograd(x, self, p_hidden=p_hidden, p_out=p_out)
         return self.forward_torch(x, identity)
 
     def forward_torch(self, x, identity=None):

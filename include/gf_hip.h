@@ -848,6 +848,51 @@ int gf_anchor_embed_backward(int n, int Da, int E, int include_opa, int S, const
 int gf_ffn_forward(int n, int Cin, int F, int E, const float *x, const void *const *params, const float *residual, float *out,
                    void *stream);
 
+/* The feed-forward block's training step: a forward with the module's two dropouts that also saves what
+ * the backward needs, and the full backward.  E, F, Cin, the alignment rules and the 10-pointer params table are
+ * gf_ffn_forward's.  Per row:
+ *   u   = LN_pre(x)
+ *   h   = relu(W1 u + b1);   h' = h * (keep_hidden ? scale_hidden : 0)      keep_hidden u8 [n, 512], nonzero = keep
+ *   a   = W2 h' + b2;        a' = a * (keep_out ? scale_out : 0)            keep_out u8 [n, 128]: the bias is dropped with it
+ *   y   = a' + (Wid u + bid) + residual;   out = LN_post(y)
+ * The masks are the caller's (the op draws nothing) and need no alignment; a NULL mask = no dropout there, its scale is
+ * ignored.  A dropout is a product, as nn.Dropout's: a NaN stays a NaN under a dropped entry.
+ *
+ * gf_ffn_train_sizes: host code; the bytes of the two caller-allocated regions for n rows (both 0 for n == 0, both monotone
+ * in n; saved_bytes <= 640 n + 4096).  GF_EINVAL: n < 0, Cin not 128 or 256, a null result pointer.
+ *
+ * gf_ffn_forward_train: with both masks NULL, and with all-ones masks at scales of 1, out is BITWISE gf_ffn_forward's at
+ * every n.  `saved` (16-byte aligned, at least saved_bytes; opaque: the row before the post norm and the two norms' (mean,
+ * rstd) -- no [n, 512] array: the backward forms the hidden row again from x by the forward's own chain of MFMAs, so which
+ * hidden features are live is the forward's decision bit for bit).
+ *
+ * gf_ffn_backward: from grad_out f32 [n, 128], x, the parameters, the same masks and scales, and `saved` of the
+ * forward_train call on them,
+ *   grad_x         f32 [n, Cin], written in full
+ *   grad_residual  f32 [n, 128] or NULL: the gradient of y, written in full
+ *   grad_params    HOST table of 10 device pointers laid out like params, each tensor of its parameter's shape and 16-byte
+ *                  aligned: every present parameter's gradient is STORED, not accumulated -- the caller zeroes nothing
+ *   workspace      16-byte aligned, at least workspace_bytes; scratch, nothing survives the call
+ * with da = dy * (keep_out ? scale_out : 0), dz = W2^T da * (keep_hidden ? scale_hidden : 0) where h > 0 (or h is NaN, as
+ * torch's threshold) and 0 elsewhere.  Three kernels and a fixed-order sum: no atomics, bitwise reproducible; a row of grad_x /
+ * grad_residual does not depend on n or on the row's position; no host synchronisation, no allocation: graph-capturable.
+ * GF_EINVAL before any HIP call for everything gf_ffn_forward refuses, a misaligned or (n > 0) null region, a scale that is
+ * not finite and positive where its mask is given, a null or misaligned gradient of a present parameter; GF_EWORKSPACE for a
+ * region shorter than the query says.  n == 0: GF_OK, the parameter gradients zero-filled.
+ * GF_FFN_WGRAD_ROWS: the rows one workgroup of the weight-gradient kernel sums (the workspace holds one partial of the three
+ * matrices per block of that many rows).  GF_FFN_CHUNK_ROWS: the backward walks the rows in chunks of this many, one after the
+ * other on the stream, and the workspace holds the per-row intermediates of one chunk only. */
+#define GF_FFN_WGRAD_ROWS 512
+#define GF_FFN_CHUNK_ROWS 32768
+int gf_ffn_train_sizes(int n, int Cin, size_t *saved_bytes, size_t *workspace_bytes);
+int gf_ffn_forward_train(int n, int Cin, int F, int E, const float *x, const void *const *params, const float *residual,
+                         const unsigned char *keep_hidden, float scale_hidden, const unsigned char *keep_out, float scale_out,
+                         float *out, void *saved, size_t saved_bytes, void *stream);
+int gf_ffn_backward(int n, int Cin, int F, int E, const float *x, const void *const *params, const unsigned char *keep_hidden,
+                    float scale_hidden, const unsigned char *keep_out, float scale_out, const void *saved, const float *grad_out,
+                    float *grad_x, float *grad_residual, void *const *grad_params, void *workspace, size_t workspace_bytes,
+                    void *stream);
+
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */
 int gf_profile_stride(int every);
