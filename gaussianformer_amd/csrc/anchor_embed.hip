@@ -57,38 +57,6 @@ struct AnchorEmbedSaveArgs : AnchorEmbedArgs {
 template <bool SAVE> struct AeFwdArgs { using type = AnchorEmbedArgs; };
 template <> struct AeFwdArgs<true> { using type = AnchorEmbedSaveArgs; };
 
-// v <- LayerNorm(relu(v + bias)) over the 128 features of the lane's anchor (biased variance, two passes); p: the stage's
-// three vectors in LDS (32 float4 each: bias, LayerNorm weight, LayerNorm bias).  SAVE: the lane also stores its 64 post-ReLU
-// values to rrow (its anchor's row of the stage, null for a row past n) as float4s from the registers, and (mean, rstd) to st2
-template <bool SAVE>
-__device__ __forceinline__ void relu_ln(f32x16 (&v)[4], const float4 *p, int h, float *rrow = nullptr, float *st2 = nullptr)
-{
-    float part[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        float s = 0.f;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float4 bb = p[8 * b + 2 * m + h];
-            const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float x = v[b][4 * m + i] + bv[i];
-                x = x < 0.f ? 0.f : x;     // (not fmaxf: a NaN stays a NaN, as torch's relu keeps it)
-                v[b][4 * m + i] = x;
-                s += x;
-            }
-            if constexpr (SAVE) {
-                if (rrow)
-                    *reinterpret_cast<float4 *>(rrow + 32 * b + 8 * m + 4 * h) =
-                        make_float4(v[b][4 * m], v[b][4 * m + 1], v[b][4 * m + 2], v[b][4 * m + 3]);
-            }
-        }
-        part[b] = s;
-    }
-    ln_rows<SAVE, 4>(v, (part[0] + part[1]) + (part[2] + part[3]), p + 32, p + 64, h, rrow ? st2 : nullptr);
-}
-
 // acc <- W1 x^T for a thin first layer: step s takes k = 2 s (lanes 0-31) and 2 s + 1 (lanes 32-63)
 __device__ __forceinline__ void thin_product(f32x16 (&acc)[4], const float *arow, const AeThin &t, int j, int h)
 {

@@ -1,6 +1,6 @@
-// gf_rows.hpp -- what the row-wise MFMA kernels share (anchor_embed.hip, ffn.hip): the register
-// layout in which a wave holds 32 rows of 128-feature blocks, the LayerNorm on it, the staging of a weight chunk through LDS,
-// the chunk's 64 MFMAs and the store of a finished tile.
+// gf_rows.hpp -- what the row-wise MFMA kernels share (anchor_embed.hip, ffn.hip, refine_mlp.hip; DESIGN.md §3.12b, §3.13,
+// §3.13c): the register layout in which a wave holds 32 rows of 128-feature blocks, the LayerNorm on it, the staging of a
+// weight chunk through LDS, the chunk's 64 MFMAs and the store of a finished tile.
 //
 // The layout.  A workgroup of four waves owns 128 rows, a wave 32 of them.  Every product is Y^T = W X^T on
 // v_mfma_f32_32x32x2_f32: the accumulator's columns are the wave's rows, its rows features, four accumulators hold a block of
@@ -76,6 +76,39 @@ __device__ __forceinline__ void ln_rows(f32x16 (&v)[NB], float lane_sum, const f
     }
 }
 
+// v <- LayerNorm(relu(v + bias)) over the 128 features of the lane's row (biased variance, two passes); p: the stage's
+// three vectors in LDS (32 float4 each: bias, LayerNorm weight, LayerNorm bias).  SAVE: the lane also stores its 64 post-ReLU
+// values to rrow (its row of the stage's saved rows, null for a row past n) as float4s from the registers, and (mean, rstd)
+// to st2
+template <bool SAVE>
+__device__ __forceinline__ void relu_ln(f32x16 (&v)[4], const float4 *p, int h, float *rrow = nullptr, float *st2 = nullptr)
+{
+    float part[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        float s = 0.f;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const float4 bb = p[8 * b + 2 * m + h];
+            const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float x = v[b][4 * m + i] + bv[i];
+                x = x < 0.f ? 0.f : x;     // (not fmaxf: a NaN stays a NaN, as torch's relu keeps it)
+                v[b][4 * m + i] = x;
+                s += x;
+            }
+            if constexpr (SAVE) {
+                if (rrow)
+                    *reinterpret_cast<float4 *>(rrow + 32 * b + 8 * m + 4 * h) =
+                        make_float4(v[b][4 * m], v[b][4 * m + 1], v[b][4 * m + 2], v[b][4 * m + 3]);
+            }
+        }
+        part[b] = s;
+    }
+    ln_rows<SAVE, 4>(v, (part[0] + part[1]) + (part[2] + part[3]), p + 32, p + 64, h, rrow ? st2 : nullptr);
+}
+
 // A weight chunk: 128 rows x 32 floats of a matrix w in torch's layout from column col0 on, ld = the matrix's row length.
 // Thread t of 256 takes rows t / 8 + 32 i, float4 t % 8: fetched from L2 into registers, then written to an LDS buffer of
 // 128 x kRowPitch4 float4 (the two halves of the double buffering: fetch before a chunk's MFMAs, stash after them)
@@ -91,13 +124,15 @@ __device__ __forceinline__ void chunk_stash(float4 *buf, const float4 (&pre)[4],
 #pragma unroll
     for (int i = 0; i < 4; ++i) buf[(ff + 32 * i) * kRowPitch4 + fq] = pre[i];
 }
-// acc += W_chunk xb^T: the staged chunk's 32 input columns against the 32 features that xb, one register block, holds
-__device__ __forceinline__ void chunk_mfma(f32x16 (&acc)[4], const f32x16 &xb, const float4 *buf, int j, int h)
+// acc += W_chunk xb^T: the staged chunk's 32 input columns against the 32 features that xb, one register block, holds; NFB
+// accumulators take the chunk's first 32 NFB rows
+template <int NFB>
+__device__ __forceinline__ void chunk_mfma(f32x16 (&acc)[NFB], const f32x16 &xb, const float4 *buf, int j, int h)
 {
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
 #pragma unroll
-        for (int fb = 0; fb < 4; ++fb) {
+        for (int fb = 0; fb < NFB; ++fb) {
             const float4 w4 = buf[(32 * fb + j) * kRowPitch4 + 2 * m + h];
             acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.x, xb[4 * m + 0], acc[fb], 0, 0, 0);
             acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.y, xb[4 * m + 1], acc[fb], 0, 0, 0);

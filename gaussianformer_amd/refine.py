@@ -1,8 +1,9 @@
 """The encoder's Gaussian refinement step: host mirror of ``SparseGaussian3DRefinementModule``
 (model/encoder/gaussian_encoder/refine_module.py:11-123) and ``SparseGaussian3DRefinementModuleV2``
-(refine_module_v2.py:12-108).  The MLP (``layers``) stays torch; everything after it -- the 30-40 slices, stacks, cats, clamps,
-sigmoids and logs of :72-123 / v2 :62-107 -- is ``gf_refine_forward`` / ``gf_refine_backward`` (include/gf_hip.h): one launch
-each way."""
+(refine_module_v2.py:12-108).  By default the MLP (``layers``) stays torch; everything after it -- the 30-40 slices, stacks,
+cats, clamps, sigmoids and logs of :72-123 / v2 :62-107 -- is ``gf_refine_forward`` / ``gf_refine_backward``
+(include/gf_hip.h): one launch each way.  ``refine_fused`` (and the modules with ``fused_mlp = True``, inference only) runs the
+MLP and the tail in one launch, ``gf_refine_mlp_forward``."""
 import ctypes
 from collections import namedtuple
 from typing import NamedTuple
@@ -95,6 +96,61 @@ def refine(output, anchor, cfg):
     return outs[0], GaussianPrediction(*outs[1:8])
 
 
+MLP_KEYS = ("layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias", "layers.4.weight", "layers.4.bias",
+            "layers.5.weight", "layers.5.bias", "layers.7.weight", "layers.7.bias", "layers.9.weight", "layers.9.bias",
+            "layers.10.weight", "layers.10.bias", "layers.11.scale")
+assert len(MLP_KEYS) == _lib.GF_REFINE_MLP_PARAMS
+
+
+def _needs_grad(tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def refine_fused(instance_feature, anchor, anchor_embed, module_or_state_dict, cfg, return_mlp_output=False):
+    """The modules' whole forward in one launch (``gf_refine_mlp_forward``), on any leading batch shape:
+    ``(anchor_out [..., D], GaussianPrediction)``, plus the MLP's result after ``Scale`` ``[..., D]`` -- the bits the tail
+    consumed -- with ``return_mlp_output``.  The parameters come from a refinement module or from a state_dict with its keys
+    (``MLP_KEYS``), as they are at the time of the call.  Forward only: it computes no gradients and refuses to run where
+    autograd would record one."""
+    state = module_or_state_dict
+    if isinstance(state, nn.Module):
+        state = dict(state.named_parameters())
+    params = [state[k] for k in MLP_KEYS]
+    if _needs_grad((instance_feature, anchor, anchor_embed, *params)):
+        raise RuntimeError("refine_fused computes no gradients: use the module with fused_mlp = False (the torch MLP + refine) "
+                           "for training, or call it under torch.no_grad()")
+    _lib.require_gpu(instance_feature, anchor, anchor_embed, *params)
+    lead, E = instance_feature.shape[:-1], instance_feature.shape[-1]
+    f = _lib.as_arg(instance_feature).reshape(-1, E)
+    e = _lib.as_arg(anchor_embed).expand(*lead, E).reshape(-1, E)
+    a = _lib.as_arg(anchor).reshape(-1, anchor.shape[-1])
+    params = [_lib.as_arg(t) for t in params]
+    n, Da, D = f.shape[0], a.shape[1], params[12].shape[0]
+    if a.shape[0] != n:
+        raise ValueError(f"instance_feature has {n} rows, anchor {a.shape[0]}")
+    shapes = [(E, E), (E,), (E, E), (E,), (E,), (E,)] * 2 + [(D, E), (D,), (D,)]
+    for k, t, want in zip(MLP_KEYS, params, shapes):
+        if tuple(t.shape) != want:
+            raise ValueError(f"{k} has shape {tuple(t.shape)}, expected {want}")
+    opa = 1 if cfg.flags & _lib.GF_REFINE_OPACITY else 0
+
+    def new(w):
+        return torch.empty(n, w, dtype=f32, device=f.device)
+
+    three = 3 if cfg.version == 2 else 0
+    outs = (new(D), new(3), new(3), new(4), new(opa), new(cfg.S), new(three), new(three))
+    mlp_out = new(D) if return_mlp_output else None
+    consts = (ctypes.c_double * 11)(*cfg.consts)
+    table = (ctypes.c_void_p * _lib.GF_REFINE_MLP_PARAMS)(*[t.data_ptr() for t in params])
+    _lib.call("gf_refine_mlp_forward", f.device, n, E, D, Da, cfg.version, cfg.flags, cfg.R, cfg.S, ctypes.cast(consts, ctypes.c_void_p),
+              f, e, a, ctypes.cast(table, ctypes.c_void_p), mlp_out, *outs)
+    outs = [t.view(*lead, t.shape[-1]) for t in outs]
+    pred = GaussianPrediction(*outs[1:6]) if cfg.version == 1 else GaussianPrediction(*outs[1:8])
+    if return_mlp_output:
+        return outs[0], pred, mlp_out.view(*lead, D)
+    return outs[0], pred
+
+
 class Scale(nn.Module):
     """One learnable factor per column, all ones at first: the parameter ``scale [width]`` that mmcv's ``Scale`` holds when the
     reference builds it from a list."""
@@ -118,7 +174,10 @@ def refinement_mlp(embed_dims, output_dim):
 
 
 class _Refinement(nn.Module):
-    """What the two drop-ins share: the torch MLP, then one library call."""
+    """What the two drop-ins share: the torch MLP, then one library call.  ``fused_mlp`` (an attribute, not a constructor key and
+    not in the state_dict; off by default): when set, a call that needs no gradient, at ``embed_dims`` 128 on fp32 GPU tensors,
+    is one launch (``refine_fused``); every other call takes the default route."""
+    fused_mlp = False
 
     def __init__(self, version, where, embed_dims, pc_range, scale_range, unit, restrict_xyz, refine_manual, semantics,
                  semantic_dim, include_opa, semantics_activation, xyz_activation, scale_activation):
@@ -136,7 +195,14 @@ class _Refinement(nn.Module):
                                   semantics_activation, xyz_activation)
         self.layers = refinement_mlp(embed_dims, self.output_dim)
 
+    def _takes_fused(self, instance_feature, anchor, anchor_embed):
+        tensors = (instance_feature, anchor, anchor_embed, *self.layers.parameters())
+        return (self.fused_mlp and self.embed_dims == 128 and not _needs_grad(tensors)
+                and all(t.is_cuda and t.dtype == f32 for t in tensors))
+
     def forward(self, instance_feature, anchor, anchor_embed):
+        if self._takes_fused(instance_feature, anchor, anchor_embed):
+            return refine_fused(instance_feature, anchor, anchor_embed, self, self._cfg)
         return refine(self.layers(instance_feature + anchor_embed), anchor, self._cfg)
 
 

@@ -756,6 +756,39 @@ int gf_refine_backward(int n, int D, int Da, int version, int flags, int R, int 
                        const float *grad_original_means, const float *grad_delta_means, float *grad_output, float *grad_anchor,
                        void *stream);
 
+/* The refinement modules' MLP and that tail in one launch, forward only: everything
+ * SparseGaussian3DRefinementModule.forward (refine_module.py:70-123) and SparseGaussian3DRefinementModuleV2.forward
+ * (refine_module_v2.py:62-107) compute from their three inputs.  Per row, E = 128:
+ *   x = instance_feature + anchor_embed                                   (refine_module.py:70, refine_module_v2.py:62)
+ *   x = relu(W0 x + b0);  x = relu(W2 x + b2);  x = LN4(x)                layers.0, .2, .4 (the modules' `layers`, :59-62)
+ *   x = relu(W5 x + b5);  x = relu(W7 x + b7);  x = LN9(x)                layers.5, .7, .9
+ *   o = (W10 x + b10) * scale                                             layers.10 [D, 128], layers.11.scale [D]
+ *   (anchor_out, means, scales, rotations, opacities, semantics[, original_means, delta_means]) = the tail above on (o, anchor)
+ * LayerNorm: eps 1e-5, biased variance, mean first, affine.  ReLU keeps a NaN.  The tail is gf_refine_forward's code on the
+ * same bits: its outputs equal gf_refine_forward(mlp_out, anchor) bit for bit; version, flags, R, S and consts are its.
+ *   instance_feature, anchor_embed  f32 [n, 128], 16-byte aligned          anchor f32 [n, Da]
+ *   params     HOST table of GF_REFINE_MLP_PARAMS = 15 device pointers, the module's own tensors in state_dict order, in
+ *              torch's layout, contiguous f32, each 16-byte aligned:
+ *                0 layers.0.weight [128, 128]   1 layers.0.bias [128]     2 layers.2.weight   3 layers.2.bias
+ *                4 layers.4.weight [128] (LayerNorm)   5 layers.4.bias    6 layers.5.weight   7 layers.5.bias
+ *                8 layers.7.weight   9 layers.7.bias   10 layers.9.weight (LayerNorm)         11 layers.9.bias
+ *                12 layers.10.weight [D, 128]   13 layers.10.bias [D]     14 layers.11.scale [D]
+ *   mlp_out    f32 [n, D] or NULL (not written): o, the bits the tail consumed
+ *   the outputs as gf_refine_forward's
+ * The table is read during the call and the weights by the kernel, in place: nothing is cached or re-laid out, nothing is
+ * loaded from beyond a tensor, and there is no workspace.
+ * GF_EINVAL before any HIP call, the message naming the offending value: everything gf_refine_forward refuses (the same
+ * messages), E != 128, a null or misaligned parameter, a null instance_feature, anchor_embed or anchor (or a misaligned one of
+ * the first two), a null output.  n == 0 returns GF_OK without a launch and without looking at any pointer.  Exact fp32
+ * products (v_mfma_f32_32x32x2_f32), no atomics, bitwise reproducible; a row's result does not depend on n or on the row's
+ * position; no host synchronisation, no allocation: graph-capturable. */
+#define GF_REFINE_MLP_PARAMS 15
+int gf_refine_mlp_forward(int n, int E, int D, int Da, int version, int flags, int R, int S, const double *consts,
+                          const float *instance_feature, const float *anchor_embed, const float *anchor,
+                          const void *const *params, float *mlp_out,
+                          float *anchor_out, float *means, float *scales, float *rotations, float *opacities,
+                          float *semantics, float *original_means, float *delta_means, void *stream);
+
 /* ---- the anchor encoder ---------------------------------------------------------------------------------------------------
  * Replaces SparseGaussian3DEncoder.forward (model/encoder/gaussian_encoder/anchor_encoder_module.py:38-53; its layers are
  * linear_relu_ln(embed_dims, 1, 2, input_dims), utils.py:49-59): one launch instead of about 40 torch kernels, DESIGN.md
