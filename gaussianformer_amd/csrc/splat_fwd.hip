@@ -1893,7 +1893,8 @@ __device__ const PhiHotTable kPhiHot = make_phi_hot_table();
 // 2.4 rounds, the last one a third full); here a slot is re-filled brick by brick.  The price: every wave scans the row
 // and fetches the candidates' boxes itself (four times the tile kernel's box traffic, all of it L2 hits).
 // LDS: 20 480 bytes per wave, carved by hand (eight workgroups fill the CU's 160 KB exactly):
-//   [    0,  6144)  record slot: six 1 KB pieces per group, written by LDS-DMA
+//   [    0,  6144)  record slot: four 1 KB planes per group in [0, 4096), written by LDS-DMA (piece p of Gaussian n at float4
+//                   64 (p & 3) + 32 (p >> 2) + n); all 6 144 bytes are the list builders' dense array while a list is built
 //   [ 6144, 12288)  candidate list: ids, packed box lo, packed box hi, kWList entries each
 //   [    0,  9216)  ... output staging in the epilogue (slot and list are dead by then)
 //   [12288, 17232)  bitmask row (kWRow words)
@@ -2111,10 +2112,15 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
 
     auto request_records_at = [&](int qh, int start, int count) {
         const uint32_t id = q_id[(qh + start + (n < count ? n : 0)) & (kQCap - 1)];
-        const char *rec = reinterpret_cast<const char *>(a.records + (size_t)id * kRecDwords);
-        // (semantics: lane h = 0 takes pieces 3..5 = channels 0..11, lane h = 1 pieces 5..7 = channels 8..19 -- see S' below)
-        const int o3 = (3 + 2 * h) * 16, o4 = (4 + 2 * h) * 16, o5 = (5 + 2 * h) * 16;
-        request_record_pieces(rec, reinterpret_cast<char *>(slot), o3, o4, o5);
+        // The two half-lanes of a Gaussian bring its record ONCE: lane (n, h) takes pieces 4 h .. 4 h + 3 into planes 0 .. 3 of the
+        // slot, so piece p of Gaussian n lies at slot[64 (p & 3) + 32 (p >> 2) + n] -- four requests and 4 KB per group.  (The tile
+        // kernel's six, request_record_pieces, fetch pieces 0 .. 2 and 5 in both half-lanes: 6 KB for the same 32 records.)
+        const char *rec = reinterpret_cast<const char *>(a.records + (size_t)id * kRecDwords) + 64 * h;
+        char *dst = reinterpret_cast<char *>(slot);
+        lds_dma16((gptr)(rec), (lptr)(dst));
+        lds_dma16((gptr)(rec + 16), (lptr)(dst + 1024));
+        lds_dma16((gptr)(rec + 32), (lptr)(dst + 2048));
+        lds_dma16((gptr)(rec + 48), (lptr)(dst + 3072));
     };
 
     // Output rows of a unit as the epilogue stores them: float4 i = lane + 64 j (j < 5) of a brick's 16 runs x 18 floats: run i / 18 =
@@ -2585,8 +2591,11 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
 #endif
                         // ---- operands of the group: lane (g = n, h)
                         const bool live = n < qn;
-                        const float4 r0 = slot[lane], r1 = slot[64 + lane], r2 = slot[128 + lane];
-                        const float4 e0 = slot[192 + lane], e1 = slot[256 + lane], e2 = slot[320 + lane];
+                        // (pieces 0 .. 2 from the h = 0 half of planes 0 .. 2: the same address in both half-lanes, a broadcast;
+                        // the semantics are pieces 3, 4, 5 = channels 0..11 for h = 0 and 5, 6, 7 = channels 8..19 for h = 1 -- see
+                        // S' below.  Both half-lanes read what the other one fetched: the wait above is the wave's.)
+                        const float4 r0 = slot[n], r1 = slot[64 + n], r2 = slot[128 + n];
+                        const float4 e0 = slot[(h ? 96 : 192) + n], e1 = slot[(h ? 160 : 32) + n], e2 = slot[(h ? 224 : 96) + n];
                         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // every lane has its pieces: the slot is free again
                         __builtin_amdgcn_wave_barrier();
                         const int nnext = (flush && avail < 32) ? 0 : min(avail, 32);   // (a flush forms no partial group)

@@ -1,7 +1,8 @@
 // splat_mfma.hpp -- what the two persistent matrix-core forward kernels of splat_fwd.hip (gf_splat_render_mfma_kernel, one tile per
-// workgroup, and gf_splat_render_mfma_wave_kernel, one double brick per wave) do alike per group of 32 Gaussians: the record request
-// and the exponent + accumulate of a block pair.  gfx950 only, device only, plain functions; each says which lanes must be active,
-// what LDS it touches and which waits and fences it leaves to the caller.  The kernels are held to bit-identity with each other
+// workgroup, and gf_splat_render_mfma_wave_kernel, one double brick per wave) do alike per group of 32 Gaussians: the exponent +
+// accumulate of a block pair -- and the tile kernel's record request (the wave kernel fetches each record once, four pieces per
+// half-lane, and keeps that request and its slot layout to itself).  gfx950 only, device only, plain functions; each says which
+// lanes must be active, what LDS it touches and which waits and fences it leaves to the caller.  The kernels are held to bit-identity with each other
 // (test_mfma_wave_and_tile_kernels_agree_bit_for_bit, test_list_builder_regimes_agree_across_kernels_and_with_the_oracle), so forms
 // that differ stay in the kernels: the tile kernel forms `tb` with selects and splits S' with fmaf (it runs at 252 VGPRs: its
 // operand phase is left alone), the wave kernel uses packed 16-bit operations and v_fma_mix_f32.  The matrix-core backward
@@ -22,9 +23,9 @@ union H8 {   // an MFMA A / B fragment, by vector, packed pair, element or dword
 };
 
 // ---- record request ------------------------------------------------------------------------------------------------------------
-// The forward's record request: six 16-byte pieces per lane of the record at `rec` into the six 1 KB planes of the wave's slot
+// The tile kernel's record request: six 16-byte pieces per lane of the record at `rec` into the six 1 KB planes of the wave's slot
 // `dst` by LDS-DMA -- mean / opacity, covariance, covariance + box, and the three semantics pieces at byte offsets o3, o4, o5 of the
-// record (the tile and the wave kernel stage other channels per half-lane).  All 64 lanes active.  Issued from inline asm: nothing
+// record (the channels its half-lane stages).  All 64 lanes active.  Issued from inline asm: nothing
 // waits here, the caller's `s_waitcnt vmcnt` does, and the slot must be free (a wave fence behind its last reads) before the call.
 // (The backward fetches other pieces and a seventh, and issues them as compiler-visible builtins on purpose: it stays there.)
 __device__ __forceinline__ void request_record_pieces(const char *rec, char *dst, int o3, int o4, int o5)
