@@ -32,7 +32,7 @@ GF_OCC_PROB, GF_OCC_MASK, GF_OCC_LOVASZ_IGNORE, GF_OCC_IGNORE_EMPTY, GF_OCC_NO_L
 GF_LIFT_MAX_BINS, GF_LIFT_MAX_ANCHORS, GF_PIXEL_LOSS_SOFTMAX, GF_PIXEL_LOSS_SIGMOID = 256, 8, 1, 2
 GF_DCN_MAX_KERNEL, GF_DCN_CHANNEL_GRANULE = 7, 32
 GF_REFINE_RESTRICT_XYZ, GF_REFINE_XYZ_IDENTITY, GF_REFINE_OPACITY, GF_REFINE_SEM_SOFTMAX, GF_REFINE_SEM_SOFTPLUS = 1, 2, 4, 8, 16
-GF_REFINE_MLP_PARAMS = 15
+GF_REFINE_MLP_PARAMS, GF_REFINE_MLP_WGRAD_ROWS, GF_REFINE_MLP_CHUNK_ROWS = 15, 512, 32768
 GF_ANCHOR_EMBED_DIMS, GF_ANCHOR_EMBED_MAX_S, GF_ANCHOR_EMBED_PARAMS, GF_ANCHOR_EMBED_WGRAD_ROWS, GF_ANCHOR_EMBED_CHUNK_ROWS = 128, 32, 48, 512, 65536
 GF_FFN_PARAMS, GF_FFN_EMBED_DIMS, GF_FFN_HIDDEN, GF_FFN_WGRAD_ROWS, GF_FFN_CHUNK_ROWS = 10, 128, 512, 512, 32768
 GF_PATH_EXACT_TILE, GF_PATH_MATRIX_CORE, GF_PATH_ARBITRARY, GF_PATH_MATRIX_CORE_WAVE, GF_PATH_MATRIX_CORE_PAIR, GF_PATH_MATRIX_CORE_SOLO = 0, 1, 2, 3, 4, 5
@@ -105,6 +105,9 @@ SIGNATURES = {
     "gf_refine_forward": (_i, [_i] * 7 + [_vp] * 11 + [_vp]),
     "gf_refine_backward": (_i, [_i] * 7 + [_vp] * 13 + [_vp]),
     "gf_refine_mlp_forward": (_i, [_i] * 8 + [_vp] * 14 + [_vp]),
+    "gf_refine_mlp_train_sizes": (_i, [_i] * 3 + [_vp] * 2),
+    "gf_refine_mlp_forward_train": (_i, [_i] * 8 + [_vp] * 14 + [_vp, _sz, _vp]),
+    "gf_refine_mlp_backward": (_i, [_i] * 8 + [_vp] * 18 + [_vp, _sz, _vp]),
     "gf_anchor_embed_forward": (_i, [_i] * 5 + [_vp] * 3 + [_vp]),
     "gf_anchor_embed_train_sizes": (_i, [_i] * 3 + [_vp] * 2),
     "gf_anchor_embed_forward_train": (_i, [_i] * 5 + [_vp] * 3 + [_vp, _sz, _vp]),

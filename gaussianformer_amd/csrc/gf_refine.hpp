@@ -1,6 +1,7 @@
-// gf_refine.hpp -- what the refinement step's two translation units share (refine.hip: the tail alone, forward and backward;
-// refine_mlp.hip: the modules' MLP and the tail in one launch): the constants, the arguments, the
-// moves between memory and the LDS tiles, a row's forward values and the forward tail on them, and the argument checks.
+// gf_refine.hpp -- what the refinement step's translation units share (refine.hip: the tail alone, forward and backward;
+// refine_mlp.hip: the modules' MLP and the tail in one launch, plain and saving; refine_mlp_train.hip: the modules' backward;
+// DESIGN.md §3.12, §3.12b, §3.12c): the constants, the arguments, the moves between memory and the LDS tiles, a row's forward
+// values and the forward tail on them, the argument checks, the tail's backward launch and the saved region's layout.
 #pragma once
 #include "gf_common.hpp"
 
@@ -239,6 +240,61 @@ inline bool refine_forward_outputs_present(int version, int flags, int S, const 
 {
     return anchor_out && means && scales && rotations && (opacities || !(flags & GF_REFINE_OPACITY)) && (semantics || S == 0) &&
            (version == 1 || (original_means && delta_means));
+}
+
+// The tail's backward launch on filled arguments (refine.hip): gf_refine_backward's, and the first step of
+// gf_refine_mlp_backward.  0 or GF_ELAUNCH, reported under `who`
+int refine_launch_backward(const char *who, const RefineArgs &a, int version, hipStream_t stream);
+
+// ---- the MLP's entry points (refine_mlp.hip, refine_mlp_train.hip) -----------------------------------------------------------
+constexpr int kRmE = 128;
+constexpr int kRmYPitch = 64;     // floats per row of the saved pre-Scale value: the last product's two accumulators
+
+static const char *const kRmName[GF_REFINE_MLP_PARAMS] = {
+    "layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias", "layers.4.weight", "layers.4.bias", "layers.5.weight", "layers.5.bias",
+    "layers.7.weight", "layers.7.bias", "layers.9.weight", "layers.9.bias", "layers.10.weight", "layers.10.bias", "layers.11.scale"};
+
+#define GF_RM_REFUSE(cond, fmt, ...)                                   \
+    do {                                                               \
+        if (!(cond)) {                                                 \
+            gf::set_error("%s: " fmt, fn, ##__VA_ARGS__);              \
+            return GF_EINVAL;                                          \
+        }                                                              \
+    } while (0)
+inline bool rm_misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// what every launching entry point of the MLP refuses of its inputs once n > 0, in gf_refine_mlp_forward's order and words,
+// under the name of the one that was called
+inline int refine_mlp_check_inputs(const char *fn, const void *const *params, const float *instance_feature, const float *anchor_embed,
+                                   const float *anchor)
+{
+    GF_RM_REFUSE(params, "null params");
+    for (int i = 0; i < GF_REFINE_MLP_PARAMS; ++i) {
+        GF_RM_REFUSE(params[i], "params[%d] (%s) is null", i, kRmName[i]);
+        GF_RM_REFUSE(!rm_misaligned(params[i]), "params[%d] (%s) = %p is not 16-byte aligned", i, kRmName[i], params[i]);
+    }
+    GF_RM_REFUSE(instance_feature, "null instance_feature");
+    GF_RM_REFUSE(anchor_embed, "null anchor_embed");
+    GF_RM_REFUSE(anchor, "null anchor");
+    GF_RM_REFUSE(!rm_misaligned(instance_feature), "instance_feature = %p is not 16-byte aligned", (const void *)instance_feature);
+    GF_RM_REFUSE(!rm_misaligned(anchor_embed), "anchor_embed = %p is not 16-byte aligned", (const void *)anchor_embed);
+    return GF_OK;
+}
+
+// What the saving forward keeps for the backward, sized and carved by one function (a null base: the size only): the four
+// post-ReLU rows [4][n][128], the two LayerNorms' (mean, rstd) [2][n][2], the last Linear's result before Scale [n][64] (zero
+// from D on) and the MLP's result o [n][D]
+struct RefineMlpSaved { float *rows, *stat, *y, *o; size_t bytes; };
+inline RefineMlpSaved refine_mlp_carve_saved(void *base, int n, int D)
+{
+    Carver c(base);
+    RefineMlpSaved s;
+    s.rows = c.take<float>((size_t)4 * n * kRmE);
+    s.stat = c.take<float>((size_t)4 * n);
+    s.y = c.take<float>((size_t)n * kRmYPitch);
+    s.o = c.take<float>((size_t)n * D);
+    s.bytes = c.bytes();
+    return s;
 }
 
 }  // namespace gf

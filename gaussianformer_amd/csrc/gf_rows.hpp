@@ -1,5 +1,5 @@
-// gf_rows.hpp -- what the row-wise MFMA kernels share (anchor_embed.hip, ffn.hip, refine_mlp.hip; DESIGN.md §3.12b, §3.13,
-// §3.13c): the register layout in which a wave holds 32 rows of 128-feature blocks, the LayerNorm on it, the staging of a
+// gf_rows.hpp -- what the row-wise MFMA kernels share (anchor_embed.hip, ffn.hip, refine_mlp.hip, refine_mlp_train.hip;
+// DESIGN.md §3.12b, §3.12c, §3.13, §3.13c): the register layout in which a wave holds 32 rows of 128-feature blocks, the LayerNorm on it, the staging of a
 // weight chunk through LDS, the chunk's 64 MFMAs and the store of a finished tile.
 //
 // The layout.  A workgroup of four waves owns 128 rows, a wave 32 of them.  Every product is Y^T = W X^T on

@@ -159,6 +159,15 @@ __global__ __launch_bounds__(64) void gf_refine_kernel(RefineArgs a)
 
 static size_t lds_bytes(const RefineArgs &a, bool backward) { return (size_t)64 * 4 * (a.po * (backward ? 2 : 1) + a.pa + a.pn); }
 
+int refine_launch_backward(const char *who, const RefineArgs &a, int version, hipStream_t stream)
+{
+    const dim3 grid((a.n + 63) / 64), block(64);
+    if (version == 1) hipLaunchKernelGGL((gf_refine_kernel<1, true>), grid, block, lds_bytes(a, true), stream, a);
+    else hipLaunchKernelGGL((gf_refine_kernel<2, true>), grid, block, lds_bytes(a, true), stream, a);
+    GF_CHECK_LAUNCH_AS(who);
+    return GF_OK;
+}
+
 }  // namespace gf
 
 extern "C" int gf_refine_forward(int n, int D, int Da, int version, int flags, int R, int S, const double *consts, const float *output,
@@ -196,9 +205,5 @@ extern "C" int gf_refine_backward(int n, int D, int Da, int version, int flags, 
     a.g_anchor_out = grad_anchor_out; a.g_means = grad_means; a.g_scales = grad_scales; a.g_rotations = grad_rotations;
     a.g_opacities = grad_opacities; a.g_semantics = grad_semantics; a.g_original = grad_original_means; a.g_delta = grad_delta_means;
     a.grad_output = grad_output; a.grad_anchor = grad_anchor;
-    const dim3 grid((n + 63) / 64), block(64);
-    if (version == 1) hipLaunchKernelGGL((gf_refine_kernel<1, true>), grid, block, lds_bytes(a, true), (hipStream_t)stream_, a);
-    else hipLaunchKernelGGL((gf_refine_kernel<2, true>), grid, block, lds_bytes(a, true), (hipStream_t)stream_, a);
-    GF_CHECK_LAUNCH();
-    return GF_OK;
+    return refine_launch_backward(__func__, a, version, (hipStream_t)stream_);
 }

@@ -18,13 +18,17 @@
 // shipped config: 67); wider rows (D = 43: 95) go in two passes of two waves.
 //
 // Rows past n in the last tile compute on row n - 1 and are not stored.
+//
+// The training step's forward (gf_refine_mlp_forward_train) is the same kernel's SAVE instantiation; the
+// backward is refine_mlp_train.hip.
+#include <type_traits>
+
 #include "gf_refine.hpp"
 #include "gf_rows.hpp"
 
 namespace gf {
 
-constexpr int kRmE = 128;
-constexpr int kRmVecs = 8;                     // b0 | b2, LN4 weight, bias | b5 | b7, LN9 weight, bias: 32 float4 each
+constexpr int kRmVecs = 8;                    // b0 | b2, LN4 weight, bias | b5 | b7, LN9 weight, bias: 32 float4 each
 constexpr int kRmTail4 = kRmVecs * 32;         // then layers.10.bias and layers.11.scale, 64 floats each, zero from D on
 constexpr int kRmWeightFloats = 2 * kRmE * kRowPitch4 * 4;
 constexpr int kRmFitAll = kRmWeightFloats / kRowTile;        // floats per row that four waves' tiles may take: 72
@@ -39,6 +43,10 @@ struct RefineMlpArgs {
     const float *b10, *scale;     // [D]
     float *mlp_out;               // [n, D] or null
     int wpp;                      // waves per pass of the tail: 4, or 2 where four waves' tiles do not fit
+};
+// the saving forward's (gf_refine_mlp_forward_train): the plain kernel's arguments as they are, then where the saved rows go
+struct RefineMlpTrainArgs : RefineMlpArgs {
+    float *sv_rows, *sv_stat, *sv_y, *sv_o;   // gf_refine.hpp's RefineMlpSaved
 };
 
 // v <- relu(v + bias); p: the bias in LDS, 32 float4
@@ -58,8 +66,12 @@ __device__ __forceinline__ void bias_relu(f32x16 (&v)[4], const float4 *p, int h
         }
 }
 
-template <int VERSION>
-__global__ __launch_bounds__(256, 2) void gf_refine_mlp_kernel(RefineMlpArgs a)
+// SAVE: the training step's forward.  The same stages on the same expressions (relu_ln<true> spells out the plain build's
+// fusions, gf_rows.hpp), and each lane also stores what the backward needs of its row: the four post-ReLU rows, the two
+// LayerNorms' (mean, rstd), the last Linear's result before Scale and o.  tests/test_refine_mlp_train_gpu.py holds the two
+// instantiations together bit for bit
+template <int VERSION, bool SAVE = false>
+__global__ __launch_bounds__(256, 2) void gf_refine_mlp_kernel(std::conditional_t<SAVE, RefineMlpTrainArgs, RefineMlpArgs> a)
 {
     __shared__ float4 s_w[2][kRmE * kRowPitch4];
     __shared__ float4 s_vec[kRmTail4 + 32];
@@ -133,8 +145,26 @@ __global__ __launch_bounds__(256, 2) void gf_refine_mlp_kernel(RefineMlpArgs a)
             __syncthreads();
         }
         const float4 *p = s_vec + 32 * (4 * (q >> 1) + (q & 1));
-        if (q & 1) relu_ln<false>(acc, p, h);      // layers.2 -> .3 -> .4, layers.7 -> .8 -> .9
-        else bias_relu(acc, p, h);                 // layers.0 -> .1,       layers.5 -> .6
+        if constexpr (SAVE) {
+            // the stage's post-ReLU row [q][row][128]; a row past n stores nothing
+            float *rrow = row0 + j < n ? a.sv_rows + ((size_t)q * n + row) * kRmE : nullptr;
+            if (q & 1) {
+                relu_ln<true>(acc, p, h, rrow, a.sv_stat + ((size_t)(q >> 1) * n + row) * 2);
+            } else {
+                bias_relu(acc, p, h);
+                if (rrow) {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+#pragma unroll
+                        for (int m = 0; m < 4; ++m)
+                            *reinterpret_cast<float4 *>(rrow + 32 * b + 8 * m + 4 * h) =
+                                make_float4(acc[b][4 * m], acc[b][4 * m + 1], acc[b][4 * m + 2], acc[b][4 * m + 3]);
+                }
+            }
+        } else {
+            if (q & 1) relu_ln<false>(acc, p, h);      // layers.2 -> .3 -> .4, layers.7 -> .8 -> .9
+            else bias_relu(acc, p, h);                 // layers.0 -> .1,       layers.5 -> .6
+        }
 #pragma unroll
         for (int b = 0; b < 4; ++b) x[b] = acc[b];
     }
@@ -160,8 +190,18 @@ __global__ __launch_bounds__(256, 2) void gf_refine_mlp_kernel(RefineMlpArgs a)
             for (int m = 0; m < 4; ++m) {
                 const float4 bb = pb[8 * b + 2 * m + h], ss = ps[8 * b + 2 * m + h];
                 const float bv[4] = {bb.x, bb.y, bb.z, bb.w}, sv[4] = {ss.x, ss.y, ss.z, ss.w};
+                if constexpr (SAVE) {     // the value before Scale, to its row (features from D on: 0, as the weight and bias are)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) y[b][4 * m + i] = (y[b][4 * m + i] + bv[i]) * sv[i];
+                    for (int i = 0; i < 4; ++i) y[b][4 * m + i] = y[b][4 * m + i] + bv[i];
+                    if (row0 + j < n)
+                        *reinterpret_cast<float4 *>(a.sv_y + row * kRmYPitch + 32 * b + 8 * m + 4 * h) =
+                            make_float4(y[b][4 * m], y[b][4 * m + 1], y[b][4 * m + 2], y[b][4 * m + 3]);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) y[b][4 * m + i] = y[b][4 * m + i] * sv[i];
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) y[b][4 * m + i] = (y[b][4 * m + i] + bv[i]) * sv[i];
+                }
             }
     }
 
@@ -186,6 +226,7 @@ __global__ __launch_bounds__(256, 2) void gf_refine_mlp_kernel(RefineMlpArgs a)
         __syncthreads();
         if (mine) {
             if (a.mlp_out) tile_store(a.mlp_out, first, t_o, po, 0, D, D, rows);
+            if constexpr (SAVE) tile_store(a.sv_o, first, t_o, po, 0, D, D, rows);
             if (l < rows) refine_row_forward<VERSION>(a.r, t_o + l * po, t_a + l * pa, t_n + l * pn);
         }
         __syncthreads();
@@ -194,45 +235,29 @@ __global__ __launch_bounds__(256, 2) void gf_refine_mlp_kernel(RefineMlpArgs a)
     }
 }
 
-static const char *const kRmName[GF_REFINE_MLP_PARAMS] = {
-    "layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias", "layers.4.weight", "layers.4.bias", "layers.5.weight", "layers.5.bias",
-    "layers.7.weight", "layers.7.bias", "layers.9.weight", "layers.9.bias", "layers.10.weight", "layers.10.bias", "layers.11.scale"};
-
-}  // namespace gf
-
-#define GF_RM_REFUSE(cond, fmt, ...)                                   \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            gf::set_error("%s: " fmt, __func__, ##__VA_ARGS__);        \
-            return GF_EINVAL;                                          \
-        }                                                              \
-    } while (0)
-
-extern "C" int gf_refine_mlp_forward(int n, int E, int D, int Da, int version, int flags, int R, int S, const double *consts,
-                                     const float *instance_feature, const float *anchor_embed, const float *anchor,
-                                     const void *const *params, float *mlp_out, float *anchor_out, float *means, float *scales,
-                                     float *rotations, float *opacities, float *semantics, float *original_means, float *delta_means,
-                                     void *stream_)
+// Both forwards: the checks in one order under the name of the entry point that was called, then the plain kernel (saved
+// null) or the saving one
+static int refine_mlp_run(const char *fn, int n, int E, int D, int Da, int version, int flags, int R, int S, const double *consts,
+                          const float *instance_feature, const float *anchor_embed, const float *anchor, const void *const *params,
+                          float *mlp_out, float *anchor_out, float *means, float *scales, float *rotations, float *opacities,
+                          float *semantics, float *original_means, float *delta_means, bool train, void *saved, size_t saved_bytes,
+                          hipStream_t stream)
 {
-    using namespace gf;
-    RefineMlpArgs a{};
-    if (int rc = refine_fill_args(a.r, __func__, n, D, Da, version, flags, R, S, consts)) return rc;
+    RefineMlpTrainArgs a{};
+    if (int rc = refine_fill_args(a.r, fn, n, D, Da, version, flags, R, S, consts)) return rc;
     GF_RM_REFUSE(E == kRmE, "E = %d: only embed_dims = 128 is supported", E);
     if (n == 0) return GF_OK;
-    auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-    GF_RM_REFUSE(params, "null params");
-    const float *const *p = reinterpret_cast<const float *const *>(params);
-    for (int i = 0; i < GF_REFINE_MLP_PARAMS; ++i) {
-        GF_RM_REFUSE(p[i], "params[%d] (%s) is null", i, kRmName[i]);
-        GF_RM_REFUSE(!misaligned(p[i]), "params[%d] (%s) = %p is not 16-byte aligned", i, kRmName[i], (const void *)p[i]);
+    if (int rc = refine_mlp_check_inputs(fn, params, instance_feature, anchor_embed, anchor)) return rc;
+    GF_CHECK_ARG_AS(fn, refine_forward_outputs_present(version, flags, S, anchor_out, means, scales, rotations, opacities, semantics, original_means, delta_means),
+                    "null pointer");
+    if (train) {
+        GF_RM_REFUSE(saved, "saved is null");
+        GF_RM_REFUSE(!rm_misaligned(saved), "saved = %p is not 16-byte aligned", saved);
+        const RefineMlpSaved sv = refine_mlp_carve_saved(saved, n, D);
+        GF_CHECK_WORKSPACE_AS(fn, "saved", saved_bytes, sv.bytes);
+        a.sv_rows = sv.rows; a.sv_stat = sv.stat; a.sv_y = sv.y; a.sv_o = sv.o;
     }
-    GF_RM_REFUSE(instance_feature, "null instance_feature");
-    GF_RM_REFUSE(anchor_embed, "null anchor_embed");
-    GF_RM_REFUSE(anchor, "null anchor");
-    GF_RM_REFUSE(!misaligned(instance_feature), "instance_feature = %p is not 16-byte aligned", (const void *)instance_feature);
-    GF_RM_REFUSE(!misaligned(anchor_embed), "anchor_embed = %p is not 16-byte aligned", (const void *)anchor_embed);
-    GF_CHECK_ARG(refine_forward_outputs_present(version, flags, S, anchor_out, means, scales, rotations, opacities, semantics, original_means, delta_means),
-                 "null pointer");
+    const float *const *p = reinterpret_cast<const float *const *>(params);
     a.feat = instance_feature; a.embed = anchor_embed; a.mlp_out = mlp_out;
     a.r.anchor = anchor; a.r.anchor_out = anchor_out; a.r.means = means; a.r.scales = scales; a.r.rotations = rotations;
     a.r.opacities = opacities; a.r.semantics = semantics; a.r.original_means = original_means; a.r.delta_means = delta_means;
@@ -242,8 +267,38 @@ extern "C" int gf_refine_mlp_forward(int n, int E, int D, int Da, int version, i
     a.b10 = p[13]; a.scale = p[14];
     a.wpp = a.r.po + a.r.pa + a.r.pn <= kRmFitAll ? 4 : 2;
     const dim3 grid((n + kRowTile - 1) / kRowTile), block(256);
-    if (version == 1) hipLaunchKernelGGL(gf_refine_mlp_kernel<1>, grid, block, 0, (hipStream_t)stream_, a);
-    else hipLaunchKernelGGL(gf_refine_mlp_kernel<2>, grid, block, 0, (hipStream_t)stream_, a);
-    GF_CHECK_LAUNCH();
+    const RefineMlpArgs &plain = a;
+    if (train) {
+        if (version == 1) hipLaunchKernelGGL((gf_refine_mlp_kernel<1, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((gf_refine_mlp_kernel<2, true>), grid, block, 0, stream, a);
+    } else {
+        if (version == 1) hipLaunchKernelGGL((gf_refine_mlp_kernel<1, false>), grid, block, 0, stream, plain);
+        else hipLaunchKernelGGL((gf_refine_mlp_kernel<2, false>), grid, block, 0, stream, plain);
+    }
+    GF_CHECK_LAUNCH_AS(fn);
     return GF_OK;
+}
+
+}  // namespace gf
+
+extern "C" int gf_refine_mlp_forward(int n, int E, int D, int Da, int version, int flags, int R, int S, const double *consts,
+                                     const float *instance_feature, const float *anchor_embed, const float *anchor,
+                                     const void *const *params, float *mlp_out, float *anchor_out, float *means, float *scales,
+                                     float *rotations, float *opacities, float *semantics, float *original_means, float *delta_means,
+                                     void *stream_)
+{
+    return gf::refine_mlp_run(__func__, n, E, D, Da, version, flags, R, S, consts, instance_feature, anchor_embed, anchor, params, mlp_out,
+                              anchor_out, means, scales, rotations, opacities, semantics, original_means, delta_means, false, nullptr, 0,
+                              (hipStream_t)stream_);
+}
+
+extern "C" int gf_refine_mlp_forward_train(int n, int E, int D, int Da, int version, int flags, int R, int S, const double *consts,
+                                           const float *instance_feature, const float *anchor_embed, const float *anchor,
+                                           const void *const *params, float *mlp_out, float *anchor_out, float *means, float *scales,
+                                           float *rotations, float *opacities, float *semantics, float *original_means,
+                                           float *delta_means, void *saved, size_t saved_bytes, void *stream_)
+{
+    return gf::refine_mlp_run(__func__, n, E, D, Da, version, flags, R, S, consts, instance_feature, anchor_embed, anchor, params, mlp_out,
+                              anchor_out, means, scales, rotations, opacities, semantics, original_means, delta_means, true, saved,
+                              saved_bytes, (hipStream_t)stream_);
 }

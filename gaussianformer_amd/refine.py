@@ -3,7 +3,8 @@
 (refine_module_v2.py:12-108).  By default the MLP (``layers``) stays torch; everything after it -- the 30-40 slices, stacks,
 cats, clamps, sigmoids and logs of :72-123 / v2 :62-107 -- is ``gf_refine_forward`` / ``gf_refine_backward``
 (include/gf_hip.h): one launch each way.  ``refine_fused`` (and the modules with ``fused_mlp = True``, inference only) runs the
-MLP and the tail in one launch, ``gf_refine_mlp_forward``."""
+MLP and the tail in one launch, ``gf_refine_mlp_forward``.  ``refine_fused_autograd`` (and the modules with
+``native_training = True``) is the native training step: ``gf_refine_mlp_forward_train`` / ``gf_refine_mlp_backward``."""
 import ctypes
 from collections import namedtuple
 from typing import NamedTuple
@@ -122,7 +123,7 @@ def refine_fused(instance_feature, anchor, anchor_embed, module_or_state_dict, c
     _lib.require_gpu(instance_feature, anchor, anchor_embed, *params)
     lead, E = instance_feature.shape[:-1], instance_feature.shape[-1]
     f = _lib.as_arg(instance_feature).reshape(-1, E)
-    e = _lib.as_arg(anchor_embed).expand(*lead, E).reshape(-1, E)
+    e = _lib.as_arg(anchor_embed).expand(*lead, E).reshape(-1, E).contiguous()   # (a broadcast one: its rows written out)
     a = _lib.as_arg(anchor).reshape(-1, anchor.shape[-1])
     params = [_lib.as_arg(t) for t in params]
     n, Da, D = f.shape[0], a.shape[1], params[12].shape[0]
@@ -151,6 +152,102 @@ def refine_fused(instance_feature, anchor, anchor_embed, module_or_state_dict, c
     return outs[0], pred
 
 
+def train_sizes(n, D, Da):
+    """``(saved_bytes, workspace_bytes)`` of the native training step on ``n`` rows (``gf_refine_mlp_train_sizes``)."""
+    saved, work = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(_lib.load().gf_refine_mlp_train_sizes(n, D, Da, ctypes.addressof(saved), ctypes.addressof(work)),
+               "gf_refine_mlp_train_sizes")
+    return saved.value, work.value
+
+
+_train_scratch = _lib.StreamScratch()   # the backward's workspace (one chunk's dz rows, the partial sums)
+
+
+class RefineFusedFunction(Function):
+    """``anchor_out, means, scales, rotations, opacities, semantics, original_means, delta_means =
+    apply(instance_feature [..., 128], anchor [..., Da], anchor_embed (broadcastable to instance_feature), cfg, *params)`` on
+    the 15 parameters in ``MLP_KEYS`` order: ``gf_refine_mlp_forward_train`` keeps the four post-ReLU rows, the LayerNorms'
+    statistics and the MLP's result, ``gf_refine_mlp_backward`` returns the gradients of the three inputs and of every
+    parameter that requires one.  The outputs carry the leading shape; the last two are empty in version 1.
+    Once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, instance_feature, anchor, anchor_embed, cfg, *params):
+        _lib.require_gpu(instance_feature, anchor, anchor_embed, *params)
+        ctx.set_materialize_grads(False)   # an unused output's gradient reaches the library as NULL, not as a tensor of zeros
+        lead, E = instance_feature.shape[:-1], instance_feature.shape[-1]
+        f = _lib.as_arg(instance_feature).reshape(-1, E)
+        e = _lib.as_arg(anchor_embed).expand(*lead, E).reshape(-1, E).contiguous()   # (a broadcast one: its rows written out)
+        a = _lib.as_arg(anchor).reshape(-1, anchor.shape[-1])
+        held = [_lib.as_arg(t) for t in params]
+        n, Da, D = f.shape[0], a.shape[1], held[12].shape[0]
+        if a.shape[0] != n:
+            raise ValueError(f"instance_feature has {n} rows, anchor {a.shape[0]}")
+        shapes = [(E, E), (E,), (E, E), (E,), (E,), (E,)] * 2 + [(D, E), (D,), (D,)]
+        for k, t, want in zip(MLP_KEYS, held, shapes):
+            if tuple(t.shape) != want:
+                raise ValueError(f"{k} has shape {tuple(t.shape)}, expected {want}")
+        opa = 1 if cfg.flags & _lib.GF_REFINE_OPACITY else 0
+
+        def new(w):
+            return torch.empty(n, w, dtype=f32, device=f.device)
+
+        three = 3 if cfg.version == 2 else 0
+        outs = (new(D), new(3), new(3), new(4), new(opa), new(cfg.S), new(three), new(three))
+        saved_bytes, _ = train_sizes(n, D, Da)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=f.device)
+        consts = (ctypes.c_double * 11)(*cfg.consts)
+        table = (ctypes.c_void_p * _lib.GF_REFINE_MLP_PARAMS)(*[t.data_ptr() for t in held])
+        ctx.call = (n, E, D, Da, cfg.version, cfg.flags, cfg.R, cfg.S, consts)
+        _lib.call("gf_refine_mlp_forward_train", f.device, *ctx.call[:8], ctypes.cast(consts, ctypes.c_void_p),
+                  f, e, a, ctypes.cast(table, ctypes.c_void_p), None, *outs, saved, saved_bytes)
+        ctx.save_for_backward(f, e, a, saved, *held)
+        ctx.shape = (lead, tuple(anchor_embed.shape), instance_feature.dtype, anchor.dtype, anchor_embed.dtype,
+                     [t.dtype for t in params])
+        return tuple(t.view(*lead, t.shape[-1]) for t in outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        f, e, a, saved, *held = ctx.saved_tensors
+        n, E, D, Da, version, flags, R, S, consts = ctx.call
+        lead, embed_shape, f_dtype, a_dtype, e_dtype, dtypes = ctx.shape
+        g = [None if t is None or t.numel() == 0 else _lib.as_arg(t).reshape(n, t.shape[-1]) for t in grads]
+        grad_x = torch.empty(n, E, dtype=f32, device=f.device)
+        grad_anchor = torch.empty(n, Da, dtype=f32, device=f.device)
+        grad_params = [torch.empty_like(t) for t in held]
+        table = (ctypes.c_void_p * _lib.GF_REFINE_MLP_PARAMS)(*[t.data_ptr() for t in held])
+        out_table = (ctypes.c_void_p * _lib.GF_REFINE_MLP_PARAMS)(*[t.data_ptr() for t in grad_params])
+        _, work_bytes = train_sizes(n, D, Da)
+        work = _train_scratch.get(f.device, work_bytes)
+        _lib.call("gf_refine_mlp_backward", f.device, n, E, D, Da, version, flags, R, S, ctypes.cast(consts, ctypes.c_void_p),
+                  f, e, a, ctypes.cast(table, ctypes.c_void_p), saved, *g, grad_x, grad_anchor, None,
+                  ctypes.cast(out_table, ctypes.c_void_p), work, work_bytes)
+        need = ctx.needs_input_grad
+        gx = grad_x.view(*lead, E)
+        return (gx.to(f_dtype) if need[0] else None,
+                grad_anchor.view(*lead, Da).to(a_dtype) if need[1] else None,
+                gx.sum_to_size(embed_shape).to(e_dtype) if need[2] else None, None,
+                *[t.to(d) if need[4 + i] else None for i, (t, d) in enumerate(zip(grad_params, dtypes))])
+
+
+def refine_fused_autograd(instance_feature, anchor, anchor_embed, module_or_state_dict, cfg):
+    """``refine_fused`` with a native backward (``RefineFusedFunction``), on any leading batch shape: ``(anchor_out [..., D],
+    GaussianPrediction)`` carrying the graph, so the three inputs and every parameter that requires grad receive their
+    gradients (the others ``None``); a broadcast ``anchor_embed`` gets its gradient summed to its shape.  With nothing that
+    needs autograd (or under ``torch.no_grad()``) it is ``refine_fused``."""
+    state = module_or_state_dict
+    if isinstance(state, nn.Module):
+        state = dict(state.named_parameters())
+    params = [state[k] for k in MLP_KEYS]
+    _lib.require_gpu(instance_feature, anchor, anchor_embed, *params)
+    if not _needs_grad((instance_feature, anchor, anchor_embed, *params)):
+        return refine_fused(instance_feature, anchor, anchor_embed, state, cfg)
+    outs = RefineFusedFunction.apply(instance_feature, anchor, anchor_embed, cfg, *params)
+    pred = GaussianPrediction(*outs[1:6]) if cfg.version == 1 else GaussianPrediction(*outs[1:8])
+    return outs[0], pred
+
+
 class Scale(nn.Module):
     """One learnable factor per column, all ones at first: the parameter ``scale [width]`` that mmcv's ``Scale`` holds when the
     reference builds it from a list."""
@@ -176,8 +273,11 @@ def refinement_mlp(embed_dims, output_dim):
 class _Refinement(nn.Module):
     """What the two drop-ins share: the torch MLP, then one library call.  ``fused_mlp`` (an attribute, not a constructor key and
     not in the state_dict; off by default): when set, a call that needs no gradient, at ``embed_dims`` 128 on fp32 GPU tensors,
-    is one launch (``refine_fused``); every other call takes the default route."""
+    is one launch (``refine_fused``); every other call takes the default route.  ``native_training`` (an attribute of the same
+    kind, off by default): when set, a call that needs autograd, under the same conditions, is ``refine_fused_autograd`` -- the
+    saving forward and the native backward -- instead of the torch layers and ``refine``."""
     fused_mlp = False
+    native_training = False
 
     def __init__(self, version, where, embed_dims, pc_range, scale_range, unit, restrict_xyz, refine_manual, semantics,
                  semantic_dim, include_opa, semantics_activation, xyz_activation, scale_activation):
@@ -200,9 +300,16 @@ class _Refinement(nn.Module):
         return (self.fused_mlp and self.embed_dims == 128 and not _needs_grad(tensors)
                 and all(t.is_cuda and t.dtype == f32 for t in tensors))
 
+    def _takes_native_training(self, instance_feature, anchor, anchor_embed):
+        tensors = (instance_feature, anchor, anchor_embed, *self.layers.parameters())
+        return (self.native_training and self.embed_dims == 128 and _needs_grad(tensors)
+                and all(t.is_cuda and t.dtype == f32 for t in tensors))
+
     def forward(self, instance_feature, anchor, anchor_embed):
         if self._takes_fused(instance_feature, anchor, anchor_embed):
             return refine_fused(instance_feature, anchor, anchor_embed, self, self._cfg)
+        if self._takes_native_training(instance_feature, anchor, anchor_embed):
+            return refine_fused_autograd(instance_feature, anchor, anchor_embed, self, self._cfg)
         return refine(self.layers(instance_feature + anchor_embed), anchor, self._cfg)
 
 

@@ -789,6 +789,56 @@ int gf_refine_mlp_forward(int n, int E, int D, int Da, int version, int flags, i
                           float *anchor_out, float *means, float *scales, float *rotations, float *opacities,
                           float *semantics, float *original_means, float *delta_means, void *stream);
 
+/* The refinement modules' training step: a forward that also keeps what the backward needs, and the backward
+ * of the MLP and the tail together.
+ *
+ * gf_refine_mlp_train_sizes: host code; the bytes of the two caller-allocated regions for n rows (both 0 for n == 0, both
+ * monotone in n).  GF_EINVAL for n < 0, a D outside 10 .. 43, a negative Da or a null result pointer.
+ *
+ * gf_refine_mlp_forward_train: gf_refine_mlp_forward's arguments and refusals, and every output, mlp_out included, has its bits;
+ * it also fills `saved` (opaque, 16-byte aligned, at least saved_bytes of the query; GF_EINVAL when null or misaligned,
+ * GF_EWORKSPACE when shorter): the four post-ReLU rows, the two LayerNorms' (mean, rstd), the last Linear's result before Scale
+ * and o.  The input sum is not saved (the backward forms it again from the two inputs); the value before Scale is (it is not
+ * recovered as o / scale: a scale entry may be 0).
+ *
+ * gf_refine_mlp_backward: the gradients of that forward.  instance_feature, anchor_embed, anchor, params, version, flags, R, S
+ * and consts as given to the forward, saved as it left it; the eight grad_* of the tail's outputs as gf_refine_backward takes
+ * them, each may be NULL (= zero).
+ *   grad_x        f32 [n, 128], 16-byte aligned, written in full: the gradient of instance_feature + anchor_embed, which the
+ *                 caller gives to both inputs
+ *   grad_anchor   f32 [n, Da], written in full; zero beyond the first R (version 1) or 3 (version 2) columns, exactly as
+ *                 gf_refine_backward leaves it
+ *   grad_mlp_out  f32 [n, D] or NULL: the gradient with respect to o that the MLP's backward consumed, the bits
+ *                 gf_refine_backward gives on (mlp_out, anchor, the same output gradients)
+ *   grad_params   HOST table of GF_REFINE_MLP_PARAMS device pointers laid out like params, each tensor of its parameter's
+ *                 shape; every gradient is STORED, not accumulated (the caller zeroes nothing); a NULL entry is refused
+ *   workspace     16-byte aligned scratch of at least workspace_bytes of the query
+ * No atomics: every sum over rows runs in a fixed order (per tile of 128 rows and per block of GF_REFINE_MLP_WGRAD_ROWS rows,
+ * then one sum over the tiles and blocks), so two calls agree bit for bit; a row of grad_x, grad_anchor and grad_mlp_out does
+ * not depend on n or on the row's position.  The rows are walked in chunks of GF_REFINE_MLP_CHUNK_ROWS, one after the other on
+ * the stream, so the workspace holds one chunk's intermediate rows.  Nothing is loaded from beyond a tensor; no host
+ * synchronisation, no allocation: graph-capturable.  n == 0 returns GF_OK without looking at the data pointers, the 15
+ * parameter gradients zero-filled.  GF_EINVAL before any HIP call, the message naming the offending value: everything
+ * gf_refine_mlp_forward refuses (the same messages), a null entry of grad_params, a null or misaligned saved, workspace or
+ * grad_x, a null grad_anchor; GF_EWORKSPACE for a workspace shorter than the query's. */
+#define GF_REFINE_MLP_WGRAD_ROWS 512
+#define GF_REFINE_MLP_CHUNK_ROWS 32768
+int gf_refine_mlp_train_sizes(int n, int D, int Da, size_t *saved_bytes, size_t *workspace_bytes);
+int gf_refine_mlp_forward_train(int n, int E, int D, int Da, int version, int flags, int R, int S, const double *consts,
+                                const float *instance_feature, const float *anchor_embed, const float *anchor,
+                                const void *const *params, float *mlp_out,
+                                float *anchor_out, float *means, float *scales, float *rotations, float *opacities,
+                                float *semantics, float *original_means, float *delta_means,
+                                void *saved, size_t saved_bytes, void *stream);
+int gf_refine_mlp_backward(int n, int E, int D, int Da, int version, int flags, int R, int S, const double *consts,
+                           const float *instance_feature, const float *anchor_embed, const float *anchor,
+                           const void *const *params, const void *saved,
+                           const float *grad_anchor_out, const float *grad_means, const float *grad_scales,
+                           const float *grad_rotations, const float *grad_opacities, const float *grad_semantics,
+                           const float *grad_original_means, const float *grad_delta_means,
+                           float *grad_x, float *grad_anchor, float *grad_mlp_out, void *const *grad_params,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the anchor encoder ---------------------------------------------------------------------------------------------------
  * Replaces SparseGaussian3DEncoder.forward (model/encoder/gaussian_encoder/anchor_encoder_module.py:38-53; its layers are
  * linear_relu_ln(embed_dims, 1, 2, input_dims), utils.py:49-59): one launch instead of about 40 torch kernels, DESIGN.md
