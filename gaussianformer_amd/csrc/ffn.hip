@@ -177,32 +177,8 @@ __global__ __launch_bounds__(256) void gf_ffn_rows32_kernel(FfnArgs a)
             sum += v[i];
         }
     }
-    if (a.post_g) {   // ln_rows<true, 4> with the four blocks' sums met in LDS
-        auto total = [&](int which, float mine) {
-            s_sum[which][wv][l] = mine;
-            __syncthreads();
-            const float part[4] = {s_sum[which][0][l], s_sum[which][1][l], s_sum[which][2][l], s_sum[which][3][l]};
-            return wave_xor_reduce_strided(tree_sum<4>(part), 32, Sum()) * (1.f / kFfnE);
-        };
-        const float mean = total(0, sum);
-        float sq = 0.f, d0 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float d = y[r] - mean;
-            y[r] = d;
-            if (r == 0) d0 = d;
-            else if (r == 1) sq = __builtin_fmaf(d0, d0, d * d);
-            else sq = __builtin_fmaf(d, d, sq);
-        }
-        const float rstd = 1.f / sqrtf(total(1, sq) + kRowLnEps);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float4 gg = s_vec[vPost + 8 * wv + 2 * m + h], ee = s_vec[vPost + 32 + 8 * wv + 2 * m + h];
-            const float gv[4] = {gg.x, gg.y, gg.z, gg.w}, ev[4] = {ee.x, ee.y, ee.z, ee.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) y[4 * m + i] = __builtin_fmaf(y[4 * m + i] * rstd, gv[i], ev[i]);
-        }
-    }
+    if (a.post_g)   // ln_rows<true, 4> with the four blocks' sums met in LDS
+        ln_rows_split(y, sum, s_sum, wv, l, [&](int which, int m) { return s_vec[vPost + 32 * which + 8 * wv + 2 * m + h]; });
     if (row0 + j < a.n) {
         float *orow = a.out + (size_t)(row0 + j) * kFfnE + 32 * wv + 4 * h;
 #pragma unroll

@@ -1,5 +1,5 @@
-// gf_rows.hpp -- what the row-wise MFMA kernels share (anchor_embed.hip, ffn.hip, refine_mlp.hip, refine_mlp_train.hip;
-// DESIGN.md §3.12b, §3.12c, §3.13, §3.13c): the register layout in which a wave holds 32 rows of 128-feature blocks, the LayerNorm on it, the staging of a
+// gf_rows.hpp -- what the row-wise MFMA kernels share (anchor_embed.hip, ffn.hip, refine_mlp.hip, refine_mlp_train.hip, deform_dense.hip;
+// DESIGN.md §3.12b, §3.12c, §3.13, §3.13c, §3.13e): the register layout in which a wave holds 32 rows of 128-feature blocks, the LayerNorm on it, the staging of a
 // weight chunk through LDS, the chunk's 64 MFMAs and the store of a finished tile.
 //
 // The layout.  A workgroup of four waves owns 128 rows, a wave 32 of them.  Every product is Y^T = W X^T on
@@ -76,6 +76,39 @@ __device__ __forceinline__ void ln_rows(f32x16 (&v)[NB], float lane_sum, const f
     }
 }
 
+// ln_rows<true, 4> of a row whose four blocks are held by the four waves of a workgroup, one each (the 32-row kernels): y is
+// wave wv's block, lane_sum the lane's sum of it; the four blocks' sums meet in s_sum, so every wave of the workgroup calls it
+// together (it holds barriers).  vec(which, m): the float4 of the LayerNorm's weight (which = 0) or bias (1) at the lane's
+// features 32 wv + 8 m + 4 h .., from wherever the caller keeps them.  The same bits as ln_rows<true, 4> on the whole row
+template <class Vec>
+__device__ __forceinline__ void ln_rows_split(f32x16 &y, float lane_sum, float (&s_sum)[2][4][64], int wv, int l, Vec &&vec)
+{
+    auto total = [&](int which, float mine) {
+        s_sum[which][wv][l] = mine;
+        __syncthreads();
+        const float part[4] = {s_sum[which][0][l], s_sum[which][1][l], s_sum[which][2][l], s_sum[which][3][l]};
+        return wave_xor_reduce_strided(tree_sum<4>(part), 32, Sum()) * (1.f / 128);
+    };
+    const float mean = total(0, lane_sum);
+    float sq = 0.f, d0 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float d = y[r] - mean;
+        y[r] = d;
+        if (r == 0) d0 = d;
+        else if (r == 1) sq = __builtin_fmaf(d0, d0, d * d);
+        else sq = __builtin_fmaf(d, d, sq);
+    }
+    const float rstd = 1.f / sqrtf(total(1, sq) + kRowLnEps);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const float4 gg = vec(0, m), ee = vec(1, m);
+        const float gv[4] = {gg.x, gg.y, gg.z, gg.w}, ev[4] = {ee.x, ee.y, ee.z, ee.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[4 * m + i] = __builtin_fmaf(y[4 * m + i] * rstd, gv[i], ev[i]);
+    }
+}
+
 // v <- LayerNorm(relu(v + bias)) over the 128 features of the lane's row (biased variance, two passes); p: the stage's
 // three vectors in LDS (32 float4 each: bias, LayerNorm weight, LayerNorm bias).  SAVE: the lane also stores its 64 post-ReLU
 // values to rrow (its row of the stage's saved rows, null for a row past n) as float4s from the registers, and (mean, rstd)
@@ -117,6 +150,15 @@ __device__ __forceinline__ void chunk_fetch(float4 (&pre)[4], const float *w, si
     const int ff = t >> 3, fq = t & 7;
 #pragma unroll
     for (int i = 0; i < 4; ++i) pre[i] = ld4(w + (size_t)(ff + 32 * i) * ld + col0 + 4 * fq);
+}
+// ... of a matrix that has only `rows` rows from w on (any number, <= 0 included): a row past them is staged as zeros and
+// never loaded
+__device__ __forceinline__ void chunk_fetch_rows(float4 (&pre)[4], const float *w, size_t ld, int col0, int t, int rows)
+{
+    const int ff = t >> 3, fq = t & 7;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        pre[i] = ff + 32 * i < rows ? ld4(w + (size_t)(ff + 32 * i) * ld + col0 + 4 * fq) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 __device__ __forceinline__ void chunk_stash(float4 *buf, const float4 (&pre)[4], int t)
 {
@@ -168,5 +210,45 @@ __device__ __forceinline__ void store_rows(float *so, const f32x16 (&x)[4], floa
     }
 }
 static_assert(4 * 32 * kRowOutPitch <= 2 * 128 * kRowPitch4 * 4, "the output staging tiles fit the two weight buffers");
+
+// store_rows for NFB <= 4 blocks and a matrix of `pitch` floats per row: the first ncols (a multiple of 4, <= 32 NFB) of the
+// blocks' features go to columns col0 .. col0 + ncols of out's rows; nothing else is written
+template <int NFB>
+__device__ __forceinline__ void store_cols(float *so, const f32x16 (&x)[NFB], float *out, size_t pitch, int col0, int ncols, int row0, int n,
+                                           int l, int j, int h)
+{
+#pragma unroll
+    for (int half = 0; half < (NFB + 1) / 2; ++half) {
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb) {
+            if (2 * half + bb >= NFB) continue;
+            const f32x16 &v = x[2 * half + bb < NFB ? 2 * half + bb : 0];
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+                *reinterpret_cast<float4 *>(so + j * kRowOutPitch + 32 * bb + 8 * m + 4 * h) =
+                    make_float4(v[4 * m], v[4 * m + 1], v[4 * m + 2], v[4 * m + 3]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int r = 4 * i + (l >> 4), col = 64 * half + 4 * (l & 15);
+            const float4 v = *reinterpret_cast<const float4 *>(so + r * kRowOutPitch + 4 * (l & 15));
+            if (row0 + r < n && col < ncols) *reinterpret_cast<float4 *>(out + (size_t)(row0 + r) * pitch + col0 + col) = v;
+        }
+        __syncthreads();
+    }
+}
+
+// x <- the lane's 64 features of the row at xrow (128 floats, 16-byte aligned), in the layout above
+__device__ __forceinline__ void load_row(f32x16 (&x)[4], const float *xrow, int h)
+{
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const float4 v = ld4(xrow + 32 * b + 8 * m + 4 * h);
+            x[b][4 * m] = v.x; x[b][4 * m + 1] = v.y; x[b][4 * m + 2] = v.z; x[b][4 * m + 3] = v.w;
+        }
+}
 
 }  // namespace gf

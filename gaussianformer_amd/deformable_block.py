@@ -1,0 +1,244 @@
+"""The deformable block: drop-in for ``DeformableFeatureAggregation`` (model/encoder/gaussian_encoder/deformable_module.py:
+93-262) and the native form of its dense ends.  The middle of the block was native already (``key_points``,
+``deformable_fused_forward`` / ``deformable_fused``); its ends ran as torch layers wherever the block was assembled:
+``kps_generator.learnable_fc`` and ``weights_fc`` on ``instance_feature + anchor_embed`` before the sampling, ``output_proj``
+with the add or the cat behind it.  ``gf_deform_logits_forward`` and ``gf_deform_output_forward`` (include/gf_hip.h, DESIGN.md
+§3.13e) are one launch each: an inference block is four launches and the ``[A, 128]`` sum never reaches memory.  Forward only:
+training, dropout and everything the native ops do not cover run the module's own torch layers around ``deformable_fused``."""
+import ctypes
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+from .deformable_aggregation import DeformableAggregationFunction as DAF
+from .deformable_prepare import deformable_fused, deformable_fused_forward
+from .key_points import SparseGaussian3DKeyPointsGenerator, key_points
+
+f32 = torch.float32
+E_NATIVE, MAX_LEARNED = _lib.GF_DEFORM_EMBED_DIMS, _lib.GF_DEFORM_MAX_LEARNED
+MODES = {"none": _lib.GF_DEFORM_NONE, "add": _lib.GF_DEFORM_ADD, "cat": _lib.GF_DEFORM_CAT}
+
+
+def _pair(layer, what, affine=nn.Linear):
+    """``(weight, bias)`` of a module or of a pair; ``(None, None)`` for ``None``."""
+    if layer is None:
+        return None, None
+    if isinstance(layer, nn.Module):
+        if not isinstance(layer, affine) or layer.weight is None or layer.bias is None:
+            raise ValueError(f"{what} is a {type(layer).__name__} without weight and bias, not an {affine.__name__} with both")
+        if affine is nn.LayerNorm and layer.eps != 1e-5:
+            raise ValueError(f"{what}: the post norm must be a LayerNorm with eps = 1e-5")
+        return layer.weight, layer.bias
+    weight, bias = layer
+    return weight, bias
+
+
+def _needs_grad(tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _aligned(t):
+    t = _lib.as_arg(t)
+    return t.clone() if t is not None and t.data_ptr() % 16 else t
+
+
+def _table(params):
+    """The library's host table of pointers, and the tensors it points into (kept alive until the launch is queued)."""
+    table = (ctypes.c_void_p * len(params))()
+    held = [_aligned(p) for p in params]
+    for i, p in enumerate(held):
+        if p is not None:
+            table[i] = p.data_ptr()
+    return ctypes.cast(table, ctypes.c_void_p), held
+
+
+def _refuse_autograd(name, tensors):
+    if _needs_grad(tensors):
+        raise RuntimeError(
+            f"{name} is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters that "
+            "do not require grad (the DeformableFeatureAggregation module routes training to its torch layers around "
+            "deformable_fused)")
+
+
+def deformable_logits(instance_feature, anchor_embed, weights_fc, learnable_fc=None):
+    """``(raw [..., Nw], learned [..., K, 3] | None)`` in one launch, on any leading shape: ``raw = weights_fc(instance_feature +
+    anchor_embed)`` (deformable_module.py:250-262; ``anchor_embed`` may be ``None``) and ``learned = learnable_fc(
+    instance_feature)`` (:59-63) as ``key_points`` takes it.  ``weights_fc`` / ``learnable_fc``: an ``nn.Linear`` or a ``(weight,
+    bias)`` pair, read in place at every call.  Forward only: inputs that need autograd are refused."""
+    ww, bw = _pair(weights_fc, "weights_fc")
+    wl, bl = _pair(learnable_fc, "learnable_fc")
+    _refuse_autograd("deformable_logits", [instance_feature, anchor_embed, ww, bw, wl, bl])
+    _lib.require_gpu(instance_feature, anchor_embed, ww, bw, wl, bl)
+    E = instance_feature.shape[-1]
+    Nw, K3 = ww.shape[0], 0 if wl is None else wl.shape[0]
+    if ww.shape != (Nw, E) or bw.shape != (Nw,) or (wl is not None and (wl.shape != (K3, E) or bl.shape != (K3,) or K3 % 3)):
+        raise ValueError(f"deformable_logits: instance_feature [..., {E}] against weights_fc {tuple(ww.shape)}, {tuple(bw.shape)}"
+                         + ("" if wl is None else f" and learnable_fc {tuple(wl.shape)}, {tuple(bl.shape)}"))
+    if anchor_embed is not None and anchor_embed.shape != instance_feature.shape:
+        raise ValueError(f"deformable_logits: anchor_embed {tuple(anchor_embed.shape)} is not {tuple(instance_feature.shape)}")
+    lead = instance_feature.shape[:-1]
+    f, e = _aligned(instance_feature).reshape(-1, E), None if anchor_embed is None else _aligned(anchor_embed).reshape(-1, E)
+    n = f.shape[0]
+    table, held = _table([wl, bl, ww, bw])
+    raw = torch.empty(n, Nw, dtype=f32, device=f.device)
+    learned = torch.empty(n, K3, dtype=f32, device=f.device) if K3 else None
+    _lib.call("gf_deform_logits_forward", f.device, n, E, K3, Nw, f, e, table, learned, raw)
+    return raw.view(*lead, Nw), None if learned is None else learned.view(*lead, K3 // 3, 3)
+
+
+def deformable_output(features, output_proj, instance_feature=None, residual_mode="add", residual=None, norm=None):
+    """``out`` of the block in one launch, on any leading shape: ``y = output_proj(features)``, then ``y`` (``residual_mode``
+    ``"none"``), ``y + instance_feature`` (``"add"``) or ``cat([y, instance_feature])`` (``"cat"``; deformable_module.py:243-248),
+    then -- not with ``"cat"`` -- ``+ residual [..., 128]`` and the ``nn.LayerNorm(128)`` ``norm`` where given: the encoder's
+    ``"add", "norm"`` behind the block.  ``output_proj`` / ``norm``: a module or a ``(weight, bias)`` pair.  ``proj_drop`` is
+    not applied (eval semantics).  Forward only: inputs that need autograd are refused."""
+    if residual_mode not in MODES:
+        raise ValueError(f"deformable_output: residual_mode {residual_mode!r} is not one of {sorted(MODES)}")
+    wo, bo = _pair(output_proj, "output_proj")
+    g, b = _pair(norm, "norm", nn.LayerNorm)
+    inst = instance_feature if residual_mode != "none" else None
+    if residual_mode != "none" and inst is None:
+        raise ValueError(f"deformable_output: residual_mode {residual_mode!r} needs instance_feature")
+    _refuse_autograd("deformable_output", [features, inst, residual, wo, bo, g, b])
+    _lib.require_gpu(features, inst, residual, wo, bo, g, b)
+    E = features.shape[-1]
+    if wo.shape != (E, E) or bo.shape != (E,) or (g is not None and (g.shape != (E,) or b.shape != (E,))):
+        raise ValueError(f"deformable_output: features [..., {E}] against output_proj {tuple(wo.shape)}, {tuple(bo.shape)}")
+    for name, t in (("instance_feature", inst), ("residual", residual)):
+        if t is not None and t.shape != features.shape:
+            raise ValueError(f"deformable_output: {name} {tuple(t.shape)} is not {tuple(features.shape)}")
+    lead = features.shape[:-1]
+    x = _aligned(features).reshape(-1, E)
+    fi, res = (None if t is None else _aligned(t).reshape(-1, E) for t in (inst, residual))
+    table, held = _table([wo, bo, g, b])
+    width = 2 * E if residual_mode == "cat" else E
+    out = torch.empty(x.shape[0], width, dtype=f32, device=x.device)
+    _lib.call("gf_deform_output_forward", x.device, x.shape[0], E, MODES[residual_mode], x, fi, table, res, out)
+    return out.view(*lead, width)
+
+
+class DeformableFeatureAggregation(nn.Module):
+    """Same constructor keys and defaults, attributes, submodule names, ``state_dict`` keys and ``forward(instance_feature, anchor,
+    anchor_embed, feature_maps, metas, **kwargs)`` as the reference class (deformable_module.py:93-262), so its checkpoints load
+    with ``strict=True``; built without mmengine (``kps_generator`` is the dict of this package's
+    ``SparseGaussian3DKeyPointsGenerator``, its ``type`` ignored).  ``feature_maps``: the list of pyramid levels, formatted per
+    call as the reference does, or an already formatted ``(table, spatial_shape, scale_start_index)`` triple, used as it is.
+
+    The native route -- ``deformable_logits``, ``key_points``, ``deformable_fused_forward``, ``deformable_output``: four launches
+    and, with ``use_camera_embed``, the camera encoder and its ``cams`` rows of ``weights_fc`` in torch (``weights_fc`` is linear:
+    the ``[A cams, 128]`` broadcast sum of :253-262 is never formed) -- runs on fp32 GPU tensors with ``embed_dims == 128``, at
+    most 32 learned columns, a ``residual_mode`` of ``"add"``, ``"cat"`` or ``"none"``, nothing that needs autograd, and in eval
+    mode or with ``proj_drop.p == 0``.  Everything else runs ``forward_torch``: the module's torch layers around
+    ``deformable_fused``, with the attention-dropout keep mask drawn as the reference draws it.
+
+    ``native_dense`` is a class attribute, not a constructor key and not part of the ``state_dict``: ``False`` forces
+    ``forward_torch``.  The keyword arguments ``residual=`` and ``norm=`` of ``forward`` fold the encoder's following ``"add",
+    "norm"`` into the output launch (``out = norm(out + residual)``; not with ``"cat"``); without them the call is the
+    reference's."""
+
+    native_dense = True
+
+    def __init__(self, embed_dims=256, num_groups=8, num_levels=4, num_cams=6, proj_drop=0.0, attn_drop=0.0, kps_generator=None,
+                 use_deformable_func=False, use_camera_embed=False, residual_mode="add"):
+        super().__init__()
+        if embed_dims % num_groups != 0:
+            raise ValueError(f"embed_dims must be divisible by num_groups, but got {embed_dims} and {num_groups}")
+        self.group_dims = int(embed_dims / num_groups)
+        self.embed_dims = embed_dims
+        self.num_levels = num_levels
+        self.num_groups = num_groups
+        self.num_cams = num_cams
+        self.use_deformable_func = use_deformable_func
+        assert self.use_deformable_func       # (the reference's :119-120: only the op's route exists)
+        self.attn_drop = attn_drop
+        self.residual_mode = residual_mode
+        self.proj_drop = nn.Dropout(proj_drop)
+        kps_generator["embed_dims"] = embed_dims
+        self.kps_generator = SparseGaussian3DKeyPointsGenerator(**{k: v for k, v in kps_generator.items() if k != "type"})
+        self.num_pts = self.kps_generator.num_pts
+        self.output_proj = nn.Linear(embed_dims, embed_dims)
+        if use_camera_embed:
+            # (the reference's linear_relu_ln(embed_dims, 1, 2, 12): keys camera_encoder.0 / .2 / .3 / .5)
+            self.camera_encoder = nn.Sequential(nn.Linear(12, embed_dims), nn.ReLU(inplace=True), nn.LayerNorm(embed_dims),
+                                                nn.Linear(embed_dims, embed_dims), nn.ReLU(inplace=True), nn.LayerNorm(embed_dims))
+            self.weights_fc = nn.Linear(embed_dims, num_groups * num_levels * self.num_pts)
+        else:
+            self.camera_encoder = None
+            self.weights_fc = nn.Linear(embed_dims, num_groups * num_cams * num_levels * self.num_pts)
+
+    def init_weight(self):
+        nn.init.constant_(self.weights_fc.weight, 0.0)
+        nn.init.constant_(self.weights_fc.bias, 0.0)
+        nn.init.xavier_uniform_(self.output_proj.weight)
+        nn.init.constant_(self.output_proj.bias, 0.0)
+
+    def _native(self, instance_feature, anchor, anchor_embed, table, residual, norm):
+        if not self.native_dense or self.embed_dims != E_NATIVE or self.residual_mode not in MODES:
+            return False
+        if self.training and self.proj_drop.p > 0:
+            return False
+        if 3 * self.kps_generator.num_learnable_pts > MAX_LEARNED:
+            return False
+        if self.residual_mode == "cat" and (residual is not None or norm is not None):
+            return False
+        if isinstance(norm, nn.LayerNorm) and (norm.eps != 1e-5 or norm.weight is None or norm.bias is None):
+            return False
+        tensors = [instance_feature, anchor, anchor_embed, table, residual, *self.parameters()]
+        tensors += list(norm.parameters()) if isinstance(norm, nn.Module) else list(norm or ())
+        if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
+            return False
+        return not _needs_grad(tensors)
+
+    def forward(self, instance_feature, anchor, anchor_embed, feature_maps, metas, **kwargs):
+        residual, norm = kwargs.get("residual"), kwargs.get("norm")
+        if not (isinstance(feature_maps, (tuple, list)) and len(feature_maps) == 3 and feature_maps[1].dim() == 2):
+            feature_maps = DAF.feature_maps_format(feature_maps)
+        if not self._native(instance_feature, anchor, anchor_embed, feature_maps[0], residual, norm):
+            return self.forward_torch(instance_feature, anchor, anchor_embed, feature_maps, metas, residual=residual, norm=norm)
+        bs, A = instance_feature.shape[:2]
+        gen = self.kps_generator
+        raw, learned = deformable_logits(instance_feature, anchor_embed, self.weights_fc,
+                                         gen.learnable_fc if gen.num_learnable_pts > 0 else None)
+        kp = key_points(anchor, learned, gen._fix, gen.pc_range, gen.scale_range, gen.learnable_fixed_scale, gen.xyz_act, gen.scale_act)
+        pm, wh = metas["projection_mat"], metas.get("image_wh")
+        L, G = self.num_levels, self.num_groups
+        if self.camera_encoder is not None:
+            raw_cam = F.linear(self.camera_encoder(pm[:, :, :3].reshape(bs, self.num_cams, -1)), self.weights_fc.weight)
+            features = deformable_fused_forward(kp, pm, wh, *feature_maps, raw_anchor=raw.view(bs, A, L, self.num_pts, G),
+                                                raw_cam=raw_cam.view(bs, self.num_cams, L, self.num_pts, G))
+        else:
+            features = deformable_fused_forward(kp, pm, wh, *feature_maps, raw_weights=raw.view(bs, A, self.num_cams, L, self.num_pts, G))
+        return deformable_output(features, self.output_proj, instance_feature, self.residual_mode, residual, norm)
+
+    def forward_torch(self, instance_feature, anchor, anchor_embed, feature_maps, metas, residual=None, norm=None):
+        """The reference's composition (:146-262) on the module's torch layers around ``deformable_fused``; ``feature_maps`` is
+        the formatted triple."""
+        bs, A = instance_feature.shape[:2]
+        kp = self.kps_generator(anchor, instance_feature)
+        pm, wh = metas["projection_mat"], metas.get("image_wh")
+        L, G, cams = self.num_levels, self.num_groups, self.num_cams
+        per_anchor = self.weights_fc(instance_feature + anchor_embed)
+        if self.camera_encoder is not None:
+            raw_cam = F.linear(self.camera_encoder(pm[:, :, :3].reshape(bs, cams, -1)), self.weights_fc.weight)
+            logits = dict(raw_anchor=per_anchor.reshape(bs, A, L, self.num_pts, G), raw_cam=raw_cam.reshape(bs, cams, L, self.num_pts, G))
+        else:
+            logits = dict(raw_weights=per_anchor.reshape(bs, A, cams, L, self.num_pts, G))
+        weight_mask = None
+        if self.training and self.attn_drop > 0:     # (:273-282)
+            weight_mask = torch.rand(bs, A, cams, L, self.num_pts, G, dtype=per_anchor.dtype, device=per_anchor.device) > self.attn_drop
+        if weight_mask is None and not _needs_grad([kp, feature_maps[0], per_anchor]):
+            features = deformable_fused_forward(kp, pm, wh, *feature_maps, **logits)     # the same block, the inference launch
+        else:
+            features = deformable_fused(kp, pm, wh, *feature_maps, weight_mask=weight_mask, **logits)
+        output = self.proj_drop(self.output_proj(features))
+        if self.residual_mode == "add":
+            output = output + instance_feature
+        elif self.residual_mode == "cat":
+            output = torch.cat([output, instance_feature], dim=-1)
+        if residual is not None:
+            output = output + residual
+        if norm is not None:
+            output = norm(output) if isinstance(norm, nn.Module) else F.layer_norm(output, (output.shape[-1],), norm[0], norm[1], 1e-5)
+        return output

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward (added without a bump: a library without it fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward, gf_ffn_*, gf_refine_mlp_*, gf_deform_logits_forward / gf_deform_output_forward (added without a bump: a library without them fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -975,6 +975,60 @@ int gf_ffn_backward(int n, int Cin, int F, int E, const float *x, const void *co
                     float scale_hidden, const unsigned char *keep_out, float scale_out, const void *saved, const float *grad_out,
                     float *grad_x, float *grad_residual, void *const *grad_params, void *workspace, size_t workspace_bytes,
                     void *stream);
+
+/* The dense front of the deformable block in one launch: the two Linear layers that
+ * DeformableFeatureAggregation.forward applies to the instance feature before the sampling -- kps_generator.learnable_fc
+ * (model/encoder/gaussian_encoder/deformable_module.py:59-63) and weights_fc on instance_feature + anchor_embed (:250-262).
+ * For every row f [E] of feature f32 [n, E] and e [E] of embed f32 [n, E]:
+ *   learned = Wl f + bl              Wl = kps_generator.learnable_fc.weight [K3, E], K3 = 3 K    (f, not f + e)
+ *   raw     = Ww (f + e) + bw        Ww = weights_fc.weight [Nw, E]
+ * embed may be NULL: raw = Ww f + bw.  K3 = 0: no learnable_fc, learned is not written (and may be NULL).
+ *   learned    f32 [n, K3]: gf_key_points' learned [n, K, 3]
+ *   raw        f32 [n, Nw]: gf_daf_fused_forward's raw_anchor [n, L, pts, G] (use_camera_embed) or raw_weights
+ *              [n, cams, L, pts, G] -- the reference's own column orders
+ *   params     HOST table of GF_DEFORM_LOGITS_PARAMS = 4 device pointers, the modules' own tensors in torch's layout,
+ *              contiguous f32:  0, 1  learnable_fc.weight [K3, E], .bias [K3] (not read when K3 = 0)
+ *                               2, 3  weights_fc.weight [Nw, E], .bias [Nw]
+ * The contract is gf_ffn_forward's: every pointer is 16-byte aligned; the outputs alias no input and not each other; nothing
+ * is read beyond feature[n E] or embed[n E], nothing written beyond learned[n K3] or raw[n Nw].  GF_EINVAL before any HIP
+ * call, the message naming the offending value: E != 128, K3 outside 0 .. GF_DEFORM_MAX_LEARNED, Nw < 4 or not a multiple of
+ * 4 (no upper bound), n < 0, a missing or misaligned pointer, an output that aliases an input.  n == 0 returns GF_OK without a
+ * launch.  Exact fp32 products (v_mfma_f32_32x32x2_f32); f + e is formed in registers and never reaches memory; no workspace,
+ * no atomics, bitwise reproducible; a NaN stays in its row; a row's result does not depend on n or on the row's position (up
+ * to 32 rows per compute unit a workgroup owns 32 rows, beyond that 128: two kernels, the same bits); no host
+ * synchronisation, no allocation: graph-capturable. */
+#define GF_DEFORM_EMBED_DIMS 128
+#define GF_DEFORM_MAX_LEARNED 32
+#define GF_DEFORM_LOGITS_PARAMS 4
+int gf_deform_logits_forward(int n, int E, int K3, int Nw, const float *feature, const float *embed, const void *const *params,
+                             float *learned, float *raw, void *stream);
+
+/* The dense back of the deformable block in one launch: output_proj and the residual of
+ * DeformableFeatureAggregation.forward (model/encoder/gaussian_encoder/deformable_module.py:243-248, proj_drop not applied:
+ * eval semantics), and the "add", "norm" that follow the block in the prob configs' operation_order.  For every row x [E] of
+ * features f32 [n, E] (gf_daf_fused_forward's output) and f [E] of instance_feature f32 [n, E]:
+ *   y   = Wo x + bo                  Wo = output_proj.weight [E, E]
+ *   out = y                          mode GF_DEFORM_NONE   out f32 [n, E]     (instance_feature is not read, may be NULL)
+ *         y + f                      mode GF_DEFORM_ADD    out f32 [n, E]
+ *         [y | f]                    mode GF_DEFORM_CAT    out f32 [n, 2 E]   (the right half is f bit for bit)
+ *   out = LN(out + residual)         GF_DEFORM_NONE / GF_DEFORM_ADD only: + residual f32 [n, E] where given (added last:
+ *                                    zeros change no bit), then the post norm where given (gf_ffn_forward's LayerNorm: eps =
+ *                                    1e-5, biased variance, mean first, then the squared deviations)
+ *   params     HOST table of GF_DEFORM_OUTPUT_PARAMS = 4 device pointers, torch's layout, contiguous f32:
+ *                0, 1  output_proj.weight [E, E], .bias [E]      2, 3  the post norm's weight, bias [E] (a NULL pair: absent)
+ * The contract is gf_ffn_forward's: every pointer is 16-byte aligned; out aliases no input; nothing is read beyond n E of an
+ * input, nothing written beyond out[n E] (out[2 n E] with GF_DEFORM_CAT).  GF_EINVAL before any HIP call, the message naming
+ * the offending value: E != 128, an unknown mode, n < 0, a missing output_proj pointer, a half-present norm pair, a post norm
+ * or a residual with GF_DEFORM_CAT, a misaligned pointer, an out that aliases an input.  n == 0 returns GF_OK without a
+ * launch.  Exact fp32 products, no workspace, no atomics, bitwise reproducible; a NaN stays in its row; a row's result does
+ * not depend on n or on the row's position (two kernels as above, the same bits); no host synchronisation, no allocation:
+ * graph-capturable. */
+#define GF_DEFORM_OUTPUT_PARAMS 4
+#define GF_DEFORM_NONE 0
+#define GF_DEFORM_ADD 1
+#define GF_DEFORM_CAT 2
+int gf_deform_output_forward(int n, int E, int mode, const float *features, const float *instance_feature,
+                             const void *const *params, const float *residual, float *out, void *stream);
 
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */
