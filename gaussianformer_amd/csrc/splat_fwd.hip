@@ -1899,13 +1899,18 @@ __device__ const PhiHotTable kPhiHot = make_phi_hot_table();
 //   [    0,  9216)  ... output staging in the epilogue (slot and list are dead by then)
 //   [12288, 17232)  bitmask row (kWRow words)
 //   [17232, 17744)  hit queue (ring of kQCap ids)
-//   [17744, 20480)  opacity * semantics of the current group, [channel][Gaussian]
+//   [17744, 20304)  opacity * semantics of the current group as f16 hi and lo, two images [Gaussian][kSTRow channels]
+//   [20304, 20480)  unused (zero)
 constexpr int kWList = 512;
 constexpr int kWLdsDwords = 5120;
 // Store instructions of a unit inside the grid.  They are issued from inline asm, which hipcc does not count, and the next unit's row
 // wait is "at most this many operations outstanding": `nst` is set from this constant and the `s_waitcnt vmcnt(N)` is written with
 // it.  A count that differs from the instructions issued is a silent race on the prefetched row, not an error.
 constexpr int kUnitStores = 10;
+// halves per Gaussian row of the two [Gaussian][channel] f16 images of S' (hi, then lo, 32 rows each): 18 channels + 2 that stay zero;
+// 40-byte rows: the 8-byte stores of a 16-lane group and the transposing reads of a 32-lane half are free of bank conflicts
+constexpr int kSTRow = 20;
+static_assert(2 * 32 * kSTRow * 2 <= (kC + 1) * kSRow * 4 && (kSTRow * 2) % 8 == 0, "the S' images fit the S' area; rows keep the reads 8-byte aligned");
 static_assert(3072 + 2 * kWRow + kQCap + (kC + 1) * kSRow == kWLdsDwords, "LDS map of the wave-autonomous kernel");
 static_assert((kWRow + 4 + 3) / 4 <= 3 * 64, "the wave kernel reads its range verdicts with three 16-byte loads per lane");
 static_assert(2 * 64 * kC <= 1536 + 3 * kWList, "output staging fits over the slot and the list");
@@ -1953,6 +1958,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     uint32_t *s_sum = s_u + kLSumAt;   // LONG: the summary row (64 lanes x 16 bytes)
     uint32_t *q_id = s_u + 3072 + 2 * kWRow;
     float *S = reinterpret_cast<float *>(s_u + 3072 + 2 * kWRow + kQCap);
+    __fp16 *Sh = reinterpret_cast<__fp16 *>(S);   // S' as f16: image hi [32 Gaussians][kSTRow], then image lo
 
     const int lane = threadIdx.x;
     const int xcd = (int)(blockIdx.x & 7u);
@@ -2088,7 +2094,7 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     }
 
     const int n = lane & 31, h = lane >> 5;
-    for (int i = lane; i < (kC + 1) * kSRow; i += 64) S[i] = 0.f;
+    for (int i = lane; i < (kC + 1) * kSRow; i += 64) S[i] = 0.f;   // (columns 18 and 19 of both S' images are never written again)
 
     // lattice of the voxel centres (fp64): position of voxel index i along an axis = p0 + i * step (loaded at the top of the kernel)
     q0x = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, q0x)));
@@ -2111,6 +2117,9 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
     }
 
     auto request_records_at = [&](int qh, int start, int count) {
+        // count >= 1 (no caller forms a group from an empty queue).  A dead lane (n >= count) brings the record of the group's FIRST
+        // Gaussian: the group step relies on that -- a dead lane's theta' and S' are a real record's, finite and inside the range
+        // verdicts, and only its one-hot row (-32768 on every coordinate) makes its weights +0.
         const uint32_t id = q_id[(qh + start + (n < count ? n : 0)) & (kQCap - 1)];
         // The two half-lanes of a Gaussian bring its record ONCE: lane (n, h) takes pieces 4 h .. 4 h + 3 into planes 0 .. 3 of the
         // slot, so piece p of Gaussian n lies at slot[64 (p & 3) + 32 (p >> 2) + n] -- four requests and 4 KB per group.  (The tile
@@ -2590,6 +2599,10 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         tl[7] += 1;
 #endif
                         // ---- operands of the group: lane (g = n, h)
+                        // A dead lane (n >= qn, the last group of a unit) holds the record of the group's first Gaussian
+                        // (request_records_at): real, finite values whose range verdicts passed.  Its one-hot row below is -32768 on
+                        // every coordinate, so its exponents are <= -98 304 + theta' phi, its weights exactly +0 and its products
+                        // S' (+0): `live` guards that row and nothing else -- theta' and S' of a dead lane are left as they come.
                         const bool live = n < qn;
                         // (pieces 0 .. 2 from the h = 0 half of planes 0 .. 2: the same address in both half-lanes, a broadcast;
                         // the semantics are pieces 3, 4, 5 = channels 0..11 for h = 0 and 5, 6, 7 = channels 8..19 for h = 1 -- see
@@ -2606,12 +2619,31 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         if (last_group && lane == 0)
                             asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(claimed) : "v"(ctr), "v"(1u) : "memory");
                         {
-                            // S' rows 8 h .. 8 h + 9 of column n: one instruction stream for both half-lanes (10 products and stores
-                            // instead of 12 and 6 in two branches); rows 8 and 9 are written by both, with the same value
-                            const float opa = live ? r0.w : 0.f;
+                            // S' channels 8 h .. 8 h + 9 of Gaussian n: one instruction stream for both half-lanes (10 products instead
+                            // of 12 and 6 in two branches); channels 8 and 9 are written by both, with the same value
+                            const float opa = r0.w;   // (a dead lane's product meets a weight of +0: see `live` above)
                             const float v[10] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y};
+                            // split into f16 hi + lo HERE, where each product is made once (the split is element-wise, so it
+                            // commutes with the transpose): ten values per lane instead of sixteen behind the transpose; the
+                            // packed halves go to row n of the [Gaussian][channel] images as they are (bytes 16 h .. 16 h + 19)
+                            uint32_t ph[5], pl[5];
 #pragma unroll
-                            for (int k = 0; k < 10; ++k) S[(8 * h + k) * kSRow + n] = opa * v[k];
+                            for (int k = 0; k < 5; ++k) {
+                                const float p0 = opa * v[2 * k], p1 = opa * v[2 * k + 1];
+                                const fp16x2 hi2 = __builtin_amdgcn_cvt_pkrtz(p0, p1);
+                                float q0, q1;   // exact residuals p - hi, the f16 halves read in place
+                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(q0) : "v"(hi2), "v"(p0));
+                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(q1) : "v"(hi2), "v"(p1));
+                                ph[k] = __builtin_bit_cast(uint32_t, hi2);
+                                pl[k] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(q0, q1));
+                            }
+                            __fp16 *wh_row = Sh + kSTRow * n + 8 * h, *wl_row = wh_row + 32 * kSTRow;
+                            *reinterpret_cast<uint2 *>(wh_row) = make_uint2(ph[0], ph[1]);
+                            *reinterpret_cast<uint2 *>(wh_row + 4) = make_uint2(ph[2], ph[3]);
+                            *reinterpret_cast<uint32_t *>(wh_row + 8) = ph[4];
+                            *reinterpret_cast<uint2 *>(wl_row) = make_uint2(pl[0], pl[1]);
+                            *reinterpret_cast<uint2 *>(wl_row + 4) = make_uint2(pl[2], pl[3]);
+                            *reinterpret_cast<uint32_t *>(wl_row + 8) = pl[4];
                         }
                         H8 t1, t2, t3;
                         {
@@ -2628,10 +2660,44 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                                 th[0] = -0.5 * L * sy * sy * c1; th[1] = -0.5 * L * sz * sz * c2;
                                 th[2] = -L * sx * sy * c3; th[3] = -L * sy * sz * c4; th[4] = -L * sx * sz * c5;
                             }
+                            // split3's three f16 terms (gf_math.hpp: the tile kernel's form), two values per conversion: a =
+                            // rne(hi), r = (hi - a) + lo, b = rne(r), c = rne(r - b) -- the same roundings of the same numbers,
+                            // with the f16 halves read in place (v_fma_mix_f32: hi - a and r - b are exact) and both halves of a
+                            // dword converted at once (v_cvt_pk_f16_f32 rounds to nearest even like (_Float16), unlike cvt_pkrtz)
+                            float fh[5], fl[5];
 #pragma unroll
-                            for (int j = 0; j < 5; ++j) split3(live ? th[j] : 0.0, t1.e[j], t2.e[j], t3.e[j]);
+                            for (int j = 0; j < 5; ++j) {   // (every lane, dead ones included: see `live` above)
+                                float hi = (float)th[j];
+                                asm volatile("" : "+v"(hi));   // (as in split3: double -> float -> half, in that order)
+                                fh[j] = hi;
+                                fl[j] = (float)(th[j] - (double)hi);
+                            }
 #pragma unroll
-                            for (int j = 5; j < 8; ++j) { t1.e[j] = (_Float16)0.f; t2.e[j] = (_Float16)0.f; t3.e[j] = (_Float16)0.f; }
+                            for (int k = 0; k < 2; ++k) {
+                                fp16x2 pa, pb, pc;
+                                float x0, x1, y0, y1;
+                                asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(pa) : "v"(fh[2 * k]), "v"(fh[2 * k + 1]));
+                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(x0) : "v"(pa), "v"(fh[2 * k]));
+                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(x1) : "v"(pa), "v"(fh[2 * k + 1]));
+                                x0 += fl[2 * k]; x1 += fl[2 * k + 1];
+                                asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(pb) : "v"(x0), "v"(x1));
+                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(y0) : "v"(pb), "v"(x0));
+                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(y1) : "v"(pb), "v"(x1));
+                                asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(pc) : "v"(y0), "v"(y1));
+                                t1.p[k] = pa; t2.p[k] = pb; t3.p[k] = pc;
+                            }
+                            {   // the fifth value, with a zero for a partner
+                                fp16x2 pa, pb, pc;
+                                float x0, y0;
+                                asm("v_cvt_pk_f16_f32 %0, %1, 0" : "=v"(pa) : "v"(fh[4]));
+                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(x0) : "v"(pa), "v"(fh[4]));
+                                x0 += fl[4];
+                                asm("v_cvt_pk_f16_f32 %0, %1, 0" : "=v"(pb) : "v"(x0));
+                                asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(y0) : "v"(pb), "v"(x0));
+                                asm("v_cvt_pk_f16_f32 %0, %1, 0" : "=v"(pc) : "v"(y0));
+                                t1.p[2] = pa; t2.p[2] = pb; t3.p[2] = pc;
+                            }
+                            t1.u[3] = 0u; t2.u[3] = 0u; t3.u[3] = 0u;
                         }
                         H8 tb;
                         {
@@ -2659,18 +2725,25 @@ __global__ __launch_bounds__(64, 2) void gf_splat_render_mfma_wave_kernel(Render
                         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                         __builtin_amdgcn_wave_barrier();
                         H8 sh[2], sl[2];
+                        // the operands ready-made, by the transposing 16-bit read: per group of 16 lanes, lane 4 q + p names row q
+                        // (Gaussian r + q), columns 4 p .. 4 p + 3 of a block and lane i receives column i of its four rows.  The
+                        // groups of channels 16 .. 31 name columns 16 .. 19 in all four p: lanes 20 .. 31 receive copies of those
+                        // (their accumulator rows, channels 20 .. 31, are never stored), lanes 18 and 19 the columns that stay zero.
+                        {
+                            typedef short i16x4 __attribute__((ext_vector_type(4)));
+                            typedef __attribute__((address_space(3))) i16x4 *trptr;
+                            const int tq = (lane >> 2) & 3, tp = (lane & 16) ? 0 : (lane & 3);
+                            const __fp16 *at = Sh + kSTRow * (4 * h + tq) + (lane & 16) + 4 * tp;
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const float4 v4 = *reinterpret_cast<const float4 *>(S + min(n, kC) * kSRow + 8 * q + 4 * h);
-                            const fp16x2 ha = __builtin_amdgcn_cvt_pkrtz(v4.x, v4.y), hb = __builtin_amdgcn_cvt_pkrtz(v4.z, v4.w);
-                            // residuals v - hi (exact), the f16 halves read in place (v_fma_mix_f32): no separate conversions
-                            float ra0, ra1, rb0, rb1;
-                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(ra0) : "v"(ha), "v"(v4.x));
-                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ra1) : "v"(ha), "v"(v4.y));
-                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rb0) : "v"(hb), "v"(v4.z));
-                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rb1) : "v"(hb), "v"(v4.w));
-                            sh[q >> 1].p[2 * (q & 1)] = ha; sh[q >> 1].p[2 * (q & 1) + 1] = hb;
-                            sl[q >> 1].p[2 * (q & 1)] = __builtin_amdgcn_cvt_pkrtz(ra0, ra1); sl[q >> 1].p[2 * (q & 1) + 1] = __builtin_amdgcn_cvt_pkrtz(rb0, rb1);
+                            for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+                                for (int blk8 = 0; blk8 < 2; ++blk8) {
+                                    const __fp16 *blk = at + kSTRow * (16 * kh + 8 * blk8);
+                                    const uint2 hv = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((trptr)blk));
+                                    const uint2 lv = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((trptr)(blk + 32 * kSTRow)));
+                                    sh[kh].u[2 * blk8] = hv.x; sh[kh].u[2 * blk8 + 1] = hv.y;
+                                    sl[kh].u[2 * blk8] = lv.x; sl[kh].u[2 * blk8 + 1] = lv.y;
+                                }
                         }
                         exp_accumulate_pair(t1, t2, t3, tb, phi[0], phi[1], hot[0], hot[1], sh, sl, acc[0], acc[1]);
                         exp_accumulate_pair(t1, t2, t3, tb, phi[2], phi[3], hot[2], hot[3], sh, sl, acc[2], acc[3]);

@@ -4,8 +4,11 @@
 // half-lane, and keeps that request and its slot layout to itself).  gfx950 only, device only, plain functions; each says which
 // lanes must be active, what LDS it touches and which waits and fences it leaves to the caller.  The kernels are held to bit-identity with each other
 // (test_mfma_wave_and_tile_kernels_agree_bit_for_bit, test_list_builder_regimes_agree_across_kernels_and_with_the_oracle), so forms
-// that differ stay in the kernels: the tile kernel forms `tb` with selects and splits S' with fmaf (it runs at 252 VGPRs: its
-// operand phase is left alone), the wave kernel uses packed 16-bit operations and v_fma_mix_f32.  The matrix-core backward
+// that differ stay in the kernels: the tile kernel forms `tb` with selects, zeroes a dead lane's opacity and theta, takes theta's
+// three f16 terms from split3 and splits S' with fmaf behind the fp32 transpose (it runs at 252 VGPRs: its operand phase is left
+// alone); the wave kernel uses packed 16-bit operations for `tb`, leaves a dead lane's opacity and theta as its record gives them
+// (its `tb` row alone makes the weights +0), forms theta's terms two per conversion (v_cvt_pk_f16_f32, v_fma_mix_f32) and splits S'
+// BEFORE the transpose, which is a transposing 16-bit LDS read of two [Gaussian][channel] f16 images.  The matrix-core backward
 // (splat_bwd_mfma.hip) takes the H8 union from here and nothing else: its group arithmetic has other operand roles and its
 // requests are compiler-visible __builtin_amdgcn_global_load_lds on purpose.  The unit decode, the two list builders, the box test
 // with its queue push and the theta operands are the same text in the wave kernel and the backward and are NOT here: each was moved
