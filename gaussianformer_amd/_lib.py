@@ -219,6 +219,52 @@ def as_arg(t, dtype=torch.float32):
     return t.contiguous()
 
 
+def needs_grad(tensors):
+    """Whether autograd would record a call on ``tensors`` (``None``s skipped)."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def aligned(t):
+    """``as_arg(t)``, cloned where its address is not a multiple of 16 (the kernels move rows as float4s)."""
+    t = as_arg(t)
+    return t.clone() if t is not None and t.data_ptr() % 16 else t
+
+
+def param_table(params, count):
+    """``(table, held)``: the library's host table of ``count`` INPUT pointers (NULL for ``None``), and the tensors it points
+    into, in the list's order without the ``None``s: a parameter as it is, or its converted copy (another dtype, not
+    contiguous, misaligned), which the caller keeps alive until the launch is queued (the caching allocator orders its reuse)."""
+    table = (ctypes.c_void_p * count)()
+    held = []
+    for i, p in enumerate(params):
+        if p is None:
+            continue
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.data_ptr() % 16:   # (a module's own parameters: never)
+            p = aligned(p)
+        held.append(p)
+        table[i] = p.data_ptr()
+    return ctypes.cast(table, ctypes.c_void_p), held
+
+
+def out_table(tensors, count):
+    """The host table of ``count`` OUTPUT pointers: the tensors themselves, never a copy -- what the library writes must land in
+    them -- so each has to be what the library writes already."""
+    table = (ctypes.c_void_p * count)()
+    for i, t in enumerate(tensors):
+        if t is not None:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+                raise ValueError("a gradient buffer must be a contiguous, 16-byte aligned float32 tensor")
+            table[i] = t.data_ptr()
+    return ctypes.cast(table, ctypes.c_void_p)
+
+
+def train_sizes(symbol, *ints):
+    """``(saved_bytes, workspace_bytes)`` of a native training step: the size query ``symbol(*ints, &saved, &workspace)``."""
+    saved, work = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    check(getattr(load(), symbol)(*ints, ctypes.addressof(saved), ctypes.addressof(work)), symbol)
+    return saved.value, work.value
+
+
 _Tensor = torch.Tensor   # (a global of this module: call() tests every argument against it)
 
 

@@ -4,8 +4,6 @@ its layers from ``linear_relu_ln``, utils.py:49-59).  Five input branches (xyz, 
 about 40 torch kernels, and ``gf_anchor_embed_forward`` (include/gf_hip.h) in one launch.  Training keeps
 the module's torch layers unless asked otherwise: ``anchor_embed_autograd`` and a module with ``native_training = True`` run the native training
 step (``gf_anchor_embed_forward_train`` / ``gf_anchor_embed_backward``)."""
-import ctypes
-
 import torch
 import torch.nn as nn
 
@@ -40,10 +38,6 @@ def _param_list(module_or_params):
     return [get(stage, slot) for stage in STAGES for slot in _SLOTS]
 
 
-def _needs_grad(tensors):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
-
-
 def _shape(anchor, params):
     """``(a [n, Da] as the library reads it, leading shape, E, opa, S)`` of a call on the 48-entry parameter list."""
     _lib.require_gpu(anchor, *params)
@@ -53,39 +47,10 @@ def _shape(anchor, params):
     return a.reshape(-1, a.shape[-1]), a.shape[:-1], params[0].shape[0], 1 if params[24] is not None else 0, 0 if params[32] is None else params[32].shape[1]
 
 
-def _table(params):
-    """The library's host table of the 48 INPUT pointers, and the tensors it points into, in the list's order without the
-    ``None``s: a parameter as it is, or its converted copy (another dtype, not contiguous, misaligned), which the caller keeps
-    alive until the launch is queued (the caching allocator orders its reuse)."""
-    table = (ctypes.c_void_p * _lib.GF_ANCHOR_EMBED_PARAMS)()
-    held = []
-    for i, p in enumerate(params):
-        if p is None:
-            continue
-        if p.dtype != f32 or not p.is_contiguous() or p.data_ptr() % 16:   # (a module's own parameters: never)
-            p = _lib.as_arg(p)
-            p = p.clone() if p.data_ptr() % 16 else p
-        held.append(p)
-        table[i] = p.data_ptr()
-    return ctypes.cast(table, ctypes.c_void_p), held
-
-
-def _out_table(tensors):
-    """The host table of 48 OUTPUT pointers: the tensors themselves, never a copy -- what the library writes must land in
-    them -- so each has to be what the library writes already."""
-    table = (ctypes.c_void_p * _lib.GF_ANCHOR_EMBED_PARAMS)()
-    for i, t in enumerate(tensors):
-        if t is not None:
-            if t.dtype != f32 or not t.is_contiguous() or t.data_ptr() % 16:
-                raise ValueError("a gradient buffer must be a contiguous, 16-byte aligned float32 tensor")
-            table[i] = t.data_ptr()
-    return ctypes.cast(table, ctypes.c_void_p)
-
-
 def _launch(anchor, params):
     """The library call on the 48-entry parameter list; the callers have settled autograd."""
     a, lead, E, opa, S = _shape(anchor, params)
-    table, held = _table(params)
+    table, held = _lib.param_table(params, _lib.GF_ANCHOR_EMBED_PARAMS)
     out = torch.empty(a.shape[0], E, dtype=f32, device=a.device)
     _lib.call("gf_anchor_embed_forward", a.device, a.shape[0], a.shape[1], E, opa, S, a, table, out)
     return out.view(*lead, E)
@@ -93,10 +58,7 @@ def _launch(anchor, params):
 
 def train_sizes(n, include_opa, S):
     """``(saved_bytes, workspace_bytes)`` of the training step on ``n`` rows (``gf_anchor_embed_train_sizes``)."""
-    saved, work = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _lib.check(_lib.load().gf_anchor_embed_train_sizes(n, int(bool(include_opa)), S, ctypes.addressof(saved), ctypes.addressof(work)),
-               "gf_anchor_embed_train_sizes")
-    return saved.value, work.value
+    return _lib.train_sizes("gf_anchor_embed_train_sizes", n, int(bool(include_opa)), S)
 
 
 class AnchorEmbedFunction(torch.autograd.Function):
@@ -107,7 +69,7 @@ class AnchorEmbedFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, *params):
         a, lead, E, opa, S = _shape(anchor, params)
-        table, held = _table(params)
+        table, held = _lib.param_table(params, _lib.GF_ANCHOR_EMBED_PARAMS)
         n, Da = a.shape
         saved_bytes, _ = train_sizes(n, opa, S)
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=a.device)
@@ -127,8 +89,8 @@ class AnchorEmbedFunction(torch.autograd.Function):
         for d in dtypes:
             params.append(None if d is None else next(it))
             grads.append(None if d is None else torch.empty_like(params[-1]))
-        table, _ = _table(params)
-        gtable = _out_table(grads)
+        table, _ = _lib.param_table(params, _lib.GF_ANCHOR_EMBED_PARAMS)
+        gtable = _lib.out_table(grads, _lib.GF_ANCHOR_EMBED_PARAMS)
         _, work_bytes = train_sizes(n, opa, S)
         work = torch.empty(work_bytes, dtype=torch.uint8, device=a.device)
         grad_anchor = torch.empty(n, Da, dtype=f32, device=a.device)
@@ -144,7 +106,7 @@ def anchor_embed_autograd(anchor, module_or_params):
     every parameter that requires grad receive their gradients (the others ``None``).  Under ``torch.no_grad()``, or when
     nothing requires grad, it is the plain forward."""
     params = _param_list(module_or_params)
-    if not _needs_grad([anchor, *params]):
+    if not _lib.needs_grad([anchor, *params]):
         return _launch(anchor, params)
     return AnchorEmbedFunction.apply(anchor, *params)
 
@@ -155,7 +117,7 @@ def anchor_embed(anchor, module_or_params):
     (``xyz_fc.0.weight`` ... ``output_fc.5.bias``); which branches exist says ``include_opa`` and the semantic width.  The
     parameters are read in place at every call.  Forward only: inputs that need autograd are refused."""
     params = _param_list(module_or_params)
-    if _needs_grad([anchor, *params]):
+    if _lib.needs_grad([anchor, *params]):
         raise RuntimeError(
             "anchor_embed is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters "
             "that do not require grad (the SparseGaussian3DEncoder module routes training to its torch layers), or call "
@@ -197,7 +159,7 @@ class SparseGaussian3DEncoder(nn.Module):
         if box_3d.is_cuda and box_3d.dtype == f32 and self.embed_dims == E_NATIVE and self.semantic_dim <= MAX_S:
             params = _param_list(self)
             if params[0].is_cuda and params[0].dtype == f32:
-                if not _needs_grad([box_3d, *params]):
+                if not _lib.needs_grad([box_3d, *params]):
                     return _launch(box_3d, params)
                 if self.native_training:
                     return AnchorEmbedFunction.apply(box_3d, *params)

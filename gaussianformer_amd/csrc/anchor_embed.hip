@@ -28,7 +28,7 @@
 //
 // Rows past n in the last tile compute on row n - 1 and are not stored.  The result leaves through LDS (the weight buffers,
 // idle by then) so that a store instruction writes runs of 256 bytes.
-#include "gf_rows.hpp"
+#include "gf_rows_bwd.hpp"
 
 namespace gf {
 
@@ -160,15 +160,7 @@ __global__ __launch_bounds__(256) void gf_anchor_embed_kernel(typename AeFwdArgs
 #pragma unroll
                 for (int b = 0; b < 4; ++b) x[b] = sum[b];
                 if constexpr (SAVE) {
-                    if (valid) {
-                        float *srow = a.sumv + (size_t)(row0 + j) * kAeE;
-#pragma unroll
-                        for (int b = 0; b < 4; ++b)
-#pragma unroll
-                            for (int m = 0; m < 4; ++m)
-                                *reinterpret_cast<float4 *>(srow + 32 * b + 8 * m + 4 * h) =
-                                    make_float4(x[b][4 * m], x[b][4 * m + 1], x[b][4 * m + 2], x[b][4 * m + 3]);
-                    }
+                    if (valid) store_row_regs(a.sumv + (size_t)(row0 + j) * kAeE, x, h);
                 }
             }
         } else {
@@ -191,7 +183,6 @@ __global__ __launch_bounds__(256) void gf_anchor_embed_kernel(typename AeFwdArgs
 // (1) and (2) into the caller's gradient tensors: stored, not accumulated.
 constexpr int kAeMaxStages = 12;
 constexpr int kAeWgRows = GF_ANCHOR_EMBED_WGRAD_ROWS;   // rows per workgroup of the weight-gradient kernel
-constexpr int kAeBwPitch = 136;   // floats per staged weight row of the data backward: rows 4 apart lie 32 banks apart
 // (1) and (2) run chunk by chunk of this many rows (512 tiles, two per CU), one after the other on the stream, so the dz rows
 // -- as large per row as everything the forward saves -- are held for one chunk only; the partials are kept for all of them
 constexpr int kAeChunkRows = GF_ANCHOR_EMBED_CHUNK_ROWS;
@@ -270,14 +261,7 @@ __device__ __forceinline__ void ae_stage_bwd(const AeBwdArgs &a, f32x16 (&g)[4],
     const size_t at = (size_t)st * a.n + row;
     const float2 ms = *reinterpret_cast<const float2 *>(a.stat + at * 2);
     ln_relu_bwd(g, a.rsave + at * kAeE, ms.x, ms.y, a.gam[st], valid, s_part[wv], j, h);
-    if (valid) {
-        float *drow = a.dz + ((size_t)st * a.crows + (row - a.base)) * kAeE;
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                *reinterpret_cast<float4 *>(drow + 32 * b + 8 * m + 4 * h) = make_float4(g[b][4 * m], g[b][4 * m + 1], g[b][4 * m + 2], g[b][4 * m + 3]);
-    }
+    if (valid) store_row_regs(a.dz + ((size_t)st * a.crows + (row - a.base)) * kAeE, g, h);
     __syncthreads();
     const int ns = 2 * a.nb + 2;
     for (int e = t; e < 3 * kAeE; e += 256)   // the four waves, in their order
@@ -285,46 +269,19 @@ __device__ __forceinline__ void ae_stage_bwd(const AeBwdArgs &a, f32x16 (&g)[4],
     __syncthreads();
 }
 
-// g <- W^T g for a square stage: W[o][k] through LDS in chunks of 32 rows o (= the features of g's register block c)
-__device__ __forceinline__ void ae_product_bwd(f32x16 (&g)[4], const float *w, float (*s_w)[32 * kAeBwPitch], int t, int j, int h)
+// g <- W^T g for a square stage
+__device__ __forceinline__ void ae_product_bwd(f32x16 (&g)[4], const float *w, float (*s_w)[32 * kRowTPitch], int t, int j, int h)
 {
     f32x16 acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-    const int rr = t >> 3, fq = t & 7;
-    float4 pre[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pre[i] = ld4(w + (size_t)rr * kAeE + 4 * (fq + 8 * i));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *reinterpret_cast<float4 *>(&s_w[0][rr * kAeBwPitch + 4 * (fq + 8 * i)]) = pre[i];
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (c < 3) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pre[i] = ld4(w + (size_t)(32 * (c + 1) + rr) * kAeE + 4 * (fq + 8 * i));
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float *wrow = &s_w[c & 1][(8 * (r >> 2) + 4 * h + (r & 3)) * kAeBwPitch + j];
-#pragma unroll
-            for (int fb = 0; fb < 4; ++fb) acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wrow[32 * fb], g[c][r], acc[fb], 0, 0, 0);
-        }
-        if (c < 3) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) *reinterpret_cast<float4 *>(&s_w[(c + 1) & 1][rr * kAeBwPitch + 4 * (fq + 8 * i)]) = pre[i];
-        }
-        __syncthreads();
-    }
+    zero_rows(acc);
+    product_t<4, false>(acc, g, w, kAeE, 0, s_w[0], s_w[1], t, j, h);
 #pragma unroll
     for (int b = 0; b < 4; ++b) g[b] = acc[b];
 }
 
 __global__ __launch_bounds__(256) void gf_anchor_embed_bwd_kernel(AeBwdArgs a)
 {
-    __shared__ float s_w[2][32 * kAeBwPitch];
+    __shared__ float s_w[2][32 * kRowTPitch];
     __shared__ float s_part[4][3 * kAeE];
     const int t = threadIdx.x, l = t & 63, wv = t >> 6, j = l & 31, h = l >> 5;
     const int row0 = a.base + blockIdx.x * kAeTile + wv * 32;
@@ -333,16 +290,7 @@ __global__ __launch_bounds__(256) void gf_anchor_embed_bwd_kernel(AeBwdArgs a)
     const int nb = a.nb;
 
     f32x16 g[4], dsum[4];
-    {
-        const float *grow = a.grad_out + (size_t)row * kAeE;
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float4 v = valid ? ld4(grow + 32 * b + 8 * m + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
-                g[b][4 * m] = v.x; g[b][4 * m + 1] = v.y; g[b][4 * m + 2] = v.z; g[b][4 * m + 3] = v.w;
-            }
-    }
+    load_row_or_zero(g, a.grad_out + (size_t)row * kAeE, valid, h);
     // i = 0, 1: output_fc's second and first stage; then the branches, last to first: square stage, thin stage
     for (int i = 0; i < nb + 2; ++i) {
         const int q = nb + 1 - i, st = i < 2 ? 2 * nb + 1 - i : nb + q;
@@ -436,57 +384,16 @@ __global__ __launch_bounds__(256) void gf_anchor_embed_wgrad_kernel(AeWgArgs a)
         ev[cb] = plain ? 0.f : a.bet[ps][32 * cb + j];
     }
     f32x16 acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-    for (int r = r0; r < r1; r += 8) {
-        float av[4], xv[4][4];
-        float2 ms[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int row = min(r + 2 * u + h, r1 - 1);
-            av[u] = dz[(size_t)(row - a.base) * kAeE];
-            ms[u] = plain ? make_float2(0.f, 1.f) : *reinterpret_cast<const float2 *>(stat + (size_t)row * 2);
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) xv[u][cb] = src[(size_t)row * kAeE + 32 * cb];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool live = r + 2 * u + h < r1;
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                const float bv = (xv[u][cb] - ms[u].x) * ms[u].y * gv[cb] + ev[cb];
-                acc[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(live ? av[u] : 0.f, live ? bv : 0.f, acc[cb], 0, 0, 0);
-            }
-        }
-    }
-    float *dst = a.wsq + ((size_t)blk * (nb + 2) + q) * (kAeE * kAeE) + j;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dst[(32 * wv + 8 * (r >> 2) + 4 * h + (r & 3)) * kAeE + 32 * cb] = acc[cb][r];
+    zero_rows(acc);
+    if (plain) wgrad_rows<kWgAsIs>(acc, dz, kAeE, a.base, src, nullptr, kAeE, 0, nullptr, gv, ev, r0, r1, r1, h);
+    else wgrad_rows<kWgNorm>(acc, dz, kAeE, a.base, src, nullptr, kAeE, 0, stat, gv, ev, r0, r1, r1, h);
+    wgrad_store(a.wsq + ((size_t)blk * (nb + 2) + q) * (kAeE * kAeE), kAeE, [&](int cb, int r) { return acc[cb][r]; }, wv, j, h);
 }
 
-// dst[e] = sum over `count` partials, `stride` floats apart, in a fixed order (four interleaved running sums, then their
-// tree); K > 0: dst is a thin weight [128][K] and its partials are rows of 32.  count == 0 stores zeros.
-struct AeSumJob { const float *src; float *dst; size_t stride; int count, len, K; };
-struct AeSumArgs { AeSumJob job[GF_ANCHOR_EMBED_PARAMS]; };
-__global__ __launch_bounds__(256) void gf_anchor_embed_sum_kernel(AeSumArgs a)
-{
-    const AeSumJob &jb = a.job[blockIdx.y];
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= jb.len) return;
-    const float *src = jb.src + (jb.K ? (e / jb.K) * 32 + e % jb.K : e);
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    int i = 0;
-    for (; i + 3 < jb.count; i += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) s[u] += src[(size_t)(i + u) * jb.stride];
-    }
-    for (; i < jb.count; ++i) s[0] += src[(size_t)i * jb.stride];
-    jb.dst[e] = (s[0] + s[1]) + (s[2] + s[3]);
-}
+// (3) is rows_sum_kernel<float>; K > 0 there: a thin weight [128][K], whose partials are rows of 32.  Instantiated here and not
+// by the launch alone: a template's kernel is otherwise emitted behind the forward kernels, whose local labels are numbered by
+// their place in the code object -- with this line their assembly is the earlier one line for line, labels included
+template __global__ void rows_sum_kernel<float, GF_ANCHOR_EMBED_PARAMS>(RowsSumArgs<GF_ANCHOR_EMBED_PARAMS>);
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
@@ -504,7 +411,7 @@ static int ae_parse(const char *fn, int n, int Da, int E, int opa, int S, const 
         const bool present = s == 5 || k[s] > 0;
         for (int i = 0; i < 8; ++i) {
             GF_CHECK_ARG_AS(fn, !present || p[i], "null parameter of a stage that is present");
-            GF_CHECK_ARG_AS(fn, !present || i == 0 || (reinterpret_cast<uintptr_t>(p[i]) & 15) == 0, "a parameter is not 16-byte aligned");
+            GF_CHECK_ARG_AS(fn, !present || i == 0 || !misaligned16(p[i]), "a parameter is not 16-byte aligned");
         }
         if (!present) continue;
         if (s < 5) {
@@ -516,7 +423,7 @@ static int ae_parse(const char *fn, int n, int Da, int E, int opa, int S, const 
             }
             ++a.nb;
         } else {
-            GF_CHECK_ARG_AS(fn, (reinterpret_cast<uintptr_t>(p[0]) & 15) == 0, "a parameter is not 16-byte aligned");
+            GF_CHECK_ARG_AS(fn, !misaligned16(p[0]), "a parameter is not 16-byte aligned");
             a.sq[a.nb] = p[0];
             a.sq[a.nb + 1] = p[4];
             for (int i = 0; i < 3; ++i) {
@@ -567,7 +474,7 @@ extern "C" int gf_anchor_embed_forward(int n, int Da, int E, int include_opa, in
     if (int rc = ae_parse(__func__, n, Da, E, include_opa ? 1 : 0, S, params, a)) return rc;
     if (n == 0) return GF_OK;
     GF_CHECK_ARG(anchor && out, "null pointer");
-    GF_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "out is not 16-byte aligned");
+    GF_CHECK_ARG(!misaligned16(out), "out is not 16-byte aligned");
     a.anchor = anchor; a.out = out;
     hipLaunchKernelGGL(gf_anchor_embed_kernel<false>, dim3((n + kAeTile - 1) / kAeTile), dim3(256), 0, (hipStream_t)stream_, a);
     GF_CHECK_LAUNCH();
@@ -594,8 +501,8 @@ extern "C" int gf_anchor_embed_forward_train(int n, int Da, int E, int include_o
     if (int rc = ae_parse(__func__, n, Da, E, include_opa ? 1 : 0, S, params, a)) return rc;
     if (n == 0) return GF_OK;
     GF_CHECK_ARG(anchor && out && saved, "null pointer");
-    GF_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "out is not 16-byte aligned");
-    GF_CHECK_ARG((reinterpret_cast<uintptr_t>(saved) & 15) == 0, "saved is not 16-byte aligned");
+    GF_CHECK_ARG(!misaligned16(out), "out is not 16-byte aligned");
+    GF_CHECK_ARG(!misaligned16(saved), "saved is not 16-byte aligned");
     const AeSaved sv = ae_carve_saved(saved, n, a.nb);
     GF_CHECK_WORKSPACE_AS(__func__, "saved", saved_bytes, sv.bytes);
     a.anchor = anchor; a.out = out;
@@ -634,9 +541,9 @@ extern "C" int gf_anchor_embed_backward(int n, int Da, int E, int include_opa, i
     const AeWork ws = ae_carve_work(n > 0 ? workspace : nullptr, n, nb);
     if (n > 0) {
         GF_CHECK_ARG(anchor && saved && grad_out && grad_anchor && workspace, "null pointer");
-        GF_CHECK_ARG((reinterpret_cast<uintptr_t>(grad_out) & 15) == 0, "grad_out is not 16-byte aligned");
-        GF_CHECK_ARG((reinterpret_cast<uintptr_t>(saved) & 15) == 0, "saved is not 16-byte aligned");
-        GF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "workspace is not 16-byte aligned");
+        GF_CHECK_ARG(!misaligned16(grad_out), "grad_out is not 16-byte aligned");
+        GF_CHECK_ARG(!misaligned16(saved), "saved is not 16-byte aligned");
+        GF_CHECK_ARG(!misaligned16(workspace), "workspace is not 16-byte aligned");
         GF_CHECK_WORKSPACE(workspace_bytes, ws.bytes);
     }
     hipStream_t stream = (hipStream_t)stream_;
@@ -667,18 +574,18 @@ extern "C" int gf_anchor_embed_backward(int n, int Da, int E, int include_opa, i
         }
     }
     // n == 0: no partials, the sums store zeros
-    AeSumArgs sa{};
+    RowsSumArgs<GF_ANCHOR_EMBED_PARAMS> sa{};   // float sums, a thread per element; K > 0: a thin weight, its partials rows of 32
     int nj = 0;
     for (int st = 0; st < ns; ++st) {
         const bool thin = st < nb;
         const int K = thin ? f.thin[st].k : 0;
         const float *wsrc = n == 0 ? nullptr : thin ? ws.wthin + (size_t)st * kAeE * 32 : ws.wsq + (size_t)(st - nb) * kAeE * kAeE;
-        sa.job[nj++] = thin ? AeSumJob{wsrc, gw[st], (size_t)nb * kAeE * 32, n > 0 ? ws.blocks : 0, kAeE * K, K}
-                            : AeSumJob{wsrc, gw[st], (size_t)(nb + 2) * kAeE * kAeE, n > 0 ? ws.blocks : 0, kAeE * kAeE, 0};
+        sa.job[nj++] = thin ? RowsSumJob{wsrc, gw[st], (size_t)nb * kAeE * 32, n > 0 ? ws.blocks : 0, kAeE * K, K, 1}
+                            : RowsSumJob{wsrc, gw[st], (size_t)(nb + 2) * kAeE * kAeE, n > 0 ? ws.blocks : 0, kAeE * kAeE, 0, 1};
         for (int v = 0; v < 3; ++v)
-            sa.job[nj++] = AeSumJob{n == 0 ? nullptr : ws.vpart + ((size_t)st * 3 + v) * kAeE, gvec[st][v], (size_t)ns * 3 * kAeE, n > 0 ? ws.tiles : 0, kAeE, 0};
+            sa.job[nj++] = RowsSumJob{n == 0 ? nullptr : ws.vpart + ((size_t)st * 3 + v) * kAeE, gvec[st][v], (size_t)ns * 3 * kAeE, n > 0 ? ws.tiles : 0, kAeE, 0, 1};
     }
-    hipLaunchKernelGGL(gf_anchor_embed_sum_kernel, dim3(kAeE * kAeE / 256, nj), dim3(256), 0, stream, sa);
+    hipLaunchKernelGGL((rows_sum_kernel<float, GF_ANCHOR_EMBED_PARAMS>), dim3(kAeE * kAeE / 256, nj), dim3(256), 0, stream, sa);
     GF_CHECK_LAUNCH();
     return GF_OK;
 }

@@ -361,14 +361,6 @@ __global__ __launch_bounds__(256) void gf_deform_output_rows32_kernel(DeformOutp
 
 // ---- the argument checks ----------------------------------------------------------------------------------------------------
 
-#define GF_DEFORM_REFUSE(cond, fmt, ...)                               \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            gf::set_error("%s: " fmt, __func__, ##__VA_ARGS__);        \
-            return GF_EINVAL;                                          \
-        }                                                              \
-    } while (0)
-static bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 // the byte ranges [a, a + na) and [b, b + nb) meet (a null or empty one meets nothing)
 static bool overlap(const void *a, size_t na, const void *b, size_t nb)
 {
@@ -384,27 +376,27 @@ extern "C" int gf_deform_logits_forward(int n, int E, int K3, int Nw, const floa
     using namespace gf;
     static const char *const name[GF_DEFORM_LOGITS_PARAMS] = {"kps_generator.learnable_fc.weight", "kps_generator.learnable_fc.bias",
                                                               "weights_fc.weight", "weights_fc.bias"};
-    GF_DEFORM_REFUSE(E == kDeformE, "E = %d: only embed_dims = 128 is supported", E);
-    GF_DEFORM_REFUSE(K3 >= 0 && K3 <= GF_DEFORM_MAX_LEARNED, "K3 = %d: the learned columns 3 K must be 0 .. %d", K3, GF_DEFORM_MAX_LEARNED);
-    GF_DEFORM_REFUSE(Nw >= 4 && Nw % 4 == 0, "Nw = %d: the logits' width must be a positive multiple of 4", Nw);
-    GF_DEFORM_REFUSE(n >= 0, "n = %d is negative", n);
-    GF_DEFORM_REFUSE(params, "null params");
+    GF_REFUSE_AS(__func__, E == kDeformE, "E = %d: only embed_dims = 128 is supported", E);
+    GF_REFUSE_AS(__func__, K3 >= 0 && K3 <= GF_DEFORM_MAX_LEARNED, "K3 = %d: the learned columns 3 K must be 0 .. %d", K3, GF_DEFORM_MAX_LEARNED);
+    GF_REFUSE_AS(__func__, Nw >= 4 && Nw % 4 == 0, "Nw = %d: the logits' width must be a positive multiple of 4", Nw);
+    GF_REFUSE_AS(__func__, n >= 0, "n = %d is negative", n);
+    GF_REFUSE_AS(__func__, params, "null params");
     const float *const *p = reinterpret_cast<const float *const *>(params);
     for (int i = K3 > 0 ? 0 : 2; i < GF_DEFORM_LOGITS_PARAMS; ++i) {
-        GF_DEFORM_REFUSE(p[i], "%s is missing", name[i]);
-        GF_DEFORM_REFUSE(!misaligned(p[i]), "%s is not 16-byte aligned", name[i]);
+        GF_REFUSE_AS(__func__, p[i], "%s is missing", name[i]);
+        GF_REFUSE_AS(__func__, !misaligned16(p[i]), "%s is not 16-byte aligned", name[i]);
     }
-    GF_DEFORM_REFUSE(!misaligned(feature), "instance_feature is not 16-byte aligned");
-    GF_DEFORM_REFUSE(!misaligned(embed), "anchor_embed is not 16-byte aligned");
-    GF_DEFORM_REFUSE(!misaligned(learned), "learned is not 16-byte aligned");
-    GF_DEFORM_REFUSE(!misaligned(raw), "raw is not 16-byte aligned");
+    GF_REFUSE_AS(__func__, !misaligned16(feature), "instance_feature is not 16-byte aligned");
+    GF_REFUSE_AS(__func__, !misaligned16(embed), "anchor_embed is not 16-byte aligned");
+    GF_REFUSE_AS(__func__, !misaligned16(learned), "learned is not 16-byte aligned");
+    GF_REFUSE_AS(__func__, !misaligned16(raw), "raw is not 16-byte aligned");
     if (n == 0) return GF_OK;
-    GF_DEFORM_REFUSE(feature && raw && (K3 == 0 || learned), "null pointer");
+    GF_REFUSE_AS(__func__, feature && raw && (K3 == 0 || learned), "null pointer");
     const size_t in_bytes = (size_t)n * kDeformE * 4, raw_bytes = (size_t)n * Nw * 4, learned_bytes = (size_t)n * K3 * 4;
-    GF_DEFORM_REFUSE(!overlap(raw, raw_bytes, feature, in_bytes) && !overlap(raw, raw_bytes, embed, in_bytes), "raw aliases an input");
-    GF_DEFORM_REFUSE(!overlap(learned, learned_bytes, feature, in_bytes) && !overlap(learned, learned_bytes, embed, in_bytes),
+    GF_REFUSE_AS(__func__, !overlap(raw, raw_bytes, feature, in_bytes) && !overlap(raw, raw_bytes, embed, in_bytes), "raw aliases an input");
+    GF_REFUSE_AS(__func__, !overlap(learned, learned_bytes, feature, in_bytes) && !overlap(learned, learned_bytes, embed, in_bytes),
                      "learned aliases an input");
-    GF_DEFORM_REFUSE(!overlap(learned, learned_bytes, raw, raw_bytes), "learned aliases raw");
+    GF_REFUSE_AS(__func__, !overlap(learned, learned_bytes, raw, raw_bytes), "learned aliases raw");
     DeformLogitsArgs a{feature, embed, K3 > 0 ? p[0] : nullptr, K3 > 0 ? p[1] : nullptr, p[2], p[3], learned, raw, n, K3, Nw};
     hipStream_t stream = (hipStream_t)stream_;
     if ((n + 31) / 32 <= cu_count())   // at most one 32-row workgroup per CU: the same bits, sooner
@@ -420,25 +412,25 @@ extern "C" int gf_deform_output_forward(int n, int E, int mode, const float *fea
 {
     using namespace gf;
     static const char *const name[GF_DEFORM_OUTPUT_PARAMS] = {"output_proj.weight", "output_proj.bias", "norm.weight", "norm.bias"};
-    GF_DEFORM_REFUSE(E == kDeformE, "E = %d: only embed_dims = 128 is supported", E);
-    GF_DEFORM_REFUSE(mode == GF_DEFORM_NONE || mode == GF_DEFORM_ADD || mode == GF_DEFORM_CAT, "mode = %d is not GF_DEFORM_NONE / ADD / CAT", mode);
-    GF_DEFORM_REFUSE(n >= 0, "n = %d is negative", n);
-    GF_DEFORM_REFUSE(params, "null params");
+    GF_REFUSE_AS(__func__, E == kDeformE, "E = %d: only embed_dims = 128 is supported", E);
+    GF_REFUSE_AS(__func__, mode == GF_DEFORM_NONE || mode == GF_DEFORM_ADD || mode == GF_DEFORM_CAT, "mode = %d is not GF_DEFORM_NONE / ADD / CAT", mode);
+    GF_REFUSE_AS(__func__, n >= 0, "n = %d is negative", n);
+    GF_REFUSE_AS(__func__, params, "null params");
     const float *const *p = reinterpret_cast<const float *const *>(params);
-    GF_DEFORM_REFUSE(p[0], "%s is missing", name[0]);
-    GF_DEFORM_REFUSE(p[1], "%s is missing", name[1]);
-    GF_DEFORM_REFUSE(!p[2] == !p[3], "a half-present pair: %s is null and %s is not", name[p[2] ? 3 : 2], name[p[2] ? 2 : 3]);
-    GF_DEFORM_REFUSE(!(p[2] && mode == GF_DEFORM_CAT), "a post norm with mode = %d (GF_DEFORM_CAT): the norm is 128 wide, the row 256", mode);
-    GF_DEFORM_REFUSE(!(residual && mode == GF_DEFORM_CAT), "a residual with mode = %d (GF_DEFORM_CAT)", mode);
-    for (int i = 0; i < GF_DEFORM_OUTPUT_PARAMS; ++i) GF_DEFORM_REFUSE(!misaligned(p[i]), "%s is not 16-byte aligned", name[i]);
-    GF_DEFORM_REFUSE(!misaligned(features), "features is not 16-byte aligned");
-    GF_DEFORM_REFUSE(!misaligned(instance_feature), "instance_feature is not 16-byte aligned");
-    GF_DEFORM_REFUSE(!misaligned(residual), "residual is not 16-byte aligned");
-    GF_DEFORM_REFUSE(!misaligned(out), "out is not 16-byte aligned");
+    GF_REFUSE_AS(__func__, p[0], "%s is missing", name[0]);
+    GF_REFUSE_AS(__func__, p[1], "%s is missing", name[1]);
+    GF_REFUSE_AS(__func__, !p[2] == !p[3], "a half-present pair: %s is null and %s is not", name[p[2] ? 3 : 2], name[p[2] ? 2 : 3]);
+    GF_REFUSE_AS(__func__, !(p[2] && mode == GF_DEFORM_CAT), "a post norm with mode = %d (GF_DEFORM_CAT): the norm is 128 wide, the row 256", mode);
+    GF_REFUSE_AS(__func__, !(residual && mode == GF_DEFORM_CAT), "a residual with mode = %d (GF_DEFORM_CAT)", mode);
+    for (int i = 0; i < GF_DEFORM_OUTPUT_PARAMS; ++i) GF_REFUSE_AS(__func__, !misaligned16(p[i]), "%s is not 16-byte aligned", name[i]);
+    GF_REFUSE_AS(__func__, !misaligned16(features), "features is not 16-byte aligned");
+    GF_REFUSE_AS(__func__, !misaligned16(instance_feature), "instance_feature is not 16-byte aligned");
+    GF_REFUSE_AS(__func__, !misaligned16(residual), "residual is not 16-byte aligned");
+    GF_REFUSE_AS(__func__, !misaligned16(out), "out is not 16-byte aligned");
     if (n == 0) return GF_OK;
-    GF_DEFORM_REFUSE(features && out && (mode == GF_DEFORM_NONE || instance_feature), "null pointer");
+    GF_REFUSE_AS(__func__, features && out && (mode == GF_DEFORM_NONE || instance_feature), "null pointer");
     const size_t in_bytes = (size_t)n * kDeformE * 4, out_bytes = in_bytes * (mode == GF_DEFORM_CAT ? 2 : 1);
-    GF_DEFORM_REFUSE(!overlap(out, out_bytes, features, in_bytes) && !overlap(out, out_bytes, residual, in_bytes) &&
+    GF_REFUSE_AS(__func__, !overlap(out, out_bytes, features, in_bytes) && !overlap(out, out_bytes, residual, in_bytes) &&
                          !(mode != GF_DEFORM_NONE && overlap(out, out_bytes, instance_feature, in_bytes)),
                      "out aliases an input");
     DeformOutputArgs a{features, mode == GF_DEFORM_NONE ? nullptr : instance_feature, residual, p[0], p[1], p[2], p[3], out, n, mode};

@@ -94,16 +94,7 @@ __global__ __launch_bounds__(256) void gf_ffn_rows32_kernel(FfnArgs a)
         put(vPost + 32, a.post_b, 32);
     }
     f32x16 u[NB];   // every wave holds the whole row: it is the B operand of all of them
-    {
-        const float *xrow = a.x + row * CIN;
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float4 v = ld4(xrow + 32 * b + 8 * m + 4 * h);
-                u[b][4 * m] = v.x; u[b][4 * m + 1] = v.y; u[b][4 * m + 2] = v.z; u[b][4 * m + 3] = v.w;
-            }
-    }
+    load_row(u, a.x + row * CIN, h);
     __syncthreads();
     if (a.pre_g) {
         float part[NB];
@@ -196,7 +187,7 @@ extern "C" int gf_ffn_forward(int n, int Cin, int F, int E, const float *x, cons
     const char *fn = __func__;
     if (int rc = ffn_check(fn, n, Cin, F, E, x, params, residual, out)) return rc;
     if (n == 0) return GF_OK;
-    GF_FFN_REFUSE(x && out, "null pointer");
+    GF_REFUSE_AS(fn, x && out, "null pointer");
     const float *const *p = reinterpret_cast<const float *const *>(params);
     FfnArgs a{x, residual, out, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], n};
     hipStream_t stream = (hipStream_t)stream_;

@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "gf_ffn.hpp"
+#include "gf_rows_bwd.hpp"
 
 namespace gf {
 
@@ -11,7 +12,7 @@ namespace gf {
 // norm's backward gives dy and da.  Pass 1 walks the four hidden slices: h_s is formed again from u by the forward's own chunk
 // chain (so h <= 0 is the forward's decision bit for bit), dh_s = W2[:, s]^T da, dz_s = dropout and ReLU backward of it.
 // Pass 2: du = Wid^T dy + sum_s W1_s^T dz_s, then the pre norm's backward.  The transposed products read the weight along its
-// rows from LDS (ffn_product_t).  It writes grad_x, grad_residual, the chunk's h', dz, da and dy rows for (2), and per tile
+// rows from LDS (product_t).  It writes grad_x, grad_residual, the chunk's h', dz, da and dy rows for (2), and per tile
 // the sums over its rows of the vector gradients.  (2) The weight gradients dW1 = dz^T u, dW2 = da^T h', dWid = dy^T u per block of
 // kFfnWgRows rows, u recomputed from x and the saved statistics.  (3) One fixed-order sum of the partials into the caller's
 // gradient tensors: stored, not accumulated.
@@ -38,85 +39,11 @@ struct FfnBwdArgs {
     int n, base;                 // base: the chunk's first row
 };
 
-// dst[0 .. 128) = the sum over the tile's rows of f(b, r), the lane's value at feature(b, r, h) of its row (rows past n add 0):
-// sum32_last over a wave's 32 rows, then the four waves in their order.  Every wave calls it together (two barriers)
-template <class F>
-__device__ __forceinline__ void ffn_tile_sum(F f, bool valid, float (*s_part)[128], float *dst, int t, int wv, int j, int h)
-{
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float s = sum32_last(valid ? f(b, r) : 0.f);
-            if (j == 31) s_part[wv][32 * b + 8 * (r >> 2) + 4 * h + (r & 3)] = s;
-        }
-    __syncthreads();
-    if (t < 128) dst[t] = (s_part[0][t] + s_part[1][t]) + (s_part[2][t] + s_part[3][t]);
-    __syncthreads();
-}
-
-// the lane's 64 values of a 128-float row, v, to / from memory as float4s
-__device__ __forceinline__ void ffn_store_row(float *p, const f32x16 (&v)[4], int h)
-{
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-            *reinterpret_cast<float4 *>(p + 32 * b + 8 * m + 4 * h) = make_float4(v[b][4 * m], v[b][4 * m + 1], v[b][4 * m + 2], v[b][4 * m + 3]);
-}
-__device__ __forceinline__ void ffn_load_block(f32x16 &v, const float *p, int h)
-{
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const float4 q = ld4(p + 8 * m + 4 * h);
-        v[4 * m] = q.x; v[4 * m + 1] = q.y; v[4 * m + 2] = q.z; v[4 * m + 3] = q.w;
-    }
-}
-
-// acc[fb] += (W^T g)'s features 32 fb ..: w points at W[o0][k0] of a row-major matrix with rows of ld floats, g holds the 128
-// features o0 .. o0 + 128 of the wave's rows, acc the features k0 .. k0 + 128.  W goes through LDS in four chunks of 32 rows o
-// (the features of g's register block c) x 128 floats, double buffered; step (c, r) sums over o = feature(c, r, 0 / 1) with g's
-// register as the B operand as it stands and W[o][32 fb + j] read along the row (gf_anchor_embed_bwd_kernel's product; pitch
-// 136: rows 4 apart lie 32 banks apart).  Every wave of the workgroup calls it together; it ends behind a barrier
-constexpr int kFfnTPitch = 136;
-__device__ __forceinline__ void ffn_product_t(f32x16 (&acc)[4], const f32x16 (&g)[4], const float *w, size_t ld, float *buf0, float *buf1,
-                                              int t, int j, int h)
-{
-    constexpr int NKB = 4, P = kFfnTPitch;
-    const int rr = t >> 3, fq = t & 7;
-    float4 pre[NKB];
-#pragma unroll
-    for (int i = 0; i < NKB; ++i) pre[i] = ld4(w + (size_t)rr * ld + 4 * (fq + 8 * i));
-#pragma unroll
-    for (int i = 0; i < NKB; ++i) *reinterpret_cast<float4 *>(buf0 + rr * P + 4 * (fq + 8 * i)) = pre[i];
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float *cur = c & 1 ? buf1 : buf0;
-        float *nxt = c & 1 ? buf0 : buf1;
-        if (c < 3) {
-#pragma unroll
-            for (int i = 0; i < NKB; ++i) pre[i] = ld4(w + (size_t)(32 * (c + 1) + rr) * ld + 4 * (fq + 8 * i));
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float *wrow = cur + (8 * (r >> 2) + 4 * h + (r & 3)) * P + j;
-#pragma unroll
-            for (int fb = 0; fb < NKB; ++fb) acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wrow[32 * fb], g[c][r], acc[fb], 0, 0, 0);
-        }
-        if (c < 3) {
-#pragma unroll
-            for (int i = 0; i < NKB; ++i) *reinterpret_cast<float4 *>(nxt + rr * P + 4 * (fq + 8 * i)) = pre[i];
-        }
-        __syncthreads();
-    }
-}
-
 template <int CIN>
 __global__ __launch_bounds__(256) void gf_ffn_bwd_kernel(FfnBwdArgs a)
 {
     constexpr int NB = CIN / 32;
-    constexpr int kFwdBuf = 128 * kRowPitch4 * 4, kTBuf = 32 * kFfnTPitch;    // floats: a forward chunk, a transposed chunk
+    constexpr int kFwdBuf = 128 * kRowPitch4 * 4, kTBuf = 32 * kRowTPitch;    // floats: a forward chunk, a transposed chunk
     constexpr int kBuf = kFwdBuf > kTBuf ? kFwdBuf : kTBuf;
     __shared__ float4 s_w[2][kBuf / 4];
     __shared__ float s_part[4][128];
@@ -131,65 +58,33 @@ __global__ __launch_bounds__(256) void gf_ffn_bwd_kernel(FfnBwdArgs a)
     // g = grad_out, then dy: the post norm's backward
     //     y^ = (y - mean) rstd,  dn = g gamma,  dy = rstd (dn - mean(dn) - y^ mean(dn y^))
     f32x16 g[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        if (valid) ffn_load_block(g[b], a.grad_out + row * kFfnE + 32 * b, h);
-        else
-#pragma unroll
-            for (int r = 0; r < 16; ++r) g[b][r] = 0.f;
-    }
+    load_row_or_zero(g, a.grad_out + row * kFfnE, valid, h);
     if (a.post_g) {
         const float2 ms = *reinterpret_cast<const float2 *>(a.stat_post + 2 * row);
         f32x16 nh[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            ffn_load_block(nh[b], a.ysave + row * kFfnE + 32 * b, h);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) nh[b][r] = (nh[b][r] - ms.x) * ms.y;
-        }
-        ffn_tile_sum([&](int b, int r) { return g[b][r] * nh[b][r]; }, valid, s_part, vp + kVpPostG, t, wv, j, h);
-        ffn_tile_sum([&](int b, int r) { return g[b][r]; }, valid, s_part, vp + kVpPostB, t, wv, j, h);
-        float p1[4], p2[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float4 gg = ld4(a.post_g + 32 * b + 8 * m + 4 * h);
-                const float gv[4] = {gg.x, gg.y, gg.z, gg.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float dn = g[b][4 * m + i] * gv[i];
-                    s1 += dn;
-                    s2 += dn * nh[b][4 * m + i];
-                    g[b][4 * m + i] = dn;
-                }
-            }
-            p1[b] = s1;
-            p2[b] = s2;
-        }
-        const float m1 = wave_xor_reduce_strided(tree_sum<4>(p1), 32, Sum()) * (1.f / kFfnE);
-        const float m2 = wave_xor_reduce_strided(tree_sum<4>(p2), 32, Sum()) * (1.f / kFfnE);
+        load_row(nh, a.ysave + row * kFfnE, h);
 #pragma unroll
         for (int b = 0; b < 4; ++b)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) g[b][r] = ms.y * (g[b][r] - m1 - nh[b][r] * m2);
+            for (int r = 0; r < 16; ++r) nh[b][r] = (nh[b][r] - ms.x) * ms.y;
+        tile_sum<4>([&](int b, int r) { return g[b][r] * nh[b][r]; }, valid, s_part, vp + kVpPostG, t, wv, j, h);
+        tile_sum<4>([&](int b, int r) { return g[b][r]; }, valid, s_part, vp + kVpPostB, t, wv, j, h);
+        ln_bwd_rows(g, nh, a.post_g, ms.y, h);
     }
     if (valid) {
-        ffn_store_row(a.dy + lrow * kFfnE, g, h);
-        if (a.grad_res) ffn_store_row(a.grad_res + row * kFfnE, g, h);
+        store_row_regs(a.dy + lrow * kFfnE, g, h);
+        if (a.grad_res) store_row_regs(a.grad_res + row * kFfnE, g, h);
     }
 
     // g = da = dy * (kept ? scale_out : 0)
-    if (a.wid) ffn_tile_sum([&](int b, int r) { return g[b][r]; }, valid, s_part, vp + kVpBid, t, wv, j, h);
+    if (a.wid) tile_sum<4>([&](int b, int r) { return g[b][r]; }, valid, s_part, vp + kVpBid, t, wv, j, h);
     if (a.keep_out) drop_rows(g, keep_bits(a.keep_out + row * kFfnE, h), a.scale_out);
-    if (valid) ffn_store_row(a.da + lrow * kFfnE, g, h);
-    ffn_tile_sum([&](int b, int r) { return g[b][r]; }, valid, s_part, vp + kVpB2, t, wv, j, h);
+    if (valid) store_row_regs(a.da + lrow * kFfnE, g, h);
+    tile_sum<4>([&](int b, int r) { return g[b][r]; }, valid, s_part, vp + kVpB2, t, wv, j, h);
 
     // Pass 1, the hidden slices: h' and dz of every slice, to the chunk's rows.  u, as the forward forms it
     f32x16 u[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) ffn_load_block(u[b], a.x + row * CIN + 32 * b, h);
+    load_row(u, a.x + row * CIN, h);
     if (a.pre_g) {
         float part[NB];
 #pragma unroll
@@ -208,10 +103,7 @@ __global__ __launch_bounds__(256) void gf_ffn_bwd_kernel(FfnBwdArgs a)
     for (int s = 0; s < kFfnSlices; ++s) {
         // h_s = relu(W1_s u + b1_s) by the forward's chain: chunk c of W1's rows 128 s .. against u's block c
         const float *w1s = a.w1 + (size_t)(128 * s) * CIN;
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) hid[b][r] = 0.f;
+        zero_rows(hid);
         chunk_fetch(pre, w1s, CIN, 0, t);
         chunk_stash(s_w[0], pre, t);
         __syncthreads();
@@ -241,54 +133,37 @@ __global__ __launch_bounds__(256) void gf_ffn_bwd_kernel(FfnBwdArgs a)
             kh = keep_bits(a.keep_hidden + row * kFfnF + 128 * s, h);
             drop_rows(hid, kh, a.scale_hidden);
         }
-        if (valid) ffn_store_row(a.hrows + lrow * kFfnF + 128 * s, hid, h);
+        if (valid) store_row_regs(a.hrows + lrow * kFfnF + 128 * s, hid, h);
 
         // dh_s = W2[:, 128 s ..]^T da, then dz_s
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) hid[b][r] = 0.f;
-        ffn_product_t(hid, g, a.w2 + 128 * s, kFfnF, buf0, buf1, t, j, h);
+        zero_rows(hid);
+        product_t<4, false>(hid, g, a.w2 + 128 * s, kFfnF, 0, buf0, buf1, t, j, h);
         if (a.keep_hidden) drop_rows(hid, kh, a.scale_hidden);
 #pragma unroll
         for (int b = 0; b < 4; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) hid[b][r] = (live >> (16 * b + r)) & 1u ? hid[b][r] : 0.f;
-        if (valid) ffn_store_row(a.dz + lrow * kFfnF + 128 * s, hid, h);
-        ffn_tile_sum([&](int b, int r) { return hid[b][r]; }, valid, s_part, vp + kVpB1 + 128 * s, t, wv, j, h);
+        if (valid) store_row_regs(a.dz + lrow * kFfnF + 128 * s, hid, h);
+        tile_sum<4>([&](int b, int r) { return hid[b][r]; }, valid, s_part, vp + kVpB1 + 128 * s, t, wv, j, h);
     }
 
     // Pass 2: du = Wid^T dy + sum over the slices of W1_s^T dz_s, from the rows the lane itself stored (u's registers are free
     // by now: u, du, da and a slice at once do not fit a wave's 512 registers at Cin = 256).  A row past n supplies zeros.
     // Each of the five products is a chain of its own from 0 and joins du by one addition: 128 terms a chain, not 640 in one
     // accumulator, whose rounding showed in the pre norm's bias gradient (a plain sum of du over the rows) at small n
-    f32x16 du[NB / 4][4];     // [group of 128 features][block]
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) du[b >> 2][b & 3][r] = 0.f;
+    f32x16 du[NB];
+    zero_rows(du);
     auto add_product = [&](const float *w) {      // du += W^T hid, W's 128 rows at w
 #pragma unroll
         for (int q = 0; q < NB / 4; ++q) {
             f32x16 acc[4];
+            zero_rows(acc);
+            product_t<4, false>(acc, hid, w + 128 * q, CIN, 0, buf0, buf1, t, j, h);
 #pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-            ffn_product_t(acc, hid, w + 128 * q, CIN, buf0, buf1, t, j, h);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) du[q][b] += acc[b];
+            for (int b = 0; b < 4; ++b) du[4 * q + b] += acc[b];
         }
     };
-    auto reload = [&](const float *p) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            if (valid) ffn_load_block(hid[b], p + 32 * b, h);
-            else
-#pragma unroll
-                for (int r = 0; r < 16; ++r) hid[b][r] = 0.f;
-        }
-    };
+    auto reload = [&](const float *p) { load_row_or_zero(hid, p, valid, h); };
     if (a.wid) {
         reload(a.dy + lrow * kFfnE);
         add_product(a.wid);
@@ -302,52 +177,19 @@ __global__ __launch_bounds__(256) void gf_ffn_bwd_kernel(FfnBwdArgs a)
     // the pre norm's backward on du, x^ formed again in u's registers
     if (a.pre_g) {
         const float2 ms = *reinterpret_cast<const float2 *>(a.stat_pre + 2 * row);
-        float p1[NB], p2[NB];
+        load_row(u, a.x + row * CIN, h);
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            ffn_load_block(u[b], a.x + row * CIN + 32 * b, h);
+        for (int b = 0; b < NB; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) u[b][r] = (u[b][r] - ms.x) * ms.y;
-        }
 #pragma unroll
         for (int q = 0; q < NB / 4; ++q) {
-            ffn_tile_sum([&](int b, int r) { return du[q][b][r] * u[4 * q + b][r]; }, valid, s_part, vp + kVpPre + 128 * q, t, wv, j, h);
-            ffn_tile_sum([&](int b, int r) { return du[q][b][r]; }, valid, s_part, vp + kVpPre + CIN + 128 * q, t, wv, j, h);
+            tile_sum<4>([&](int b, int r) { return du[4 * q + b][r] * u[4 * q + b][r]; }, valid, s_part, vp + kVpPre + 128 * q, t, wv, j, h);
+            tile_sum<4>([&](int b, int r) { return du[4 * q + b][r]; }, valid, s_part, vp + kVpPre + CIN + 128 * q, t, wv, j, h);
         }
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float4 gg = ld4(a.pre_g + 32 * b + 8 * m + 4 * h);
-                const float gv[4] = {gg.x, gg.y, gg.z, gg.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float dn = du[b >> 2][b & 3][4 * m + i] * gv[i];
-                    s1 += dn;
-                    s2 += dn * u[b][4 * m + i];
-                    du[b >> 2][b & 3][4 * m + i] = dn;
-                }
-            }
-            p1[b] = s1;
-            p2[b] = s2;
-        }
-        const float m1 = wave_xor_reduce_strided(tree_sum<NB>(p1), 32, Sum()) * (1.f / CIN);
-        const float m2 = wave_xor_reduce_strided(tree_sum<NB>(p2), 32, Sum()) * (1.f / CIN);
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) du[b >> 2][b & 3][r] = ms.y * (du[b >> 2][b & 3][r] - m1 - u[b][r] * m2);
+        ln_bwd_rows(du, u, a.pre_g, ms.y, h);
     }
-    if (valid) {
-        float *xrow = a.grad_x + row * CIN;
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                *reinterpret_cast<float4 *>(xrow + 32 * b + 8 * m + 4 * h) =
-                    make_float4(du[b >> 2][b & 3][4 * m], du[b >> 2][b & 3][4 * m + 1], du[b >> 2][b & 3][4 * m + 2], du[b >> 2][b & 3][4 * m + 3]);
-    }
+    if (valid) store_row_regs(a.grad_x + row * CIN, du, h);
 }
 
 struct FfnWgArgs {
@@ -400,56 +242,10 @@ __global__ __launch_bounds__(256) void gf_ffn_wgrad_kernel(FfnWgArgs a)
         ev[cb] = norm ? a.pre_b[kcol + 32 * cb + j] : 0.f;
     }
     f32x16 acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-    for (int r = r0; r < r1; r += 8) {
-        float av[4], xv[4][4];
-        float2 ms[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int row = min(r + 2 * q + h, r1 - 1);
-            av[q] = left[(size_t)(row - a.base) * ldl];
-            ms[q] = norm ? *reinterpret_cast<const float2 *>(a.stat_pre + (size_t)row * 2) : make_float2(0.f, 1.f);
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) xv[q][cb] = right[(size_t)(row - rsub) * ldr + 32 * cb];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool live = r + 2 * q + h < r1;
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                const float bv = norm ? (xv[q][cb] - ms[q].x) * ms[q].y * gv[cb] + ev[cb] : xv[q][cb];
-                acc[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(live ? av[q] : 0.f, live ? bv : 0.f, acc[cb], 0, 0, 0);
-            }
-        }
-    }
-    dst += j;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dst[(size_t)(32 * wv + 8 * (r >> 2) + 4 * h + (r & 3)) * ldd + 32 * cb] = acc[cb][r];
-}
-
-// dst[e] = sum over `count` partials, `stride` floats apart, in a fixed order (four interleaved running sums, then their
-// tree), as gf_anchor_embed_sum_kernel's.  count == 0 stores zeros.
-struct FfnSumJob { const float *src; float *dst; size_t stride; int count, len; };
-struct FfnSumArgs { FfnSumJob job[GF_FFN_PARAMS]; };
-__global__ __launch_bounds__(256) void gf_ffn_sum_kernel(FfnSumArgs a)
-{
-    const FfnSumJob &jb = a.job[blockIdx.y];
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= jb.len) return;
-    const float *src = jb.src + e;
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    int i = 0;
-    for (; i + 3 < jb.count; i += 4) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] += src[(size_t)(i + q) * jb.stride];
-    }
-    for (; i < jb.count; ++i) s[0] += src[(size_t)i * jb.stride];
-    jb.dst[e] = (s[0] + s[1]) + (s[2] + s[3]);
+    zero_rows(acc);
+    if (norm) wgrad_rows<kWgNorm>(acc, left, ldl, a.base, right, nullptr, ldr, rsub, a.stat_pre, gv, ev, r0, r1, r1, h);
+    else wgrad_rows<kWgAsIs>(acc, left, ldl, a.base, right, nullptr, ldr, rsub, nullptr, gv, ev, r0, r1, r1, h);
+    wgrad_store(dst, ldd, [&](int cb, int r) { return acc[cb][r]; }, wv, j, h);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
@@ -457,7 +253,7 @@ __global__ __launch_bounds__(256) void gf_ffn_sum_kernel(FfnSumArgs a)
 // a dropout's scale where its mask is given
 static int ffn_check_scale(const char *fn, const char *what, const unsigned char *keep, float scale)
 {
-    GF_FFN_REFUSE(!keep || (std::isfinite(scale) && scale > 0.f), "%s = %g is not a positive finite number", what, (double)scale);
+    GF_REFUSE_AS(fn, !keep || (std::isfinite(scale) && scale > 0.f), "%s = %g is not a positive finite number", what, (double)scale);
     return GF_OK;
 }
 
@@ -497,9 +293,9 @@ extern "C" int gf_ffn_train_sizes(int n, int Cin, size_t *saved_bytes, size_t *w
 {
     using namespace gf;
     const char *fn = __func__;
-    GF_FFN_REFUSE(Cin == 128 || Cin == 256, "Cin = %d: only in_channels = 128 or 256 is supported", Cin);
-    GF_FFN_REFUSE(n >= 0, "n = %d is negative", n);
-    GF_FFN_REFUSE(saved_bytes && workspace_bytes, "null pointer");
+    GF_REFUSE_AS(fn, Cin == 128 || Cin == 256, "Cin = %d: only in_channels = 128 or 256 is supported", Cin);
+    GF_REFUSE_AS(fn, n >= 0, "n = %d is negative", n);
+    GF_REFUSE_AS(fn, saved_bytes && workspace_bytes, "null pointer");
     *saved_bytes = ffn_carve_saved(nullptr, n).bytes;
     *workspace_bytes = ffn_carve_work(nullptr, n, Cin).bytes;
     return GF_OK;
@@ -514,10 +310,10 @@ extern "C" int gf_ffn_forward_train(int n, int Cin, int F, int E, const float *x
     if (int rc = ffn_check(fn, n, Cin, F, E, x, params, residual, out)) return rc;
     if (int rc = ffn_check_scale(fn, "scale_hidden", keep_hidden, scale_hidden)) return rc;
     if (int rc = ffn_check_scale(fn, "scale_out", keep_out, scale_out)) return rc;
-    GF_FFN_REFUSE(!ffn_misaligned(saved), "saved is not 16-byte aligned");
+    GF_REFUSE_AS(fn, !misaligned16(saved), "saved is not 16-byte aligned");
     if (n == 0) return GF_OK;
-    GF_FFN_REFUSE(x && out, "null pointer");
-    GF_FFN_REFUSE(saved, "saved is null");
+    GF_REFUSE_AS(fn, x && out, "null pointer");
+    GF_REFUSE_AS(fn, saved, "saved is null");
     const FfnSaved sv = ffn_carve_saved(saved, n);
     GF_CHECK_WORKSPACE_AS(fn, "saved", saved_bytes, sv.bytes);
     const float *const *p = reinterpret_cast<const float *const *>(params);
@@ -542,26 +338,26 @@ extern "C" int gf_ffn_backward(int n, int Cin, int F, int E, const float *x, con
     using namespace gf;
     const char *fn = __func__;
     if (int rc = ffn_check(fn, n, Cin, F, E, x, params, nullptr, nullptr)) return rc;
-    GF_FFN_REFUSE(!ffn_misaligned(grad_x), "grad_x is not 16-byte aligned");
-    GF_FFN_REFUSE(!ffn_misaligned(grad_residual), "grad_residual is not 16-byte aligned");
+    GF_REFUSE_AS(fn, !misaligned16(grad_x), "grad_x is not 16-byte aligned");
+    GF_REFUSE_AS(fn, !misaligned16(grad_residual), "grad_residual is not 16-byte aligned");
     if (int rc = ffn_check_scale(fn, "scale_hidden", keep_hidden, scale_hidden)) return rc;
     if (int rc = ffn_check_scale(fn, "scale_out", keep_out, scale_out)) return rc;
-    GF_FFN_REFUSE(grad_params, "null grad_params");
+    GF_REFUSE_AS(fn, grad_params, "null grad_params");
     const float *const *p = reinterpret_cast<const float *const *>(params);
     float *const *gp = reinterpret_cast<float *const *>(grad_params);
     for (int i = 0; i < GF_FFN_PARAMS; ++i) {
-        GF_FFN_REFUSE(!p[i] || gp[i], "the gradient of %s is null", kFfnName[i]);
-        GF_FFN_REFUSE(!p[i] || !ffn_misaligned(gp[i]), "the gradient of %s is not 16-byte aligned", kFfnName[i]);
+        GF_REFUSE_AS(fn, !p[i] || gp[i], "the gradient of %s is null", kFfnName[i]);
+        GF_REFUSE_AS(fn, !p[i] || !misaligned16(gp[i]), "the gradient of %s is not 16-byte aligned", kFfnName[i]);
     }
-    GF_FFN_REFUSE(!ffn_misaligned(grad_out), "grad_out is not 16-byte aligned");
-    GF_FFN_REFUSE(!ffn_misaligned(saved), "saved is not 16-byte aligned");
-    GF_FFN_REFUSE(!ffn_misaligned(workspace), "workspace is not 16-byte aligned");
+    GF_REFUSE_AS(fn, !misaligned16(grad_out), "grad_out is not 16-byte aligned");
+    GF_REFUSE_AS(fn, !misaligned16(saved), "saved is not 16-byte aligned");
+    GF_REFUSE_AS(fn, !misaligned16(workspace), "workspace is not 16-byte aligned");
     const FfnSaved sv = ffn_carve_saved(n > 0 ? const_cast<void *>(saved) : nullptr, n);
     const FfnWork ws = ffn_carve_work(n > 0 ? workspace : nullptr, n, Cin);
     if (n > 0) {
-        GF_FFN_REFUSE(x && grad_out && grad_x, "null pointer");
-        GF_FFN_REFUSE(saved, "saved is null");
-        GF_FFN_REFUSE(workspace, "workspace is null");
+        GF_REFUSE_AS(fn, x && grad_out && grad_x, "null pointer");
+        GF_REFUSE_AS(fn, saved, "saved is null");
+        GF_REFUSE_AS(fn, workspace, "workspace is null");
         GF_CHECK_WORKSPACE_AS(fn, "workspace", workspace_bytes, ws.bytes);
     }
     hipStream_t stream = (hipStream_t)stream_;
@@ -590,14 +386,14 @@ extern "C" int gf_ffn_backward(int n, int Cin, int F, int E, const float *x, con
         }
     }
     // n == 0: no partials, the sums store zeros
-    FfnSumArgs sa{};
+    RowsSumArgs<GF_FFN_PARAMS> sa{};   // float sums, a thread per element
     int nj = 0;
     const int vlen = ffn_vpart_len(Cin);
     auto vec = [&](int i, int at, int len) {
-        if (p[i]) sa.job[nj++] = FfnSumJob{n > 0 ? ws.vpart + at : nullptr, gp[i], (size_t)vlen, n > 0 ? ws.tiles : 0, len};
+        if (p[i]) sa.job[nj++] = RowsSumJob{n > 0 ? ws.vpart + at : nullptr, gp[i], (size_t)vlen, n > 0 ? ws.tiles : 0, len, 0, 1};
     };
     auto mat = [&](int i, size_t at, int len) {
-        if (p[i]) sa.job[nj++] = FfnSumJob{n > 0 ? ws.wpart + at : nullptr, gp[i], ffn_wpart_len(Cin), n > 0 ? ws.blocks : 0, len};
+        if (p[i]) sa.job[nj++] = RowsSumJob{n > 0 ? ws.wpart + at : nullptr, gp[i], ffn_wpart_len(Cin), n > 0 ? ws.blocks : 0, len, 0, 1};
     };
     vec(0, kVpPre, Cin);
     vec(1, kVpPre + Cin, Cin);
@@ -609,7 +405,7 @@ extern "C" int gf_ffn_backward(int n, int Cin, int F, int E, const float *x, con
     vec(7, kVpBid, kFfnE);
     vec(8, kVpPostG, kFfnE);
     vec(9, kVpPostB, kFfnE);
-    hipLaunchKernelGGL(gf_ffn_sum_kernel, dim3(kFfnF * Cin / 256, nj), dim3(256), 0, stream, sa);
+    hipLaunchKernelGGL((rows_sum_kernel<float, GF_FFN_PARAMS>), dim3(kFfnF * Cin / 256, nj), dim3(256), 0, stream, sa);
     GF_CHECK_LAUNCH();
     return GF_OK;
 }

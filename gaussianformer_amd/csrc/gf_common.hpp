@@ -228,6 +228,16 @@ bool profile_slot(hipEvent_t *before, hipEvent_t *after);  // gf_api.hip
         }                                      \
     } while (0)
 #define GF_CHECK_ARG(cond, msg) GF_CHECK_ARG_AS(__func__, cond, msg)
+// ... with a formatted message, under the name `fn` of the entry point that was called
+#define GF_REFUSE_AS(fn, cond, fmt, ...)                                \
+    do {                                                               \
+        if (!(cond)) {                                                 \
+            gf::set_error("%s: " fmt, fn, ##__VA_ARGS__);              \
+            return GF_EINVAL;                                          \
+        }                                                              \
+    } while (0)
+// the kernels move rows as float4s: what every row pointer and parameter must not be (null is aligned)
+inline bool misaligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 #define GF_CHECK_LAUNCH_AS(fn)                                                 \
     do {                                                                       \

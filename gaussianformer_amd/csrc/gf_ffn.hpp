@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void gf_ffn_kernel(typename FfnFwdArgs<TRAIN>:
         put(vPost + 32, a.post_b, 32);
     }
     f32x16 u[NB];
-    {
+    {   // (not load_row: with it the plain kernel comes out with another instruction order)
         const float *xrow = a.x + row * CIN;
 #pragma unroll
         for (int b = 0; b < NB; ++b)
@@ -217,12 +217,7 @@ __global__ __launch_bounds__(256) void gf_ffn_kernel(typename FfnFwdArgs<TRAIN>:
         if constexpr (TRAIN) {
             if (valid) {
                 st2 = a.stat_post + 2 * row;
-                float *yrow = a.ysave + row * kFfnE;
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-#pragma unroll
-                    for (int m = 0; m < 4; ++m)
-                        *reinterpret_cast<float4 *>(yrow + 32 * b + 8 * m + 4 * h) = make_float4(y[b][4 * m], y[b][4 * m + 1], y[b][4 * m + 2], y[b][4 * m + 3]);
+                store_row_regs(a.ysave + row * kFfnE, y, h);
             }
         }
         ln_rows<true, 4>(y, tree_sum<4>(part), s_vec + vPost, s_vec + vPost + 32, h, st2);
@@ -234,36 +229,28 @@ __global__ __launch_bounds__(256) void gf_ffn_kernel(typename FfnFwdArgs<TRAIN>:
 
 inline constexpr const char *kFfnName[GF_FFN_PARAMS] = {"pre_norm.weight", "pre_norm.bias", "layers.0.0.weight", "layers.0.0.bias", "layers.1.weight",
                                                     "layers.1.bias", "identity_fc.weight", "identity_fc.bias", "norm.weight", "norm.bias"};
-#define GF_FFN_REFUSE(cond, fmt, ...)                                  \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            gf::set_error("%s: " fmt, fn, ##__VA_ARGS__);              \
-            return GF_EINVAL;                                          \
-        }                                                              \
-    } while (0)
-inline bool ffn_misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 // what all three launching entry points refuse, in gf_ffn_forward's order and words, under the name of the one that was called
 inline int ffn_check(const char *fn, int n, int Cin, int F, int E, const float *x, const void *const *params, const float *residual,
                      const float *out)
 {
-    GF_FFN_REFUSE(E == kFfnE, "E = %d: only embed_dims = 128 is supported", E);
-    GF_FFN_REFUSE(F == kFfnF, "F = %d: only feedforward_channels = 512 is supported", F);
-    GF_FFN_REFUSE(Cin == 128 || Cin == 256, "Cin = %d: only in_channels = 128 or 256 is supported", Cin);
-    GF_FFN_REFUSE(n >= 0, "n = %d is negative", n);
-    GF_FFN_REFUSE(params, "null params");
+    GF_REFUSE_AS(fn, E == kFfnE, "E = %d: only embed_dims = 128 is supported", E);
+    GF_REFUSE_AS(fn, F == kFfnF, "F = %d: only feedforward_channels = 512 is supported", F);
+    GF_REFUSE_AS(fn, Cin == 128 || Cin == 256, "Cin = %d: only in_channels = 128 or 256 is supported", Cin);
+    GF_REFUSE_AS(fn, n >= 0, "n = %d is negative", n);
+    GF_REFUSE_AS(fn, params, "null params");
     const float *const *p = reinterpret_cast<const float *const *>(params);
     for (int i = 0; i < GF_FFN_PARAMS; i += 2) {
         if (i == 2 || i == 4) {
-            GF_FFN_REFUSE(p[i], "%s is missing", kFfnName[i]);
-            GF_FFN_REFUSE(p[i + 1], "%s is missing", kFfnName[i + 1]);
+            GF_REFUSE_AS(fn, p[i], "%s is missing", kFfnName[i]);
+            GF_REFUSE_AS(fn, p[i + 1], "%s is missing", kFfnName[i + 1]);
         }
-        GF_FFN_REFUSE(!p[i] == !p[i + 1], "a half-present pair: %s is null and %s is not", kFfnName[p[i] ? i + 1 : i], kFfnName[p[i] ? i : i + 1]);
-        for (int k = i; k < i + 2; ++k) GF_FFN_REFUSE(!ffn_misaligned(p[k]), "%s is not 16-byte aligned", kFfnName[k]);
+        GF_REFUSE_AS(fn, !p[i] == !p[i + 1], "a half-present pair: %s is null and %s is not", kFfnName[p[i] ? i + 1 : i], kFfnName[p[i] ? i : i + 1]);
+        for (int k = i; k < i + 2; ++k) GF_REFUSE_AS(fn, !misaligned16(p[k]), "%s is not 16-byte aligned", kFfnName[k]);
     }
-    GF_FFN_REFUSE(!ffn_misaligned(x), "x is not 16-byte aligned");
-    GF_FFN_REFUSE(!ffn_misaligned(residual), "residual is not 16-byte aligned");
-    GF_FFN_REFUSE(!ffn_misaligned(out), "out is not 16-byte aligned");
+    GF_REFUSE_AS(fn, !misaligned16(x), "x is not 16-byte aligned");
+    GF_REFUSE_AS(fn, !misaligned16(residual), "residual is not 16-byte aligned");
+    GF_REFUSE_AS(fn, !misaligned16(out), "out is not 16-byte aligned");
     return GF_OK;
 }
 }  // namespace gf

@@ -254,30 +254,21 @@ static const char *const kRmName[GF_REFINE_MLP_PARAMS] = {
     "layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias", "layers.4.weight", "layers.4.bias", "layers.5.weight", "layers.5.bias",
     "layers.7.weight", "layers.7.bias", "layers.9.weight", "layers.9.bias", "layers.10.weight", "layers.10.bias", "layers.11.scale"};
 
-#define GF_RM_REFUSE(cond, fmt, ...)                                   \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            gf::set_error("%s: " fmt, fn, ##__VA_ARGS__);              \
-            return GF_EINVAL;                                          \
-        }                                                              \
-    } while (0)
-inline bool rm_misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 // what every launching entry point of the MLP refuses of its inputs once n > 0, in gf_refine_mlp_forward's order and words,
 // under the name of the one that was called
 inline int refine_mlp_check_inputs(const char *fn, const void *const *params, const float *instance_feature, const float *anchor_embed,
                                    const float *anchor)
 {
-    GF_RM_REFUSE(params, "null params");
+    GF_REFUSE_AS(fn, params, "null params");
     for (int i = 0; i < GF_REFINE_MLP_PARAMS; ++i) {
-        GF_RM_REFUSE(params[i], "params[%d] (%s) is null", i, kRmName[i]);
-        GF_RM_REFUSE(!rm_misaligned(params[i]), "params[%d] (%s) = %p is not 16-byte aligned", i, kRmName[i], params[i]);
+        GF_REFUSE_AS(fn, params[i], "params[%d] (%s) is null", i, kRmName[i]);
+        GF_REFUSE_AS(fn, !misaligned16(params[i]), "params[%d] (%s) = %p is not 16-byte aligned", i, kRmName[i], params[i]);
     }
-    GF_RM_REFUSE(instance_feature, "null instance_feature");
-    GF_RM_REFUSE(anchor_embed, "null anchor_embed");
-    GF_RM_REFUSE(anchor, "null anchor");
-    GF_RM_REFUSE(!rm_misaligned(instance_feature), "instance_feature = %p is not 16-byte aligned", (const void *)instance_feature);
-    GF_RM_REFUSE(!rm_misaligned(anchor_embed), "anchor_embed = %p is not 16-byte aligned", (const void *)anchor_embed);
+    GF_REFUSE_AS(fn, instance_feature, "null instance_feature");
+    GF_REFUSE_AS(fn, anchor_embed, "null anchor_embed");
+    GF_REFUSE_AS(fn, anchor, "null anchor");
+    GF_REFUSE_AS(fn, !misaligned16(instance_feature), "instance_feature = %p is not 16-byte aligned", (const void *)instance_feature);
+    GF_REFUSE_AS(fn, !misaligned16(anchor_embed), "anchor_embed = %p is not 16-byte aligned", (const void *)anchor_embed);
     return GF_OK;
 }
 

@@ -1,4 +1,5 @@
-// gf_rows.hpp -- what the row-wise MFMA kernels share (anchor_embed.hip, ffn.hip, refine_mlp.hip, refine_mlp_train.hip, deform_dense.hip;
+// gf_rows.hpp -- what the row-wise MFMA kernels share (anchor_embed.hip, ffn.hip, ffn_train.hip, refine_mlp.hip, refine_mlp_train.hip,
+// deform_dense.hip; the training backwards' parts on the same layout: gf_rows_bwd.hpp;
 // DESIGN.md §3.12b, §3.12c, §3.13, §3.13c, §3.13e): the register layout in which a wave holds 32 rows of 128-feature blocks, the LayerNorm on it, the staging of a
 // weight chunk through LDS, the chunk's 64 MFMAs and the store of a finished tile.
 //
@@ -239,16 +240,42 @@ __device__ __forceinline__ void store_cols(float *so, const f32x16 (&x)[NFB], fl
     }
 }
 
-// x <- the lane's 64 features of the row at xrow (128 floats, 16-byte aligned), in the layout above
-__device__ __forceinline__ void load_row(f32x16 (&x)[4], const float *xrow, int h)
+// The lane's 16 NB values of NB blocks of its row, in the layout above, from / to the row at p (32 NB floats, 16-byte aligned)
+// as float4s
+template <int NB>
+__device__ __forceinline__ void load_row(f32x16 (&x)[NB], const float *p, int h)
 {
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int b = 0; b < NB; ++b)
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            const float4 v = ld4(xrow + 32 * b + 8 * m + 4 * h);
+            const float4 v = ld4(p + 32 * b + 8 * m + 4 * h);
             x[b][4 * m] = v.x; x[b][4 * m + 1] = v.y; x[b][4 * m + 2] = v.z; x[b][4 * m + 3] = v.w;
         }
+}
+template <int NB>
+__device__ __forceinline__ void store_row_regs(float *p, const f32x16 (&x)[NB], int h)
+{
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+            *reinterpret_cast<float4 *>(p + 32 * b + 8 * m + 4 * h) = make_float4(x[b][4 * m], x[b][4 * m + 1], x[b][4 * m + 2], x[b][4 * m + 3]);
+}
+template <int NB>
+__device__ __forceinline__ void zero_rows(f32x16 (&x)[NB])
+{
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) x[b][r] = 0.f;
+}
+// load_row where the lane has a row, zeros where it has none (nothing is loaded then)
+template <int NB>
+__device__ __forceinline__ void load_row_or_zero(f32x16 (&x)[NB], const float *p, bool valid, int h)
+{
+    if (valid) load_row(x, p, h);
+    else zero_rows(x);
 }
 
 }  // namespace gf

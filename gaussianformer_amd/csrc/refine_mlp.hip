@@ -152,14 +152,7 @@ __global__ __launch_bounds__(256, 2) void gf_refine_mlp_kernel(std::conditional_
                 relu_ln<true>(acc, p, h, rrow, a.sv_stat + ((size_t)(q >> 1) * n + row) * 2);
             } else {
                 bias_relu(acc, p, h);
-                if (rrow) {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-#pragma unroll
-                        for (int m = 0; m < 4; ++m)
-                            *reinterpret_cast<float4 *>(rrow + 32 * b + 8 * m + 4 * h) =
-                                make_float4(acc[b][4 * m], acc[b][4 * m + 1], acc[b][4 * m + 2], acc[b][4 * m + 3]);
-                }
+                if (rrow) store_row_regs(rrow, acc, h);
             }
         } else {
             if (q & 1) relu_ln<false>(acc, p, h);      // layers.2 -> .3 -> .4, layers.7 -> .8 -> .9
@@ -245,14 +238,14 @@ static int refine_mlp_run(const char *fn, int n, int E, int D, int Da, int versi
 {
     RefineMlpTrainArgs a{};
     if (int rc = refine_fill_args(a.r, fn, n, D, Da, version, flags, R, S, consts)) return rc;
-    GF_RM_REFUSE(E == kRmE, "E = %d: only embed_dims = 128 is supported", E);
+    GF_REFUSE_AS(fn, E == kRmE, "E = %d: only embed_dims = 128 is supported", E);
     if (n == 0) return GF_OK;
     if (int rc = refine_mlp_check_inputs(fn, params, instance_feature, anchor_embed, anchor)) return rc;
     GF_CHECK_ARG_AS(fn, refine_forward_outputs_present(version, flags, S, anchor_out, means, scales, rotations, opacities, semantics, original_means, delta_means),
                     "null pointer");
     if (train) {
-        GF_RM_REFUSE(saved, "saved is null");
-        GF_RM_REFUSE(!rm_misaligned(saved), "saved = %p is not 16-byte aligned", saved);
+        GF_REFUSE_AS(fn, saved, "saved is null");
+        GF_REFUSE_AS(fn, !misaligned16(saved), "saved = %p is not 16-byte aligned", saved);
         const RefineMlpSaved sv = refine_mlp_carve_saved(saved, n, D);
         GF_CHECK_WORKSPACE_AS(fn, "saved", saved_bytes, sv.bytes);
         a.sv_rows = sv.rows; a.sv_stat = sv.stat; a.sv_y = sv.y; a.sv_o = sv.o;

@@ -10,7 +10,7 @@
 // block of kRmWgRows rows, x_s formed again from what was saved as the forward applies it.  (3) One fixed-order sum of the
 // partials into the caller's 15 gradient tensors: stored, not accumulated.
 #include "gf_refine.hpp"
-#include "gf_rows.hpp"
+#include "gf_rows_bwd.hpp"
 
 namespace gf {
 
@@ -38,103 +38,9 @@ struct RmBwdArgs {
     int n, D, base, crows;           // base: the chunk's first row
 };
 
-// dst[0 .. 32 NB) = the sum over the tile's rows of f(b, r), the lane's value at feature(b, r, h) of its row (rows past n add
-// 0): sum32_last over a wave's 32 rows, then the four waves in their order.  Every wave calls it together (two barriers)
-template <int NB, class F>
-__device__ __forceinline__ void rm_tile_sum(F f, bool valid, float (*s_part)[kRmE], float *dst, int t, int wv, int j, int h)
-{
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float s = sum32_last(valid ? f(b, r) : 0.f);
-            if (j == 31) s_part[wv][32 * b + 8 * (r >> 2) + 4 * h + (r & 3)] = s;
-        }
-    __syncthreads();
-    if (t < 32 * NB) dst[t] = (s_part[0][t] + s_part[1][t]) + (s_part[2][t] + s_part[3][t]);
-    __syncthreads();
-}
-
-// the lane's values of NB blocks of its row, to / from memory as float4s
-template <int NB>
-__device__ __forceinline__ void rm_store_row(float *p, const f32x16 (&v)[NB], int h)
-{
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-            *reinterpret_cast<float4 *>(p + 32 * b + 8 * m + 4 * h) = make_float4(v[b][4 * m], v[b][4 * m + 1], v[b][4 * m + 2], v[b][4 * m + 3]);
-}
-template <int NB>
-__device__ __forceinline__ void rm_load_row(f32x16 (&v)[NB], const float *p, int h)
-{
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float4 q = ld4(p + 32 * b + 8 * m + 4 * h);
-            v[b][4 * m] = q.x; v[b][4 * m + 1] = q.y; v[b][4 * m + 2] = q.z; v[b][4 * m + 3] = q.w;
-        }
-}
-
-// acc[fb] += (W^T g)'s features 32 fb ..: W [nrows, 128] row-major, g holds the features 0 .. 32 NC of the wave's rows, acc the
-// 128 input features.  A local copy of ffn_train.hip's ffn_product_t (that one stays where it is: its translation unit's
-// assembly is not touched) with two differences: NC chunks of 32 rows o instead of four, and W's rows from nrows on supplied as
-// zero -- the row index is clamped and the value masked, nothing beyond the tensor is loaded.  W goes through LDS in chunks of
-// 32 rows x 128 floats, double buffered; step (c, r) sums over o = feature(c, r, 0 / 1) with g's register as the B operand as
-// it stands and W[o][32 fb + j] read along the row (pitch 136: rows 4 apart lie 32 banks apart).  Every wave of the workgroup
-// calls it together; it ends behind a barrier
-constexpr int kRmTPitch = 136;
-template <int NC>
-__device__ __forceinline__ void rm_product_t(f32x16 (&acc)[4], const f32x16 (&g)[NC], const float *w, int nrows, float *buf0, float *buf1,
-                                             int t, int j, int h)
-{
-    constexpr int P = kRmTPitch;
-    const int rr = t >> 3, fq = t & 7;
-    float4 pre[4];
-    auto fetch = [&](int c) {
-        const int o = 32 * c + rr;
-        const float *src = w + (size_t)min(o, nrows - 1) * kRmE;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 v = ld4(src + 4 * (fq + 8 * i));
-            pre[i] = o < nrows ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    fetch(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *reinterpret_cast<float4 *>(buf0 + rr * P + 4 * (fq + 8 * i)) = pre[i];
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const float *cur = c & 1 ? buf1 : buf0;
-        float *nxt = c & 1 ? buf0 : buf1;
-        if (c + 1 < NC) fetch(c + 1);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float *wrow = cur + (8 * (r >> 2) + 4 * h + (r & 3)) * P + j;
-#pragma unroll
-            for (int fb = 0; fb < 4; ++fb) acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wrow[32 * fb], g[c][r], acc[fb], 0, 0, 0);
-        }
-        if (c + 1 < NC) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) *reinterpret_cast<float4 *>(nxt + rr * P + 4 * (fq + 8 * i)) = pre[i];
-        }
-        __syncthreads();
-    }
-}
-
-__device__ __forceinline__ void rm_zero(f32x16 (&v)[4])
-{
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[b][r] = 0.f;
-}
-
 __global__ __launch_bounds__(256) void gf_refine_mlp_bwd_kernel(RmBwdArgs a)
 {
-    __shared__ float4 s_w[2][32 * kRmTPitch / 4];
+    __shared__ float4 s_w[2][32 * kRowTPitch / 4];
     __shared__ float s_part[4][kRmE];
     float *buf0 = reinterpret_cast<float *>(s_w[0]), *buf1 = reinterpret_cast<float *>(s_w[1]);
     const int t = threadIdx.x, l = t & 63, wv = t >> 6, j = l & 31, h = l >> 5;
@@ -150,7 +56,7 @@ __global__ __launch_bounds__(256) void gf_refine_mlp_bwd_kernel(RmBwdArgs a)
     // from D on carry zeros
     {
         f32x16 gy[2], yv[2];
-        rm_load_row<2>(yv, a.y + row * kRmYPitch, h);
+        load_row(yv, a.y + row * kRmYPitch, h);
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -161,18 +67,18 @@ __global__ __launch_bounds__(256) void gf_refine_mlp_bwd_kernel(RmBwdArgs a)
                 yv[b][r] = in ? gv * yv[b][r] : 0.f;
                 gy[b][r] = in ? gv * sc : 0.f;
             }
-        rm_tile_sum<2>([&](int b, int r) { return yv[b][r]; }, valid, s_part, vp + kRmVScale, t, wv, j, h);
-        rm_tile_sum<2>([&](int b, int r) { return gy[b][r]; }, valid, s_part, vp + kRmVB10, t, wv, j, h);
-        if (valid) rm_store_row<2>(a.dz4 + lrow * kRmYPitch, gy, h);
-        rm_zero(acc);
-        rm_product_t<2>(acc, gy, a.w[4], D, buf0, buf1, t, j, h);
+        tile_sum<2>([&](int b, int r) { return yv[b][r]; }, valid, s_part, vp + kRmVScale, t, wv, j, h);
+        tile_sum<2>([&](int b, int r) { return gy[b][r]; }, valid, s_part, vp + kRmVB10, t, wv, j, h);
+        if (valid) store_row_regs(a.dz4 + lrow * kRmYPitch, gy, h);
+        zero_rows(acc);
+        product_t<2, true>(acc, gy, a.w[4], kRmE, D, buf0, buf1, t, j, h);
     }
 
     // the four square stages, last first: acc holds the gradient of the stage's output (behind the LayerNorm where it has one)
 #pragma unroll 1
     for (int q = 3; q >= 0; --q) {
         // the stage's saved post-ReLU row, and where it passes a gradient
-        rm_load_row<4>(g, a.rows + ((size_t)q * n + row) * kRmE, h);
+        load_row(g, a.rows + ((size_t)q * n + row) * kRmE, h);
         uint64_t live = 0;       // bit 16 b + r
 #pragma unroll
         for (int b = 0; b < 4; ++b)
@@ -181,51 +87,26 @@ __global__ __launch_bounds__(256) void gf_refine_mlp_bwd_kernel(RmBwdArgs a)
         if (q & 1) {
             // the LayerNorm's backward: r^ = (r - mean) rstd, dn = acc gamma, dr = rstd (dn - mean(dn) - r^ mean(dn r^))
             const float2 ms = *reinterpret_cast<const float2 *>(a.stat + ((size_t)(q >> 1) * n + row) * 2);
-            const float *gam = a.ln_g[q >> 1];
 #pragma unroll
             for (int b = 0; b < 4; ++b)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) g[b][r] = (g[b][r] - ms.x) * ms.y;
             float *vln = vp + kRmVLn + 2 * kRmE * (q >> 1);
-            rm_tile_sum<4>([&](int b, int r) { return acc[b][r] * g[b][r]; }, valid, s_part, vln, t, wv, j, h);
-            rm_tile_sum<4>([&](int b, int r) { return acc[b][r]; }, valid, s_part, vln + kRmE, t, wv, j, h);
-            float p1[4], p2[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const float4 gg = ld4(gam + 32 * b + 8 * m + 4 * h);
-                    const float gv[4] = {gg.x, gg.y, gg.z, gg.w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float dn = acc[b][4 * m + i] * gv[i];
-                        s1 += dn;
-                        s2 += dn * g[b][4 * m + i];
-                        acc[b][4 * m + i] = dn;
-                    }
-                }
-                p1[b] = s1;
-                p2[b] = s2;
-            }
-            const float m1 = wave_xor_reduce_strided(tree_sum<4>(p1), 32, Sum()) * (1.f / kRmE);
-            const float m2 = wave_xor_reduce_strided(tree_sum<4>(p2), 32, Sum()) * (1.f / kRmE);
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[b][r] = ms.y * (acc[b][r] - m1 - g[b][r] * m2);
+            tile_sum<4>([&](int b, int r) { return acc[b][r] * g[b][r]; }, valid, s_part, vln, t, wv, j, h);
+            tile_sum<4>([&](int b, int r) { return acc[b][r]; }, valid, s_part, vln + kRmE, t, wv, j, h);
+            ln_bwd_rows(acc, g, a.ln_g[q >> 1], ms.y, h);
         }
         // dz = the ReLU's backward; a row past n carries zeros
 #pragma unroll
         for (int b = 0; b < 4; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) g[b][r] = valid && ((live >> (16 * b + r)) & 1u) ? acc[b][r] : 0.f;
-        if (valid) rm_store_row<4>(a.dz + ((size_t)q * a.crows + lrow) * kRmE, g, h);
-        rm_tile_sum<4>([&](int b, int r) { return g[b][r]; }, valid, s_part, vp + kRmVBias + kRmE * q, t, wv, j, h);
-        rm_zero(acc);
-        rm_product_t<4>(acc, g, a.w[q], kRmE, buf0, buf1, t, j, h);
+        if (valid) store_row_regs(a.dz + ((size_t)q * a.crows + lrow) * kRmE, g, h);
+        tile_sum<4>([&](int b, int r) { return g[b][r]; }, valid, s_part, vp + kRmVBias + kRmE * q, t, wv, j, h);
+        zero_rows(acc);
+        product_t<4, false>(acc, g, a.w[q], kRmE, 0, buf0, buf1, t, j, h);
     }
-    if (valid) rm_store_row<4>(a.grad_x + row * kRmE, acc, h);
+    if (valid) store_row_regs(a.grad_x + row * kRmE, acc, h);
 }
 
 struct RmWgArgs {
@@ -241,9 +122,8 @@ struct RmWgArgs {
 // 0-31 one, lanes 32-63 the other), loaded from the row-major arrays as they lie; a wave owns 32 rows o.  x_s: s = 0 the sum of
 // the two inputs, s = 1, 3 the saved post-ReLU rows 0, 2, s = 2, 4 the LayerNorm of the saved rows 1, 3 from its saved
 // (mean, rstd), in the saving forward's expression.  Job 4 (layers.10) has 64 rows o: waves 2 and 3 have nothing to do.  A lane
-// beyond the block's rows supplies 0 (a select) and loads the block's last row.  (gf_ffn_wgrad_kernel's scheme.)
-// (KIND: 0 the sum of the two inputs, 1 saved rows as they are, 2 their LayerNorm -- a template, so the row loop has no branch
-// in it and its loads go out together)
+// beyond the block's rows supplies 0 (a select) and loads the block's last row.  (KIND: wgrad_rows' -- kWgSum the sum of the two
+// inputs, kWgAsIs saved rows as they are, kWgNorm their LayerNorm)
 template <int KIND>
 __device__ __forceinline__ void rm_wgrad_job(const RmWgArgs &a, int s)
 {
@@ -254,13 +134,13 @@ __device__ __forceinline__ void rm_wgrad_job(const RmWgArgs &a, int s)
     const float *left = s < 4 ? a.dz + (size_t)s * a.crows * kRmE : a.dz4;
     const size_t ldl = s < 4 ? kRmE : kRmYPitch;
     left += 32 * wv + j;
-    const float *right = (KIND == 0 ? a.feat : a.rows + (size_t)(s - 1) * n * kRmE) + j, *right2 = a.embed + j;
+    const float *right = (KIND == kWgSum ? a.feat : a.rows + (size_t)(s - 1) * n * kRmE) + j, *right2 = a.embed + j;
     const float *stat = a.stat + (size_t)(s == 4 ? 1 : 0) * n * 2;
     float gv[4], ev[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
-        gv[cb] = KIND == 2 ? a.ln_g[s == 4][32 * cb + j] : 1.f;
-        ev[cb] = KIND == 2 ? a.ln_b[s == 4][32 * cb + j] : 0.f;
+        gv[cb] = KIND == kWgNorm ? a.ln_g[s == 4][32 * cb + j] : 1.f;
+        ev[cb] = KIND == kWgNorm ? a.ln_b[s == 4][32 * cb + j] : 0.f;
     }
     // Two levels: an fp32 MFMA chain over kRmWgFlush rows, then the chains of the block join in double and the block's partial is
     // rounded once.  One chain over all 512 rows left the last Linear's gradients at n = 33 350 at 2.5 times the error of
@@ -273,95 +153,22 @@ __device__ __forceinline__ void rm_wgrad_job(const RmWgArgs &a, int s)
         for (int r = 0; r < 16; ++r) outer[cb][r] = 0.0;
 #pragma unroll 1
     for (int rb = r0; rb < r1; rb += kRmWgFlush) {
-        const int re = min(r1, rb + kRmWgFlush);
-        rm_zero(acc);
-        for (int r = rb; r < re; r += 8) {
-            float av[4], xv[4][4];
-            float2 ms[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int row = min(r + 2 * q + h, r1 - 1);
-                av[q] = left[(size_t)(row - a.base) * ldl];
-                if constexpr (KIND == 2) ms[q] = *reinterpret_cast<const float2 *>(stat + (size_t)row * 2);
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) {
-                    xv[q][cb] = right[(size_t)row * kRmE + 32 * cb];
-                    if constexpr (KIND == 0) xv[q][cb] = xv[q][cb] + right2[(size_t)row * kRmE + 32 * cb];
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const bool live = r + 2 * q + h < r1;
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) {
-                    float bv = xv[q][cb];
-                    if constexpr (KIND == 2) bv = __builtin_fmaf((bv - ms[q].x) * ms[q].y, gv[cb], ev[cb]);
-                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(live ? av[q] : 0.f, live ? bv : 0.f, acc[cb], 0, 0, 0);
-                }
-            }
-        }
+        zero_rows(acc);
+        wgrad_rows<KIND>(acc, left, ldl, a.base, right, right2, kRmE, 0, stat, gv, ev, rb, min(r1, rb + kRmWgFlush), r1, h);
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) outer[cb][r] += (double)acc[cb][r];
     }
-    float *dst = a.wpart + (size_t)blk * kRmWLen + (size_t)s * kRmE * kRmE + j;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dst[(size_t)(32 * wv + 8 * (r >> 2) + 4 * h + (r & 3)) * kRmE + 32 * cb] = (float)outer[cb][r];
+    wgrad_store(a.wpart + (size_t)blk * kRmWLen + (size_t)s * kRmE * kRmE, kRmE, [&](int cb, int r) { return (float)outer[cb][r]; }, wv, j, h);
 }
 
 __global__ __launch_bounds__(256, 2) void gf_refine_mlp_wgrad_kernel(RmWgArgs a)
 {
     const int s = blockIdx.y;
-    if (s == 0) rm_wgrad_job<0>(a, s);
-    else if (s & 1) rm_wgrad_job<1>(a, s);
-    else rm_wgrad_job<2>(a, s);
-}
-
-// dst[e] = the sum over `count` partials, `stride` floats apart, in a fixed order, accumulated in double and rounded once (the
-// partials are fp32 sums over 128 or 512 rows; at 144 000 rows there are 1 125 or 282 of them).  slots == 1 (the matrices:
-// many elements, few partials): a thread per element, four interleaved running sums, then their tree, as gf_ffn_sum_kernel's.
-// slots == kRmSumSlots (the vectors: few elements, a partial per tile): 16 threads per element, thread k takes the partials
-// k, k + 16, .. the same way, and the 16 results meet in a tree -- the two-level sum §3.13b asked for.  count == 0 stores zeros.
-constexpr int kRmSumSlots = 16;
-struct RmSumJob { const float *src; float *dst; size_t stride; int count, len, slots; };
-struct RmSumArgs { RmSumJob job[GF_REFINE_MLP_PARAMS]; };
-__global__ __launch_bounds__(256) void gf_refine_mlp_sum_kernel(RmSumArgs a)
-{
-    __shared__ double s_sum[256];
-    const RmSumJob &jb = a.job[blockIdx.y];
-    const int slots = jb.slots, per = 256 / slots;          // elements of a workgroup
-    if ((int)blockIdx.x * per >= jb.len) return;            // (the whole workgroup)
-    const int el = threadIdx.x % per, slot = threadIdx.x / per, e = blockIdx.x * per + el;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    if (e < jb.len) {
-        const float *src = jb.src + e;
-        int i = slot;
-        for (; i + 3 * slots < jb.count; i += 4 * slots) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s[q] += (double)src[(size_t)(i + q * slots) * jb.stride];
-        }
-        for (; i < jb.count; i += slots) s[0] += (double)src[(size_t)i * jb.stride];
-    }
-    const double v = (s[0] + s[1]) + (s[2] + s[3]);
-    if (slots == 1) {
-        if (e < jb.len) jb.dst[e] = (float)v;
-        return;
-    }
-    s_sum[threadIdx.x] = v;
-    __syncthreads();
-    if (slot == 0 && e < jb.len) {
-        double p[kRmSumSlots];
-#pragma unroll
-        for (int k = 0; k < kRmSumSlots; ++k) p[k] = s_sum[k * per + el];
-#pragma unroll
-        for (int w = kRmSumSlots / 2; w > 0; w >>= 1)
-#pragma unroll
-            for (int k = 0; k < w; ++k) p[k] = p[2 * k] + p[2 * k + 1];
-        jb.dst[e] = (float)p[0];
-    }
+    if (s == 0) rm_wgrad_job<kWgSum>(a, s);
+    else if (s & 1) rm_wgrad_job<kWgAsIs>(a, s);
+    else rm_wgrad_job<kWgNorm>(a, s);
 }
 
 // The backward's scratch, sized and carved by one function (a null base: the size only)
@@ -388,10 +195,10 @@ extern "C" int gf_refine_mlp_train_sizes(int n, int D, int Da, size_t *saved_byt
 {
     using namespace gf;
     const char *fn = __func__;
-    GF_RM_REFUSE(n >= 0, "n = %d is negative", n);
-    GF_RM_REFUSE(D >= 10 && D <= 10 + 1 + kRefMaxS, "D = %d is not in 10 .. %d", D, 10 + 1 + kRefMaxS);
-    GF_RM_REFUSE(Da >= 0, "Da = %d is negative", Da);
-    GF_RM_REFUSE(saved_bytes && workspace_bytes, "null pointer");
+    GF_REFUSE_AS(fn, n >= 0, "n = %d is negative", n);
+    GF_REFUSE_AS(fn, D >= 10 && D <= 10 + 1 + kRefMaxS, "D = %d is not in 10 .. %d", D, 10 + 1 + kRefMaxS);
+    GF_REFUSE_AS(fn, Da >= 0, "Da = %d is negative", Da);
+    GF_REFUSE_AS(fn, saved_bytes && workspace_bytes, "null pointer");
     *saved_bytes = refine_mlp_carve_saved(nullptr, n, D).bytes;
     *workspace_bytes = rm_carve_work(nullptr, n, D).bytes;
     return GF_OK;
@@ -409,22 +216,22 @@ extern "C" int gf_refine_mlp_backward(int n, int E, int D, int Da, int version, 
     const char *fn = __func__;
     RefineArgs r{};
     if (int rc = refine_fill_args(r, fn, n, D, Da, version, flags, R, S, consts)) return rc;
-    GF_RM_REFUSE(E == kRmE, "E = %d: only embed_dims = 128 is supported", E);
-    GF_RM_REFUSE(grad_params, "null grad_params");
+    GF_REFUSE_AS(fn, E == kRmE, "E = %d: only embed_dims = 128 is supported", E);
+    GF_REFUSE_AS(fn, grad_params, "null grad_params");
     float *const *gp = reinterpret_cast<float *const *>(grad_params);
-    for (int i = 0; i < GF_REFINE_MLP_PARAMS; ++i) GF_RM_REFUSE(gp[i], "grad_params[%d] (the gradient of %s) is null", i, kRmName[i]);
+    for (int i = 0; i < GF_REFINE_MLP_PARAMS; ++i) GF_REFUSE_AS(fn, gp[i], "grad_params[%d] (the gradient of %s) is null", i, kRmName[i]);
     hipStream_t stream = (hipStream_t)stream_;
     const RefineMlpSaved sv = refine_mlp_carve_saved(n > 0 ? const_cast<void *>(saved) : nullptr, n, D);
     const RmWork ws = rm_carve_work(n > 0 ? workspace : nullptr, n, D);
     if (n > 0) {
         if (int rc = refine_mlp_check_inputs(fn, params, instance_feature, anchor_embed, anchor)) return rc;
-        GF_RM_REFUSE(saved, "saved is null");
-        GF_RM_REFUSE(!rm_misaligned(saved), "saved = %p is not 16-byte aligned", saved);
-        GF_RM_REFUSE(workspace, "workspace is null");
-        GF_RM_REFUSE(!rm_misaligned(workspace), "workspace = %p is not 16-byte aligned", workspace);
-        GF_RM_REFUSE(grad_x, "grad_x is null");
-        GF_RM_REFUSE(!rm_misaligned(grad_x), "grad_x = %p is not 16-byte aligned", (const void *)grad_x);
-        GF_RM_REFUSE(grad_anchor, "grad_anchor is null");
+        GF_REFUSE_AS(fn, saved, "saved is null");
+        GF_REFUSE_AS(fn, !misaligned16(saved), "saved = %p is not 16-byte aligned", saved);
+        GF_REFUSE_AS(fn, workspace, "workspace is null");
+        GF_REFUSE_AS(fn, !misaligned16(workspace), "workspace = %p is not 16-byte aligned", workspace);
+        GF_REFUSE_AS(fn, grad_x, "grad_x is null");
+        GF_REFUSE_AS(fn, !misaligned16(grad_x), "grad_x = %p is not 16-byte aligned", (const void *)grad_x);
+        GF_REFUSE_AS(fn, grad_anchor, "grad_anchor is null");
         GF_CHECK_WORKSPACE_AS(fn, "workspace", workspace_bytes, ws.bytes);
         const float *const *p = reinterpret_cast<const float *const *>(params);
 
@@ -458,13 +265,15 @@ extern "C" int gf_refine_mlp_backward(int n, int E, int D, int Da, int version, 
             GF_CHECK_LAUNCH();
         }
     }
-    // (3) n == 0: no partials, the sums store zeros
-    RmSumArgs sa{};
+    // (3) sums in double, rounded once (the partials are fp32 sums over 128 or 512 rows; at 144 000 rows there are 1 125 or 282
+    // of them): the matrices -- many elements, few partials -- a thread per element, the vectors -- few elements, a partial per
+    // tile -- kRowsSumSlots threads per element, the two-level sum §3.13b asked for.  n == 0: no partials, the sums store zeros
+    RowsSumArgs<GF_REFINE_MLP_PARAMS> sa{};
     auto vec = [&](int i, int at, int len) {
-        sa.job[i] = RmSumJob{n > 0 ? ws.vpart + at : nullptr, gp[i], (size_t)kRmVLen, n > 0 ? ws.tiles : 0, len, kRmSumSlots};
+        sa.job[i] = RowsSumJob{n > 0 ? ws.vpart + at : nullptr, gp[i], (size_t)kRmVLen, n > 0 ? ws.tiles : 0, len, 0, kRowsSumSlots};
     };
     auto mat = [&](int i, int s, int len) {
-        sa.job[i] = RmSumJob{n > 0 ? ws.wpart + (size_t)s * kRmE * kRmE : nullptr, gp[i], kRmWLen, n > 0 ? ws.blocks : 0, len, 1};
+        sa.job[i] = RowsSumJob{n > 0 ? ws.wpart + (size_t)s * kRmE * kRmE : nullptr, gp[i], kRmWLen, n > 0 ? ws.blocks : 0, len, 0, 1};
     };
     mat(0, 0, kRmE * kRmE);   vec(1, kRmVBias, kRmE);
     mat(2, 1, kRmE * kRmE);   vec(3, kRmVBias + kRmE, kRmE);
@@ -474,7 +283,7 @@ extern "C" int gf_refine_mlp_backward(int n, int E, int D, int Da, int version, 
     vec(10, kRmVLn + 2 * kRmE, kRmE); vec(11, kRmVLn + 3 * kRmE, kRmE);
     mat(12, 4, D * kRmE);     vec(13, kRmVB10, D);
     vec(14, kRmVScale, D);
-    hipLaunchKernelGGL(gf_refine_mlp_sum_kernel, dim3(kRmE * kRmE / 256, GF_REFINE_MLP_PARAMS), dim3(256), 0, stream, sa);
+    hipLaunchKernelGGL((rows_sum_kernel<double, GF_REFINE_MLP_PARAMS>), dim3(kRmE * kRmE / 256, GF_REFINE_MLP_PARAMS), dim3(256), 0, stream, sa);
     GF_CHECK_LAUNCH();
     return GF_OK;
 }

@@ -5,8 +5,6 @@
 with the add or the cat behind it.  ``gf_deform_logits_forward`` and ``gf_deform_output_forward`` (include/gf_hip.h, DESIGN.md
 §3.13e) are one launch each: an inference block is four launches and the ``[A, 128]`` sum never reaches memory.  Forward only:
 training, dropout and everything the native ops do not cover run the module's own torch layers around ``deformable_fused``."""
-import ctypes
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -35,27 +33,8 @@ def _pair(layer, what, affine=nn.Linear):
     return weight, bias
 
 
-def _needs_grad(tensors):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
-
-
-def _aligned(t):
-    t = _lib.as_arg(t)
-    return t.clone() if t is not None and t.data_ptr() % 16 else t
-
-
-def _table(params):
-    """The library's host table of pointers, and the tensors it points into (kept alive until the launch is queued)."""
-    table = (ctypes.c_void_p * len(params))()
-    held = [_aligned(p) for p in params]
-    for i, p in enumerate(held):
-        if p is not None:
-            table[i] = p.data_ptr()
-    return ctypes.cast(table, ctypes.c_void_p), held
-
-
 def _refuse_autograd(name, tensors):
-    if _needs_grad(tensors):
+    if _lib.needs_grad(tensors):
         raise RuntimeError(
             f"{name} is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters that "
             "do not require grad (the DeformableFeatureAggregation module routes training to its torch layers around "
@@ -79,9 +58,9 @@ def deformable_logits(instance_feature, anchor_embed, weights_fc, learnable_fc=N
     if anchor_embed is not None and anchor_embed.shape != instance_feature.shape:
         raise ValueError(f"deformable_logits: anchor_embed {tuple(anchor_embed.shape)} is not {tuple(instance_feature.shape)}")
     lead = instance_feature.shape[:-1]
-    f, e = _aligned(instance_feature).reshape(-1, E), None if anchor_embed is None else _aligned(anchor_embed).reshape(-1, E)
+    f, e = _lib.aligned(instance_feature).reshape(-1, E), None if anchor_embed is None else _lib.aligned(anchor_embed).reshape(-1, E)
     n = f.shape[0]
-    table, held = _table([wl, bl, ww, bw])
+    table, held = _lib.param_table([wl, bl, ww, bw], _lib.GF_DEFORM_LOGITS_PARAMS)
     raw = torch.empty(n, Nw, dtype=f32, device=f.device)
     learned = torch.empty(n, K3, dtype=f32, device=f.device) if K3 else None
     _lib.call("gf_deform_logits_forward", f.device, n, E, K3, Nw, f, e, table, learned, raw)
@@ -110,9 +89,9 @@ def deformable_output(features, output_proj, instance_feature=None, residual_mod
         if t is not None and t.shape != features.shape:
             raise ValueError(f"deformable_output: {name} {tuple(t.shape)} is not {tuple(features.shape)}")
     lead = features.shape[:-1]
-    x = _aligned(features).reshape(-1, E)
-    fi, res = (None if t is None else _aligned(t).reshape(-1, E) for t in (inst, residual))
-    table, held = _table([wo, bo, g, b])
+    x = _lib.aligned(features).reshape(-1, E)
+    fi, res = (None if t is None else _lib.aligned(t).reshape(-1, E) for t in (inst, residual))
+    table, held = _lib.param_table([wo, bo, g, b], _lib.GF_DEFORM_OUTPUT_PARAMS)
     width = 2 * E if residual_mode == "cat" else E
     out = torch.empty(x.shape[0], width, dtype=f32, device=x.device)
     _lib.call("gf_deform_output_forward", x.device, x.shape[0], E, MODES[residual_mode], x, fi, table, res, out)
@@ -189,7 +168,7 @@ class DeformableFeatureAggregation(nn.Module):
         tensors += list(norm.parameters()) if isinstance(norm, nn.Module) else list(norm or ())
         if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
             return False
-        return not _needs_grad(tensors)
+        return not _lib.needs_grad(tensors)
 
     def forward(self, instance_feature, anchor, anchor_embed, feature_maps, metas, **kwargs):
         residual, norm = kwargs.get("residual"), kwargs.get("norm")
@@ -228,7 +207,7 @@ class DeformableFeatureAggregation(nn.Module):
         weight_mask = None
         if self.training and self.attn_drop > 0:     # (:273-282)
             weight_mask = torch.rand(bs, A, cams, L, self.num_pts, G, dtype=per_anchor.dtype, device=per_anchor.device) > self.attn_drop
-        if weight_mask is None and not _needs_grad([kp, feature_maps[0], per_anchor]):
+        if weight_mask is None and not _lib.needs_grad([kp, feature_maps[0], per_anchor]):
             features = deformable_fused_forward(kp, pm, wh, *feature_maps, **logits)     # the same block, the inference launch
         else:
             features = deformable_fused(kp, pm, wh, *feature_maps, weight_mask=weight_mask, **logits)

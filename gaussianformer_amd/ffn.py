@@ -5,8 +5,6 @@ torch runs a block as two LayerNorms, three GEMMs, a ReLU and an add around an `
 training step -- the module's two dropouts, a saving forward and the full backward (``gf_ffn_forward_train``,
 ``gf_ffn_backward``) -- is ``ffn_block_autograd`` and, on the module, the opt-in ``native_training``; without
 it training, dropout and everything the native op does not cover run the module's own torch layers."""
-import ctypes
-
 import torch
 import torch.nn as nn
 
@@ -53,31 +51,6 @@ def _param_list(ffn, norm):
     return params
 
 
-def _needs_grad(tensors):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
-
-
-def _table(params):
-    """The library's host table of the 10 pointers, and the tensors it points into: a parameter as it is, or its converted copy
-    (another dtype, not contiguous, misaligned), which the caller keeps alive until the launch is queued."""
-    table = (ctypes.c_void_p * _lib.GF_FFN_PARAMS)()
-    held = []
-    for i, p in enumerate(params):
-        if p is None:
-            continue
-        if p.dtype != f32 or not p.is_contiguous() or p.data_ptr() % 16:   # (a module's own parameters: never)
-            p = _lib.as_arg(p)
-            p = p.clone() if p.data_ptr() % 16 else p
-        held.append(p)
-        table[i] = p.data_ptr()
-    return ctypes.cast(table, ctypes.c_void_p), held
-
-
-def _aligned(t):
-    t = _lib.as_arg(t)
-    return t.clone() if t is not None and t.data_ptr() % 16 else t
-
-
 def _shape(x, params, residual):
     """``(x [n, Cin], residual [n, E] or None, leading shape, Cin, F, E)`` as the library reads them, the shapes checked."""
     _lib.require_gpu(x, residual, *params)
@@ -94,19 +67,19 @@ def _shape(x, params, residual):
     if params[6] is not None and tuple(params[6].shape) != (E, Cin):
         raise ValueError(f"ffn_block: identity_fc.weight {tuple(params[6].shape)} is not ({E}, {Cin})")
     lead = x.shape[:-1]
-    xa = _aligned(x).reshape(-1, Cin)
+    xa = _lib.aligned(x).reshape(-1, Cin)
     res = None
     if residual is not None:
         if tuple(residual.shape) != (*lead, E):
             raise ValueError(f"ffn_block: residual {tuple(residual.shape)} is not {(*lead, E)}")
-        res = _aligned(residual).reshape(-1, E)
+        res = _lib.aligned(residual).reshape(-1, E)
     return xa, res, lead, Cin, F, E
 
 
 def _launch(x, params, residual):
     """The library call on the 10-entry parameter list; the callers have settled autograd."""
     xa, res, lead, Cin, F, E = _shape(x, params, residual)
-    table, held = _table(params)
+    table, held = _lib.param_table(params, _lib.GF_FFN_PARAMS)
     out = torch.empty(xa.shape[0], E, dtype=f32, device=xa.device)
     _lib.call("gf_ffn_forward", xa.device, xa.shape[0], Cin, F, E, xa, table, res, out)
     return out.view(*lead, E)
@@ -120,7 +93,7 @@ def ffn_block(x, ffn, norm=None, residual=None):
     ``identity_fc.*``); ``norm``: an ``nn.LayerNorm``, a ``(weight, bias)`` pair or ``None``.  Dropout is not applied (eval
     semantics); the parameters are read in place at every call.  Forward only: inputs that need autograd are refused."""
     params = _param_list(ffn, norm)
-    if _needs_grad([x, residual, *params]):
+    if _lib.needs_grad([x, residual, *params]):
         raise RuntimeError(
             "ffn_block is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters "
             "that do not require grad (the AsymmetricFFN module routes training to its torch layers)")
@@ -129,9 +102,7 @@ def ffn_block(x, ffn, norm=None, residual=None):
 
 def train_sizes(n, cin):
     """``(saved_bytes, workspace_bytes)`` of the training step on ``n`` rows of width ``cin`` (``gf_ffn_train_sizes``)."""
-    saved, work = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _lib.check(_lib.load().gf_ffn_train_sizes(n, cin, ctypes.addressof(saved), ctypes.addressof(work)), "gf_ffn_train_sizes")
-    return saved.value, work.value
+    return _lib.train_sizes("gf_ffn_train_sizes", n, cin)
 
 
 def _keep_mask(keep, p, shape, device, what):
@@ -157,15 +128,6 @@ def _keep_mask(keep, p, shape, device, what):
     return keep, 1.0 / (1.0 - p)
 
 
-def _out_table(tensors):
-    """The host table of the 10 OUTPUT pointers: the tensors themselves, never a copy."""
-    table = (ctypes.c_void_p * _lib.GF_FFN_PARAMS)()
-    for i, t in enumerate(tensors):
-        if t is not None:
-            table[i] = t.data_ptr()
-    return ctypes.cast(table, ctypes.c_void_p)
-
-
 class FFNBlockFunction(torch.autograd.Function):
     """``out = FFNBlockFunction.apply(x, residual, keep_hidden, scale_hidden, keep_out, scale_out, *params)`` on the 10-entry
     parameter list (``None`` for an absent part) and the two keep masks (uint8, ``None``: no dropout there):
@@ -175,7 +137,7 @@ class FFNBlockFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, keep_hidden, scale_hidden, keep_out, scale_out, *params):
         xa, res, lead, Cin, F, E = _shape(x, params, residual)
-        table, held = _table(params)
+        table, held = _lib.param_table(params, _lib.GF_FFN_PARAMS)
         n = xa.shape[0]
         saved_bytes, _ = train_sizes(n, Cin)
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=xa.device)
@@ -197,15 +159,15 @@ class FFNBlockFunction(torch.autograd.Function):
         for d in dtypes:
             params.append(None if d is None else next(it))
             grads.append(None if d is None else torch.empty_like(params[-1]))
-        table, _ = _table(params)
+        table, _ = _lib.param_table(params, _lib.GF_FFN_PARAMS)
         _, work_bytes = train_sizes(n, Cin)
         work = torch.empty(work_bytes, dtype=torch.uint8, device=xa.device)
         grad_x = torch.empty(n, Cin, dtype=f32, device=xa.device)
         need = ctx.needs_input_grad
         grad_res = torch.empty(n, E, dtype=f32, device=xa.device) if res_dtype is not None and need[1] else None
-        go = _aligned(grad_out).reshape(n, E)
+        go = _lib.aligned(grad_out).reshape(n, E)
         _lib.call("gf_ffn_backward", xa.device, n, Cin, F, E, xa, table, keep_hidden, scale_hidden, keep_out, scale_out, saved, go,
-                  grad_x, grad_res, _out_table(grads), work, work_bytes)
+                  grad_x, grad_res, _lib.out_table(grads, _lib.GF_FFN_PARAMS), work, work_bytes)
         return (grad_x.view(*lead, Cin).to(x_dtype) if need[0] else None,
                 None if grad_res is None else grad_res.view(*lead, E).to(res_dtype), None, None, None, None,
                 *[g.to(d) if g is not None and need[6 + i] else None for i, (g, d) in enumerate(zip(grads, dtypes))])
@@ -223,7 +185,7 @@ def ffn_block_autograd(x, ffn, norm=None, residual=None, p_hidden=0.0, p_out=0.0
     lead = tuple(x.shape[:-1])
     keep_hidden, scale_hidden = _keep_mask(keep_hidden, p_hidden, (*lead, F_NATIVE), x.device, "p_hidden")
     keep_out, scale_out = _keep_mask(keep_out, p_out, (*lead, E_NATIVE), x.device, "p_out")
-    if keep_hidden is None and keep_out is None and not _needs_grad([x, residual, *params]):
+    if keep_hidden is None and keep_out is None and not _lib.needs_grad([x, residual, *params]):
         return _launch(x, params, residual)
     return FFNBlockFunction.apply(x, residual, keep_hidden, scale_hidden, keep_out, scale_out, *params)
 
@@ -324,7 +286,7 @@ class AsymmetricFFN(nn.Module):
         if self._native(x, identity):
             params = _param_list(self, None)
             if not self._dropout_active():
-                if not _needs_grad([x, *params]):
+                if not _lib.needs_grad([x, *params]):
                     return _launch(x, params, None)
                 if self.native_training:
                     return FFNBlockFunction.apply(x, None, None, 1.0, None, 1.0, *params)

@@ -103,8 +103,10 @@ MLP_KEYS = ("layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bia
 assert len(MLP_KEYS) == _lib.GF_REFINE_MLP_PARAMS
 
 
-def _needs_grad(tensors):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+def _mlp_table(params):
+    """The library's host table of the 15 parameter pointers, the tensors as ``_lib.as_arg`` left them.  (Not
+    ``_lib.param_table``: that clones a misaligned parameter, and this op's contract is that the library refuses one.)"""
+    return ctypes.cast((ctypes.c_void_p * _lib.GF_REFINE_MLP_PARAMS)(*[t.data_ptr() for t in params]), ctypes.c_void_p)
 
 
 def refine_fused(instance_feature, anchor, anchor_embed, module_or_state_dict, cfg, return_mlp_output=False):
@@ -117,7 +119,7 @@ def refine_fused(instance_feature, anchor, anchor_embed, module_or_state_dict, c
     if isinstance(state, nn.Module):
         state = dict(state.named_parameters())
     params = [state[k] for k in MLP_KEYS]
-    if _needs_grad((instance_feature, anchor, anchor_embed, *params)):
+    if _lib.needs_grad((instance_feature, anchor, anchor_embed, *params)):
         raise RuntimeError("refine_fused computes no gradients: use the module with fused_mlp = False (the torch MLP + refine) "
                            "for training, or call it under torch.no_grad()")
     _lib.require_gpu(instance_feature, anchor, anchor_embed, *params)
@@ -142,9 +144,8 @@ def refine_fused(instance_feature, anchor, anchor_embed, module_or_state_dict, c
     outs = (new(D), new(3), new(3), new(4), new(opa), new(cfg.S), new(three), new(three))
     mlp_out = new(D) if return_mlp_output else None
     consts = (ctypes.c_double * 11)(*cfg.consts)
-    table = (ctypes.c_void_p * _lib.GF_REFINE_MLP_PARAMS)(*[t.data_ptr() for t in params])
     _lib.call("gf_refine_mlp_forward", f.device, n, E, D, Da, cfg.version, cfg.flags, cfg.R, cfg.S, ctypes.cast(consts, ctypes.c_void_p),
-              f, e, a, ctypes.cast(table, ctypes.c_void_p), mlp_out, *outs)
+              f, e, a, _mlp_table(params), mlp_out, *outs)
     outs = [t.view(*lead, t.shape[-1]) for t in outs]
     pred = GaussianPrediction(*outs[1:6]) if cfg.version == 1 else GaussianPrediction(*outs[1:8])
     if return_mlp_output:
@@ -154,10 +155,7 @@ def refine_fused(instance_feature, anchor, anchor_embed, module_or_state_dict, c
 
 def train_sizes(n, D, Da):
     """``(saved_bytes, workspace_bytes)`` of the native training step on ``n`` rows (``gf_refine_mlp_train_sizes``)."""
-    saved, work = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _lib.check(_lib.load().gf_refine_mlp_train_sizes(n, D, Da, ctypes.addressof(saved), ctypes.addressof(work)),
-               "gf_refine_mlp_train_sizes")
-    return saved.value, work.value
+    return _lib.train_sizes("gf_refine_mlp_train_sizes", n, D, Da)
 
 
 _train_scratch = _lib.StreamScratch()   # the backward's workspace (one chunk's dz rows, the partial sums)
@@ -197,10 +195,9 @@ class RefineFusedFunction(Function):
         saved_bytes, _ = train_sizes(n, D, Da)
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=f.device)
         consts = (ctypes.c_double * 11)(*cfg.consts)
-        table = (ctypes.c_void_p * _lib.GF_REFINE_MLP_PARAMS)(*[t.data_ptr() for t in held])
         ctx.call = (n, E, D, Da, cfg.version, cfg.flags, cfg.R, cfg.S, consts)
         _lib.call("gf_refine_mlp_forward_train", f.device, *ctx.call[:8], ctypes.cast(consts, ctypes.c_void_p),
-                  f, e, a, ctypes.cast(table, ctypes.c_void_p), None, *outs, saved, saved_bytes)
+                  f, e, a, _mlp_table(held), None, *outs, saved, saved_bytes)
         ctx.save_for_backward(f, e, a, saved, *held)
         ctx.shape = (lead, tuple(anchor_embed.shape), instance_feature.dtype, anchor.dtype, anchor_embed.dtype,
                      [t.dtype for t in params])
@@ -216,13 +213,11 @@ class RefineFusedFunction(Function):
         grad_x = torch.empty(n, E, dtype=f32, device=f.device)
         grad_anchor = torch.empty(n, Da, dtype=f32, device=f.device)
         grad_params = [torch.empty_like(t) for t in held]
-        table = (ctypes.c_void_p * _lib.GF_REFINE_MLP_PARAMS)(*[t.data_ptr() for t in held])
-        out_table = (ctypes.c_void_p * _lib.GF_REFINE_MLP_PARAMS)(*[t.data_ptr() for t in grad_params])
         _, work_bytes = train_sizes(n, D, Da)
         work = _train_scratch.get(f.device, work_bytes)
         _lib.call("gf_refine_mlp_backward", f.device, n, E, D, Da, version, flags, R, S, ctypes.cast(consts, ctypes.c_void_p),
-                  f, e, a, ctypes.cast(table, ctypes.c_void_p), saved, *g, grad_x, grad_anchor, None,
-                  ctypes.cast(out_table, ctypes.c_void_p), work, work_bytes)
+                  f, e, a, _mlp_table(held), saved, *g, grad_x, grad_anchor, None,
+                  _lib.out_table(grad_params, _lib.GF_REFINE_MLP_PARAMS), work, work_bytes)
         need = ctx.needs_input_grad
         gx = grad_x.view(*lead, E)
         return (gx.to(f_dtype) if need[0] else None,
@@ -241,7 +236,7 @@ def refine_fused_autograd(instance_feature, anchor, anchor_embed, module_or_stat
         state = dict(state.named_parameters())
     params = [state[k] for k in MLP_KEYS]
     _lib.require_gpu(instance_feature, anchor, anchor_embed, *params)
-    if not _needs_grad((instance_feature, anchor, anchor_embed, *params)):
+    if not _lib.needs_grad((instance_feature, anchor, anchor_embed, *params)):
         return refine_fused(instance_feature, anchor, anchor_embed, state, cfg)
     outs = RefineFusedFunction.apply(instance_feature, anchor, anchor_embed, cfg, *params)
     pred = GaussianPrediction(*outs[1:6]) if cfg.version == 1 else GaussianPrediction(*outs[1:8])
@@ -297,12 +292,12 @@ class _Refinement(nn.Module):
 
     def _takes_fused(self, instance_feature, anchor, anchor_embed):
         tensors = (instance_feature, anchor, anchor_embed, *self.layers.parameters())
-        return (self.fused_mlp and self.embed_dims == 128 and not _needs_grad(tensors)
+        return (self.fused_mlp and self.embed_dims == 128 and not _lib.needs_grad(tensors)
                 and all(t.is_cuda and t.dtype == f32 for t in tensors))
 
     def _takes_native_training(self, instance_feature, anchor, anchor_embed):
         tensors = (instance_feature, anchor, anchor_embed, *self.layers.parameters())
-        return (self.native_training and self.embed_dims == 128 and _needs_grad(tensors)
+        return (self.native_training and self.embed_dims == 128 and _lib.needs_grad(tensors)
                 and all(t.is_cuda and t.dtype == f32 for t in tensors))
 
     def forward(self, instance_feature, anchor, anchor_embed):
