@@ -2,9 +2,11 @@
 (model/encoder/gaussian_encoder/anchor_encoder_module.py:38-53 with ``linear_relu_ln``, utils.py:49-59) on a plain mapping of
 its state_dict.  In float64 it is the truth the tests hold every path to; in float32 it is what a user of the reference runs
 today.  ``fixed_weights`` gives the reproducible parameter sets, so no weights are committed.  Never imported by the product."""
-import numpy as np
 import torch
 import torch.nn.functional as F
+
+import row_ref
+from row_ref import cast, fixed_input, output_weights  # noqa: F401  (re-exported: the tests reach them as ``ref.``)
 
 STAGES = ("xyz_fc", "scale_fc", "rot_fc", "opacity_fc", "semantics_fc", "output_fc")
 # the fixture's families (tools/make_golden_anchor_embed.py): constructor keys of the module, embed_dims = 128
@@ -14,6 +16,11 @@ FAMILIES = {
     "opa_nosem": dict(include_opa=True, semantics=False, semantic_dim=None),
 }
 GOLDEN_ROWS = 96
+# the GPU tests' layouts, name: (include_opa, S, Da)
+LAYOUTS = {
+    "opa_s17": (1, 17, 28), "gs144000": (0, 18, 28), "opa_s0": (1, 0, 11), "noopa_s0": (0, 0, 10),
+    "opa_s1": (1, 1, 12), "opa_s5": (1, 5, 16), "opa_s32": (1, 32, 43), "opa_s17_da40": (1, 17, 40),
+}
 
 
 def shapes(include_opa, S, E=128):
@@ -28,32 +35,22 @@ def shapes(include_opa, S, E=128):
     return out
 
 
-def _uniform(count, stream):
-    """``count`` values in [-1, 1) from an integer hash of (index, stream): exactly reproducible, no generator state."""
-    m = np.uint64(0xFFFFFFFF)
-    x = (np.arange(count, dtype=np.uint64) * np.uint64(2654435761) + np.uint64(stream) * np.uint64(40503) + np.uint64(12345)) & m
-    x ^= x >> np.uint64(15)
-    x = (x * np.uint64(2246822519)) & m
-    x ^= x >> np.uint64(13)
-    x = (x * np.uint64(3266489917)) & m
-    x ^= x >> np.uint64(16)
-    return x.astype(np.float64) / 2.0 ** 31 - 1.0
-
-
 def fixed_weights(include_opa=True, S=17, E=128, seed=0, dtype=torch.float32):
-    """A seeded state_dict away from the initial state: Linear weights uniform with variance 1 / fan_in, biases of +-0.3,
-    LayerNorm weights in [0.7, 1.3] and biases of +-0.3 (computed in float64, rounded once to float32, then cast)."""
-    sd = {}
-    for i, (key, shape) in enumerate(shapes(include_opa, S, E).items()):
-        u = _uniform(int(np.prod(shape)), 1000 * seed + i).reshape(shape)
-        if len(shape) == 2:
-            v = u * np.sqrt(3.0 / shape[1])
-        elif key.endswith("weight"):
-            v = 1.0 + 0.3 * u
-        else:
-            v = 0.3 * u
-        sd[key] = torch.from_numpy(v.astype(np.float32)).to(dtype)
-    return sd
+    """``row_ref.fixed_weights`` of the module's state_dict (stream offset 0)."""
+    return row_ref.fixed_weights(shapes(include_opa, S, E), 0, seed, dtype)
+
+
+def make_input(n, opa, S, Da, seed):
+    """N(0, 1) logits with the planted rows (as many of them as n admits)."""
+    x = fixed_input(n, Da, seed)
+    ss = 10 + opa
+    plant = [lambda r: r.zero_(), lambda r: r.fill_(1e-30),
+             lambda r: r[ss:ss + S].fill_(80.0), lambda r: r[ss:ss + S].fill_(-80.0),
+             lambda r: r[0:3].fill_(1e4), lambda r: r[0:3].fill_(-1e4)]
+    for i, f in enumerate(plant):
+        if i < n:
+            f(x[i])
+    return x
 
 
 def _stage(x, sd, name):
@@ -74,18 +71,3 @@ def anchor_embed_ref(anchor, sd):
         S = sd["semantics_fc.0.weight"].shape[1]
         out = out + _stage(anchor[..., 10 + opa:10 + opa + S], sd, "semantics_fc")
     return _stage(out, sd, "output_fc")
-
-
-def cast(sd, dtype=None, device=None):
-    return {k: v.to(dtype=dtype, device=device) for k, v in sd.items()}
-
-
-def fixed_input(n, Da, seed):
-    """N(0, 1) rows [n, Da], float32."""
-    return torch.from_numpy(np.random.default_rng(seed).standard_normal((n, Da)).astype(np.float32))
-
-
-def output_weights(shape, dtype=torch.float64):
-    """The fixed weights of the scalar that gradients come from: cos(0.37 i) over the output's elements."""
-    n = int(np.prod(shape))
-    return torch.cos(torch.arange(n, dtype=torch.float64) * 0.37).reshape(shape).to(dtype)

@@ -1,20 +1,19 @@
 """TEST INFRASTRUCTURE for the anchor encoder's training step: the float64 walk of ``anchor_embed_ref`` that also returns every
-stage's pre-activations, the kink filter built on it, and the gradients of the fixed scalar ``sum(out * output_weights)``.
+stage's pre-activations, the kink filter's candidates built on it, and the kinds of its leaves.
 
-The kink filter.  A ReLU whose pre-activation z lies within float32 rounding of 0 can take different sides in float64 and in
-float32; that is no error of a float32 kernel, but it moves that row's gradient by about 10 %.  A row is therefore kept iff, at
-every stage and feature, ``|z| >= 1e-5 (1 + sum_k |W_ok x_k| + |b_o|)``: the margin (about 1e-4 for ordinary rows) is 10-20 times
-the forward's measured error of 4-5.5e-6.  Never imported by the product."""
+The kink filter is tests/row_ref.py's, on every Linear of the twelve stages (each stands in front of a ReLU).  Never imported by
+the product."""
 import functools
 
 import torch
 import torch.nn.functional as F
 
 import anchor_embed_ref as ref
-from test_anchor_encoder_gpu import FAMILIES, make_input
+import row_ref
+from anchor_embed_ref import LAYOUTS as FAMILIES, make_input
+from row_ref import CANDIDATES
 
-KINK_MARGIN = 1e-5
-CANDIDATES, PLANTS, INPUT_SEED = 1400, 6, 7
+PLANTS, INPUT_SEED = 6, 7
 
 
 def walk(anchor, sd):
@@ -26,8 +25,8 @@ def walk(anchor, sd):
         E = sd[name + ".0.bias"].shape[0]
         for lin, ln in ((0, 2), (3, 5)):
             W, b = sd[f"{name}.{lin}.weight"], sd[f"{name}.{lin}.bias"]
-            z = F.linear(x, W, b)
-            stages.append((f"{name}.{lin}", z, x.abs() @ W.abs().t() + b.abs()))
+            z, scale = row_ref.linear_stage(x, W, b)
+            stages.append((f"{name}.{lin}", z, scale))
             x = F.layer_norm(F.relu(z), (E,), sd[f"{name}.{ln}.weight"], sd[f"{name}.{ln}.bias"], 1e-5)
         return x
 
@@ -41,14 +40,11 @@ def walk(anchor, sd):
     return stage(out, "output_fc"), stages
 
 
-def kink_free(anchor, sd):
-    """bool [n]: the rows of ``anchor`` (float32 values) that the filter keeps, judged in float64 on the CPU."""
+def relu_stages(anchor, sd):
+    """The ``(z, scale)`` the kink filter judges the rows of ``anchor`` (float32 values) by: in float64, on the CPU."""
     with torch.no_grad():
         _, stages = walk(anchor.double().cpu(), ref.cast(sd, torch.float64, "cpu"))
-    keep = torch.ones(anchor.shape[0], dtype=torch.bool)
-    for _, z, scale in stages:
-        keep &= (z.abs() >= KINK_MARGIN * (1.0 + scale)).all(dim=1)
-    return keep
+    return [(z, scale) for _, z, scale in stages]
 
 
 @functools.lru_cache(maxsize=None)
@@ -60,7 +56,7 @@ def candidates(name, seed=0, dead_branch=None):
     if dead_branch:
         sd[dead_branch + ".0.bias"] = torch.full_like(sd[dead_branch + ".0.bias"], -1e6)
     x = make_input(CANDIDATES, opa, S, Da, INPUT_SEED + seed)
-    return x, kink_free(x, sd), sd
+    return x, row_ref.kink_free(relu_stages(x, sd)), sd
 
 
 def survivors(name, seed=0, dead_branch=None):
@@ -76,13 +72,3 @@ def kind(key):
         return "square weight" if slot == "3.weight" or stage == "output_fc" else "thin weight"
     return {"0.bias": "Linear bias", "3.bias": "Linear bias", "2.weight": "LN weight", "5.weight": "LN weight",
             "2.bias": "LN bias", "5.bias": "LN bias"}[slot]
-
-
-def gradients(forward, x, sd):
-    """``{"anchor": d/dx, key: d/d sd[key]}`` of ``sum(forward(x, sd) * output_weights)`` in the dtype of ``x``; ``forward`` is
-    ``ref.anchor_embed_ref`` or the native functional."""
-    x = x.detach().clone().requires_grad_(True)
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in sd.items()}
-    out = forward(x, leaves)
-    (out * ref.output_weights(out.shape, out.dtype).to(out.device)).sum().backward()
-    return {"anchor": x.grad, **{k: v.grad for k, v in leaves.items()}}

@@ -5,16 +5,15 @@ state_dict.  The middle (key points, projection, masked softmax, bilinear sampli
 oracle/daf_prepare_ref.py's and tests/daf_fused_ref.py's.  In float64 it is the truth the tests hold every path to; in float32
 it is what a user of the reference runs today.  ``fixed_weights`` gives the reproducible parameter sets, so no weights are
 committed.  Never imported by the product."""
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 import daf_fused_ref
-from anchor_embed_ref import _uniform, cast  # noqa: F401  (the same reproducible hash; cast is re-exported)
+import row_ref
 from oracle import daf_prepare_ref
+from row_ref import NORM_KEYS, cast, fixed_input, module_state, planted  # noqa: F401  (re-exported: the tests reach them as ``ref.``)
 
 E = 128
-NORM_KEYS = ("norm.weight", "norm.bias")   # the post norm's place in a weight mapping (not part of the module's state_dict)
 FIX7 = [[0, 0, 0], [0.45, 0, 0], [-0.45, 0, 0], [0, 0.45, 0], [0, -0.45, 0], [0, 0, 0.45], [0, 0, -0.45]]
 # the configuration tests/golden/caller_dfa.npz was recorded with (tools/make_golden_callers.py; tests/test_ref_callers.py:231-258)
 FIXTURE_CONFIG = dict(embed_dims=32, num_groups=4, num_levels=3, num_cams=3, use_deformable_func=True, use_camera_embed=True,
@@ -70,19 +69,8 @@ def shapes(cfg, norm=False):
 
 
 def fixed_weights(shape_map, seed=0, dtype=torch.float32):
-    """A seeded weight mapping away from the initial state for ``{key: shape}``: Linear weights uniform with variance 1 / fan_in,
-    biases of +-0.3, LayerNorm weights in [0.7, 1.3] (computed in float64, rounded once to float32, then cast)."""
-    sd = {}
-    for i, (key, shape) in enumerate(shape_map.items()):
-        u = _uniform(int(np.prod(shape)), 1000 * seed + 700 + i).reshape(shape)
-        if len(shape) == 2:
-            v = u * np.sqrt(3.0 / shape[1])
-        elif key.endswith("weight"):          # a LayerNorm's (camera_encoder.2 / .5, norm)
-            v = 1.0 + 0.3 * u
-        else:
-            v = 0.3 * u
-        sd[key] = torch.from_numpy(v.astype(np.float32)).to(dtype)
-    return sd
+    """``row_ref.fixed_weights`` of ``{key: shape}`` (stream offset 700; the LayerNorms: camera_encoder.2 / .5, norm)."""
+    return row_ref.fixed_weights(shape_map, 700, seed, dtype)
 
 
 def dense_shapes(k3, nw, norm=False):
@@ -95,25 +83,6 @@ def dense_shapes(k3, nw, norm=False):
     if norm:
         out.update({"norm.weight": (E,), "norm.bias": (E,)})
     return out
-
-
-def module_state(sd):
-    return {k: v for k, v in sd.items() if k not in NORM_KEYS}
-
-
-def fixed_input(n, width, seed):
-    """N(0, 1) rows [n, width], float32."""
-    return torch.from_numpy(np.random.default_rng(seed).standard_normal((n, width)).astype(np.float32))
-
-
-def planted(x):
-    """Rows that a random draw does not reach (as many as ``x`` has room for): zeros, tiny, +-1e4 in a few columns."""
-    x = x.clone()
-    plant = [lambda r: r.zero_(), lambda r: r.fill_(1e-30), lambda r: r[3:6].fill_(1e4), lambda r: r[40:43].fill_(-1e4)]
-    for i, f in enumerate(plant):
-        if i < x.shape[0]:
-            f(x[i])
-    return x
 
 
 def camera_embed(sd, pm, cams):

@@ -3,11 +3,11 @@
 encoder's ``operation_order`` -- on a plain mapping of the module's state_dict.  In float64 it is the truth the tests hold
 every path to; in float32 it is what a user of the reference runs today.  ``fixed_weights`` gives the reproducible parameter
 sets, so no weights are committed.  Never imported by the product."""
-import numpy as np
 import torch
 import torch.nn.functional as F
 
-from anchor_embed_ref import _uniform, cast  # noqa: F401  (the same reproducible hash; cast is re-exported)
+import row_ref
+from row_ref import NORM_KEYS, cast, fixed_input, module_state, planted  # noqa: F401  (re-exported: the tests reach them as ``ref.``)
 
 E, HIDDEN = 128, 512
 # the fixture's families (tools/make_golden_ffn.py): the constructor arguments of the two shipped config families
@@ -20,7 +20,15 @@ FAMILIES = {
 }
 FOLLOWED_BY_ADD = {"base": False, "prob": True}
 GOLDEN_ROWS = 64
-NORM_KEYS = ("norm.weight", "norm.bias")   # the post norm's place in a weight mapping (not part of the module's state_dict)
+# the GPU tests' variants, name: (Cin, pre_norm, identity_fc, residual, post norm)
+VARIANTS = {
+    "base_norm": (256, True, True, False, True),
+    "base": (256, True, True, False, False),
+    "prob_add_norm": (128, False, False, True, True),
+    "prob": (128, False, False, False, False),
+    "c256_nopre_id": (256, False, True, False, True),
+    "c128_pre": (128, True, False, False, True),
+}
 
 
 def shapes(cin=256, pre_norm=True, identity=True, norm=True, e=E, f=HIDDEN):
@@ -47,24 +55,13 @@ def family_shapes(name):
 
 
 def fixed_weights(cin=256, pre_norm=True, identity=True, norm=True, e=E, f=HIDDEN, seed=0, dtype=torch.float32):
-    """A seeded weight mapping away from the initial state: Linear weights uniform with variance 1 / fan_in, biases of +-0.3,
-    LayerNorm weights in [0.7, 1.3] and biases of +-0.3 (computed in float64, rounded once to float32, then cast)."""
-    sd = {}
-    for i, (key, shape) in enumerate(shapes(cin, pre_norm, identity, norm, e, f).items()):
-        u = _uniform(int(np.prod(shape)), 1000 * seed + 500 + i).reshape(shape)
-        if len(shape) == 2:
-            v = u * np.sqrt(3.0 / shape[1])
-        elif key.endswith("weight") and ("norm" in key):
-            v = 1.0 + 0.3 * u
-        else:
-            v = 0.3 * u
-        sd[key] = torch.from_numpy(v.astype(np.float32)).to(dtype)
-    return sd
+    """``row_ref.fixed_weights`` of the block's weight mapping (stream offset 500)."""
+    return row_ref.fixed_weights(shapes(cin, pre_norm, identity, norm, e, f), 500, seed, dtype)
 
 
-def module_state(sd):
-    """The module's part of a weight mapping (without the post norm's pair): what ``load_state_dict`` takes."""
-    return {k: v for k, v in sd.items() if k not in NORM_KEYS}
+def parts(sd):
+    """A weight mapping as ``ffn_block`` takes it: the module's part, and the post norm's pair or ``None``."""
+    return module_state(sd), ((sd["norm.weight"], sd["norm.bias"]) if "norm.weight" in sd else None)
 
 
 def ffn_ref(x, sd, residual=None, norm=True, act=F.relu):
@@ -81,18 +78,3 @@ def ffn_ref(x, sd, residual=None, norm=True, act=F.relu):
     if norm and "norm.weight" in sd:
         y = F.layer_norm(y, (y.shape[-1],), sd["norm.weight"], sd["norm.bias"], 1e-5)
     return y
-
-
-def fixed_input(n, cin, seed):
-    """N(0, 1) rows [n, cin], float32."""
-    return torch.from_numpy(np.random.default_rng(seed).standard_normal((n, cin)).astype(np.float32))
-
-
-def planted(x):
-    """Rows that a random draw does not reach (as many as ``x`` has room for): zeros, tiny, +-1e4 in a few columns."""
-    x = x.clone()
-    plant = [lambda r: r.zero_(), lambda r: r.fill_(1e-30), lambda r: r[3:6].fill_(1e4), lambda r: r[40:43].fill_(-1e4)]
-    for i, f in enumerate(plant):
-        if i < x.shape[0]:
-            f(x[i])
-    return x

@@ -2,9 +2,8 @@
 keep masks and scales, in a generic dtype; the kink filter on the hidden layer's pre-activations; seeded masks; and the
 gradients of the fixed scalar ``sum(out * output_weights)``.
 
-The kink filter (tests/anchor_embed_train_ref.py).  A ReLU whose pre-activation z lies within float32 rounding of 0 may take
-either side in float32; that is no error of a float32 kernel, but it moves the row's gradient.  A candidate row is kept iff
-``|z| >= 1e-5 (1 + sum_k |W1_ok u_k| + |b1_o|)`` for all 512 hidden features, judged in float64.  Never imported by the product."""
+The kink filter is tests/row_ref.py's, on the hidden layer's 512 pre-activations (``layers.0.0``, the only Linear in front of
+a ReLU).  Never imported by the product."""
 import functools
 
 import numpy as np
@@ -12,10 +11,9 @@ import torch
 import torch.nn.functional as F
 
 import ffn_ref as ref
-from anchor_embed_ref import output_weights
+import row_ref
+from row_ref import CANDIDATES, output_weights  # noqa: F401  (output_weights is re-exported)
 
-KINK_MARGIN = 1e-5
-CANDIDATES = 1400
 E, HIDDEN = ref.E, ref.HIDDEN
 
 
@@ -40,17 +38,14 @@ def ffn_train_ref(x, sd, residual=None, keep_hidden=None, scale_hidden=1.0, keep
     return y
 
 
-def kink_free(x, sd):
-    """bool [n]: the rows of ``x`` (float32 values) that the filter keeps, judged in float64 on the CPU."""
+def relu_stages(x, sd):
+    """The ``(z, scale)`` the kink filter judges the rows of ``x`` (float32 values) by: in float64, on the CPU."""
     with torch.no_grad():
         sd = ref.cast(sd, torch.float64, "cpu")
         u = x.double().cpu()
         if "pre_norm.weight" in sd:
             u = F.layer_norm(u, (u.shape[-1],), sd["pre_norm.weight"], sd["pre_norm.bias"], 1e-5)
-        W, b = sd["layers.0.0.weight"], sd["layers.0.0.bias"]
-        z = F.linear(u, W, b)
-        scale = u.abs() @ W.abs().t() + b.abs()
-    return (z.abs() >= KINK_MARGIN * (1.0 + scale)).all(dim=1)
+        return [row_ref.linear_stage(u, sd["layers.0.0.weight"], sd["layers.0.0.bias"])]
 
 
 @functools.lru_cache(maxsize=None)
@@ -61,7 +56,7 @@ def candidates(cin, pre_norm, identity, norm=True, seed=0, count=CANDIDATES, dea
     if dead:
         sd["layers.0.0.bias"] = torch.full_like(sd["layers.0.0.bias"], -1e6)
     x = ref.fixed_input(count, cin, 100 + seed)
-    return x, kink_free(x, sd), sd
+    return x, row_ref.kink_free(relu_stages(x, sd)), sd
 
 
 def survivors(cin, pre_norm, identity, norm=True, seed=0, count=CANDIDATES, dead=False):
@@ -86,18 +81,3 @@ def kind(key):
     of a per-row quantity.  The block has at most two leaves of each finer kind and, without one of the norms, a single one --
     a kind of one leaf would be that leaf's own yardstick, which the rule (the largest error over a kind) exists to avoid."""
     return "matrix" if key.endswith("weight") and "norm" not in key else "vector"
-
-
-def gradients(forward, x, sd, residual=None):
-    """``{"out": out, "x": d/dx, "residual": d/dresidual (where given), key: d/d sd[key]}`` of ``sum(forward(x, leaves, residual)
-    * output_weights)`` in the dtype of ``x``; ``forward(x, sd, residual)`` is the restatement (masks bound) or the native
-    functional."""
-    x = x.detach().clone().requires_grad_(True)
-    res = None if residual is None else residual.detach().clone().requires_grad_(True)
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in sd.items()}
-    out = forward(x, leaves, res)
-    (out * output_weights(out.shape, out.dtype).to(out.device)).sum().backward()
-    got = {"out": out.detach(), "x": x.grad, **{k: v.grad for k, v in leaves.items()}}
-    if res is not None:
-        got["residual"] = res.grad
-    return got

@@ -1,20 +1,18 @@
 """TEST INFRASTRUCTURE for the refinement modules' native training step: the float64 walk of ``refine_ref.mlp`` that also
-returns every stage's pre-activation, the kink filter built on it, and the vector-Jacobian product of the MLP.
+returns every stage's pre-activation, the kink filter's candidates built on it, and the kinds of its leaves.
 
-The kink filter.  A ReLU whose pre-activation z lies within float32 rounding of 0 can take different sides in float64 and in
-float32; that is no error of a float32 kernel, but it moves that row's gradient by about 10 %.  A row is therefore kept iff, at
-all four ReLU stages and every feature, ``|z| >= 1e-5 (1 + sum_k |W_ok x_k| + |b_o|)`` (tests/anchor_embed_train_ref.py's
-rule).  Never imported by the product."""
+The kink filter is tests/row_ref.py's, on the four Linears in front of a ReLU (the last Linear's pre-activation is walked too,
+but no ReLU follows it).  Never imported by the product."""
 import functools
 
 import torch
 import torch.nn.functional as F
 
+import row_ref
 from gaussianformer_amd.refine import MLP_KEYS
-from test_refine_mlp_gpu import VARIANTS, make_inputs, make_module
+from refine_ref import VARIANTS, make_inputs, make_module
+from row_ref import CANDIDATES
 
-KINK_MARGIN = 1e-5
-CANDIDATES = 1400
 RELU_STAGES = (0, 2, 5, 7)
 
 
@@ -26,26 +24,21 @@ def walk(state, x):
     for first in (0, 5):
         for k in (first, first + 2):
             W, b = state[f"layers.{k}.weight"], state[f"layers.{k}.bias"]
-            z = F.linear(x, W, b)
-            stages.append((f"layers.{k}", z, x.abs() @ W.abs().t() + b.abs()))
+            z, scale = row_ref.linear_stage(x, W, b)
+            stages.append((f"layers.{k}", z, scale))
             x = F.relu(z)
         ln = first + 4
         x = F.layer_norm(x, x.shape[-1:], state[f"layers.{ln}.weight"], state[f"layers.{ln}.bias"])
-    W, b = state["layers.10.weight"], state["layers.10.bias"]
-    z = F.linear(x, W, b)
-    stages.append(("layers.10", z, x.abs() @ W.abs().t() + b.abs()))
+    z, scale = row_ref.linear_stage(x, state["layers.10.weight"], state["layers.10.bias"])
+    stages.append(("layers.10", z, scale))
     return z * state["layers.11.scale"], stages
 
 
-def kink_free(state, x):
-    """bool [n]: the rows of ``x`` that the filter keeps, judged in float64 on the CPU at the four ReLU stages."""
+def relu_stages(state, x):
+    """The ``(z, scale)`` the kink filter judges the rows of ``x`` by: the four ReLU stages, in float64, on the CPU."""
     with torch.no_grad():
         _, stages = walk({k: v.detach().double().cpu() for k, v in state.items()}, x.double().cpu())
-    keep = torch.ones(x.shape[0], dtype=torch.bool)
-    for key, z, scale in stages:
-        if int(key.split(".")[1]) in RELU_STAGES:
-            keep &= (z.abs() >= KINK_MARGIN * (1.0 + scale)).all(dim=1)
-    return keep
+    return [(z, scale) for key, z, scale in stages if int(key.split(".")[1]) in RELU_STAGES]
 
 
 @functools.lru_cache(maxsize=None)
@@ -56,7 +49,7 @@ def candidates(variant):
     seed = 200 + list(VARIANTS).index(variant)
     module = make_module(cfg, seed)
     feat, anchor, embed = make_inputs(module.output_dim, extra, CANDIDATES, seed + 1000)
-    keep = kink_free(module.state_dict(), feat.double() + embed.double())
+    keep = row_ref.kink_free(relu_stages(module.state_dict(), feat.double() + embed.double()))
     return module, feat, anchor, embed, keep
 
 
@@ -64,16 +57,6 @@ def survivors(variant):
     """``(module, feat, anchor, embed)``: the candidate rows the filter keeps, in their order (float32, CPU)."""
     module, feat, anchor, embed, keep = candidates(variant)
     return module, feat[keep].contiguous(), anchor[keep].contiguous(), embed[keep].contiguous()
-
-
-def vjp(mlp, x, state, cotangent):
-    """``{"x": d/dx, key: d/d state[key]}`` of ``sum(mlp(state, x) * cotangent)`` in the dtype and on the device of ``x``;
-    ``mlp`` is ``refine_ref.mlp`` (or anything with its signature)."""
-    x = x.detach().clone().requires_grad_(True)
-    leaves = {k: state[k].detach().clone().requires_grad_(True) for k in MLP_KEYS}
-    out = mlp(leaves, x)
-    grads = torch.autograd.grad((out * cotangent).sum(), [x, *leaves.values()])
-    return dict(zip(("x", *MLP_KEYS), grads))
 
 
 def kind(key):

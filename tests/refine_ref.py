@@ -3,6 +3,7 @@ their MLP's output (SparseGaussian3DRefinementModule, model/encoder/gaussian_enc
 SparseGaussian3DRefinementModuleV2, refine_module_v2.py:62-107, ``version=2``) and the whole module from a state_dict.  In
 float64 it is the truth the GPU tests measure against, in float32 the comparator (what a user runs today) and what
 tools/bench_refine.py times.  Not a test module."""
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -20,6 +21,50 @@ FAMILIES = {
     "prob": dict(version=2, pc_range=_PC, scale_range=[0.01, 3.2], unit_xyz=[4.0, 4.0, 1.0], semantics=True, semantic_dim=17,
                  include_opa=True, semantics_activation="identity"),
 }
+
+
+def _v1(**kw):
+    return dict(FAMILIES["solid"], **kw)
+
+
+# the fused step's GPU tests' variants at embed_dims = 128, name -> (settings, anchor columns beyond D)
+E = 128
+VARIANTS = {
+    "solid": (FAMILIES["solid"], 0),                                               # D 28
+    "gs144000": (FAMILIES["gs144000"], 0),                                         # D 28, no opacity
+    "prob": (FAMILIES["prob"], 0),                                                 # D 28, version 2
+    "D10": (_v1(semantics=False, semantic_dim=0, include_opa=False), 0),
+    "D11": (dict(FAMILIES["prob"], semantics=False, semantic_dim=0), 0),           # version 2
+    "D43": (_v1(semantic_dim=32, semantics_activation="softmax"), 0),              # the tail in two passes
+    "Da>D": (_v1(), 5),
+    "R12": (_v1(refine_manual=list(range(12))), 3),                                # anchor columns from 10 on are added too
+}
+
+
+def make_module(cfg, seed):
+    """The drop-in module at E = 128 with seeded weights, LayerNorm and Scale moved away from the identity as
+    tools/make_golden_refine.py moves them."""
+    from gaussianformer_amd import refine as R
+    torch.manual_seed(seed)
+    rng = np.random.default_rng(seed)
+    cls = {1: R.SparseGaussian3DRefinementModule, 2: R.SparseGaussian3DRefinementModuleV2}[cfg["version"]]
+    module = cls(embed_dims=E, phi_activation="sigmoid", xyz_coordinate="cartesian", **{k: v for k, v in cfg.items() if k != "version"})
+    with torch.no_grad():
+        for p in module.parameters():
+            p.add_(torch.from_numpy(rng.standard_normal(tuple(p.shape)).astype(np.float32)) * 0.1)
+    return module
+
+
+def make_inputs(D, extra, n, seed):
+    rng = np.random.default_rng(seed)
+    f32 = lambda a: torch.from_numpy(a.astype(np.float32))
+    feat, embed = f32(rng.standard_normal((n, E))), f32(rng.standard_normal((n, E)))
+    anchor = f32(np.concatenate([rng.uniform(-3.0, 3.0, (n, 3)), rng.standard_normal((n, D + extra - 3))], axis=-1))
+    return feat, anchor, embed
+
+
+def outputs_of(anchor_out, pred):
+    return dict(anchor_out=anchor_out, **{k: v for k, v in pred._asdict().items() if v is not None})
 
 
 def safe_sigmoid(x):

@@ -9,10 +9,10 @@ import torch
 
 import anchor_embed_ref as ref
 from gaussianformer_amd import anchor_encoder
+from row_judge import bound, max_error
 from gaussianformer_amd.anchor_encoder import SparseGaussian3DEncoder, anchor_embed
 
 GOLDEN = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_embed.npz"))
-EPS32 = float(np.finfo(np.float32).eps)
 FAMILIES = list(ref.FAMILIES)
 
 
@@ -85,10 +85,8 @@ def test_cpu_route_is_torch_and_meets_the_truth_with_its_gradients(name, monkeyp
     _, g32 = grads(torch.float32)
 
     def held(what, got, truth, yard):
-        truth = truth.double()
-        bound = 2 * (yard.double() - truth).abs().max().item() + 4 * EPS32 * truth.abs().max().item()
-        err = (got.double() - truth).abs().max().item()
-        assert err <= bound, (what, err, bound)
+        err, limit = max_error(got, truth), bound(max_error(yard, truth), truth)
+        assert err <= limit, (what, err, limit)
 
     held("output", out.detach(), torch.from_numpy(g["out64"]), torch.from_numpy(g["out32"]))
     def yard(k):

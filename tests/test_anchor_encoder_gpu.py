@@ -8,7 +8,6 @@ one yardstick per family serve all its cases.  The measured ``max|native - truth
 recorded in DESIGN.md §3.13.
 
 Invariants are bitwise.  Nothing here reads past an input's end or inspects code."""
-import ctypes
 import functools
 import os
 
@@ -17,34 +16,16 @@ import pytest
 import torch
 
 import anchor_embed_ref as ref
+from anchor_embed_ref import LAYOUTS as FAMILIES, make_input
 from gaussianformer_amd import _lib, anchor_encoder
 from gaussianformer_amd.anchor_encoder import SparseGaussian3DEncoder, anchor_embed
+from row_judge import ROWS, bound, held, max_error, ptr_table, spy  # noqa: F401  (spy is a fixture)
 
 pytestmark = pytest.mark.gpu
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = torch.device("cuda")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_embed.npz")
 
-# name: (include_opa, S, Da)
-FAMILIES = {
-    "opa_s17": (1, 17, 28), "gs144000": (0, 18, 28), "opa_s0": (1, 0, 11), "noopa_s0": (0, 0, 10),
-    "opa_s1": (1, 1, 12), "opa_s5": (1, 5, 16), "opa_s32": (1, 32, 43), "opa_s17_da40": (1, 17, 40),
-}
-ROWS = (1, 31, 32, 33, 127, 128, 129, 1000)   # the edges of the wave's 32 rows and the workgroup's 128
 N_FAMILY = 1000
-
-
-def make_input(n, opa, S, Da, seed):
-    """N(0, 1) logits with the planted rows (as many of them as n admits)."""
-    x = ref.fixed_input(n, Da, seed)
-    ss = 10 + opa
-    plant = [lambda r: r.zero_(), lambda r: r.fill_(1e-30),
-             lambda r: r[ss:ss + S].fill_(80.0), lambda r: r[ss:ss + S].fill_(-80.0),
-             lambda r: r[0:3].fill_(1e4), lambda r: r[0:3].fill_(-1e4)]
-    for i, f in enumerate(plant):
-        if i < n:
-            f(x[i])
-    return x
 
 
 class Case:
@@ -62,8 +43,8 @@ class Case:
             self.truth = ref.anchor_embed_ref(self.x.double(), self.sd64)
             self.torch32 = ref.anchor_embed_ref(self.x, self.sd)
             self.native = anchor_embed(self.x, self.sd)
-        self.Y = (self.torch32.double() - self.truth).abs().max().item()
-        self.bound = 2 * self.Y + 4 * EPS32 * self.truth.abs().max().item()
+        self.Y = max_error(self.torch32, self.truth)
+        self.bound = bound(self.Y, self.truth)
 
 
 @functools.lru_cache(maxsize=None)
@@ -71,19 +52,10 @@ def case(name, dead_branch=None):
     return Case(name, dead_branch=dead_branch)
 
 
-def held(what, got, truth, bound):
-    err = (got.double() - truth).abs().max().item()
-    print(f"{what}: max|native - truth| = {err:.3e}, bound = {bound:.3e}, ratio = {err / bound:.3f}")
-    assert got.shape == truth.shape and torch.isfinite(got).all()
-    assert err <= bound, (what, err, bound)
-
-
 def raw_call(x, sd, opa, S, out, n=None, Da=None, E=128):
     """The C entry point on caller-made buffers (``sd``: a state_dict on the GPU)."""
-    params = anchor_encoder._param_list(sd)
-    table = (ctypes.c_void_p * 48)(*[None if p is None else p.data_ptr() for p in params])
     _lib.call("gf_anchor_embed_forward", x.device, x.shape[0] if n is None else n, x.shape[1] if Da is None else Da, E, opa, S,
-              x, ctypes.cast(table, ctypes.c_void_p), out)
+              x, ptr_table(anchor_encoder._param_list(sd), 48), out)
     return out
 
 
@@ -149,9 +121,9 @@ def test_module_with_the_fixture_s_weights(name):
     module.load_state_dict(ref.fixed_weights(opa, S, seed=int(g[name + ".seed"])), strict=True)
     module.to(DEV)
     truth = torch.from_numpy(g[name + ".out64"]).to(DEV)
-    bound = 2 * np.abs(g[name + ".out32"].astype(np.float64) - g[name + ".out64"]).max() + 4 * EPS32 * np.abs(g[name + ".out64"]).max()
     with torch.no_grad():
-        held(f"fixture {name}", module(torch.from_numpy(g[name + ".input"]).to(DEV)), truth, bound)
+        held(f"fixture {name}", module(torch.from_numpy(g[name + ".input"]).to(DEV)), truth,
+             bound(max_error(g[name + ".out32"], g[name + ".out64"]), g[name + ".out64"]))
 
 
 # ---- 2. invariants, bitwise -------------------------------------------------------------------------------------------------
@@ -213,18 +185,6 @@ def test_a_nan_stays_in_its_row(col):
 
 
 # ---- 3. module --------------------------------------------------------------------------------------------------------------
-
-@pytest.fixture
-def spy(monkeypatch):
-    names = []
-    real = _lib.call
-
-    def call(name, *a):
-        names.append(name)
-        return real(name, *a)
-    monkeypatch.setattr(_lib, "call", call)
-    return names
-
 
 def _module(name="opa_s17", E=128, seed=0):
     opa, S, Da = FAMILIES[name]
@@ -312,6 +272,6 @@ def test_other_widths_take_the_torch_route(spy):
     with torch.no_grad():
         out = m(x)
         truth = ref.anchor_embed_ref(x.double(), ref.cast(m.state_dict(), torch.float64))
-        y = (ref.anchor_embed_ref(x, dict(m.state_dict())).double() - truth).abs().max().item()
+        y = max_error(ref.anchor_embed_ref(x, dict(m.state_dict())), truth)
     assert spy == [] and out.shape == (129, 256)
-    held("embed_dims 256", out, truth, 2 * y + 4 * EPS32 * truth.abs().max().item())
+    held("embed_dims 256", out, truth, bound(y, truth))

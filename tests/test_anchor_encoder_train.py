@@ -10,8 +10,10 @@ import torch
 
 import anchor_embed_ref as ref
 import anchor_embed_train_ref as tr
+import row_ref
 from gaussianformer_amd import _lib, anchor_encoder
 from gaussianformer_amd.anchor_encoder import SparseGaussian3DEncoder, anchor_embed, anchor_embed_autograd, train_sizes
+from row_judge import ptr_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -43,12 +45,12 @@ def test_kink_filter_rejects_a_kink():
     """A row whose first pre-activation is moved onto 0 (through the bias) is rejected; the untouched weights keep it."""
     x, keep, sd = tr.candidates("opa_s0")
     row = int(torch.nonzero(keep)[10])
-    assert bool(tr.kink_free(x[row:row + 1], sd))
+    assert bool(row_ref.kink_free(tr.relu_stages(x[row:row + 1], sd)))
     z0 = torch.nn.functional.linear(x[row, 0:3].double(), sd["xyz_fc.0.weight"].double(), sd["xyz_fc.0.bias"].double())
     sd2 = dict(sd)
     sd2["xyz_fc.0.bias"] = sd["xyz_fc.0.bias"].clone()
     sd2["xyz_fc.0.bias"][5] -= z0[5].float()
-    assert not bool(tr.kink_free(x[row:row + 1], sd2))
+    assert not bool(row_ref.kink_free(tr.relu_stages(x[row:row + 1], sd2)))
 
 
 def test_kinds():
@@ -108,8 +110,7 @@ def test_sizes_refuses():
 
 def test_entry_points_check_arguments_before_the_device():
     lib = _lib.load()
-    table = (ctypes.c_void_p * 48)()
-    pt = ctypes.cast(table, ctypes.c_void_p)
+    pt = ptr_table([], 48)
     assert lib.gf_anchor_embed_forward_train(8, 28, 256, 1, 17, None, pt, None, None, 0, None) == -1
     assert b"gf_anchor_embed_forward_train" in lib.gf_last_error() and b"128" in lib.gf_last_error()
     assert lib.gf_anchor_embed_backward(8, 28, 128, 1, 33, None, pt, None, None, None, pt, None, 0, None) == -1

@@ -11,10 +11,8 @@ weight, Linear bias, LN weight, LN bias) at the same n, so that one lucky 128-va
 measured ratios are printed (-s) and recorded in DESIGN.md §3.13b.
 
 Invariants are bitwise.  Nothing here reads past a buffer's end or inspects code."""
-import ctypes
 import functools
 
-import numpy as np
 import pytest
 import torch
 
@@ -22,15 +20,15 @@ import anchor_embed_ref as ref
 import anchor_embed_train_ref as tr
 from gaussianformer_amd import _lib, anchor_encoder
 from gaussianformer_amd.anchor_encoder import SparseGaussian3DEncoder, anchor_embed, anchor_embed_autograd, train_sizes
-from test_anchor_encoder_gpu import FAMILIES, ROWS, make_input
+from anchor_embed_ref import LAYOUTS as FAMILIES, make_input
+from row_ref import scalar_gradients
+from row_judge import ROWS, Guarded, edge_rows, judge_leaves, max_error, ptr_table, spy  # noqa: F401  (spy is a fixture)
 
 pytestmark = pytest.mark.gpu
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = torch.device("cuda")
 N_FAMILY = 1000
 B = _lib.GF_ANCHOR_EMBED_WGRAD_ROWS
-# the tile's edges, the weight-gradient block's edges, three blocks with a ragged tail
-EDGE_ROWS = (1, 31, 32, 33, 127, 128, 129, B - 1, B, B + 1, 2 * B + 76)
+EDGE_ROWS = edge_rows(B)
 
 
 class Case:
@@ -46,12 +44,12 @@ class Case:
     @functools.lru_cache(maxsize=None)
     def grads(self, n):
         x = self.x[:n].contiguous()
-        return (tr.gradients(ref.anchor_embed_ref, x.double(), self.sd64), tr.gradients(ref.anchor_embed_ref, x, self.sd),
-                tr.gradients(anchor_embed_autograd, x, self.sd))
+        return (scalar_gradients(ref.anchor_embed_ref, {"anchor": x.double()}, self.sd64),
+                scalar_gradients(ref.anchor_embed_ref, {"anchor": x}, self.sd), scalar_gradients(anchor_embed_autograd, {"anchor": x}, self.sd))
 
     def anchor_yardstick(self):
         truth, t32, _ = self.grads(N_FAMILY)
-        return (t32["anchor"].double() - truth["anchor"]).abs().max().item()
+        return max_error(t32["anchor"], truth["anchor"])
 
 
 @functools.lru_cache(maxsize=None)
@@ -59,53 +57,27 @@ def case(name, dead_branch=None, repeat=1):
     return Case(name, dead_branch, repeat)
 
 
-def held(c, n):
+def judged(c, n):
     """Every gradient of case ``c`` at ``n`` rows against the bound; returns the native gradients."""
     truth, t32, native = c.grads(n)
-    err = (native["anchor"].double() - truth["anchor"]).abs().max().item()
-    bound = 2 * c.anchor_yardstick() + 4 * EPS32 * truth["anchor"].abs().max().item()
-    print(f"{c.name} n={n} grad_anchor: err = {err:.3e}, bound = {bound:.3e}, ratio = {err / bound:.3f}")
-    assert native["anchor"].shape == truth["anchor"].shape and bool(torch.isfinite(native["anchor"]).all())
-    assert err <= bound, ("grad_anchor", err, bound)
-
-    def rel(g, k):
-        scale = truth[k].abs().max().item()
-        return (g[k].double() - truth[k]).abs().max().item() / scale if scale > 0 else None
-    keys = [k for k in truth if k != "anchor"]
-    yard = {}
-    for k in keys:
-        r = rel(t32, k)
-        if r is not None:
-            yard[tr.kind(k)] = max(yard.get(tr.kind(k), 0.0), r)
-    worst = {}
-    for k in keys:
-        assert native[k].shape == truth[k].shape and bool(torch.isfinite(native[k]).all()), k
-        r = rel(native, k)
-        if r is None:      # the truth is identically 0 (a dead branch's first stage): so is the native gradient
-            assert bool((native[k] == 0).all()), k
-            continue
-        bound = 2 * yard[tr.kind(k)] + 4 * EPS32
-        worst[tr.kind(k)] = max(worst.get(tr.kind(k), 0.0), r / bound)
-        assert r <= bound, (k, r, bound)
-    print(f"{c.name} n={n} parameters, worst ratio per kind: " + ", ".join(f"{k} {v:.3f}" for k, v in sorted(worst.items())))
+    judge_leaves(native, truth, t32, tr.kind, f"{c.name} n={n}", per_row=("anchor",), row_yardstick={"anchor": c.anchor_yardstick()})
     return native
 
 
 # ---- raw calls on caller-made buffers ---------------------------------------------------------------------------------------
 
-def _ptrs(tensors):
-    return ctypes.cast((ctypes.c_void_p * 48)(*[None if p is None else p.data_ptr() for p in tensors]), ctypes.c_void_p)
+def _ptrs(sd):
+    return ptr_table(anchor_encoder._param_list(sd), 48)
 
 
 def raw_forward_train(x, sd, opa, S, out, saved, saved_bytes, n=None, E=128):
     n = x.shape[0] if n is None else n
-    _lib.call("gf_anchor_embed_forward_train", x.device, n, x.shape[1], E, opa, S, x, _ptrs(anchor_encoder._param_list(sd)), out, saved, saved_bytes)
+    _lib.call("gf_anchor_embed_forward_train", x.device, n, x.shape[1], E, opa, S, x, _ptrs(sd), out, saved, saved_bytes)
 
 
 def raw_backward(x, sd, opa, S, saved, go, ga, grads, work, work_bytes, n=None, E=128):
     n = x.shape[0] if n is None else n
-    _lib.call("gf_anchor_embed_backward", x.device, n, x.shape[1], E, opa, S, x, _ptrs(anchor_encoder._param_list(sd)), saved, go, ga,
-              _ptrs(anchor_encoder._param_list(grads)), work, work_bytes)
+    _lib.call("gf_anchor_embed_backward", x.device, n, x.shape[1], E, opa, S, x, _ptrs(sd), saved, go, ga, _ptrs(grads), work, work_bytes)
 
 
 class Raw:
@@ -116,8 +88,8 @@ class Raw:
         self.c, self.n = c, n
         self.x = c.x[:n].contiguous()
         self.sb, self.wb = train_sizes(n, c.opa, c.S)
-        self.saved = torch.full((self.sb + pad,), 0xA5, dtype=torch.uint8, device=DEV)
-        self.work = torch.full((self.wb + pad,), 0xA5, dtype=torch.uint8, device=DEV)
+        self.guarded = [Guarded(nbytes, DEV, pad, 0xA5, body=0xA5) for nbytes in (self.sb, self.wb)]
+        self.saved, self.work = [g.buf for g in self.guarded]
         self.out = torch.empty(n, 128, device=DEV)
         self.go = ref.output_weights((n, 128), torch.float32).to(DEV)
         self.ga = torch.full((n + pad_rows, c.Da), 12345.0, device=DEV)
@@ -152,13 +124,13 @@ def test_saving_forward_is_bitwise_the_plain_forward(name):
 
 @pytest.mark.parametrize("name", list(FAMILIES))
 def test_gradients(name):
-    held(case(name), N_FAMILY)
+    judged(case(name), N_FAMILY)
 
 
 @pytest.mark.parametrize("n", EDGE_ROWS)
 @pytest.mark.parametrize("name", ["opa_s17", "gs144000"])
 def test_gradients_at_the_edges(name, n):
-    held(case(name), n)
+    judged(case(name), n)
 
 
 def test_gradients_across_chunks():
@@ -167,7 +139,7 @@ def test_gradients_across_chunks():
     n = _lib.GF_ANCHOR_EMBED_CHUNK_ROWS + B + 70
     c = case("opa_s17", repeat=-(-n // 1000))     # (the CPU suite asserts at least 1 000 survivors per family)
     assert c.x.shape[0] >= n, f"{c.x.shape[0]} rows from the repeated survivors, {n} needed"
-    held(c, n)
+    judged(c, n)
 
 
 # ---- 3. exact zeros ----------------------------------------------------------------------------------------------------------
@@ -179,7 +151,7 @@ def test_unread_columns_get_exact_zeros():
     c0 = case("opa_s0")
     wide = torch.full((N_FAMILY, 20), float("nan"), device=DEV)
     wide[:, :11] = c0.x[:N_FAMILY]
-    g = tr.gradients(anchor_embed_autograd, wide, c0.sd)
+    g = scalar_gradients(anchor_embed_autograd, {"anchor": wide}, c0.sd)
     assert bool((g["anchor"][:, 11:] == 0).all())
     assert torch.equal(g["anchor"][:, :11], c0.grads(N_FAMILY)[2]["anchor"])
 
@@ -189,7 +161,7 @@ def test_dead_branch(branch):
     """The branch's first ReLU is 0 in every feature: its first stage's weight, bias and LayerNorm-weight gradients are exactly
     0, and so are the gradients of the anchor columns it reads; everything else meets the bound."""
     c = case("opa_s17", dead_branch=branch)
-    native = held(c, N_FAMILY)
+    native = judged(c, N_FAMILY)
     for slot in ("0.weight", "0.bias", "2.weight"):
         assert bool((native[f"{branch}.{slot}"] == 0).all()), slot
     cols = slice(0, 3) if branch == "xyz_fc" else slice(11, 28)
@@ -241,7 +213,7 @@ def test_rows_under_a_permutation_and_a_prefix():
 def test_nothing_is_written_beyond_the_queried_sizes(n):
     c = case("opa_s17")
     r = Raw(c, n).run()
-    assert bool((r.saved[r.sb:] == 0xA5).all()) and bool((r.work[r.wb:] == 0xA5).all())
+    assert all(g.intact() for g in r.guarded)
     assert bool((r.ga[n:] == 12345.0).all()) and bool(torch.isfinite(r.ga[:n]).all())
     native = c.grads(n)[2]
     assert torch.equal(r.ga[:n], native["anchor"])
@@ -254,7 +226,7 @@ def test_unread_columns_do_not_matter():
     x[:, 28:34] = float("nan")
     x[:, 34:37] = float("inf")
     x[:, 37:40] = float("-inf")
-    _same(tr.gradients(anchor_embed_autograd, x, c.sd), c.grads(N_FAMILY)[2])
+    _same(scalar_gradients(anchor_embed_autograd, {"anchor": x}, c.sd), c.grads(N_FAMILY)[2])
 
 
 @pytest.mark.parametrize("col", [0, 4, 9, 10, 11, 27])
@@ -262,7 +234,7 @@ def test_a_nan_stays_in_its_row(col):
     c = case("opa_s17")
     x = c.x[:N_FAMILY].clone()
     x[77, col] = float("nan")
-    got, t32 = tr.gradients(anchor_embed_autograd, x, c.sd), tr.gradients(ref.anchor_embed_ref, x, c.sd)
+    got, t32 = scalar_gradients(anchor_embed_autograd, {"anchor": x}, c.sd), scalar_gradients(ref.anchor_embed_ref, {"anchor": x}, c.sd)
     assert bool(torch.isnan(got["anchor"][77, :28]).all())
     keep = torch.arange(N_FAMILY, device=DEV) != 77
     assert torch.equal(got["anchor"][keep], c.grads(N_FAMILY)[2]["anchor"][keep])
@@ -272,18 +244,6 @@ def test_a_nan_stays_in_its_row(col):
 
 
 # ---- 5. autograd and module ----------------------------------------------------------------------------------------------------
-
-@pytest.fixture
-def spy(monkeypatch):
-    names = []
-    real = _lib.call
-
-    def call(name, *a):
-        names.append(name)
-        return real(name, *a)
-    monkeypatch.setattr(_lib, "call", call)
-    return names
-
 
 def _module(name="opa_s17", native_training=True, E=128):
     opa, S, Da = FAMILIES[name]

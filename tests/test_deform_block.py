@@ -1,7 +1,6 @@
 """The deformable block without a GPU: the restatement against what the reference's own module computed
 (tests/golden/caller_dfa.npz), the drop-in module's structure, and the two entry points' refusals (which come before any HIP
 call)."""
-import ctypes
 import os
 
 import numpy as np
@@ -13,6 +12,7 @@ import deform_block_ref as ref
 from gaussianformer_amd import _lib
 from gaussianformer_amd.deformable_block import DeformableFeatureAggregation, deformable_logits, deformable_output
 from gaussianformer_amd.key_points import SparseGaussian3DKeyPointsGenerator
+from row_judge import host_table
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "caller_dfa.npz")
 CPU = torch.device("cpu")
@@ -125,12 +125,7 @@ BUF = torch.zeros(4096)
 
 
 def _table(count, drop=(), misalign=None):
-    table = (ctypes.c_void_p * count)(*[BUF.data_ptr()] * count)
-    for i in drop:
-        table[i] = None
-    if misalign is not None:
-        table[misalign] = BUF.data_ptr() + 4
-    return ctypes.cast(table, ctypes.c_void_p)
+    return host_table(BUF, count, drop, misalign)
 
 
 def _logits(n=4, e=128, k3=6, nw=144, feature=BUF, embed=BUF, learned=None, raw=None, table=None, **kw):

@@ -10,7 +10,6 @@ bound from those rows' own Y and truth, a thousand times smaller); cases without
 ``max|native - truth| / bound`` per variant is printed (-s) and recorded in DESIGN.md §3.13e.
 
 Invariants are bitwise.  Nothing here reads past an input's end or inspects code."""
-import ctypes
 import functools
 import os
 
@@ -23,9 +22,9 @@ import deform_block_ref as ref
 from gaussianformer_amd import _lib, synthetic
 from gaussianformer_amd.deformable_block import DeformableFeatureAggregation, deformable_logits, deformable_output
 from gaussianformer_amd.deformable_prepare import deformable_fused
+from row_judge import ROWS, TILE_EDGES, bound, held, max_error, ptr_table, spy  # noqa: F401  (spy is a fixture)
 
 pytestmark = pytest.mark.gpu
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = torch.device("cuda")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "caller_dfa.npz")
 
@@ -36,22 +35,13 @@ FRONT = {"solid": (6, 144, True), "base": (18, 208, True), "nocam_solid": (0, 86
 # name: (residual_mode, residual, post norm)
 BACK = {"none": ("none", False, False), "add": ("add", False, False), "cat": ("cat", False, False),
         "none_res_norm": ("none", True, True), "add_norm": ("add", False, True)}
-ROWS = (1, 31, 32, 33, 127, 128, 129, 1000)   # the edges of a wave's 32 rows and of a workgroup's 128
 N_VARIANT = 1000
 SENTINEL = 12345.0
 PLANTED = 4                                   # ref.planted()'s rows
 
 
 def bound_of(truth, torch32):
-    y = (torch32.double() - truth).abs().max().item()
-    return 2 * y + 4 * EPS32 * truth.abs().max().item()
-
-
-def held(what, got, truth, bound):
-    err = (got.double() - truth).abs().max().item()
-    print(f"{what}: max|native - truth| = {err:.3e}, bound = {bound:.3e}, ratio = {err / bound:.3f}")
-    assert got.shape == truth.shape and torch.isfinite(got).all()
-    assert err <= bound, (what, err, bound)
+    return bound(max_error(torch32, truth), truth)
 
 
 def big_rows():
@@ -95,8 +85,7 @@ class Front:
     def raw_call(self, f, e, n, learned, raw):
         """The C entry point on caller-made buffers."""
         (ww, bw), (wl, bl) = self.params()
-        table = (ctypes.c_void_p * 4)(*[None if p is None else p.data_ptr() for p in (wl, bl, ww, bw)])
-        _lib.call("gf_deform_logits_forward", DEV, n, 128, self.k3, self.nw, f, e, ctypes.cast(table, ctypes.c_void_p), learned, raw)
+        _lib.call("gf_deform_logits_forward", DEV, n, 128, self.k3, self.nw, f, e, ptr_table((wl, bl, ww, bw)), learned, raw)
 
     def check(self, what, got, truth, planted=True):
         """``planted``: the rows are a prefix of the variant's own (all rows to the variant's bound, rows 4 .. to the ordinary
@@ -151,9 +140,8 @@ class Back:
     def raw_call(self, x, f, res, n, out):
         sd = self.sd
         ps = (sd["output_proj.weight"], sd["output_proj.bias"], sd.get("norm.weight"), sd.get("norm.bias"))
-        table = (ctypes.c_void_p * 4)(*[None if p is None else p.data_ptr() for p in ps])
         mode = {"none": 0, "add": 1, "cat": 2}[self.mode]
-        _lib.call("gf_deform_output_forward", DEV, n, 128, mode, x, None if mode == 0 else f, ctypes.cast(table, ctypes.c_void_p), res, out)
+        _lib.call("gf_deform_output_forward", DEV, n, 128, mode, x, None if mode == 0 else f, ptr_table(ps), res, out)
 
 
 @functools.lru_cache(maxsize=None)
@@ -234,7 +222,7 @@ def test_back_two_kernels_give_the_same_bits(name):
     assert torch.equal(native[:N_VARIANT], c.native)
 
 
-@pytest.mark.parametrize("r", [1, 31, 32, 33, 127, 128, 129])
+@pytest.mark.parametrize("r", TILE_EDGES)
 @pytest.mark.parametrize("name", ["solid", "nocam_base", "narrow"])
 def test_front_tile_kernel_at_its_edges(name, r):
     """The 128-row kernel with r rows in its last tile: the prefix, and nothing written beyond n x width."""
@@ -248,7 +236,7 @@ def test_front_tile_kernel_at_its_edges(name, r):
     assert torch.equal(learned[:n * c.k3].view(n, c.k3), native[1][:n]) and bool((learned[n * c.k3:] == SENTINEL).all())
 
 
-@pytest.mark.parametrize("r", [1, 31, 32, 33, 127, 128, 129])
+@pytest.mark.parametrize("r", TILE_EDGES)
 @pytest.mark.parametrize("name", ["cat", "none_res_norm"])
 def test_back_tile_kernel_at_its_edges(name, r):
     c = back(name)
@@ -453,18 +441,6 @@ def module_of(name, seed=0):
     m = DeformableFeatureAggregation(**cfg)
     m.load_state_dict(ref.module_state(sd), strict=True)
     return m.to(DEV).eval(), cfg, sd
-
-
-@pytest.fixture
-def spy(monkeypatch):
-    names = []
-    real = _lib.call
-
-    def call(name, *a):
-        names.append(name)
-        return real(name, *a)
-    monkeypatch.setattr(_lib, "call", call)
-    return names
 
 
 @pytest.mark.parametrize("name", list(SHAPES))

@@ -1,6 +1,5 @@
 """The feed-forward block without a GPU: the restatement against the reference's recorded outputs, the drop-in module's
 structure and CPU route, and the entry point's refusals (which come before any HIP call)."""
-import ctypes
 import os
 
 import numpy as np
@@ -11,9 +10,9 @@ import torch.nn as nn
 import ffn_ref as ref
 from gaussianformer_amd import _lib
 from gaussianformer_amd.ffn import AsymmetricFFN, ffn_block
+from row_judge import bound, held, host_table, max_error
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ffn.npz")
-EPS32 = float(np.finfo(np.float32).eps)
 CPU = torch.device("cpu")
 
 
@@ -32,15 +31,6 @@ def module_of(golden, name):
     m = AsymmetricFFN(**ref.FAMILIES[name])
     m.load_state_dict(ref.module_state(weights_of(golden, name)), strict=True)
     return m
-
-
-def held(what, got, truth, yardstick):
-    """The project's bound: max|got - truth| <= 2 Y + 4 eps32 max|truth|, Y = max|the float32 reference - truth|."""
-    truth = np.asarray(truth, dtype=np.float64)
-    bound = 2 * np.abs(np.asarray(yardstick, dtype=np.float64) - truth).max() + 4 * EPS32 * np.abs(truth).max()
-    err = np.abs(np.asarray(got, dtype=np.float64) - truth).max()
-    print(f"{what}: err = {err:.3e}, bound = {bound:.3e}, ratio = {err / bound:.3f}")
-    assert err <= bound, (what, err, bound)
 
 
 @pytest.mark.parametrize("name", list(ref.FAMILIES))
@@ -82,7 +72,8 @@ def test_cpu_route_meets_the_recorded_truth(golden, name):
     x = torch.from_numpy(golden[name + ".input"])
     with torch.no_grad():
         out = m(x)
-    held(f"{name} cpu route", out.numpy(), golden[name + ".ffn64"], golden[name + ".ffn32"])
+    truth = golden[name + ".ffn64"]
+    held(f"{name} cpu route", out.numpy(), truth, bound(max_error(golden[name + ".ffn32"], truth), truth))
 
 
 def test_training_with_dropout_takes_the_torch_route_and_is_stochastic(golden, monkeypatch):
@@ -126,12 +117,7 @@ def _raw(n=4, cin=256, f=512, e=128, drop=(), misalign=None, half=None):
     """``gf_ffn_forward`` through ``_lib.call`` on host memory: it must refuse before it touches a device."""
     buf = torch.zeros(64)
     assert buf.data_ptr() % 16 == 0
-    table = (ctypes.c_void_p * 10)(*[buf.data_ptr()] * 10)
-    for i in drop:
-        table[i] = None
-    if misalign is not None:
-        table[misalign] = buf.data_ptr() + 4
-    _lib.call("gf_ffn_forward", CPU, n, cin, f, e, buf, ctypes.cast(table, ctypes.c_void_p), None, buf)
+    _lib.call("gf_ffn_forward", CPU, n, cin, f, e, buf, host_table(buf, 10, drop, misalign), None, buf)
 
 
 def test_entry_point_refusals():

@@ -7,7 +7,6 @@ prefix of the variant's 1 000 rows, so one truth and one yardstick per variant s
 ``max|native - truth| / bound`` per variant is printed (-s) and recorded in DESIGN.md §3.13c.
 
 Invariants are bitwise.  Nothing here reads past an input's end or inspects code."""
-import ctypes
 import functools
 import os
 
@@ -17,30 +16,16 @@ import torch
 import torch.nn.functional as F
 
 import ffn_ref as ref
+from ffn_ref import VARIANTS, parts
 from gaussianformer_amd import _lib, ffn as ffn_mod
 from gaussianformer_amd.ffn import AsymmetricFFN, ffn_block
+from row_judge import ROWS, TILE_EDGES, bound, held, max_error, ptr_table, spy  # noqa: F401  (spy is a fixture)
 
 pytestmark = pytest.mark.gpu
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = torch.device("cuda")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ffn.npz")
 
-# name: (Cin, pre_norm, identity_fc, residual, post norm)
-VARIANTS = {
-    "base_norm": (256, True, True, False, True),
-    "base": (256, True, True, False, False),
-    "prob_add_norm": (128, False, False, True, True),
-    "prob": (128, False, False, False, False),
-    "c256_nopre_id": (256, False, True, False, True),
-    "c128_pre": (128, True, False, False, True),
-}
-ROWS = (1, 31, 32, 33, 127, 128, 129, 1000)   # the edges of 32 rows and of 128 (the 32-row kernel; the 128-row one: big_rows())
 N_VARIANT = 1000
-
-
-def parts(sd):
-    """A weight mapping as ``ffn_block`` takes it: the module's part, and the post norm's pair or ``None``."""
-    return ref.module_state(sd), ((sd["norm.weight"], sd["norm.bias"]) if "norm.weight" in sd else None)
 
 
 class Case:
@@ -59,8 +44,8 @@ class Case:
             self.truth = ref.ffn_ref(self.x.double(), self.sd64, None if self.res is None else self.res.double())
             self.torch32 = ref.ffn_ref(self.x, self.sd, self.res)
             self.native = self.run(self.x, self.res)
-        self.Y = (self.torch32.double() - self.truth).abs().max().item()
-        self.bound = 2 * self.Y + 4 * EPS32 * self.truth.abs().max().item()
+        self.Y = max_error(self.torch32, self.truth)
+        self.bound = bound(self.Y, self.truth)
 
     def run(self, x, res=None, sd=None):
         module, norm = parts(self.sd if sd is None else sd)
@@ -73,20 +58,11 @@ def case(name, dead=False):
     return Case(name, dead=dead)
 
 
-def held(what, got, truth, bound):
-    err = (got.double() - truth).abs().max().item()
-    print(f"{what}: max|native - truth| = {err:.3e}, bound = {bound:.3e}, ratio = {err / bound:.3f}")
-    assert got.shape == truth.shape and torch.isfinite(got).all()
-    assert err <= bound, (what, err, bound)
-
-
 def raw_call(x, sd, out, res=None, n=None, cin=None, F_=512, E=128):
     """The C entry point on caller-made buffers (``sd``: a weight mapping on the GPU)."""
     module, norm = parts(sd)
-    params = ffn_mod._param_list(module, norm)
-    table = (ctypes.c_void_p * 10)(*[None if p is None else p.data_ptr() for p in params])
     _lib.call("gf_ffn_forward", x.device, x.shape[0] if n is None else n, x.shape[1] if cin is None else cin, F_, E,
-              x, ctypes.cast(table, ctypes.c_void_p), res, out)
+              x, ptr_table(ffn_mod._param_list(module, norm), 10), res, out)
     return out
 
 
@@ -135,7 +111,7 @@ def test_the_two_kernels_give_the_same_bits(name):
     assert torch.equal(native[:N_VARIANT], c.native)
 
 
-@pytest.mark.parametrize("r", [1, 31, 32, 33, 127, 128, 129])
+@pytest.mark.parametrize("r", TILE_EDGES)
 @pytest.mark.parametrize("name", ["base_norm", "prob_add_norm"])
 def test_tile_kernel_at_its_edges(name, r):
     """The 128-row kernel with r rows in its last tile: the values, the prefix, and nothing written beyond row n."""
@@ -206,13 +182,13 @@ def test_module_with_the_fixture_s_weights(name):
     norm.to(DEV)
     x = torch.from_numpy(g[name + ".input"]).to(DEV)
 
-    def bound(key):
+    def recorded(key):
         t = g[f"{name}.{key}64"]
-        return 2 * np.abs(g[f"{name}.{key}32"].astype(np.float64) - t).max() + 4 * EPS32 * np.abs(t).max()
+        return bound(max_error(g[f"{name}.{key}32"], t), t)
     with torch.no_grad():
-        held(f"fixture {name} ffn", module(x), torch.from_numpy(g[name + ".ffn64"]).to(DEV), bound("ffn"))
+        held(f"fixture {name} ffn", module(x), torch.from_numpy(g[name + ".ffn64"]).to(DEV), recorded("ffn"))
         block = ffn_block(x, module, norm=norm, residual=x if ref.FOLLOWED_BY_ADD[name] else None)
-        held(f"fixture {name} block", block, torch.from_numpy(g[name + ".block64"]).to(DEV), bound("block"))
+        held(f"fixture {name} block", block, torch.from_numpy(g[name + ".block64"]).to(DEV), recorded("block"))
 
 
 # ---- 2. invariants, bitwise -------------------------------------------------------------------------------------------------
@@ -270,18 +246,6 @@ def test_a_residual_of_zeros_changes_nothing():
 
 
 # ---- 3. module --------------------------------------------------------------------------------------------------------------
-
-@pytest.fixture
-def spy(monkeypatch):
-    names = []
-    real = _lib.call
-
-    def call(name, *a):
-        names.append(name)
-        return real(name, *a)
-    monkeypatch.setattr(_lib, "call", call)
-    return names
-
 
 def _module(name="base", seed=0, **over):
     """The family's module with the variant's weights (``base`` = the variants base / base_norm, ``prob`` = prob / prob_add_norm)."""
@@ -382,8 +346,7 @@ def test_entry_point_refuses_what_it_does_not_support():
 
 
 def _own_truth(what, out, truth, y32):
-    y = (y32.double() - truth).abs().max().item()
-    held(what, out, truth, 2 * y + 4 * EPS32 * truth.abs().max().item())
+    held(what, out, truth, bound(max_error(y32, truth), truth))
 
 
 def test_other_configurations_take_the_torch_route(spy):

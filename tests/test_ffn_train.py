@@ -12,6 +12,7 @@ import ffn_ref as ref
 import ffn_train_ref as tr
 from gaussianformer_amd import _lib
 from gaussianformer_amd.ffn import AsymmetricFFN, FFNBlockFunction, ffn_block_autograd, train_sizes
+from row_judge import host_table
 
 CPU = torch.device("cpu")
 FAMILY_ARGS = {"base": (256, True, True), "prob": (128, False, False)}    # Cin, pre_norm, identity_fc
@@ -76,12 +77,7 @@ def _buf():
 
 
 def _table(buf, drop=(), misalign=None):
-    table = (ctypes.c_void_p * 10)(*[buf.data_ptr()] * 10)
-    for i in drop:
-        table[i] = None
-    if misalign is not None:
-        table[misalign] = buf.data_ptr() + 4
-    return ctypes.cast(table, ctypes.c_void_p)
+    return host_table(buf, 10, drop, misalign)
 
 
 def _fwd(n=4, cin=256, f=512, e=128, drop=(), misalign=None, keep_hidden=True, scale_hidden=1.0, keep_out=True, scale_out=1.0,

@@ -9,10 +9,8 @@ on rows that pass the kink filter.  Per tensor ``max|native - truth| <= 2 Y + 4 
 ratios are printed (-s) and recorded in DESIGN.md §3.13d.
 
 Invariants are bitwise.  Nothing here reads past a buffer's end or inspects code."""
-import ctypes
 import functools
 
-import numpy as np
 import pytest
 import torch
 
@@ -20,15 +18,22 @@ import ffn_ref as ref
 import ffn_train_ref as tr
 from gaussianformer_amd import _lib, ffn as ffn_mod
 from gaussianformer_amd.ffn import AsymmetricFFN, ffn_block, ffn_block_autograd, train_sizes
-from test_ffn_gpu import ROWS, VARIANTS, parts
+from ffn_ref import VARIANTS, parts
+from row_ref import scalar_gradients
+from row_judge import ROWS, Guarded, judge_leaves, max_error, ptr_table, spy  # noqa: F401  (spy is a fixture)
 
 pytestmark = pytest.mark.gpu
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = torch.device("cuda")
 N_VARIANT = 1000
 P = 0.1
 B, CHUNK = _lib.GF_FFN_WGRAD_ROWS, _lib.GF_FFN_CHUNK_ROWS
 PER_ROW = ("out", "x", "residual")
+
+
+def gradients(forward, x, res, sd):
+    """``{"out": out, "x": d/dx, "residual": d/dresidual (where given), key: d/d sd[key]}`` of ``sum(forward(x, res, leaves) *
+    output_weights)``; ``forward`` is the restatement (masks bound) or the native functional."""
+    return scalar_gradients(forward, {"x": x, "residual": res}, sd, with_out=True)
 
 
 class Case:
@@ -47,7 +52,7 @@ class Case:
         return (self.kh[:n], self.ko[:n], P) if self.masked else (None, None, 0.0)
 
     def native_forward(self, kh, ko, p):
-        def forward(x, sd, res):
+        def forward(x, res, sd):
             module, norm = parts(sd)
             return ffn_block_autograd(x, module, norm=norm, residual=res, p_hidden=p, p_out=p, keep_hidden=kh, keep_out=ko)
         return forward
@@ -61,10 +66,10 @@ class Case:
         kh, ko, p = self.masks(n)
         scale = 1.0 / (1.0 - p)
 
-        def restated(x, sd, res):
+        def restated(x, res, sd):
             return tr.ffn_train_ref(x, sd, res, kh, scale, ko, scale)
-        return (tr.gradients(restated, x.double(), self.sd64, None if res is None else res.double()), tr.gradients(restated, x, self.sd, res),
-                tr.gradients(self.native_forward(kh, ko, p), x, self.sd, res))
+        return (gradients(restated, x.double(), None if res is None else res.double(), self.sd64), gradients(restated, x, res, self.sd),
+                gradients(self.native_forward(kh, ko, p), x, res, self.sd))
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,39 +77,12 @@ def case(name, masked=True, dead=False, count=tr.CANDIDATES):
     return Case(name, masked, dead, count)
 
 
-def held(c, n):
+def judged(c, n):
     """Every result of case ``c`` at ``n`` rows against its bound; returns the native results."""
     truth, t32, native = c.grads(n)
     ytruth, y32, _ = c.grads(max(n, N_VARIANT))
-    for k in PER_ROW:
-        if k not in truth:
-            continue
-        err = (native[k].double() - truth[k]).abs().max().item()
-        bound = 2 * (y32[k].double() - ytruth[k]).abs().max().item() + 4 * EPS32 * truth[k].abs().max().item()
-        print(f"{c.name} masked={c.masked} n={n} {k}: err = {err:.3e}, bound = {bound:.3e}, ratio = {err / bound if bound > 0 else 0.0:.3f}")
-        assert native[k].shape == truth[k].shape and bool(torch.isfinite(native[k]).all()), k
-        assert err <= bound, (k, err, bound)
-
-    def rel(g, k):
-        scale = truth[k].abs().max().item()
-        return (g[k].double() - truth[k]).abs().max().item() / scale if scale > 0 else None
-    keys = [k for k in truth if k not in PER_ROW]
-    yard = {}
-    for k in keys:
-        r = rel(t32, k)
-        if r is not None:
-            yard[tr.kind(k)] = max(yard.get(tr.kind(k), 0.0), r)
-    worst = {}
-    for k in keys:
-        assert native[k].shape == truth[k].shape and bool(torch.isfinite(native[k]).all()), k
-        r = rel(native, k)
-        if r is None:      # the truth is identically 0 (a dead hidden layer): so is the native gradient
-            assert bool((native[k] == 0).all()), k
-            continue
-        bound = 2 * yard[tr.kind(k)] + 4 * EPS32
-        worst[tr.kind(k)] = max(worst.get(tr.kind(k), 0.0), r / bound)
-        assert r <= bound, (k, r, bound)
-    print(f"{c.name} masked={c.masked} n={n} parameters, worst ratio per kind: " + ", ".join(f"{k} {v:.3f}" for k, v in sorted(worst.items())))
+    judge_leaves(native, truth, t32, tr.kind, f"{c.name} masked={c.masked} n={n}", per_row=PER_ROW,
+                 row_yardstick={k: max_error(y32[k], ytruth[k]) for k in PER_ROW if k in ytruth})
     return native
 
 
@@ -114,13 +92,13 @@ def held(c, n):
 @pytest.mark.parametrize("masked", [True, False])
 @pytest.mark.parametrize("name", list(VARIANTS))
 def test_values(name, masked, n):
-    held(case(name, masked), n)
+    judged(case(name, masked), n)
 
 
 @pytest.mark.parametrize("n", [B - 1, B, B + 1])
 @pytest.mark.parametrize("name", ["base_norm", "prob_add_norm"])
 def test_values_at_the_weight_gradient_block_s_edges(name, n):
-    held(case(name), n)
+    judged(case(name), n)
 
 
 def test_values_beyond_a_chunk():
@@ -129,7 +107,7 @@ def test_values_beyond_a_chunk():
     c = case("base_norm", True, False, 36000)
     n = CHUNK + 1
     assert c.rows >= n
-    native = held(c, n)
+    native = judged(c, n)
     x, res = c.inputs(n)
     module, norm = parts(c.sd)
     with torch.no_grad():
@@ -145,7 +123,7 @@ def test_values_beyond_a_chunk():
 
 def _grads_with(c, n, kh, ko, sd=None):
     x, res = c.inputs(n)
-    return tr.gradients(c.native_forward(kh, ko, P), x, c.sd if sd is None else sd, res)
+    return gradients(c.native_forward(kh, ko, P), x, res, c.sd if sd is None else sd)
 
 
 @pytest.mark.parametrize("name", ["base_norm", "prob_add_norm"])
@@ -174,7 +152,7 @@ def test_dead_hidden_layer(name):
     """``layers.0.0.bias = -1e6``: the hidden row is 0 in every feature, so are the three gradients behind it; the rest is held
     to the truth."""
     c = case(name, True, True)
-    g = held(c, 333)
+    g = judged(c, 333)
     for k in ("layers.0.0.weight", "layers.0.0.bias", "layers.1.weight"):
         assert bool((g[k] == 0).all()), k
 
@@ -239,7 +217,7 @@ def test_graph_replay_equals_eager():
     forward = c.native_forward(c.kh[:n].contiguous(), c.ko[:n].contiguous(), P)
 
     def step():
-        out = forward(x, leaves, None)
+        out = forward(x, None, leaves)
         return out, torch.autograd.grad((out * w).sum(), [x] + [leaves[k] for k in keys])
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -262,23 +240,18 @@ def _raw_step(c, n, kh, ko, tail=4096, fill=12345.0):
     x, res = c.inputs(n)
     module, norm = parts(c.sd)
     params = ffn_mod._param_list(module, norm)
-    table = (ctypes.c_void_p * 10)(*[None if p is None else p.data_ptr() for p in params])
+    table = ptr_table(params)
     grads = [None if p is None else torch.empty_like(p) for p in params]
-    gtable = (ctypes.c_void_p * 10)(*[None if g is None else g.data_ptr() for g in grads])
     saved_bytes, work_bytes = train_sizes(n, c.cin)
-    out = torch.full((n * 128 + tail,), fill, device=DEV)
-    gx = torch.full((n * c.cin + tail,), fill, device=DEV)
-    gres = torch.full((n * 128 + tail,), fill, device=DEV)
-    saved = torch.full((saved_bytes + tail,), 0x5A, dtype=torch.uint8, device=DEV)
-    work = torch.full((work_bytes + tail,), 0x5A, dtype=torch.uint8, device=DEV)
+    out, gx, gres = [Guarded(4 * n * width, DEV, 4 * tail, fill, body=fill) for width in (128, c.cin, 128)]
+    saved, work = [Guarded(nbytes, DEV, tail, 0x5A, body=0x5A) for nbytes in (saved_bytes, work_bytes)]
     scale = 1.0 / (1.0 - P)
-    _lib.call("gf_ffn_forward_train", DEV, n, c.cin, 512, 128, x, ctypes.cast(table, ctypes.c_void_p), res, kh, scale, ko, scale, out, saved, saved_bytes)
+    _lib.call("gf_ffn_forward_train", DEV, n, c.cin, 512, 128, x, table, res, kh, scale, ko, scale, out.buf, saved.buf, saved_bytes)
     go = tr.output_weights((n, 128), torch.float32).to(DEV)
-    _lib.call("gf_ffn_backward", DEV, n, c.cin, 512, 128, x, ctypes.cast(table, ctypes.c_void_p), kh, scale, ko, scale, saved, go, gx,
-              gres if res is not None else None, ctypes.cast(gtable, ctypes.c_void_p), work, work_bytes)
-    intact = (bool((out[n * 128:] == fill).all()) and bool((gx[n * c.cin:] == fill).all()) and bool((saved[saved_bytes:] == 0x5A).all())
-              and bool((work[work_bytes:] == 0x5A).all()) and bool((gres[n * 128:] == fill).all()) and (res is not None or bool((gres == fill).all())))
-    return out[:n * 128].view(n, 128), gx[:n * c.cin].view(n, c.cin), gres[:n * 128].view(n, 128), grads, intact
+    _lib.call("gf_ffn_backward", DEV, n, c.cin, 512, 128, x, table, kh, scale, ko, scale, saved.buf, go, gx.buf,
+              gres.buf if res is not None else None, ptr_table(grads), work.buf, work_bytes)
+    intact = all(g.intact() for g in (out, gx, gres, saved, work)) and (res is not None or bool((gres.floats(n, 128) == fill).all()))
+    return out.floats(n, 128), gx.floats(n, c.cin), gres.floats(n, 128), grads, intact
 
 
 @pytest.mark.parametrize("n", [1, 33, 129, B + 1])
@@ -328,8 +301,8 @@ def test_a_nan_stays_in_its_row(name, col):
     x[bad, col] = float("nan")
     kh, ko = c.kh[:n], c.ko[:n]
     scale = 1.0 / (1.0 - P)
-    native = tr.gradients(c.native_forward(kh, ko, P), x, c.sd, res)
-    t32 = tr.gradients(lambda x, sd, res: tr.ffn_train_ref(x, sd, res, kh, scale, ko, scale), x, c.sd, res)
+    native = gradients(c.native_forward(kh, ko, P), x, res, c.sd)
+    t32 = gradients(lambda x, res, sd: tr.ffn_train_ref(x, sd, res, kh, scale, ko, scale), x, res, c.sd)
     keep = torch.arange(n, device=DEV) != bad
     for k in PER_ROW:
         if k in native:
@@ -341,18 +314,6 @@ def test_a_nan_stays_in_its_row(name, col):
 
 
 # ---- 5. module ---------------------------------------------------------------------------------------------------------------
-
-@pytest.fixture
-def spy(monkeypatch):
-    names = []
-    real = _lib.call
-
-    def call(name, *a):
-        names.append(name)
-        return real(name, *a)
-    monkeypatch.setattr(_lib, "call", call)
-    return names
-
 
 def _module(name="base", **over):
     m = AsymmetricFFN(**dict(ref.FAMILIES[name], **over))

@@ -15,10 +15,10 @@ import torch
 
 import refine_ref
 from gaussianformer_amd import refine as R
+from row_judge import EPS32, bound
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EPS32 = float(np.finfo(np.float32).eps)
 PC = [-50.0, -50.0, -5.0, 50.0, 50.0, 3.0]
 
 
@@ -196,13 +196,13 @@ def judge(c, res, report=None):
             comp = dict(groups(c, name, res["composition"][name]))[label]
             assert torch.isfinite(nat).all(), label
             err, ref = float((nat - t).abs().max()), float((comp - t).abs().max())
-            bound = 2 * ref + 4 * EPS32 * float(t.abs().max())
-            print(f"{case_id(c)} {label}: native {err:.3e} composition {ref:.3e} bound {bound:.3e} "
-                  f"ratio {err / bound if bound else 0.0:.3f}")
+            limit = bound(ref, t)
+            print(f"{case_id(c)} {label}: native {err:.3e} composition {ref:.3e} bound {limit:.3e} "
+                  f"ratio {err / limit if limit else 0.0:.3f}")
             if report is not None:
-                report.append((case_id(c), label, err, ref, bound))
-            if not err <= bound:
-                bad.append((label, err, ref, bound))
+                report.append((case_id(c), label, err, ref, limit))
+            if not err <= limit:
+                bad.append((label, err, ref, limit))
             if name.startswith("grad_"):
                 zero = t == 0
                 if not bool((nat[zero] == 0).all()):
@@ -266,10 +266,10 @@ def test_modules_against_the_fixture(name):
         short = {"out.anchor_out": "anchor_out", "grad.anchor": "grad_anchor"}.get(k, k)
         for (label, tt), (_, nn_), (_, cc) in zip(groups(c, short, t), groups(c, short, nat), groups(c, short, comp)):
             err, ref = float((nn_ - tt).abs().max()), float((cc - tt).abs().max())
-            bound = 2 * ref + 4 * EPS32 * float(tt.abs().max())
-            print(f"{name} {label}: native {err:.3e} reference fp32 {ref:.3e} bound {bound:.3e}")
-            if not err <= bound:
-                bad.append((label, err, ref, bound))
+            limit = bound(ref, tt)
+            print(f"{name} {label}: native {err:.3e} reference fp32 {ref:.3e} bound {limit:.3e}")
+            if not err <= limit:
+                bad.append((label, err, ref, limit))
     assert not bad, bad
 
 

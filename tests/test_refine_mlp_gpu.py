@@ -14,60 +14,16 @@
 The measured ratios are in DESIGN.md §3.12b."""
 import functools
 
-import numpy as np
 import pytest
 import torch
 
 import refine_ref
 from gaussianformer_amd import refine as R
+from refine_ref import VARIANTS, make_inputs, make_module, outputs_of
+from row_judge import bound
 
 pytestmark = pytest.mark.gpu
-EPS32 = float(np.finfo(np.float32).eps)
-E = 128
 NS = (1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 1000)
-CLASSES = {1: R.SparseGaussian3DRefinementModule, 2: R.SparseGaussian3DRefinementModuleV2}
-
-
-def _v1(**kw):
-    return dict(refine_ref.FAMILIES["solid"], **kw)
-
-
-# name -> (settings, anchor columns beyond D)
-VARIANTS = {
-    "solid": (refine_ref.FAMILIES["solid"], 0),                                               # D 28
-    "gs144000": (refine_ref.FAMILIES["gs144000"], 0),                                         # D 28, no opacity
-    "prob": (refine_ref.FAMILIES["prob"], 0),                                                 # D 28, version 2
-    "D10": (_v1(semantics=False, semantic_dim=0, include_opa=False), 0),
-    "D11": (dict(refine_ref.FAMILIES["prob"], semantics=False, semantic_dim=0), 0),           # version 2
-    "D43": (_v1(semantic_dim=32, semantics_activation="softmax"), 0),                         # the tail in two passes
-    "Da>D": (_v1(), 5),
-    "R12": (_v1(refine_manual=list(range(12))), 3),                                           # anchor columns from 10 on are added too
-}
-
-
-def make_module(cfg, seed):
-    """The drop-in module at E = 128 with seeded weights, LayerNorm and Scale moved away from the identity as
-    tools/make_golden_refine.py moves them."""
-    torch.manual_seed(seed)
-    rng = np.random.default_rng(seed)
-    module = CLASSES[cfg["version"]](embed_dims=E, phi_activation="sigmoid", xyz_coordinate="cartesian",
-                                     **{k: v for k, v in cfg.items() if k != "version"})
-    with torch.no_grad():
-        for p in module.parameters():
-            p.add_(torch.from_numpy(rng.standard_normal(tuple(p.shape)).astype(np.float32)) * 0.1)
-    return module
-
-
-def make_inputs(D, extra, n, seed):
-    rng = np.random.default_rng(seed)
-    f32 = lambda a: torch.from_numpy(a.astype(np.float32))
-    feat, embed = f32(rng.standard_normal((n, E))), f32(rng.standard_normal((n, E)))
-    anchor = f32(np.concatenate([rng.uniform(-3.0, 3.0, (n, 3)), rng.standard_normal((n, D + extra - 3))], axis=-1))
-    return feat, anchor, embed
-
-
-def outputs_of(anchor_out, pred):
-    return dict(anchor_out=anchor_out, **{k: v for k, v in pred._asdict().items() if v is not None})
 
 
 class Setup:
@@ -104,10 +60,10 @@ class Setup:
         """Rule (1) on mlp_out against the first rows of the truth."""
         t = self.truth_mlp[:mlp_out.shape[0]] if rows is None else rows
         err = float((mlp_out.double().cpu() - t).abs().max())
-        bound = 2 * self.Y + 4 * EPS32 * float(t.abs().max())
-        print(f"{self.name} n={mlp_out.shape[0]}: mlp_out native {err:.3e} composition(n={self.n}) {self.Y:.3e} bound {bound:.3e} ratio {err / bound:.3f}")
+        limit = bound(self.Y, t)
+        print(f"{self.name} n={mlp_out.shape[0]}: mlp_out native {err:.3e} composition(n={self.n}) {self.Y:.3e} bound {limit:.3e} ratio {err / limit:.3f}")
         assert torch.isfinite(mlp_out).all()
-        assert err <= bound, (self.name, mlp_out.shape[0], err, self.Y, bound)
+        assert err <= limit, (self.name, mlp_out.shape[0], err, self.Y, limit)
 
     def check_tail(self, outs, mlp_out, anchor):
         """Rule (2): the fused outputs against the standalone tail on the bits the fused tail consumed."""

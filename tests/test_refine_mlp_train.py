@@ -13,7 +13,7 @@ import refine_mlp_train_ref as T
 import refine_ref
 from gaussianformer_amd import _lib
 from gaussianformer_amd import refine as R
-from test_refine_mlp_gpu import VARIANTS
+from refine_ref import VARIANTS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLASSES = {1: R.SparseGaussian3DRefinementModule, 2: R.SparseGaussian3DRefinementModuleV2}

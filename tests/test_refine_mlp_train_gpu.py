@@ -26,32 +26,16 @@ import refine_mlp_train_ref as T
 import refine_ref
 from gaussianformer_amd import _lib
 from gaussianformer_amd import refine as R
-from test_refine_mlp_gpu import VARIANTS, make_inputs, make_module, outputs_of
+from refine_ref import VARIANTS, make_module, outputs_of
+from row_ref import scalar_gradients
+from row_judge import EPS32, Guarded, edge_rows, judge_leaves, max_error, ptr_table
 
 pytestmark = pytest.mark.gpu
-EPS32 = float(np.finfo(np.float32).eps)
 E = 128
 B, CHUNK = _lib.GF_REFINE_MLP_WGRAD_ROWS, _lib.GF_REFINE_MLP_CHUNK_ROWS
-EDGES = (1, 31, 32, 33, 127, 128, 129, B - 1, B, B + 1, 2 * B + 76)
+EDGES = edge_rows(B)
 FULL = 1000
 GUARD = 256          # sentinel bytes behind every buffer the library writes
-
-
-def _guarded(nbytes, device, fill=None):
-    """A buffer of ``nbytes`` (a multiple of 4) with ``GUARD`` bytes of 0xA5 behind it."""
-    buf = torch.empty(nbytes + GUARD, dtype=torch.uint8, device=device)
-    if fill is not None:
-        buf[:nbytes].view(torch.float32).fill_(fill)
-    buf[nbytes:].fill_(0xA5)
-    return buf
-
-
-def _floats(buf, *shape):
-    return buf[:buf.numel() - GUARD].view(torch.float32).view(*shape)
-
-
-def _table(tensors):
-    return ctypes.cast((ctypes.c_void_p * 15)(*[t.data_ptr() for t in tensors]), ctypes.c_void_p)
 
 
 class Setup:
@@ -98,31 +82,31 @@ class Setup:
         saved_bytes, work_bytes = R.train_sizes(n, D, Da)
         res = dict(n=n, bufs=[])
 
+        def guarded(nbytes, fill=None):
+            res["bufs"].append(Guarded(nbytes, dev, GUARD, 0xA5, body=fill))
+            return res["bufs"][-1]
+
         def new(*shape, fill=None):
-            buf = _guarded(4 * int(np.prod(shape)), dev, fill)
-            res["bufs"].append(buf)
-            return _floats(buf, *shape)
+            return guarded(4 * int(np.prod(shape)), fill).floats(*shape)
 
         outs = [new(n, self.widths[k]) for k in refine_ref.NAMES]
         mlp_out = new(n, D)
-        saved, work = _guarded(saved_bytes, dev), _guarded(work_bytes, dev)
-        res["bufs"] += [saved, work]
-        table = _table(self.params)
+        saved, work = guarded(saved_bytes).buf, guarded(work_bytes).buf
+        table = ptr_table(self.params)
         _lib.call("gf_refine_mlp_forward_train", dev, n, E, D, Da, c.version, c.flags, c.R, c.S, cp, feat, embed, anchor, table,
                   mlp_out, *outs, saved, saved_bytes)
         grad_x, grad_anchor = new(n, E), new(n, Da)
         gmo = new(n, D) if want_gmo else None
         grads = [new(*p.shape, fill=prefill) for p in self.params]
         _lib.call("gf_refine_mlp_backward", dev, n, E, D, Da, c.version, c.flags, c.R, c.S, cp, feat, embed, anchor, table, saved,
-                  *gouts, grad_x, grad_anchor, gmo, _table(grads), work, work_bytes)
+                  *gouts, grad_x, grad_anchor, gmo, ptr_table(grads), work, work_bytes)
         res.update(outs=dict(zip(refine_ref.NAMES, outs)), mlp_out=mlp_out, grad_x=grad_x, grad_anchor=grad_anchor, gmo=gmo,
                    grads=dict(zip(R.MLP_KEYS, grads)))
         return res
 
     @staticmethod
     def finish(res):
-        for buf in res["bufs"]:
-            assert bool((buf[-GUARD:] == 0xA5).all()), "sentinel bytes behind a buffer were overwritten"
+        assert all(buf.intact() for buf in res["bufs"]), "sentinel bytes behind a buffer were overwritten"
         return res
 
     def run(self, n, **kw):
@@ -136,45 +120,33 @@ class Setup:
         pairs = [(t, g) for t, g in zip(outs, gouts) if g is not None]
         return torch.autograd.grad([t for t, _ in pairs], [o, a], [g for _, g in pairs])
 
-    def mlp_errors(self, res, feat, embed):
-        """Per tensor: (max|native - truth|, max|fp32 torch - truth|, max|truth|) with the call's own cotangent."""
+    def mlp_grads(self, res, feat, embed):
+        """(native, truth, float32 torch) gradients of the MLP with the call's own cotangent, on the CPU in float64 (the truth is
+        computed there)."""
         gmo = res["gmo"]
-        truth = T.vjp(refine_ref.mlp, feat.double().cpu() + embed.double().cpu(), self.state64, gmo.double().cpu())
-        torch32 = T.vjp(refine_ref.mlp, feat + embed, self.state, gmo)
-        native = dict(x=res["grad_x"], **res["grads"])
-        out = {}
-        for k, t in truth.items():
-            assert native[k].shape == t.shape and bool(torch.isfinite(native[k]).all()), (self.name, k)
-            out[k] = (float((native[k].double().cpu() - t).abs().max()), float((torch32[k].double().cpu() - t).abs().max()),
-                      float(t.abs().max()))
-        return out
+        def vjp(x, state, cotangent):
+            return scalar_gradients(lambda x, leaves: refine_ref.mlp(leaves, x), {"x": x}, {k: state[k] for k in R.MLP_KEYS}, cotangent)
+        truth = vjp(feat.double().cpu() + embed.double().cpu(), self.state64, gmo.double().cpu())
+        torch32 = vjp(feat + embed, self.state, gmo)
+        on_cpu = lambda g: {k: v.double().cpu() for k, v in g.items()}
+        return on_cpu(dict(x=res["grad_x"], **res["grads"])), truth, on_cpu(torch32)
 
     @functools.cached_property
     def full(self):
         return self.run(FULL)
 
     @functools.cached_property
-    def full_errors(self):
+    def full_grads(self):
         feat, _, embed = self.rows(FULL)
-        return self.mlp_errors(self.full, feat, embed)
+        return self.mlp_grads(self.full, feat, embed)
 
     def check_mlp(self, res, feat, embed):
         """Rule (3)."""
-        errs = self.mlp_errors(res, feat, embed)
-        n = res["n"]
-        err, _, ref = errs["x"]
-        bound = 2 * self.full_errors["x"][1] + 4 * EPS32 * ref
-        print(f"{self.name} n={n}: grad_x error {err:.3e} bound {bound:.3e} ratio {err / bound:.3f}")
-        worst = {"grad_x": err / bound}
-        failed = [] if err <= bound else [("x", err, bound)]
-        yard = {kind: max(errs[k][1] / errs[k][2] for k in R.MLP_KEYS if T.kind(k) == kind) for kind in T.KINDS}
-        for k in R.MLP_KEYS:
-            rel, bound = errs[k][0] / errs[k][2], 2 * yard[T.kind(k)] + 4 * EPS32
-            worst[T.kind(k)] = max(worst.get(T.kind(k), 0.0), rel / bound)
-            if not rel <= bound:
-                failed.append((k, rel, bound))
-        print(f"{self.name} n={n}: error / bound per kind: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
-        assert not failed, (self.name, n, failed)
+        native, truth, torch32 = self.full_grads if res is self.full else self.mlp_grads(res, feat, embed)
+        _, full_truth, full32 = self.full_grads
+        worst = judge_leaves(native, truth, torch32, T.kind, f"{self.name} n={res['n']}", per_row=("x",),
+                             row_yardstick={"x": max_error(full32["x"], full_truth["x"])})
+        assert sorted(worst) == sorted(("x",) + T.KINDS)
 
 
 @functools.lru_cache(maxsize=None)
@@ -317,7 +289,7 @@ def test_no_rows_zero_fills_the_gradients(name):
     consts = (ctypes.c_double * 11)(*s.rcfg.consts)
     c = s.rcfg
     _lib.call("gf_refine_mlp_backward", dev, 0, E, s.D, s.Da, c.version, c.flags, c.R, c.S, ctypes.cast(consts, ctypes.c_void_p),
-              None, None, None, None, None, *([None] * 8), None, None, None, _table(grads), None, 0)
+              None, None, None, None, None, *([None] * 8), None, None, None, ptr_table(grads), None, 0)
     torch.cuda.synchronize()
     for k, g in zip(R.MLP_KEYS, grads):
         assert bool((g == 0).all()), (name, k)

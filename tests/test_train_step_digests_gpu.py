@@ -27,9 +27,9 @@ import torch
 import anchor_embed_ref
 import ffn_ref
 from gaussianformer_amd import _lib
-from test_anchor_encoder_gpu import FAMILIES as ANCHOR_FAMILIES
-from test_ffn_gpu import VARIANTS as FFN_VARIANTS, parts
-from test_refine_mlp_gpu import VARIANTS as REFINE_VARIANTS, make_module, outputs_of
+from anchor_embed_ref import LAYOUTS as ANCHOR_FAMILIES
+from ffn_ref import VARIANTS as FFN_VARIANTS, parts
+from refine_ref import VARIANTS as REFINE_VARIANTS, make_module, outputs_of
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_step_digests.json")
 ROWS = (1, 33, 129, 513, 1100)
