@@ -31,6 +31,7 @@ GF_WORKSPACE_ZEROED = 2048
 GF_OCC_PROB, GF_OCC_MASK, GF_OCC_LOVASZ_IGNORE, GF_OCC_IGNORE_EMPTY, GF_OCC_NO_LOVASZ, GF_OCC_MAX_LAYERS = 1, 2, 4, 8, 16, 8
 GF_LIFT_MAX_BINS, GF_LIFT_MAX_ANCHORS, GF_PIXEL_LOSS_SOFTMAX, GF_PIXEL_LOSS_SIGMOID = 256, 8, 1, 2
 GF_DCN_MAX_KERNEL, GF_DCN_CHANNEL_GRANULE = 7, 32
+GF_MIOU_TARGETS_U8, GF_MIOU_FILTER_MINMAX, GF_MIOU_REMAP, GF_MIOU_MAX_CLASSES, GF_MIOU_MAX_D = 1, 2, 4, 32, 64
 GF_REFINE_RESTRICT_XYZ, GF_REFINE_XYZ_IDENTITY, GF_REFINE_OPACITY, GF_REFINE_SEM_SOFTMAX, GF_REFINE_SEM_SOFTPLUS = 1, 2, 4, 8, 16
 GF_REFINE_MLP_PARAMS, GF_REFINE_MLP_WGRAD_ROWS, GF_REFINE_MLP_CHUNK_ROWS = 15, 512, 32768
 GF_ANCHOR_EMBED_DIMS, GF_ANCHOR_EMBED_MAX_S, GF_ANCHOR_EMBED_PARAMS, GF_ANCHOR_EMBED_WGRAD_ROWS, GF_ANCHOR_EMBED_CHUNK_ROWS = 128, 32, 48, 512, 65536
@@ -96,6 +97,9 @@ SIGNATURES = {
     "gf_occ_loss_scratch_bytes": (_sz, [_i] * 4),
     "gf_occ_loss_forward": (_i, [_i] * 4 + [_vp, _ll, _ll] + [_vp] * 3 + [_f, _f] + [_i] * 3 + [_vp, _vp, _sz, _vp, _sz, _vp]),
     "gf_occ_loss_backward": (_i, [_i] * 4 + [_vp, _ll, _ll] + [_vp] * 3 + [_f, _f] + [_i] * 3 + [_vp, _vp, _vp, _sz, _vp]),
+    "gf_miou_workspace_size": (_sz, [_ll, _i, _i]),
+    "gf_miou_step": (_i, [_ll, _i, _i] + [_vp] * 3 + [_i, _vp, _i, _i] + [_vp, _vp] + [_vp, _sz, _vp]),
+    "gf_miou_step_logits": (_i, [_ll, _i, _i, _i, _i] + [_vp, _vp, _f] + [_vp, _vp] + [_i, _vp, _i, _i] + [_vp, _vp] + [_vp, _sz, _vp]),
     "gf_lift_workspace_bytes": (_sz, [_i] * 3),
     "gf_lift_pixels": (_i, [_i] * 6 + [_vp] * 5 + [_f] + [_i] * 3 + [_vp] * 6 + [_vp, _sz, _vp]),
     "gf_pixel_loss_workspace_bytes": (_sz, [_i] * 2),

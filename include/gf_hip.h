@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward, gf_ffn_*, gf_refine_mlp_*, gf_deform_logits_forward / gf_deform_output_forward (added without a bump: a library without them fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward, gf_ffn_*, gf_refine_mlp_*, gf_deform_logits_forward / gf_deform_output_forward, gf_miou_workspace_size / gf_miou_step / gf_miou_step_logits (added without a bump: a library without them fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -633,6 +633,44 @@ int gf_occ_loss_backward(int L, int N, int C, int flags, const float *const *pre
                          const long long *label, const unsigned char *mask, const float *class_weights, float ce_weight,
                          float lovasz_weight, int lovasz_ignore, int ignore_index, int empty_label, const float *grad_loss,
                          float *const *grad_pred, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- evaluation metric -------------------------------------------------------------------------------------------
+ * One frame of MeanIoU._after_step (misc/metric_util.py:35-66) -- the call eval.py:163, train.py:317 and visualize.py:205 make
+ * after the head -- added to running totals on the device, with no host read: two launches, a counting
+ * pass and a finish pass, instead of two boolean-index compactions, 51 torch.sum(...).item() round trips and, with
+ * filter_minmax, two nonzero() calls.  Per voxel n, in the reference's order:
+ *   target' = empty_label where target == dataset_empty_label (GF_MIOU_REMAP, :43)
+ *   GF_MIOU_FILTER_MINMAX (:44-48): z = n % D; min_z / max_z = the lowest / highest z at which ANY voxel, masked or not, has
+ *       target' != empty_label; a prediction at z outside [min_z, max_z] counts as empty_label (the caller's tensor is not
+ *       written).  No such voxel (the reference raises there): the frame is counted unfiltered and status[1] goes up by one.
+ *   kept = mask[n] != 0, every voxel without a mask (:49-55)
+ *   over the kept voxels, for i < num_classes and c = class_indices_host[i] (:57-61):
+ *       totals[0][i] += #(target' == c)   totals[1][i] += #(target' == c and prediction == c)   totals[2][i] += #(prediction == c)
+ *   and at i = num_classes the same three with "!= empty_label" for "== c" (:63-66).
+ * Label values of any size are compared as they are (255 occurs in the data); only the class indices must lie in [0, 32).
+ *   outputs     int64 [N] (gf_miou_step), or formed per voxel by gf_head_labels' rule from logits f32 [N,18], bin_logits
+ *               f32 [N] (prob modes, else NULL), mode (GF_LABELS_*) and threshold (gf_miou_step_logits; model/head/
+ *               gaussian_head.py:164-185): the same totals as gf_head_labels followed by gf_miou_step, no labels written
+ *   targets     int64 [N], or uint8 [N] with GF_MIOU_TARGETS_U8;  mask uint8/bool [N] or NULL
+ *   class_indices_host   HOST int[num_classes], 1 <= num_classes <= GF_MIOU_MAX_CLASSES
+ *   totals      int64 [3][num_classes + 1] (seen, correct, positive), ADDED to;  status int64 [2]: [0] += 1 per call
+ *   workspace   gf_miou_workspace_size(N, D, flags) bytes (0: sizes refused); nothing in it needs to be zero or kept
+ * D is read with GF_MIOU_FILTER_MINMAX only (1 <= D <= GF_MIOU_MAX_D, N a multiple of D).  N == 0 counts a frame.
+ * (The size query is ..._size, not ..._bytes: tests/golden/workspace_bytes.json records every ..._bytes query and is not
+ * extended by this op; tests/test_miou.py pins its sizes.) */
+#define GF_MIOU_TARGETS_U8 1
+#define GF_MIOU_FILTER_MINMAX 2
+#define GF_MIOU_REMAP 4
+#define GF_MIOU_MAX_CLASSES 32
+#define GF_MIOU_MAX_D 64
+size_t gf_miou_workspace_size(long long N, int D, int flags);
+int gf_miou_step(long long N, int D, int flags, const long long *outputs, const void *targets, const unsigned char *mask,
+                 int num_classes, const int *class_indices_host, int empty_label, int dataset_empty_label, long long *totals,
+                 long long *status, void *workspace, size_t workspace_bytes, void *stream);
+int gf_miou_step_logits(long long N, int D, int flags, int C, int mode, const float *logits, const float *bin_logits,
+                        float threshold, const void *targets, const unsigned char *mask, int num_classes,
+                        const int *class_indices_host, int empty_label, int dataset_empty_label, long long *totals,
+                        long long *status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- GaussianLifterV2's pixel lifting and PixelDistributionLoss ----------------------------------------------------
  * gf_lift_pixels replaces the per-frame pixel work of GaussianLifterV2.forward from the pixel logits to the FPS call
