@@ -4,3 +4,13 @@ cross-attention sampler (``DeformableAggregationFunction``).  Hand-written HIP k
 behind a C-ABI shared library (``include/gf_hip.h``); this package is the Python host side
 that mirrors the reference's operator API."""
 __version__ = "0.1.0"
+
+__all__ = ["GaussianOccEncoder"]
+
+
+def __getattr__(name):
+    # (on first use: the package itself stays importable without torch being loaded)
+    if name == "GaussianOccEncoder":
+        from .encoder import GaussianOccEncoder
+        return GaussianOccEncoder
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

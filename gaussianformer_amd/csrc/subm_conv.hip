@@ -760,9 +760,21 @@ __global__ __launch_bounds__(256, (Format<CIN, COUT, RUN>::kMinBlocks)) void gf_
     }
 }
 
-// out[i] = sum over k ascending of the partial rows of (i, k): COUT/4 lanes per point
-template <int COUT>
-__global__ __launch_bounds__(256) void gf_subm_reduce_kernel(SubmArgs a)
+// what gf_subm_conv_apply_epilogue applies to a finished row before it is stored (every part optional, in this order):
+// + bias, + residual[i], LayerNorm, ReLU
+struct SubmEpilogue {
+    const float *bias;       // [Cout] or null
+    const float *residual;   // [N, Cout] or null
+    const float *ln_weight;  // [Cout], with ln_bias or both null
+    const float *ln_bias;
+    int relu;
+};
+
+// out[i] = sum over k ascending of the partial rows of (i, k): COUT/4 lanes per point.  EPI: the row then passes through `e`
+// in the registers it was summed in (one float4 per lane, the LayerNorm's two sums by gf::group_sum over the row's lanes);
+// without EPI `e` is not read and the kernel is the instruction stream it was before the epilogue existed
+template <int COUT, bool EPI>
+__global__ __launch_bounds__(256) void gf_subm_reduce_kernel(SubmArgs a, SubmEpilogue e)
 {
     constexpr int CG = COUT / 4;
     constexpr int ROWS = 256 / CG;
@@ -810,6 +822,33 @@ __global__ __launch_bounds__(256) void gf_subm_reduce_kernel(SubmArgs a)
                     acc.x += e.x; acc.y += e.y; acc.z += e.z; acc.w += e.w;
                 }
             }
+        }
+    }
+    if constexpr (EPI) {
+        // Every lane of the workgroup arrives here (no early return above; the hit loop has reconverged), so the shuffles of
+        // group_sum read active lanes; a row >= N computes on zeros and row 0's residual and stores nothing.  A NaN row (over
+        // capacity) stays NaN through every part: the ReLU is a comparison, not fmaxf.
+        if (e.bias) {
+            const float4 b = reinterpret_cast<const float4 *>(e.bias)[tc];
+            acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
+        }
+        if (e.residual) {
+            const float4 r = reinterpret_cast<const float4 *>(e.residual + (size_t)(i < a.N ? i : 0) * COUT)[tc];
+            acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
+        }
+        if (e.ln_weight) {
+            // gf_ffn_forward's rule: the mean first, then the squared deviations (biased variance), eps = 1e-5
+            const float mean = group_sum((acc.x + acc.y) + (acc.z + acc.w), CG) * (1.f / COUT);
+            const float dx = acc.x - mean, dy = acc.y - mean, dz = acc.z - mean, dw = acc.w - mean;
+            const float var = group_sum((dx * dx + dy * dy) + (dz * dz + dw * dw), CG) * (1.f / COUT);
+            const float rstd = 1.f / sqrtf(var + 1e-5f);
+            const float4 g = reinterpret_cast<const float4 *>(e.ln_weight)[tc], b = reinterpret_cast<const float4 *>(e.ln_bias)[tc];
+            acc.x = dx * rstd * g.x + b.x; acc.y = dy * rstd * g.y + b.y;
+            acc.z = dz * rstd * g.z + b.z; acc.w = dw * rstd * g.w + b.w;
+        }
+        if (e.relu) {
+            acc.x = acc.x < 0.f ? 0.f : acc.x; acc.y = acc.y < 0.f ? 0.f : acc.y;
+            acc.z = acc.z < 0.f ? 0.f : acc.z; acc.w = acc.w < 0.f ? 0.f : acc.w;
         }
     }
     if (i < a.N) reinterpret_cast<float4 *>(a.out + (size_t)i * COUT)[tc] = acc;  // NaN for an over-capacity rulebook
@@ -1202,7 +1241,8 @@ extern "C" size_t gf_subm_apply_scratch_bytes(int N, int Cin)
 
 static int subm_conv_apply_impl(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
                                 const float *features, const float *weight, const void *tables, const int *pair_in,
-                                float *partial, float *out, void *scratch, size_t scratch_bytes, void *stream_)
+                                float *partial, float *out, void *scratch, size_t scratch_bytes, void *stream_,
+                                const gf::SubmEpilogue *epi = nullptr)
 {
     using namespace gf;
     hipStream_t stream = (hipStream_t)stream_;
@@ -1247,9 +1287,16 @@ static int subm_conv_apply_impl(int N, int batch, int X, int Y, int Z, int K, in
     } else {
         launch_gemm<SubmBf16x3, false>(Cin, Cout, tiles, stream, a, SubmSplit{}, 0);
     }
-    if (Cout == 128) hipLaunchKernelGGL(gf_subm_reduce_kernel<128>, dim3((N + rows - 1) / rows), dim3(256), 0, stream, a);
-    else if (Cout == 64) hipLaunchKernelGGL(gf_subm_reduce_kernel<64>, dim3((N + rows - 1) / rows), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(gf_subm_reduce_kernel<32>, dim3((N + rows - 1) / rows), dim3(256), 0, stream, a);
+    const dim3 rgrid((N + rows - 1) / rows);
+#define GF_REDUCE(CO)                                                                                                      \
+    do {                                                                                                                   \
+        if (epi) hipLaunchKernelGGL((gf_subm_reduce_kernel<CO, true>), rgrid, dim3(256), 0, stream, a, *epi);              \
+        else hipLaunchKernelGGL((gf_subm_reduce_kernel<CO, false>), rgrid, dim3(256), 0, stream, a, SubmEpilogue{});      \
+    } while (0)
+    if (Cout == 128) GF_REDUCE(128);
+    else if (Cout == 64) GF_REDUCE(64);
+    else GF_REDUCE(32);
+#undef GF_REDUCE
     GF_CHECK_LAUNCH();
     return GF_OK;
 }
@@ -1270,6 +1317,45 @@ extern "C" int gf_subm_conv_apply_scratch(int N, int batch, int X, int Y, int Z,
         return GF_EINVAL;
     }
     return subm_conv_apply_impl(N, batch, X, Y, Z, K, Cin, Cout, total_pairs, features, weight, tables, pair_in, partial, out, scratch, scratch_bytes, stream_);
+}
+
+// [p, p + pn) and [q, q + qn) share a byte
+static bool subm_overlap(const void *p, size_t pn, const void *q, size_t qn)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && a < b + qn && b < a + pn;
+}
+
+extern "C" int gf_subm_conv_apply_epilogue(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
+                                           const float *features, const float *weight, const void *tables, const int *pair_in,
+                                           float *partial, float *out, void *scratch, size_t scratch_bytes, const float *bias,
+                                           const float *residual, const float *ln_weight, const float *ln_bias, int relu,
+                                           void *stream_)
+{
+    // every refusal comes before the first HIP call (the shared ones inside subm_conv_apply_impl, ahead of its launches)
+    GF_REFUSE_AS(__func__, (ln_weight == nullptr) == (ln_bias == nullptr), "ln_weight = %p with ln_bias = %p: both or neither",
+                 (const void *)ln_weight, (const void *)ln_bias);
+    GF_REFUSE_AS(__func__, relu == 0 || relu == 1, "relu = %d is not 0 or 1", relu);
+    if (N > 0 && !scratch) {
+        gf::set_error("%s: null scratch (gf_subm_apply_scratch_bytes)", __func__);
+        return GF_EINVAL;
+    }
+    const struct { const char *name; const void *p; } aligned[] = {{"bias", bias}, {"residual", residual}, {"ln_weight", ln_weight},
+                                                                   {"ln_bias", ln_bias}, {"out", out}, {"partial", partial}};
+    for (const auto &q : aligned)
+        GF_REFUSE_AS(__func__, !gf::misaligned16(q.p), "%s = %p is not 16-byte aligned", q.name, q.p);
+    if (N > 0 && out && gf::subm_channels_ok(Cin, Cout) && K >= 1 && K <= 7 && total_pairs >= 0) {
+        const size_t row = (size_t)Cout * sizeof(float), out_bytes = (size_t)N * row;
+        const struct { const char *name; const void *p; size_t n; } inputs[] = {
+            {"residual", residual, out_bytes}, {"features", features, (size_t)N * Cin * sizeof(float)},
+            {"weight", weight, (size_t)K * K * K * Cin * row}, {"bias", bias, row}, {"ln_weight", ln_weight, row},
+            {"ln_bias", ln_bias, row}, {"partial", partial, (size_t)total_pairs * row}, {"scratch", scratch, scratch_bytes},
+            {"pair_in", pair_in, (size_t)total_pairs * sizeof(int)}, {"tables", tables, 1}};
+        for (const auto &q : inputs)
+            GF_REFUSE_AS(__func__, !subm_overlap(out, out_bytes, q.p, q.n), "out = %p aliases %s = %p", (const void *)out, q.name, q.p);
+    }
+    const gf::SubmEpilogue epi = {bias, residual, ln_weight, ln_bias, relu};
+    return subm_conv_apply_impl(N, batch, X, Y, Z, K, Cin, Cout, total_pairs, features, weight, tables, pair_in, partial, out, scratch, scratch_bytes, stream_, &epi);
 }
 
 extern "C" int gf_subm_conv_weight_grad(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout,

@@ -2,7 +2,9 @@
 
 Host mirror of ``SparseConv3D`` (model/encoder/gaussian_encoder/spconv3d_module.py:10-83), whose
 ``spconv.SubMConv3d`` has no ROCm build: the rulebook and the gather-GEMM run in
-``gf_subm_rulebook_* / gf_subm_conv_apply / gf_subm_conv_weight_grad`` (include/gf_hip.h).
+``gf_subm_rulebook_* / gf_subm_conv_apply / gf_subm_conv_weight_grad`` (include/gf_hip.h).  Without autograd the block's dense
+tail -- bias, LayerNorm, ReLU, ``output_proj``, the encoder's ``"add"`` / ``"norm"`` -- runs inside the convolutions' last pass
+(``gf_subm_conv_apply_epilogue``) and one ``gf_deform_output_forward`` launch.
 """
 import math
 
@@ -16,6 +18,37 @@ from torch.autograd.function import Function, once_differentiable
 from . import _lib
 
 f32, i32 = torch.float32, torch.int32
+E_NATIVE = 128   # the width at which the block's dense tail has a native form (gf_deform_output_forward)
+
+
+def _norm_pair(norm, what):
+    """``(weight, bias)`` of a post norm: an affine ``nn.LayerNorm`` with eps 1e-5, or a pair; ``(None, None)`` for ``None``."""
+    if norm is None:
+        return None, None
+    if isinstance(norm, nn.Module):
+        if not isinstance(norm, nn.LayerNorm) or norm.eps != 1e-5 or norm.weight is None or norm.bias is None:
+            raise ValueError(f"{what}: norm must be an affine LayerNorm with eps = 1e-5, or a (weight, bias) pair")
+        return norm.weight, norm.bias
+    try:
+        weight, bias = norm
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: norm must be an affine LayerNorm with eps = 1e-5, or a (weight, bias) pair") from None
+    if weight is None or bias is None:
+        raise ValueError(f"{what}: norm must be an affine LayerNorm with eps = 1e-5, or a (weight, bias) pair")
+    return weight, bias
+
+
+def _norm_native(norm):
+    """Whether ``_norm_pair`` accepts ``norm`` (the same checks, as a question)."""
+    if norm is None:
+        return True
+    if isinstance(norm, nn.Module):
+        return isinstance(norm, nn.LayerNorm) and norm.eps == 1e-5 and norm.weight is not None and norm.bias is not None
+    return isinstance(norm, (tuple, list)) and len(norm) == 2 and all(isinstance(t, torch.Tensor) for t in norm)
+
+
+def _apply_norm(x, norm):
+    return norm(x) if isinstance(norm, nn.Module) else nn.functional.layer_norm(x, (x.shape[-1],), norm[0], norm[1], 1e-5)
 
 
 class Rulebook:
@@ -110,17 +143,34 @@ class Rulebook:
                             "more than 2^31 - 1 neighbour pairs" if refused & 2 else
                             f"{total} neighbour pairs exceed the pair_capacity of {self.total}"))
 
-    def apply(self, features, weight):
-        """``out[N, Cout]`` for ``features [N, Cin]`` and ``weight [K^3, Cin, Cout]`` (no autograd)."""
+    def apply(self, features, weight, bias=None, residual=None, norm=None, relu=False):
+        """``out[N, Cout]`` for ``features [N, Cin]`` and ``weight [K^3, Cin, Cout]`` (no autograd).
+
+        With any of the further arguments the convolution's last pass finishes the row before it stores it
+        (``gf_subm_conv_apply_epilogue``): ``out = relu?(norm?((conv + bias) + residual))``, ``bias [Cout]``, ``residual [N, Cout]``,
+        ``norm`` an affine ``nn.LayerNorm(Cout)`` with eps 1e-5 or a ``(weight, bias)`` pair.  Without them it is the plain call."""
         lib = _lib.load()
         features, weight = _lib.as_arg(features), _lib.as_arg(weight)
         cin, cout = weight.shape[1], weight.shape[2]
         dev = features.device
+        epilogue = bias is not None or residual is not None or norm is not None or relu
+        if epilogue:
+            gamma, beta = _norm_pair(norm, "Rulebook.apply")
+            _lib.require_gpu(bias, residual, gamma, beta)
+            for name, t, shape in (("bias", bias, (cout,)), ("residual", residual, (self.N, cout)), ("norm weight", gamma, (cout,)),
+                                   ("norm bias", beta, (cout,))):
+                if t is not None and tuple(t.shape) != shape:
+                    raise ValueError(f"Rulebook.apply: {name} {tuple(t.shape)} is not {shape}")
+            bias, residual, gamma, beta = (_lib.aligned(t) for t in (bias, residual, gamma, beta))
         out = torch.empty(self.N, cout, dtype=f32, device=dev)
         partial = torch.empty(max(self.total, 1), cout, dtype=f32, device=dev)
         # (the rows as two f16 terms under a power-of-two scale per row, split once per call: gf_subm_conv_apply_scratch)
         nscratch = int(lib.gf_subm_apply_scratch_bytes(self.N, cin))
         scratch = torch.empty(max(nscratch, 16), dtype=torch.uint8, device=dev)
+        if epilogue:
+            _lib.call("gf_subm_conv_apply_epilogue", dev, *self.dims, cin, cout, self.total, features, weight, self.tables,
+                      self.pair_in, partial, out, scratch, nscratch, bias, residual, gamma, beta, int(bool(relu)))
+            return out
         _lib.call("gf_subm_conv_apply_scratch", dev, *self.dims, cin, cout, self.total, features, weight, self.tables,
                   self.pair_in, partial, out, scratch, nscratch)
         return out
@@ -210,9 +260,12 @@ class SparseConv3D(nn.Module):
     conv + LayerNorm + ReLU stages, :26-37), output projection.  The three stages share one
     rulebook -- a submanifold convolution keeps the active set."""
 
+    native_tail = True
+
     def __init__(self, in_channels, embed_channels, pc_range, grid_size, xyz_activation="sigmoid", use_out_proj=False,
                  kernel_size=5, use_multi_layer=False, pairs_per_point=None, duplicates="sum", **kwargs):
         super().__init__()
+        self.embed_channels = embed_channels
         # extra keyword ``duplicates`` ("sum" | "last"): what several anchors in one cell mean, see subm_conv3d
         # extra keyword: with ``pairs_per_point=n`` the rulebook is built for at most n * points neighbour pairs without
         # reading the pair count back (no host synchronisation in the encoder loop); ``self.last_rulebook.check()``
@@ -276,11 +329,20 @@ class SparseConv3D(nn.Module):
         bidx = torch.arange(bs, device=idx.device, dtype=torch.int32).repeat_interleave(g)[:, None]
         return torch.cat([bidx, idx], dim=-1)
 
-    def forward(self, instance_feature, anchor, out_range=None):
-        """``out_range=(lo, hi)`` (extra keyword, inference, batch size 1, single-layer blocks): ``instance_feature`` / ``anchor``
+    def forward(self, instance_feature, anchor, out_range=None, residual=None, norm=None):
+        """``residual=`` / ``norm=`` (extra keywords, as on the deformable block): the encoder's ``"add"`` / ``"norm"`` behind the
+        block, ``norm(block(instance_feature, anchor) + residual)`` with ``residual [b, g, C]`` and ``norm`` an ``nn.LayerNorm`` or a
+        ``(weight, bias)`` pair.  With ``native_tail`` (a class attribute, not a constructor key and not part of the
+        ``state_dict``), nothing that needs autograd, fp32 GPU tensors and ``embed_channels == 128`` they, the stages' bias,
+        LayerNorm and ReLU and ``output_proj`` run inside the convolutions' last pass and one ``gf_deform_output_forward`` launch;
+        every other call runs the torch layers, the two keywords as torch ops behind them.
+
+        ``out_range=(lo, hi)`` (extra keyword, inference, batch size 1, single-layer blocks): ``instance_feature`` / ``anchor``
         are the WHOLE (all-gathered) anchor set, the block is evaluated for the anchors ``[lo, hi)`` only and returns
         ``[1, hi - lo, C]`` -- the rows an anchor-sharded rank owns, bit-identical to the same rows of the whole block, at
         ``(hi - lo) / g`` of the gather-GEMM and projection work."""
+        if out_range is not None and (residual is not None or norm is not None):
+            raise ValueError("SparseConv3D: out_range= does not take residual= / norm= (the sharded frame applies them to its own rows)")
         bs, g, _ = instance_feature.shape
         indices = self.voxel_indices(anchor)
         feats = instance_feature.flatten(0, 1)
@@ -307,10 +369,65 @@ class SparseConv3D(nn.Module):
         rb = self.last_rulebook = Rulebook(indices, bs, self._spatial, self.kernel_size, pair_capacity=cap)
         if cap is not None and not rb.checked and rb._status_event is not None:
             self._unchecked.append(rb)
+        if self._native_tail(instance_feature, anchor, residual, norm):
+            return self._forward_native_tail(feats, rb, residual, norm).unflatten(0, (bs, g))
         if isinstance(self.layer, SubMConv3d):
             out = self.layer(feats, indices, bs, self._spatial, rulebook=rb)
         else:
             out = feats
             for m in self.layer:
                 out = m(out, indices, bs, self._spatial, rulebook=rb) if isinstance(m, SubMConv3d) else m(out)
-        return self.output_proj(out.unflatten(0, (bs, g)))
+        out = self.output_proj(out.unflatten(0, (bs, g)))
+        if residual is not None:
+            out = out + residual
+        if norm is not None:
+            out = _apply_norm(out, norm)
+        return out
+
+    def _native_tail(self, instance_feature, anchor, residual, norm):
+        """Whether this call's dense tail runs natively: the checks ``Rulebook.apply`` and ``deformable_output`` make, asked first."""
+        if not self.native_tail or self.embed_channels != E_NATIVE or not _norm_native(norm):
+            return False
+        if not isinstance(self.output_proj, (nn.Linear, nn.Identity)):
+            return False
+        if isinstance(self.output_proj, nn.Linear) and self.output_proj.bias is None:
+            return False
+        if not isinstance(self.layer, SubMConv3d):
+            stages = list(self.layer)
+            if len(stages) != 9:
+                return False
+            for conv, ln, act in zip(stages[0::3], stages[1::3], stages[2::3]):
+                if not (isinstance(conv, SubMConv3d) and isinstance(ln, nn.LayerNorm) and _norm_native(ln) and isinstance(act, nn.ReLU)):
+                    return False
+        tensors = [instance_feature, anchor, residual, *self.parameters()]
+        tensors += list(norm.parameters()) if isinstance(norm, nn.Module) else list(norm or ())
+        if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
+            return False
+        return not _lib.needs_grad(tensors)
+
+    def _forward_native_tail(self, feats, rb, residual, norm):
+        """``[b*g, 128]``: the block with every dense op behind a convolution inside that convolution's last pass, and
+        ``output_proj`` with the encoder's ``"add"`` / ``"norm"`` in one ``gf_deform_output_forward`` launch."""
+        from .deformable_block import deformable_output   # (here: deformable_block's imports reach back to this package)
+        res = None if residual is None else residual.flatten(0, 1)
+        proj = isinstance(self.output_proj, nn.Linear)
+
+        def source(conv, x):
+            return x * rb.representative_mask() if conv.duplicates == "last" else x
+        if isinstance(self.layer, SubMConv3d):
+            conv = self.layer
+            if proj:
+                out = rb.apply(source(conv, feats), conv.weight, bias=conv.bias)
+                return deformable_output(out, self.output_proj, residual_mode="none", residual=res, norm=norm)
+            return rb.apply(source(conv, feats), conv.weight, bias=conv.bias, residual=res, norm=norm)
+        out, stages = feats, list(self.layer)
+        for conv, ln in zip(stages[0::3], stages[1::3]):
+            out = rb.apply(source(conv, out), conv.weight, bias=conv.bias, norm=ln, relu=True)
+        if proj:
+            return deformable_output(out, self.output_proj, residual_mode="none", residual=res, norm=norm)
+        # (not the third stage's epilogue: its own LayerNorm and ReLU sit between the convolution and this add)
+        if res is not None:
+            out = out + res
+        if norm is not None:
+            out = _apply_norm(out, norm)
+        return out

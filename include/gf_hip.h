@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward, gf_ffn_*, gf_refine_mlp_*, gf_deform_logits_forward / gf_deform_output_forward, gf_miou_workspace_size / gf_miou_step / gf_miou_step_logits (added without a bump: a library without them fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward, gf_ffn_*, gf_refine_mlp_*, gf_deform_logits_forward / gf_deform_output_forward, gf_miou_workspace_size / gf_miou_step / gf_miou_step_logits, gf_subm_conv_apply_epilogue (added without a bump: a library without them fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -439,6 +439,23 @@ size_t gf_subm_apply_scratch_bytes(int N, int Cin);
 int gf_subm_conv_apply_scratch(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
                                const float *features, const float *weight, const void *tables, const int *pair_in,
                                float *partial, float *out, void *scratch, size_t scratch_bytes, void *stream);
+/* gf_subm_conv_apply_scratch with an epilogue in its last pass (the reduction holds a finished row in registers): for every
+ * row i < N, with c the sum of the row's partial rows in exactly the order gf_subm_conv_apply_scratch forms it,
+ *     out[i] = relu?( LN?( (c + bias) + residual[i] ) )
+ * every part optional (NULL / relu = 0), applied in that order; with all of them absent the bytes are gf_subm_conv_apply_scratch's.
+ * LN is LayerNorm over the Cout values with eps = 1e-5 and biased variance, the mean first and then the squared deviations --
+ * gf_ffn_forward's rule; a lane sums its four values as (x + y) + (z + w) and the Cout / 4 lanes of a row combine by a
+ * butterfly (xor Cout / 8 .. 1), so a row's bits depend neither on N nor on the row's place in its workgroup.  ReLU is
+ * v < 0 ? 0 : v: a NaN stays a NaN, and an over-capacity rulebook gives NaN in every output row whatever epilogue is asked for.
+ * bias, ln_weight, ln_bias: [Cout]; residual: [N, Cout]; all device pointers, 16-byte aligned, read only.  Refused with
+ * GF_EINVAL before any HIP call: ln_weight without ln_bias or the reverse, relu other than 0 or 1, a misaligned pointer, out
+ * overlapping residual or any other input, and everything gf_subm_conv_apply_scratch refuses.  scratch is
+ * gf_subm_apply_scratch_bytes(N, Cin) bytes as there.  N == 0 returns GF_OK without a launch.  No host synchronisation, no
+ * allocation, no atomics: graph-capturable and bitwise reproducible. */
+int gf_subm_conv_apply_epilogue(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
+                                const float *features, const float *weight, const void *tables, const int *pair_in,
+                                float *partial, float *out, void *scratch, size_t scratch_bytes, const float *bias,
+                                const float *residual, const float *ln_weight, const float *ln_bias, int relu, void *stream);
 int gf_subm_conv_weight_grad(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
                              const float *features, const float *grad_out, const void *tables, const int *pair_in,
                              const int *pair_out, float *grad_weight, void *stream);
