@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-from gaussianformer_amd.synthetic import make_splat_inputs
+from gaussianformer_amd import _lib
+from gaussianformer_amd.local_aggregate import SplatForwardPlan, splat_forward_labels
 
-from util import prep, to_dev
+from splat_cases import run_plan, same_bits, tensors, wave_equals_tile, wide_radius_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -20,26 +21,7 @@ LOGITS_ARG = 17        # SplatForwardPlan.args: 9 scalars, 8 inputs, then out_lo
 FLAGS_ARG = 2
 
 
-def _inputs(seed, P, H, W, D):
-    """P Gaussians + the whole-grid one; a tenth of them isotropic with scales of 1 - 12 m: radii of 6 - 72 voxels, i.e. from one
-    supertile to the whole of these grids, next to the config's own radii of 1 - 4 voxels."""
-    si = make_splat_inputs("nuscenes_gs25600_solid", seed=seed, P=P, H=H, W=W, D=D)
-    rng = np.random.default_rng(seed + 1000)
-    wide = rng.choice(P, size=P // 10, replace=False)
-    s = (1.0 + 11.0 * rng.random(len(wide))).astype(np.float32)
-    si.scales[wide] = s[:, None]
-    si.cov3D[wide] = (np.eye(3, dtype=np.float64)[None] / (s.astype(np.float64) ** 2)[:, None, None]).astype(np.float32)
-    return si
-
-
-def _tensors(gpu, si):
-    pi, mi, radii, cov6 = prep(si)
-    return to_dev(gpu, si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6)
-
-
-def _plan(gpu, si, t, flags=0, offset_floats=0, unzeroed=False):
-    from gaussianformer_amd import _lib
-    from gaussianformer_amd.local_aggregate import SplatForwardPlan
+def _plan(si, t, flags=0, offset_floats=0, unzeroed=False):
     plan = SplatForwardPlan(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, flags=flags)
     if offset_floats:
         n = plan.logits.numel()
@@ -53,32 +35,20 @@ def _plan(gpu, si, t, flags=0, offset_floats=0, unzeroed=False):
     return plan
 
 
-def _run_bits(plan):
+def _run(plan, tile=False):
+    """(logits, SplatState) of one run over the NaN pattern, every voxel written."""
     plan.logits.view(torch.int32).fill_(PATTERN)
-    bits = plan.run().view(torch.int32).cpu().numpy()
-    assert not (bits == PATTERN).any(), "a voxel was not written"
-    return bits
+    logits, state = run_plan(plan, tile)
+    assert not (logits.view(np.int32) == PATTERN).any(), "a voxel was not written"
+    return logits, state
 
 
-def _reference(gpu, si, t, flags=0):
-    from gaussianformer_amd import _lib
-    tile = _plan(gpu, si, t, flags=flags)
-    with _lib.option("splat.mfma_tile_kernel", 1):
-        ref = _run_bits(tile)
-    assert tile.state_words()[1] == _lib.GF_PATH_MATRIX_CORE
-    return ref
-
-
-def _wave_equals_tile(gpu, si, runs=1, want_path=None, **plan_kw):
-    from gaussianformer_amd import _lib
-    t = _tensors(gpu, si)
-    ref = _reference(gpu, si, t)
-    wave = _plan(gpu, si, t, **plan_kw)
+def _stores_equal_the_tile_kernels(gpu, si, runs=1, **plan_kw):
+    t = tensors(gpu, si)
+    tile = _run(_plan(si, t), tile=True)
+    wave = _plan(si, t, **plan_kw)
     for _ in range(runs):
-        got = _run_bits(wave)
-        assert wave.state_words()[1] == (want_path or _lib.GF_PATH_MATRIX_CORE_WAVE)
-        assert np.array_equal(got, ref)
-    return t, ref
+        wave_equals_tile(_run(wave), tile)
 
 
 @pytest.mark.parametrize("shape", [(8, 8, 16), (10, 13, 16), (16, 16, 12), (16, 16, 8), (16, 16, 4), (16, 16, 6)])
@@ -87,38 +57,34 @@ def test_logits_equal_the_tile_kernels_bit_for_bit(gpu, shape):
     in y.  16 x 16 x 12: a depth that is a multiple of 4 whose upper z unit crosses the edge.  16 x 16 x 8 and x 4: one z unit, whole
     and half.  16 x 16 x 6: the element-wise path."""
     H, W, D = shape
-    _wave_equals_tile(gpu, _inputs(61 + H + W + D, 1200, H, W, D))
+    _stores_equal_the_tile_kernels(gpu, wide_radius_scene(61 + H + W + D, 1200, H, W, D))
 
 
 @pytest.mark.parametrize("shape", [(8, 8, 16), (10, 13, 16)])
 @pytest.mark.parametrize("keep_logits", [False, True])
 def test_labels_are_the_argmax_of_the_tile_kernels_logits(gpu, shape, keep_logits):
     """Label mode takes its labels from the staged rows: the first maximum of the very values the tile kernel stores."""
-    from gaussianformer_amd import _lib
-    from gaussianformer_amd.local_aggregate import splat_forward_labels
     H, W, D = shape
-    si = _inputs(71 + H, 1200, H, W, D)
-    t = _tensors(gpu, si)
-    ref = _reference(gpu, si, t)
-    want = np.argmax(ref.view(np.float32), axis=1)
+    si = wide_radius_scene(71 + H, 1200, H, W, D)
+    t = tensors(gpu, si)
+    ref, state = _run(_plan(si, t), tile=True)
+    assert state.path == _lib.GF_PATH_MATRIX_CORE
+    want = np.argmax(ref, axis=1)
     out = splat_forward_labels(_lib.GF_SPLAT_BASE, *t, H, W, D, keep_logits=keep_logits)
     labels = (out[0] if keep_logits else out).cpu().numpy()
     assert np.array_equal(labels, want)
     if keep_logits:
-        assert np.array_equal(out[1].view(torch.int32).cpu().numpy(), ref)
+        same_bits(out[1].cpu().numpy(), ref, "labels instantiation's logits vs tile kernel")
 
 
 def test_prepared_forward_stores_the_same_logits(gpu):
     """GF_PREPARE_BACKWARD (its own instantiation of the wave kernel) at 10 x 13 x 16."""
-    from gaussianformer_amd import _lib
-    si = _inputs(81, 1200, 10, 13, 16)
-    _wave_equals_tile(gpu, si, flags=_lib.GF_PREPARE_BACKWARD)
+    _stores_equal_the_tile_kernels(gpu, wide_radius_scene(81, 1200, 10, 13, 16), flags=_lib.GF_PREPARE_BACKWARD)
 
 
 def test_long_rows(gpu):
     """P just above 39 552: the long-row instantiation, on 16 x 16 x 16."""
-    si = _inputs(82, 39_600, 16, 16, 16)
-    _wave_equals_tile(gpu, si)
+    _stores_equal_the_tile_kernels(gpu, wide_radius_scene(82, 39_600, 16, 16, 16))
 
 
 def test_second_units_and_the_counted_row_wait(gpu):
@@ -130,15 +96,15 @@ def test_second_units_and_the_counted_row_wait(gpu):
     cus = torch.cuda.get_device_properties(gpu).multi_processor_count
     side = 8 * (int(np.floor(np.sqrt(cus))) + 1)
     assert (side // 8) ** 2 * 8 > 8 * cus >= (side // 8 - 1) ** 2 * 8
-    _wave_equals_tile(gpu, _inputs(83, 2000, side, side, 16), runs=3)
+    _stores_equal_the_tile_kernels(gpu, wide_radius_scene(83, 2000, side, side, 16), runs=3)
 
 
 def test_output_16_bytes_past_a_64_byte_boundary(gpu):
     """An out_logits view that is only 16-byte aligned: the stores' segments no longer start on 64-byte boundaries; same bits."""
-    _wave_equals_tile(gpu, _inputs(84, 1200, 10, 13, 16), offset_floats=4)
+    _stores_equal_the_tile_kernels(gpu, wide_radius_scene(84, 1200, 10, 13, 16), offset_floats=4)
 
 
 def test_workspace_not_flagged_zeroed(gpu):
     """Without GF_WORKSPACE_ZEROED every wave reads the per-wave verdict words of the flag section, which the records pass writes
     with plain stores."""
-    _wave_equals_tile(gpu, _inputs(85, 1200, 10, 13, 16), unzeroed=True)
+    _stores_equal_the_tile_kernels(gpu, wide_radius_scene(85, 1200, 10, 13, 16), unzeroed=True)

@@ -8,6 +8,7 @@ import torch
 import oracle
 from gaussianformer_amd.synthetic import make_splat_inputs
 
+from splat_cases import bwd, range_bounds, run_route, tensors, units, wave_equals_tile
 from util import GRAD_RTOL, assert_grad_rows_close, assert_logits_close, hip_splat_forward, prep, print_grad_rows, whole_grid_rows
 
 GRAD_NAMES = ("means3D_grad", "opacity_grad", "semantics_grad", "cov3D_grad")
@@ -36,6 +37,14 @@ SMALL = [
 
 def _oracle_logits(si, pi, mi, radii, cov6):
     return oracle.splat_forward(si.variant, si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D)["logits"]
+
+
+def _reference_logits(si, pi, mi, radii, cov6):
+    """The reference's own kernels when oracle/_ref is built, else the CPU oracle."""
+    from oracle import ref as oref
+    if oref.available():
+        return oref.splat_forward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D)["logits"]
+    return _oracle_logits(si, pi, mi, radii, cov6)
 
 
 @pytest.mark.parametrize("config,P,H,W,D", SMALL)
@@ -92,16 +101,11 @@ def test_mfma_wave_and_tile_kernels_agree_bit_for_bit(gpu, config, kw):
     arithmetic on them: equal bits, whatever path (fast fill, chunked refill, long-row passes) built the lists."""
     from gaussianformer_amd import _lib
     si = make_splat_inputs(config, seed=4, **kw)
-    pi, mi, radii, cov6 = prep(si)
-    wave, _, wstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
-    with _lib.option("splat.mfma_tile_kernel", 1):
-        tile, _, tstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
-    assert _lib.SplatState.of(wstate).path == _lib.GF_PATH_MATRIX_CORE_WAVE
-    assert _lib.SplatState.of(tstate).path == _lib.GF_PATH_MATRIX_CORE
-    assert np.isfinite(wave["logits"]).all()
-    assert np.array_equal(wave["logits"], tile["logits"])
-    ref = _oracle_logits(si, pi, mi, radii, cov6)
-    assert_logits_close(wave["logits"], ref, tol=1e-4)
+    prepped = prep(si)
+    t = tensors(gpu, si, prepped)
+    wave = run_route(t, si, _lib.GF_MFMA_SPLAT)
+    wave_equals_tile(wave, run_route(t, si, _lib.GF_MFMA_SPLAT, tile=True))
+    assert_logits_close(wave[0], _oracle_logits(si, *prepped), tol=1e-4)
 
 
 def test_mfma_inexact_lattice_falls_back(gpu):
@@ -158,13 +162,9 @@ def test_mfma_forward_full_size(gpu, config):
     """BASELINE shapes: against the reference's own kernels when oracle/_ref is built, else the CPU oracle; linear in the
     semantics; deterministic."""
     from gaussianformer_amd import _lib
-    from oracle import ref as oref
     si = make_splat_inputs(config, seed=0)
     pi, mi, radii, cov6 = prep(si)
-    if oref.available():
-        want = oref.splat_forward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D)["logits"]
-    else:
-        want = _oracle_logits(si, pi, mi, radii, cov6)
+    want = _reference_logits(si, pi, mi, radii, cov6)
     got, *_ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
     assert_logits_close(got["logits"], want, tol=1e-4)
     again, *_ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
@@ -241,31 +241,10 @@ def test_mfma_module_keyword_and_autograd(gpu):
 
 # ---- round 4: the verdicts of the records pass (every call) and inputs at the edge of what stays on the matrix cores
 
-def _range_bounds(cov6, radii, H, W, D, step=(0.5, 0.5, 0.5)):
-    """numpy twin of ``range_of`` in gf_splat_prep_kernel: (overflow bound, accuracy bound) per Gaussian."""
-    c = np.abs(cov6.astype(np.float64))
-    sx, sy, sz = step
-    ex, ey, ez = (np.minimum(radii, H) + 3) * sx, (np.minimum(radii, W) + 3) * sy, (np.minimum(radii, D) + 5) * sz
-    bound = 0.7213475204444817 * (c[:, 0] + c[:, 1] + c[:, 2]) * (ex * ex + ey * ey + ez * ez)
-    rx, ry, rz = 1.5 * sx, 1.5 * sy, 3.5 * sz
-    Q = c[:, 0] * rx * rx + c[:, 1] * ry * ry + c[:, 2] * rz * rz + 2.0 * (c[:, 3] * rx * ry + c[:, 4] * ry * rz + c[:, 5] * rx * rz)
-    return bound, 0.7213475204444817 * (4.3 + np.sqrt(Q)) ** 2
-
-
-def _reference_logits(si, pi, mi, radii, cov6):
-    from oracle import ref as oref
-    if oref.available():
-        return oref.splat_forward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D)["logits"]
-    return _oracle_logits(si, pi, mi, radii, cov6)
-
-
-def _run_default(gpu, si, pi, mi, radii, cov6, flags=0):
-    import torch
-    from gaussianformer_amd import _lib
-    from gaussianformer_amd.local_aggregate import splat_forward
-    t = [torch.from_numpy(np.ascontiguousarray(a)).to(gpu) for a in (si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6)]
-    logits, _, _, _, state = splat_forward(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, flags=flags)
-    return logits.cpu().numpy(), state.view(torch.int32)[:3].tolist()
+def _run(gpu, si, pi, mi, radii, cov6, flags=0):
+    """splat_cases.run_route on fresh tensors: (logits, [not-dense flag, GF_PATH_*, verdict bits])."""
+    logits, state = run_route(tensors(gpu, si, (pi, mi, radii, cov6)), si, flags)
+    return logits, list(state[:3])
 
 
 @pytest.mark.parametrize("assume_dense", [False, True])
@@ -281,19 +260,19 @@ def test_mfma_large_semantics_fall_back(gpu, assume_dense):
     si.semantics *= np.float32(1e5)
     want = _reference_logits(si, pi, mi, radii, cov6)
     flags = _lib.GF_PTS_ASSUME_DENSE if assume_dense else 0
-    got, state = _run_default(gpu, si, pi, mi, radii, cov6, flags)
+    got, state = _run(gpu, si, pi, mi, radii, cov6, flags)
     assert state == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_OPASEM]
     assert_logits_close(got, want, tol=1e-4)
     # one Gaussian is enough, and so is a NaN
     si.semantics /= np.float32(1e5)
     si.semantics[123, 4] = np.float32(7e4)
-    got, state = _run_default(gpu, si, pi, mi, radii, cov6, flags)
+    got, state = _run(gpu, si, pi, mi, radii, cov6, flags)
     assert state[1:] == [_lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_OPASEM]
     assert_logits_close(got, _reference_logits(si, pi, mi, radii, cov6), tol=1e-4)
     # ... and just inside the bound (|opacity * semantics| < 64) the call stays on the matrix cores, still within the tolerance
     si.opacities[123] = np.float32(1.0)
     si.semantics[123, 4] = np.float32(63.0)
-    got, state = _run_default(gpu, si, pi, mi, radii, cov6, flags)
+    got, state = _run(gpu, si, pi, mi, radii, cov6, flags)
     assert state == [0, _lib.GF_PATH_MATRIX_CORE_WAVE, 0]
     assert_logits_close(got, _reference_logits(si, pi, mi, radii, cov6), tol=1e-4)
 
@@ -306,7 +285,7 @@ def test_mfma_coefficient_range_verdict_under_assume_dense(gpu):
     pi, mi, radii, cov6 = prep(si)
     cov6[5] = (np.float32(1.0 / 0.004 ** 2), np.float32(1.0), np.float32(1.0), 0, 0, 0)
     radii[5] = 12
-    got, state = _run_default(gpu, si, pi, mi, radii, cov6, _lib.GF_PTS_ASSUME_DENSE)
+    got, state = _run(gpu, si, pi, mi, radii, cov6, _lib.GF_PTS_ASSUME_DENSE)
     assert state == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_THETA]
     assert_logits_close(got, _reference_logits(si, pi, mi, radii, cov6), tol=1e-4)
 
@@ -335,30 +314,30 @@ def test_mfma_adversarial_inputs_just_inside_the_verdicts(gpu, seed):
                       [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
         A = R @ np.diag(1.0 / s ** 2) @ R.T
         c = np.array([A[0, 0], A[1, 1], A[2, 2], A[0, 1], A[1, 2], A[0, 2]])
-        _, near = _range_bounds(c[None].astype(np.float32), np.array([1]), si.H, si.W, si.D)
+        _, near = range_bounds(c[None].astype(np.float32), np.array([1]), si.H, si.W, si.D)
         target = rng.uniform(900.0, 1190.0)
         # scale A so that the accuracy bound hits the target: sqrt(t Q) = sqrt(target / 0.7213) - 4.3
         sq_now = np.sqrt(near[0] / 0.7213475204444817) - 4.3
         t = ((np.sqrt(target / 0.7213475204444817) - 4.3) / sq_now) ** 2
         cov6[g] = (c * t).astype(np.float32)
         for r in (4, 3, 2, 1):
-            b, n = _range_bounds(cov6[g][None], np.array([r]), si.H, si.W, si.D)
+            b, n = range_bounds(cov6[g][None], np.array([r]), si.H, si.W, si.D)
             if b[0] < 2.9e4:
                 break
         radii[g] = r
-    b, n = _range_bounds(cov6, radii, si.H, si.W, si.D)
+    b, n = range_bounds(cov6, radii, si.H, si.W, si.D)
     assert (b < 3e4).all() and (n < 1200).all() and (n[pick] > 880).all()
     scale = np.float32(10.0) ** rng.integers(-6, 1, size=(P, 1)).astype(np.float32)
     si.semantics = (si.semantics * scale).astype(np.float32)
     want = _reference_logits(si, pi, mi, radii, cov6)
-    got, state = _run_default(gpu, si, pi, mi, radii, cov6)
+    got, state = _run(gpu, si, pi, mi, radii, cov6)
     assert state == [0, _lib.GF_PATH_MATRIX_CORE_WAVE, 0], state
     assert_logits_close(got, want, tol=1e-4)
     # one step over the accuracy bound: the verdict notices and the call is still right
     g = int(pick[0])
     cov6[g] *= np.float32(2.0)
-    assert _range_bounds(cov6[g][None], radii[g:g + 1], si.H, si.W, si.D)[1][0] > 1200
-    got, state = _run_default(gpu, si, pi, mi, radii, cov6)
+    assert range_bounds(cov6[g][None], radii[g:g + 1], si.H, si.W, si.D)[1][0] > 1200
+    got, state = _run(gpu, si, pi, mi, radii, cov6)
     assert state == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_THETA]
     assert_logits_close(got, _reference_logits(si, pi, mi, radii, cov6), tol=1e-4)
 
@@ -372,7 +351,7 @@ def test_mfma_very_thin_far_reaching_gaussians(gpu):
     for g, r in ((3, 12), (77, 20), (150, 12)):
         cov6[g] = (np.float32(1e4), np.float32(4.0), np.float32(1.0), np.float32(3.0), 0, 0)
         radii[g] = r
-    got, state = _run_default(gpu, si, pi, mi, radii, cov6)
+    got, state = _run(gpu, si, pi, mi, radii, cov6)
     assert state == [0, _lib.GF_PATH_ARBITRARY, _lib.GF_VERDICT_THETA]
     assert_logits_close(got, _reference_logits(si, pi, mi, radii, cov6), tol=1e-4)
 
@@ -402,11 +381,6 @@ def test_registered_grid_skips_the_scan_and_keeps_the_verdicts(gpu):
     assert torch.isfinite(again).all()
 
 
-def _bwd(gpu, si, t, state, g, flags=0):
-    from util import hip_splat_backward
-    return hip_splat_backward(gpu, si, t, state, None, g, flags=flags)
-
-
 @pytest.mark.gpu
 def test_backward_takes_the_forward_records_when_the_workspace_still_holds_them(gpu):
     """The forward's records pass lays out the matrix-core backward's rows; the backward repeats that pass only if the workspace
@@ -420,34 +394,34 @@ def test_backward_takes_the_forward_records_when_the_workspace_still_holds_them(
     g = np.random.default_rng(5).standard_normal((si.pts.shape[0], 18)).astype(np.float32)
     _, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
     assert not _lib.SplatState.of(state0).rows_ready                 # a forward that was not told of a backward prepares nothing
-    plain = _bwd(gpu, si, t, state0, g)
+    plain = bwd(gpu, si, t, state0, g)
     _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
     words = _lib.SplatState.of(state)
     assert words.path == _lib.GF_PATH_MATRIX_CORE_WAVE and words.rows_ready
-    base = _bwd(gpu, si, t, state, g)                                    # records still there
+    base = bwd(gpu, si, t, state, g)                                    # records still there
     ref = oracle.splat_backward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D, g)
     for a, b in zip(base, ref):
         assert np.abs(a - b.reshape(a.shape)).max() <= 1e-4 * max(np.abs(b).max(), 1e-30)
     _rows_close(base, ref, whole_grid_rows(mi, radii, si.H, si.W, si.D), "records of the forward, P=1500 40x36x16")
-    again = _bwd(gpu, si, t, state, g)                                   # a second backward of the same forward
-    asserted = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
+    again = bwd(gpu, si, t, state, g)                                   # a second backward of the same forward
+    asserted = bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
     for a, b, c, d in zip(base, again, asserted, plain):
         assert np.array_equal(a, b) and np.array_equal(a, c) and np.array_equal(a, d)
     # another shape through the same workspace: its sections lie over this forward's records
     hip_splat_forward(gpu, other, *prep(other))
-    redo = _bwd(gpu, si, t, state, g)
+    redo = bwd(gpu, si, t, state, g)
     for a, b in zip(base, redo):
         assert np.array_equal(a, b)
     # ... and a caller who vouches for records that are gone gets NaN, not numbers
     hip_splat_forward(gpu, other, *prep(other))
-    wrong = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
+    wrong = bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
     assert all(np.isnan(a).all() for a in wrong)
     # the exact pipeline of another shape uses the workspace too
     _, t2, state2, _ = hip_splat_forward(gpu, other, *prep(other), flags=_lib.GF_EXACT_FP32)
     _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
     g2 = np.random.default_rng(6).standard_normal((other.pts.shape[0], 18)).astype(np.float32)
-    _bwd(gpu, other, t2, state2, g2, flags=_lib.GF_EXACT_FP32)
-    after = _bwd(gpu, si, t, state, g)
+    bwd(gpu, other, t2, state2, g2, flags=_lib.GF_EXACT_FP32)
+    after = bwd(gpu, si, t, state, g)
     for a, b in zip(base, after):
         assert np.array_equal(a, b)
 
@@ -469,10 +443,10 @@ def test_backward_after_a_prepared_forward_on_a_grid_of_few_workgroups(gpu, shap
     for fflags in (0, _lib.GF_PREPARE_BACKWARD):
         _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=fflags)
         words = _lib.SplatState.of(state)
-        nwg = 8 * -(-(-(-H // 8) * -(-W // 8) * 4 * -(-D // 8)) // 8)
+        nwg = 8 * -(-units((H, W, D)) // 8)
         if fflags and nwg < 64:
             assert not words.rows_ready, words
-        got = _bwd(gpu, si, t, state, g)
+        got = bwd(gpu, si, t, state, g)
         outs.append(got)
         for a, b in zip(got, ref):
             assert np.isfinite(a).all()
@@ -505,7 +479,7 @@ def test_backward_rows_of_whole_grid_gaussians_and_of_a_full_buffer(gpu, case):
         _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=fflags)
         if fflags:   # the forward reports whether every row fitted
             assert _lib.SplatState.of(state).rows_ready == (case == "several_whole_grid")
-        got = _bwd(gpu, si, t, state, g)
+        got = bwd(gpu, si, t, state, g)
         for a, b in zip(got, ref):
             assert np.isfinite(a).all()
             assert np.abs(a - b.reshape(a.shape)).max() <= 2e-4 * max(np.abs(b).max(), 1e-30)
@@ -529,11 +503,11 @@ def test_backward_when_a_supertile_has_more_candidates_than_a_published_list_hol
     g = np.random.default_rng(27).standard_normal((si.pts.shape[0], 18)).astype(np.float32)
     ref = oracle.splat_backward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D, g)
     _, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
-    plain = _bwd(gpu, si, t, state0, g)
+    plain = bwd(gpu, si, t, state0, g)
     _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
     words = _lib.SplatState.of(state)
     assert words.path == _lib.GF_PATH_MATRIX_CORE_WAVE and words.rows_ready
-    got = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
+    got = bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
     for a, b, c in zip(got, plain, ref):
         assert np.isfinite(a).all() and np.array_equal(a, b)
         assert np.abs(a - c.reshape(a.shape)).max() <= 2e-4 * max(np.abs(c).max(), 1e-30)
@@ -561,8 +535,8 @@ def test_backward_on_long_rows(gpu, config, kw):
     g = np.random.default_rng(1).standard_normal((si.pts.shape[0], 18)).astype(np.float32)
     whole = whole_grid_rows(mi, radii, si.H, si.W, si.D)
     _, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
-    plain = _bwd(gpu, si, t, state0, g)                                  # the backward lays its rows out itself, scans the rows
-    exact = _bwd(gpu, si, t, state0, g, flags=_lib.GF_EXACT_FP32)
+    plain = bwd(gpu, si, t, state0, g)                                  # the backward lays its rows out itself, scans the rows
+    exact = bwd(gpu, si, t, state0, g, flags=_lib.GF_EXACT_FP32)
     _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
     words = _lib.SplatState.of(state)
     assert not words.not_dense and words.path == _lib.GF_PATH_MATRIX_CORE_WAVE, words
@@ -570,7 +544,7 @@ def test_backward_on_long_rows(gpu, config, kw):
     assert prepared == (config == "nuscenes_gs144000"), words
     # "the rows do not fit": the module takes the Gaussian-major backward then
     assert words.rows_overflow == (not prepared and si.H > 16), words
-    got = _bwd(gpu, si, t, state, g, flags=(_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if prepared else 0)
+    got = bwd(gpu, si, t, state, g, flags=(_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if prepared else 0)
     for a, b, c, name in zip(got, plain, exact, ("means", "opacity", "semantics", "cov")):
         if prepared:   # (rows that do not fit are added with atomics, in no fixed order)
             assert np.array_equal(a, b), name
@@ -592,7 +566,7 @@ def test_forward_and_backward_past_the_longest_rows(gpu):
     words = _lib.SplatState.of(state)
     assert not words.not_dense and words.path == _lib.GF_PATH_MATRIX_CORE and not words.rows_ready and not words.rows_overflow, words
     assert np.abs(out["logits"] - exact_out["logits"]).max() <= 1e-4
-    whole = _bwd(gpu, si, t, state, g)          # the Python op shards the set for the C entry point (262 144 per call)
+    whole = bwd(gpu, si, t, state, g)          # the Python op shards the set for the C entry point (262 144 per call)
     from gaussianformer_amd.local_aggregate import BACKWARD_MAX_GAUSSIANS
     assert BACKWARD_MAX_GAUSSIANS < 270000 and all(np.isfinite(a).all() and a.shape[0] == 270000 for a in whole)
     # two shards of 135 000: the matrix-core backward (long rows) of each against the exact one
@@ -604,8 +578,8 @@ def test_forward_and_backward_past_the_longest_rows(gpu):
         _, ts, sts, _ = hip_splat_forward(gpu, sh, spi, smi, sradii, scov6, flags=_lib.GF_PREPARE_BACKWARD)
         ws = _lib.SplatState.of(sts)
         assert ws[1] == _lib.GF_PATH_MATRIX_CORE_WAVE, ws
-        got = _bwd(gpu, sh, ts, sts, g, flags=(_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if ws.rows_ready else 0)
-        ex = _bwd(gpu, sh, ts, sts, g, flags=_lib.GF_EXACT_FP32)
+        got = bwd(gpu, sh, ts, sts, g, flags=(_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if ws.rows_ready else 0)
+        ex = bwd(gpu, sh, ts, sts, g, flags=_lib.GF_EXACT_FP32)
         from util import assert_grad_rows_close
         for a, b, w, name in zip(got, ex, whole, ("means", "opacity", "semantics", "cov")):
             assert_grad_rows_close(a, b.reshape(a.shape), None, what=name)
@@ -874,14 +848,14 @@ def test_list_builder_regimes_agree_across_kernels_and_with_the_oracle(gpu, side
     gref = oracle.splat_backward("base", si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6, si.H, si.W, si.D, g)
     _, t, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
     assert _lib.SplatState.of(state0).path == _lib.GF_PATH_MATRIX_CORE_WAVE
-    plain = _bwd(gpu, si, t, state0, g)
+    plain = bwd(gpu, si, t, state0, g)
     _, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
     words = _lib.SplatState.of(state)
     print("prepared forward: state words", words)
     assert words.path == _lib.GF_PATH_MATRIX_CORE_WAVE
     assert words.rows_ready == (side == 32)
-    prepared = _bwd(gpu, si, t, state, g)
-    asserted = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if words.rows_ready else prepared
+    prepared = bwd(gpu, si, t, state, g)
+    asserted = bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID) if words.rows_ready else prepared
     for a, b, c, r in zip(plain, prepared, asserted, gref):
         print("backward: max error / max |ref|", np.abs(a - r.reshape(a.shape)).max() / max(np.abs(r).max(), 1e-30))
         assert np.isfinite(a).all()

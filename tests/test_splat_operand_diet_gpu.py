@@ -6,20 +6,20 @@ behind the transpose) bit for bit -- the logits compared as int32, so +0 and -0 
 
 Every Gaussian here has radius 1 and its centre voxel in the interior of one unit (a double brick of 4 x 4 x 8 voxels), so it hits
 exactly that unit; the hit counts are recounted on the CPU from ``oracle.prepare_splat_inputs`` and asserted."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+from gaussianformer_amd import _lib
+from gaussianformer_amd.local_aggregate import SplatForwardPlan
 from gaussianformer_amd.synthetic import cov_inverse, make_splat_inputs
 
-from util import assert_grad_rows_close, assert_logits_close, hip_splat_backward, hip_splat_forward, prep, to_dev, whole_grid_rows
+from splat_cases import (SHORT_ROW_P, WAVE, WAVE_LONG, all_routes_agree, bwd, range_bounds, render_kernel, run_plan, same_bits, tensors,
+                         wave_equals_tile)
+from util import assert_grad_rows_close, hip_splat_forward, prep, whole_grid_rows
 
 pytestmark = pytest.mark.gpu
 
-K_WROW = 618            # splat_fwd.hip: kWRow, the longest bitmask row (in words) the short-row instantiation holds in LDS
-ROUTE_WAVE, ROUTE_WAVE_LONG = 3, 4   # word 0 of gf_debug_splat_route
 COUNTS = (1, 31, 32, 33, 63)         # hits of a unit: the last group has 31, 1, 0, 31 and 1 dead rows
 GRIDS = {
     # grid -> origins of the five counted units (a unit: 4 x 4 columns, 8 voxels deep)
@@ -31,19 +31,6 @@ GRIDS = {
     (24, 36, 16): [(16, 32, 0), (16, 32, 8), (20, 28, 0), (0, 0, 8), (12, 16, 0)],
 }
 PREPARING = (24, 36, 16)
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.int32)
-
-
-def _route_kernel(P, H, W, D):
-    from gaussianformer_amd import _lib
-    fn = _lib.load().gf_debug_splat_route
-    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_int]
-    out = (ctypes.c_int * 18)()
-    assert fn(_lib.GF_SPLAT_BASE, _lib.GF_WORKSPACE_ZEROED, -1, P, H * W * D, H, W, D, out, 18) == 18
-    return out[0]
 
 
 def _placed_inputs(H, W, D, plan, seed):
@@ -104,38 +91,8 @@ def _counted_inputs(shape, seed=0, padding=()):
 
 
 def _forward_all_routes(gpu, si, prepped, exact_tol=1e-4):
-    """default == tile == GF_PREPARE_BACKWARD == labels instantiation's logits, bit for bit; labels = argmax; within 1e-4 of the
-    exact-fp32 kernel (``exact_tol=None``: not compared -- for inputs at the thin end of the theta verdict, where the exact kernel's own
-    fp32 quadratic form cancels from terms of several hundred).  Returns the wave kernel's logits."""
-    from gaussianformer_amd import _lib
-    from gaussianformer_amd.local_aggregate import splat_forward, splat_forward_labels
-    H, W, D = si.H, si.W, si.D
-    pi, mi, radii, cov6 = prepped
-    t = to_dev(gpu, si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6)
-    V = _lib.GF_SPLAT_BASE
-
-    def run(flags):
-        logits, _, _, _, state = splat_forward(V, *t, H, W, D, flags=flags)
-        return logits.cpu().numpy(), _lib.SplatState.of(state)
-
-    wave, wstate = run(0)
-    assert (wstate.not_dense, wstate.path, wstate.verdict) == (False, _lib.GF_PATH_MATRIX_CORE_WAVE, 0), wstate   # "matrix cores"
-    assert np.isfinite(wave).all()
-    with _lib.option("splat.mfma_tile_kernel", 1):
-        tile, tstate = run(_lib.GF_MFMA_SPLAT)
-    assert tstate.path == _lib.GF_PATH_MATRIX_CORE, tstate
-    assert np.array_equal(_bits(wave), _bits(tile)), "wave kernel vs tile kernel"
-    prepared, pstate = run(_lib.GF_PREPARE_BACKWARD)
-    assert pstate.path == _lib.GF_PATH_MATRIX_CORE_WAVE and pstate.rows_ready == ((H, W, D) == PREPARING), pstate
-    assert np.array_equal(_bits(wave), _bits(prepared)), "default vs GF_PREPARE_BACKWARD"
-    labels, kept = splat_forward_labels(V, *t, H, W, D, keep_logits=True)
-    assert np.array_equal(_bits(kept.cpu().numpy()), _bits(wave)), "labels instantiation's logits"
-    assert np.array_equal(labels.cpu().numpy(), wave.argmax(axis=1))
-    if exact_tol is not None:
-        exact, estate = run(_lib.GF_EXACT_FP32)
-        assert estate.path not in (_lib.GF_PATH_MATRIX_CORE_WAVE, _lib.GF_PATH_MATRIX_CORE), estate
-        assert_logits_close(wave, exact, tol=exact_tol)
-    return wave
+    """splat_cases.all_routes_agree; a GF_PREPARE_BACKWARD call prepares on the ``PREPARING`` grid and on no other."""
+    return all_routes_agree(gpu, si, prepped, exact_tol=exact_tol, rows_ready=(si.H, si.W, si.D) == PREPARING)
 
 
 # ---- partial groups of every kind, channels 8 / 9 / 17, every short-row route ----------------------------------------------------
@@ -155,21 +112,10 @@ def test_partial_groups_of_every_kind_on_every_route(gpu, shape):
     counted = np.zeros((si.H, si.W, si.D), dtype=bool)
     for x0, y0, z0 in GRIDS[shape]:
         counted[x0:x0 + 4, y0:y0 + 4, z0:z0 + 8] = True
-    assert not _bits(wave).reshape(si.H, si.W, si.D, 18)[~counted].any()
+    assert not wave.view(np.int32).reshape(si.H, si.W, si.D, 18)[~counted].any()
 
 
 # ---- a first Gaussian that would show a leak -----------------------------------------------------------------------------------------
-def _range_bounds(cov6, radii, H, W, D, step=(0.5, 0.5, 0.5)):
-    """numpy twin of ``range_of`` in gf_splat_prep_kernel (tests/test_splat_mfma_gpu.py): (overflow bound, accuracy bound)."""
-    c = np.abs(cov6.astype(np.float64))
-    sx, sy, sz = step
-    ex, ey, ez = (np.minimum(radii, H) + 3) * sx, (np.minimum(radii, W) + 3) * sy, (np.minimum(radii, D) + 5) * sz
-    bound = 0.7213475204444817 * (c[:, 0] + c[:, 1] + c[:, 2]) * (ex * ex + ey * ey + ez * ez)
-    rx, ry, rz = 1.5 * sx, 1.5 * sy, 3.5 * sz
-    Q = c[:, 0] * rx * rx + c[:, 1] * ry * ry + c[:, 2] * rz * rz + 2.0 * (c[:, 3] * rx * ry + c[:, 4] * ry * rz + c[:, 5] * rx * rz)
-    return bound, 0.7213475204444817 * (4.3 + np.sqrt(Q)) ** 2
-
-
 @pytest.mark.parametrize("shape,count", [((16, 16, 16), 5), ((12, 20, 16), 37)])
 def test_a_strong_thin_first_gaussian_does_not_leak_through_dead_rows(gpu, shape, count):
     """The first Gaussian of a partial group (27 dead rows; 5 live ones behind a full group: 27 dead rows again) has opacity x
@@ -188,10 +134,10 @@ def test_a_strong_thin_first_gaussian_does_not_leak_through_dead_rows(gpu, shape
     # thin, rotated, scaled so that the accuracy bound of range_of is 1 100
     A = cov_inverse(np.array([[0.05, 0.4, 0.2]]), rng.standard_normal((1, 4)))[0]
     c = np.array([A[0, 0], A[1, 1], A[2, 2], A[0, 1], A[1, 2], A[0, 2]])
-    near = _range_bounds(c[None].astype(np.float32), np.array([1]), H, W, D)[1][0]
+    near = range_bounds(c[None].astype(np.float32), np.array([1]), H, W, D)[1][0]
     s = ((np.sqrt(1100.0 / 0.7213475204444817) - 4.3) / (np.sqrt(near / 0.7213475204444817) - 4.3)) ** 2
     cov6[first] = (c * s).astype(np.float32)
-    b, nb = _range_bounds(cov6, np.asarray(radii), H, W, D)
+    b, nb = range_bounds(cov6, np.asarray(radii), H, W, D)
     assert (b < 3e4).all() and (nb < 1200).all() and 1050 < nb[first] < 1150
     assert np.abs(si.opacities[first] * si.semantics[first]).max() < 64 and np.abs(si.opacities[first] * si.semantics[first]).min() >= 20
     hits = _unit_hits(si, mi, radii)
@@ -220,7 +166,7 @@ def test_exact_zeros_next_to_negative_dead_rows_stay_plus_zero(gpu):
     hits = _unit_hits(si, prepped[1], prepped[2])
     assert list(hits) == [origin] and list(hits[origin]) == [0, 1, 2]
     wave = _forward_all_routes(gpu, si, prepped)
-    bits = _bits(wave).reshape(H, W, D, 18)
+    bits = wave.view(np.int32).reshape(H, W, D, 18)
     x0, y0, z0 = origin
     last = bits[x0 + 3, y0 + 3, z0 + 7]
     assert (last[[3, 8, 17]] == 0).all(), last
@@ -235,8 +181,8 @@ def test_long_rows(gpu):
     five counted units as before, the rest of the Gaussians in the units of the supertiles that hold no counted unit (crowded:
     several passes of the list, each ending in a flush, which forms no partial group)."""
     shape = PREPARING
-    total = 64 * K_WROW + 1
-    assert _route_kernel(total - 1, *shape) == ROUTE_WAVE and _route_kernel(total, *shape) == ROUTE_WAVE_LONG
+    total = SHORT_ROW_P + 1
+    assert render_kernel(total - 1, shape) == WAVE and render_kernel(total, shape) == WAVE_LONG
     counted = {(x // 8, y // 8) for x, y, _ in GRIDS[shape]}
     others = [(x, y, z) for x in range(0, shape[0], 4) for y in range(0, shape[1], 4) for z in (0, 8) if (x // 8, y // 8) not in counted]
     rest = total - sum(COUNTS)
@@ -247,18 +193,12 @@ def test_long_rows(gpu):
 
 
 def test_one_workspace_eager_and_replayed_from_a_graph(gpu):
-    from gaussianformer_amd import _lib
-    from gaussianformer_amd.local_aggregate import SplatForwardPlan
     si, prepped = _counted_inputs((12, 20, 16), seed=5)
-    pi, mi, radii, cov6 = prepped
-    t = to_dev(gpu, si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6)
-    tile = SplatForwardPlan(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, flags=0)
-    with _lib.option("splat.mfma_tile_kernel", 1):
-        want = tile.run().cpu().numpy()
-    assert tile.state_words()[1] == _lib.GF_PATH_MATRIX_CORE
+    t = tensors(gpu, si, prepped)
+    tile = run_plan(SplatForwardPlan(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, flags=0), tile=True)
+    want = tile[0]
     plan = SplatForwardPlan(_lib.GF_SPLAT_BASE, *t, si.H, si.W, si.D, flags=0)
-    assert np.array_equal(_bits(plan.run().cpu().numpy()), _bits(want))
-    assert plan.state_words()[1] == _lib.GF_PATH_MATRIX_CORE_WAVE
+    wave_equals_tile(run_plan(plan), tile)
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
         plan.run(); torch.cuda.synchronize()
@@ -269,22 +209,21 @@ def test_one_workspace_eager_and_replayed_from_a_graph(gpu):
         plan.logits.fill_(float("nan"))
         g.replay()
         torch.cuda.synchronize()
-        assert np.array_equal(_bits(plan.logits.cpu().numpy()), _bits(want))
+        same_bits(plan.logits.cpu().numpy(), want, "replayed vs tile kernel")
 
 
 # ---- the prepared backward on what the new forward leaves -----------------------------------------------------------------------------
 def test_prepared_backward_after_the_forward(gpu):
-    from gaussianformer_amd import _lib
     si, prepped = _counted_inputs(PREPARING, seed=7)
     pi, mi, radii, cov6 = prepped
     g = np.random.default_rng(65).standard_normal((si.pts.shape[0], 18)).astype(np.float32)
     prepared, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
     words = _lib.SplatState.of(state)
     assert words.path == _lib.GF_PATH_MATRIX_CORE_WAVE and words.rows_ready, words
-    got = hip_splat_backward(gpu, si, t, state, None, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
+    got = bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
     plain, t0, state0, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6)
-    assert np.array_equal(_bits(prepared["logits"]), _bits(plain["logits"]))
-    exact = hip_splat_backward(gpu, si, t0, state0, None, g, flags=_lib.GF_EXACT_FP32)
+    same_bits(prepared["logits"], plain["logits"], "GF_PREPARE_BACKWARD vs default")
+    exact = bwd(gpu, si, t0, state0, g, flags=_lib.GF_EXACT_FP32)
     whole = whole_grid_rows(mi, radii, si.H, si.W, si.D)
     assert not whole.any()
     for a, c, what in zip(got, exact, ("means", "opacity", "semantics", "cov")):

@@ -1,13 +1,12 @@
 """The wave-autonomous matrix-core render kernel's group operand phase (S' rows split between the half-lanes, the box rows as
 packed 16-bit compares, the S' residuals by v_fma_mix) against the tile kernel, which forms the same operands its own way: equal
 bits on the shapes where the one-hot rows meet ragged edges, partial groups and long rows."""
-import numpy as np
 import pytest
-import torch
 
+from gaussianformer_amd import _lib
 from gaussianformer_amd.synthetic import make_splat_inputs
 
-from util import hip_splat_forward, prep
+from splat_cases import run_route, tensors, wave_equals_tile
 
 pytestmark = pytest.mark.gpu
 
@@ -19,13 +18,6 @@ pytestmark = pytest.mark.gpu
     ("nuscenes_gs144000", dict(P=40000, H=64, W=40, D=8)),            # long rows
 ])
 def test_wave_and_tile_kernels_agree_on_the_operand_phase(gpu, config, kw):
-    from gaussianformer_amd import _lib
     si = make_splat_inputs(config, seed=7, **kw)
-    pi, mi, radii, cov6 = prep(si)
-    wave, _, wstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
-    with _lib.option("splat.mfma_tile_kernel", 1):
-        tile, _, tstate, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_MFMA_SPLAT)
-    assert _lib.SplatState.of(wstate).path == _lib.GF_PATH_MATRIX_CORE_WAVE
-    assert _lib.SplatState.of(tstate).path == _lib.GF_PATH_MATRIX_CORE
-    assert np.isfinite(wave["logits"]).all()
-    assert np.array_equal(wave["logits"], tile["logits"])
+    t = tensors(gpu, si)
+    wave_equals_tile(run_route(t, si, _lib.GF_MFMA_SPLAT), run_route(t, si, _lib.GF_MFMA_SPLAT, tile=True))

@@ -13,12 +13,9 @@ from gaussianformer_amd._lib import (GF_COMP_EXP, GF_EXACT_FP32, GF_FAST_EXP, GF
                                      GF_LABELS_PROB_THRESHOLD, GF_LIBM_EXP, GF_MFMA_SPLAT, GF_PREPARE_BACKWARD, GF_PTS_ASSUME_DENSE,
                                      GF_PTS_GENERAL, GF_SPLAT_BASE, GF_SPLAT_PROB, GF_WORKSPACE_ZEROED)
 
-WORDS = ("kernel", "labels", "prep_backward", "exp", "prep_waves", "prep_blocks", "prep_grid", "verify", "lattice", "prescale",
-         "range_theta_here", "range_flags", "one_verdict", "summaries", "row_layout", "tile_counter_init", "bwd_counter_init",
-         "render_grid")
-EXACT_TILE, ARBITRARY, MFMA_TILE, WAVE, WAVE_LONG = range(5)   # word 0
+from splat_cases import ARBITRARY, EXACT_TILE, MFMA_TILE, NO_LABELS, WAVE, WAVE_LONG, splat_route, tensors, units
+
 EXP_LIBM, EXP_COMP, EXP_FAST = range(3)                          # word 3
-NO_LABELS = -1
 CUS = 256
 GRIDS = [(8, 8, 8), (48, 40, 16), (200, 200, 16)]
 H, W, D = GRIDS[1]
@@ -26,25 +23,13 @@ V = H * W * D
 
 
 def route(variant=GF_SPLAT_BASE, flags=0, label_mode=NO_LABELS, P=25601, N=V, grid=(H, W, D)):
-    lib = _lib.load()
-    fn = lib.gf_debug_splat_route
-    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_int]
-    out = (ctypes.c_int * len(WORDS))()
-    rc = fn(variant, flags, label_mode, P, N, *grid, out, len(WORDS))
-    assert rc == len(WORDS), lib.gf_last_error()
-    return dict(zip(WORDS, out))
+    return splat_route(variant, flags, label_mode, P, N, grid)
 
 
 @pytest.fixture
 def tile_option():
     with _lib.option("splat.mfma_tile_kernel", 1):
         yield
-
-
-def units(grid):
-    """Double bricks (4 x 4 x 8 voxels) of a grid: four per 8 x 8 supertile and 8 voxels of depth."""
-    h, w, d = grid
-    return -(-h // 8) * -(-w // 8) * 4 * -(-d // 8)
 
 
 def xcd_grid(items, per_cu):
@@ -206,14 +191,12 @@ def test_the_route_is_the_body_the_state_block_reports(gpu):
 
     from gaussianformer_amd.local_aggregate import splat_forward
     from gaussianformer_amd.synthetic import make_splat_inputs
-    from util import prep, to_dev
     path_of = {EXACT_TILE: _lib.GF_PATH_EXACT_TILE, ARBITRARY: _lib.GF_PATH_ARBITRARY, MFMA_TILE: _lib.GF_PATH_MATRIX_CORE,
                WAVE: _lib.GF_PATH_MATRIX_CORE_WAVE, WAVE_LONG: _lib.GF_PATH_MATRIX_CORE_WAVE}
     g = 16
     si = make_splat_inputs("nuscenes_gs25600_solid", seed=11, P=200, H=g, W=g, D=g)
-    pi, mi, radii, cov6 = prep(si)
     P = si.means3D.shape[0]
-    t = to_dev(gpu, si.pts, pi, si.means3D, mi, si.opacities, si.semantics, radii, cov6)
+    t = tensors(gpu, si)
 
     def both(flags=0, drop=0):
         n = g ** 3 - drop

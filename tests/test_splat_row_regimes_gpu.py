@@ -22,10 +22,8 @@ import torch
 import oracle
 from gaussianformer_amd.synthetic import make_splat_inputs
 
-from util import assert_grad_rows_close, assert_logits_close, hip_splat_backward, hip_splat_forward, prep, whole_grid_rows
-
-# gaussianformer_amd/csrc: gf_common.hpp (kSuper, kLongWords), splat_fwd.hip (kRowLayoutBlocks, kLSumAt)
-K_SUPER, K_LONG_WORDS, K_ROW_LAYOUT_BLOCKS, K_LSUM_AT = 8, 4096, 64, 3968
+from splat_cases import K, bwd, integer_boxes
+from util import assert_grad_rows_close, assert_logits_close, hip_splat_forward, prep, whole_grid_rows
 
 CONFIG = "nuscenes_gs144000"
 H, W, D = 48, 40, 16   # 30 supertiles x 8 units: a wave grid of 240 workgroups, so workgroups 0..63 exist and the layout is taken
@@ -50,11 +48,11 @@ def first_units(H, W, D):
     starts at unit b >> 3 of the XCD b & 7, i.e. unit r of supertile 8 q + (b & 7) with (q, r) = divmod(b >> 3, units per supertile)
     -- the mapping of gf_splat_render_mfma_wave_kernel's first-unit prefetch.  Returns per workgroup ((x0, x1), (y0, y1), (z0, z1))
     voxel ranges, or None where the workgroup has no first unit (no prefetched summary)."""
-    nsx, nsy = -(-H // K_SUPER), -(-W // K_SUPER)
+    nsx, nsy = -(-H // K.kSuper), -(-W // K.kSuper)
     per_super = 4 * ((D + 7) >> 3)
     per_xcd = ((nsx * nsy + 7) >> 3) * per_super
     out = []
-    for b in range(K_ROW_LAYOUT_BLOCKS):
+    for b in range(K.kRowLayoutBlocks):
         local, xcd = b >> 3, b & 7
         q, r = divmod(local, per_super)
         s = 8 * q + xcd
@@ -62,7 +60,7 @@ def first_units(H, W, D):
             out.append(None)
             continue
         srow, scol = divmod(s, nsy)
-        x0, y0, z0 = srow * K_SUPER + 4 * (r & 1), scol * K_SUPER + 4 * ((r >> 1) & 1), 8 * (r >> 2)
+        x0, y0, z0 = srow * K.kSuper + 4 * (r & 1), scol * K.kSuper + 4 * ((r >> 1) & 1), 8 * (r >> 2)
         out.append(((x0, min(x0 + 4, H)), (y0, min(y0 + 4, W)), (z0, min(z0 + 8, D))) if x0 < H and y0 < W else None)
     return out
 
@@ -70,7 +68,7 @@ def first_units(H, W, D):
 def reached_dwords(nwords):
     """Summary dwords that finish_row_layout_long's prefix covers at this row length (at 3968 words: the one the next word would
     reach).  Dword i covers row words 16 i .. 16 i + 15, i.e. Gaussians 1024 i .. 1024 i + 1023."""
-    return range(max(1, min(nwords, K_LONG_WORDS) - K_LSUM_AT))
+    return range(max(1, min(nwords, K.kLongWords) - K.kLSumAt))
 
 
 _inputs_cache, _oracle_cache = {}, {}
@@ -84,7 +82,7 @@ def case_inputs(P):
     if P not in _inputs_cache:
         si = make_splat_inputs(CONFIG, seed=4, P=P, H=H, W=W, D=D)
         nwords = _nwords(si)
-        if nwords >= K_LSUM_AT:
+        if nwords >= K.kLSumAt:
             rng = np.random.default_rng(8)
             units = first_units(H, W, D)
             assert all(u is not None for u in units)
@@ -107,19 +105,7 @@ def case_oracle(P):
     return _oracle_cache[P]
 
 
-def integer_boxes(mi, radii, H, W, D):
-    """[lo, hi) voxel box of every Gaussian (src/auxiliary.h getRect: mean +- radius, clipped to the grid), checked against the
-    oracle's binning: the box volumes are its tiles_touched."""
-    dims = np.array([H, W, D], dtype=np.int64)
-    mi, r = np.asarray(mi, np.int64), np.asarray(radii, np.int64)[:, None]
-    lo = np.minimum(dims, np.maximum(0, mi - r))
-    hi = np.minimum(dims, np.maximum(0, mi + r + 1))
-    touched, _, _ = oracle.box_offsets(mi, radii, H, W, D)
-    assert np.array_equal(np.prod(hi - lo, axis=1).astype(np.uint32), touched)
-    return lo, hi
-
-
-@pytest.mark.parametrize("name,P,nwords", [c for c in CASES if c[2] >= K_LSUM_AT], ids=lambda v: str(v))
+@pytest.mark.parametrize("name,P,nwords", [c for c in CASES if c[2] >= K.kLSumAt], ids=lambda v: str(v))
 def test_clobber_cases_reach_the_first_units(name, P, nwords):
     """CPU: the inputs of the long-row cases from 3968 words on are sensitive to a summary row that the row-layout prefix
     overwrites.  Every workgroup 0..63 has a first unit, and it has candidates (integer box meets the unit's voxels) in all sixteen
@@ -127,8 +113,8 @@ def test_clobber_cases_reach_the_first_units(name, P, nwords):
     si, pi, mi, radii, cov6 = case_inputs(P)
     assert _nwords(si) == nwords
     lo, hi = integer_boxes(mi, radii, si.H, si.W, si.D)
-    nsuper = -(-si.H // K_SUPER) * -(-si.W // K_SUPER)
-    assert nsuper * 4 * ((si.D + 7) >> 3) >= K_ROW_LAYOUT_BLOCKS   # units: a wave grid of >= 64 workgroups (layout_ok)
+    nsuper = -(-si.H // K.kSuper) * -(-si.W // K.kSuper)
+    assert nsuper * 4 * ((si.D + 7) >> 3) >= K.kRowLayoutBlocks   # units: a wave grid of >= 64 workgroups (layout_ok)
     for b, u in enumerate(first_units(si.H, si.W, si.D)):
         assert u is not None, b
         meets = np.ones(lo.shape[0], bool)
@@ -139,10 +125,6 @@ def test_clobber_cases_reach_the_first_units(name, P, nwords):
         assert np.array_equal(words0, np.arange(16)), (b, u, words0)
         for i in reached_dwords(nwords):
             assert ((cand >= 1024 * i) & (cand < 1024 * (i + 1))).any(), (b, u, i)
-
-
-def _bwd(gpu, si, t, state, g, flags=0):
-    return hip_splat_backward(gpu, si, t, state, None, g, flags=flags)
 
 
 def _words(state):
@@ -162,7 +144,7 @@ def test_prepared_forward_and_backward_at_row_regime(gpu, name, P, nwords):
     from gaussianformer_amd.local_aggregate import _LocalAggregate
     si, pi, mi, radii, cov6 = case_inputs(P)
     assert _nwords(si) == nwords
-    on_wave = nwords <= K_LONG_WORDS
+    on_wave = nwords <= K.kLongWords
     g = np.random.default_rng(1).standard_normal((si.pts.shape[0], 18)).astype(np.float32)
 
     prepared, t, state, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
@@ -171,7 +153,7 @@ def test_prepared_forward_and_backward_at_row_regime(gpu, name, P, nwords):
     if on_wave:
         assert words.path == _lib.GF_PATH_MATRIX_CORE_WAVE and words.rows_ready and not words.rows_overflow, words
         # (right after its forward: the workspace still holds the records and the layout)
-        got = _bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
+        got = bwd(gpu, si, t, state, g, flags=_lib.GF_MFMA_SPLAT | _lib.GF_RECORDS_VALID)
     else:
         assert words.path == _lib.GF_PATH_MATRIX_CORE and not words.rows_ready and not words.rows_overflow, words
 
@@ -180,8 +162,8 @@ def test_prepared_forward_and_backward_at_row_regime(gpu, name, P, nwords):
     assert not words0.not_dense and words0.path == (_lib.GF_PATH_MATRIX_CORE_WAVE if on_wave else _lib.GF_PATH_MATRIX_CORE), words0
     assert not words0.rows_ready and not words0.rows_overflow, words0
     if on_wave:
-        unprepared = _bwd(gpu, si, t0, state0, g, flags=_lib.GF_MFMA_SPLAT)
-        exact = _bwd(gpu, si, t0, state0, g, flags=_lib.GF_EXACT_FP32)
+        unprepared = bwd(gpu, si, t0, state0, g, flags=_lib.GF_MFMA_SPLAT)
+        exact = bwd(gpu, si, t0, state0, g, flags=_lib.GF_EXACT_FP32)
 
     with _lib.option("splat.mfma_tile_kernel", 1):
         tile_p, _, tstate_p, _ = hip_splat_forward(gpu, si, pi, mi, radii, cov6, flags=_lib.GF_PREPARE_BACKWARD)
@@ -230,7 +212,7 @@ def test_module_training_step_at_the_longest_rows(gpu):
     from gaussianformer_amd import _lib
     from gaussianformer_amd.local_aggregate import LocalAggregator
     si, _, mi, radii, _ = case_inputs(262000)
-    assert K_LSUM_AT < _nwords(si) <= K_LONG_WORDS
+    assert K.kLSumAt < _nwords(si) <= K.kLongWords
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(gpu)[None]
     mk = lambda mc: LocalAggregator(si.scale_multiplier, si.H, si.W, si.D, list(si.pc_min), si.grid_size, matrix_cores=mc).to(gpu)
     g = torch.from_numpy(np.random.default_rng(3).standard_normal((si.pts.shape[0], 18)).astype(np.float32)).to(gpu)
