@@ -137,16 +137,17 @@ def check_lift(r, scans, srcs, pixel_gt=None, atol=1e-4, bound=1e-4, what=""):
     return exempted, compared
 
 
-def pixel_loss(logits, gt, use_sigmoid):
-    """``(loss, grad)``: torch's binary_cross_entropy of ``p = softmax / sigmoid(logits)`` (fp32 p, as the reference) with
-    the log clamped at -100, mean over all entries, and its gradient in the logits (BCE backward floor 1e-12 on
-    ``p (1 - p)``), evaluated in float64 from the fp32 ``p``."""
+def pixel_probs(logits, use_sigmoid):
+    """The correctly rounded fp32 ``p = softmax / sigmoid(logits)`` (float64 evaluation, rounded once)."""
     x = np.asarray(logits, np.float32).astype(np.float64)
+    with np.errstate(over="ignore"):
+        p = 1.0 / (1.0 + np.exp(-x)) if use_sigmoid else softmax64(x)
+    return p.astype(np.float32)
+
+
+def _pixel_loss(logits, gt, use_sigmoid, p=None):
     t = np.asarray(gt).astype(np.float64)
-    if use_sigmoid:
-        p = (1.0 / (1.0 + np.exp(-x))).astype(np.float32).astype(np.float64)
-    else:
-        p = softmax64(x).astype(np.float32).astype(np.float64)
+    p = (pixel_probs(logits, use_sigmoid) if p is None else np.asarray(p, np.float32)).astype(np.float64)
     with np.errstate(divide="ignore"):
         lp = np.maximum(np.log(p), -100.0)
         l1p = np.maximum(np.log1p(-p), -100.0)
@@ -154,6 +155,23 @@ def pixel_loss(logits, gt, use_sigmoid):
     gp = (p - t) / np.maximum((1 - p) * p, float(np.float32(1e-12))) / t.size
     if use_sigmoid:
         g = gp * (1 - p) * p
+        y = np.abs(g)
     else:
         g = p * (gp - (gp * p).sum(-1, keepdims=True))
-    return loss, g
+        y = p * (np.abs(gp) + (np.abs(gp) * p).sum(-1, keepdims=True))
+    return loss, g, y
+
+
+def pixel_loss(logits, gt, use_sigmoid):
+    """``(loss, grad)``: torch's binary_cross_entropy of ``p = softmax / sigmoid(logits)`` (fp32 p, as the reference) with
+    the log clamped at -100, mean over all entries, and its gradient in the logits (BCE backward floor 1e-12 on
+    ``p (1 - p)``), evaluated in float64 from the fp32 ``p``."""
+    return _pixel_loss(logits, gt, use_sigmoid)[:2]
+
+
+def pixel_loss_terms(logits, gt, use_sigmoid, p=None):
+    """``(loss, grad, y)`` of ``pixel_loss`` with ``y`` the size of the terms each gradient element is formed from, the
+    yardstick of its fp32 error: sigmoid ``y = |g|``; softmax ``y_i = p_i (|gp_i| + sum_j |gp_j| p_j)`` with ``gp`` the BCE
+    backward before the softmax Jacobian (at few bins ``g_i = p_i (gp_i - sum_j gp_j p_j)`` is a difference of terms far
+    larger than itself).  ``p``: an fp32 array to evaluate at in place of the correctly rounded one (the tests' ulp probe)."""
+    return _pixel_loss(logits, gt, use_sigmoid, p)
