@@ -5,7 +5,7 @@ behind a C-ABI shared library (``include/gf_hip.h``); this package is the Python
 that mirrors the reference's operator API."""
 __version__ = "0.1.0"
 
-__all__ = ["GaussianOccEncoder"]
+__all__ = ["GaussianOccEncoder", "GaussianHead"]
 
 
 def __getattr__(name):
@@ -13,4 +13,7 @@ def __getattr__(name):
     if name == "GaussianOccEncoder":
         from .encoder import GaussianOccEncoder
         return GaussianOccEncoder
+    if name == "GaussianHead":
+        from .head import GaussianHead
+        return GaussianHead
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

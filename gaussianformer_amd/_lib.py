@@ -81,6 +81,8 @@ SIGNATURES = {
     "gf_subm_conv_weight_grad": (_i, [_i] * 8 + [ctypes.c_longlong] + [_vp] * 6 + [_vp]),
     "gf_feature_maps_format": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "gf_head_labels": (_i, [ctypes.c_longlong, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
+    "gf_head_geosem_forward": (_i, [_ll, _i] + [_vp] * 4 + [_vp]),
+    "gf_head_geosem_backward": (_i, [_ll, _i] + [_vp] * 5 + [_vp]),
     "gf_daf_fused_forward": (_i, [_i] * 8 + [_vp] * 11),
     "gf_daf_fused_forward_masked": (_i, [_i] * 8 + [_vp] * 12),
     "gf_daf_fused_backward_workspace_bytes": (_sz, [_i] * 6),

@@ -173,31 +173,45 @@ class GaussianArgs(nn.Module):
     def forward(self, means, scales, rotations, semantics, opacities=None):
         """Tensors are ``[b,g,3] [b,g,3] [b,g,4] [b,g,c] [b,g,1]|empty`` (the fields of the
         reference's ``gaussians`` namedtuple, gaussian_head.py:83-87)."""
-        sem = semantics
-        origi_opa = opacities
-        kitti = 'kitti' in self.dataset_type
-        if means.is_cuda and means.shape[0] == 1 and (self.with_emtpy or self.use_localaggprob):
-            # one launch (gf_gaussian_pack) instead of the reference's zeros_like + six torch.cat (or softmax + cat)
-            assert sem.shape[-1] == self.num_classes - 1
-            opa_in = None if (origi_opa is None or origi_opa.numel() == 0) else origi_opa
-            empty_host = None
-            if self.with_emtpy:
-                # the buffers are constants of the head: read once -- and again when one of them has been assigned or written in
-                # place since (load_state_dict, .copy_(), .to(): storage pointer / version counter), ADVICE r4
-                key = tuple((t.data_ptr(), t._version) for t in (self.empty_mean, self.empty_scale, self.empty_rot))
-                if self._empty_host is None or self._empty_host[0] != key:
-                    self._empty_host = (key, [self.empty_mean.flatten().tolist(), self.empty_scale.flatten().tolist(),
-                                              self.empty_rot.flatten().tolist()])
-                empty_host = self._empty_host[1]
-            means, scales, rotations, sem, origi_opa = _GaussianPack.apply(
-                means, scales, rotations, sem, opa_in, self.empty_scalar if self.with_emtpy else None, empty_host,
-                self.num_classes, kitti, self.with_emtpy, not self.with_emtpy, self.empty_label)
+        if self._packs(means):
+            means, scales, rotations, sem, origi_opa = self._pack(means, scales, rotations, semantics, opacities)
             return means, origi_opa, sem, scales, covariance_inverse(scales, rotations)
-        return self._forward_torch(means, scales, rotations, sem, origi_opa)
+        return self._forward_torch(means, scales, rotations, semantics, opacities)
+
+    def _packs(self, means):
+        """Whether ``_pack`` applies: GPU tensors at batch size 1 of a head that appends the empty Gaussian or is a prob head."""
+        return means.is_cuda and means.shape[0] == 1 and (self.with_emtpy or self.use_localaggprob)
+
+    def _pack(self, means, scales, rotations, sem, origi_opa):
+        """``(means, scales, rotations, sem, origi_opa)`` as the aggregator takes them, in one launch (gf_gaussian_pack) instead
+        of the reference's zeros_like + six torch.cat (or softmax + cat)."""
+        kitti = 'kitti' in self.dataset_type
+        assert sem.shape[-1] == self.num_classes - 1
+        opa_in = None if (origi_opa is None or origi_opa.numel() == 0) else origi_opa
+        empty_host = None
+        if self.with_emtpy:
+            # the buffers are constants of the head: read once -- and again when one of them has been assigned or written in
+            # place since (load_state_dict, .copy_(), .to(): storage pointer / version counter), ADVICE r4
+            key = tuple((t.data_ptr(), t._version) for t in (self.empty_mean, self.empty_scale, self.empty_rot))
+            if self._empty_host is None or self._empty_host[0] != key:
+                self._empty_host = (key, [self.empty_mean.flatten().tolist(), self.empty_scale.flatten().tolist(),
+                                          self.empty_rot.flatten().tolist()])
+            empty_host = self._empty_host[1]
+        return _GaussianPack.apply(
+            means, scales, rotations, sem, opa_in, self.empty_scalar if self.with_emtpy else None, empty_host,
+            self.num_classes, kitti, self.with_emtpy, not self.with_emtpy, self.empty_label)
 
     def _forward_torch(self, means, scales, rotations, sem, origi_opa):
         """The reference's op sequence (gaussian_head.py:88-119 with the device-side Sigma^-1): batch sizes above 1, CPU
         tensors of the configuration tests, and the checker of the fused path (tests/test_prepare.py)."""
+        means, scales, rotations, sem, origi_opa = self._fields_torch(means, scales, rotations, sem, origi_opa)
+        cov_inv = self._covariance_inverse(scales, rotations)  # b, g, 3, 3
+        return means, origi_opa, sem, scales, cov_inv
+
+    _covariance_inverse = staticmethod(covariance_inverse)   # (a subclass that takes CPU tensors supplies its own)
+
+    def _fields_torch(self, means, scales, rotations, sem, origi_opa):
+        """gaussian_head.py:88-109 op by op: ``(means, scales, rotations, sem, origi_opa)`` as the aggregator takes them."""
         kitti = 'kitti' in self.dataset_type
         if origi_opa is None or origi_opa.numel() == 0:
             origi_opa = torch.ones_like(sem[..., :1], requires_grad=False)
@@ -218,5 +232,4 @@ class GaussianArgs(nn.Module):
             sem = sem.softmax(dim=-1)
             zero = torch.zeros_like(sem[..., :1])
             sem = torch.cat([zero, sem] if kitti else [sem, zero], dim=-1)
-        cov_inv = covariance_inverse(scales, rotations)  # b, g, 3, 3
-        return means, origi_opa, sem, scales, cov_inv
+        return means, scales, rotations, sem, origi_opa

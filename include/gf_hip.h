@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward, gf_ffn_*, gf_refine_mlp_*, gf_deform_logits_forward / gf_deform_output_forward, gf_miou_workspace_size / gf_miou_step / gf_miou_step_logits, gf_subm_conv_apply_epilogue (added without a bump: a library without them fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward, gf_ffn_*, gf_refine_mlp_*, gf_deform_logits_forward / gf_deform_output_forward, gf_miou_workspace_size / gf_miou_step / gf_miou_step_logits, gf_subm_conv_apply_epilogue, gf_head_geosem_forward / gf_head_geosem_backward (added without a bump: a library without them fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -473,6 +473,25 @@ int gf_subm_conv_weight_grad(int N, int batch, int X, int Y, int Z, int K, int C
  */
 int gf_head_labels(long long N, int C, int mode, const float *logits, const float *bin_logits,
                    float threshold, int empty_label, long long *labels, void *stream);
+
+/*
+ * The prob head's geosem step (model/head/gaussian_head.py:166-168), one launch each way instead of three torch launches
+ * with two [N,17] / [N,18] intermediates (backward: autograd's zero-fill, two products and a strided sum):
+ *   forward    out[n,c] = logits[n,c] * bin_logits[n] (c < 17),  out[n,17] = 1 - bin_logits[n]
+ *              labels (may be NULL): the head's final_occ of the row, by gf_head_labels' GF_LABELS_PROB_GEOSEM rule -- the same
+ *              labels bit for bit, from the same launch
+ *   backward   grad_logits[n,c] = grad_out[n,c] * bin_logits[n] (c < 17),  grad_logits[n,17] = +0.0
+ *              grad_bin[n] = sum_{c<17} grad_out[n,c] * logits[n,c] - grad_out[n,17]
+ *   logits, out, grad_out, grad_logits f32 [N,18]   bin_logits, grad_bin f32 [N]   labels i64 [N]
+ * Every element of out and grad_logits is one correctly rounded fp32 operation (equal to the torch expression bit for bit);
+ * grad_bin is summed in fp32 in ascending c by one lane per row, no atomics: it repeats bit for bit.  Non-finite inputs
+ * propagate by IEEE rules.  C must be 18.  Any 4-byte aligned base pointer is taken (16-byte accesses where a base allows);
+ * inputs and outputs must not alias.  N == 0 returns GF_OK.  No host read, no allocation.
+ */
+int gf_head_geosem_forward(long long N, int C, const float *logits, const float *bin_logits,
+                           float *out, long long *labels /* may be NULL */, void *stream);
+int gf_head_geosem_backward(long long N, int C, const float *logits, const float *bin_logits,
+                            const float *grad_out, float *grad_logits, float *grad_bin, void *stream);
 
 /*
  * gf_splat_forward with the head epilogue folded into the render kernel: the labels are taken from
