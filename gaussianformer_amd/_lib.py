@@ -78,6 +78,10 @@ SIGNATURES = {
     "gf_subm_apply_scratch_bytes": (_sz, [_i, _i]),
     "gf_subm_conv_apply_scratch": (_i, [_i] * 8 + [ctypes.c_longlong] + [_vp] * 6 + [_vp, _sz, _vp]),
     "gf_subm_conv_apply_epilogue": (_i, [_i] * 8 + [ctypes.c_longlong] + [_vp] * 6 + [_vp, _sz] + [_vp] * 4 + [_i, _vp]),
+    "gf_subm_stage_train_sizes": (_i, [_i] * 2 + [_vp] * 2),
+    "gf_subm_conv_apply_epilogue_train": (_i, [_i] * 8 + [ctypes.c_longlong] + [_vp] * 6 + [_vp, _sz] + [_vp] * 4 + [_i, _vp, _vp]),
+    "gf_subm_stage_backward": (_i, [_i] * 2 + [_vp] * 4 + [_i] + [_vp] * 5 + [_sz, _vp]),
+    "gf_subm_conv_apply_stage_backward": (_i, [_i] * 8 + [ctypes.c_longlong] + [_vp] * 5 + [_vp, _sz] + [_vp] * 3 + [_i] + [_vp] * 5 + [_sz, _vp]),
     "gf_subm_conv_weight_grad": (_i, [_i] * 8 + [ctypes.c_longlong] + [_vp] * 6 + [_vp]),
     "gf_feature_maps_format": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "gf_head_labels": (_i, [ctypes.c_longlong, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),

@@ -21,6 +21,7 @@
 // The gradient w.r.t. the features is the same operator with W'[k] = W[K^3-1-k]^T (the neighbour
 // relation is symmetric), the gradient w.r.t. W[k] is feat[pair_in]^T . grad_out[pair_out] per segment.
 #include "gf_common.hpp"
+#include "gf_rows_bwd.hpp"   // rows_sum_kernel: the stage backward's partial triples
 
 namespace gf {
 
@@ -770,11 +771,102 @@ struct SubmEpilogue {
     int relu;
 };
 
+// ---- the training step of a stage y = relu?(LN((c + bias) + residual)) ----------------------------------------
+// What the reduce kernel's two training instantiations and the standalone stage backward read beyond SubmEpilogue.
+enum { kStageNone = 0, kStageSave = 1, kStageBackward = 2 };
+struct SubmStage {
+    float *pre_out;          // kStageSave: [N, Cout], the row as the LayerNorm reads it
+    const float *pre;        // the backward: those rows
+    const float *ln_weight;  // [Cout]
+    const float *ln_bias;
+    float *grad_pre;         // [N, Cout]
+    float *part;             // [workgroups][3][Cout]: a workgroup's sums of the column terms g_u, g_u xhat, g_pre over its rows
+    int relu, N;
+};
+struct SubmStageCols { float4 gu, gux, gpre; };   // a lane's column terms: -> dbeta, dgamma, the convolution's dbias
+
+// The backward of one row in the registers of its COUT/4 lanes: gy = dL/dy, p = the saved pre-norm row, g / b = the lane's four
+// LayerNorm weights and biases.  Mean and rstd are recomputed from p by the forward epilogue's own expressions (the same bits),
+// u = xhat gamma + beta likewise; u == 0 passes nothing (the forward's u < 0 ? 0 : u, torch's result > 0).  A row with a NaN or
+// an infinity (an over-capacity rulebook) has rstd = NaN and gives NaN in all three terms, with or without the ReLU.  Returns
+// g_pre = rstd (g_xhat - mean(g_xhat) - xhat mean(g_xhat xhat)).  Every lane of the wave calls it (group_sum)
+template <int COUT>
+__device__ __forceinline__ float4 subm_stage_bwd_row(float4 gy, float4 p, float4 g, float4 b, int relu, SubmStageCols &c)
+{
+    constexpr int CG = COUT / 4;
+    const float mean = group_sum((p.x + p.y) + (p.z + p.w), CG) * (1.f / COUT);
+    const float dx = p.x - mean, dy = p.y - mean, dz = p.z - mean, dw = p.w - mean;
+    const float var = group_sum((dx * dx + dy * dy) + (dz * dz + dw * dw), CG) * (1.f / COUT);
+    const float rstd = 1.f / sqrtf(var + 1e-5f);
+    const float ux = dx * rstd * g.x + b.x, uy = dy * rstd * g.y + b.y;
+    const float uz = dz * rstd * g.z + b.z, uw = dw * rstd * g.w + b.w;
+    const float hx = dx * rstd, hy = dy * rstd, hz = dz * rstd, hw = dw * rstd;
+    const bool bad = rstd != rstd;
+    const bool act = relu != 0;
+    float4 gu;
+    gu.x = bad ? rstd : act && !(ux > 0.f) ? 0.f : gy.x;
+    gu.y = bad ? rstd : act && !(uy > 0.f) ? 0.f : gy.y;
+    gu.z = bad ? rstd : act && !(uz > 0.f) ? 0.f : gy.z;
+    gu.w = bad ? rstd : act && !(uw > 0.f) ? 0.f : gy.w;
+    const float gx = gu.x * g.x, gyy = gu.y * g.y, gz = gu.z * g.z, gw = gu.w * g.w;   // g_xhat
+    const float m1 = group_sum((gx + gyy) + (gz + gw), CG) * (1.f / COUT);
+    const float m2 = group_sum((gx * hx + gyy * hy) + (gz * hz + gw * hw), CG) * (1.f / COUT);
+    float4 gp;
+    gp.x = rstd * (gx - m1 - hx * m2); gp.y = rstd * (gyy - m1 - hy * m2);
+    gp.z = rstd * (gz - m1 - hz * m2); gp.w = rstd * (gw - m1 - hw * m2);
+    c.gu = gu;
+    c.gux = make_float4(gu.x * hx, gu.y * hy, gu.z * hz, gu.w * hw);
+    c.gpre = gp;
+    return gp;
+}
+
+// What both callers do with a row's gy (row i of the workgroup's 256 / (COUT/4) rows, one float4 per lane): the row backward,
+// g_pre stored, the three column terms summed over the workgroup's rows -- within a wave over the lanes that share a column
+// (xor COUT/4 .. 32 ascending), then the four waves in their order through LDS -- and written as the workgroup's partial triple.
+// The same row -> workgroup mapping in both callers, so the same bits.  Every thread of the workgroup calls it (one barrier);
+// a row >= N computes on zeros, stores nothing and adds zeros
+template <int COUT>
+__device__ __forceinline__ void subm_stage_bwd_tail(float4 gy, int i, const SubmStage &s)
+{
+    constexpr int CG = COUT / 4;
+    const int tc = threadIdx.x % CG, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool valid = i < s.N;
+    float4 p = reinterpret_cast<const float4 *>(s.pre + (size_t)(valid ? i : 0) * COUT)[tc];
+    if (!valid) p = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 g = reinterpret_cast<const float4 *>(s.ln_weight)[tc], b = reinterpret_cast<const float4 *>(s.ln_bias)[tc];
+    SubmStageCols c;
+    const float4 gp = subm_stage_bwd_row<COUT>(gy, p, g, b, s.relu, c);
+    if (valid) reinterpret_cast<float4 *>(s.grad_pre + (size_t)i * COUT)[tc] = gp;
+    float v[12] = {c.gu.x, c.gu.y, c.gu.z, c.gu.w, c.gux.x, c.gux.y, c.gux.z, c.gux.w, c.gpre.x, c.gpre.y, c.gpre.z, c.gpre.w};
+    __shared__ float s_col[4][3 * COUT];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        v[k] = wave_xor_reduce_strided(valid ? v[k] : 0.f, CG, Sum());
+        if (lane < CG) s_col[wave][(k >> 2) * COUT + 4 * tc + (k & 3)] = v[k];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 3 * COUT; e += 256)
+        s.part[(size_t)blockIdx.x * (3 * COUT) + e] = ((s_col[0][e] + s_col[1][e]) + s_col[2][e]) + s_col[3][e];
+}
+
+// the standalone stage backward: gy from memory, the reduce kernel's workgroup shape
+template <int COUT>
+__global__ __launch_bounds__(256) void gf_subm_stage_bwd_kernel(SubmStage s, const float *grad_out)
+{
+    constexpr int CG = COUT / 4;
+    const int i = blockIdx.x * (256 / CG) + threadIdx.x / CG;
+    float4 gy = reinterpret_cast<const float4 *>(grad_out + (size_t)(i < s.N ? i : 0) * COUT)[threadIdx.x % CG];
+    if (i >= s.N) gy = make_float4(0.f, 0.f, 0.f, 0.f);
+    subm_stage_bwd_tail<COUT>(gy, i, s);
+}
+
 // out[i] = sum over k ascending of the partial rows of (i, k): COUT/4 lanes per point.  EPI: the row then passes through `e`
 // in the registers it was summed in (one float4 per lane, the LayerNorm's two sums by gf::group_sum over the row's lanes);
-// without EPI `e` is not read and the kernel is the instruction stream it was before the epilogue existed
-template <int COUT, bool EPI>
-__global__ __launch_bounds__(256) void gf_subm_reduce_kernel(SubmArgs a, SubmEpilogue e)
+// without EPI `e` is not read and the kernel is the instruction stream it was before the epilogue existed.  TRAIN (only then is
+// `st` read): kStageSave, with EPI, also stores the row as the LayerNorm reads it; kStageBackward, without EPI, takes the finished
+// row (of a data-gradient convolution) as dL/dy of the stage whose rows st.pre are and stores only g_pre
+template <int COUT, bool EPI, int TRAIN = kStageNone>
+__global__ __launch_bounds__(256) void gf_subm_reduce_kernel(SubmArgs a, SubmEpilogue e, SubmStage st)
 {
     constexpr int CG = COUT / 4;
     constexpr int ROWS = 256 / CG;
@@ -836,6 +928,9 @@ __global__ __launch_bounds__(256) void gf_subm_reduce_kernel(SubmArgs a, SubmEpi
             const float4 r = reinterpret_cast<const float4 *>(e.residual + (size_t)(i < a.N ? i : 0) * COUT)[tc];
             acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
         }
+        if constexpr (TRAIN == kStageSave) {
+            if (i < a.N) reinterpret_cast<float4 *>(st.pre_out + (size_t)i * COUT)[tc] = acc;
+        }
         if (e.ln_weight) {
             // gf_ffn_forward's rule: the mean first, then the squared deviations (biased variance), eps = 1e-5
             const float mean = group_sum((acc.x + acc.y) + (acc.z + acc.w), CG) * (1.f / COUT);
@@ -851,7 +946,12 @@ __global__ __launch_bounds__(256) void gf_subm_reduce_kernel(SubmArgs a, SubmEpi
             acc.z = acc.z < 0.f ? 0.f : acc.z; acc.w = acc.w < 0.f ? 0.f : acc.w;
         }
     }
-    if (i < a.N) reinterpret_cast<float4 *>(a.out + (size_t)i * COUT)[tc] = acc;  // NaN for an over-capacity rulebook
+    if constexpr (TRAIN == kStageBackward) {
+        // (every lane arrives here, as above; a row >= N holds zeros, or NaN with everything else of an over-capacity rulebook)
+        subm_stage_bwd_tail<COUT>(acc, i, st);
+    } else {
+        if (i < a.N) reinterpret_cast<float4 *>(a.out + (size_t)i * COUT)[tc] = acc;  // NaN for an over-capacity rulebook
+    }
 }
 
 // staging helpers of the weight gradient: thread tid owns float4 (tid + 256 u) of the 32 x C block, u < Q
@@ -1242,7 +1342,7 @@ extern "C" size_t gf_subm_apply_scratch_bytes(int N, int Cin)
 static int subm_conv_apply_impl(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
                                 const float *features, const float *weight, const void *tables, const int *pair_in,
                                 float *partial, float *out, void *scratch, size_t scratch_bytes, void *stream_,
-                                const gf::SubmEpilogue *epi = nullptr)
+                                const gf::SubmEpilogue *epi = nullptr, const gf::SubmStage *stage = nullptr)
 {
     using namespace gf;
     hipStream_t stream = (hipStream_t)stream_;
@@ -1290,8 +1390,10 @@ static int subm_conv_apply_impl(int N, int batch, int X, int Y, int Z, int K, in
     const dim3 rgrid((N + rows - 1) / rows);
 #define GF_REDUCE(CO)                                                                                                      \
     do {                                                                                                                   \
-        if (epi) hipLaunchKernelGGL((gf_subm_reduce_kernel<CO, true>), rgrid, dim3(256), 0, stream, a, *epi);              \
-        else hipLaunchKernelGGL((gf_subm_reduce_kernel<CO, false>), rgrid, dim3(256), 0, stream, a, SubmEpilogue{});      \
+        if (epi && stage) hipLaunchKernelGGL((gf_subm_reduce_kernel<CO, true, kStageSave>), rgrid, dim3(256), 0, stream, a, *epi, *stage); \
+        else if (stage) hipLaunchKernelGGL((gf_subm_reduce_kernel<CO, false, kStageBackward>), rgrid, dim3(256), 0, stream, a, SubmEpilogue{}, *stage); \
+        else if (epi) hipLaunchKernelGGL((gf_subm_reduce_kernel<CO, true>), rgrid, dim3(256), 0, stream, a, *epi, SubmStage{}); \
+        else hipLaunchKernelGGL((gf_subm_reduce_kernel<CO, false>), rgrid, dim3(256), 0, stream, a, SubmEpilogue{}, SubmStage{}); \
     } while (0)
     if (Cout == 128) GF_REDUCE(128);
     else if (Cout == 64) GF_REDUCE(64);
@@ -1344,7 +1446,7 @@ extern "C" int gf_subm_conv_apply_epilogue(int N, int batch, int X, int Y, int Z
                                                                    {"ln_bias", ln_bias}, {"out", out}, {"partial", partial}};
     for (const auto &q : aligned)
         GF_REFUSE_AS(__func__, !gf::misaligned16(q.p), "%s = %p is not 16-byte aligned", q.name, q.p);
-    if (N > 0 && out && gf::subm_channels_ok(Cin, Cout) && K >= 1 && K <= 7 && total_pairs >= 0) {
+    if (N > 0 && out && gf::subm_channels_ok(Cin, Cout) && K >= 1 && K <= 7 && (K & 1) && total_pairs >= 0) {
         const size_t row = (size_t)Cout * sizeof(float), out_bytes = (size_t)N * row;
         const struct { const char *name; const void *p; size_t n; } inputs[] = {
             {"residual", residual, out_bytes}, {"features", features, (size_t)N * Cin * sizeof(float)},
@@ -1356,6 +1458,193 @@ extern "C" int gf_subm_conv_apply_epilogue(int N, int batch, int X, int Y, int Z
     }
     const gf::SubmEpilogue epi = {bias, residual, ln_weight, ln_bias, relu};
     return subm_conv_apply_impl(N, batch, X, Y, Z, K, Cin, Cout, total_pairs, features, weight, tables, pair_in, partial, out, scratch, scratch_bytes, stream_, &epi);
+}
+
+// ---- the stage's training step (spconv3d_module.py:26-37) ------------------------------------------------------
+// The two caller regions, sized and carved by one function each (a null base: sizes only).
+struct SubmStageWork { float *part; int blocks; size_t bytes; };
+static SubmStageWork subm_stage_carve(void *base, int N, int Cout)
+{
+    gf::Carver c(base);
+    SubmStageWork w;
+    const int rows = 256 / (Cout / 4);
+    w.blocks = N > 0 ? (N + rows - 1) / rows : 0;
+    w.part = c.take<float>((size_t)w.blocks * 3 * Cout);
+    w.bytes = c.bytes();
+    return w;
+}
+static size_t subm_stage_saved_bytes(int N, int Cout)
+{
+    gf::Carver c(nullptr);
+    c.take<float>((size_t)(N > 0 ? N : 0) * Cout);   // pre
+    return c.bytes();
+}
+
+extern "C" int gf_subm_stage_train_sizes(int N, int Cout, size_t *saved_bytes, size_t *workspace_bytes)
+{
+    const char *fn = __func__;
+    GF_REFUSE_AS(fn, Cout == 32 || Cout == 64 || Cout == 128, "unsupported channels: Cout = %d is not 32, 64 or 128", Cout);
+    GF_REFUSE_AS(fn, N >= 0, "N = %d is negative", N);
+    GF_REFUSE_AS(fn, saved_bytes && workspace_bytes, "null pointer");
+    *saved_bytes = subm_stage_saved_bytes(N, Cout);
+    *workspace_bytes = subm_stage_carve(nullptr, N, Cout).bytes;
+    return GF_OK;
+}
+
+// what the two backward entries refuse about the stage's own arguments, before any HIP call; `others`: the further regions
+// grad_pre must not share a byte with
+struct SubmRegion { const char *name; const void *p; size_t n; };
+static int subm_stage_check(const char *fn, int N, int Cout, const float *pre, const float *ln_weight, const float *ln_bias, int relu,
+                            const float *grad_pre, const float *grad_ln_weight, const float *grad_ln_bias, const float *grad_bias,
+                            const void *workspace, size_t workspace_bytes, const SubmRegion *others, int nothers)
+{
+    GF_REFUSE_AS(fn, Cout == 32 || Cout == 64 || Cout == 128, "unsupported channels: Cout = %d is not 32, 64 or 128", Cout);
+    GF_REFUSE_AS(fn, N >= 0, "N = %d is negative", N);
+    GF_REFUSE_AS(fn, ln_weight && ln_bias, "ln_weight = %p with ln_bias = %p: a training stage needs the LayerNorm pair",
+                 (const void *)ln_weight, (const void *)ln_bias);
+    GF_REFUSE_AS(fn, relu == 0 || relu == 1, "relu = %d is not 0 or 1", relu);
+    GF_REFUSE_AS(fn, grad_ln_weight && grad_ln_bias, "grad_ln_weight = %p with grad_ln_bias = %p: both are written",
+                 (const void *)grad_ln_weight, (const void *)grad_ln_bias);
+    const SubmRegion aligned[] = {{"pre", pre, 0}, {"ln_weight", ln_weight, 0}, {"ln_bias", ln_bias, 0}, {"grad_pre", grad_pre, 0},
+                                  {"grad_ln_weight", grad_ln_weight, 0}, {"grad_ln_bias", grad_ln_bias, 0}, {"grad_bias", grad_bias, 0},
+                                  {"workspace", workspace, 0}};
+    for (const auto &q : aligned) GF_REFUSE_AS(fn, !gf::misaligned16(q.p), "%s = %p is not 16-byte aligned", q.name, q.p);
+    if (N == 0) return GF_OK;
+    GF_REFUSE_AS(fn, pre && grad_pre, "null pointer (pre, grad_pre)");
+    GF_REFUSE_AS(fn, workspace, "workspace is null");
+    const size_t row = (size_t)Cout * sizeof(float), rows_bytes = (size_t)N * row;
+    const SubmRegion own[] = {{"pre", pre, rows_bytes}, {"ln_weight", ln_weight, row}, {"ln_bias", ln_bias, row},
+                              {"workspace", workspace, workspace_bytes}};
+    for (const auto &q : own)
+        GF_REFUSE_AS(fn, !subm_overlap(grad_pre, rows_bytes, q.p, q.n), "grad_pre = %p aliases %s = %p", (const void *)grad_pre, q.name, q.p);
+    for (int k = 0; k < nothers; ++k)
+        GF_REFUSE_AS(fn, !subm_overlap(grad_pre, rows_bytes, others[k].p, others[k].n), "grad_pre = %p aliases %s = %p",
+                     (const void *)grad_pre, others[k].name, others[k].p);
+    GF_CHECK_WORKSPACE_AS(fn, "workspace", workspace_bytes, subm_stage_carve(nullptr, N, Cout).bytes);
+    return GF_OK;
+}
+
+// the three sums of the partial triples, in double and a fixed order; N == 0: no partials, zeros
+static void subm_stage_sums(const SubmStageWork &w, int N, int Cout, float *grad_ln_weight, float *grad_ln_bias, float *grad_bias,
+                            hipStream_t stream)
+{
+    using namespace gf;
+    float *const dst[3] = {grad_ln_bias, grad_ln_weight, grad_bias};   // the order of the triple: g_u, g_u xhat, g_pre
+    RowsSumArgs<3> sa{};
+    for (int q = 0; q < 3; ++q)
+        sa.job[q] = RowsSumJob{N > 0 ? w.part + (size_t)q * Cout : nullptr, dst[q], (size_t)3 * Cout, w.blocks, dst[q] ? Cout : 0, 0, kRowsSumSlots};
+    constexpr int per = 256 / kRowsSumSlots;
+    hipLaunchKernelGGL((rows_sum_kernel<double, 3>), dim3((Cout + per - 1) / per, 3), dim3(256), 0, stream, sa);
+}
+
+static gf::SubmStage subm_stage_args(int N, const float *pre, const float *ln_weight, const float *ln_bias, int relu, float *grad_pre,
+                                     float *part)
+{
+    gf::SubmStage s{};
+    s.pre = pre; s.ln_weight = ln_weight; s.ln_bias = ln_bias; s.grad_pre = grad_pre; s.part = part; s.relu = relu; s.N = N;
+    return s;
+}
+
+extern "C" int gf_subm_conv_apply_epilogue_train(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
+                                                 const float *features, const float *weight, const void *tables, const int *pair_in,
+                                                 float *partial, float *out, void *scratch, size_t scratch_bytes, const float *bias,
+                                                 const float *residual, const float *ln_weight, const float *ln_bias, int relu,
+                                                 float *pre, void *stream_)
+{
+    const char *fn = __func__;
+    GF_REFUSE_AS(fn, ln_weight && ln_bias, "ln_weight = %p with ln_bias = %p: a training stage needs the LayerNorm pair",
+                 (const void *)ln_weight, (const void *)ln_bias);
+    GF_REFUSE_AS(fn, relu == 0 || relu == 1, "relu = %d is not 0 or 1", relu);
+    if (N > 0 && !scratch) {
+        gf::set_error("%s: null scratch (gf_subm_apply_scratch_bytes)", fn);
+        return GF_EINVAL;
+    }
+    const SubmRegion aligned[] = {{"bias", bias, 0}, {"residual", residual, 0}, {"ln_weight", ln_weight, 0}, {"ln_bias", ln_bias, 0},
+                                  {"out", out, 0}, {"partial", partial, 0}, {"pre", pre, 0}};
+    for (const auto &q : aligned) GF_REFUSE_AS(fn, !gf::misaligned16(q.p), "%s = %p is not 16-byte aligned", q.name, q.p);
+    GF_REFUSE_AS(fn, N <= 0 || pre, "pre is null");
+    if (N > 0 && out && gf::subm_channels_ok(Cin, Cout) && K >= 1 && K <= 7 && (K & 1) && total_pairs >= 0) {
+        const size_t row = (size_t)Cout * sizeof(float), out_bytes = (size_t)N * row;
+        const SubmRegion inputs[] = {
+            {"residual", residual, out_bytes}, {"features", features, (size_t)N * Cin * sizeof(float)},
+            {"weight", weight, (size_t)K * K * K * Cin * row}, {"bias", bias, row}, {"ln_weight", ln_weight, row},
+            {"ln_bias", ln_bias, row}, {"partial", partial, (size_t)total_pairs * row}, {"scratch", scratch, scratch_bytes},
+            {"pair_in", pair_in, (size_t)total_pairs * sizeof(int)}, {"tables", tables, 1}};
+        for (const auto &q : inputs) {
+            GF_REFUSE_AS(fn, !subm_overlap(out, out_bytes, q.p, q.n), "out = %p aliases %s = %p", (const void *)out, q.name, q.p);
+            GF_REFUSE_AS(fn, !subm_overlap(pre, out_bytes, q.p, q.n), "pre = %p aliases %s = %p", (const void *)pre, q.name, q.p);
+        }
+        GF_REFUSE_AS(fn, !subm_overlap(pre, out_bytes, out, out_bytes), "pre = %p aliases out = %p", (const void *)pre, (const void *)out);
+    }
+    const gf::SubmEpilogue epi = {bias, residual, ln_weight, ln_bias, relu};
+    gf::SubmStage st{};
+    st.pre_out = pre; st.N = N;
+    return subm_conv_apply_impl(N, batch, X, Y, Z, K, Cin, Cout, total_pairs, features, weight, tables, pair_in, partial, out, scratch, scratch_bytes, stream_, &epi, &st);
+}
+
+extern "C" int gf_subm_stage_backward(int N, int Cout, const float *pre, const float *grad_out, const float *ln_weight, const float *ln_bias,
+                                      int relu, float *grad_pre, float *grad_ln_weight, float *grad_ln_bias, float *grad_bias,
+                                      void *workspace, size_t workspace_bytes, void *stream_)
+{
+    using namespace gf;
+    const char *fn = __func__;
+    const SubmRegion others[] = {{"grad_out", grad_out, (size_t)(N > 0 ? N : 0) * (Cout > 0 ? Cout : 0) * sizeof(float)}};
+    GF_REFUSE_AS(fn, !misaligned16(grad_out), "grad_out = %p is not 16-byte aligned", (const void *)grad_out);
+    if (int rc = subm_stage_check(fn, N, Cout, pre, ln_weight, ln_bias, relu, grad_pre, grad_ln_weight, grad_ln_bias, grad_bias, workspace,
+                                  workspace_bytes, others, 1))
+        return rc;
+    GF_REFUSE_AS(fn, N == 0 || grad_out, "null pointer (grad_out)");
+    hipStream_t stream = (hipStream_t)stream_;
+    const SubmStageWork w = subm_stage_carve(N > 0 ? workspace : nullptr, N, Cout);
+    if (N > 0) {
+        const SubmStage s = subm_stage_args(N, pre, ln_weight, ln_bias, relu, grad_pre, w.part);
+        if (Cout == 128) hipLaunchKernelGGL(gf_subm_stage_bwd_kernel<128>, dim3(w.blocks), dim3(256), 0, stream, s, grad_out);
+        else if (Cout == 64) hipLaunchKernelGGL(gf_subm_stage_bwd_kernel<64>, dim3(w.blocks), dim3(256), 0, stream, s, grad_out);
+        else hipLaunchKernelGGL(gf_subm_stage_bwd_kernel<32>, dim3(w.blocks), dim3(256), 0, stream, s, grad_out);
+        GF_CHECK_LAUNCH();
+    }
+    subm_stage_sums(w, N, Cout, grad_ln_weight, grad_ln_bias, grad_bias, stream);
+    GF_CHECK_LAUNCH();
+    return GF_OK;
+}
+
+extern "C" int gf_subm_conv_apply_stage_backward(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
+                                                 const float *features, const float *weight, const void *tables, const int *pair_in,
+                                                 float *partial, void *scratch, size_t scratch_bytes, const float *pre,
+                                                 const float *ln_weight, const float *ln_bias, int relu, float *grad_pre,
+                                                 float *grad_ln_weight, float *grad_ln_bias, float *grad_bias, void *workspace,
+                                                 size_t workspace_bytes, void *stream_)
+{
+    using namespace gf;
+    const char *fn = __func__;
+    const bool sized = N > 0 && subm_channels_ok(Cin, Cout) && K >= 1 && K <= 7 && (K & 1) && total_pairs >= 0;
+    const size_t row = sized ? (size_t)Cout * sizeof(float) : 0;
+    const SubmRegion others[] = {{"features", features, sized ? (size_t)N * Cin * sizeof(float) : 0},
+                                 {"weight", weight, (size_t)K * K * K * Cin * row}, {"partial", partial, (size_t)total_pairs * row},
+                                 {"scratch", scratch, sized ? scratch_bytes : 0}, {"pair_in", pair_in, sized ? (size_t)total_pairs * sizeof(int) : 0},
+                                 {"tables", tables, (size_t)(sized ? 1 : 0)}};
+    GF_REFUSE_AS(fn, (Cin == 32 || Cin == 64 || Cin == 128), "unsupported channels: Cin = %d is not 32, 64 or 128", Cin);
+    if (int rc = subm_stage_check(fn, N, Cout, pre, ln_weight, ln_bias, relu, grad_pre, grad_ln_weight, grad_ln_bias, grad_bias, workspace,
+                                  workspace_bytes, others, 6))
+        return rc;
+    GF_REFUSE_AS(fn, !misaligned16(partial), "partial = %p is not 16-byte aligned", (const void *)partial);
+    if (N > 0 && !scratch) {
+        set_error("%s: null scratch (gf_subm_apply_scratch_bytes)", fn);
+        return GF_EINVAL;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    const SubmStageWork w = subm_stage_carve(N > 0 ? workspace : nullptr, N, Cout);
+    if (N > 0) {
+        const SubmStage s = subm_stage_args(N, pre, ln_weight, ln_bias, relu, grad_pre, w.part);
+        if (int rc = subm_conv_apply_impl(N, batch, X, Y, Z, K, Cin, Cout, total_pairs, features, weight, tables, pair_in, partial, grad_pre,
+                                          scratch, scratch_bytes, stream_, nullptr, &s))
+            return rc;
+    } else if (int rc = subm_check(N, batch, X, Y, Z, K)) {
+        return rc;
+    }
+    subm_stage_sums(w, N, Cout, grad_ln_weight, grad_ln_bias, grad_bias, stream);
+    GF_CHECK_LAUNCH();
+    return GF_OK;
 }
 
 extern "C" int gf_subm_conv_weight_grad(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout,

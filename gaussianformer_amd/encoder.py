@@ -135,7 +135,8 @@ class GaussianOccEncoder(nn.Module):
 
     def set_native(self, training=None, fused_mlp=None):
         """Sets ``native_training`` / ``fused_mlp`` on every submodule that has the attribute (``None``: left alone); returns
-        ``self``.  Their defaults do not change."""
+        ``self``.  Their defaults do not change.  ``native_training`` is an attribute of the anchor encoder, the feed-forward block, the
+        refinement modules and the sparse convolution block (``SparseConv3D``: its LayerNorm stages)."""
         for m in self.modules():
             if training is not None and hasattr(m, "native_training"):
                 m.native_training = bool(training)

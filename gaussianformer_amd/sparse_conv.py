@@ -4,7 +4,9 @@ Host mirror of ``SparseConv3D`` (model/encoder/gaussian_encoder/spconv3d_module.
 ``spconv.SubMConv3d`` has no ROCm build: the rulebook and the gather-GEMM run in
 ``gf_subm_rulebook_* / gf_subm_conv_apply / gf_subm_conv_weight_grad`` (include/gf_hip.h).  Without autograd the block's dense
 tail -- bias, LayerNorm, ReLU, ``output_proj``, the encoder's ``"add"`` / ``"norm"`` -- runs inside the convolutions' last pass
-(``gf_subm_conv_apply_epilogue``) and one ``gf_deform_output_forward`` launch.
+(``gf_subm_conv_apply_epilogue``) and one ``gf_deform_output_forward`` launch.  With autograd, a stage
+``relu?(LN((conv + bias) + residual))`` has a native training step (``subm_stage`` / ``subm_stages``, ``SubMStageFunction``,
+the block's opt-in ``native_training``).
 """
 import math
 
@@ -175,6 +177,49 @@ class Rulebook:
                   self.pair_in, partial, out, scratch, nscratch)
         return out
 
+    def stage(self, features, weight, bias=None, residual=None, norm=None, relu=False):
+        """The differentiable stage ``relu?(norm((conv + bias) + residual))`` with a native training step: :func:`subm_stage`."""
+        return subm_stage(features, self, weight, bias=bias, residual=residual, norm=norm, relu=relu)
+
+    def _scratch(self, cin, cout, dev):
+        """``(partial, scratch, nscratch)`` of one convolution call."""
+        nscratch = int(_lib.load().gf_subm_apply_scratch_bytes(self.N, cin))
+        return (torch.empty(max(self.total, 1), cout, dtype=f32, device=dev),
+                torch.empty(max(nscratch, 16), dtype=torch.uint8, device=dev), nscratch)
+
+    def stage_forward(self, features, weight, bias, residual, gamma, beta, relu):
+        """``(out, pre)`` of the saving forward (``gf_subm_conv_apply_epilogue_train``); the arguments as the library reads them."""
+        cin, cout = weight.shape[1], weight.shape[2]
+        dev = features.device
+        out = torch.empty(self.N, cout, dtype=f32, device=dev)
+        pre = torch.empty(self.N, cout, dtype=f32, device=dev)
+        partial, scratch, nscratch = self._scratch(cin, cout, dev)
+        _lib.call("gf_subm_conv_apply_epilogue_train", dev, *self.dims, cin, cout, self.total, features, weight, self.tables,
+                  self.pair_in, partial, out, scratch, nscratch, bias, residual, gamma, beta, int(bool(relu)), pre)
+        return out, pre
+
+    def stage_backward(self, pre, gamma, beta, relu, want_bias, grad_out=None, grad_next=None, weight_t=None):
+        """``(g_pre, g_gamma, g_beta, g_bias | None)`` of a stage.  With ``grad_out`` the standalone form
+        (``gf_subm_stage_backward``); with ``grad_next`` / ``weight_t`` -- the next stage's ``g_pre`` and its mirrored, transposed
+        weight -- the form inside that stage's data-gradient convolution (``gf_subm_conv_apply_stage_backward``): the same bits."""
+        cout = pre.shape[1]
+        dev = pre.device
+        g_pre = torch.empty_like(pre)
+        g_gamma, g_beta = torch.empty(cout, dtype=f32, device=dev), torch.empty(cout, dtype=f32, device=dev)
+        g_bias = torch.empty(cout, dtype=f32, device=dev) if want_bias else None
+        nwork = _lib.train_sizes("gf_subm_stage_train_sizes", self.N, cout)[1]
+        work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
+        if grad_out is not None:
+            _lib.call("gf_subm_stage_backward", dev, self.N, cout, pre, _lib.aligned(grad_out), gamma, beta, int(bool(relu)), g_pre,
+                      g_gamma, g_beta, g_bias, work, nwork)
+        else:
+            cin = weight_t.shape[1]
+            partial, scratch, nscratch = self._scratch(cin, cout, dev)
+            _lib.call("gf_subm_conv_apply_stage_backward", dev, *self.dims, cin, cout, self.total, grad_next, weight_t, self.tables,
+                      self.pair_in, partial, scratch, nscratch, pre, gamma, beta, int(bool(relu)), g_pre, g_gamma, g_beta, g_bias,
+                      work, nwork)
+        return g_pre, g_gamma, g_beta, g_bias
+
     def weight_grad(self, features, grad_out):
         features, grad_out = _lib.as_arg(features), _lib.as_arg(grad_out)
         cin, cout = features.shape[1], grad_out.shape[1]
@@ -204,6 +249,100 @@ class _SubMConv(Function):
         if ctx.needs_input_grad[1]:
             g_w = rb.weight_grad(features, grad_out)
         return g_feat, g_w, None
+
+
+STAGE_CHANNELS = (32, 64, 128)   # the widths the stage's training entries take (the epilogue's)
+
+
+class SubMStageFunction(Function):
+    """``S >= 1`` chained stages ``x <- relu?(LN((conv(x) + bias) + residual))`` on one rulebook with a native training step
+    (DESIGN.md §3.7c).  Forward: ``gf_subm_conv_apply_epilogue_train`` per stage; saved are each stage's input, weight, ``pre`` and
+    LayerNorm pair.  Backward, last stage first: the last stage's ``g_pre`` by ``gf_subm_stage_backward`` on ``grad_out``, every
+    earlier one's inside the data-gradient convolution of the stage behind it (``gf_subm_conv_apply_stage_backward``: ``dL/dy`` of
+    a stage in between never reaches memory), each followed by ``weight_grad(input, g_pre)``; the first stage's data gradient is
+    the plain convolution.  Arguments: ``rulebook, relus, features``, then per stage ``weight, bias | None, residual | None,
+    ln_weight, ln_bias``."""
+
+    @staticmethod
+    def forward(ctx, rulebook, relus, features, *flat):
+        x = _lib.as_arg(features)
+        saved, has = [], []
+        for s, relu in enumerate(relus):
+            weight, bias, residual, gamma, beta = flat[5 * s:5 * s + 5]
+            weight = _lib.as_arg(weight)
+            bias, residual, gamma, beta = (_lib.aligned(t) for t in (bias, residual, gamma, beta))
+            out, pre = rulebook.stage_forward(x, weight, bias, residual, gamma, beta, relu)
+            saved += [x, weight, gamma, beta, pre]
+            has.append((bias is not None, residual is not None))
+            x = out
+        ctx.rulebook, ctx.relus, ctx.has = rulebook, tuple(relus), has
+        ctx.save_for_backward(*saved)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        rb, saved, S = ctx.rulebook, ctx.saved_tensors, len(ctx.relus)
+        need = ctx.needs_input_grad
+        grads = [None] * (3 + 5 * S)
+        g_pre = weight_t = None
+        for s in reversed(range(S)):
+            x, weight, gamma, beta, pre = saved[5 * s:5 * s + 5]
+            has_bias, has_residual = ctx.has[s]
+            if s == S - 1:
+                g_pre, g_gamma, g_beta, g_bias = rb.stage_backward(pre, gamma, beta, ctx.relus[s], has_bias, grad_out=grad_out)
+            else:
+                g_pre, g_gamma, g_beta, g_bias = rb.stage_backward(pre, gamma, beta, ctx.relus[s], has_bias, grad_next=g_pre,
+                                                                   weight_t=weight_t)
+            # the neighbour relation is symmetric: same rulebook, kernel mirrored and transposed
+            weight_t = weight.flip(0).transpose(1, 2).contiguous() if s > 0 or need[2] else None
+            at = 3 + 5 * s
+            if need[at]:
+                grads[at] = rb.weight_grad(x, g_pre)
+            if has_bias and need[at + 1]:
+                grads[at + 1] = g_bias
+            if has_residual and need[at + 2]:
+                grads[at + 2] = g_pre
+            grads[at + 3], grads[at + 4] = (g_gamma if need[at + 3] else None), (g_beta if need[at + 4] else None)
+        if need[2]:
+            grads[2] = rb.apply(g_pre, weight_t)
+        return tuple(grads)
+
+
+def subm_stages(features, rulebook, stages):
+    """``stages``: a list of ``dict(weight=, bias=None, residual=None, norm=, relu=False)``, applied in their order to ``features``
+    on one rulebook as ONE :class:`SubMStageFunction` (``duplicates="sum"`` semantics: every point is a source).  ``norm`` is
+    required: a stage without a LayerNorm has no native training step."""
+    if rulebook.out_range is not None:
+        raise RuntimeError("a Rulebook with out_range is inference-only")
+    for st in stages:
+        if st.get("norm") is None:
+            raise ValueError("subm_stage: norm is required (an affine LayerNorm with eps = 1e-5, or a (weight, bias) pair)")
+        _norm_pair(st["norm"], "subm_stage")
+    _lib.require_gpu(features)
+    flat, relus, cin = [], [], features.shape[-1]
+    for st in stages:
+        weight, bias, residual = st["weight"], st.get("bias"), st.get("residual")
+        gamma, beta = _norm_pair(st["norm"], "subm_stage")
+        _lib.require_gpu(weight, bias, residual, gamma, beta)
+        cout = weight.shape[2]
+        if weight.shape[1] != cin or cin not in STAGE_CHANNELS or cout not in STAGE_CHANNELS:
+            raise ValueError(f"subm_stage: weight {tuple(weight.shape)} on {cin} input channels; channels must be in {STAGE_CHANNELS}")
+        for name, t, shape in (("bias", bias, (cout,)), ("residual", residual, (rulebook.N, cout)), ("norm weight", gamma, (cout,)),
+                               ("norm bias", beta, (cout,))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError(f"subm_stage: {name} {tuple(t.shape)} is not {shape}")
+        flat += [weight, bias, residual, gamma, beta]
+        relus.append(bool(st.get("relu", False)))
+        cin = cout
+    return SubMStageFunction.apply(rulebook, tuple(relus), features, *flat)
+
+
+def subm_stage(features, rulebook, weight, bias=None, residual=None, norm=None, relu=False):
+    """The differentiable stage ``relu?(norm((conv(features) + bias) + residual))`` on ``rulebook`` (:meth:`Rulebook.apply`'s
+    arguments; ``norm`` required) with a native forward and backward.  A chain of stages whose data gradients run inside one
+    another's backward is :func:`subm_stages`; calls of this function chain too, unfused, to the same bits."""
+    return subm_stages(features, rulebook, [dict(weight=weight, bias=bias, residual=residual, norm=norm, relu=relu)])
 
 
 DUPLICATES = ("sum", "last")
@@ -261,6 +400,7 @@ class SparseConv3D(nn.Module):
     rulebook -- a submanifold convolution keeps the active set."""
 
     native_tail = True
+    native_training = False   # opt-in: a call that needs autograd runs its LayerNorm stages' native training step (§3.7c)
 
     def __init__(self, in_channels, embed_channels, pc_range, grid_size, xyz_activation="sigmoid", use_out_proj=False,
                  kernel_size=5, use_multi_layer=False, pairs_per_point=None, duplicates="sum", **kwargs):
@@ -335,7 +475,10 @@ class SparseConv3D(nn.Module):
         ``(weight, bias)`` pair.  With ``native_tail`` (a class attribute, not a constructor key and not part of the
         ``state_dict``), nothing that needs autograd, fp32 GPU tensors and ``embed_channels == 128`` they, the stages' bias,
         LayerNorm and ReLU and ``output_proj`` run inside the convolutions' last pass and one ``gf_deform_output_forward`` launch;
-        every other call runs the torch layers, the two keywords as torch ops behind them.
+        every other call runs the torch layers, the two keywords as torch ops behind them.  With ``native_training`` (likewise a
+        class attribute, off by default) a call that DOES need autograd runs every stage that has a LayerNorm -- a multi-layer
+        block's three, a single-layer block's ``norm(conv + residual)`` where ``output_proj`` is the identity -- as a
+        ``SubMStageFunction`` (fp32 GPU tensors, widths 32 / 64 / 128); ``output_proj`` and what follows it stay torch ops.
 
         ``out_range=(lo, hi)`` (extra keyword, inference, batch size 1, single-layer blocks): ``instance_feature`` / ``anchor``
         are the WHOLE (all-gathered) anchor set, the block is evaluated for the anchors ``[lo, hi)`` only and returns
@@ -371,6 +514,8 @@ class SparseConv3D(nn.Module):
             self._unchecked.append(rb)
         if self._native_tail(instance_feature, anchor, residual, norm):
             return self._forward_native_tail(feats, rb, residual, norm).unflatten(0, (bs, g))
+        if self._native_training(instance_feature, anchor, residual, norm):
+            return self._forward_native_training(feats, rb, residual, norm, bs, g)
         if isinstance(self.layer, SubMConv3d):
             out = self.layer(feats, indices, bs, self._spatial, rulebook=rb)
         else:
@@ -404,6 +549,59 @@ class SparseConv3D(nn.Module):
         if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
             return False
         return not _lib.needs_grad(tensors)
+
+    def _stage_modules(self):
+        """``[(conv, ln)]`` of a multi-layer block built as conv + LayerNorm + ReLU three times, else ``None``."""
+        if isinstance(self.layer, SubMConv3d):
+            return None
+        stages = list(self.layer)
+        if len(stages) != 9:
+            return None
+        for conv, ln, act in zip(stages[0::3], stages[1::3], stages[2::3]):
+            if not (isinstance(conv, SubMConv3d) and isinstance(ln, nn.LayerNorm) and _norm_native(ln) and isinstance(act, nn.ReLU)):
+                return None
+        return list(zip(stages[0::3], stages[1::3]))
+
+    def _native_training(self, instance_feature, anchor, residual, norm):
+        """Whether this call's stages run their native training step (``native_training``): a call that needs
+        autograd, fp32 GPU tensors, widths in ``STAGE_CHANNELS``, and stages that have a LayerNorm -- the three of a multi-layer
+        block, or a single-layer block's ``norm(conv + residual)`` where ``output_proj`` is the identity and ``norm=`` is given."""
+        if not self.native_training or self.embed_channels not in STAGE_CHANNELS or instance_feature.shape[-1] not in STAGE_CHANNELS:
+            return False
+        if isinstance(self.layer, SubMConv3d):
+            if not isinstance(self.output_proj, nn.Identity) or norm is None or not _norm_native(norm):
+                return False
+        elif self._stage_modules() is None:
+            return False
+        tensors = [instance_feature, anchor, residual, *self.parameters()]
+        tensors += list(norm.parameters()) if isinstance(norm, nn.Module) else list(norm or ())
+        if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
+            return False
+        return _lib.needs_grad(tensors)
+
+    def _forward_native_training(self, feats, rb, residual, norm, bs, g):
+        """``[b, g, C]``: every stage that has a LayerNorm as a :class:`SubMStageFunction`; ``output_proj`` and what follows it stay
+        torch ops.  ``duplicates="sum"``: the three stages are one chained Function; ``"last"``: the mask multiply sits between the
+        stages, so they are three."""
+        def source(conv, x):
+            return x * rb.representative_mask() if conv.duplicates == "last" else x
+        if isinstance(self.layer, SubMConv3d):
+            conv = self.layer
+            res = None if residual is None else residual.flatten(0, 1)
+            return subm_stage(source(conv, feats), rb, conv.weight, bias=conv.bias, residual=res, norm=norm).unflatten(0, (bs, g))
+        pairs = self._stage_modules()
+        if all(conv.duplicates == "sum" for conv, _ in pairs):
+            out = subm_stages(feats, rb, [dict(weight=conv.weight, bias=conv.bias, norm=ln, relu=True) for conv, ln in pairs])
+        else:
+            out = feats
+            for conv, ln in pairs:
+                out = subm_stage(source(conv, out), rb, conv.weight, bias=conv.bias, norm=ln, relu=True)
+        out = self.output_proj(out.unflatten(0, (bs, g)))
+        if residual is not None:
+            out = out + residual
+        if norm is not None:
+            out = _apply_norm(out, norm)
+        return out
 
     def _forward_native_tail(self, feats, rb, residual, norm):
         """``[b*g, 128]``: the block with every dense op behind a convolution inside that convolution's last pass, and

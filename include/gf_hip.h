@@ -456,6 +456,51 @@ int gf_subm_conv_apply_epilogue(int N, int batch, int X, int Y, int Z, int K, in
                                 const float *features, const float *weight, const void *tables, const int *pair_in,
                                 float *partial, float *out, void *scratch, size_t scratch_bytes, const float *bias,
                                 const float *residual, const float *ln_weight, const float *ln_bias, int relu, void *stream);
+/* The training step of a stage y = relu?( LN( (c + bias?) + residual? ) ), the three conv + LayerNorm + ReLU stages of
+ * spconv3d_module.py:26-37 (and a single-layer block's norm(conv + residual)); the LayerNorm pair is required.
+ *
+ * gf_subm_stage_train_sizes (spconv3d_module.py:26-37): host code; the bytes of the two caller-allocated regions of a stage of N
+ * rows: `saved` holds pre [N, Cout], `workspace` the backward's partial triples (both 0 for N == 0, both monotone in N).
+ * GF_EINVAL: Cout outside {32, 64, 128}, N < 0, a null pointer.
+ *
+ * gf_subm_conv_apply_epilogue_train (spconv3d_module.py:26-37): gf_subm_conv_apply_epilogue -- the same arguments, the same
+ * refusals, out BITWISE the same -- that also stores pre[i] = (c + bias) + residual[i], the row the LayerNorm reads, to
+ * pre [N, Cout] (16-byte aligned, overlapping neither out nor an input).  Mean and rstd are not saved: the backward recomputes
+ * them from pre by the forward's own arithmetic.  ln_weight / ln_bias must both be given.
+ *
+ * gf_subm_stage_backward (spconv3d_module.py:26-37): from grad_out = dL/dy [N, Cout] and pre, with xhat, mean, rstd of pre,
+ *     u = xhat ln_weight + ln_bias,   g_u = relu ? (u > 0 ? grad_out : 0) : grad_out,   g_xhat = g_u ln_weight,
+ *     grad_pre = rstd (g_xhat - mean_c(g_xhat) - xhat mean_c(g_xhat xhat))               (= dL/dc = dL/dresidual)
+ *     grad_ln_bias = sum_i g_u,  grad_ln_weight = sum_i g_u xhat,  grad_bias = sum_i grad_pre   (grad_bias may be NULL)
+ * A workgroup sums the three column terms over its 256 / (Cout / 4) rows in a fixed order (a wave's rows by a butterfly, the
+ * four waves in their order), writes one partial triple to `workspace`, and a second launch adds the partials in double in a
+ * fixed order: no float atomics, bitwise reproducible.  A row of pre with a NaN or an infinity (an over-capacity rulebook's
+ * forward) gives NaN in grad_pre and in all three sums.
+ *
+ * gf_subm_conv_apply_stage_backward (spconv3d_module.py:26-37): gf_subm_conv_apply_scratch's arguments without `out`, then the
+ * stage backward's without grad_out: the convolution's finished row IS dL/dy of the stage whose rows `pre` are (the caller passes
+ * the next stage's grad_pre as features and that stage's mirrored, transposed weight, Cout = the width of `pre`); it goes through
+ * the stage backward in the reduce pass's registers and only grad_pre is stored.  grad_pre and the three sums are BITWISE those
+ * of gf_subm_conv_apply_scratch followed by gf_subm_stage_backward.
+ *
+ * Both backward entries refuse with GF_EINVAL before any HIP call: a null ln_weight or ln_bias, relu other than 0 or 1, a
+ * misaligned pointer, grad_pre overlapping any input or the workspace, Cout (Cin) outside {32, 64, 128}; GF_EWORKSPACE: a
+ * workspace shorter than gf_subm_stage_train_sizes says.  N == 0 returns GF_OK with the parameter gradients zero-filled.  No
+ * allocation, no host synchronisation: graph-capturable. */
+int gf_subm_stage_train_sizes(int N, int Cout, size_t *saved_bytes, size_t *workspace_bytes);
+int gf_subm_conv_apply_epilogue_train(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
+                                      const float *features, const float *weight, const void *tables, const int *pair_in,
+                                      float *partial, float *out, void *scratch, size_t scratch_bytes, const float *bias,
+                                      const float *residual, const float *ln_weight, const float *ln_bias, int relu, float *pre,
+                                      void *stream);
+int gf_subm_stage_backward(int N, int Cout, const float *pre, const float *grad_out, const float *ln_weight, const float *ln_bias,
+                           int relu, float *grad_pre, float *grad_ln_weight, float *grad_ln_bias, float *grad_bias, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int gf_subm_conv_apply_stage_backward(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
+                                      const float *features, const float *weight, const void *tables, const int *pair_in,
+                                      float *partial, void *scratch, size_t scratch_bytes, const float *pre, const float *ln_weight,
+                                      const float *ln_bias, int relu, float *grad_pre, float *grad_ln_weight, float *grad_ln_bias,
+                                      float *grad_bias, void *workspace, size_t workspace_bytes, void *stream);
 int gf_subm_conv_weight_grad(int N, int batch, int X, int Y, int Z, int K, int Cin, int Cout, long long total_pairs,
                              const float *features, const float *grad_out, const void *tables, const int *pair_in,
                              const int *pair_out, float *grad_weight, void *stream);
