@@ -1,5 +1,5 @@
 // gf_rows.hpp -- what the row-wise MFMA kernels share (anchor_embed.hip, ffn.hip, ffn_train.hip, refine_mlp.hip, refine_mlp_train.hip,
-// deform_dense.hip; the training backwards' parts on the same layout: gf_rows_bwd.hpp;
+// deform_dense.hip / gf_deform.hpp; the training backwards' parts on the same layout: gf_rows_bwd.hpp;
 // DESIGN.md §3.12b, §3.12c, §3.13, §3.13c, §3.13e): the register layout in which a wave holds 32 rows of 128-feature blocks, the LayerNorm on it, the staging of a
 // weight chunk through LDS, the chunk's 64 MFMAs and the store of a finished tile.
 //

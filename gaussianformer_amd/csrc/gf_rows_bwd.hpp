@@ -1,5 +1,5 @@
 // gf_rows_bwd.hpp -- what the native training backwards share on gf_rows.hpp's layout (anchor_embed.hip, ffn_train.hip,
-// refine_mlp_train.hip; the organisation: DESIGN.md §3.13b): the sum of a per-lane value over a tile's rows, the transposed
+// refine_mlp_train.hip, deform_dense_train.hip; the organisation: DESIGN.md §3.13b): the sum of a per-lane value over a tile's rows, the transposed
 // product dX^T = W^T dZ^T through LDS, the LayerNorm's data backward on registers, the weight gradient's row loop and the
 // fixed-order sum of the partials.  Every order of additions here is part of the results' bits
 // (tests/test_train_step_digests_gpu.py).

@@ -3,8 +3,10 @@
 ``deformable_fused_forward`` / ``deformable_fused``); its ends ran as torch layers wherever the block was assembled:
 ``kps_generator.learnable_fc`` and ``weights_fc`` on ``instance_feature + anchor_embed`` before the sampling, ``output_proj``
 with the add or the cat behind it.  ``gf_deform_logits_forward`` and ``gf_deform_output_forward`` (include/gf_hip.h, DESIGN.md
-§3.13e) are one launch each: an inference block is four launches and the ``[A, 128]`` sum never reaches memory.  Forward only:
-training, dropout and everything the native ops do not cover run the module's own torch layers around ``deformable_fused``."""
+§3.13e) are one launch each: an inference block is four launches and the ``[A, 128]`` sum never reaches memory.  The back end has
+a native training step as well (``deformable_output_autograd``: ``gf_deform_output_forward_train`` / ``gf_deform_output_backward``,
+DESIGN.md §3.13f), which the module takes with the opt-in ``native_training``; without it training, dropout and everything the
+native ops do not cover run the module's own torch layers around ``deformable_fused``."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -67,35 +69,117 @@ def deformable_logits(instance_feature, anchor_embed, weights_fc, learnable_fc=N
     return raw.view(*lead, Nw), None if learned is None else learned.view(*lead, K3 // 3, 3)
 
 
+def _output_args(name, features, output_proj, instance_feature, residual_mode, residual, norm):
+    """``(wo, bo, g, b, inst)`` of an output call, its mode and pairs checked; ``inst`` is ``None`` with ``"none"``."""
+    if residual_mode not in MODES:
+        raise ValueError(f"{name}: residual_mode {residual_mode!r} is not one of {sorted(MODES)}")
+    wo, bo = _pair(output_proj, "output_proj")
+    g, b = _pair(norm, "norm", nn.LayerNorm)
+    inst = instance_feature if residual_mode != "none" else None
+    if residual_mode != "none" and inst is None:
+        raise ValueError(f"{name}: residual_mode {residual_mode!r} needs instance_feature")
+    return wo, bo, g, b, inst
+
+
+def _output_shapes(name, features, inst, residual, wo, bo, g, b):
+    """``(x [n, E], inst [n, E] | None, residual [n, E] | None, leading shape, E)`` as the library reads them, the shapes checked."""
+    _lib.require_gpu(features, inst, residual, wo, bo, g, b)
+    E = features.shape[-1]
+    if wo.shape != (E, E) or bo.shape != (E,) or (g is not None and (g.shape != (E,) or b.shape != (E,))):
+        raise ValueError(f"{name}: features [..., {E}] against output_proj {tuple(wo.shape)}, {tuple(bo.shape)}")
+    for what, t in (("instance_feature", inst), ("residual", residual)):
+        if t is not None and t.shape != features.shape:
+            raise ValueError(f"{name}: {what} {tuple(t.shape)} is not {tuple(features.shape)}")
+    x = _lib.aligned(features).reshape(-1, E)
+    fi, res = (None if t is None else _lib.aligned(t).reshape(-1, E) for t in (inst, residual))
+    return x, fi, res, features.shape[:-1], E
+
+
 def deformable_output(features, output_proj, instance_feature=None, residual_mode="add", residual=None, norm=None):
     """``out`` of the block in one launch, on any leading shape: ``y = output_proj(features)``, then ``y`` (``residual_mode``
     ``"none"``), ``y + instance_feature`` (``"add"``) or ``cat([y, instance_feature])`` (``"cat"``; deformable_module.py:243-248),
     then -- not with ``"cat"`` -- ``+ residual [..., 128]`` and the ``nn.LayerNorm(128)`` ``norm`` where given: the encoder's
     ``"add", "norm"`` behind the block.  ``output_proj`` / ``norm``: a module or a ``(weight, bias)`` pair.  ``proj_drop`` is
     not applied (eval semantics).  Forward only: inputs that need autograd are refused."""
-    if residual_mode not in MODES:
-        raise ValueError(f"deformable_output: residual_mode {residual_mode!r} is not one of {sorted(MODES)}")
-    wo, bo = _pair(output_proj, "output_proj")
-    g, b = _pair(norm, "norm", nn.LayerNorm)
-    inst = instance_feature if residual_mode != "none" else None
-    if residual_mode != "none" and inst is None:
-        raise ValueError(f"deformable_output: residual_mode {residual_mode!r} needs instance_feature")
+    wo, bo, g, b, inst = _output_args("deformable_output", features, output_proj, instance_feature, residual_mode, residual, norm)
     _refuse_autograd("deformable_output", [features, inst, residual, wo, bo, g, b])
-    _lib.require_gpu(features, inst, residual, wo, bo, g, b)
-    E = features.shape[-1]
-    if wo.shape != (E, E) or bo.shape != (E,) or (g is not None and (g.shape != (E,) or b.shape != (E,))):
-        raise ValueError(f"deformable_output: features [..., {E}] against output_proj {tuple(wo.shape)}, {tuple(bo.shape)}")
-    for name, t in (("instance_feature", inst), ("residual", residual)):
-        if t is not None and t.shape != features.shape:
-            raise ValueError(f"deformable_output: {name} {tuple(t.shape)} is not {tuple(features.shape)}")
-    lead = features.shape[:-1]
-    x = _lib.aligned(features).reshape(-1, E)
-    fi, res = (None if t is None else _lib.aligned(t).reshape(-1, E) for t in (inst, residual))
+    return _output_launch("deformable_output", features, inst, residual_mode, residual, wo, bo, g, b)
+
+
+def _output_launch(name, features, inst, residual_mode, residual, wo, bo, g, b):
+    """The inference launch; the callers have settled autograd."""
+    x, fi, res, lead, E = _output_shapes(name, features, inst, residual, wo, bo, g, b)
     table, held = _lib.param_table([wo, bo, g, b], _lib.GF_DEFORM_OUTPUT_PARAMS)
     width = 2 * E if residual_mode == "cat" else E
     out = torch.empty(x.shape[0], width, dtype=f32, device=x.device)
     _lib.call("gf_deform_output_forward", x.device, x.shape[0], E, MODES[residual_mode], x, fi, table, res, out)
     return out.view(*lead, width)
+
+
+def output_train_sizes(n, residual_mode="add", with_norm=False, E=E_NATIVE):
+    """``(saved_bytes, workspace_bytes)`` of the output's training step on ``n`` rows (``gf_deform_output_train_sizes``)."""
+    return _lib.train_sizes("gf_deform_output_train_sizes", n, E, MODES[residual_mode], int(bool(with_norm)))
+
+
+class DeformOutputFunction(torch.autograd.Function):
+    """``out = DeformOutputFunction.apply(residual_mode, features, instance_feature, residual, wo, bo, g, b)`` (``None`` for an
+    absent tensor): ``gf_deform_output_forward_train`` keeps the row before the post norm and its statistics (nothing without a
+    norm), ``gf_deform_output_backward`` returns the gradients of ``features``, ``instance_feature``, the residual and the four
+    parameters -- of those that require one; the others get ``None`` and the library a NULL slot.  Once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, residual_mode, features, instance_feature, residual, wo, bo, g, b):
+        x, fi, res, lead, E = _output_shapes("deformable_output_autograd", features, instance_feature, residual, wo, bo, g, b)
+        params = [wo, bo, g, b]
+        table, held = _lib.param_table(params, _lib.GF_DEFORM_OUTPUT_PARAMS)
+        n, mode = x.shape[0], MODES[residual_mode]
+        saved_bytes, _ = output_train_sizes(n, residual_mode, g is not None, E)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device) if saved_bytes else None
+        width = 2 * E if residual_mode == "cat" else E
+        out = torch.empty(n, width, dtype=f32, device=x.device)
+        _lib.call("gf_deform_output_forward_train", x.device, n, E, mode, x, fi, table, res, out, saved, saved_bytes)
+        ctx.save_for_backward(x, saved, *held)
+        ctx.shape = (lead, E, residual_mode, features.dtype, None if instance_feature is None else instance_feature.dtype,
+                     None if residual is None else residual.dtype, [None if p is None else p.dtype for p in params])
+        return out.view(*lead, width)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, saved, *held = ctx.saved_tensors
+        lead, E, residual_mode, x_dtype, inst_dtype, res_dtype, dtypes = ctx.shape
+        n, mode, need = x.shape[0], MODES[residual_mode], ctx.needs_input_grad
+        params, grads, it = [], [], iter(held)
+        for i, d in enumerate(dtypes):
+            params.append(None if d is None else next(it))
+            grads.append(torch.empty_like(params[-1]) if d is not None and need[4 + i] else None)
+        table, _ = _lib.param_table(params, _lib.GF_DEFORM_OUTPUT_PARAMS)
+        _, work_bytes = output_train_sizes(n, residual_mode, params[2] is not None, E)
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=x.device)
+        new = lambda: torch.empty(n, E, dtype=f32, device=x.device)
+        grad_x = new()     # (the library writes it in full whoever asks)
+        grad_inst = new() if inst_dtype is not None and need[2] else None
+        grad_res = new() if res_dtype is not None and need[3] else None
+        width = 2 * E if residual_mode == "cat" else E
+        go = _lib.aligned(grad_out).reshape(n, width)
+        _lib.call("gf_deform_output_backward", x.device, n, E, mode, x, table, saved, go, grad_x, grad_inst, grad_res,
+                  _lib.out_table(grads, _lib.GF_DEFORM_OUTPUT_PARAMS), work, work_bytes)
+        return (None, grad_x.view(*lead, E).to(x_dtype) if need[1] else None,
+                None if grad_inst is None else grad_inst.view(*lead, E).to(inst_dtype),
+                None if grad_res is None else grad_res.view(*lead, E).to(res_dtype),
+                *[None if gr is None else gr.to(d) for gr, d in zip(grads, dtypes)])
+
+
+def deformable_output_autograd(features, output_proj, instance_feature=None, residual_mode="add", residual=None, norm=None):
+    """``deformable_output`` with a native backward: the same arguments and checks, and ``out`` carries the graph of
+    ``DeformOutputFunction``, so ``features``, ``instance_feature``, the residual and each of the four parameters that requires
+    grad receives its gradient (the others ``None``).  ``proj_drop`` is not part of the op.  With nothing that needs autograd
+    (or under ``torch.no_grad()``) it is ``deformable_output``."""
+    name = "deformable_output_autograd"
+    wo, bo, g, b, inst = _output_args(name, features, output_proj, instance_feature, residual_mode, residual, norm)
+    if not _lib.needs_grad([features, inst, residual, wo, bo, g, b]):
+        return _output_launch(name, features, inst, residual_mode, residual, wo, bo, g, b)
+    return DeformOutputFunction.apply(residual_mode, features, inst, residual, wo, bo, g, b)
 
 
 class DeformableFeatureAggregation(nn.Module):
@@ -115,9 +199,17 @@ class DeformableFeatureAggregation(nn.Module):
     ``native_dense`` is a class attribute, not a constructor key and not part of the ``state_dict``: ``False`` forces
     ``forward_torch``.  The keyword arguments ``residual=`` and ``norm=`` of ``forward`` fold the encoder's following ``"add",
     "norm"`` into the output launch (``out = norm(out + residual)``; not with ``"cat"``); without them the call is the
-    reference's."""
+    reference's.
+
+    ``native_training`` is likewise a class attribute, off by default and not part of the ``state_dict``: with it a call that
+    needs autograd runs ``forward_torch`` as it is up to ``features`` and then ``deformable_output_autograd`` -- ``output_proj``,
+    the add or the cat, ``residual=`` and ``norm=`` in one saving launch with a native backward -- under
+    the conditions of the native route that concern the back end: ``embed_dims == 128``, fp32 GPU tensors, a known
+    ``residual_mode``, eval mode or ``proj_drop.p == 0``, an affine ``LayerNorm`` with ``eps = 1e-5``.  The front end
+    (``weights_fc``, ``learnable_fc``) stays on torch there."""
 
     native_dense = True
+    native_training = False
 
     def __init__(self, embed_dims=256, num_groups=8, num_levels=4, num_cams=6, proj_drop=0.0, attn_drop=0.0, kps_generator=None,
                  use_deformable_func=False, use_camera_embed=False, residual_mode="add"):
@@ -153,29 +245,44 @@ class DeformableFeatureAggregation(nn.Module):
         nn.init.xavier_uniform_(self.output_proj.weight)
         nn.init.constant_(self.output_proj.bias, 0.0)
 
-    def _native(self, instance_feature, anchor, anchor_embed, table, residual, norm):
-        if not self.native_dense or self.embed_dims != E_NATIVE or self.residual_mode not in MODES:
-            return False
+    def _output_native(self, instance_feature, anchor, anchor_embed, table, residual, norm):
+        """The tensors of a call whose back end has a native form, else ``None``: the conditions the inference route and
+        the training step share."""
+        if self.embed_dims != E_NATIVE or self.residual_mode not in MODES:
+            return None
         if self.training and self.proj_drop.p > 0:
-            return False
-        if 3 * self.kps_generator.num_learnable_pts > MAX_LEARNED:
-            return False
+            return None
         if self.residual_mode == "cat" and (residual is not None or norm is not None):
-            return False
+            return None
         if isinstance(norm, nn.LayerNorm) and (norm.eps != 1e-5 or norm.weight is None or norm.bias is None):
-            return False
+            return None
         tensors = [instance_feature, anchor, anchor_embed, table, residual, *self.parameters()]
         tensors += list(norm.parameters()) if isinstance(norm, nn.Module) else list(norm or ())
         if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
+            return None
+        return tensors
+
+    def _native(self, instance_feature, anchor, anchor_embed, table, residual, norm):
+        if not self.native_dense or 3 * self.kps_generator.num_learnable_pts > MAX_LEARNED:
             return False
-        return not _lib.needs_grad(tensors)
+        tensors = self._output_native(instance_feature, anchor, anchor_embed, table, residual, norm)
+        return tensors is not None and not _lib.needs_grad(tensors)
+
+    def _native_training(self, instance_feature, anchor, anchor_embed, table, residual, norm):
+        """Whether this call's back end runs its native training step (``native_training``)."""
+        if not self.native_training or (isinstance(norm, nn.Module) and not isinstance(norm, nn.LayerNorm)):
+            return False
+        tensors = self._output_native(instance_feature, anchor, anchor_embed, table, residual, norm)
+        return tensors is not None and _lib.needs_grad(tensors)
 
     def forward(self, instance_feature, anchor, anchor_embed, feature_maps, metas, **kwargs):
         residual, norm = kwargs.get("residual"), kwargs.get("norm")
         if not (isinstance(feature_maps, (tuple, list)) and len(feature_maps) == 3 and feature_maps[1].dim() == 2):
             feature_maps = DAF.feature_maps_format(feature_maps)
         if not self._native(instance_feature, anchor, anchor_embed, feature_maps[0], residual, norm):
-            return self.forward_torch(instance_feature, anchor, anchor_embed, feature_maps, metas, residual=residual, norm=norm)
+            native_output = self._native_training(instance_feature, anchor, anchor_embed, feature_maps[0], residual, norm)
+            return self.forward_torch(instance_feature, anchor, anchor_embed, feature_maps, metas, residual=residual, norm=norm,
+                                      native_output=native_output)
         bs, A = instance_feature.shape[:2]
         gen = self.kps_generator
         raw, learned = deformable_logits(instance_feature, anchor_embed, self.weights_fc,
@@ -191,9 +298,10 @@ class DeformableFeatureAggregation(nn.Module):
             features = deformable_fused_forward(kp, pm, wh, *feature_maps, raw_weights=raw.view(bs, A, self.num_cams, L, self.num_pts, G))
         return deformable_output(features, self.output_proj, instance_feature, self.residual_mode, residual, norm)
 
-    def forward_torch(self, instance_feature, anchor, anchor_embed, feature_maps, metas, residual=None, norm=None):
+    def forward_torch(self, instance_feature, anchor, anchor_embed, feature_maps, metas, residual=None, norm=None, native_output=False):
         """The reference's composition (:146-262) on the module's torch layers around ``deformable_fused``; ``feature_maps`` is
-        the formatted triple."""
+        the formatted triple.  ``native_output``: everything behind ``features`` is ``deformable_output_autograd`` (the caller
+        has asked ``_native_training``)."""
         bs, A = instance_feature.shape[:2]
         kp = self.kps_generator(anchor, instance_feature)
         pm, wh = metas["projection_mat"], metas.get("image_wh")
@@ -211,6 +319,8 @@ class DeformableFeatureAggregation(nn.Module):
             features = deformable_fused_forward(kp, pm, wh, *feature_maps, **logits)     # the same block, the inference launch
         else:
             features = deformable_fused(kp, pm, wh, *feature_maps, weight_mask=weight_mask, **logits)
+        if native_output:
+            return deformable_output_autograd(features, self.output_proj, instance_feature, self.residual_mode, residual, norm)
         output = self.proj_drop(self.output_proj(features))
         if self.residual_mode == "add":
             output = output + instance_feature

@@ -3,8 +3,9 @@ walks a config's ``operation_order`` over the anchor encoder, the deformable blo
 convolution block, the refinement step and the LayerNorms between them.  Every one of those has a one-launch inference form
 that takes the ``"add"`` / ``"norm"`` behind it (``ffn_block``, ``DeformableFeatureAggregation.forward(residual=, norm=)``,
 ``SparseConv3D.forward(residual=, norm=)``); :func:`plan` turns the runs ``"identity", X, "add", "norm"`` and ``X, "norm"`` of an
-order into those calls.  Inference only: training, and every call the fused forms do not cover, walks the
-order op by op as the reference does."""
+order into those calls.  Training folds the same steps with the opt-in ``fold_training``, where a step's
+layer has a native training route that takes the add and the norm; without it training, and every call the
+fused forms do not cover, walks the order op by op as the reference does."""
 import copy
 from collections import namedtuple
 
@@ -15,9 +16,9 @@ from . import _lib
 from .anchor_encoder import SparseGaussian3DEncoder
 from .deformable_aggregation import DeformableAggregationFunction as DAF
 from .deformable_block import DeformableFeatureAggregation
-from .ffn import AsymmetricFFN, ffn_block
+from .ffn import AsymmetricFFN, ffn_block, ffn_block_autograd
 from .refine import SparseGaussian3DRefinementModule, SparseGaussian3DRefinementModuleV2
-from .sparse_conv import SparseConv3D, _norm_native
+from .sparse_conv import SparseConv3D, SubMConv3d, _norm_native
 
 f32 = torch.float32
 
@@ -98,9 +99,18 @@ class GaussianOccEncoder(nn.Module):
 
     ``fold`` is a class attribute, not a constructor key and not part of the ``state_dict``.  With it, in eval mode, on fp32 GPU
     inputs and with nothing that needs autograd, the call runs the steps of :func:`plan`: one fused call per step.  Every
-    other call, training included, walks the order op by op on each module's own route."""
+    other call, training included, walks the order op by op on each module's own route.
+
+    ``fold_training`` is likewise a class attribute, off by default (``set_native(fold_training=True)`` sets it on the instance).
+    With it a call in train mode or one that needs autograd, on fp32 GPU inputs, runs the steps of :func:`plan` too: a step that
+    absorbed an ``"add"`` or a ``"norm"`` is one call where its layer's own native training route takes them -- a deformable
+    block with ``native_training`` or a sparse block with ``native_training`` and ``native_tail_training`` (``residual=`` /
+    ``norm=``), an ``AsymmetricFFN`` with ``native_training``
+    and no active ``dropout_layer`` (``ffn_block_autograd`` with the module's dropout probabilities) -- and the same ops one by
+    one otherwise.  The random draws come in the unfolded route's order."""
 
     fold = True
+    fold_training = False
 
     def __init__(self, anchor_encoder, norm_layer, ffn, deformable_model, refine_layer, mid_refine_layer=None, spconv_layer=None,
                  num_decoder=6, operation_order=None, init_cfg=None, **kwargs):
@@ -133,11 +143,18 @@ class GaussianOccEncoder(nn.Module):
             if hasattr(m, "init_weight"):
                 m.init_weight()
 
-    def set_native(self, training=None, fused_mlp=None):
+    def set_native(self, training=None, fused_mlp=None, fold_training=None):
         """Sets ``native_training`` / ``fused_mlp`` on every submodule that has the attribute (``None``: left alone); returns
-        ``self``.  Their defaults do not change.  ``native_training`` is an attribute of the anchor encoder, the feed-forward block, the
-        refinement modules and the sparse convolution block (``SparseConv3D``: its LayerNorm stages)."""
+        ``self``.  Their defaults do not change.  ``native_training`` is an attribute of the anchor encoder, the feed-forward
+        block, the refinement modules, the deformable block (its back end) and the sparse convolution block
+        (``SparseConv3D``: its LayerNorm stages).  ``fold_training`` sets this encoder's attribute of that name
+        and ``native_tail_training`` on every submodule that has it (``SparseConv3D``: the tail that takes the block's add and
+        norm in training); ``training=`` touches neither."""
+        if fold_training is not None:
+            self.fold_training = bool(fold_training)
         for m in self.modules():
+            if fold_training is not None and hasattr(m, "native_tail_training"):
+                m.native_tail_training = bool(fold_training)
             if training is not None and hasattr(m, "native_training"):
                 m.native_training = bool(training)
             if fused_mlp is not None and hasattr(m, "fused_mlp"):
@@ -153,6 +170,15 @@ class GaussianOccEncoder(nn.Module):
             return False
         return not _lib.needs_grad([*tensors, *self.parameters()])
 
+    def _folds_training(self, anchor, instance_feature, feature_maps):
+        if not self.fold_training:
+            return False
+        maps = [] if feature_maps is None else [feature_maps[0]] if _formatted(feature_maps) else list(feature_maps)
+        tensors = [anchor, instance_feature, *maps]
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == f32 for t in tensors):
+            return False
+        return self.training or _lib.needs_grad([*tensors, *self.parameters()])
+
     def forward(self, representation, rep_features, ms_img_feats=None, metas=None, **kwargs):
         feature_maps = ms_img_feats
         if isinstance(feature_maps, torch.Tensor):
@@ -160,26 +186,31 @@ class GaussianOccEncoder(nn.Module):
         instance_feature = rep_features
         anchor = representation
         fold = self._folds(anchor, instance_feature, feature_maps)
+        fold_training = not fold and self._folds_training(anchor, instance_feature, feature_maps)
         if feature_maps is not None and not _formatted(feature_maps) and "deformable" in self.operation_order:
             feature_maps = DAF.feature_maps_format(list(feature_maps))    # once, not in every block
         anchor_embed = self.anchor_encoder(anchor)
         identity = None
         prediction = []
         last = len(self.operation_order) - 1
-        steps = self.steps if fold else [Step(op, i, False, None) for i, op in enumerate(self.operation_order)]
+        steps = self.steps if fold or fold_training else [Step(op, i, False, None) for i, op in enumerate(self.operation_order)]
         for step in steps:
             op, i = step.op, step.index
             layer = self.layers[i]
             norm = None if step.norm is None else self.layers[step.norm]
             residual = identity if step.add else None
             fused = step.add or norm is not None
-            if fused and not self._step_folds(op, layer, instance_feature, anchor, anchor_embed, feature_maps, residual, norm):
+            folds = self._step_folds_training if fold_training else self._step_folds
+            if fused and not folds(op, layer, instance_feature, anchor, anchor_embed, feature_maps, residual, norm):
                 # the fused call would refuse this configuration: the same ops one by one
                 instance_feature = self._one(op, layer, instance_feature, anchor, anchor_embed, feature_maps, metas)
                 if step.add:
                     instance_feature = instance_feature + identity
                 if norm is not None:
                     instance_feature = norm(instance_feature)
+            elif fused and op == "ffn" and fold_training:
+                p_hidden, p_out = (layer.layers[0][2].p, layer.layers[2].p) if layer.training else (0.0, 0.0)
+                instance_feature = ffn_block_autograd(instance_feature, layer, norm, residual, p_hidden, p_out)
             elif fused and op == "ffn":
                 instance_feature = ffn_block(instance_feature, layer, norm, residual)
             elif fused and op == "deformable":
@@ -223,3 +254,31 @@ class GaussianOccEncoder(nn.Module):
         if layer.add_identity and isinstance(layer.identity_fc, nn.Identity):
             return False
         return layer.pre_norm is None or isinstance(layer.pre_norm, nn.LayerNorm)
+
+    @classmethod
+    def _step_folds_training(cls, op, layer, instance_feature, anchor, anchor_embed, feature_maps, residual, norm):
+        """``_step_folds`` for a training call: whether the layer's own native training route takes the step's add and norm.
+        The deformable block and the sparse block are asked what their ``forward`` asks (a call that needs no autograd
+        after all is their inference route's); the feed-forward block must have ``native_training``, no active
+        ``dropout_layer`` and dropout probabilities below 1, as its own ``forward`` requires."""
+        if not getattr(layer, "native_training", False):
+            return False
+        if op == "deformable":
+            if not isinstance(layer, DeformableFeatureAggregation) or feature_maps is None:
+                return False
+            args = (instance_feature, anchor, anchor_embed, feature_maps[0], residual, norm)
+            return layer._native_training(*args) or layer._native(*args)
+        if op == "spconv":
+            if not isinstance(layer, SparseConv3D):
+                return False
+            args = (instance_feature, anchor, residual, norm)
+            if layer._native_tail(*args):
+                return True
+            return layer._native_training(*args) and (layer._tail_training(norm) or isinstance(layer.layer, SubMConv3d))
+        if not cls._step_folds(op, layer, instance_feature, anchor, anchor_embed, feature_maps, residual, norm):
+            return False
+        if not isinstance(norm, (nn.LayerNorm, type(None))):
+            return False
+        if layer.training and isinstance(layer.dropout_layer, nn.Dropout) and layer.dropout_layer.p > 0:
+            return False
+        return not layer.training or (layer.layers[0][2].p < 1.0 and layer.layers[2].p < 1.0)

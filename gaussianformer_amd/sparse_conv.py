@@ -401,6 +401,7 @@ class SparseConv3D(nn.Module):
 
     native_tail = True
     native_training = False   # opt-in: a call that needs autograd runs its LayerNorm stages' native training step (§3.7c)
+    native_tail_training = False   # opt-in, with native_training: output_proj and the add / norm behind it as one native training step (§3.13f)
 
     def __init__(self, in_channels, embed_channels, pc_range, grid_size, xyz_activation="sigmoid", use_out_proj=False,
                  kernel_size=5, use_multi_layer=False, pairs_per_point=None, duplicates="sum", **kwargs):
@@ -478,7 +479,11 @@ class SparseConv3D(nn.Module):
         every other call runs the torch layers, the two keywords as torch ops behind them.  With ``native_training`` (likewise a
         class attribute, off by default) a call that DOES need autograd runs every stage that has a LayerNorm -- a multi-layer
         block's three, a single-layer block's ``norm(conv + residual)`` where ``output_proj`` is the identity -- as a
-        ``SubMStageFunction`` (fp32 GPU tensors, widths 32 / 64 / 128); ``output_proj`` and what follows it stay torch ops.
+        ``SubMStageFunction`` (fp32 GPU tensors, widths 32 / 64 / 128); ``output_proj`` and what follows it stay torch ops
+        unless ``native_tail_training`` (a third class attribute, off by default, effective with ``native_training`` only) is
+        set as well: then an ``output_proj`` that is a Linear with bias at ``embed_channels == 128``, with the ``residual=`` /
+        ``norm=`` behind it, runs as ``deformable_output_autograd`` -- so a single-layer block with such an
+        ``output_proj`` qualifies too: its convolution Function with the bias, then that tail.
 
         ``out_range=(lo, hi)`` (extra keyword, inference, batch size 1, single-layer blocks): ``instance_feature`` / ``anchor``
         are the WHOLE (all-gathered) anchor set, the block is evaluated for the anchors ``[lo, hi)`` only and returns
@@ -565,11 +570,14 @@ class SparseConv3D(nn.Module):
     def _native_training(self, instance_feature, anchor, residual, norm):
         """Whether this call's stages run their native training step (``native_training``): a call that needs
         autograd, fp32 GPU tensors, widths in ``STAGE_CHANNELS``, and stages that have a LayerNorm -- the three of a multi-layer
-        block, or a single-layer block's ``norm(conv + residual)`` where ``output_proj`` is the identity and ``norm=`` is given."""
+        block, or a single-layer block's ``norm(conv + residual)`` where ``output_proj`` is the identity and ``norm=`` is given,
+        or a single-layer block whose ``output_proj`` has the native tail (``_tail_training``)."""
         if not self.native_training or self.embed_channels not in STAGE_CHANNELS or instance_feature.shape[-1] not in STAGE_CHANNELS:
             return False
         if isinstance(self.layer, SubMConv3d):
-            if not isinstance(self.output_proj, nn.Identity) or norm is None or not _norm_native(norm):
+            if self._tail_training(norm):
+                pass
+            elif not isinstance(self.output_proj, nn.Identity) or norm is None or not _norm_native(norm):
                 return False
         elif self._stage_modules() is None:
             return False
@@ -579,15 +587,27 @@ class SparseConv3D(nn.Module):
             return False
         return _lib.needs_grad(tensors)
 
+    def _tail_training(self, norm):
+        """Whether ``output_proj`` with the ``residual=`` / ``norm=`` behind it runs its native training step (§3.13f):
+        ``native_tail_training``, a Linear with bias at width 128 and a norm the library takes."""
+        proj = self.output_proj
+        return self.native_tail_training and self.embed_channels == E_NATIVE and isinstance(proj, nn.Linear) and proj.bias is not None and _norm_native(norm)
+
     def _forward_native_training(self, feats, rb, residual, norm, bs, g):
-        """``[b, g, C]``: every stage that has a LayerNorm as a :class:`SubMStageFunction`; ``output_proj`` and what follows it stay
-        torch ops.  ``duplicates="sum"``: the three stages are one chained Function; ``"last"``: the mask multiply sits between the
-        stages, so they are three."""
+        """``[b, g, C]``: every stage that has a LayerNorm as a :class:`SubMStageFunction`, and ``output_proj`` with what follows
+        it as ``deformable_output_autograd`` where ``_tail_training`` says so (torch ops otherwise).  ``duplicates="sum"``: the
+        three stages are one chained Function; ``"last"``: the mask multiply sits between the stages, so they are three."""
+        from .deformable_block import deformable_output_autograd   # (here: deformable_block's imports reach back to this package)
+
         def source(conv, x):
             return x * rb.representative_mask() if conv.duplicates == "last" else x
+        tail = self._tail_training(norm)
+        res = None if residual is None else residual.flatten(0, 1)
         if isinstance(self.layer, SubMConv3d):
             conv = self.layer
-            res = None if residual is None else residual.flatten(0, 1)
+            if tail:
+                out = conv(feats, rb.indices, bs, self._spatial, rulebook=rb)
+                return deformable_output_autograd(out, self.output_proj, residual_mode="none", residual=res, norm=norm).unflatten(0, (bs, g))
             return subm_stage(source(conv, feats), rb, conv.weight, bias=conv.bias, residual=res, norm=norm).unflatten(0, (bs, g))
         pairs = self._stage_modules()
         if all(conv.duplicates == "sum" for conv, _ in pairs):
@@ -596,6 +616,8 @@ class SparseConv3D(nn.Module):
             out = feats
             for conv, ln in pairs:
                 out = subm_stage(source(conv, out), rb, conv.weight, bias=conv.bias, norm=ln, relu=True)
+        if tail:
+            return deformable_output_autograd(out, self.output_proj, residual_mode="none", residual=res, norm=norm).unflatten(0, (bs, g))
         out = self.output_proj(out.unflatten(0, (bs, g)))
         if residual is not None:
             out = out + residual

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward, gf_ffn_*, gf_refine_mlp_*, gf_deform_logits_forward / gf_deform_output_forward, gf_miou_workspace_size / gf_miou_step / gf_miou_step_logits, gf_subm_conv_apply_epilogue, gf_head_geosem_forward / gf_head_geosem_backward (added without a bump: a library without them fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
+#define GF_ABI_VERSION 10   /* 10: gf_refine_forward / gf_refine_backward, and gf_anchor_embed_forward, gf_ffn_*, gf_refine_mlp_*, gf_deform_logits_forward / gf_deform_output_forward, gf_deform_output_train_sizes / gf_deform_output_forward_train / gf_deform_output_backward, gf_miou_workspace_size / gf_miou_step / gf_miou_step_logits, gf_subm_conv_apply_epilogue, gf_head_geosem_forward / gf_head_geosem_backward (added without a bump: a library without them fails to load, the binding resolves every symbol); 9: gf_dcn_workspace_bytes / gf_dcn_forward / gf_dcn_backward; 8: gf_lift_workspace_bytes / gf_lift_pixels, gf_pixel_loss_workspace_bytes / gf_pixel_loss_forward / gf_pixel_loss_backward; 7: gf_occ_loss_workspace_bytes / gf_occ_loss_forward / gf_occ_loss_backward; 6: gf_daf_fused_forward_masked / gf_daf_fused_backward_workspace_bytes / gf_daf_fused_backward; 5: gf_fps_workspace_bytes / gf_farthest_point_sampling, option "fps.exhaustive"; 4 (round 6, later): gf_subm_conv_apply_scratch / gf_subm_apply_scratch_bytes, option "subm.bf16x3", state word 4 bit 1, long rows in the matrix-core backward; 3 (round 6): gf_set_option / gf_get_option / gf_is_development_build, gf_daf_fused_forward; GF_WORKSPACE_ZEROED = one verdict word; workspace without the fused forward's per-XCD copies */
 
 /* error codes */
 #define GF_OK 0
@@ -1148,6 +1148,46 @@ int gf_deform_logits_forward(int n, int E, int K3, int Nw, const float *feature,
 #define GF_DEFORM_CAT 2
 int gf_deform_output_forward(int n, int E, int mode, const float *features, const float *instance_feature,
                              const void *const *params, const float *residual, float *out, void *stream);
+
+/* The training step of the dense back: a forward that also saves what the backward needs, and the full
+ * backward.  The modes, the 4-pointer params table, E == 128 and the alignment and aliasing rules are
+ * gf_deform_output_forward's; proj_drop is not part of the op.
+ *
+ * gf_deform_output_train_sizes: host code; the bytes of the two caller-allocated regions for n rows (both 0 for n == 0, both
+ * monotone in n).  with_norm: whether the call has a post norm.  saved_bytes is 0 without one (the op is linear then: its
+ * backward needs features and Wo only), otherwise <= 520 n + 4096: the row the norm reads and its (mean, rstd).  The
+ * workspace holds one partial of dWo per block of GF_DEFORM_OUTPUT_WGRAD_ROWS rows, one partial of the vector gradients per
+ * tile of 128 rows (four a block) and, with a post norm, the [n, E] gradient before the norm.  GF_EINVAL: E != 128, an unknown
+ * mode, a post norm with GF_DEFORM_CAT, n < 0, a null result pointer.
+ *
+ * gf_deform_output_forward_train: out is BITWISE gf_deform_output_forward's at every n and in every variant.  `saved`
+ * (16-byte aligned, at least saved_bytes, opaque) is written with a post norm only and may be NULL without one.
+ *
+ * gf_deform_output_backward: from grad_out f32 [n, E] ([n, 2 E] with GF_DEFORM_CAT), features, the parameters and `saved` of
+ * the forward_train call on them; g_s = the post norm's data backward of grad_out (grad_out itself without a norm), g_y = g_s
+ * (the left half of grad_out with GF_DEFORM_CAT):
+ *   grad_features  f32 [n, E]          Wo^T g_y, written in full
+ *   grad_instance  f32 [n, E] or NULL  g_s with GF_DEFORM_ADD; the right half of grad_out bit for bit with GF_DEFORM_CAT;
+ *                                      must be NULL with GF_DEFORM_NONE
+ *   grad_residual  f32 [n, E] or NULL  g_s (not with GF_DEFORM_CAT)
+ *   grad_params    HOST table of 4 device pointers laid out like params: dWo = sum g_y x^T, dbo = sum g_y, d(norm weight) =
+ *                  sum grad_out x^, d(norm bias) = sum grad_out -- each STORED, never accumulated; a NULL slot is skipped
+ *   workspace      16-byte aligned, at least workspace_bytes; scratch, nothing survives the call
+ * Three kernels -- the data backward, the weight gradient on the matrix cores per block of rows, one fixed-order sum of the
+ * partials -- no atomics, bitwise reproducible; a row of the three per-row outputs does not depend on n or on the row's
+ * position; exact fp32 products; no host synchronisation, no allocation: graph-capturable.  GF_EINVAL before any HIP call, the
+ * message naming the offending value, for everything gf_deform_output_forward refuses, a null or misaligned saved region or
+ * workspace where one is needed, a gradient slot that is misaligned, grad_instance with GF_DEFORM_NONE, grad_residual with
+ * GF_DEFORM_CAT, an output that aliases an input, the saved region, the workspace or another output; GF_EWORKSPACE for a
+ * region shorter than the query says.  n == 0: GF_OK, the parameter gradients zero-filled. */
+#define GF_DEFORM_OUTPUT_WGRAD_ROWS 512
+int gf_deform_output_train_sizes(int n, int E, int mode, int with_norm, size_t *saved_bytes, size_t *workspace_bytes);
+int gf_deform_output_forward_train(int n, int E, int mode, const float *features, const float *instance_feature,
+                                   const void *const *params, const float *residual, float *out, void *saved, size_t saved_bytes,
+                                   void *stream);
+int gf_deform_output_backward(int n, int E, int mode, const float *features, const void *const *params, const void *saved,
+                              const float *grad_out, float *grad_features, float *grad_instance, float *grad_residual,
+                              void *const *grad_params, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */
