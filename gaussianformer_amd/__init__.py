@@ -5,7 +5,7 @@ behind a C-ABI shared library (``include/gf_hip.h``); this package is the Python
 that mirrors the reference's operator API."""
 __version__ = "0.1.0"
 
-__all__ = ["GaussianOccEncoder", "GaussianHead"]
+__all__ = ["GaussianOccEncoder", "GaussianHead", "deformable_logits_autograd", "DeformLogitsFunction"]
 
 
 def __getattr__(name):
@@ -16,4 +16,7 @@ def __getattr__(name):
     if name == "GaussianHead":
         from .head import GaussianHead
         return GaussianHead
+    if name in ("deformable_logits_autograd", "DeformLogitsFunction"):
+        from . import deformable_block
+        return getattr(deformable_block, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

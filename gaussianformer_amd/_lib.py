@@ -38,6 +38,7 @@ GF_ANCHOR_EMBED_DIMS, GF_ANCHOR_EMBED_MAX_S, GF_ANCHOR_EMBED_PARAMS, GF_ANCHOR_E
 GF_FFN_PARAMS, GF_FFN_EMBED_DIMS, GF_FFN_HIDDEN, GF_FFN_WGRAD_ROWS, GF_FFN_CHUNK_ROWS = 10, 128, 512, 512, 32768
 GF_DEFORM_EMBED_DIMS, GF_DEFORM_MAX_LEARNED, GF_DEFORM_LOGITS_PARAMS, GF_DEFORM_OUTPUT_PARAMS, GF_DEFORM_OUTPUT_WGRAD_ROWS = 128, 32, 4, 4, 512
 GF_DEFORM_NONE, GF_DEFORM_ADD, GF_DEFORM_CAT = 0, 1, 2
+GF_DEFORM_LOGITS_WGRAD_ROWS = 512
 GF_PATH_EXACT_TILE, GF_PATH_MATRIX_CORE, GF_PATH_ARBITRARY, GF_PATH_MATRIX_CORE_WAVE, GF_PATH_MATRIX_CORE_PAIR, GF_PATH_MATRIX_CORE_SOLO = 0, 1, 2, 3, 4, 5
 GF_PATHS_MATRIX_CORE = (GF_PATH_MATRIX_CORE, GF_PATH_MATRIX_CORE_WAVE, GF_PATH_MATRIX_CORE_PAIR, GF_PATH_MATRIX_CORE_SOLO)
 GF_STATE_NOT_DENSE, GF_STATE_PATH, GF_STATE_VERDICT, GF_STATE_GENERATION, GF_STATE_ROWS, GF_STATE_WORDS = 0, 1, 2, 3, 4, 5
@@ -134,6 +135,8 @@ SIGNATURES = {
     "gf_deform_output_train_sizes": (_i, [_i] * 4 + [_vp] * 2),
     "gf_deform_output_forward_train": (_i, [_i] * 3 + [_vp] * 5 + [_vp, _sz, _vp]),
     "gf_deform_output_backward": (_i, [_i] * 3 + [_vp] * 8 + [_vp, _sz, _vp]),
+    "gf_deform_logits_train_sizes": (_i, [_i] * 4 + [_vp] * 2),
+    "gf_deform_logits_backward": (_i, [_i] * 4 + [_vp] * 8 + [_vp, _sz, _vp]),
     "gf_profile_enable": (_i, [_i]),
     "gf_profile_stride": (_i, [_i]),
     "gf_profile_read": (_i, [_vp, _i]),

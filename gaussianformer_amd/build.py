@@ -10,7 +10,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_NAME = "libgf_hip.so"
-SOURCES = ["gf_api.hip", "splat_fwd.hip", "splat_bwd.hip", "splat_bwd_mfma.hip", "daf.hip", "gaussian_prepare.hip", "daf_prepare.hip", "daf_fused.hip", "head_labels.hip", "head_geosem.hip", "feature_format.hip", "subm_conv.hip", "key_points.hip", "fps.hip", "occ_loss.hip", "lifter.hip", "deform_conv.hip", "refine.hip", "refine_mlp.hip", "refine_mlp_train.hip", "anchor_embed.hip", "ffn.hip", "ffn_train.hip", "deform_dense.hip", "deform_dense_train.hip", "miou.hip"]
+SOURCES = ["gf_api.hip", "splat_fwd.hip", "splat_bwd.hip", "splat_bwd_mfma.hip", "daf.hip", "gaussian_prepare.hip", "daf_prepare.hip", "daf_fused.hip", "head_labels.hip", "head_geosem.hip", "feature_format.hip", "subm_conv.hip", "key_points.hip", "fps.hip", "occ_loss.hip", "lifter.hip", "deform_conv.hip", "refine.hip", "refine_mlp.hip", "refine_mlp_train.hip", "anchor_embed.hip", "ffn.hip", "ffn_train.hip", "deform_dense.hip", "deform_dense_train.hip", "deform_logits_train.hip", "miou.hip"]
 HEADERS = ["gf_common.hpp", "gf_labels.hpp", "gf_wave.hpp", "gf_math.hpp", "gf_daf.hpp", "gf_rows.hpp", "gf_rows_bwd.hpp", "gf_ffn.hpp", "gf_deform.hpp", "gf_refine.hpp", "splat_mfma.hpp", os.path.join("..", "..", "include", "gf_hip.h")]
 ARCH = "gfx950"
 # -munsafe-fp-atomics only for the translation units that issue float atomics (hardware fp32 adds without a CAS loop); the

@@ -5,8 +5,10 @@
 with the add or the cat behind it.  ``gf_deform_logits_forward`` and ``gf_deform_output_forward`` (include/gf_hip.h, DESIGN.md
 §3.13e) are one launch each: an inference block is four launches and the ``[A, 128]`` sum never reaches memory.  The back end has
 a native training step as well (``deformable_output_autograd``: ``gf_deform_output_forward_train`` / ``gf_deform_output_backward``,
-DESIGN.md §3.13f), which the module takes with the opt-in ``native_training``; without it training, dropout and everything the
-native ops do not cover run the module's own torch layers around ``deformable_fused``."""
+DESIGN.md §3.13f), which the module takes with the opt-in ``native_training``, and so has the front end
+(``deformable_logits_autograd``: ``gf_deform_logits_forward`` / ``gf_deform_logits_backward``) with the opt-in
+``native_front_training``; without them training, dropout and everything the native ops do not cover run the module's own
+torch layers around ``deformable_fused``."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -43,30 +45,118 @@ def _refuse_autograd(name, tensors):
             "deformable_fused)")
 
 
-def deformable_logits(instance_feature, anchor_embed, weights_fc, learnable_fc=None):
-    """``(raw [..., Nw], learned [..., K, 3] | None)`` in one launch, on any leading shape: ``raw = weights_fc(instance_feature +
-    anchor_embed)`` (deformable_module.py:250-262; ``anchor_embed`` may be ``None``) and ``learned = learnable_fc(
-    instance_feature)`` (:59-63) as ``key_points`` takes it.  ``weights_fc`` / ``learnable_fc``: an ``nn.Linear`` or a ``(weight,
-    bias)`` pair, read in place at every call.  Forward only: inputs that need autograd are refused."""
+def _logits_args(weights_fc, learnable_fc):
+    """``(ww, bw, wl, bl)`` of a logits call, the pairs checked (``wl``, ``bl``: ``None`` without ``learnable_fc``)."""
     ww, bw = _pair(weights_fc, "weights_fc")
     wl, bl = _pair(learnable_fc, "learnable_fc")
-    _refuse_autograd("deformable_logits", [instance_feature, anchor_embed, ww, bw, wl, bl])
+    return ww, bw, wl, bl
+
+
+def _logits_shapes(name, instance_feature, anchor_embed, ww, bw, wl, bl):
+    """``(f [n, E], e [n, E] | None, leading shape, E, K3, Nw)`` as the library reads them, the shapes checked."""
     _lib.require_gpu(instance_feature, anchor_embed, ww, bw, wl, bl)
     E = instance_feature.shape[-1]
     Nw, K3 = ww.shape[0], 0 if wl is None else wl.shape[0]
     if ww.shape != (Nw, E) or bw.shape != (Nw,) or (wl is not None and (wl.shape != (K3, E) or bl.shape != (K3,) or K3 % 3)):
-        raise ValueError(f"deformable_logits: instance_feature [..., {E}] against weights_fc {tuple(ww.shape)}, {tuple(bw.shape)}"
+        raise ValueError(f"{name}: instance_feature [..., {E}] against weights_fc {tuple(ww.shape)}, {tuple(bw.shape)}"
                          + ("" if wl is None else f" and learnable_fc {tuple(wl.shape)}, {tuple(bl.shape)}"))
     if anchor_embed is not None and anchor_embed.shape != instance_feature.shape:
-        raise ValueError(f"deformable_logits: anchor_embed {tuple(anchor_embed.shape)} is not {tuple(instance_feature.shape)}")
-    lead = instance_feature.shape[:-1]
+        raise ValueError(f"{name}: anchor_embed {tuple(anchor_embed.shape)} is not {tuple(instance_feature.shape)}")
     f, e = _lib.aligned(instance_feature).reshape(-1, E), None if anchor_embed is None else _lib.aligned(anchor_embed).reshape(-1, E)
+    return f, e, instance_feature.shape[:-1], E, K3, Nw
+
+
+def _logits_launch(f, e, E, K3, Nw, table):
+    """``(raw [n, Nw], learned [n, K3] | None)`` of ``gf_deform_logits_forward``."""
     n = f.shape[0]
-    table, held = _lib.param_table([wl, bl, ww, bw], _lib.GF_DEFORM_LOGITS_PARAMS)
     raw = torch.empty(n, Nw, dtype=f32, device=f.device)
     learned = torch.empty(n, K3, dtype=f32, device=f.device) if K3 else None
     _lib.call("gf_deform_logits_forward", f.device, n, E, K3, Nw, f, e, table, learned, raw)
-    return raw.view(*lead, Nw), None if learned is None else learned.view(*lead, K3 // 3, 3)
+    return raw, learned
+
+
+def _logits_views(raw, learned, lead):
+    return raw.view(*lead, raw.shape[-1]), None if learned is None else learned.view(*lead, learned.shape[-1] // 3, 3)
+
+
+def deformable_logits(instance_feature, anchor_embed, weights_fc, learnable_fc=None):
+    """``(raw [..., Nw], learned [..., K, 3] | None)`` in one launch, on any leading shape: ``raw = weights_fc(instance_feature +
+    anchor_embed)`` (deformable_module.py:250-262; ``anchor_embed`` may be ``None``) and ``learned = learnable_fc(
+    instance_feature)`` (:59-63) as ``key_points`` takes it.  ``weights_fc`` / ``learnable_fc``: an ``nn.Linear`` or a ``(weight,
+    bias)`` pair, read in place at every call.  Forward only: inputs that need autograd are refused
+    (``deformable_logits_autograd`` takes them)."""
+    ww, bw, wl, bl = _logits_args(weights_fc, learnable_fc)
+    _refuse_autograd("deformable_logits", [instance_feature, anchor_embed, ww, bw, wl, bl])
+    return _logits_inference("deformable_logits", instance_feature, anchor_embed, ww, bw, wl, bl)
+
+
+def _logits_inference(name, instance_feature, anchor_embed, ww, bw, wl, bl):
+    """The inference launch; the callers have settled autograd."""
+    f, e, lead, E, K3, Nw = _logits_shapes(name, instance_feature, anchor_embed, ww, bw, wl, bl)
+    table, held = _lib.param_table([wl, bl, ww, bw], _lib.GF_DEFORM_LOGITS_PARAMS)
+    return _logits_views(*_logits_launch(f, e, E, K3, Nw, table), lead)
+
+
+def logits_train_sizes(n, K3, Nw, E=E_NATIVE):
+    """``(saved_bytes, workspace_bytes)`` of the front's training step on ``n`` rows (``gf_deform_logits_train_sizes``);
+    ``saved_bytes`` is 0: the op is linear."""
+    return _lib.train_sizes("gf_deform_logits_train_sizes", n, E, K3, Nw)
+
+
+class DeformLogitsFunction(torch.autograd.Function):
+    """``raw, learned = DeformLogitsFunction.apply(instance_feature, anchor_embed, ww, bw, wl, bl)`` (``None`` for an absent
+    tensor; ``learned`` is ``None`` without ``wl``): the forward is ``gf_deform_logits_forward`` -- the op is linear, nothing is
+    saved but the inputs themselves -- and ``gf_deform_logits_backward`` returns the gradients of ``instance_feature``,
+    ``anchor_embed`` and the four parameters -- of those that require one; the others get ``None`` and the library a NULL slot.
+    Once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, instance_feature, anchor_embed, ww, bw, wl, bl):
+        f, e, lead, E, K3, Nw = _logits_shapes("deformable_logits_autograd", instance_feature, anchor_embed, ww, bw, wl, bl)
+        params = [wl, bl, ww, bw]
+        table, held = _lib.param_table(params, _lib.GF_DEFORM_LOGITS_PARAMS)
+        raw, learned = _logits_launch(f, e, E, K3, Nw, table)
+        ctx.save_for_backward(f, e, *held)
+        ctx.shape = (lead, E, K3, Nw, instance_feature.dtype, None if anchor_embed is None else anchor_embed.dtype,
+                     [None if p is None else p.dtype for p in params])
+        ctx.set_materialize_grads(False)     # an output nobody used: a NULL cotangent, not a tensor of zeros
+        return _logits_views(raw, learned, lead)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_raw, grad_learned):
+        f, e, *held = ctx.saved_tensors
+        lead, E, K3, Nw, f_dtype, e_dtype, dtypes = ctx.shape
+        n, need = f.shape[0], ctx.needs_input_grad
+        slot = (4, 5, 2, 3)      # the table's order (wl, bl, ww, bw) in apply()'s arguments
+        params, grads, it = [], [], iter(held)
+        for i, d in enumerate(dtypes):
+            params.append(None if d is None else next(it))
+            grads.append(torch.empty_like(params[-1]) if d is not None and need[slot[i]] else None)
+        table, _ = _lib.param_table(params, _lib.GF_DEFORM_LOGITS_PARAMS)
+        _, work_bytes = logits_train_sizes(n, K3, Nw, E)
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=f.device) if any(g is not None for g in grads) else None
+        new = lambda: torch.empty(n, E, dtype=f32, device=f.device)
+        grad_f = new() if need[0] else None
+        grad_e = new() if e is not None and need[1] else None
+        gr = None if grad_raw is None else _lib.aligned(grad_raw).reshape(n, Nw)
+        gl = None if grad_learned is None or K3 == 0 else _lib.as_arg(grad_learned).reshape(n, K3)
+        _lib.call("gf_deform_logits_backward", f.device, n, E, K3, Nw, f, e, table, gl, gr, grad_f, grad_e,
+                  _lib.out_table(grads, _lib.GF_DEFORM_LOGITS_PARAMS), work, work_bytes if work is not None else 0)
+        wl_g, bl_g, ww_g, bw_g = (None if g is None else g.to(d) for g, d in zip(grads, dtypes))
+        return (None if grad_f is None else grad_f.view(*lead, E).to(f_dtype),
+                None if grad_e is None else grad_e.view(*lead, E).to(e_dtype), ww_g, bw_g, wl_g, bl_g)
+
+
+def deformable_logits_autograd(instance_feature, anchor_embed, weights_fc, learnable_fc=None):
+    """``deformable_logits`` with a native backward: the same arguments and checks, the same bits, and ``raw``
+    and ``learned`` carry the graph of ``DeformLogitsFunction``, so ``instance_feature``, ``anchor_embed`` and each of the four
+    parameters that requires grad receives its gradient (the others ``None``).  With nothing that needs autograd (or under
+    ``torch.no_grad()``) it is ``deformable_logits``."""
+    ww, bw, wl, bl = _logits_args(weights_fc, learnable_fc)
+    if not _lib.needs_grad([instance_feature, anchor_embed, ww, bw, wl, bl]):
+        return _logits_inference("deformable_logits_autograd", instance_feature, anchor_embed, ww, bw, wl, bl)
+    return DeformLogitsFunction.apply(instance_feature, anchor_embed, ww, bw, wl, bl)
 
 
 def _output_args(name, features, output_proj, instance_feature, residual_mode, residual, norm):
@@ -206,10 +296,19 @@ class DeformableFeatureAggregation(nn.Module):
     the add or the cat, ``residual=`` and ``norm=`` in one saving launch with a native backward -- under
     the conditions of the native route that concern the back end: ``embed_dims == 128``, fp32 GPU tensors, a known
     ``residual_mode``, eval mode or ``proj_drop.p == 0``, an affine ``LayerNorm`` with ``eps = 1e-5``.  The front end
-    (``weights_fc``, ``learnable_fc``) stays on torch there."""
+    (``weights_fc``, ``learnable_fc``) stays on torch there.
+
+    ``native_front_training`` is a switch of its own for that front end, again a class attribute, off by default and not part
+    of the ``state_dict``: with it a call that needs autograd, with ``embed_dims == 128``, fp32 GPU tensors and at most 32
+    learned columns -- in train or eval mode, with any ``attn_drop``: the mask is drawn behind the front as before -- takes
+    ``raw`` and ``learned`` from ``deformable_logits_autograd`` (one launch forward, a native backward) and the
+    key points from the functional ``key_points``; ``weights_fc`` and ``learnable_fc`` do not run as modules.  The camera encoder
+    and its rows of ``weights_fc`` stay on torch (``weights_fc.weight`` then has two producers; autograd adds them).  The two
+    switches are independent; together they leave only the camera encoder on torch."""
 
     native_dense = True
     native_training = False
+    native_front_training = False
 
     def __init__(self, embed_dims=256, num_groups=8, num_levels=4, num_cams=6, proj_drop=0.0, attn_drop=0.0, kps_generator=None,
                  use_deformable_func=False, use_camera_embed=False, residual_mode="add"):
@@ -275,14 +374,24 @@ class DeformableFeatureAggregation(nn.Module):
         tensors = self._output_native(instance_feature, anchor, anchor_embed, table, residual, norm)
         return tensors is not None and _lib.needs_grad(tensors)
 
+    def _native_front_training(self, instance_feature, anchor, anchor_embed, table):
+        """Whether this call's front end runs its native training step (``native_front_training``)."""
+        if not self.native_front_training or self.embed_dims != E_NATIVE or 3 * self.kps_generator.num_learnable_pts > MAX_LEARNED:
+            return False
+        tensors = [instance_feature, anchor, anchor_embed, table, *self.parameters()]
+        if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
+            return False
+        return _lib.needs_grad(tensors)
+
     def forward(self, instance_feature, anchor, anchor_embed, feature_maps, metas, **kwargs):
         residual, norm = kwargs.get("residual"), kwargs.get("norm")
         if not (isinstance(feature_maps, (tuple, list)) and len(feature_maps) == 3 and feature_maps[1].dim() == 2):
             feature_maps = DAF.feature_maps_format(feature_maps)
         if not self._native(instance_feature, anchor, anchor_embed, feature_maps[0], residual, norm):
             native_output = self._native_training(instance_feature, anchor, anchor_embed, feature_maps[0], residual, norm)
+            native_front = self._native_front_training(instance_feature, anchor, anchor_embed, feature_maps[0])
             return self.forward_torch(instance_feature, anchor, anchor_embed, feature_maps, metas, residual=residual, norm=norm,
-                                      native_output=native_output)
+                                      native_output=native_output, native_front=native_front)
         bs, A = instance_feature.shape[:2]
         gen = self.kps_generator
         raw, learned = deformable_logits(instance_feature, anchor_embed, self.weights_fc,
@@ -298,15 +407,24 @@ class DeformableFeatureAggregation(nn.Module):
             features = deformable_fused_forward(kp, pm, wh, *feature_maps, raw_weights=raw.view(bs, A, self.num_cams, L, self.num_pts, G))
         return deformable_output(features, self.output_proj, instance_feature, self.residual_mode, residual, norm)
 
-    def forward_torch(self, instance_feature, anchor, anchor_embed, feature_maps, metas, residual=None, norm=None, native_output=False):
+    def forward_torch(self, instance_feature, anchor, anchor_embed, feature_maps, metas, residual=None, norm=None, native_output=False,
+                      native_front=False):
         """The reference's composition (:146-262) on the module's torch layers around ``deformable_fused``; ``feature_maps`` is
         the formatted triple.  ``native_output``: everything behind ``features`` is ``deformable_output_autograd`` (the caller
-        has asked ``_native_training``)."""
+        has asked ``_native_training``).  ``native_front``: ``weights_fc`` on the sum and ``learnable_fc`` are
+        ``deformable_logits_autograd`` and the key points the functional ``key_points`` (the caller has asked
+        ``_native_front_training``)."""
         bs, A = instance_feature.shape[:2]
-        kp = self.kps_generator(anchor, instance_feature)
         pm, wh = metas["projection_mat"], metas.get("image_wh")
         L, G, cams = self.num_levels, self.num_groups, self.num_cams
-        per_anchor = self.weights_fc(instance_feature + anchor_embed)
+        if native_front:
+            gen = self.kps_generator
+            per_anchor, learned = deformable_logits_autograd(instance_feature, anchor_embed, self.weights_fc,
+                                                             gen.learnable_fc if gen.num_learnable_pts > 0 else None)
+            kp = key_points(anchor, learned, gen._fix, gen.pc_range, gen.scale_range, gen.learnable_fixed_scale, gen.xyz_act, gen.scale_act)
+        else:
+            kp = self.kps_generator(anchor, instance_feature)
+            per_anchor = self.weights_fc(instance_feature + anchor_embed)
         if self.camera_encoder is not None:
             raw_cam = F.linear(self.camera_encoder(pm[:, :, :3].reshape(bs, cams, -1)), self.weights_fc.weight)
             logits = dict(raw_anchor=per_anchor.reshape(bs, A, L, self.num_pts, G), raw_cam=raw_cam.reshape(bs, cams, L, self.num_pts, G))

@@ -143,13 +143,15 @@ class GaussianOccEncoder(nn.Module):
             if hasattr(m, "init_weight"):
                 m.init_weight()
 
-    def set_native(self, training=None, fused_mlp=None, fold_training=None):
+    def set_native(self, training=None, fused_mlp=None, fold_training=None, front_training=None):
         """Sets ``native_training`` / ``fused_mlp`` on every submodule that has the attribute (``None``: left alone); returns
         ``self``.  Their defaults do not change.  ``native_training`` is an attribute of the anchor encoder, the feed-forward
         block, the refinement modules, the deformable block (its back end) and the sparse convolution block
         (``SparseConv3D``: its LayerNorm stages).  ``fold_training`` sets this encoder's attribute of that name
         and ``native_tail_training`` on every submodule that has it (``SparseConv3D``: the tail that takes the block's add and
-        norm in training); ``training=`` touches neither."""
+        norm in training); ``training=`` touches neither.  ``front_training`` sets ``native_front_training`` on
+        every submodule that has it (the deformable block's dense front) and nothing else; ``training=`` and
+        ``fold_training=`` do not touch it."""
         if fold_training is not None:
             self.fold_training = bool(fold_training)
         for m in self.modules():
@@ -157,6 +159,8 @@ class GaussianOccEncoder(nn.Module):
                 m.native_tail_training = bool(fold_training)
             if training is not None and hasattr(m, "native_training"):
                 m.native_training = bool(training)
+            if front_training is not None and hasattr(m, "native_front_training"):
+                m.native_front_training = bool(front_training)
             if fused_mlp is not None and hasattr(m, "fused_mlp"):
                 m.fused_mlp = bool(fused_mlp)
         return self

@@ -1189,6 +1189,40 @@ int gf_deform_output_backward(int n, int E, int mode, const float *features, con
                               const float *grad_out, float *grad_features, float *grad_instance, float *grad_residual,
                               void *const *grad_params, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The training step of the dense front.  The op is linear, so nothing is saved: the forward of the
+ * training step IS gf_deform_logits_forward.  Here are its backward and the size query; K3, Nw, E == 128, the 4-pointer params
+ * table and embed == NULL are the forward's.
+ *
+ * gf_deform_logits_train_sizes: host code.  saved_bytes is always 0 (kept so that the one size-query shape serves this op
+ * too); workspace_bytes holds one partial of dWw and dWl per block of GF_DEFORM_LOGITS_WGRAD_ROWS rows ((Nw + 32) x 128
+ * floats, Nw x 128 with K3 = 0) and one partial of the bias gradients per tile of 128 rows; 0 for n == 0, monotone in n and Nw.
+ * GF_EINVAL: E != 128, K3 or Nw outside the forward's, n < 0, a null result pointer.
+ *
+ * gf_deform_logits_backward: with g_l = grad_learned f32 [n, K3] and g_r = grad_raw f32 [n, Nw], either NULL for a zero
+ * cotangent (its weight and bias gradients, where asked for, are stored as zeros, its term is left out of the data chain):
+ *   grad_embed    f32 [n, E] or NULL   g_r Ww = (G0 + G1) + .., Gq the accumulator chain of raw's columns 128 q .. 128 q + 127
+ *   grad_feature  f32 [n, E] or NULL   g_r Ww + g_l Wl in ONE fixed order: ((G0 + G1) + ..) + L, L the learned columns'
+ *                                      chain -- bitwise grad_embed where g_l is NULL or K3 = 0; written in full whenever given
+ *   grad_params   HOST table of 4 device pointers laid out like params: dWl = g_l^T f [K3, E], dbl = sum over rows of g_l,
+ *                 dWw = g_r^T (f + e) [Nw, E] with the sum formed in registers as the forward forms it, dbw = sum over rows of
+ *                 g_r -- each STORED, never accumulated; a NULL slot is a gradient nobody asked for and is skipped
+ *   workspace     16-byte aligned, at least workspace_bytes, needed when n > 0 and a parameter gradient is asked for; scratch
+ * Three kernels -- the data backward with the per-tile bias partials (column sums in double), the weight gradients on the
+ * matrix cores per block of rows and group of 128 gradient columns, one fixed-order sum of the partials -- no atomics,
+ * bitwise reproducible; a row of grad_feature / grad_embed does not depend on n or on the row's position; a NaN in a row of
+ * a cotangent or of feature stays out of every other row's data gradients; exact fp32 products; no host synchronisation, no
+ * allocation: graph-capturable.
+ * Every pointer is 16-byte aligned, grad_learned and the gradients of learnable_fc only 4 (a row of K3 floats).  GF_EINVAL
+ * before any HIP call, the message naming the offending value: everything gf_deform_logits_forward refuses of the sizes and
+ * the table, grad_learned with K3 = 0, a gradient slot for a parameter that is absent, a misaligned pointer, a null or
+ * misaligned workspace where one is needed, an output that aliases an input, the workspace or an earlier output;
+ * GF_EWORKSPACE for a workspace shorter than the query says.  n == 0: GF_OK, the parameter gradients asked for zero-filled. */
+#define GF_DEFORM_LOGITS_WGRAD_ROWS 512
+int gf_deform_logits_train_sizes(int n, int E, int K3, int Nw, size_t *saved_bytes, size_t *workspace_bytes);
+int gf_deform_logits_backward(int n, int E, int K3, int Nw, const float *feature, const float *embed, const void *const *params,
+                              const float *grad_learned, const float *grad_raw, float *grad_feature, float *grad_embed,
+                              void *const *grad_params, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Time only every `every`-th dominant-kernel launch (default 1): the two event records cost a few
  * microseconds of stream time each, so sampling keeps the timed region close to the un-instrumented one. */
 int gf_profile_stride(int every);
