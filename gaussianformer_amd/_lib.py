@@ -5,6 +5,7 @@ raised.  Tensors cross the boundary as raw device pointers + sizes; the stream i
 current HIP stream.
 """
 import collections
+import contextlib
 import ctypes
 import os
 
@@ -28,7 +29,7 @@ GF_EXACT_FP32 = 256
 GF_RECORDS_VALID = 512
 GF_PREPARE_BACKWARD = 1024
 GF_WORKSPACE_ZEROED = 2048
-GF_OCC_PROB, GF_OCC_MASK, GF_OCC_LOVASZ_IGNORE, GF_OCC_IGNORE_EMPTY, GF_OCC_NO_LOVASZ, GF_OCC_MAX_LAYERS = 1, 2, 4, 8, 16, 8
+GF_OCC_PROB, GF_OCC_MASK, GF_OCC_LOVASZ_IGNORE, GF_OCC_IGNORE_EMPTY, GF_OCC_NO_LOVASZ, GF_OCC_SCAL, GF_OCC_MAX_LAYERS = 1, 2, 4, 8, 16, 32, 8
 GF_LIFT_MAX_BINS, GF_LIFT_MAX_ANCHORS, GF_PIXEL_LOSS_SOFTMAX, GF_PIXEL_LOSS_SIGMOID = 256, 8, 1, 2
 GF_DCN_MAX_KERNEL, GF_DCN_CHANNEL_GRANULE = 7, 32
 GF_MIOU_TARGETS_U8, GF_MIOU_FILTER_MINMAX, GF_MIOU_REMAP, GF_MIOU_MAX_CLASSES, GF_MIOU_MAX_D = 1, 2, 4, 32, 64
@@ -105,6 +106,8 @@ SIGNATURES = {
     "gf_occ_loss_scratch_bytes": (_sz, [_i] * 4),
     "gf_occ_loss_forward": (_i, [_i] * 4 + [_vp, _ll, _ll] + [_vp] * 3 + [_f, _f] + [_i] * 3 + [_vp, _vp, _sz, _vp, _sz, _vp]),
     "gf_occ_loss_backward": (_i, [_i] * 4 + [_vp, _ll, _ll] + [_vp] * 3 + [_f, _f] + [_i] * 3 + [_vp, _vp, _vp, _sz, _vp]),
+    "gf_occ_loss_scal_forward": (_i, [_i] * 4 + [_vp, _ll, _ll] + [_vp] * 3 + [_f] * 4 + [_i] * 3 + [_vp, _vp, _sz, _vp, _sz, _vp]),
+    "gf_occ_loss_scal_backward": (_i, [_i] * 4 + [_vp, _ll, _ll] + [_vp] * 3 + [_f] * 4 + [_i] * 3 + [_vp, _vp, _vp, _sz, _vp]),
     "gf_miou_workspace_size": (_sz, [_ll, _i, _i]),
     "gf_miou_step": (_i, [_ll, _i, _i] + [_vp] * 3 + [_i, _vp, _i, _i] + [_vp, _vp] + [_vp, _sz, _vp]),
     "gf_miou_step_logits": (_i, [_ll, _i, _i, _i, _i] + [_vp, _vp, _f] + [_vp, _vp] + [_i, _vp, _i, _i] + [_vp, _vp] + [_vp, _sz, _vp]),
@@ -163,6 +166,29 @@ def load():
     if lib.gf_abi_version() != GF_ABI_VERSION:
         raise RuntimeError(f"libgf_hip.so ABI {lib.gf_abi_version()} != expected {GF_ABI_VERSION}; rebuild")
     _lib = lib
+    return lib
+
+
+@contextlib.contextmanager
+def routed_to(other):
+    """Inside the block ``load()`` and ``call()`` use ``other``, another build of the library with ``SIGNATURES`` applied to
+    the entry points it has (``tools/bench_loss.py --parent-lib`` times a parent commit's build this way)."""
+    global _lib
+    own = load()
+    _lib = other
+    try:
+        yield other
+    finally:
+        _lib = own
+
+
+def load_other(path):
+    """Another build of the library, or of some of its entry points, for ``routed_to``: not cached, no ABI check."""
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
     return lib
 
 

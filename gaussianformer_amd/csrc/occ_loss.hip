@@ -17,6 +17,10 @@
 //             reference), per-tile partial dot products and the derivative per (layer, compacted voxel, class)
 //   finalise  one workgroup sums every partial in a fixed order (no float atomics: the loss is bitwise reproducible)
 // Backward: one thread per (voxel, layer) writes its gradient row in the input's layout; every element has one producer.
+// With GF_OCC_SCAL (gf_occ_loss_scal_*) the scene-class affinity terms sem_scal / geo_scal (loss/occupancy_loss.py:185-268) ride
+// along in instantiations of main, finalise and backward of their own: main adds per-workgroup column sums S_c, N_c, T_c of
+// the rows it holds; scal_sums adds them over the workgroups; finalise evaluates the terms and leaves a_c, b_c; the backward
+// adds a_c + b_c [y = c] before its softmax Jacobian.  The instantiations without the terms are the kernels as they were.
 #include "gf_common.hpp"
 
 namespace gf {
@@ -58,11 +62,24 @@ struct OccWs {
     double *lov_part;  // [L*C][T]
 };
 
+// the sections of the scene-class affinity terms (GF_OCC_SCAL), carved behind the others: one of the workspace, two of the scratch
+struct OccScalWs {
+    float *ab;         // [L][2][C]   d loss_l / d S_c and d loss_l / d N_c, weights and 1/count folded in
+    double *sn_part;   // [L][2C][NB] per voxel block: S_c = sum of p_c over V, then N_c = the same over the voxels labelled c
+    int *t_part;       // [C][NB]     voxels of V labelled c per voxel block
+    double *sums;      // [L*2C + C]  the partials summed over the voxel blocks: S_c, N_c per layer, then T_c (exact in a double)
+    float sem_w, geo_w;
+};
+// the kernels that have an instantiation with these terms take the sections as a parameter pack: empty without them, so that
+// instantiation's arguments and code are those of the kernel without the terms
+__device__ __forceinline__ const OccScalWs &scal_ws(const OccScalWs &sw) { return sw; }
+
 inline int num_blocks(int N) { return (N + kVox - 1) / kVox; }
 inline int num_tiles(int N) { return (N + kTile - 1) / kTile; }
 
 // the sections of both regions (null for a null base) and, where asked for, the regions' sizes
-inline OccWs carve(void *workspace, void *scratch, int L, int N, size_t *workspace_bytes = nullptr, size_t *scratch_bytes = nullptr)
+inline OccWs carve(void *workspace, void *scratch, int L, int N, size_t *workspace_bytes = nullptr, size_t *scratch_bytes = nullptr,
+                   OccScalWs *scal = nullptr)
 {
     const size_t S = (size_t)L * kC, NB = num_blocks(N), T = num_tiles(N);
     OccWs ws;
@@ -81,6 +98,12 @@ inline OccWs carve(void *workspace, void *scratch, int L, int N, size_t *workspa
     ws.tot = b.take<int>(S * 256);
     ws.fgt = b.take<int>(S * T);
     ws.lov_part = b.take<double>(S * T);
+    if (scal) {
+        scal->ab = a.take<float>(2 * S);
+        scal->sn_part = b.take<double>(2 * S * NB);
+        scal->t_part = b.take<int>(kC * NB);
+        scal->sums = b.take<double>(2 * S + kC);
+    }
     if (workspace_bytes) *workspace_bytes = a.bytes();
     if (scratch_bytes) *scratch_bytes = b.bytes();
     return ws;
@@ -223,8 +246,42 @@ __device__ __forceinline__ void load_probs(const OccParams &a, const float *pred
 // float(1e-6) and float(1 - 1e-6): torch.clamp's bounds on an fp32 tensor
 constexpr float kProbLo = (float)1e-6, kProbHi = (float)(1.0 - 1e-6);
 
-__global__ void __launch_bounds__(kVox) gf_occ_main_kernel(OccParams a, OccPreds preds, OccWs ws)
+// Column sums of the block's rows of p in the tile (zero outside V; ylds = the label, -1 outside V), in a fixed order: lanes
+// 8c .. 8c + 7 take class c, lane j of them the rows j, j + 8, ..., summed in row order in double; the eight are then added by a
+// butterfly, which gives every lane the same bits.
+__device__ __forceinline__ void scal_block_sums(const float *tile, const int *ylds, int l, const OccScalWs &sw)
 {
+    const int c = threadIdx.x >> 3, seg = threadIdx.x & 7, NB = gridDim.x;
+    double s = 0.0, sy = 0.0;
+    int t = 0;
+    if (c < kC)
+#pragma unroll
+        for (int k = 0; k < kVox / 8; ++k) {
+            const int r = k * 8 + seg;
+            const float pv = tile[r * kC + c];
+            const bool fg = ylds[r] == c;
+            s += (double)pv;
+            sy += fg ? (double)pv : 0.0;
+            t += fg ? 1 : 0;
+        }
+#pragma unroll
+    for (int d = 4; d > 0; d >>= 1) {
+        s += __shfl_xor(s, d, 64);
+        sy += __shfl_xor(sy, d, 64);
+        t += __shfl_xor(t, d, 64);
+    }
+    if (c < kC && seg == 0) {
+        sw.sn_part[((size_t)l * 2 * kC + c) * NB + blockIdx.x] = s;
+        sw.sn_part[((size_t)l * 2 * kC + kC + c) * NB + blockIdx.x] = sy;
+        if (l == 0) sw.t_part[(size_t)c * NB + blockIdx.x] = t;
+    }
+}
+
+// Scal = OccScalWs: with the affinity terms' block sums; empty: without (the instantiation of gf_occ_loss_forward)
+template <class... Scal>
+__global__ void __launch_bounds__(kVox) gf_occ_main_kernel(OccParams a, OccPreds preds, OccWs ws, Scal... sw_)
+{
+    constexpr bool kScal = sizeof...(Scal) != 0;
     __shared__ double red[kVox];
     __shared__ int lds[kVox / 64];
     __shared__ float tile[kVox * kC];
@@ -263,6 +320,19 @@ __global__ void __launch_bounds__(kVox) gf_occ_main_kernel(OccParams a, OccPreds
             const float e = fabsf((fg ? 1.f : 0.f) - p[c]);
             ws.keys[0][((size_t)l * kC + c) * N + gpos] = make_uint2(~__float_as_uint(e), (unsigned)gpos | (fg ? 0x80000000u : 0u));
         }
+    }
+    if constexpr (kScal) {
+        // every thread puts its row of p back into its own row of the tile (it alone has read that row)
+        __shared__ int ylds[kVox];
+#pragma unroll
+        for (int c = 0; c < kC; ++c) tile[threadIdx.x * kC + c] = 0.f;
+        if (v.ce) {
+#pragma unroll
+            for (int c = 0; c < kC; ++c) tile[threadIdx.x * kC + c] = p[c];
+        }
+        ylds[threadIdx.x] = v.ce ? v.y : -1;
+        __syncthreads();
+        scal_block_sums(tile, ylds, l, scal_ws(sw_...));
     }
     const double sn = block_sum256(num, red);
     __syncthreads();
@@ -436,9 +506,113 @@ __global__ void __launch_bounds__(256) gf_occ_lovasz_kernel(int N, int T, const 
     if (tid == 0) ws.lov_part[(size_t)s * T + t] = sum;
 }
 
-__global__ void __launch_bounds__(kFin) gf_occ_finalise_kernel(OccParams a, int NB, int T, OccWs ws, float *loss)
+// ---- scene-class affinity terms (sem_scal_loss, geo_scal_loss of loss/occupancy_loss.py:185-268) from the sums of one layer
+
+// binary_cross_entropy_with_logits(inverse_sigmoid(x), 1) on an fp32 scalar and its derivative -1 / x' at the shifted x'.  The
+// reference's two while loops, each cut off after kScalSteps steps: a ratio of probabilities needs three at the most, and one
+// that is still out of range then (inputs that are no probabilities) is reported as bad instead of looping on.
+constexpr int kScalSteps = 8;
+
+__device__ __forceinline__ float scal_f(float x, float &dfdx, bool &bad)
 {
+    const float hi = (float)(1.0 - 1e-5), eps = 1e-5f;
+    for (int i = 0; i < kScalSteps && x >= hi; ++i) x -= eps;
+    for (int i = 0; i < kScalSteps && x < eps; ++i) x += eps;
+    if (!(x >= eps && x < hi)) bad = true;        // NaN included
+    dfdx = -1.f / x;
+    const float u = logf(1.f / x - 1.f);          // -inverse_sigmoid(x); the loss is softplus(u)
+    return fmaxf(u, 0.f) + log1pf(expf(-fabsf(u)));
+}
+
+// Thread i of a layer's C: i < C - 1 evaluates class i's precision, recall and specificity (0 for a class absent from V), i = C - 1
+// the geo term of class `empty`.  From S_c, N_c (sums: [2C] doubles, each rounded to fp32 once), T_c and |V|.  Returns the
+// term and, unweighted, its derivatives by S and N of its class.
+__device__ __forceinline__ float scal_class_term(int i, const double *sums, const int *tc, int V, int empty, float &da, float &db,
+                                                 bool &bad)
+{
+    const float eps = 1e-5f;
+    float d;
+    da = db = 0.f;
+    if (i < kC - 1) {
+        if (tc[i] == 0) return 0.f;
+        const float S = (float)sums[i], Ny = (float)sums[kC + i], Tf = (float)tc[i];
+        float cls = 0.f;
+        if (S > 0.f) {
+            const float den = S + eps, x = Ny / den;
+            cls += scal_f(x, d, bad);
+            da -= d * x / den;
+            db += d / den;
+        }
+        {
+            const float den = Tf + eps, x = Ny / den;
+            cls += scal_f(x, d, bad);
+            db += d / den;
+        }
+        if (V - tc[i] > 0) {
+            const float R = (float)(V - tc[i]), den = R + eps, x = (R - (S - Ny)) / den;
+            cls += scal_f(x, d, bad);
+            da -= d / den;
+            db += d / den;
+        }
+        return cls;
+    }
+    const float S = (float)sums[empty], Ny = (float)sums[kC + empty], Tf = (float)tc[empty], R = (float)(V - tc[empty]);
+    const float I = R - (S - Ny), d1 = ((float)V - S) + eps, d2 = R + eps, d3 = Tf + eps;
+    const float x1 = I / d1, x2 = I / d2, x3 = Ny / d3;
+    float f1, f2, f3;
+    float geo = scal_f(x1, f1, bad);
+    geo += scal_f(x2, f2, bad);
+    geo += scal_f(x3, f3, bad);
+    da = f1 * (x1 - 1.f) / d1 - f2 / d2;
+    db = f1 / d1 + f2 / d2 + f3 / d3;
+    return geo;
+}
+
+// finalise's LDS for the terms: only the instantiation with them refers to it
+struct ScalLds {
+    double sums[GF_OCC_MAX_LAYERS * 2 * kC];   // S_c, N_c per layer
+    int tc[kC];                                // T_c
+    float term[GF_OCC_MAX_LAYERS][kC];         // per layer: the sem term of the classes 0 .. C-2, then geo
+    float geo_d[GF_OCC_MAX_LAYERS][2];         // d geo / d S_e, d geo / d N_e
+    double scal[GF_OCC_MAX_LAYERS];            // sem_w sem + geo_w geo
+    int bad;
+};
+__device__ __forceinline__ ScalLds &scal_lds()
+{
+    __shared__ ScalLds lds;
+    return lds;
+}
+
+// One workgroup per sum: thread t adds the voxel blocks t, t + 256, ... in that order, then the workgroup's fixed tree.
+__global__ void __launch_bounds__(256) gf_occ_scal_sums_kernel(int NB, int nsn, OccScalWs sw)
+{
+    __shared__ double red[256];
+    const int j = blockIdx.x;
+    double v = 0.0;
+    if (j < nsn) {
+        const double *src = sw.sn_part + (size_t)j * NB;
+        for (int b = threadIdx.x; b < NB; b += 256) v += src[b];
+    } else {
+        const int *src = sw.t_part + (size_t)(j - nsn) * NB;
+        for (int b = threadIdx.x; b < NB; b += 256) v += (double)src[b];
+    }
+    v = block_sum256(v, red);
+    if (threadIdx.x == 0) sw.sums[j] = v;
+}
+
+template <class... Scal>
+__global__ void __launch_bounds__(kFin) gf_occ_finalise_kernel(OccParams a, int NB, int T, OccWs ws, float *loss, Scal... sw_)
+{
+    constexpr bool kScal = sizeof...(Scal) != 0;
     __shared__ double res[2 * GF_OCC_MAX_LAYERS + GF_OCC_MAX_LAYERS * kC];
+    if constexpr (kScal) {
+        const OccScalWs &sw = scal_ws(sw_...);
+        ScalLds &sl = scal_lds();
+        if (threadIdx.x == 0) sl.bad = 0;
+        const int nsn = a.L * 2 * kC;
+        if ((int)threadIdx.x < nsn) sl.sums[threadIdx.x] = sw.sums[threadIdx.x];
+        if ((int)threadIdx.x < kC) sl.tc[threadIdx.x] = (int)sw.sums[nsn + threadIdx.x];
+    }
     const int L = a.L, S = L * kC, M = ws.hdr[0], nt = (M + kTile - 1) / kTile;
     const int w = threadIdx.x >> 6, lane = lane_id();
     for (int j = w; j < 2 * L + S; j += kFin / 64) {
@@ -469,6 +643,44 @@ __global__ void __launch_bounds__(kFin) gf_occ_finalise_kernel(OccParams a, int 
         if (lane == 0) res[j] = v;
     }
     __syncthreads();
+    if constexpr (kScal) {
+        // C threads per layer: one per class of the sem term, the last one the geo term; then one store of a and b per class
+        const OccScalWs &sw = scal_ws(sw_...);
+        ScalLds &sl = scal_lds();
+        const bool active = (int)threadIdx.x < L * kC;
+        const int l = threadIdx.x / kC, i = threadIdx.x % kC;
+        int V = 0, count = 0;
+        float da = 0.f, db = 0.f;
+        if (active) {
+            for (int c = 0; c < kC; ++c) V += sl.tc[c];
+            for (int c = 0; c < kC - 1; ++c) count += sl.tc[c] > 0;
+            bool bad = count == 0;                    // the reference divides by zero in Python here
+            sl.term[l][i] = scal_class_term(i, sl.sums + l * 2 * kC, sl.tc, V, a.empty_label, da, db, bad);
+            if (i == kC - 1) {
+                sl.geo_d[l][0] = da;
+                sl.geo_d[l][1] = db;
+            }
+            if (bad) atomicOr(&sl.bad, 1);
+        }
+        __syncthreads();
+        if (active) {
+            const float inv = sw.sem_w / (float)count;
+            float ga = i < kC - 1 ? inv * da : 0.f, gb = i < kC - 1 ? inv * db : 0.f;
+            if (i == a.empty_label) {
+                ga += sw.geo_w * sl.geo_d[l][0];
+                gb += sw.geo_w * sl.geo_d[l][1];
+            }
+            sw.ab[l * 2 * kC + i] = ga;
+            sw.ab[l * 2 * kC + kC + i] = gb;
+            if (i == 0) {
+                float total = 0.f;                    // in class order, as the reference's loop (an absent class adds 0)
+                for (int c = 0; c < kC - 1; ++c) total += sl.term[l][c];
+                const float sem = total / (float)count;
+                sl.scal[l] = (double)sw.sem_w * (double)sem + (double)sw.geo_w * (double)sl.term[l][kC - 1];
+            }
+        }
+        __syncthreads();
+    }
     if (threadIdx.x != 0) return;
     int present = 0;
     for (int c = 0; c < kC; ++c) present += ws.hdr[8 + c] != 0;
@@ -479,17 +691,22 @@ __global__ void __launch_bounds__(kFin) gf_occ_finalise_kernel(OccParams a, int 
         for (int c = 0; c < kC; ++c) lov += res[2 * L + l * kC + c];
         lov = present ? lov / present : 0.0;
         total += (double)a.ce_weight * ce + (double)a.lovasz_weight * lov;
+        if constexpr (kScal) total += scal_lds().scal[l];
     }
     total /= L;
     if (ws.hdr[1] || ws.hdr[2]) total = __builtin_nan("");
+    if constexpr (kScal)
+        if (scal_lds().bad) total = __builtin_nan("");
     for (int j = 0; j < 2 * L + S; ++j) ws.res[j] = res[j];
     ws.hdr[3] = present;
     *loss = (float)total;
 }
 
-__global__ void __launch_bounds__(kVox) gf_occ_backward_kernel(OccParams a, OccPreds preds, OccGrads grads,
-                                                               const float *grad_loss, OccWs ws)
+template <class... Scal>
+__global__ void __launch_bounds__(kVox) gf_occ_backward_kernel(OccParams a, OccPreds preds, OccGrads grads, const float *grad_loss,
+                                                               OccWs ws, Scal... sw_)
 {
+    constexpr bool kScal = sizeof...(Scal) != 0;
     __shared__ float tile[kVox * kC];
     const int l = blockIdx.y, n = blockIdx.x * kVox + threadIdx.x;
     const bool staged = rows_staged(a);
@@ -534,6 +751,20 @@ __global__ void __launch_bounds__(kVox) gf_occ_backward_kernel(OccParams a, OccP
 #pragma unroll
             for (int c = 0; c < kC; ++c) g[c] += prob ? gl[c] : p[c] * (gl[c] - dot);
         }
+        if constexpr (kScal) {
+            // the affinity terms' gradient in p-space, a_c + b_c [y = c], on every voxel of V (Lovász voxel or not)
+            if (v.ce) {
+                const float *ab = scal_ws(sw_...).ab + l * 2 * kC;
+                float gs[kC], dot = 0.f;
+#pragma unroll
+                for (int c = 0; c < kC; ++c) {
+                    gs[c] = go * (ab[c] + (c == v.y ? ab[kC + c] : 0.f));
+                    dot += gs[c] * p[c];
+                }
+#pragma unroll
+                for (int c = 0; c < kC; ++c) g[c] += prob ? gs[c] : p[c] * (gs[c] - dot);
+            }
+        }
     }
     if (staged) {
         __syncthreads();     // every thread has read its row of the input tile
@@ -546,14 +777,21 @@ __global__ void __launch_bounds__(kVox) gf_occ_backward_kernel(OccParams a, OccP
     }
 }
 
-int check_common(const char *fn, int L, int N, int C, int flags, const float *const *pred, long long sc, long long sn,
-                 const long long *label, const unsigned char *mask, const float *cw, void *workspace, size_t workspace_bytes)
+// `scal`: the caller is one of the gf_occ_loss_scal_* entry points, which take (and require) GF_OCC_SCAL
+int check_common(const char *fn, bool scal, int L, int N, int C, int flags, const float *const *pred, long long sc, long long sn,
+                 const long long *label, const unsigned char *mask, const float *cw, int empty_label, void *workspace,
+                 size_t workspace_bytes)
 {
     if (C != kC) { set_error("%s: C = %d; only %d channels are supported", fn, C, kC); return GF_EINVAL; }
     if (L < 1 || L > GF_OCC_MAX_LAYERS) { set_error("%s: L = %d; 1 <= L <= %d", fn, L, GF_OCC_MAX_LAYERS); return GF_EINVAL; }
     if (N < 1 || N > (1 << 28)) { set_error("%s: N = %d; 1 <= N <= 2^28", fn, N); return GF_EINVAL; }
-    if (flags & ~(GF_OCC_PROB | GF_OCC_MASK | GF_OCC_LOVASZ_IGNORE | GF_OCC_IGNORE_EMPTY | GF_OCC_NO_LOVASZ)) {
+    if (flags & ~(GF_OCC_PROB | GF_OCC_MASK | GF_OCC_LOVASZ_IGNORE | GF_OCC_IGNORE_EMPTY | GF_OCC_NO_LOVASZ | (scal ? GF_OCC_SCAL : 0))) {
         set_error("%s: unknown flags 0x%x", fn, flags);
+        return GF_EINVAL;
+    }
+    if (scal && !(flags & GF_OCC_SCAL)) { set_error("%s: flags 0x%x lack GF_OCC_SCAL", fn, flags); return GF_EINVAL; }
+    if (scal && (empty_label < 0 || empty_label >= kC)) {
+        set_error("%s: empty_label = %d; the geo term needs a class in [0, %d)", fn, empty_label, kC);
         return GF_EINVAL;
     }
     if (sc < 1 || sn < 1) { set_error("%s: strides must be positive (got %lld, %lld)", fn, sc, sn); return GF_EINVAL; }
@@ -562,7 +800,8 @@ int check_common(const char *fn, int L, int N, int C, int flags, const float *co
         if (!pred[l]) { set_error("%s: null prediction pointer of layer %d", fn, l); return GF_EINVAL; }
     if ((flags & GF_OCC_MASK) && !mask) { set_error("%s: GF_OCC_MASK without a mask", fn); return GF_EINVAL; }
     size_t need = 0;
-    carve(nullptr, nullptr, L, N, &need);
+    OccScalWs sw{};
+    carve(nullptr, nullptr, L, N, &need, nullptr, scal ? &sw : nullptr);
     GF_CHECK_WORKSPACE_AS(fn, "workspace", workspace_bytes, need);
     return GF_OK;
 }
@@ -577,43 +816,32 @@ OccParams make_params(int L, int N, int flags, long long sc, long long sn, const
     return a;
 }
 
-}  // namespace occ
-}  // namespace gf
-
-extern "C" size_t gf_occ_loss_workspace_bytes(int L, int N, int C, int flags)
+size_t region_bytes(int L, int N, int C, int flags, bool scratch)
 {
-    (void)flags;
     if (C != GF_NUM_CHANNELS || L < 1 || L > GF_OCC_MAX_LAYERS || N < 1 || N > (1 << 28)) return 0;
-    size_t w = 0;
-    gf::occ::carve(nullptr, nullptr, L, N, &w);
-    return w;
+    size_t w = 0, b = 0;
+    OccScalWs sw{};
+    carve(nullptr, nullptr, L, N, &w, &b, (flags & GF_OCC_SCAL) ? &sw : nullptr);
+    return scratch ? b : w;
 }
 
-extern "C" size_t gf_occ_loss_scratch_bytes(int L, int N, int C, int flags)
+// both forwards: the kernels of the affinity terms (`scal`) are instantiations of their own, chosen here on the host
+int forward(const char *fn, bool scal, int L, int N, int C, int flags, const float *const *pred, long long stride_c,
+            long long stride_n, const long long *label, const unsigned char *mask, const float *class_weights, float ce_weight,
+            float lovasz_weight, float sem_scal_weight, float geo_scal_weight, int lovasz_ignore, int ignore_index, int empty_label,
+            float *loss, void *workspace, size_t workspace_bytes, void *scratch, size_t scratch_bytes, void *stream_)
 {
-    (void)flags;
-    if (C != GF_NUM_CHANNELS || L < 1 || L > GF_OCC_MAX_LAYERS || N < 1 || N > (1 << 28)) return 0;
-    size_t b = 0;
-    gf::occ::carve(nullptr, nullptr, L, N, nullptr, &b);
-    return b;
-}
-
-extern "C" int gf_occ_loss_forward(int L, int N, int C, int flags, const float *const *pred, long long stride_c,
-                                   long long stride_n, const long long *label, const unsigned char *mask,
-                                   const float *class_weights, float ce_weight, float lovasz_weight, int lovasz_ignore,
-                                   int ignore_index, int empty_label, float *loss, void *workspace, size_t workspace_bytes,
-                                   void *scratch, size_t scratch_bytes, void *stream_)
-{
-    using namespace gf;
-    using namespace gf::occ;
-    int rc = check_common(__func__, L, N, C, flags, pred, stride_c, stride_n, label, mask, class_weights, workspace,
+    int rc = check_common(fn, scal, L, N, C, flags, pred, stride_c, stride_n, label, mask, class_weights, empty_label, workspace,
                           workspace_bytes);
     if (rc != GF_OK) return rc;
-    GF_CHECK_ARG(loss, "null loss pointer");
-    GF_CHECK_ARG(scratch, "null scratch pointer");
+    GF_CHECK_ARG_AS(fn, loss, "null loss pointer");
+    GF_CHECK_ARG_AS(fn, scratch, "null scratch pointer");
     size_t need = 0;
-    const OccWs ws = carve(workspace, scratch, L, N, nullptr, &need);
-    GF_CHECK_WORKSPACE_AS(__func__, "scratch", scratch_bytes, need);
+    OccScalWs sw{};
+    const OccWs ws = carve(workspace, scratch, L, N, nullptr, &need, scal ? &sw : nullptr);
+    GF_CHECK_WORKSPACE_AS(fn, "scratch", scratch_bytes, need);
+    sw.sem_w = sem_scal_weight;
+    sw.geo_w = geo_scal_weight;
     const hipStream_t stream = (hipStream_t)stream_;
     const OccParams a = make_params(L, N, flags, stride_c, stride_n, label, mask, class_weights, ce_weight, lovasz_weight,
                                     lovasz_ignore, ignore_index, empty_label);
@@ -623,7 +851,10 @@ extern "C" int gf_occ_loss_forward(int L, int N, int C, int flags, const float *
     hipLaunchKernelGGL(gf_occ_clear_kernel, dim3(1), dim3(64), 0, stream, ws);
     hipLaunchKernelGGL(gf_occ_prep_kernel, dim3(NB), dim3(kVox), 0, stream, a, ws);
     hipLaunchKernelGGL(gf_occ_offsets_kernel, dim3(1), dim3(1024), 0, stream, NB, ws);
-    hipLaunchKernelGGL(gf_occ_main_kernel, dim3(NB, L), dim3(kVox), 0, stream, a, preds, ws);
+    if (scal)
+        hipLaunchKernelGGL(gf_occ_main_kernel<OccScalWs>, dim3(NB, L), dim3(kVox), 0, stream, a, preds, ws, sw);
+    else
+        hipLaunchKernelGGL(gf_occ_main_kernel<>, dim3(NB, L), dim3(kVox), 0, stream, a, preds, ws);
     // without the Lovász term no voxel has a key (M = 0, no present class): the sort and the Lovász pass are not launched
     for (int pass = 0; pass < 4 && !(flags & GF_OCC_NO_LOVASZ); ++pass) {
         const uint2 *in = ws.keys[pass & 1];
@@ -637,25 +868,28 @@ extern "C" int gf_occ_loss_forward(int L, int N, int C, int flags, const float *
         hipLaunchKernelGGL(gf_occ_fg_count_kernel, dim3(T, S), dim3(256), 0, stream, N, T, ws.keys[0], ws);
         hipLaunchKernelGGL(gf_occ_lovasz_kernel, dim3(T, S), dim3(256), 0, stream, N, T, ws.keys[0], ws);
     }
-    hipLaunchKernelGGL(gf_occ_finalise_kernel, dim3(1), dim3(kFin), 0, stream, a, NB, T, ws, loss);
-    GF_CHECK_LAUNCH();
+    if (scal)
+        hipLaunchKernelGGL(gf_occ_scal_sums_kernel, dim3(2 * S + kC), dim3(256), 0, stream, NB, 2 * S, sw);
+    if (scal)
+        hipLaunchKernelGGL(gf_occ_finalise_kernel<OccScalWs>, dim3(1), dim3(kFin), 0, stream, a, NB, T, ws, loss, sw);
+    else
+        hipLaunchKernelGGL(gf_occ_finalise_kernel<>, dim3(1), dim3(kFin), 0, stream, a, NB, T, ws, loss);
+    GF_CHECK_LAUNCH_AS(fn);
     return GF_OK;
 }
 
-extern "C" int gf_occ_loss_backward(int L, int N, int C, int flags, const float *const *pred, long long stride_c,
-                                    long long stride_n, const long long *label, const unsigned char *mask,
-                                    const float *class_weights, float ce_weight, float lovasz_weight, int lovasz_ignore,
-                                    int ignore_index, int empty_label, const float *grad_loss, float *const *grad_pred,
-                                    void *workspace, size_t workspace_bytes, void *stream_)
+int backward(const char *fn, bool scal, int L, int N, int C, int flags, const float *const *pred, long long stride_c,
+             long long stride_n, const long long *label, const unsigned char *mask, const float *class_weights, float ce_weight,
+             float lovasz_weight, int lovasz_ignore, int ignore_index, int empty_label, const float *grad_loss,
+             float *const *grad_pred, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    using namespace gf;
-    using namespace gf::occ;
-    int rc = check_common(__func__, L, N, C, flags, pred, stride_c, stride_n, label, mask, class_weights, workspace,
+    int rc = check_common(fn, scal, L, N, C, flags, pred, stride_c, stride_n, label, mask, class_weights, empty_label, workspace,
                           workspace_bytes);
     if (rc != GF_OK) return rc;
-    GF_CHECK_ARG(grad_loss && grad_pred, "null gradient pointer");
-    for (int l = 0; l < L; ++l) GF_CHECK_ARG(grad_pred[l], "null gradient pointer of a layer");
-    const OccWs ws = carve(workspace, nullptr, L, N);
+    GF_CHECK_ARG_AS(fn, grad_loss && grad_pred, "null gradient pointer");
+    for (int l = 0; l < L; ++l) GF_CHECK_ARG_AS(fn, grad_pred[l], "null gradient pointer of a layer");
+    OccScalWs sw{};
+    const OccWs ws = carve(workspace, nullptr, L, N, nullptr, nullptr, scal ? &sw : nullptr);
     const OccParams a = make_params(L, N, flags, stride_c, stride_n, label, mask, class_weights, ce_weight, lovasz_weight,
                                     lovasz_ignore, ignore_index, empty_label);
     OccPreds preds{};
@@ -664,8 +898,73 @@ extern "C" int gf_occ_loss_backward(int L, int N, int C, int flags, const float 
         preds.p[l] = pred[l];
         grads.p[l] = grad_pred[l];
     }
-    hipLaunchKernelGGL(gf_occ_backward_kernel, dim3(num_blocks(N), L), dim3(kVox), 0, (hipStream_t)stream_, a, preds, grads,
-                       grad_loss, ws);
-    GF_CHECK_LAUNCH();
+    if (scal)
+        hipLaunchKernelGGL(gf_occ_backward_kernel<OccScalWs>, dim3(num_blocks(N), L), dim3(kVox), 0, (hipStream_t)stream_, a,
+                           preds, grads, grad_loss, ws, sw);
+    else
+        hipLaunchKernelGGL(gf_occ_backward_kernel<>, dim3(num_blocks(N), L), dim3(kVox), 0, (hipStream_t)stream_, a, preds,
+                           grads, grad_loss, ws);
+    GF_CHECK_LAUNCH_AS(fn);
     return GF_OK;
+}
+
+}  // namespace occ
+}  // namespace gf
+
+extern "C" size_t gf_occ_loss_workspace_bytes(int L, int N, int C, int flags)
+{
+    return gf::occ::region_bytes(L, N, C, flags, false);
+}
+
+extern "C" size_t gf_occ_loss_scratch_bytes(int L, int N, int C, int flags)
+{
+    return gf::occ::region_bytes(L, N, C, flags, true);
+}
+
+extern "C" int gf_occ_loss_forward(int L, int N, int C, int flags, const float *const *pred, long long stride_c,
+                                   long long stride_n, const long long *label, const unsigned char *mask,
+                                   const float *class_weights, float ce_weight, float lovasz_weight, int lovasz_ignore,
+                                   int ignore_index, int empty_label, float *loss, void *workspace, size_t workspace_bytes,
+                                   void *scratch, size_t scratch_bytes, void *stream)
+{
+    return gf::occ::forward(__func__, false, L, N, C, flags, pred, stride_c, stride_n, label, mask, class_weights, ce_weight,
+                            lovasz_weight, 0.f, 0.f, lovasz_ignore, ignore_index, empty_label, loss, workspace, workspace_bytes,
+                            scratch, scratch_bytes, stream);
+}
+
+extern "C" int gf_occ_loss_backward(int L, int N, int C, int flags, const float *const *pred, long long stride_c,
+                                    long long stride_n, const long long *label, const unsigned char *mask,
+                                    const float *class_weights, float ce_weight, float lovasz_weight, int lovasz_ignore,
+                                    int ignore_index, int empty_label, const float *grad_loss, float *const *grad_pred,
+                                    void *workspace, size_t workspace_bytes, void *stream)
+{
+    return gf::occ::backward(__func__, false, L, N, C, flags, pred, stride_c, stride_n, label, mask, class_weights, ce_weight,
+                             lovasz_weight, lovasz_ignore, ignore_index, empty_label, grad_loss, grad_pred, workspace,
+                             workspace_bytes, stream);
+}
+
+extern "C" int gf_occ_loss_scal_forward(int L, int N, int C, int flags, const float *const *pred, long long stride_c,
+                                        long long stride_n, const long long *label, const unsigned char *mask,
+                                        const float *class_weights, float ce_weight, float lovasz_weight, float sem_scal_weight,
+                                        float geo_scal_weight, int lovasz_ignore, int ignore_index, int empty_label, float *loss,
+                                        void *workspace, size_t workspace_bytes, void *scratch, size_t scratch_bytes, void *stream)
+{
+    return gf::occ::forward(__func__, true, L, N, C, flags, pred, stride_c, stride_n, label, mask, class_weights, ce_weight,
+                            lovasz_weight, sem_scal_weight, geo_scal_weight, lovasz_ignore, ignore_index, empty_label, loss,
+                            workspace, workspace_bytes, scratch, scratch_bytes, stream);
+}
+
+// the weights are folded into what the forward left in the workspace; they are taken here for the symmetry of the two lists
+extern "C" int gf_occ_loss_scal_backward(int L, int N, int C, int flags, const float *const *pred, long long stride_c,
+                                         long long stride_n, const long long *label, const unsigned char *mask,
+                                         const float *class_weights, float ce_weight, float lovasz_weight, float sem_scal_weight,
+                                         float geo_scal_weight, int lovasz_ignore, int ignore_index, int empty_label,
+                                         const float *grad_loss, float *const *grad_pred, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    (void)sem_scal_weight;
+    (void)geo_scal_weight;
+    return gf::occ::backward(__func__, true, L, N, C, flags, pred, stride_c, stride_n, label, mask, class_weights, ce_weight,
+                             lovasz_weight, lovasz_ignore, ignore_index, empty_label, grad_loss, grad_pred, workspace,
+                             workspace_bytes, stream);
 }

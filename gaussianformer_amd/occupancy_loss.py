@@ -14,7 +14,7 @@ Inputs: ``pred_occ``, a list of L (1 <= L <= 8) fp32 tensors ``[1, C, N]`` with 
 contiguous ``[1, C, N]`` tensor; all layers share one layout.  ``sampled_label`` ``[1, N]`` integer; optional ``occ_mask``
 (bool, anything that flattens to ``[N]``).
 
-    loss = (1/L) * sum_layers (ce_weight * CE + lovasz_weight * Lovasz)
+    loss = (1/L) * sum_layers (ce_weight * CE + lovasz_weight * Lovasz [+ sem_scal_weight * sem + geo_scal_weight * geo])
 
 over the voxels kept by ``occ_mask`` and, with ``ignore_empty``, by ``label != empty_label``.
 
@@ -32,6 +32,21 @@ over the voxels kept by ``occ_mask`` and, with ``ignore_empty``, by ``label != e
   prob mode, where the prob head produces exact zeros).
 * A non-finite input on a voxel that enters either term, or a label outside ``[0, C)`` that is not ``ignore_index``, makes
   the loss NaN (flagged on the device; no host check).
+
+* The scene-class affinity terms (``sem_scal_loss`` / ``geo_scal_loss``, loss/occupancy_loss.py:185-268; only with
+  ``sem_scal_weight`` or ``geo_scal_weight``).  ``V`` = the CE's voxels (kept, ``y != ignore_index``, ``0 <= y < C``); per
+  layer ``S_c = sum_V p_c``, ``N_c = sum_{V, y=c} p_c`` (accumulated in double in a fixed order, each rounded to fp32 once),
+  ``T_c = #{V, y=c}``, ``eps = 1e-5``; every ratio and ``f`` below is evaluated in fp32, operation by operation.
+  ``f(x)`` is ``binary_cross_entropy_with_logits(inverse_sigmoid(x), 1)``: while ``x >= float32(1 - 1e-5)``: ``x -= 1e-5``;
+  while ``x < 1e-5``: ``x += 1e-5``; ``f = softplus(log(1/x - 1))`` (``-log x`` in exact arithmetic), ``f' = -1/x`` at the
+  shifted ``x`` (the shifts pass gradient 1).  The loops run on the device, at most 8 steps each (a ratio of probabilities
+  needs 3); a ratio still out of range then -- inputs that are no probabilities, prob mode only -- makes the loss NaN.
+  ``sem = (1/count) sum_i [f(N_i/(S_i+eps)) if S_i > 0] + f(N_i/(T_i+eps)) + [f(((|V|-T_i) - (S_i-N_i)) / ((|V|-T_i)+eps)) if
+  |V| > T_i]`` over the classes ``i`` in ``0 .. C-2`` with ``T_i > 0``, ``count`` of them; ``count == 0`` gives NaN (the
+  reference divides by zero in Python).  ``geo``, with ``e = empty_label`` in ``[0, C)`` and ``I = (|V|-T_e) - (S_e-N_e)``:
+  ``f(I/((|V|-S_e)+eps)) + f(I/((|V|-T_e)+eps)) + f(N_e/(T_e+eps))``, no guards, as the reference.  The gradient is
+  ``a_c + b_c [y = c]`` in ``p``-space on the voxels of ``V`` (Lovász voxels or not), through the softmax Jacobian in softmax
+  mode.  The NaN rules below apply to the voxels of ``V``.
 
 The loss is bitwise reproducible: every partial is summed in a fixed order, with no float atomics.  ``use_lovasz=False``
 computes the CE term alone (the reference's ``use_lovasz_loss=False``): no sort, and non-finite inputs count only on CE
@@ -81,9 +96,9 @@ class _OccLoss(torch.autograd.Function):
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)     # the forward's own: freed when it returns
         loss = torch.empty((), dtype=torch.float32, device=dev)
         ptrs = (ctypes.c_void_p * L)(*[p.data_ptr() for p in preds])
-        _lib.call("gf_occ_loss_forward", dev, L, N, _C, cfg["flags"], ptrs, sc, sn, label, mask, class_weights,
-                  cfg["ce_weight"], cfg["lovasz_weight"], cfg["lovasz_ignore"], cfg["ignore_index"], cfg["empty_label"], loss,
-                  ws, nbytes, scratch, sbytes)
+        _lib.call("gf_occ_loss_scal_forward" if cfg["scal"] else "gf_occ_loss_forward", dev, L, N, _C, cfg["flags"], ptrs, sc, sn,
+                  label, mask, class_weights, cfg["ce_weight"], cfg["lovasz_weight"], *cfg["scal"], cfg["lovasz_ignore"],
+                  cfg["ignore_index"], cfg["empty_label"], loss, ws, nbytes, scratch, sbytes)
         ctx.cfg, ctx.layout = cfg, (N, sc, sn)
         ctx.save_for_backward(label, mask, class_weights, ws, *preds)
         return loss
@@ -98,16 +113,22 @@ class _OccLoss(torch.autograd.Function):
         g = _lib.as_arg(grad_loss)
         pp = (ctypes.c_void_p * L)(*[p.data_ptr() for p in preds])
         gp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in grads])
-        _lib.call("gf_occ_loss_backward", dev, L, N, _C, cfg["flags"], pp, sc, sn, label, mask, class_weights,
-                  cfg["ce_weight"], cfg["lovasz_weight"], cfg["lovasz_ignore"], cfg["ignore_index"], cfg["empty_label"], g, gp,
-                  ws, ws.numel())
+        _lib.call("gf_occ_loss_scal_backward" if cfg["scal"] else "gf_occ_loss_backward", dev, L, N, _C, cfg["flags"], pp, sc, sn,
+                  label, mask, class_weights, cfg["ce_weight"], cfg["lovasz_weight"], *cfg["scal"], cfg["lovasz_ignore"],
+                  cfg["ignore_index"], cfg["empty_label"], g, gp, ws, ws.numel())
         return (None, None, None, None, *grads)
 
 
 def occupancy_loss(pred_occ, sampled_label, occ_mask=None, *, class_weights, ce_weight=1.0, lovasz_weight=1.0,
-                   lovasz_ignore=None, use_softmax=True, ignore_index=255, empty_label=17, ignore_empty=False, use_lovasz=True):
+                   lovasz_ignore=None, use_softmax=True, ignore_index=255, empty_label=17, ignore_empty=False, use_lovasz=True,
+                   sem_scal_weight=None, geo_scal_weight=None):
     """The occupancy loss of the module docstring for ``pred_occ`` (list of ``[1, C, N]``); returns a 0-dim tensor.
-    No ``.item()``, ``nonzero()`` or boolean indexing: forward and backward never wait for the device."""
+    No ``.item()``, ``nonzero()`` or boolean indexing: forward and backward never wait for the device.
+
+    ``sem_scal_weight`` / ``geo_scal_weight``: with both ``None`` the loss is CE + Lovász, by ``gf_occ_loss_*``.  With either
+    given, the scene-class affinity terms are added by ``gf_occ_loss_scal_*`` (the one not given weighs 0).  Where the
+    reference's ``sem_scal_loss`` divides by zero in Python -- no class of ``0 .. C-2`` among the voxels of ``V`` -- the loss
+    is NaN, flagged on the device; so it is for a ratio that more than 8 shift steps do not bring into range."""
     pred_occ = list(pred_occ)
     N, _, _ = _layout(pred_occ)
     dev = pred_occ[0].device
@@ -135,7 +156,13 @@ def occupancy_loss(pred_occ, sampled_label, occ_mask=None, *, class_weights, ce_
     cw = torch.as_tensor(class_weights, dtype=torch.float32, device=dev).reshape(-1).contiguous()
     if cw.numel() != _C:
         raise ValueError(f"class_weights must have {_C} entries")
-    cfg = dict(flags=flags, ce_weight=float(ce_weight), lovasz_weight=float(lovasz_weight),
+    scal = ()
+    if sem_scal_weight is not None or geo_scal_weight is not None:
+        if not 0 <= int(empty_label) < _C:
+            raise ValueError(f"empty_label={empty_label}: the geo_scal term needs a class in [0, {_C})")
+        flags |= _lib.GF_OCC_SCAL
+        scal = (float(sem_scal_weight or 0.0), float(geo_scal_weight or 0.0))
+    cfg = dict(flags=flags, scal=scal, ce_weight=float(ce_weight), lovasz_weight=float(lovasz_weight),
                lovasz_ignore=int(lovasz_ignore) if lovasz_ignore is not None else 0, ignore_index=int(ignore_index),
                empty_label=int(empty_label))
     return _OccLoss.apply(cfg, label, mask, cw, *pred_occ)
@@ -144,7 +171,13 @@ def occupancy_loss(pred_occ, sampled_label, occ_mask=None, *, class_weights, ce_
 class OccupancyLoss(nn.Module):
     """Drop-in for the reference's ``OccupancyLoss`` (register it in its place): the same constructor keywords and the
     ``forward(inputs)`` dict contract of ``BaseLoss`` (``weight * loss_voxel(**{k: inputs[v] for k, v in input_dict})``).
-    Options this op does not cover raise ``ValueError`` naming them."""
+    Options this op does not cover raise ``ValueError`` naming them.
+
+    ``native_scal``: opt-in for ``use_sem_geo_scal_loss=True`` (the reference's default).  Set the class attribute to ``True``
+    and the constructor accepts the option: the two affinity terms run in the HIP op, weighted by
+    ``loss_voxel_sem_scal_weight`` and ``loss_voxel_geo_scal_weight`` of ``multi_loss_weights`` (default 1.0)."""
+
+    native_scal = False
 
     def __init__(self, weight=1.0, empty_label=17, num_classes=18, use_focal_loss=False, focal_loss_args=dict(),
                  use_dice_loss=False, balance_cls_weight=False, multi_loss_weights=dict(), use_sem_geo_scal_loss=True,
@@ -155,8 +188,9 @@ class OccupancyLoss(nn.Module):
             raise ValueError("OccupancyLoss: use_focal_loss is not supported by the HIP op")
         if use_dice_loss:
             raise ValueError("OccupancyLoss: use_dice_loss is not supported by the HIP op")
-        if use_sem_geo_scal_loss:
-            raise ValueError("OccupancyLoss: use_sem_geo_scal_loss is not supported by the HIP op (the shipped configs set it False)")
+        if use_sem_geo_scal_loss and not self.native_scal:
+            raise ValueError("OccupancyLoss: use_sem_geo_scal_loss is off by default in the HIP op (the shipped configs set it "
+                             "False); set OccupancyLoss.native_scal = True to run the two terms natively")
         if balance_cls_weight and manual_class_weight is None:
             raise ValueError("OccupancyLoss: balance_cls_weight without manual_class_weight is not supported")
         if num_classes != _C:
@@ -166,11 +200,14 @@ class OccupancyLoss(nn.Module):
             'pred_occ': 'pred_occ', 'sampled_xyz': 'sampled_xyz', 'sampled_label': 'sampled_label', 'occ_mask': 'occ_mask'}
         self.empty_label = empty_label
         self.num_classes = num_classes
+        self.use_sem_geo_scal_loss = use_sem_geo_scal_loss
         self.use_lovasz_loss = use_lovasz_loss
         self.lovasz_ignore = lovasz_ignore
         self.ignore_empty = ignore_empty
         self.lovasz_use_softmax = lovasz_use_softmax
         self.loss_voxel_ce_weight = multi_loss_weights.get('loss_voxel_ce_weight', 1.0)
+        self.loss_voxel_sem_scal_weight = multi_loss_weights.get('loss_voxel_sem_scal_weight', 1.0)
+        self.loss_voxel_geo_scal_weight = multi_loss_weights.get('loss_voxel_geo_scal_weight', 1.0)
         self.loss_voxel_lovasz_weight = multi_loss_weights.get('loss_voxel_lovasz_weight', 1.0)
         if balance_cls_weight:
             # as the reference: num_classes * L1-normalised manual weights, in fp32
@@ -184,7 +221,9 @@ class OccupancyLoss(nn.Module):
                               ce_weight=self.loss_voxel_ce_weight,
                               lovasz_weight=self.loss_voxel_lovasz_weight, lovasz_ignore=self.lovasz_ignore,
                               use_softmax=self.lovasz_use_softmax, ignore_index=255, empty_label=self.empty_label,
-                              ignore_empty=self.ignore_empty, use_lovasz=self.use_lovasz_loss)
+                              ignore_empty=self.ignore_empty, use_lovasz=self.use_lovasz_loss,
+                              sem_scal_weight=self.loss_voxel_sem_scal_weight if self.use_sem_geo_scal_loss else None,
+                              geo_scal_weight=self.loss_voxel_geo_scal_weight if self.use_sem_geo_scal_loss else None)
 
     def forward(self, inputs):
         actual = {k: inputs[v] for k, v in self.input_dict.items()}

@@ -703,6 +703,7 @@ int gf_farthest_point_sampling(int n, int b, const int *offset_host, const int *
 #define GF_OCC_LOVASZ_IGNORE 4
 #define GF_OCC_IGNORE_EMPTY 8
 #define GF_OCC_NO_LOVASZ 16 /* CE only (use_lovasz_loss=False): no Lovász voxels, no sort; non-finite checks on CE voxels only */
+#define GF_OCC_SCAL 32      /* the scene-class affinity terms: gf_occ_loss_scal_* only (below); the size queries honour it */
 #define GF_OCC_MAX_LAYERS 8
 size_t gf_occ_loss_workspace_bytes(int L, int N, int C, int flags);
 size_t gf_occ_loss_scratch_bytes(int L, int N, int C, int flags);
@@ -714,6 +715,32 @@ int gf_occ_loss_backward(int L, int N, int C, int flags, const float *const *pre
                          const long long *label, const unsigned char *mask, const float *class_weights, float ce_weight,
                          float lovasz_weight, int lovasz_ignore, int ignore_index, int empty_label, const float *grad_loss,
                          float *const *grad_pred, void *workspace, size_t workspace_bytes, void *stream);
+/* The same loss with the scene-class affinity terms of MonoScene / SurroundOcc (sem_scal_loss, geo_scal_loss of
+ * loss/occupancy_loss.py:185-268; use_sem_geo_scal_loss=True):
+ *   loss = (1/L) sum_layers (ce_weight * CE + lovasz_weight * Lovasz + sem_scal_weight * sem + geo_scal_weight * geo)
+ * V = the kept voxels with label != ignore_index and a label in [0, C) (the CE's voxels); p as for the Lovasz term.  Per layer
+ * S_c = sum_V p_c, N_c = sum_{V, y = c} p_c (summed in double in a fixed order, each rounded to fp32 once), T_c = #{V, y = c};
+ * every ratio below and f are then evaluated in fp32, eps = 1e-5.
+ *   f(x) = binary_cross_entropy_with_logits(inverse_sigmoid(x), 1): while x >= float(1 - 1e-5): x -= 1e-5f; while x < 1e-5f:
+ *       x += 1e-5f; f = softplus(log(1/x - 1)), f' = -1/x at the shifted x.  Each loop is cut off after 8 steps; a ratio still
+ *       out of range then (inputs that are no probabilities, GF_OCC_PROB only) makes the loss NaN where the reference loops on.
+ *   sem = (1/count) sum over the classes i in [0, C-1) with T_i > 0 (count of them) of
+ *       f(N_i / (S_i + eps)) [if S_i > 0] + f(N_i / (T_i + eps)) + f(((|V| - T_i) - (S_i - N_i)) / ((|V| - T_i) + eps)) [if |V| > T_i];
+ *       count == 0 (the reference divides by zero): the loss is NaN.
+ *   geo, with e = empty_label (must lie in [0, C)) and I = (|V| - T_e) - (S_e - N_e):
+ *       f(I / ((|V| - S_e) + eps)) + f(I / ((|V| - T_e) + eps)) + f(N_e / (T_e + eps)), without guards, as the reference.
+ * The gradient in p-space is a_c + b_c [y = c] on the voxels of V, through the softmax Jacobian unless GF_OCC_PROB.
+ * flags must hold GF_OCC_SCAL, and workspace and scratch the sizes the queries give with it; every other argument as above. */
+int gf_occ_loss_scal_forward(int L, int N, int C, int flags, const float *const *pred, long long stride_c, long long stride_n,
+                             const long long *label, const unsigned char *mask, const float *class_weights, float ce_weight,
+                             float lovasz_weight, float sem_scal_weight, float geo_scal_weight, int lovasz_ignore,
+                             int ignore_index, int empty_label, float *loss, void *workspace, size_t workspace_bytes,
+                             void *scratch, size_t scratch_bytes, void *stream);
+int gf_occ_loss_scal_backward(int L, int N, int C, int flags, const float *const *pred, long long stride_c, long long stride_n,
+                              const long long *label, const unsigned char *mask, const float *class_weights, float ce_weight,
+                              float lovasz_weight, float sem_scal_weight, float geo_scal_weight, int lovasz_ignore,
+                              int ignore_index, int empty_label, const float *grad_loss, float *const *grad_pred,
+                              void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- evaluation metric -------------------------------------------------------------------------------------------
  * One frame of MeanIoU._after_step (misc/metric_util.py:35-66) -- the call eval.py:163, train.py:317 and visualize.py:205 make

@@ -12,8 +12,23 @@ Device time per call (CUDA events around each call, after warm-up; median and sp
 of each path.  Prints one JSON line per (path, L).  Needs an MI355X.
 
     python tools/bench_loss.py [--steps K] [--warmup W] [--n N] [--paths native,torch,native_all] [--layers 1,4]
+
+``--scal``: the scene-class affinity terms (sem_scal / geo_scal, weights 1).  Forward + backward of
+
+  scal            the native op with both terms
+  base            the native op without them, this build
+  parent          the same through another build of the library (``--parent-lib``: libgf_hip.so, or a library with the
+                  occupancy-loss entry points alone, built from the parent commit)
+  base+torch      ``base`` plus a torch restatement of the two terms (the reference's loop: three host synchronisations per
+                  class and layer, the shift loops on a device scalar) -- what enabling the terms costs without the native ones
+
+with the sides alternating in one process: ``--rounds`` rounds, in each the median of ``--steps`` calls per side; reported is
+the median of these medians and their spread (min .. max).  The lines are appended to profiles/bench_loss_scal.jsonl.
+
+    python tools/bench_loss.py --scal [--parent-lib PATH] [--rounds R] [--steps K] [--layers 1,4]
 """
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -24,6 +39,7 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from gaussianformer_amd import _lib  # noqa: E402
 from gaussianformer_amd.occupancy_loss import occupancy_loss  # noqa: E402
 from gaussianformer_amd.synthetic import make_occ_loss_inputs  # noqa: E402
 
@@ -61,6 +77,88 @@ def torch_loss(pred_occ, label, mask, cw, ce_weight=10.0, lovasz_weight=1.0, lov
     return tot / len(pred_occ)
 
 
+def _f_torch(x):
+    """-log sigmoid(inverse_sigmoid(x)) as the reference evaluates it: the shifts are host loops on a device scalar."""
+    x = x.float()
+    while x >= 1 - 1e-5:
+        x = x - 1e-5
+    while x < 1e-5:
+        x = x + 1e-5
+    return F.softplus(torch.log(1 / x - 1))
+
+
+def torch_scal(pred_occ, label, mask, empty=17, ignore=255):
+    """The two affinity terms restated with torch ops, host synchronisations included: sum over layers of sem + geo."""
+    occ = mask.flatten(1)
+    lab = label[occ]
+    valid = lab != ignore
+    y = lab[valid]
+    tot = 0.0
+    for sem in pred_occ:
+        p = torch.softmax(sem.transpose(1, 2)[occ], dim=1)[valid]          # [|V|, C]
+        loss, count = 0.0, 0
+        for i in range(p.shape[1] - 1):
+            t = (y == i).float()
+            if t.sum() > 0:
+                count += 1
+                num = (p[:, i] * t).sum()
+                if p[:, i].sum() > 0:
+                    loss = loss + _f_torch(num / (p[:, i].sum() + 1e-5))
+                loss = loss + _f_torch(num / (t.sum() + 1e-5))
+                if (1 - t).sum() > 0:
+                    loss = loss + _f_torch(((1 - p[:, i]) * (1 - t)).sum() / ((1 - t).sum() + 1e-5))
+        occupied, q = (y != empty).float(), 1 - p[:, empty]
+        inter = (occupied * q).sum()
+        geo = (_f_torch(inter / (q.sum() + 1e-5)) + _f_torch(inter / (occupied.sum() + 1e-5))
+               + _f_torch(((1 - occupied) * p[:, empty]).sum() / ((1 - occupied).sum() + 1e-5)))
+        tot = tot + loss / count + geo
+    return tot / len(pred_occ)
+
+
+def bench_scal(args, dev, cw):
+    out = os.path.join(ROOT, "profiles", "bench_loss_scal.jsonl")
+    parent = _lib.load_other(args.parent_lib) if args.parent_lib else None
+    for L in (int(v) for v in args.layers.split(",")):
+        x, label, mask = make_occ_loss_inputs(args.n, L, seed=L, mask_frac=0.05)
+        leaves = [torch.from_numpy(r).to(dev)[None].requires_grad_(True) for r in x]
+        lab = torch.from_numpy(label).to(dev)[None]
+        m = torch.from_numpy(mask).to(dev)[None]
+        kw = dict(class_weights=cw, ce_weight=10.0, lovasz_ignore=17)
+        sides = {
+            "scal": lambda p: occupancy_loss(p, lab, m, sem_scal_weight=1.0, geo_scal_weight=1.0, **kw),
+            "base": lambda p: occupancy_loss(p, lab, m, **kw),
+            "base+torch": lambda p: occupancy_loss(p, lab, m, **kw) + torch_scal(p, lab, m),
+        }
+        if parent is not None:
+            sides["parent"] = lambda p: occupancy_loss(p, lab, m, **kw)
+        medians = {k: [] for k in sides}
+        losses = {}
+        for r in range(args.rounds + 1):                 # round 0 warms every side up and is not counted
+            for name, fn in sides.items():
+                times = []
+                with _lib.routed_to(parent) if name == "parent" else contextlib.nullcontext():
+                    for _ in range(args.warmup if r == 0 else args.steps):
+                        for t in leaves:
+                            t.grad = None
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        loss = fn([t.transpose(1, 2) for t in leaves])
+                        loss.backward()
+                        b.record()
+                        b.synchronize()
+                        times.append(a.elapsed_time(b) * 1e3)
+                if r:
+                    medians[name].append(statistics.median(times))
+                losses[name] = float(loss.item())
+        with open(out, "a") as f:
+            for name, meds in medians.items():
+                line = json.dumps(dict(bench="occ_loss_scal", path=name, L=L, N=args.n, rounds=args.rounds, steps=args.steps,
+                                       median_us=round(statistics.median(meds), 1), min_us=round(min(meds), 1),
+                                       max_us=round(max(meds), 1), loss=losses[name]))
+                print(line, flush=True)
+                f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
@@ -68,11 +166,16 @@ def main():
     ap.add_argument("--n", type=int, default=640000)
     ap.add_argument("--paths", default="native,torch,native_all", help="comma-separated subset of the paths")
     ap.add_argument("--layers", default="1,4", help="comma-separated layer counts")
+    ap.add_argument("--scal", action="store_true", help="the affinity terms: native with them against the baselines")
+    ap.add_argument("--rounds", type=int, default=7, help="--scal: rounds of alternating sides")
+    ap.add_argument("--parent-lib", default=None, help="--scal: a build of the library at the parent commit")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_loss.py needs an MI355X")
     dev = torch.device("cuda:0")
     cw = (18 * F.normalize(torch.tensor(MANUAL), 1, -1)).to(dev)
+    if args.scal:
+        return bench_scal(args, dev, cw)
     for L in (int(v) for v in args.layers.split(",")):
         x, label, mask = make_occ_loss_inputs(args.n, L, seed=L, mask_frac=0.05)
         leaves = [torch.from_numpy(r).to(dev)[None].requires_grad_(True) for r in x]
