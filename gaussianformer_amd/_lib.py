@@ -3,6 +3,10 @@
 There is NO fallback: if the library is missing or a call fails, a ``RuntimeError`` is
 raised.  Tensors cross the boundary as raw device pointers + sizes; the stream is torch's
 current HIP stream.
+
+Also here, once for every module above: how arguments and parameter tables are made (``as_arg``, ``aligned``, ``param_table``,
+``out_table``), how a training Function carries its parameter list to its backward (``ParamSlots``), and the
+questions the modules' routes share (``needs_grad``, ``native_tensors``, ``refuse_autograd``, the post norm's ``norm_*``).
 """
 import collections
 import contextlib
@@ -10,6 +14,7 @@ import ctypes
 import os
 
 import torch
+import torch.nn as nn
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GF_LIB selects an instrumentation build (-DGF_TIMELINE=1, -DGF_DAF_TL) made by build.build(lib_name=...) (tools/ only)
@@ -267,6 +272,50 @@ def needs_grad(tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
+def refuse_autograd(name, tensors, hint):
+    """A forward-only function's refusal of a call that autograd would record; ``hint`` says where training goes instead."""
+    if needs_grad(tensors):
+        raise RuntimeError(
+            f"{name} is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters that "
+            f"do not require grad {hint}")
+
+
+def native_tensors(tensors):
+    """Whether every entry is ``None`` or an fp32 GPU tensor: what a module's native route asks of its inputs and parameters."""
+    return all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in tensors)
+
+
+# The post norm: the ``norm`` behind a block that the block's launch takes in (the encoder's ``"norm"``): ``None``, an affine
+# ``nn.LayerNorm`` with eps 1e-5 (the kernels' constant), or its ``(weight, bias)`` pair.
+
+def norm_pair(norm, what):
+    """``(weight, bias)`` of a post norm, ``(None, None)`` for ``None``; anything else is refused under the caller's name."""
+    if norm is None:
+        return None, None
+    if not norm_native(norm):
+        raise ValueError(f"{what}: norm must be an affine LayerNorm with eps = 1e-5, or a (weight, bias) pair")
+    return (norm.weight, norm.bias) if isinstance(norm, nn.Module) else tuple(norm)
+
+
+def norm_native(norm):
+    """Whether ``norm`` is a post norm as the library takes it (what ``norm_pair`` accepts, as a question)."""
+    if norm is None:
+        return True
+    if isinstance(norm, nn.Module):
+        return isinstance(norm, nn.LayerNorm) and not (norm.eps != 1e-5 or norm.weight is None or norm.bias is None)
+    return isinstance(norm, (tuple, list)) and len(norm) == 2 and all(isinstance(t, torch.Tensor) for t in norm)
+
+
+def norm_tensors(norm):
+    """The tensors of a ``norm`` argument of any kind (a module's parameters, a pair's entries, none for ``None``)."""
+    return list(norm.parameters()) if isinstance(norm, nn.Module) else list(norm or ())
+
+
+def apply_norm(x, norm):
+    """The post norm as a torch op, on the routes that do not take it into a launch."""
+    return norm(x) if isinstance(norm, nn.Module) else nn.functional.layer_norm(x, (x.shape[-1],), norm[0], norm[1], 1e-5)
+
+
 def aligned(t):
     """``as_arg(t)``, cloned where its address is not a multiple of 16 (the kernels move rows as float4s)."""
     t = as_arg(t)
@@ -299,6 +348,48 @@ def out_table(tensors, count):
                 raise ValueError("a gradient buffer must be a contiguous, 16-byte aligned float32 tensor")
             table[i] = t.data_ptr()
     return ctypes.cast(table, ctypes.c_void_p)
+
+
+class ParamSlots:
+    """A training ``autograd.Function``'s parameter list between its forward and its backward.  Three
+    things correspond slot by slot: the list in the library's table order with ``None`` for an absent parameter; the tensors
+    handed to the library (``param_table``'s ``held``: a parameter itself, or its converted copy), which travel through
+    ``save_for_backward`` without the ``None``s; and each slot's own dtype, which its gradient goes back in.  This record
+    holds the count and the dtypes and no tensor, so it is kept on ``ctx``.  Which slots get a gradient buffer is the op's
+    decision, passed as a list of booleans."""
+
+    def __init__(self, params, count):
+        self.count = count
+        self.dtypes = [None if p is None else p.dtype for p in params]
+
+    @classmethod
+    def pack(cls, params, count):
+        """The forward's ``(slots, table, held)``: ``param_table(params, count)`` and the record; ``held`` is appended to
+        ``save_for_backward``."""
+        table, held = param_table(params, count)
+        return cls(params, count), table, held
+
+    def _spread(self, held):
+        it = iter(held)
+        return [None if d is None else next(it) for d in self.dtypes]
+
+    def unpack(self, held):
+        """The backward's ``(params, table)`` from the held tensors as ``ctx.saved_tensors`` returns them: the list with its
+        ``None`` slots again, and a table made anew of exactly these tensors -- saved-tensor hooks may have handed back other
+        storage than the forward's table pointed into, and what ``param_table`` had to copy of it stays alive in ``params``."""
+        table, held = param_table(self._spread(held), self.count)
+        return self._spread(held), table
+
+    def grad_buffers(self, params, wanted):
+        """``(grads, table)``: a buffer like the held tensor for every present slot whose ``wanted`` entry is true, ``None``
+        (the library: a NULL slot) for the others, and their ``out_table``."""
+        grads = [torch.empty_like(p) if p is not None and w else None for p, w in zip(params, wanted)]
+        return grads, out_table(grads, self.count)
+
+    def returned(self, grads, needed):
+        """The gradients as ``backward`` returns them, one per slot: each buffer in its slot's own dtype where ``needed`` (the
+        slots' part of ``ctx.needs_input_grad``, in the slots' order) says so, ``None`` otherwise."""
+        return tuple(g.to(d) if g is not None and n else None for g, d, n in zip(grads, self.dtypes, needed))
 
 
 def train_sizes(symbol, *ints):

@@ -69,36 +69,31 @@ class AnchorEmbedFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, *params):
         a, lead, E, opa, S = _shape(anchor, params)
-        table, held = _lib.param_table(params, _lib.GF_ANCHOR_EMBED_PARAMS)
+        slots, table, held = _lib.ParamSlots.pack(params, _lib.GF_ANCHOR_EMBED_PARAMS)
         n, Da = a.shape
         saved_bytes, _ = train_sizes(n, opa, S)
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=a.device)
         out = torch.empty(n, E, dtype=f32, device=a.device)
         _lib.call("gf_anchor_embed_forward_train", a.device, n, Da, E, opa, S, a, table, out, saved, saved_bytes)
         ctx.save_for_backward(a, saved, *held)
-        ctx.shape = (lead, E, opa, S, anchor.dtype, [None if p is None else p.dtype for p in params])
+        ctx.shape = (lead, E, opa, S, anchor.dtype, slots)
         return out.view(*lead, E)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         a, saved, *held = ctx.saved_tensors
-        lead, E, opa, S, anchor_dtype, dtypes = ctx.shape
+        lead, E, opa, S, anchor_dtype, slots = ctx.shape
         n, Da = a.shape
-        params, grads, it = [], [], iter(held)
-        for d in dtypes:
-            params.append(None if d is None else next(it))
-            grads.append(None if d is None else torch.empty_like(params[-1]))
-        table, _ = _lib.param_table(params, _lib.GF_ANCHOR_EMBED_PARAMS)
-        gtable = _lib.out_table(grads, _lib.GF_ANCHOR_EMBED_PARAMS)
+        params, table = slots.unpack(held)
+        grads, gtable = slots.grad_buffers(params, [True] * len(params))     # every present parameter
         _, work_bytes = train_sizes(n, opa, S)
         work = torch.empty(work_bytes, dtype=torch.uint8, device=a.device)
         grad_anchor = torch.empty(n, Da, dtype=f32, device=a.device)
         go = _lib.as_arg(grad_out).reshape(n, E)
         _lib.call("gf_anchor_embed_backward", a.device, n, Da, E, opa, S, a, table, saved, go, grad_anchor, gtable, work, work_bytes)
         need = ctx.needs_input_grad
-        return (grad_anchor.view(*lead, Da).to(anchor_dtype) if need[0] else None,
-                *[g.to(d) if g is not None and need[1 + i] else None for i, (g, d) in enumerate(zip(grads, dtypes))])
+        return (grad_anchor.view(*lead, Da).to(anchor_dtype) if need[0] else None, *slots.returned(grads, need[1:]))
 
 
 def anchor_embed_autograd(anchor, module_or_params):
@@ -117,11 +112,8 @@ def anchor_embed(anchor, module_or_params):
     (``xyz_fc.0.weight`` ... ``output_fc.5.bias``); which branches exist says ``include_opa`` and the semantic width.  The
     parameters are read in place at every call.  Forward only: inputs that need autograd are refused."""
     params = _param_list(module_or_params)
-    if _lib.needs_grad([anchor, *params]):
-        raise RuntimeError(
-            "anchor_embed is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters "
-            "that do not require grad (the SparseGaussian3DEncoder module routes training to its torch layers), or call "
-            "anchor_embed_autograd, which has one")
+    _lib.refuse_autograd("anchor_embed", [anchor, *params], "(the SparseGaussian3DEncoder module routes training to its torch "
+                         "layers), or call anchor_embed_autograd, which has one")
     return _launch(anchor, params)
 
 

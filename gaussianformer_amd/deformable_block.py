@@ -23,26 +23,21 @@ E_NATIVE, MAX_LEARNED = _lib.GF_DEFORM_EMBED_DIMS, _lib.GF_DEFORM_MAX_LEARNED
 MODES = {"none": _lib.GF_DEFORM_NONE, "add": _lib.GF_DEFORM_ADD, "cat": _lib.GF_DEFORM_CAT}
 
 
-def _pair(layer, what, affine=nn.Linear):
-    """``(weight, bias)`` of a module or of a pair; ``(None, None)`` for ``None``."""
+def _pair(layer, what):
+    """``(weight, bias)`` of an ``nn.Linear`` or of a pair; ``(None, None)`` for ``None``."""
     if layer is None:
         return None, None
     if isinstance(layer, nn.Module):
-        if not isinstance(layer, affine) or layer.weight is None or layer.bias is None:
-            raise ValueError(f"{what} is a {type(layer).__name__} without weight and bias, not an {affine.__name__} with both")
-        if affine is nn.LayerNorm and layer.eps != 1e-5:
-            raise ValueError(f"{what}: the post norm must be a LayerNorm with eps = 1e-5")
+        if not isinstance(layer, nn.Linear) or layer.weight is None or layer.bias is None:
+            raise ValueError(f"{what} is a {type(layer).__name__} without weight and bias, not an Linear with both")
         return layer.weight, layer.bias
     weight, bias = layer
     return weight, bias
 
 
 def _refuse_autograd(name, tensors):
-    if _lib.needs_grad(tensors):
-        raise RuntimeError(
-            f"{name} is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters that "
-            "do not require grad (the DeformableFeatureAggregation module routes training to its torch layers around "
-            "deformable_fused)")
+    _lib.refuse_autograd(name, tensors, "(the DeformableFeatureAggregation module routes training to its torch layers around "
+                         "deformable_fused)")
 
 
 def _logits_args(weights_fc, learnable_fc):
@@ -113,12 +108,10 @@ class DeformLogitsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, instance_feature, anchor_embed, ww, bw, wl, bl):
         f, e, lead, E, K3, Nw = _logits_shapes("deformable_logits_autograd", instance_feature, anchor_embed, ww, bw, wl, bl)
-        params = [wl, bl, ww, bw]
-        table, held = _lib.param_table(params, _lib.GF_DEFORM_LOGITS_PARAMS)
+        slots, table, held = _lib.ParamSlots.pack([wl, bl, ww, bw], _lib.GF_DEFORM_LOGITS_PARAMS)
         raw, learned = _logits_launch(f, e, E, K3, Nw, table)
         ctx.save_for_backward(f, e, *held)
-        ctx.shape = (lead, E, K3, Nw, instance_feature.dtype, None if anchor_embed is None else anchor_embed.dtype,
-                     [None if p is None else p.dtype for p in params])
+        ctx.shape = (lead, E, K3, Nw, instance_feature.dtype, None if anchor_embed is None else anchor_embed.dtype, slots)
         ctx.set_materialize_grads(False)     # an output nobody used: a NULL cotangent, not a tensor of zeros
         return _logits_views(raw, learned, lead)
 
@@ -126,14 +119,11 @@ class DeformLogitsFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_raw, grad_learned):
         f, e, *held = ctx.saved_tensors
-        lead, E, K3, Nw, f_dtype, e_dtype, dtypes = ctx.shape
+        lead, E, K3, Nw, f_dtype, e_dtype, slots = ctx.shape
         n, need = f.shape[0], ctx.needs_input_grad
-        slot = (4, 5, 2, 3)      # the table's order (wl, bl, ww, bw) in apply()'s arguments
-        params, grads, it = [], [], iter(held)
-        for i, d in enumerate(dtypes):
-            params.append(None if d is None else next(it))
-            grads.append(torch.empty_like(params[-1]) if d is not None and need[slot[i]] else None)
-        table, _ = _lib.param_table(params, _lib.GF_DEFORM_LOGITS_PARAMS)
+        wanted = need[4:6] + need[2:4]      # the table's order (wl, bl, ww, bw) from apply()'s (..., ww, bw, wl, bl)
+        params, table = slots.unpack(held)
+        grads, gtable = slots.grad_buffers(params, wanted)     # only those that require one: the others a NULL slot
         _, work_bytes = logits_train_sizes(n, K3, Nw, E)
         work = torch.empty(work_bytes, dtype=torch.uint8, device=f.device) if any(g is not None for g in grads) else None
         new = lambda: torch.empty(n, E, dtype=f32, device=f.device)
@@ -141,9 +131,9 @@ class DeformLogitsFunction(torch.autograd.Function):
         grad_e = new() if e is not None and need[1] else None
         gr = None if grad_raw is None else _lib.aligned(grad_raw).reshape(n, Nw)
         gl = None if grad_learned is None or K3 == 0 else _lib.as_arg(grad_learned).reshape(n, K3)
-        _lib.call("gf_deform_logits_backward", f.device, n, E, K3, Nw, f, e, table, gl, gr, grad_f, grad_e,
-                  _lib.out_table(grads, _lib.GF_DEFORM_LOGITS_PARAMS), work, work_bytes if work is not None else 0)
-        wl_g, bl_g, ww_g, bw_g = (None if g is None else g.to(d) for g, d in zip(grads, dtypes))
+        _lib.call("gf_deform_logits_backward", f.device, n, E, K3, Nw, f, e, table, gl, gr, grad_f, grad_e, gtable,
+                  work, work_bytes if work is not None else 0)
+        wl_g, bl_g, ww_g, bw_g = slots.returned(grads, wanted)
         return (None if grad_f is None else grad_f.view(*lead, E).to(f_dtype),
                 None if grad_e is None else grad_e.view(*lead, E).to(e_dtype), ww_g, bw_g, wl_g, bl_g)
 
@@ -164,7 +154,7 @@ def _output_args(name, features, output_proj, instance_feature, residual_mode, r
     if residual_mode not in MODES:
         raise ValueError(f"{name}: residual_mode {residual_mode!r} is not one of {sorted(MODES)}")
     wo, bo = _pair(output_proj, "output_proj")
-    g, b = _pair(norm, "norm", nn.LayerNorm)
+    g, b = _lib.norm_pair(norm, name)
     inst = instance_feature if residual_mode != "none" else None
     if residual_mode != "none" and inst is None:
         raise ValueError(f"{name}: residual_mode {residual_mode!r} needs instance_feature")
@@ -220,8 +210,7 @@ class DeformOutputFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, residual_mode, features, instance_feature, residual, wo, bo, g, b):
         x, fi, res, lead, E = _output_shapes("deformable_output_autograd", features, instance_feature, residual, wo, bo, g, b)
-        params = [wo, bo, g, b]
-        table, held = _lib.param_table(params, _lib.GF_DEFORM_OUTPUT_PARAMS)
+        slots, table, held = _lib.ParamSlots.pack([wo, bo, g, b], _lib.GF_DEFORM_OUTPUT_PARAMS)
         n, mode = x.shape[0], MODES[residual_mode]
         saved_bytes, _ = output_train_sizes(n, residual_mode, g is not None, E)
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device) if saved_bytes else None
@@ -230,20 +219,17 @@ class DeformOutputFunction(torch.autograd.Function):
         _lib.call("gf_deform_output_forward_train", x.device, n, E, mode, x, fi, table, res, out, saved, saved_bytes)
         ctx.save_for_backward(x, saved, *held)
         ctx.shape = (lead, E, residual_mode, features.dtype, None if instance_feature is None else instance_feature.dtype,
-                     None if residual is None else residual.dtype, [None if p is None else p.dtype for p in params])
+                     None if residual is None else residual.dtype, slots)
         return out.view(*lead, width)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         x, saved, *held = ctx.saved_tensors
-        lead, E, residual_mode, x_dtype, inst_dtype, res_dtype, dtypes = ctx.shape
+        lead, E, residual_mode, x_dtype, inst_dtype, res_dtype, slots = ctx.shape
         n, mode, need = x.shape[0], MODES[residual_mode], ctx.needs_input_grad
-        params, grads, it = [], [], iter(held)
-        for i, d in enumerate(dtypes):
-            params.append(None if d is None else next(it))
-            grads.append(torch.empty_like(params[-1]) if d is not None and need[4 + i] else None)
-        table, _ = _lib.param_table(params, _lib.GF_DEFORM_OUTPUT_PARAMS)
+        params, table = slots.unpack(held)
+        grads, gtable = slots.grad_buffers(params, need[4:])     # only those that require one: the others a NULL slot
         _, work_bytes = output_train_sizes(n, residual_mode, params[2] is not None, E)
         work = torch.empty(work_bytes, dtype=torch.uint8, device=x.device)
         new = lambda: torch.empty(n, E, dtype=f32, device=x.device)
@@ -252,12 +238,12 @@ class DeformOutputFunction(torch.autograd.Function):
         grad_res = new() if res_dtype is not None and need[3] else None
         width = 2 * E if residual_mode == "cat" else E
         go = _lib.aligned(grad_out).reshape(n, width)
-        _lib.call("gf_deform_output_backward", x.device, n, E, mode, x, table, saved, go, grad_x, grad_inst, grad_res,
-                  _lib.out_table(grads, _lib.GF_DEFORM_OUTPUT_PARAMS), work, work_bytes)
+        _lib.call("gf_deform_output_backward", x.device, n, E, mode, x, table, saved, go, grad_x, grad_inst, grad_res, gtable,
+                  work, work_bytes)
         return (None, grad_x.view(*lead, E).to(x_dtype) if need[1] else None,
                 None if grad_inst is None else grad_inst.view(*lead, E).to(inst_dtype),
                 None if grad_res is None else grad_res.view(*lead, E).to(res_dtype),
-                *[None if gr is None else gr.to(d) for gr, d in zip(grads, dtypes)])
+                *slots.returned(grads, need[4:]))
 
 
 def deformable_output_autograd(features, output_proj, instance_feature=None, residual_mode="add", residual=None, norm=None):
@@ -353,13 +339,10 @@ class DeformableFeatureAggregation(nn.Module):
             return None
         if self.residual_mode == "cat" and (residual is not None or norm is not None):
             return None
-        if isinstance(norm, nn.LayerNorm) and (norm.eps != 1e-5 or norm.weight is None or norm.bias is None):
+        if isinstance(norm, nn.LayerNorm) and not _lib.norm_native(norm):
             return None
-        tensors = [instance_feature, anchor, anchor_embed, table, residual, *self.parameters()]
-        tensors += list(norm.parameters()) if isinstance(norm, nn.Module) else list(norm or ())
-        if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
-            return None
-        return tensors
+        tensors = [instance_feature, anchor, anchor_embed, table, residual, *self.parameters(), *_lib.norm_tensors(norm)]
+        return tensors if _lib.native_tensors(tensors) else None
 
     def _native(self, instance_feature, anchor, anchor_embed, table, residual, norm):
         if not self.native_dense or 3 * self.kps_generator.num_learnable_pts > MAX_LEARNED:
@@ -379,9 +362,7 @@ class DeformableFeatureAggregation(nn.Module):
         if not self.native_front_training or self.embed_dims != E_NATIVE or 3 * self.kps_generator.num_learnable_pts > MAX_LEARNED:
             return False
         tensors = [instance_feature, anchor, anchor_embed, table, *self.parameters()]
-        if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
-            return False
-        return _lib.needs_grad(tensors)
+        return _lib.native_tensors(tensors) and _lib.needs_grad(tensors)
 
     def forward(self, instance_feature, anchor, anchor_embed, feature_maps, metas, **kwargs):
         residual, norm = kwargs.get("residual"), kwargs.get("norm")
@@ -447,5 +428,5 @@ class DeformableFeatureAggregation(nn.Module):
         if residual is not None:
             output = output + residual
         if norm is not None:
-            output = norm(output) if isinstance(norm, nn.Module) else F.layer_norm(output, (output.shape[-1],), norm[0], norm[1], 1e-5)
+            output = _lib.apply_norm(output, norm)
         return output

@@ -18,9 +18,7 @@ from .deformable_aggregation import DeformableAggregationFunction as DAF
 from .deformable_block import DeformableFeatureAggregation
 from .ffn import AsymmetricFFN, ffn_block, ffn_block_autograd
 from .refine import SparseGaussian3DRefinementModule, SparseGaussian3DRefinementModuleV2
-from .sparse_conv import SparseConv3D, SubMConv3d, _norm_native
-
-f32 = torch.float32
+from .sparse_conv import SparseConv3D, SubMConv3d
 
 # the drop-ins a config dict's ``type`` may name
 MODULES = {cls.__name__: cls for cls in (SparseGaussian3DEncoder, AsymmetricFFN, DeformableFeatureAggregation,
@@ -165,23 +163,27 @@ class GaussianOccEncoder(nn.Module):
                 m.fused_mlp = bool(fused_mlp)
         return self
 
+    @staticmethod
+    def _fold_inputs(anchor, instance_feature, feature_maps):
+        """The inputs both folds look at -- the two tensors and the feature maps (a formatted triple's table) -- or ``None``
+        unless every one of them is an fp32 GPU tensor."""
+        maps = [] if feature_maps is None else [feature_maps[0]] if _formatted(feature_maps) else list(feature_maps)
+        tensors = [anchor, instance_feature, *maps]
+        if not all(isinstance(t, torch.Tensor) for t in tensors) or not _lib.native_tensors(tensors):
+            return None
+        return tensors
+
     def _folds(self, anchor, instance_feature, feature_maps):
         if not self.fold or self.training:
             return False
-        maps = [] if feature_maps is None else [feature_maps[0]] if _formatted(feature_maps) else list(feature_maps)
-        tensors = [anchor, instance_feature, *maps]
-        if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == f32 for t in tensors):
-            return False
-        return not _lib.needs_grad([*tensors, *self.parameters()])
+        tensors = self._fold_inputs(anchor, instance_feature, feature_maps)
+        return tensors is not None and not _lib.needs_grad([*tensors, *self.parameters()])
 
     def _folds_training(self, anchor, instance_feature, feature_maps):
         if not self.fold_training:
             return False
-        maps = [] if feature_maps is None else [feature_maps[0]] if _formatted(feature_maps) else list(feature_maps)
-        tensors = [anchor, instance_feature, *maps]
-        if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == f32 for t in tensors):
-            return False
-        return self.training or _lib.needs_grad([*tensors, *self.parameters()])
+        tensors = self._fold_inputs(anchor, instance_feature, feature_maps)
+        return tensors is not None and (self.training or _lib.needs_grad([*tensors, *self.parameters()]))
 
     def forward(self, representation, rep_features, ms_img_feats=None, metas=None, **kwargs):
         feature_maps = ms_img_feats
@@ -253,7 +255,7 @@ class GaussianOccEncoder(nn.Module):
             return isinstance(layer, DeformableFeatureAggregation) and feature_maps is not None
         if op == "spconv":
             return isinstance(layer, SparseConv3D)
-        if not _norm_native(norm) or not isinstance(layer, AsymmetricFFN) or not layer._native(instance_feature, None):
+        if not _lib.norm_native(norm) or not isinstance(layer, AsymmetricFFN) or not layer._native(instance_feature, None):
             return False
         if layer.add_identity and isinstance(layer.identity_fc, nn.Identity):
             return False

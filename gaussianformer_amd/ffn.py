@@ -39,16 +39,7 @@ def _param_list(ffn, norm):
         params = [get(k) for k in _KEYS]
     else:
         params = [ffn.get(k) for k in _KEYS]
-    if norm is None:
-        params += [None, None]
-    elif isinstance(norm, nn.LayerNorm):
-        if norm.eps != 1e-5 or norm.weight is None or norm.bias is None:
-            raise ValueError("ffn_block: the post norm must be an affine LayerNorm with eps = 1e-5")
-        params += [norm.weight, norm.bias]
-    else:
-        weight, bias = norm
-        params += [weight, bias]
-    return params
+    return [*params, *_lib.norm_pair(norm, "ffn_block")]
 
 
 def _shape(x, params, residual):
@@ -93,10 +84,7 @@ def ffn_block(x, ffn, norm=None, residual=None):
     ``identity_fc.*``); ``norm``: an ``nn.LayerNorm``, a ``(weight, bias)`` pair or ``None``.  Dropout is not applied (eval
     semantics); the parameters are read in place at every call.  Forward only: inputs that need autograd are refused."""
     params = _param_list(ffn, norm)
-    if _lib.needs_grad([x, residual, *params]):
-        raise RuntimeError(
-            "ffn_block is a forward without a native backward: call it under torch.no_grad() or with inputs and parameters "
-            "that do not require grad (the AsymmetricFFN module routes training to its torch layers)")
+    _lib.refuse_autograd("ffn_block", [x, residual, *params], "(the AsymmetricFFN module routes training to its torch layers)")
     return _launch(x, params, residual)
 
 
@@ -137,7 +125,7 @@ class FFNBlockFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, keep_hidden, scale_hidden, keep_out, scale_out, *params):
         xa, res, lead, Cin, F, E = _shape(x, params, residual)
-        table, held = _lib.param_table(params, _lib.GF_FFN_PARAMS)
+        slots, table, held = _lib.ParamSlots.pack(params, _lib.GF_FFN_PARAMS)
         n = xa.shape[0]
         saved_bytes, _ = train_sizes(n, Cin)
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=xa.device)
@@ -145,21 +133,17 @@ class FFNBlockFunction(torch.autograd.Function):
         _lib.call("gf_ffn_forward_train", xa.device, n, Cin, F, E, xa, table, res, keep_hidden, scale_hidden, keep_out, scale_out,
                   out, saved, saved_bytes)
         ctx.save_for_backward(xa, saved, keep_hidden, keep_out, *held)
-        ctx.shape = (lead, Cin, F, E, scale_hidden, scale_out, x.dtype, None if residual is None else residual.dtype,
-                     [None if p is None else p.dtype for p in params])
+        ctx.shape = (lead, Cin, F, E, scale_hidden, scale_out, x.dtype, None if residual is None else residual.dtype, slots)
         return out.view(*lead, E)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         xa, saved, keep_hidden, keep_out, *held = ctx.saved_tensors
-        lead, Cin, F, E, scale_hidden, scale_out, x_dtype, res_dtype, dtypes = ctx.shape
+        lead, Cin, F, E, scale_hidden, scale_out, x_dtype, res_dtype, slots = ctx.shape
         n = xa.shape[0]
-        params, grads, it = [], [], iter(held)
-        for d in dtypes:
-            params.append(None if d is None else next(it))
-            grads.append(None if d is None else torch.empty_like(params[-1]))
-        table, _ = _lib.param_table(params, _lib.GF_FFN_PARAMS)
+        params, table = slots.unpack(held)
+        grads, gtable = slots.grad_buffers(params, [True] * len(params))     # every present parameter
         _, work_bytes = train_sizes(n, Cin)
         work = torch.empty(work_bytes, dtype=torch.uint8, device=xa.device)
         grad_x = torch.empty(n, Cin, dtype=f32, device=xa.device)
@@ -167,10 +151,10 @@ class FFNBlockFunction(torch.autograd.Function):
         grad_res = torch.empty(n, E, dtype=f32, device=xa.device) if res_dtype is not None and need[1] else None
         go = _lib.aligned(grad_out).reshape(n, E)
         _lib.call("gf_ffn_backward", xa.device, n, Cin, F, E, xa, table, keep_hidden, scale_hidden, keep_out, scale_out, saved, go,
-                  grad_x, grad_res, _lib.out_table(grads, _lib.GF_FFN_PARAMS), work, work_bytes)
+                  grad_x, grad_res, gtable, work, work_bytes)
         return (grad_x.view(*lead, Cin).to(x_dtype) if need[0] else None,
                 None if grad_res is None else grad_res.view(*lead, E).to(res_dtype), None, None, None, None,
-                *[g.to(d) if g is not None and need[6 + i] else None for i, (g, d) in enumerate(zip(grads, dtypes))])
+                *slots.returned(grads, need[6:]))
 
 
 def ffn_block_autograd(x, ffn, norm=None, residual=None, p_hidden=0.0, p_out=0.0, keep_hidden=None, keep_out=None):
@@ -278,9 +262,7 @@ class AsymmetricFFN(nn.Module):
             return False
         if not (first.weight.is_cuda and first.weight.dtype == f32):
             return False
-        if self.pre_norm is not None and (self.pre_norm.eps != 1e-5 or self.pre_norm.weight is None or self.pre_norm.bias is None):
-            return False
-        return True
+        return _lib.norm_native(self.pre_norm)     # (the kernel's pre norm is the post norm's LayerNorm: affine, eps 1e-5)
 
     def forward(self, x, identity=None):
         if self._native(x, identity):

@@ -91,10 +91,12 @@ def refine(output, anchor, cfg):
     """Functional form on any leading batch shape: ``(anchor_out [..., D], GaussianPrediction)``."""
     lead = output.shape[:-1]
     outs = RefineFunction.apply(output.reshape(-1, output.shape[-1]), anchor.reshape(-1, anchor.shape[-1]), cfg)
-    outs = [t.view(*lead, t.shape[-1]) for t in outs]
-    if cfg.version == 1:
-        return outs[0], GaussianPrediction(*outs[1:6])
-    return outs[0], GaussianPrediction(*outs[1:8])
+    return _prediction([t.view(*lead, t.shape[-1]) for t in outs], cfg)
+
+
+def _prediction(outs, cfg):
+    """``(anchor_out, GaussianPrediction)`` of a launch's eight outputs; version 1 has no ``original_means`` / ``delta_means``."""
+    return outs[0], GaussianPrediction(*outs[1:6 if cfg.version == 1 else 8])
 
 
 MLP_KEYS = ("layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias", "layers.4.weight", "layers.4.bias",
@@ -122,6 +124,21 @@ def refine_fused(instance_feature, anchor, anchor_embed, module_or_state_dict, c
     if _lib.needs_grad((instance_feature, anchor, anchor_embed, *params)):
         raise RuntimeError("refine_fused computes no gradients: use the module with fused_mlp = False (the torch MLP + refine) "
                            "for training, or call it under torch.no_grad()")
+    f, e, a, params, lead, call, outs, consts = _fused_args(instance_feature, anchor, anchor_embed, cfg, params)
+    D = call[2]
+    mlp_out = torch.empty(f.shape[0], D, dtype=f32, device=f.device) if return_mlp_output else None
+    _lib.call("gf_refine_mlp_forward", f.device, *call, ctypes.cast(consts, ctypes.c_void_p), f, e, a, _mlp_table(params), mlp_out, *outs)
+    anchor_out, pred = _prediction([t.view(*lead, t.shape[-1]) for t in outs], cfg)
+    if return_mlp_output:
+        return anchor_out, pred, mlp_out.view(*lead, D)
+    return anchor_out, pred
+
+
+def _fused_args(instance_feature, anchor, anchor_embed, cfg, params):
+    """What the one-launch forward and its saving form share: ``(f [n, E], e [n, E], a [n, Da], params, leading shape, call,
+    outs, consts)`` -- the inputs and the 15 parameters as the library reads them, their shapes checked; ``call = (n, E, D, Da,
+    version, flags, R, S)``, the launch's integers; the eight outputs ``[n, ...]`` (the last two empty in version 1); the
+    constants as the array the launch points at."""
     _lib.require_gpu(instance_feature, anchor, anchor_embed, *params)
     lead, E = instance_feature.shape[:-1], instance_feature.shape[-1]
     f = _lib.as_arg(instance_feature).reshape(-1, E)
@@ -142,15 +159,7 @@ def refine_fused(instance_feature, anchor, anchor_embed, module_or_state_dict, c
 
     three = 3 if cfg.version == 2 else 0
     outs = (new(D), new(3), new(3), new(4), new(opa), new(cfg.S), new(three), new(three))
-    mlp_out = new(D) if return_mlp_output else None
-    consts = (ctypes.c_double * 11)(*cfg.consts)
-    _lib.call("gf_refine_mlp_forward", f.device, n, E, D, Da, cfg.version, cfg.flags, cfg.R, cfg.S, ctypes.cast(consts, ctypes.c_void_p),
-              f, e, a, _mlp_table(params), mlp_out, *outs)
-    outs = [t.view(*lead, t.shape[-1]) for t in outs]
-    pred = GaussianPrediction(*outs[1:6]) if cfg.version == 1 else GaussianPrediction(*outs[1:8])
-    if return_mlp_output:
-        return outs[0], pred, mlp_out.view(*lead, D)
-    return outs[0], pred
+    return f, e, a, params, lead, (n, E, D, Da, cfg.version, cfg.flags, cfg.R, cfg.S), outs, (ctypes.c_double * 11)(*cfg.consts)
 
 
 def train_sizes(n, D, Da):
@@ -171,36 +180,18 @@ class RefineFusedFunction(Function):
 
     @staticmethod
     def forward(ctx, instance_feature, anchor, anchor_embed, cfg, *params):
-        _lib.require_gpu(instance_feature, anchor, anchor_embed, *params)
         ctx.set_materialize_grads(False)   # an unused output's gradient reaches the library as NULL, not as a tensor of zeros
-        lead, E = instance_feature.shape[:-1], instance_feature.shape[-1]
-        f = _lib.as_arg(instance_feature).reshape(-1, E)
-        e = _lib.as_arg(anchor_embed).expand(*lead, E).reshape(-1, E).contiguous()   # (a broadcast one: its rows written out)
-        a = _lib.as_arg(anchor).reshape(-1, anchor.shape[-1])
-        held = [_lib.as_arg(t) for t in params]
-        n, Da, D = f.shape[0], a.shape[1], held[12].shape[0]
-        if a.shape[0] != n:
-            raise ValueError(f"instance_feature has {n} rows, anchor {a.shape[0]}")
-        shapes = [(E, E), (E,), (E, E), (E,), (E,), (E,)] * 2 + [(D, E), (D,), (D,)]
-        for k, t, want in zip(MLP_KEYS, held, shapes):
-            if tuple(t.shape) != want:
-                raise ValueError(f"{k} has shape {tuple(t.shape)}, expected {want}")
-        opa = 1 if cfg.flags & _lib.GF_REFINE_OPACITY else 0
-
-        def new(w):
-            return torch.empty(n, w, dtype=f32, device=f.device)
-
-        three = 3 if cfg.version == 2 else 0
-        outs = (new(D), new(3), new(3), new(4), new(opa), new(cfg.S), new(three), new(three))
+        f, e, a, held, lead, call, outs, consts = _fused_args(instance_feature, anchor, anchor_embed, cfg, params)
+        n, E, D, Da = call[:4]
         saved_bytes, _ = train_sizes(n, D, Da)
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=f.device)
-        consts = (ctypes.c_double * 11)(*cfg.consts)
-        ctx.call = (n, E, D, Da, cfg.version, cfg.flags, cfg.R, cfg.S, consts)
-        _lib.call("gf_refine_mlp_forward_train", f.device, *ctx.call[:8], ctypes.cast(consts, ctypes.c_void_p),
+        ctx.call = (*call, consts)
+        _lib.call("gf_refine_mlp_forward_train", f.device, *call, ctypes.cast(consts, ctypes.c_void_p),
                   f, e, a, _mlp_table(held), None, *outs, saved, saved_bytes)
         ctx.save_for_backward(f, e, a, saved, *held)
+        # (no table from the record: a misaligned parameter is the library's to refuse, so the tables stay _mlp_table's)
         ctx.shape = (lead, tuple(anchor_embed.shape), instance_feature.dtype, anchor.dtype, anchor_embed.dtype,
-                     [t.dtype for t in params])
+                     _lib.ParamSlots(params, _lib.GF_REFINE_MLP_PARAMS))
         return tuple(t.view(*lead, t.shape[-1]) for t in outs)
 
     @staticmethod
@@ -208,7 +199,7 @@ class RefineFusedFunction(Function):
     def backward(ctx, *grads):
         f, e, a, saved, *held = ctx.saved_tensors
         n, E, D, Da, version, flags, R, S, consts = ctx.call
-        lead, embed_shape, f_dtype, a_dtype, e_dtype, dtypes = ctx.shape
+        lead, embed_shape, f_dtype, a_dtype, e_dtype, slots = ctx.shape
         g = [None if t is None or t.numel() == 0 else _lib.as_arg(t).reshape(n, t.shape[-1]) for t in grads]
         grad_x = torch.empty(n, E, dtype=f32, device=f.device)
         grad_anchor = torch.empty(n, Da, dtype=f32, device=f.device)
@@ -223,7 +214,7 @@ class RefineFusedFunction(Function):
         return (gx.to(f_dtype) if need[0] else None,
                 grad_anchor.view(*lead, Da).to(a_dtype) if need[1] else None,
                 gx.sum_to_size(embed_shape).to(e_dtype) if need[2] else None, None,
-                *[t.to(d) if need[4 + i] else None for i, (t, d) in enumerate(zip(grad_params, dtypes))])
+                *slots.returned(grad_params, need[4:]))
 
 
 def refine_fused_autograd(instance_feature, anchor, anchor_embed, module_or_state_dict, cfg):
@@ -238,9 +229,7 @@ def refine_fused_autograd(instance_feature, anchor, anchor_embed, module_or_stat
     _lib.require_gpu(instance_feature, anchor, anchor_embed, *params)
     if not _lib.needs_grad((instance_feature, anchor, anchor_embed, *params)):
         return refine_fused(instance_feature, anchor, anchor_embed, state, cfg)
-    outs = RefineFusedFunction.apply(instance_feature, anchor, anchor_embed, cfg, *params)
-    pred = GaussianPrediction(*outs[1:6]) if cfg.version == 1 else GaussianPrediction(*outs[1:8])
-    return outs[0], pred
+    return _prediction(RefineFusedFunction.apply(instance_feature, anchor, anchor_embed, cfg, *params), cfg)
 
 
 class Scale(nn.Module):
@@ -290,15 +279,17 @@ class _Refinement(nn.Module):
                                   semantics_activation, xyz_activation)
         self.layers = refinement_mlp(embed_dims, self.output_dim)
 
-    def _takes_fused(self, instance_feature, anchor, anchor_embed):
+    def _takes_launch(self, switch, with_grad, instance_feature, anchor, anchor_embed):
+        """Whether a call goes to the one-launch route behind ``switch``: ``embed_dims`` 128, fp32 GPU tensors, and a call that
+        autograd would record exactly when ``with_grad``."""
         tensors = (instance_feature, anchor, anchor_embed, *self.layers.parameters())
-        return (self.fused_mlp and self.embed_dims == 128 and not _lib.needs_grad(tensors)
-                and all(t.is_cuda and t.dtype == f32 for t in tensors))
+        return switch and self.embed_dims == 128 and _lib.needs_grad(tensors) == with_grad and _lib.native_tensors(tensors)
+
+    def _takes_fused(self, instance_feature, anchor, anchor_embed):
+        return self._takes_launch(self.fused_mlp, False, instance_feature, anchor, anchor_embed)
 
     def _takes_native_training(self, instance_feature, anchor, anchor_embed):
-        tensors = (instance_feature, anchor, anchor_embed, *self.layers.parameters())
-        return (self.native_training and self.embed_dims == 128 and _lib.needs_grad(tensors)
-                and all(t.is_cuda and t.dtype == f32 for t in tensors))
+        return self._takes_launch(self.native_training, True, instance_feature, anchor, anchor_embed)
 
     def forward(self, instance_feature, anchor, anchor_embed):
         if self._takes_fused(instance_feature, anchor, anchor_embed):

@@ -23,36 +23,6 @@ f32, i32 = torch.float32, torch.int32
 E_NATIVE = 128   # the width at which the block's dense tail has a native form (gf_deform_output_forward)
 
 
-def _norm_pair(norm, what):
-    """``(weight, bias)`` of a post norm: an affine ``nn.LayerNorm`` with eps 1e-5, or a pair; ``(None, None)`` for ``None``."""
-    if norm is None:
-        return None, None
-    if isinstance(norm, nn.Module):
-        if not isinstance(norm, nn.LayerNorm) or norm.eps != 1e-5 or norm.weight is None or norm.bias is None:
-            raise ValueError(f"{what}: norm must be an affine LayerNorm with eps = 1e-5, or a (weight, bias) pair")
-        return norm.weight, norm.bias
-    try:
-        weight, bias = norm
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: norm must be an affine LayerNorm with eps = 1e-5, or a (weight, bias) pair") from None
-    if weight is None or bias is None:
-        raise ValueError(f"{what}: norm must be an affine LayerNorm with eps = 1e-5, or a (weight, bias) pair")
-    return weight, bias
-
-
-def _norm_native(norm):
-    """Whether ``_norm_pair`` accepts ``norm`` (the same checks, as a question)."""
-    if norm is None:
-        return True
-    if isinstance(norm, nn.Module):
-        return isinstance(norm, nn.LayerNorm) and norm.eps == 1e-5 and norm.weight is not None and norm.bias is not None
-    return isinstance(norm, (tuple, list)) and len(norm) == 2 and all(isinstance(t, torch.Tensor) for t in norm)
-
-
-def _apply_norm(x, norm):
-    return norm(x) if isinstance(norm, nn.Module) else nn.functional.layer_norm(x, (x.shape[-1],), norm[0], norm[1], 1e-5)
-
-
 class Rulebook:
     """Neighbour pairs of one point set (reusable across layers and by the backward pass).
 
@@ -115,6 +85,10 @@ class Rulebook:
             self._rep_mask = ((last[key] == me) | ~valid).to(f32)[:, None]
         return self._rep_mask
 
+    def sources(self, features, duplicates):
+        """``features`` as a convolution reads them: with ``duplicates="last"`` only a cell's representative row is a source."""
+        return features * self.representative_mask() if duplicates == "last" else features
+
     def check(self):
         """Reads the device status (synchronises): returns the pair count, raises if the point set was refused."""
         total, refused = self._status.tolist()
@@ -157,7 +131,7 @@ class Rulebook:
         dev = features.device
         epilogue = bias is not None or residual is not None or norm is not None or relu
         if epilogue:
-            gamma, beta = _norm_pair(norm, "Rulebook.apply")
+            gamma, beta = _lib.norm_pair(norm, "Rulebook.apply")
             _lib.require_gpu(bias, residual, gamma, beta)
             for name, t, shape in (("bias", bias, (cout,)), ("residual", residual, (self.N, cout)), ("norm weight", gamma, (cout,)),
                                    ("norm bias", beta, (cout,))):
@@ -318,12 +292,12 @@ def subm_stages(features, rulebook, stages):
     for st in stages:
         if st.get("norm") is None:
             raise ValueError("subm_stage: norm is required (an affine LayerNorm with eps = 1e-5, or a (weight, bias) pair)")
-        _norm_pair(st["norm"], "subm_stage")
+        _lib.norm_pair(st["norm"], "subm_stage")
     _lib.require_gpu(features)
     flat, relus, cin = [], [], features.shape[-1]
     for st in stages:
         weight, bias, residual = st["weight"], st.get("bias"), st.get("residual")
-        gamma, beta = _norm_pair(st["norm"], "subm_stage")
+        gamma, beta = _lib.norm_pair(st["norm"], "subm_stage")
         _lib.require_gpu(weight, bias, residual, gamma, beta)
         cout = weight.shape[2]
         if weight.shape[1] != cin or cin not in STAGE_CHANNELS or cout not in STAGE_CHANNELS:
@@ -364,9 +338,7 @@ def subm_conv3d(features, indices, weight, batch_size, spatial_shape, kernel_siz
     if rb.out_range is not None and torch.is_grad_enabled() and (features.requires_grad or weight.requires_grad):
         # (the backward relies on the neighbour relation being symmetric: a rulebook restricted to a range of output points is not)
         raise RuntimeError("a Rulebook with out_range is inference-only")
-    if duplicates == "last":
-        features = features * rb.representative_mask()
-    return _SubMConv.apply(features, weight, rb)
+    return _SubMConv.apply(rb.sources(features, duplicates), weight, rb)
 
 
 class SubMConv3d(nn.Module):
@@ -531,29 +503,21 @@ class SparseConv3D(nn.Module):
         if residual is not None:
             out = out + residual
         if norm is not None:
-            out = _apply_norm(out, norm)
+            out = _lib.apply_norm(out, norm)
         return out
 
     def _native_tail(self, instance_feature, anchor, residual, norm):
         """Whether this call's dense tail runs natively: the checks ``Rulebook.apply`` and ``deformable_output`` make, asked first."""
-        if not self.native_tail or self.embed_channels != E_NATIVE or not _norm_native(norm):
+        if not self.native_tail or self.embed_channels != E_NATIVE or not _lib.norm_native(norm):
             return False
         if not isinstance(self.output_proj, (nn.Linear, nn.Identity)):
             return False
         if isinstance(self.output_proj, nn.Linear) and self.output_proj.bias is None:
             return False
-        if not isinstance(self.layer, SubMConv3d):
-            stages = list(self.layer)
-            if len(stages) != 9:
-                return False
-            for conv, ln, act in zip(stages[0::3], stages[1::3], stages[2::3]):
-                if not (isinstance(conv, SubMConv3d) and isinstance(ln, nn.LayerNorm) and _norm_native(ln) and isinstance(act, nn.ReLU)):
-                    return False
-        tensors = [instance_feature, anchor, residual, *self.parameters()]
-        tensors += list(norm.parameters()) if isinstance(norm, nn.Module) else list(norm or ())
-        if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
+        if not isinstance(self.layer, SubMConv3d) and self._stage_modules() is None:
             return False
-        return not _lib.needs_grad(tensors)
+        tensors = [instance_feature, anchor, residual, *self.parameters(), *_lib.norm_tensors(norm)]
+        return _lib.native_tensors(tensors) and not _lib.needs_grad(tensors)
 
     def _stage_modules(self):
         """``[(conv, ln)]`` of a multi-layer block built as conv + LayerNorm + ReLU three times, else ``None``."""
@@ -563,7 +527,7 @@ class SparseConv3D(nn.Module):
         if len(stages) != 9:
             return None
         for conv, ln, act in zip(stages[0::3], stages[1::3], stages[2::3]):
-            if not (isinstance(conv, SubMConv3d) and isinstance(ln, nn.LayerNorm) and _norm_native(ln) and isinstance(act, nn.ReLU)):
+            if not (isinstance(conv, SubMConv3d) and isinstance(ln, nn.LayerNorm) and _lib.norm_native(ln) and isinstance(act, nn.ReLU)):
                 return None
         return list(zip(stages[0::3], stages[1::3]))
 
@@ -577,30 +541,24 @@ class SparseConv3D(nn.Module):
         if isinstance(self.layer, SubMConv3d):
             if self._tail_training(norm):
                 pass
-            elif not isinstance(self.output_proj, nn.Identity) or norm is None or not _norm_native(norm):
+            elif not isinstance(self.output_proj, nn.Identity) or norm is None or not _lib.norm_native(norm):
                 return False
         elif self._stage_modules() is None:
             return False
-        tensors = [instance_feature, anchor, residual, *self.parameters()]
-        tensors += list(norm.parameters()) if isinstance(norm, nn.Module) else list(norm or ())
-        if not all(t is None or (t.is_cuda and t.dtype == f32) for t in tensors):
-            return False
-        return _lib.needs_grad(tensors)
+        tensors = [instance_feature, anchor, residual, *self.parameters(), *_lib.norm_tensors(norm)]
+        return _lib.native_tensors(tensors) and _lib.needs_grad(tensors)
 
     def _tail_training(self, norm):
         """Whether ``output_proj`` with the ``residual=`` / ``norm=`` behind it runs its native training step (§3.13f):
         ``native_tail_training``, a Linear with bias at width 128 and a norm the library takes."""
         proj = self.output_proj
-        return self.native_tail_training and self.embed_channels == E_NATIVE and isinstance(proj, nn.Linear) and proj.bias is not None and _norm_native(norm)
+        return self.native_tail_training and self.embed_channels == E_NATIVE and isinstance(proj, nn.Linear) and proj.bias is not None and _lib.norm_native(norm)
 
     def _forward_native_training(self, feats, rb, residual, norm, bs, g):
         """``[b, g, C]``: every stage that has a LayerNorm as a :class:`SubMStageFunction`, and ``output_proj`` with what follows
         it as ``deformable_output_autograd`` where ``_tail_training`` says so (torch ops otherwise).  ``duplicates="sum"``: the
         three stages are one chained Function; ``"last"``: the mask multiply sits between the stages, so they are three."""
         from .deformable_block import deformable_output_autograd   # (here: deformable_block's imports reach back to this package)
-
-        def source(conv, x):
-            return x * rb.representative_mask() if conv.duplicates == "last" else x
         tail = self._tail_training(norm)
         res = None if residual is None else residual.flatten(0, 1)
         if isinstance(self.layer, SubMConv3d):
@@ -608,21 +566,21 @@ class SparseConv3D(nn.Module):
             if tail:
                 out = conv(feats, rb.indices, bs, self._spatial, rulebook=rb)
                 return deformable_output_autograd(out, self.output_proj, residual_mode="none", residual=res, norm=norm).unflatten(0, (bs, g))
-            return subm_stage(source(conv, feats), rb, conv.weight, bias=conv.bias, residual=res, norm=norm).unflatten(0, (bs, g))
+            return subm_stage(rb.sources(feats, conv.duplicates), rb, conv.weight, bias=conv.bias, residual=res, norm=norm).unflatten(0, (bs, g))
         pairs = self._stage_modules()
         if all(conv.duplicates == "sum" for conv, _ in pairs):
             out = subm_stages(feats, rb, [dict(weight=conv.weight, bias=conv.bias, norm=ln, relu=True) for conv, ln in pairs])
         else:
             out = feats
             for conv, ln in pairs:
-                out = subm_stage(source(conv, out), rb, conv.weight, bias=conv.bias, norm=ln, relu=True)
+                out = subm_stage(rb.sources(out, conv.duplicates), rb, conv.weight, bias=conv.bias, norm=ln, relu=True)
         if tail:
             return deformable_output_autograd(out, self.output_proj, residual_mode="none", residual=res, norm=norm).unflatten(0, (bs, g))
         out = self.output_proj(out.unflatten(0, (bs, g)))
         if residual is not None:
             out = out + residual
         if norm is not None:
-            out = _apply_norm(out, norm)
+            out = _lib.apply_norm(out, norm)
         return out
 
     def _forward_native_tail(self, feats, rb, residual, norm):
@@ -631,23 +589,20 @@ class SparseConv3D(nn.Module):
         from .deformable_block import deformable_output   # (here: deformable_block's imports reach back to this package)
         res = None if residual is None else residual.flatten(0, 1)
         proj = isinstance(self.output_proj, nn.Linear)
-
-        def source(conv, x):
-            return x * rb.representative_mask() if conv.duplicates == "last" else x
         if isinstance(self.layer, SubMConv3d):
             conv = self.layer
             if proj:
-                out = rb.apply(source(conv, feats), conv.weight, bias=conv.bias)
+                out = rb.apply(rb.sources(feats, conv.duplicates), conv.weight, bias=conv.bias)
                 return deformable_output(out, self.output_proj, residual_mode="none", residual=res, norm=norm)
-            return rb.apply(source(conv, feats), conv.weight, bias=conv.bias, residual=res, norm=norm)
-        out, stages = feats, list(self.layer)
-        for conv, ln in zip(stages[0::3], stages[1::3]):
-            out = rb.apply(source(conv, out), conv.weight, bias=conv.bias, norm=ln, relu=True)
+            return rb.apply(rb.sources(feats, conv.duplicates), conv.weight, bias=conv.bias, residual=res, norm=norm)
+        out = feats
+        for conv, ln in self._stage_modules():
+            out = rb.apply(rb.sources(out, conv.duplicates), conv.weight, bias=conv.bias, norm=ln, relu=True)
         if proj:
             return deformable_output(out, self.output_proj, residual_mode="none", residual=res, norm=norm)
         # (not the third stage's epilogue: its own LayerNorm and ReLU sit between the convolution and this add)
         if res is not None:
             out = out + res
         if norm is not None:
-            out = _apply_norm(out, norm)
+            out = _lib.apply_norm(out, norm)
         return out
